@@ -3,13 +3,16 @@
 
     python bench.py --gpus N --steps K --warmup W       (N = 1: in this process; N > 1: re-launches itself, one rank per GPU)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W   (the driver's N > 1 form)
+    python bench.py ... --full                 (also every extra object listed below: kernel roofline, parity, CPU baseline, ...)
+    python bench.py ... --dump-outputs DIR     (after the timed steps: what the last timed step returned, as DIR/<name>.npy)
 
 A "step" is one pass of the hot path over one batch: forward of the decoder, Fusion10_freq loss, backward, [one flat-bucket
 RCCL all-reduce when N > 1], fused Adan -- exactly train_nerv_all.py:328-348 of the reference -- on frames already resident
 in HBM.  Workload at N=1: BASELINE configs[1] = NeRV-boost 1.5M on a Bunny-shaped synthetic clip (132 x 3x720x1280), batch
 1 per GPU (the reference recipe's `-b 1`; `-b N -d` on N GPUs), weak scaling.  Prints ONE JSON line on rank 0.
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps and prints the headline (value, ms_per_step, the step's algorithmic
+`step_roofline`, config).  Extra objects on the line, measured only with --full:
   roofline      the conv family the step launches at the model's last stage (C -> C 3x3 at full resolution: TAT conv0 / conv1
                 forwards, their data gradients, the weight gradients), each instantiation timed live with HIP events on the
                 stream it is launched on; `achieved` = flop-weighted mean against the dense fp32 MFMA peak, `slowest` and the
@@ -18,6 +21,12 @@ Extra objects on the line:
   eval_psnr_db  pred_seen_psnr of a few frames after the timed steps
   cpu_baseline  the CPU oracle (oracle/cpu_ref.py: the reference's algorithm in plain fp32 torch) running the SAME train step
                 on this box's host cores for a bounded sample (rank 0, N=1 only): 3 warm-up + up to 20 timed steps, 30 s budget
+  parity, host_frames, recipe, other_configs, stock_rocm   (see main())
+
+--dump-outputs DIR writes the arrays a caller of the timed step receives after its LAST timed step (rank 0): loss.npy, psnr.npy
+(bpp.npy for c5) and param.<state_dict key>.npy for every floating-point model tensor, float32, at most 64 MB in all (a larger tensor
+is replaced by a fixed seeded sample of its elements).  The inputs are seeded, so two builds run with the same arguments can be
+compared file by file.
 """
 import argparse
 import json
@@ -476,6 +485,32 @@ def last_stage_channels(model):
     raise RuntimeError("no head layer found")
 
 
+def dump_outputs(out_dir, step, model, budget_bytes=60_000_000):
+    """--dump-outputs: what the last timed step handed its caller -- loss, per-sample PSNR (bpp for the compression step) and the
+    updated model tensors -- as float32 .npy files.  Tensors are taken smallest first; one larger than its even share of what is
+    left of the budget is written as a fixed seeded sample of its flattened elements (same indices on every run)."""
+    import numpy as np
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    arrays = {"loss": step.loss_out, "psnr": step.psnr_out}
+    if getattr(step, "bpp_out", None) is not None:
+        arrays["bpp"] = step.bpp_out
+    for k, v in model.state_dict().items():
+        if torch.is_floating_point(v):
+            arrays["param." + k] = v
+    os.makedirs(out_dir, exist_ok=True)
+    left, items = budget_bytes, sorted(arrays.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    for j, (name, t) in enumerate(items):
+        a = t.detach().float().cpu().numpy()
+        share = left // (len(items) - j)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=max(share // 4, 1), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32, copy=False))
+        left -= a.nbytes
+    return len(items)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -487,7 +522,11 @@ def main():
     ap.add_argument("--steps_only", action="store_true", help="profiling aid: time the steps and print a short line (no kernel micro-benchmark, eval, CPU baseline)")
     ap.add_argument("--brief", action="store_true", help="child mode of the C1 line's `other_configs`: time the steps, add the dominant final-stage kernel's roofline row, print one short JSON object")
     ap.add_argument("--stock_only", action="store_true", help="child mode of the stock-ops yardstick: print its JSON object and exit")
-    ap.add_argument("--stock_rocm", action="store_true", help="also time the oracle restatement on stock PyTorch-ROCm ops (slow first run)")
+    ap.add_argument("--stock_rocm", action="store_true", help="with --full: give the stock PyTorch-ROCm yardstick 240 s instead of 75 s (slow first run)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: kernel roofline, parity, host-frames rate, other configs, eval PSNR, "
+                                                        "CPU baseline and stock-ops yardstick (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (loss, PSNR, updated model tensors) to DIR/<name>.npy, float32, <= 64 MB")
     a = ap.parse_args()
 
     if a.stock_only:
@@ -517,7 +556,8 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(a.gpus), "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        import subprocess
+        raise SystemExit(subprocess.call(cmd))      # (a fresh child process: this one may already hold the HIP runtime)
     if world != a.gpus:
         raise SystemExit(f"bench.py --gpus {a.gpus} started with WORLD_SIZE={world}: launch one rank per GPU (or run plain `python bench.py --gpus N`)")
     assert torch.cuda.is_available(), "bench.py needs the MI355X (no CPU fallback for the product path)"
@@ -692,6 +732,8 @@ def main():
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         replicas_in_sync = bool(torch.equal(lo, hi))
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, step, model)      # (before anything below trains further: parity, host frames)
     if rank == 0 and a.steps_only:
         print(json.dumps({"metric": "train frames/sec", "value": round(a.steps * per_gpu_batch * world / dt, 2), "ms_per_step": round(dt / a.steps * 1e3, 4), "steps_only": True, "settle_ms": settle_ms}), flush=True)
     elif rank == 0 and a.brief:
@@ -740,20 +782,21 @@ def main():
             out["allreduce_us"] = dp_diag["allreduce_us"]
         if world > 1 and not replicas_in_sync:
             out["error"] = "replicas diverged: the ranks do not hold the same parameter bits after the timed steps (the gradient exchange did not run, or ran out of order)"
-        c_last = last_stage_channels(model)
-        out["roofline"] = step_kernel_roofline(dev, c_last, r["h"], r["w"], reps=20 if r["h"] <= 720 else 8)
+        # --full: everything past the headline -- kernel roofline, parity, host frames, recorded recipe, other configs, eval PSNR, baselines
+        if a.full:
+            out["roofline"] = step_kernel_roofline(dev, last_stage_channels(model), r["h"], r["w"], reps=20 if r["h"] <= 720 else 8)
         fl, by = STEP_WORK[a.config]
         t_step = dt / a.steps / per_gpu_batch                                   # seconds per trained frame on one GPU
         t_roof = max(fl / (PEAK_FP32_MFMA_TFLOPS * 1e12), by / (PEAK_HBM_GBS * 1e9))
         out["step_roofline"] = {"flops_per_frame": fl, "bytes_per_frame": by, "t_roof_ms": round(t_roof * 1e3, 4), "bound": "mfma" if fl / (PEAK_FP32_MFMA_TFLOPS * 1e12) >= by / (PEAK_HBM_GBS * 1e9) else "hbm",
                                 "achieved_TFLOPs": round(fl / t_step / 1e12, 2), "achieved_GBs": round(by / t_step / 1e9, 1), "frac_of_t_roof": round(t_roof / t_step, 4),
                                 "note": "algorithmic conv+dense work of one trained frame (BASELINE.md section 3) against the whole measured step, loss / optimizer / launches included"}
-        if world == 1 and not a.no_cpu_baseline and a.config != "c5":
+        if a.full and world == 1 and not a.no_cpu_baseline and a.config != "c5":
             def set_lr(sg, ig):
                 adjust_lr(opt, (sg / n_iter) / args.epochs, ig, args)
             out["parity"] = parity_leg(args, model, opt, (lambda ig: step.step_frame(ig)) if by_index else (lambda ig: step(frames[ig:ig + 1], norm[ig:ig + 1])),
                                        frames, norm, takes_image, max(a.warmup, 5) + a.steps, n_iter, set_lr, K=3 if r["h"] <= 720 else 2)
-        if world == 1 and not a.no_cpu_baseline and a.config != "c5":
+        if a.full and world == 1 and not a.no_cpu_baseline and a.config != "c5":
             # the end-to-end rate with the frame crossing PCIe every step (pinned host clip -> device copy -> step), next to
             # `value` (frames resident in HBM), never as `value`
             n_h = 40
@@ -770,7 +813,7 @@ def main():
             t_h = time.time() - t_h
             out["host_frames"] = {"value": round(n_h / t_h, 2), "unit": "frames/s", "ms_per_step": round(t_h / n_h * 1e3, 4),
                                   "what": f"{n_h} steps with the frame copied from pinned host memory each step ({frames[0].numel() * 4 / 1e6:.1f} MB over PCIe) before the same captured step"}
-        if a.config == "c1":
+        if a.full and a.config == "c1":
             # the "eval PSNR" half of BASELINE's metric needs the whole schedule (300 epochs): recorded once per round through the CLI
             # (tools/recipe_record.py -> profiles/rNN_cli_c1_e300.json), quoted here next to the live numbers, never as `value`
             import glob
@@ -783,14 +826,15 @@ def main():
                     out["recipe"]["recorded"] = "a committed record of an earlier run of the full schedule on an MI355X (not measured by this invocation)"
                 except (OSError, ValueError):
                     pass
-        if a.config == "c1" and world == 1 and not a.no_cpu_baseline and os.environ.get("BNERV_BENCH_OTHER", "1") != "0":
+        if a.full and a.config == "c1" and world == 1 and not a.no_cpu_baseline and os.environ.get("BNERV_BENCH_OTHER", "1") != "0":
             # BASELINE configs[3] / configs[2] beside the headline: the captured step of each, timed in a child process after this
             # line's timed region (the driver only runs C1; profiles/rNN_bench_c{3,4}.json are the long forms of the same numbers)
             out["other_configs"] = {c_: other_config_child(c_, 10, 150.0) for c_ in ("c4", "c3")}
-        ev, nev = eval_psnr(model, frames, norm, takes_image)
-        out["eval_psnr_db"] = round(ev, 3)
-        out["config"]["eval"] = f"pred_seen_psnr over the first {nev} frames of the shard after {max(a.warmup, 5) + a.steps + (out['parity']['steps'] if 'parity' in out else 0)} train steps from random init (fp32 model)"
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full:
+            ev, nev = eval_psnr(model, frames, norm, takes_image)
+            out["eval_psnr_db"] = round(ev, 3)
+            out["config"]["eval"] = f"pred_seen_psnr over the first {nev} frames of the shard after {max(a.warmup, 5) + a.steps + (out['parity']['steps'] if 'parity' in out else 0)} train steps from random init (fp32 model)"
+        if a.full and world == 1 and not a.no_cpu_baseline:
             fcpu = torch.stack([vid.frame(i) for i in keep[:4]])
             ncpu = torch.tensor([(i + 1) / r["n"] for i in keep[:4]], dtype=torch.float64)
             out["cpu_baseline"] = cpu_baseline(args, sd_cpu, fcpu, ncpu)
@@ -798,7 +842,7 @@ def main():
             # second yardstick of SURVEY 8(d): the same restatement on stock PyTorch-ROCm ops, in a child process under a time budget
             # (on a fresh box MIOpen may compile / search solvers for ~50 conv shapes: minutes) -- the bench line never waits longer
             out["stock_rocm"] = stock_rocm_child(a.config, budget_s=240.0 if a.stock_rocm else 75.0)
-        else:
+        elif a.full:
             out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
     if dist.is_available() and dist.is_initialized():      # (also the 1-rank group of BNERV_BENCH_FORCE_BUCKET: a live watchdog thread must not meet the teardown)

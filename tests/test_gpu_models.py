@@ -979,7 +979,7 @@ def test_bench_two_ranks_share_one_gpu(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     # plain `python bench.py --gpus 2`: the script launches its own ranks (torch.distributed.run, free local port)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "5"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "5", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -996,6 +996,34 @@ def test_bench_two_ranks_share_one_gpu(tmp_path):
     assert set(out["dp"]["probe_ms_per_step"]) == {"1", "2"} and all(v > 0 for v in out["dp"]["probe_ms_per_step"].values())
     pm = out["dp"]["probe_ms_per_step"]
     assert out["config"]["dp_buckets"] == (2 if pm["2"] < pm["1"] else 1)
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """The lean form `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: ONE JSON line with the headline keys (ms_per_step of
+    exactly K timed steps) and none of --full's extras; DIR holds what the last timed step returned -- loss, PSNR, the trained model's
+    tensors -- as float32 .npy files within 64 MB, and the dumped loss is the line's last_loss."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "BNERV_BENCH_SHARE_GPU", "BNERV_BENCH_FORCE_BUCKET")}
+    d = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "5", "--dump-outputs", str(d)]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["metric"] == "train frames/sec" and out["unit"] == "frames/s" and out["higher_is_better"] is True and out["dtype"] == "fp32"
+    assert out["steps"] == 4 and out["n_gpus"] == 1 and out["ms_per_step"] > 0
+    assert abs(out["value"] - 1e3 / out["ms_per_step"]) <= 1e-3 * out["value"]
+    assert not {"roofline", "parity", "host_frames", "recipe", "other_configs", "eval_psnr_db", "cpu_baseline", "stock_rocm"} & set(out)
+    files = sorted(os.listdir(d))
+    assert "loss.npy" in files and "psnr.npy" in files and sum(f.startswith("param.") for f in files) > 10
+    arrays = {f: np.load(d / f) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(os.path.getsize(d / f) for f in files) <= 64 * 2 ** 20
+    assert arrays["loss.npy"].size == 1 and round(float(arrays["loss.npy"].reshape(-1)[0]), 6) == out["config"]["last_loss"]
 
 
 @pytest.mark.isolated
@@ -1016,7 +1044,7 @@ def test_bench_eight_ranks_share_one_gpu(tmp_path):
         so.bind(("127.0.0.1", 0))
         port = so.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "5", "--warmup", "5"]
+           os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "5", "--warmup", "5", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -6,17 +6,17 @@ R=$PWD
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $O/e2_bench_c1.json 2> $O/e2_bench_c1.err
-for c in c3 c4 c5; do python $R/bench.py --config $c 2>/dev/null | tail -1 > $O/e2_bench_$c.json; done
+python $R/bench.py --full > $O/e2_bench_c1.json 2> $O/e2_bench_c1.err
+for c in c3 c4 c5; do python $R/bench.py --full --config $c 2>/dev/null | tail -1 > $O/e2_bench_$c.json; done
 # kernel traces (--stats) of the graph-replayed step for c1 / c3 / c4, and an eager per-launch timeline for c1 / c3
-rocprofv3 --kernel-trace --stats -d /tmp/ks_c1 -- python $R/bench.py --steps 40 --warmup 6 --no_cpu_baseline --no_graph > /tmp/ks_c1.log 2>&1
+rocprofv3 --kernel-trace --stats -d /tmp/ks_c1 -- python $R/bench.py --full --steps 40 --warmup 6 --no_cpu_baseline --no_graph > /tmp/ks_c1.log 2>&1
 python $R/tools/prof_summary.py /tmp/ks_c1 46 45 > $O/e2_c1_trace.md 2>&1
 for c in c3 c4; do
-  rocprofv3 --kernel-trace --stats -d /tmp/ks_$c -- python $R/bench.py --config $c --steps 20 --warmup 5 --no_cpu_baseline > /tmp/ks_$c.log 2>&1
+  rocprofv3 --kernel-trace --stats -d /tmp/ks_$c -- python $R/bench.py --full --config $c --steps 20 --warmup 5 --no_cpu_baseline > /tmp/ks_$c.log 2>&1
   python $R/tools/prof_summary.py /tmp/ks_$c 25 40 > $O/e2_${c}_trace.md 2>&1
 done
 for c in c1 c3; do
-  rocprofv3 --kernel-trace --output-format csv -d /tmp/kt_$c -- python $R/bench.py --config $c --steps 4 --warmup 5 --no_cpu_baseline --no_graph > /tmp/kt_$c.log 2>&1
+  rocprofv3 --kernel-trace --output-format csv -d /tmp/kt_$c -- python $R/bench.py --full --config $c --steps 4 --warmup 5 --no_cpu_baseline --no_graph > /tmp/kt_$c.log 2>&1
   python $R/tools/ktimeline.py /tmp/kt_$c loss_final_kernel > $O/e2_timeline_$c.md 2>&1
 done
 # PMC of the step's dominant instantiation (K2s: conv_lean_kernel<3,1,7,3>) and of the lean weight gradient

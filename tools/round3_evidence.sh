@@ -9,8 +9,8 @@ python tools/pmc_traffic.py wide > /dev/null 2>&1
 python tools/pmc_traffic.py c4 > /dev/null 2>&1
 cp $O/r03_traffic.json $O/r03_traffic_wide.json $O/r03_traffic_c4.json $R/profiles/ 2>/dev/null      # the bench lines below read (and verify) them
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $O/r03_bench_c1.json 2> $O/r03_bench_c1.err
-for c in c3 c4 c5; do python $R/bench.py --config $c 2>/dev/null | tail -1 > $O/r03_bench_$c.json; done
+python $R/bench.py --full > $O/r03_bench_c1.json 2> $O/r03_bench_c1.err
+for c in c3 c4 c5; do python $R/bench.py --full --config $c 2>/dev/null | tail -1 > $O/r03_bench_$c.json; done
 for c in c1 c3 c4; do
   rm -rf /tmp/ks_$c
   rocprofv3 --kernel-trace --stats -d /tmp/ks_$c -- python $R/bench.py --config $c --steps 20 --warmup 5 --steps_only > /tmp/ks_$c.log 2>&1

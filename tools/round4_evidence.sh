@@ -8,8 +8,8 @@ R=$PWD; O=$R/gpurun_out; mkdir -p $O
 for k in pair_dk2s pair_dk3s pair_dk1 k2s c4 wide; do python tools/pmc_traffic.py $k r04 > /dev/null 2>&1; done
 cp $O/r04_traffic_*.json $R/profiles/ 2>/dev/null          # the bench lines below read (and verify) them
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $O/r04_bench_c1.json 2> $O/r04_bench_c1.err
-for c in c3 c4 c5; do python $R/bench.py --config $c 2>/dev/null | tail -1 > $O/r04_bench_$c.json; done
+python $R/bench.py --full > $O/r04_bench_c1.json 2> $O/r04_bench_c1.err
+for c in c3 c4 c5; do python $R/bench.py --full --config $c 2>/dev/null | tail -1 > $O/r04_bench_$c.json; done
 for c in c1 c3 c4; do
   rm -rf /tmp/ks_$c
   rocprofv3 --kernel-trace --stats -d /tmp/ks_$c -- python $R/bench.py --config $c --steps 20 --warmup 5 --steps_only > /tmp/ks_$c.log 2>&1

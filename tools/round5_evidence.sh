@@ -10,9 +10,9 @@ if [ "${1:-}" != nopmc ] && [ "${2:-}" != nopmc ]; then
 fi
 cp $O/r05_traffic_*.json $R/profiles/ 2>/dev/null          # the bench lines below read (and verify) them
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $O/r05_bench_c1.json 2> $O/r05_bench_c1.err
+python $R/bench.py --full > $O/r05_bench_c1.json 2> $O/r05_bench_c1.err
 if [ "${1:-}" != fast ]; then
-  for c in c3 c4 c5; do python $R/bench.py --config $c 2>/dev/null | tail -1 > $O/r05_bench_$c.json; done
+  for c in c3 c4 c5; do python $R/bench.py --full --config $c 2>/dev/null | tail -1 > $O/r05_bench_$c.json; done
 fi
 for c in c1 c3 c4; do
   rm -rf /tmp/ks_$c

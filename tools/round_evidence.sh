@@ -7,12 +7,12 @@ R=$PWD
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $O/${TAG}_bench_c1.json 2> $O/${TAG}_bench_c1.err
-for c in c3 c4 c5; do python $R/bench.py --config $c --no_cpu_baseline 2>/dev/null | tail -1 > $O/${TAG}_bench_$c.json; done
-rocprofv3 --kernel-trace --stats -d /tmp/kt_c1 -- python $R/bench.py --steps 40 --warmup 6 --no_cpu_baseline --no_graph > /tmp/kt_c1.log 2>&1
+python $R/bench.py --full > $O/${TAG}_bench_c1.json 2> $O/${TAG}_bench_c1.err
+for c in c3 c4 c5; do python $R/bench.py --full --config $c --no_cpu_baseline 2>/dev/null | tail -1 > $O/${TAG}_bench_$c.json; done
+rocprofv3 --kernel-trace --stats -d /tmp/kt_c1 -- python $R/bench.py --full --steps 40 --warmup 6 --no_cpu_baseline --no_graph > /tmp/kt_c1.log 2>&1
 python $R/tools/prof_summary.py /tmp/kt_c1 46 45 > $O/${TAG}_c1_trace.md 2>&1
 for c in c3 c4; do
-  rocprofv3 --kernel-trace --stats -d /tmp/kt_$c -- python $R/bench.py --config $c --steps 20 --warmup 5 --no_cpu_baseline > /tmp/kt_$c.log 2>&1
+  rocprofv3 --kernel-trace --stats -d /tmp/kt_$c -- python $R/bench.py --full --config $c --steps 20 --warmup 5 --no_cpu_baseline > /tmp/kt_$c.log 2>&1
   python $R/tools/prof_summary.py /tmp/kt_$c 25 40 > $O/${TAG}_${c}_trace.md 2>&1
 done
 for k in conv wgrad conv38 wgrad38; do

@@ -9,8 +9,8 @@ python -m pytest tests/test_gpu_models.py -x -q -k "plan or trajectory or dp_ste
 tail -3 $O/wp_tests.log
 cd /tmp && export TMPDIR=/tmp
 for c in c1 c3 c4; do
-  BNERV_WPLAN=0 python $R/bench.py --config $c --no_cpu_baseline 2>/dev/null | tail -1 > $O/wp_off_bench_$c.json
-  python $R/bench.py --config $c --no_cpu_baseline 2>/dev/null | tail -1 > $O/wp_on_bench_$c.json
+  BNERV_WPLAN=0 python $R/bench.py --full --config $c --no_cpu_baseline 2>/dev/null | tail -1 > $O/wp_off_bench_$c.json
+  python $R/bench.py --full --config $c --no_cpu_baseline 2>/dev/null | tail -1 > $O/wp_on_bench_$c.json
   python - <<EOF
 import json
 for k in ("off", "on"):
@@ -20,7 +20,7 @@ for k in ("off", "on"):
         print("$c", k, "failed", e)
 EOF
 done
-rocprofv3 --kernel-trace --stats -d /tmp/ks_c1 -- python $R/bench.py --steps 40 --warmup 6 --no_cpu_baseline > /tmp/ks_c1.log 2>&1
+rocprofv3 --kernel-trace --stats -d /tmp/ks_c1 -- python $R/bench.py --full --steps 40 --warmup 6 --no_cpu_baseline > /tmp/ks_c1.log 2>&1
 python $R/tools/prof_summary.py /tmp/ks_c1 46 45 > $O/wp_c1_trace.md 2>&1
 head -30 $O/wp_c1_trace.md
 echo done
