@@ -138,6 +138,12 @@ SYMBOLS = {
     "bnerv_conv_wgrad_ws_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
     "bnerv_conv_wgrad_pair": (_I, [_V, C.POINTER(ConvDesc), C.POINTER(WgradDesc)]),
     "bnerv_conv_wgrad": (_I, [_V, C.POINTER(WgradDesc)]),
+    "bnerv_conv5_ws_bytes": (_Z, [_I, _I]),
+    "bnerv_conv5_igemm": (_I, [_V, C.POINTER(ConvDesc), _V, _Z]),
+    "bnerv_conv5_wgrad_ws_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "bnerv_conv5_wgrad": (_I, [_V, C.POINTER(WgradDesc)]),
+    "bnerv_gelu_fwd": (_I, [_V, _V, _V, _V, _Z]),
+    "bnerv_mul": (_I, [_V, _V, _V, _V, _Z]),
     "bnerv_cem_ws_bytes": (_Z, [_I, _I]),
     "bnerv_cem_scale_fwd": (_I, [_V, C.POINTER(CemChunk), _V, _V, _Z]),
     "bnerv_cem_scale_bwd": (_I, [_V, C.POINTER(CemChunkBwd), _V, _V, _V, _V, _Z]),
@@ -168,6 +174,8 @@ SYMBOLS = {
     "bnerv_adan_multi_tensor": (_I, [_V, C.POINTER(AdanChunk), C.POINTER(AdanHyper)]),
     "bnerv_adan_table_blocks": (_I, [_I]),
     "bnerv_adan_table": (_I, [_V, _V, _I, _I, C.POINTER(AdanHyper)]),
+    "bnerv_adam_table_blocks": (_I, [_I]),
+    "bnerv_adam_table": (_I, [_V, _V, _I, _I, C.POINTER(AdanHyper)]),
     "bnerv_fetch_frame": (_I, [_V, _V, _V, _V, _I, _Z, _V, _V]),
     "bnerv_bucket_gather": (_I, [_V, C.POINTER(BucketChunk), _V, _F]),
     "bnerv_bucket_scatter": (_I, [_V, C.POINTER(BucketChunk), _V, _F]),

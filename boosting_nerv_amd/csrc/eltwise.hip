@@ -47,7 +47,54 @@ __global__ __launch_bounds__(256) void tanh_grad_kernel(const float* __restrict_
         part[((size_t)b * nblk + blk) * C + c] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
     }
 }
+
+// y = gelu(u), gp = gelu'(u) (gp may be NULL), in place allowed; and du = g * gp: the GELU of the HNeRV baseline's 1x1 / 3x3 stages
+// (NeRVBlock, model_blocks.py:34-46 with act = 'gelu') around the existing EP_BIAS (+ PixelShuffle) convolutions.
+__global__ __launch_bounds__(256) void gelu_fwd_kernel(const float* __restrict__ u, float* __restrict__ y, float* __restrict__ gp, const size_t n, const int vec) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    if (vec) {
+        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n / 4; i += stride) {
+            f32x4 h, g;
+            gelu_pair4_f(reinterpret_cast<const f32x4*>(u)[i], &h, &g);
+            reinterpret_cast<f32x4*>(y)[i] = h;
+            if (gp) reinterpret_cast<f32x4*>(gp)[i] = g;
+        }
+    } else {
+        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+            float h, g;
+            gelu_pair_f(u[i], &h, &g);
+            y[i] = h;
+            if (gp) gp[i] = g;
+        }
+    }
+}
+__global__ __launch_bounds__(256) void mul_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, const size_t n, const int vec) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    if (vec) {
+        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n / 4; i += stride)
+            reinterpret_cast<f32x4*>(out)[i] = reinterpret_cast<const f32x4*>(a)[i] * reinterpret_cast<const f32x4*>(b)[i];
+    } else {
+        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) out[i] = a[i] * b[i];
+    }
+}
+static int stream_grid(size_t n) { const size_t b = (n + 1023) / 1024; return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b)); }
 }  // namespace
+
+extern "C" int bnerv_gelu_fwd(void* stream, const float* u, float* y, float* gp, size_t n) {
+    BNERV_REQUIRE(u && y && n > 0, "gelu_fwd: bad args");
+    const int vec = (n % 4 == 0) && ((reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gp)) & 15) == 0;
+    hipLaunchKernelGGL(gelu_fwd_kernel, dim3(stream_grid(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), u, y, gp, n, vec);
+    BNERV_LAUNCH_CHECK("gelu_fwd");
+    return BNERV_OK;
+}
+
+extern "C" int bnerv_mul(void* stream, const float* a, const float* b, float* out, size_t n) {
+    BNERV_REQUIRE(a && b && out && n > 0, "mul: bad args");
+    const int vec = (n % 4 == 0) && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    hipLaunchKernelGGL(mul_kernel, dim3(stream_grid(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, b, out, n, vec);
+    BNERV_LAUNCH_CHECK("mul");
+    return BNERV_OK;
+}
 
 extern "C" int bnerv_tanh_grad_blocks(int HW) { return HW > 0 ? cdiv(HW, TG_PER_BLOCK) : 0; }
 

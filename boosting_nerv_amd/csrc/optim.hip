@@ -98,6 +98,38 @@ __global__ __launch_bounds__(256) void adan_table_kernel(const bnerv_adan_entry*
     adan_update(e.p, e.g, e.exp_avg, e.exp_avg_sq, e.exp_avg_diff, e.neg_pre_grad, e.n, (int)blockIdx.x - e.bstart, gx, h);
 }
 
+// Fused Adam (torch.optim.Adam defaults: no weight decay, no amsgrad; torch/optim/adam.py _single_tensor_adam order of operations):
+//   m = m + (1 - b1) (g - m);  v = v b2 + (1 - b2) g g;  denom = sqrt(v) / sqrt(bc2) + eps;  p = p - (lr / bc1) (m / denom)
+// sched_dev = {lr, bias_correction1, sqrt(bias_correction2), 1 - b1, 1 - b2}: read from device memory, so a captured step replays with a moving
+// step count.  The two complements come from the host, rounded from their float64 values as torch's kernels receive them (1.0f - 0.999f is
+// 4.7e-5 off 0.001).
+// Same device table as the Adan table form (exp_avg_diff / neg_pre_grad unused).
+__global__ __launch_bounds__(256) void adam_table_kernel(const bnerv_adan_entry* __restrict__ tab, const int n_tensors, const bnerv_adan_hyper h) {
+#pragma clang fp contract(off)
+    int t = 0;
+    for (int hi = n_tensors; hi - t > 1;) {
+        const int mid = (t + hi) >> 1;
+        if ((int)blockIdx.x >= tab[mid].bstart) t = mid; else hi = mid;
+    }
+    const bnerv_adan_entry e = tab[t];
+    const int gx = min(cdiv_dev(e.n, 256 * 4), 1024), bx = (int)blockIdx.x - e.bstart;
+    const float lr = h.sched_dev[0], bc1 = h.sched_dev[1], bc2s = h.sched_dev[2], omb1 = h.sched_dev[3], omb2 = h.sched_dev[4];
+    const float b2 = h.beta2, eps = h.eps;
+    const float step_size = lr / bc1;
+    float* __restrict__ p = e.p;
+    const float* __restrict__ g = e.g;
+    float* __restrict__ m = e.exp_avg;
+    float* __restrict__ v = e.exp_avg_sq;
+    for (int i = bx * 256 + threadIdx.x; i < e.n; i += gx * 256) {
+        const float gi = g[i];
+        const float mi = m[i] + omb1 * (gi - m[i]);
+        const float vi = v[i] * b2 + omb2 * (gi * gi);
+        const float denom = sqrtf(vi) / bc2s + eps;
+        p[i] = p[i] + (-step_size) * (mi / denom);
+        m[i] = mi; v[i] = vi;
+    }
+}
+
 __global__ __launch_bounds__(256) void fetch_frame_kernel(const float* __restrict__ clip, const double* __restrict__ norms, const float* __restrict__ sel,
                                                           const int n_frames, const size_t frame_elems, float* __restrict__ dst, double* __restrict__ dst_norm) {
     fetch_frame_body(clip, norms, sel, n_frames, frame_elems, dst, dst_norm, (int)blockIdx.x, (int)gridDim.x);
@@ -155,6 +187,17 @@ extern "C" int bnerv_adan_table(void* stream, const bnerv_adan_entry* table_dev,
     BNERV_REQUIRE(n_tensors > 0 && total_blocks > 0, "adan_table: n_tensors=%d total_blocks=%d", n_tensors, total_blocks);
     hipLaunchKernelGGL(adan_table_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, table_dev, n_tensors, *h);
     BNERV_LAUNCH_CHECK("adan_table");
+    return BNERV_OK;
+}
+
+extern "C" int bnerv_adam_table_blocks(int n) { return bnerv_adan_table_blocks(n); }
+
+extern "C" int bnerv_adam_table(void* stream, const bnerv_adan_entry* table_dev, int n_tensors, int total_blocks, const bnerv_adan_hyper* h) {
+    BNERV_REQUIRE(table_dev && h && h->sched_dev, "adam_table: null args");
+    BNERV_REQUIRE(n_tensors > 0 && total_blocks > 0, "adam_table: n_tensors=%d total_blocks=%d", n_tensors, total_blocks);
+    BNERV_REQUIRE(h->beta1 >= 0.f && h->beta1 < 1.f && h->beta2 >= 0.f && h->beta2 < 1.f && h->eps >= 0.f, "adam_table: bad hyper-parameters");
+    hipLaunchKernelGGL(adam_table_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, table_dev, n_tensors, *h);
+    BNERV_LAUNCH_CHECK("adam_table");
     return BNERV_OK;
 }
 

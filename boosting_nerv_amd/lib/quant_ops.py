@@ -42,14 +42,14 @@ class CustomConv2d(nn.Conv2d):
 
     def hip_supported(self):
         k = self.kernel_size[0]
-        return (self.kernel_size[0] == self.kernel_size[1] and k in (1, 3) and self.stride == (1, 1)
+        return (self.kernel_size[0] == self.kernel_size[1] and k in (1, 3, 5) and self.stride == (1, 1)
                 and self.padding == ((k - 1) // 2, (k - 1) // 2) and self.dilation == (1, 1) and self.groups == 1)
 
     def forward(self, x):
         w, b = self.effective_weight(), self.effective_bias()
         if not self.hip_supported():
             raise NotImplementedError(f"CustomConv2d{tuple(self.weight.shape)} stride={self.stride} padding={self.padding}: only "
-                                      f"stride-1 'same' 1x1/3x3 convs exist on the HIP decoder path")
+                                      f"stride-1 'same' 1x1/3x3/5x5 convs exist on the HIP decoder path")
         if self.kernel_size[0] == 1 and x.shape[-2:] == (1, 1):
             y = ops.dense_grouped([x], [w], [b], ["none"])[0]
             return y.view(x.shape[0], -1, 1, 1)

@@ -56,6 +56,8 @@ def _act_name(m):
         return "relu"
     if isinstance(m, nn.Identity):
         return "none"
+    if isinstance(m, nn.GELU) and m.approximate == "none":
+        return "gelu"
     return None
 
 
@@ -235,8 +237,9 @@ class DownConv(nn.Module):
         super().__init__()
         ks, ngf, new_ngf, strd = kargs["ks"], kargs["ngf"], kargs["new_ngf"], kargs["strd"]
         if kargs["conv_type"] != "conv" or ks + strd != 1:
-            raise NotImplementedError("DownConv: only the HNeRV_Boost decoder[0] form (conv_type='conv', ks=0, strd=1 -> 1x1 conv) "
-                                      "is on the path (model_hnerv.py:200-201); encoder down-convs belong to the non-boost HNeRV baseline")
+            raise NotImplementedError("DownConv: only the decoder[0] form of HNeRV / HNeRV_Boost (conv_type='conv', ks=0, strd=1 -> 1x1 conv) "
+                                      "is on the path (model_hnerv.py:46-47, :200-201); strided encoder down-convs (the NeRVBlock encoder of "
+                                      "HNeRV, conv_type[0] != 'convnext') are not")
         self.downconv = CustomConv2d(ngf, new_ngf, ks + strd, strd, ceil(ks / 2), bias=kargs["bias"], args=kargs["args"])
         self.stride = 1
 
@@ -256,8 +259,8 @@ class UpConv(nn.Module):
         if ct == "pshuffel_3x3":
             ks = 3 if ks > 3 else ks
         elif ct != "pshuffel":
-            raise NotImplementedError(f"UpConv conv_type={ct!r}: the boost recipes use 'pshuffel_3x3' (and 'pshuffel'); "
-                                      f"'conv'/'interpolate' are not on the HIP path")
+            raise NotImplementedError(f"UpConv conv_type={ct!r}: the boost recipes use 'pshuffel_3x3', the HNeRV baseline 'pshuffel' "
+                                      f"(ks up to 5); 'conv'/'interpolate' are not on the HIP path")
         self.upconv = nn.Sequential(
             CustomConv2d(ngf, new_ngf * strd * strd, ks, 1, ceil((ks - 1) // 2), bias=kargs["bias"], args=args),
             nn.PixelShuffle(strd) if strd != 1 else nn.Identity(),
@@ -285,7 +288,7 @@ class NeRVBlock(nn.Module):
         if args.sft_block == "res_sft" and kargs.get("sft_ngf", 0) != 0:
             if not self.dec_block:
                 raise NotImplementedError("NeRVBlock without dec_block and without encoder strides (fc-reshape TAT form, "
-                                          "model_blocks.py:40-43) is only used by the non-boost HNeRV baseline")
+                                          "model_blocks.py:40-43: a PE-embedding model with TAT) is not on the HIP path")
             sft_ch = kargs["new_ngf"]
             self.sft_block = ResBlock_SFT(sft_ch, sft_ch, cond_ch=kargs["sft_ngf"], in_act="relu", out_act="gelu", omega=1, args=args)
 
@@ -308,7 +311,12 @@ class NeRVBlock(nn.Module):
             return ops.snerv_block(feat, c.effective_weight(), c.effective_bias(), s0, t0, s1, t1,
                                    sb.conv0.effective_weight(), sb.conv0.effective_bias(),
                                    sb.conv1.effective_weight(), sb.conv1.effective_bias(), self.conv.stride)
-        return self.act(self.norm(self.conv(x)))
+        # plain tensor (the HNeRV baseline, sft_block='none'): conv + bias + PixelShuffle + activation as ONE operator
+        act = _act_name(self.act)
+        if not (isinstance(self.norm, nn.Identity) and act in ops.UPCONV_ACTS and self.conv.conv_module().hip_supported()):
+            raise NotImplementedError("NeRVBlock(x) on the HIP path needs norm='none', act in ('gelu', none) and a stride-1 'same' 1x1/3x3/5x5 conv")
+        c = self.conv.conv_module()
+        return ops.upconv_act(x, c.effective_weight(), c.effective_bias(), self.conv.stride, act)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

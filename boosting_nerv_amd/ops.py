@@ -6,6 +6,7 @@ ATen):
   positional_encoding      PositionEncoding.forward              model_blocks.py:120-126
   dense_grouped            NeRV_MLP / SFTLayer 1x1 convs         model_blocks.py:66-71, :92-105
   conv2d_ps                CustomConv2d (+PixelShuffle)          lib/quant_ops.py:39-41, model_blocks.py:213-218
+  upconv_act               NeRVBlock.forward without TAT         model_blocks.py:34-46 (HNeRV baseline: conv + PixelShuffle + GELU)
   snerv_block              NeRVBlock.forward with TAT            model_blocks.py:34-39 + :83-89
   tat_block                ResBlock_SFT.forward                  model_blocks.py:83-89
   sft_affine               SFTLayer.forward (affine part)        model_blocks.py:101-105
@@ -493,31 +494,119 @@ class _Conv2dPS(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, w = ctx.saved_tensors
+        dx, dw, db = _conv_ps_backward(x, w, L.f32c(g), ctx.s, ctx.has_b, ctx.needs_input_grad[0])
+        return dx, dw, db, None
+
+
+def _conv_ps_backward(x, w, g, s, has_b, need_dx):
+    """Backward of conv (k in {1,3}) + bias + PixelShuffle(s) from the gradient g of the shuffled output: (dx or None, dw, db or None)."""
+    B, Cin, H, W = x.shape
+    Cout, k = w.shape[0], w.shape[-1]
+    dw = torch.empty_like(w)
+    db = torch.empty(Cout, dtype=torch.float32, device=x.device) if has_b else None
+    dx = None
+    dxq = False
+    if need_dx and k == 3:                                     # (dW | dx): one launch where the library pairs them
+        dx = torch.empty_like(x)
+        _wgrad_conv_pair(dict(x=x, g=g, dw=dw, db=db, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=k, in_mode=L.IN_PLAIN, g_mode=L.IN_UNSHUFFLE, g_s=s),
+                         dict(x=g, w=w, bias=None, out=dx, B=B, Cin=Cout, Cout=Cin, H=H, W=W, k=k, in_mode=L.IN_UNSHUFFLE, ep_mode=L.EP_PLAIN, in_s=s, transposed=1))
+        dxq = _pair_dx_deferred
+    else:
+        _wgrad(x, g, dw, db, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=k, in_mode=L.IN_PLAIN, g_mode=L.IN_UNSHUFFLE, g_s=s, defer=True)
+        if need_dx:
+            dx = torch.empty_like(x)
+            _conv(g, w, None, dx, B=B, Cin=Cout, Cout=Cin, H=H, W=W, k=k, in_mode=L.IN_UNSHUFFLE, ep_mode=L.EP_PLAIN, in_s=s, transposed=1)
+    _flush_deferred(block_end=True, dx_deferred=dxq)
+    return dx, dw, db
+
+
+def conv2d_ps(x, w, b, shuffle=1):
+    """F.conv2d(x, w, b, stride 1, padding (k-1)//2) followed by PixelShuffle(shuffle); k in {1,3}, and k = 5 through upconv_act."""
+    if w.shape[-1] == 5:
+        return upconv_act(x, w, b, shuffle, "none")
+    return _Conv2dPS.apply(x, w, b, int(shuffle))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# up-conv block of the HNeRV baseline: conv (k in {1,3,5}) + bias + PixelShuffle + activation (none | gelu)
+# ----------------------------------------------------------------------------------------------------------------------
+def _conv5(x, w, bias, out, *, B, Cin, Cout, H, W, in_mode=L.IN_PLAIN, ep_mode, in_s=1, out_s=1, transposed=0, out2=None, aux0=None):
+    lib = L.load()
+    nbytes = lib.bnerv_conv5_ws_bytes(Cin, Cout)
+    ws = _ws(nbytes, x.device)
+    d = L.ConvDesc(L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(out), L.ptr(out2), L.ptr(aux0), None, None, None, None, None,
+                   B, Cin, Cout, H, W, 5, in_mode, ep_mode, in_s, out_s, transposed, w.shape[0], w.shape[1], None)
+    L.check(lib.bnerv_conv5_igemm(L.stream(), C.byref(d), L.ptr(ws), nbytes), "bnerv_conv5_igemm")
+
+
+def _wgrad5(x, g, dw, db, *, B, Cin, Cout, H, W, g_s=1, gaux=None):
+    lib = L.load()
+    nbytes = lib.bnerv_conv5_wgrad_ws_bytes(B, Cin, Cout, H, W)
+    ws = _ws(nbytes, x.device)
+    d = L.WgradDesc(L.ptr(x), L.ptr(g), L.ptr(gaux), None, None, L.ptr(dw), L.ptr(db), L.ptr(ws), nbytes,
+                    B, Cin, Cout, H, W, 5, L.IN_PLAIN, L.IN_UNSHUFFLE if g_s > 1 else L.IN_PLAIN, g_s, 0, None)
+    L.check(lib.bnerv_conv5_wgrad(L.stream(), C.byref(d)), "bnerv_conv5_wgrad")
+
+
+UPCONV_ACTS = ("none", "gelu")
+
+
+class _UpConvAct(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, s, act):
+        x = L.f32c(L.require_device(x, "x")); w = L.f32c(w); b = None if b is None else L.f32c(b)
+        B, Cin, H, W = x.shape
+        Cout, k = w.shape[0], w.shape[-1]
+        gelu = act == "gelu"
+        train = any(ctx.needs_input_grad)                   # False under torch.no_grad(): decode keeps no gelu'
+        out = torch.empty(B, Cout // (s * s), H * s, W * s, dtype=torch.float32, device=x.device)
+        gp = torch.empty_like(out) if (gelu and train) else None
+        if k == 5:
+            _conv5(x, w, b, out, B=B, Cin=Cin, Cout=Cout, H=H, W=W, ep_mode=L.EP_BIAS_GELU if gelu else L.EP_BIAS, out_s=s, out2=gp)
+        else:
+            _conv(x, w, b, out, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=k, in_mode=L.IN_PLAIN, ep_mode=L.EP_BIAS, out_s=s)
+            if gelu:
+                L.check(L.load().bnerv_gelu_fwd(L.stream(), L.ptr(out), L.ptr(out), L.ptr(gp), out.numel()), "bnerv_gelu_fwd")
+        if train:
+            ctx.save_for_backward(x, w, gp)
+        ctx.s, ctx.has_b = s, b is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, gp = ctx.saved_tensors
         s = ctx.s
         g = L.f32c(g)
         B, Cin, H, W = x.shape
         Cout, k = w.shape[0], w.shape[-1]
+        if k != 5:
+            if gp is not None:
+                du = torch.empty_like(g)
+                L.check(L.load().bnerv_mul(L.stream(), L.ptr(g), L.ptr(gp), L.ptr(du), g.numel()), "bnerv_mul")
+                g = du
+            dx, dw, db = _conv_ps_backward(x, w, g, s, ctx.has_b, ctx.needs_input_grad[0])
+            return dx, dw, db, None, None
+        # 5x5: the product with the saved gelu' is folded into the gradient staging of both kernels (du is never written out)
         dw = torch.empty_like(w)
         db = torch.empty(Cout, dtype=torch.float32, device=x.device) if ctx.has_b else None
+        _wgrad5(x, g, dw, db, B=B, Cin=Cin, Cout=Cout, H=H, W=W, g_s=s, gaux=gp)
         dx = None
-        dxq = False
-        if ctx.needs_input_grad[0] and k == 3:                 # (dW | dx): one launch where the library pairs them
+        if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            _wgrad_conv_pair(dict(x=x, g=g, dw=dw, db=db, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=k, in_mode=L.IN_PLAIN, g_mode=L.IN_UNSHUFFLE, g_s=s),
-                             dict(x=g, w=w, bias=None, out=dx, B=B, Cin=Cout, Cout=Cin, H=H, W=W, k=k, in_mode=L.IN_UNSHUFFLE, ep_mode=L.EP_PLAIN, in_s=s, transposed=1))
-            dxq = _pair_dx_deferred
-        else:
-            _wgrad(x, g, dw, db, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=k, in_mode=L.IN_PLAIN, g_mode=L.IN_UNSHUFFLE, g_s=s, defer=True)
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-                _conv(g, w, None, dx, B=B, Cin=Cout, Cout=Cin, H=H, W=W, k=k, in_mode=L.IN_UNSHUFFLE, ep_mode=L.EP_PLAIN, in_s=s, transposed=1)
-        _flush_deferred(block_end=True, dx_deferred=dxq)
-        return dx, dw, db, None
+            _conv5(g, w, None, dx, B=B, Cin=Cout, Cout=Cin, H=H, W=W, in_mode=L.IN_UNSHUFFLE if s > 1 else L.IN_PLAIN, ep_mode=L.EP_PLAIN,
+                   in_s=s, transposed=1, aux0=gp)
+        return dx, dw, db, None, None
 
 
-def conv2d_ps(x, w, b, shuffle=1):
-    """F.conv2d(x, w, b, stride 1, padding (k-1)//2) followed by PixelShuffle(shuffle); k in {1,3}."""
-    return _Conv2dPS.apply(x, w, b, int(shuffle))
+def upconv_act(x, w, b, stride=1, act="none"):
+    """act(PixelShuffle_stride(F.conv2d(x, w, b, padding (k-1)//2))) -- NeRVBlock.forward of the HNeRV baseline (norm='none'); k in {1,3,5},
+    act in {"none", "gelu"}.  5x5: stride in {1, 2}, GELU fused into the conv's epilogue and its derivative into the backward's staging."""
+    k = w.shape[-1]
+    if act not in UPCONV_ACTS:
+        raise NotImplementedError(f"upconv_act: act={act!r} (supported: {UPCONV_ACTS})")
+    if w.shape[-2] != k or k not in (1, 3, 5) or (k == 5 and int(stride) not in (1, 2)) or w.shape[0] % (int(stride) ** 2):
+        raise NotImplementedError(f"upconv_act: weight {tuple(w.shape)} with stride {stride} is not on the HIP path (k in {{1,3,5}}; 5x5: stride 1 or 2)")
+    return _UpConvAct.apply(x, w, b, int(stride), act)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -16,23 +16,13 @@ from torch.optim.optimizer import Optimizer
 from . import _lib as L
 
 
-class Adan(Optimizer):
+class _FusedTableOptimizer(Optimizer):
+    """The driver the fused optimizers share: the device schedule record written by prepare_step(), the device-resident descriptor table
+    of launch_step() and its capture bracket.  A subclass supplies the record's values (_sched_record), the per-parameter state
+    (_ensure_state), the state tensors of a table entry (_entry_state) and the launch (_launch)."""
     _RING = 512
 
-    def __init__(self, params, lr=1e-3, betas=(0.98, 0.92, 0.99), eps=1e-8, weight_decay=0.0, max_grad_norm=0.0,
-                 no_prox=False, foreach: bool = True, fused: bool = False):
-        if not 0.0 <= max_grad_norm:
-            raise ValueError("Invalid Max grad norm: {}".format(max_grad_norm))
-        if not 0.0 <= lr:
-            raise ValueError("Invalid learning rate: {}".format(lr))
-        if not 0.0 <= eps:
-            raise ValueError("Invalid epsilon value: {}".format(eps))
-        for i in range(3):
-            if not 0.0 <= betas[i] < 1.0:
-                raise ValueError("Invalid beta parameter at index {}: {}".format(i, betas[i]))
-        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm, no_prox=no_prox,
-                        foreach=foreach, fused=fused)
-        super().__init__(params, defaults)
+    def _init_driver(self):
         self._sched = {}          # group index -> (pinned host [5], device [5])
         self._cap_open = None     # begin_capture() .. finish_capture(): group index -> (pinned host, device) descriptor table of THIS capture
         self._chunk_cache = {}    # group index -> (key, device descriptor table, n, blocks, tensors the table points into, pending host table)
@@ -44,55 +34,20 @@ class Adan(Optimizer):
         self._chunk_cache = {}
         self.state_epoch = getattr(self, "state_epoch", 0) + 1
 
-    def __setstate__(self, state):
-        super().__setstate__(state)
-        for group in self.param_groups:
-            group.setdefault("no_prox", False)
-        self.__dict__.setdefault("_sched", {})
-        self.__dict__["_cap_open"] = None
-        self._invalidate()
-
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._invalidate()
 
-    @torch.no_grad()
-    def restart_opt(self):
-        for group in self.param_groups:
-            group["step"] = 0
-            for p in group["params"]:
-                if p.requires_grad:
-                    state = self.state[p]
-                    state["exp_avg"] = torch.zeros_like(p)
-                    state["exp_avg_sq"] = torch.zeros_like(p)
-                    state["exp_avg_diff"] = torch.zeros_like(p)
-        self._invalidate()
-
-    # ------------------------------------------------------------------------------------------------------------------
     def _clip_coef(self):
-        if self.defaults["max_grad_norm"] <= 0:
-            return 1.0
-        # optimizer.py:136-156: global-norm clipping (a device sync, exactly as in the reference; off in every recipe)
-        device = self.param_groups[0]["params"][0].device
-        total = torch.zeros(1, device=device)
-        for group in self.param_groups:
-            for p in group["params"]:
-                if p.grad is not None:
-                    total.add_(p.grad.pow(2).sum())
-        total = torch.sqrt(total)
-        return torch.clamp(self.defaults["max_grad_norm"] / (total + self.param_groups[-1]["eps"]), max=1.0).item()
+        return 1.0
 
     @torch.no_grad()
     def prepare_step(self, aux=None):
-        """Host side of a step: advance the step count and publish {lr, bc1, bc2, sqrt(bc3), first_step, aux} to the device.
+        """Host side of a step: advance the step count and publish the schedule record (_sched_record: lr and bias corrections, slots 0..4) and aux to the device.
         `aux` (a float, optional) rides in slot 5 of the same 32-byte record: engine.TrainStep puts the index of the step's frame
         there when the clip is resident on the device, so a step costs ONE host -> device copy."""
         for gi, group in enumerate(self.param_groups):
-            beta1, beta2, beta3 = group["betas"]
             group["step"] = group.get("step", 0) + 1
-            bc1 = 1.0 - beta1 ** group["step"]
-            bc2 = 1.0 - beta2 ** group["step"]
-            bc3 = 1.0 - beta3 ** group["step"]
             dev = group["params"][0].device
             L.require_device(group["params"][0], "parameter")
             if gi not in self._sched:
@@ -107,25 +62,15 @@ class Adan(Optimizer):
             if events[slot] is not None:
                 events[slot].synchronize()
             host = ring[slot]
-            host[0], host[1], host[2], host[3] = group["lr"], bc1, bc2, math.sqrt(bc3)
-            host[4] = 1.0 if group["step"] == 1 else 0.0
+            rec = self._sched_record(group)
+            for i, v in enumerate(rec):
+                host[i] = v
             if aux is not None:
                 host[5] = float(aux)
             devbuf.copy_(host, non_blocking=True)
             if events[slot] is None:
                 events[slot] = torch.cuda.Event()
             events[slot].record()
-
-    def _ensure_state(self, p, step, clip):
-        state = self.state[p]
-        if len(state) == 0:
-            state["exp_avg"] = torch.zeros_like(p)
-            state["exp_avg_sq"] = torch.zeros_like(p)
-            state["exp_avg_diff"] = torch.zeros_like(p)
-        if "neg_pre_grad" not in state:
-            # step 1: the kernel's first_step flag substitutes -g; later first appearances follow optimizer.py:190-192
-            state["neg_pre_grad"] = torch.zeros_like(p) if step <= 1 else p.grad.clone().mul_(-clip)
-        return state
 
     @torch.no_grad()
     def launch_step(self, clip=1.0):
@@ -144,28 +89,29 @@ class Adan(Optimizer):
             # the key covers every pointer a descriptor holds (parameter, gradient and the four state tensors), and the cache
             # entry keeps the state tensors alive, so a descriptor can never point at freed memory
             sts = [self._ensure_state(p, group.get("step", 1), clip) for p in ps]
-            key = tuple((p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                         st["exp_avg_diff"].data_ptr(), st["neg_pre_grad"].data_ptr()) for p, st in zip(ps, sts))
+            ents = [self._entry_state(st) for st in sts]          # (exp_avg, exp_avg_sq, exp_avg_diff | None, neg_pre_grad | None)
+            key = tuple((p.data_ptr(), p.grad.data_ptr()) + tuple(0 if t is None else t.data_ptr() for t in en) for p, en in zip(ps, ents))
             capturing = torch.cuda.is_current_stream_capturing()
             ck = (gi, capturing)        # a captured launch owns its table: an eager step in between must not rewrite the addresses it replays with
             if capturing and self._cap_open is None:
-                raise L.BnervError("Adan.launch_step() inside a stream capture needs an open begin_capture() .. finish_capture() bracket "
+                raise L.BnervError(f"{type(self).__name__}.launch_step() inside a stream capture needs an open begin_capture() .. finish_capture() bracket "
                                    "(the captured launch reads a descriptor table that finish_capture() uploads)")
             cached = self._chunk_cache.get(ck)
             if capturing and cached is not None and cached[1] is not self._cap_open[gi][1]:
                 cached = None               # a table of an earlier capture: that graph keeps it; this capture writes its own
             if cached is None or cached[0] != key:
                 # (not p.grad: it is alive whenever the step launches, and pinning it would move the next eager gradient elsewhere)
-                keep = [(p, st["exp_avg"], st["exp_avg_sq"], st["exp_avg_diff"], st["neg_pre_grad"]) for p, st in zip(ps, sts)]
+                keep = [(p,) + tuple(en) for p, en in zip(ps, ents)]
                 tab = (L.AdanEntry * len(ps))()
                 blocks = 0
-                for j, (p, st) in enumerate(zip(ps, sts)):
+                for j, (p, en) in enumerate(zip(ps, ents)):
                     if not (p.is_contiguous() and p.grad.is_contiguous() and p.dtype == torch.float32 and p.grad.dtype == torch.float32):
-                        raise L.BnervError("fused Adan needs contiguous fp32 parameters and gradients")
+                        raise L.BnervError(f"fused {type(self).__name__} needs contiguous fp32 parameters and gradients")
                     e = tab[j]
                     e.p, e.g = p.data_ptr(), p.grad.data_ptr()
-                    e.exp_avg, e.exp_avg_sq = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
-                    e.exp_avg_diff, e.neg_pre_grad = st["exp_avg_diff"].data_ptr(), st["neg_pre_grad"].data_ptr()
+                    e.exp_avg, e.exp_avg_sq = en[0].data_ptr(), en[1].data_ptr()
+                    e.exp_avg_diff = None if en[2] is None else en[2].data_ptr()
+                    e.neg_pre_grad = None if en[3] is None else en[3].data_ptr()
                     e.n, e.bstart = p.numel(), blocks
                     blocks += lib.bnerv_adan_table_blocks(p.numel())
                 raw = bytes(tab)
@@ -173,7 +119,7 @@ class Adan(Optimizer):
                     # nothing may allocate pinned or device memory inside a capture: begin_capture() set both aside
                     host, dev_tab = self._cap_open[gi]
                     if host.numel() < len(raw):
-                        raise L.BnervError("fused Adan: the capture-time descriptor table is larger than the one begin_capture() reserved")
+                        raise L.BnervError("fused optimizer: the capture-time descriptor table is larger than the one begin_capture() reserved")
                     C.memmove(host.data_ptr(), raw, len(raw))
                 else:
                     host = torch.frombuffer(bytearray(raw), dtype=torch.uint8).pin_memory()
@@ -184,10 +130,7 @@ class Adan(Optimizer):
             if cached[5] is not None and not capturing:
                 cached[1].copy_(cached[5], non_blocking=True)      # stream-ordered before the launch below
                 cached[5] = None                                   # (inside a capture the upload waits for finish_capture(): a copy node would replay every step)
-            beta1, beta2, beta3 = group["betas"]
-            hyper = L.AdanHyper(beta1, beta2, beta3, group["eps"], group["weight_decay"], clip, int(group["no_prox"]),
-                                self._sched[gi][1].data_ptr())
-            L.check(lib.bnerv_adan_table(L.stream(), cached[1].data_ptr(), cached[2], cached[3], C.byref(hyper)), "bnerv_adan_table")
+            self._launch(lib, group, clip, self._sched[gi][1].data_ptr(), cached[1].data_ptr(), cached[2], cached[3])
 
     def begin_capture(self):
         """Before a hipGraph capture that will contain launch_step(): reserve THIS capture's descriptor tables (pinned host + device,
@@ -222,3 +165,147 @@ class Adan(Optimizer):
         self.prepare_step()
         self.launch_step(clip)
         return loss
+
+
+class Adan(_FusedTableOptimizer):
+    def __init__(self, params, lr=1e-3, betas=(0.98, 0.92, 0.99), eps=1e-8, weight_decay=0.0, max_grad_norm=0.0,
+                 no_prox=False, foreach: bool = True, fused: bool = False):
+        if not 0.0 <= max_grad_norm:
+            raise ValueError("Invalid Max grad norm: {}".format(max_grad_norm))
+        if not 0.0 <= lr:
+            raise ValueError("Invalid learning rate: {}".format(lr))
+        if not 0.0 <= eps:
+            raise ValueError("Invalid epsilon value: {}".format(eps))
+        for i in range(3):
+            if not 0.0 <= betas[i] < 1.0:
+                raise ValueError("Invalid beta parameter at index {}: {}".format(i, betas[i]))
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm, no_prox=no_prox,
+                        foreach=foreach, fused=fused)
+        super().__init__(params, defaults)
+        self._init_driver()
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for group in self.param_groups:
+            group.setdefault("no_prox", False)
+        self.__dict__.setdefault("_sched", {})
+        self.__dict__["_cap_open"] = None
+        self._invalidate()
+
+    @torch.no_grad()
+    def restart_opt(self):
+        for group in self.param_groups:
+            group["step"] = 0
+            for p in group["params"]:
+                if p.requires_grad:
+                    state = self.state[p]
+                    state["exp_avg"] = torch.zeros_like(p)
+                    state["exp_avg_sq"] = torch.zeros_like(p)
+                    state["exp_avg_diff"] = torch.zeros_like(p)
+        self._invalidate()
+
+    # ------------------------------------------------------------------------------------------------------------------
+    def _clip_coef(self):
+        if self.defaults["max_grad_norm"] <= 0:
+            return 1.0
+        # optimizer.py:136-156: global-norm clipping (a device sync, exactly as in the reference; off in every recipe)
+        device = self.param_groups[0]["params"][0].device
+        total = torch.zeros(1, device=device)
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is not None:
+                    total.add_(p.grad.pow(2).sum())
+        total = torch.sqrt(total)
+        return torch.clamp(self.defaults["max_grad_norm"] / (total + self.param_groups[-1]["eps"]), max=1.0).item()
+
+    def _sched_record(self, group):
+        beta1, beta2, beta3 = group["betas"]
+        t = group["step"]
+        return (group["lr"], 1.0 - beta1 ** t, 1.0 - beta2 ** t, math.sqrt(1.0 - beta3 ** t), 1.0 if t == 1 else 0.0)
+
+    def _ensure_state(self, p, step, clip):
+        state = self.state[p]
+        if len(state) == 0:
+            state["exp_avg"] = torch.zeros_like(p)
+            state["exp_avg_sq"] = torch.zeros_like(p)
+            state["exp_avg_diff"] = torch.zeros_like(p)
+        if "neg_pre_grad" not in state:
+            # step 1: the kernel's first_step flag substitutes -g; later first appearances follow optimizer.py:190-192
+            state["neg_pre_grad"] = torch.zeros_like(p) if step <= 1 else p.grad.clone().mul_(-clip)
+        return state
+
+    @staticmethod
+    def _entry_state(st):
+        return st["exp_avg"], st["exp_avg_sq"], st["exp_avg_diff"], st["neg_pre_grad"]
+
+    def _launch(self, lib, group, clip, sched_ptr, table_ptr, n, blocks):
+        beta1, beta2, beta3 = group["betas"]
+        hyper = L.AdanHyper(beta1, beta2, beta3, group["eps"], group["weight_decay"], clip, int(group["no_prox"]), sched_ptr)
+        L.check(lib.bnerv_adan_table(L.stream(), table_ptr, n, blocks, C.byref(hyper)), "bnerv_adan_table")
+
+
+class Adam(_FusedTableOptimizer):
+    """torch.optim.Adam with its defaults (betas 0.9 / 0.999, eps 1e-8, no weight decay, no amsgrad) as ONE fused launch per step
+    (bnerv_adam_table), with the driver interface of Adan -- so engine.TrainStep captures it, and bind_clip() finds the frame index in its
+    schedule record.  state_dict() has torch.optim.Adam's layout (per parameter 'step', 'exp_avg', 'exp_avg_sq'), so a checkpoint of the
+    reference (`--optim_type Adam`, train_nerv_all.py:250-251) resumes here and the other way round."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False):
+        if not 0.0 <= lr:
+            raise ValueError("Invalid learning rate: {}".format(lr))
+        if not 0.0 <= eps:
+            raise ValueError("Invalid epsilon value: {}".format(eps))
+        for i in range(2):
+            if not 0.0 <= betas[i] < 1.0:
+                raise ValueError("Invalid beta parameter at index {}: {}".format(i, betas[i]))
+        if weight_decay != 0 or amsgrad:
+            raise NotImplementedError("fused Adam: weight_decay / amsgrad are not on the HIP path (no recipe sets them)")
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=False, foreach=None, capturable=False,
+                        differentiable=False, fused=None)
+        super().__init__(params, defaults)
+        self._init_driver()
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self.__dict__.setdefault("_sched", {})
+        self.__dict__["_cap_open"] = None
+        self._invalidate()
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        for group in self.param_groups:                    # the step count lives in the per-parameter state of a torch.optim.Adam checkpoint
+            steps = [int(self.state[p]["step"]) for p in group["params"] if "step" in self.state.get(p, {})]
+            if steps:
+                group["step"] = max(steps)
+
+    def state_dict(self):
+        for group in self.param_groups:                    # publish the group's step count where torch.optim.Adam keeps it
+            for p in group["params"]:
+                if p in self.state and "exp_avg" in self.state[p]:
+                    self.state[p]["step"] = torch.tensor(float(group.get("step", 0)))
+        sd = super().state_dict()
+        for g in sd["param_groups"]:
+            g.pop("step", None)
+        return sd
+
+    def _sched_record(self, group):
+        beta1, beta2 = group["betas"]
+        t = group["step"]
+        return (group["lr"], 1.0 - beta1 ** t, math.sqrt(1.0 - beta2 ** t), 1.0 - beta1, 1.0 - beta2)
+
+    def _ensure_state(self, p, step, clip):
+        state = self.state[p]
+        if "exp_avg" not in state:
+            state["step"] = torch.tensor(0.0)
+            state["exp_avg"] = torch.zeros_like(p)
+            state["exp_avg_sq"] = torch.zeros_like(p)
+        return state
+
+    @staticmethod
+    def _entry_state(st):
+        return st["exp_avg"], st["exp_avg_sq"], None, None
+
+    def _launch(self, lib, group, clip, sched_ptr, table_ptr, n, blocks):
+        beta1, beta2 = group["betas"]
+        hyper = L.AdanHyper(beta1, beta2, 0.0, group["eps"], 0.0, 1.0, 0, sched_ptr)
+        L.check(lib.bnerv_adam_table(L.stream(), table_ptr, n, blocks, C.byref(hyper)), "bnerv_adam_table")

@@ -228,6 +228,9 @@ def _make_loaders(args, world):
 
 def _make_optimizer(model, args):
     if args.optim_type == "Adam":
+        if args.model == "HNeRV":              # the baseline's recipes: the fused Adam of this package (capturable; torch.optim.Adam's state_dict layout)
+            from .optimizer import Adam
+            return Adam(model.parameters(), lr=args.lr)
         return optim.Adam(model.parameters(), lr=args.lr)
     if args.optim_type == "Adan":
         from .optimizer import Adan
@@ -291,7 +294,7 @@ def train(local_rank, args):
 
     h, w = (int(x) for x in args.crop_list.split('_')[:2])
     takes_image = 'pe' not in args.embed or "HNeRV_Boost" in args.model
-    fused = args.optim_type == "Adan" and args.transform_func.identity
+    fused = hasattr(optimizer, "launch_step") and args.transform_func.identity        # Adan, and Adam for the HNeRV baseline
     step = TrainStep(model, optimizer, args.loss, takes_image, (args.batchSize, 3, h, w), device, use_graph=not args.no_graph,
                      world_size=world, clip_max_norm=args.clip_max_norm) if fused else None
     # the generic path (Adam, inpainting masks) averages its gradients over the ranks with the same flat bucket the fused step uses

@@ -265,6 +265,30 @@ typedef struct {
 size_t bnerv_conv_wgrad_ws_bytes(int B, int Cin, int Cout, int H, int W, int k);
 int bnerv_conv_wgrad(void* stream, const bnerv_wgrad_desc* d);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * 5x5 'same' convolution family of the HNeRV baseline decoder (csrc/conv5.hip; additive to ABI 9).  Replaces the F.conv2d of
+ * UpConv 'pshuffel' with ks = 5 (model_blocks.py:196-220) as built by HNeRV (model_hnerv.py:49-56, `--ks 0_1_5`), its PixelShuffle and
+ * the GELU of NeRVBlock (model_blocks.py:34-46), and autograd's backward of the three.  f32 contract on the bf16 matrix pipe (three
+ * bf16 pieces per operand, six products, f32 accumulate).  The descriptors are those of bnerv_conv_igemm / bnerv_conv_wgrad with
+ *   k = 5;  any Cin, Cout, B, H, W >= 1;
+ *   bnerv_conv5_igemm:  in_mode IN_PLAIN | IN_UNSHUFFLE (in_s 1 | 2); aux0 != NULL multiplies the gathered input element-wise by
+ *                       aux0 (same storage layout as x: the saved gelu' of the block, so du = g * gelu'(u) is never written out);
+ *                       ep_mode EP_BIAS | EP_BIAS_GELU (out2 = gelu'(u), may be NULL) | EP_PLAIN; out_s 1 | 2; transposed as documented above.
+ *                       ws: bnerv_conv5_ws_bytes(Cin, Cout) bytes of 16-byte aligned device memory (the split weight fragments of THIS
+ *                       call; written by a preparation launch, then read by the main launch).
+ *   bnerv_conv5_wgrad:  in_mode IN_PLAIN; g_mode IN_PLAIN | IN_UNSHUFFLE (g_s 1 | 2); gaux != NULL multiplies the gathered gradient by gaux
+ *                       (same layout as g); ws of bnerv_conv5_wgrad_ws_bytes() bytes; the slab sums are finished in a fixed order by a
+ *                       launch of their own (defer_finish / ctx are ignored).
+ * ------------------------------------------------------------------------------------------------------------------ */
+size_t bnerv_conv5_ws_bytes(int Cin, int Cout);
+int bnerv_conv5_igemm(void* stream, const bnerv_conv_desc* d, void* ws, size_t ws_bytes);
+size_t bnerv_conv5_wgrad_ws_bytes(int B, int Cin, int Cout, int H, int W);
+int bnerv_conv5_wgrad(void* stream, const bnerv_wgrad_desc* d);
+/* Streaming GELU around the 1x1 / 3x3 up-convs of the same decoder: y = gelu(u), gp = gelu'(u) (gp may be NULL; y may alias u), and the
+ * element-wise product out = a * b (du = g * gelu'). */
+int bnerv_gelu_fwd(void* stream, const float* u, float* y, float* gp, size_t n);
+int bnerv_mul(void* stream, const float* a, const float* b, float* out, size_t n);
+
 #define BNERV_LOSS_STATS 5
 /* ------------------------------------------------------------------------------------------------------------------
  * CEM compression path: the per-step quantise + rate term of model.cal_params(entropy_model)
@@ -440,6 +464,13 @@ typedef struct {
 } bnerv_adan_entry;
 int bnerv_adan_table_blocks(int n);
 int bnerv_adan_table(void* stream, const bnerv_adan_entry* table_dev, int n_tensors, int total_blocks, const bnerv_adan_hyper* h);
+
+/* Fused Adam, table form (additive to ABI 9): torch.optim.Adam with its defaults (no weight decay, no amsgrad), one launch over the same
+ * device table as bnerv_adan_table (exp_avg_diff / neg_pre_grad are not read).  Of `h`: beta1, beta2, eps and
+ * sched_dev = {lr, bias_correction1, sqrt(bias_correction2), 1 - beta1, 1 - beta2} in device memory (the complements rounded from float64):
+ *   m += (1 - b1)(g - m);  v = b2 v + (1 - b2) g^2;  p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps) */
+int bnerv_adam_table_blocks(int n);
+int bnerv_adam_table(void* stream, const bnerv_adan_entry* table_dev, int n_tensors, int total_blocks, const bnerv_adan_hyper* h);
 
 /* Frame fetch of a step whose clip is resident in device memory (train_nerv_all.py:329 moves one frame host -> device per step; with
  * the clip in HBM the step only needs to know WHICH frame): copies frame k = (int)sel_dev[0] of clip [N][frame_elems] to dst_img

@@ -1,11 +1,14 @@
 """Randomised shape sweep of the wide split kernels (conv_bfw / wgrad_bfw) against float64 torch references on the GPU: plain and
 PixelShuffle(2 / 3 / 5) convolutions with their data / weight / bias gradients, and the TAT block (affine prologues, gelu pair, residual,
-dGELU / dSIN epilogues with their per-channel sums).  usage: python tools/fuzz_wide.py [cases=120] [seed=0] [small]
+dGELU / dSIN epilogues with their per-channel sums).  usage: python tools/fuzz_wide.py [cases=120] [seed=0] [small | k5]
+"k5": the 5x5 family instead (csrc/conv5.hip through ops.upconv_act): stride 1 / PixelShuffle(2), with and without GELU, any width from 1 channel,
+any image size (ragged edges on both axes).
 "small": the same sweep over the shapes of the low-resolution family (convs.hip: Cin <= 32, up-conv data gradients up to 64 channels).
 (checker tool: torch fp64 is the reference here, not part of the product)"""
 import math, os, random, sys, torch
 os.environ.setdefault("BNERV_SPLIT_WIDE_MIN_TILES", "1")
 SMALL = "small" in sys.argv[3:]
+K5 = "k5" in sys.argv[3:]
 os.environ["BNERV_SMALL"] = "1" if SMALL else "0"   # wide sweep: keep small test images on the split kernels (not the low-resolution family)
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch.nn.functional as F
@@ -53,7 +56,26 @@ for it in range(N):
     H, W = rng.randint(3, 45), 4 * rng.randint(1, 40)
     g = torch.Generator(device="cpu").manual_seed(rng.randint(0, 1 << 30))
     rn = lambda *s: torch.randn(*s, generator=g).to(dev)
-    if kind == "tat":
+    if K5:
+        s, act = rng.choice([1, 2]), rng.choice(["none", "gelu"])
+        H, W = rng.randint(1, 45), rng.randint(1, 150)
+        Cin, Ct = rng.randint(1, 120), s * s * rng.randint(1, 150 // (s * s))
+        case = ("k5", B, Cin, Ct, H, W, s, act)
+        x = rn(B, Cin, H, W).requires_grad_(True)
+        w = (rn(Ct, Cin, 5, 5) / math.sqrt(25 * Cin)).requires_grad_(True)
+        b = (rn(Ct) * 0.1).requires_grad_(True)
+        out = ops.upconv_act(x, w, b, s, act)
+        cot = rn(*out.shape)
+        grads = torch.autograd.grad(out, [x, w, b], cot)
+        ld = [t.detach().double().requires_grad_(True) for t in (x, w, b)]
+        ref = F.conv2d(ld[0], ld[1], ld[2], padding=2)
+        ref = F.pixel_shuffle(ref, s) if s > 1 else ref
+        ref = F.gelu(ref) if act == "gelu" else ref
+        rgrads = torch.autograd.grad(ref, ld, cot.double())
+        bad += check("k5 fwd", out, ref, case)
+        for n_, a, r in zip(["dx", "dw", "db"], grads, rgrads):
+            bad += check(f"k5 {n_}", a, r, case)
+    elif kind == "tat":
         Cc = rng.randint(13, 32) if SMALL else rng.randint(17, 130)
         case = (kind, B, Cc, H, W, os.environ["BNERV_SPLIT_WIDE_MIN_ITEMS"])
         x0 = rn(B, Cc, H, W).requires_grad_(True)
