@@ -21,6 +21,7 @@
 #include "common.h"
 #include "sidejob.h"
 #include "conv_common.h"
+#include "launch.h"
 
 int bnerv_convbf_try(hipStream_t st, const bnerv_conv_desc& d, int vec, int ksplit, int chunks_per_split);   // convbf.hip
 namespace bnerv_conv { struct KArgs; }
@@ -667,16 +668,8 @@ int launch_fast(hipStream_t st, KArgs& ka) {
     int ncs = d.Cout >= 16 ? 16 : ((d.Cout + 3) / 4) * 4;          // multiple of 4: float4 / PixelShuffle(2) groups stay whole
     if (s2 > 4) ncs = 16;
     const size_t lds = ((size_t)NQ1 * 4 * G::PLANE + (size_t)ncs * CS + (size_t)G::T * NQ1 * NTB * 64) * sizeof(float);
-    static size_t attr_lds = 0;
-    static int blocks_per_cu = 0;
-    if (lds > attr_lds || blocks_per_cu == 0) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_fast_kernel<KS, IN, EP, NTB, NQ1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_lds = lds;
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&conv_fast_kernel<KS, IN, EP, NTB, NQ1>), 256, lds) != hipSuccess || nb < 1) nb = 1;
-        blocks_per_cu = nb > 4 ? 4 : nb;
-    }
-    int grid = 256 * blocks_per_cu;                       // everything resident: the static item partition is then balanced
+    if (const int rc = dyn_lds<&conv_fast_kernel<KS, IN, EP, NTB, NQ1>>(lds, "conv_fast")) return rc;
+    int grid = 256 * blocks_per_cu<&conv_fast_kernel<KS, IN, EP, NTB, NQ1>>(256, lds, 4);      // everything resident: the static item partition is then balanced
     if (grid > ka.total_items) grid = ka.total_items;
     SidePack side;
     bnerv_side_take(ka.d.ctx, &side, 2 * grid);
@@ -1065,13 +1058,7 @@ int launch_lean(hipStream_t st, KArgs& ka) {
     ka.magic_tiles = div_magic(ka.tiles_x * ka.tiles_y);
     ka.magic_tiles_x = div_magic(ka.tiles_x);
     const size_t lds = ((size_t)NCH * G::PLANE + (size_t)(NPRE * 256 - NSLOT) * 4 + (size_t)G::T * NQ1 * 64 + 128 + 32) * sizeof(float);
-    static int blocks_per_cu = 0;
-    if (blocks_per_cu == 0) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&conv_lean_kernel<KS, IN, EP, NQ1>), 256, lds) != hipSuccess || nb < 1) nb = 1;
-        blocks_per_cu = nb;
-    }
-    int grid = 256 * blocks_per_cu;                       // everything resident: the static item partition is then balanced
+    int grid = 256 * blocks_per_cu<&conv_lean_kernel<KS, IN, EP, NQ1>>(256, lds, 8);      // (8 = no cap: a CU holds 32 waves) everything resident: the static item partition is then balanced
     if (grid > ka.total_items) grid = ka.total_items;
     SidePack side;
     bnerv_side_take(ka.d.ctx, &side, 2 * grid);
@@ -1469,14 +1456,8 @@ int launch_lean2(hipStream_t st, KArgs& ka) {
     if ((IN == BNERV_IN_TANHGRAD || NTB == 1) && !ka.w_resident) return -1;       // caller falls back to the generic kernel
     const size_t wfl = ka.w_resident ? wres : (size_t)G::T * 4 * NTB * 64;
     const size_t lds = ((size_t)16 * G::PLANE + (size_t)(NPRE * 256 - NSLOT) * 4 + (size_t)4 * 2 * NTB * 16 + 2 * 128 + wfl) * sizeof(float);   // (dump area unused by the unshuffle path)
-    static size_t attr_lds = 0;
-    if (lds > attr_lds) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_lean2_kernel<KS, IN, EP, NTB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_lds = lds;
-    }
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&conv_lean2_kernel<KS, IN, EP, NTB>), 256, lds) != hipSuccess || nb < 1) nb = 1;
-    int grid = 256 * (nb > 4 ? 4 : nb);
+    if (const int rc = dyn_lds<&conv_lean2_kernel<KS, IN, EP, NTB>>(lds, "conv_lean2")) return rc;
+    int grid = 256 * blocks_per_cu<&conv_lean2_kernel<KS, IN, EP, NTB>>(256, lds, 4);
     if (grid > ka.total_items) grid = ka.total_items;
     SidePack side;
     bnerv_side_take(ka.d.ctx, &side, 2 * grid);
@@ -1488,8 +1469,6 @@ int launch_lean2(hipStream_t st, KArgs& ka) {
 static bool lean2_ok(const KArgs& ka) {
     const bnerv_conv_desc& d = ka.d;
     const size_t cmax = (size_t)(d.Cin > d.Cout ? d.Cin : d.Cout);
-    static const bool off = getenv("BNERV_NO_LEAN2") != nullptr;          // A/B switch for tools/kbench.py
-    if (off) return false;
     if (d.in_mode == BNERV_IN_UNSHUFFLE && (d.in_s != 2 || d.Cin % 4 != 0)) return false;
     const bool affine = d.in_mode == BNERV_IN_AFFINE || d.in_mode == BNERV_IN_GELU_AFFINE;   // (the LDS table of scale/shift holds 128 channels)
     return ka.vec && d.out_s == 1 && d.k == 3 && (d.Cin > 16 || d.Cout > 16) && (d.Cin <= 128 || !affine) && ka.ksplit == 1 &&
@@ -1533,11 +1512,7 @@ int launch_one(hipStream_t st, KArgs& ka) {
     ka.w_resident = wres <= (size_t)W_RESIDENT_MAX ? 1 : 0;
     const size_t wfl = ka.w_resident ? wres : (size_t)G::T * NQ * NTB * 64;
     const size_t lds = ((size_t)CC * G::PLANE + (size_t)16 * CS + wfl) * sizeof(float);
-    static size_t attr_lds = 0;
-    if (lds > attr_lds) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<KS, IN, EP, NTB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_lds = lds;
-    }
+    if (const int rc = dyn_lds<&conv_igemm_kernel<KS, IN, EP, NTB>>(lds, "conv_igemm")) return rc;
     const int per_cu = (int)((size_t)160 * 1024 / lds);
     int grid = 256 * (per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu));
     if (grid > ka.total_items) grid = ka.total_items;
@@ -1610,11 +1585,6 @@ SplitPlan plan_split(const bnerv_conv_desc& d) {
 extern "C" int bnerv_debug_trace_read(void* host) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_trace), sizeof(g_trace)); }
 #endif
 extern "C" int bnerv_conv_tiles(int H, int W) { return cdiv(H, TH) * cdiv(W, TW); }
-
-static int conv_vec_ok(const bnerv_conv_desc& d) {
-    auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    return ((d.W % 4 == 0) && al(d.x) && al(d.out) && al(d.out2) && al(d.aux0) && al(d.aux1) && al(d.aux2)) ? 1 : 0;
-}
 
 extern "C" int bnerv_conv_partial_rows(const bnerv_conv_desc* dp) {
     if (!dp || dp->H <= 0 || dp->W <= 0) return 0;
@@ -1726,7 +1696,6 @@ extern "C" int bnerv_conv_igemm(void* stream, const bnerv_conv_desc* dp) {
     if (d.in_mode == BNERV_IN_UNSHUFFLE && d.in_s == 1) d.in_mode = BNERV_IN_PLAIN;       // same gather, faster staging
     ka.tiles_x = cdiv(d.W, TW);
     ka.tiles_y = cdiv(d.H, TH);
-    // float4 paths need 16-B aligned rows: W % 4 == 0 and 16-B aligned base pointers (NULL counts as aligned)
     ka.vec = conv_vec_ok(d);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     ka.ksplit = 1;
@@ -1737,15 +1706,12 @@ extern "C" int bnerv_conv_igemm(void* stream, const bnerv_conv_desc* dp) {
         ka.ksplit = p.ksplit;
         ka.chunks_per_split = p.chunks_per_split;
     }
-    {
-        const char* hf = getenv("BNERV_HEAD_FWD");         // A/B switch, read per call
-        if (!(hf && hf[0] == '0') && d.k == 1 && d.in_mode == BNERV_IN_PLAIN && d.ep_mode == BNERV_EP_BIAS_TANH && d.out_s == 1 && ka.vec && !d.transposed &&
-            d.Cin == 12 && d.Cout == 3 && d.wCo == 3 && d.wCi == 12 && ((size_t)d.H * d.W) % 4 == 0 && d.B <= 65535) {
-            const int hw4 = (int)(((size_t)d.H * d.W) / 4);
-            hipLaunchKernelGGL((head1x1_fwd_kernel<3, 12>), dim3(cdiv(hw4, 256), d.B), dim3(256), 0, st, d, hw4);
-            BNERV_LAUNCH_CHECK("head1x1_fwd");
-            return BNERV_OK;
-        }
+    if (d.k == 1 && d.in_mode == BNERV_IN_PLAIN && d.ep_mode == BNERV_EP_BIAS_TANH && d.out_s == 1 && ka.vec && !d.transposed &&
+        d.Cin == 12 && d.Cout == 3 && d.wCo == 3 && d.wCi == 12 && ((size_t)d.H * d.W) % 4 == 0 && d.B <= 65535) {
+        const int hw4 = (int)(((size_t)d.H * d.W) / 4);
+        hipLaunchKernelGGL((head1x1_fwd_kernel<3, 12>), dim3(cdiv(hw4, 256), d.B), dim3(256), 0, st, d, hw4);
+        BNERV_LAUNCH_CHECK("head1x1_fwd");
+        return BNERV_OK;
     }
     if (d.k == 1 && d.in_mode == BNERV_IN_TANHGRAD && d.ep_mode == BNERV_EP_PLAIN && d.out_s == 1 && ka.vec && ka.ksplit == 1 &&
         d.Cin <= HEAD_KMAX && d.Cout <= HEAD_CMAX && ((size_t)d.H * d.W) % 4 == 0 && d.B <= 65535) {
@@ -1766,7 +1732,7 @@ extern "C" int bnerv_conv_igemm(void* stream, const bnerv_conv_desc* dp) {
         const int rs = bnerv_convs_try(st, d, ka.vec, ka.ksplit);
         if (rs != 1) return rs;
     }
-    // split-bf16 kernels (convbf.hip) next: the wide layers (with the same split-K plan: its slabs are reduced below), opt-in 12-channel ones
+    // split-bf16 kernels (convbf.hip) next: the wide layers (with the same split-K plan: its slabs are reduced below)
     int rc = bnerv_convbf_try(st, d, ka.vec, ka.ksplit, ka.chunks_per_split);
     if (rc == 1) {                                         // +1: not the split kernels' layer (negative values are real errors)
         ka.magic_tiles = ka.magic_tiles_x = 0;

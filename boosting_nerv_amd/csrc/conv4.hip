@@ -19,6 +19,7 @@
 // Tile geometry, staging (raw buffer loads prefetched under the matrix phase, prologue applied on the way into LDS), item
 // partition, epilogues and the hosted slab reductions are those of conv_lean_kernel (conv.hip).
 #include "conv4_body.h"
+#include "launch.h"
 
 namespace {
 using namespace bnerv_conv;
@@ -33,13 +34,7 @@ template <int IN, int EP>
 int launch_q4(hipStream_t st, KArgs& ka) {
     q4_prepare(ka);
     const size_t lds = q4_lds_bytes();
-    static int blocks_per_cu = 0;
-    if (blocks_per_cu == 0) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&conv_q4_kernel<IN, EP>), 256, lds) != hipSuccess || nb < 1) nb = 1;
-        blocks_per_cu = nb;
-    }
-    int grid = 256 * blocks_per_cu;                        // everything resident: the static item partition is then balanced
+    int grid = 256 * blocks_per_cu<&conv_q4_kernel<IN, EP>>(256, lds, 8);      // (8 = no cap: a CU holds 32 waves) everything resident: the static item partition is then balanced
     if (grid > ka.total_items) grid = ka.total_items;
     SidePack side;
     bnerv_side_take(ka.d.ctx, &side, 2 * grid);
@@ -56,8 +51,6 @@ extern "C" int bnerv_debug_trace4_read(void* host) { return (int)hipMemcpyFromSy
 // 1: not this family's layer (the caller goes on to the 16x16x4 kernels); BNERV_OK / negative BNERV_E_*: handled.
 int bnerv_conv4_try(hipStream_t st, bnerv_conv::KArgs& ka) {
     const bnerv_conv_desc& d = ka.d;
-    static const bool off = [] { const char* e = getenv("BNERV_Q4"); return e && e[0] == '0'; }();      // A/B switch (tools/kbench.py)
-    if (off) return 1;
     if (!q4_shape_ok(ka)) return 1;
     const int in = d.in_mode, ep = d.ep_mode;
 #define BNERV_CASE(I, E) if (in == I && ep == E) return launch_q4<I, E>(st, ka);

@@ -27,8 +27,7 @@
 //   * every block writes its share as a slab [tap][cout][cin]; wgrad5_reduce_kernel sums the slabs in a fixed order and transposes to OIHW.
 #include "common.h"
 #include "split16.h"
-#include <stdlib.h>
-#include <string.h>
+#include "launch.h"
 
 namespace {
 
@@ -37,14 +36,8 @@ constexpr int C5_TH = 8, C5_TW = 32, C5_ROWS = C5_TH + 2 * C5_PAD, C5_NP = C5_TW
 constexpr int C5_PIECE = C5_ROWS * C5_NP * 2 * 16;                                                  // bytes of one piece: 13824
 constexpr int C5_NTB = 4;                                                                           // cout tiles per block
 
-static int c5_mode() {                                     // BNERV_SPLIT_WIDE = bf16x6 (default) | bf16x3   (as the wide 3x3 kernels; no f32 5x5 kernel exists)
-    static const int v = [] {
-        const char* e = getenv("BNERV_SPLIT_WIDE");
-        if (e && !strcmp(e, "bf16x3")) return (int)SP_BF16X3;
-        return (int)SP_BF16X6;
-    }();
-    return v;
-}
+// BNERV_SPLIT_WIDE picks the arithmetic as for the wide 3x3 kernels (split_wide_mode(), launch.h); there is no f32 5x5 kernel, so "off" runs bf16x6
+static bool c5_x3() { return split_wide_mode() == SP_BF16X3; }
 
 struct C5Args {
     bnerv_conv_desc d;
@@ -465,7 +458,7 @@ extern "C" int bnerv_conv5_igemm(void* stream, const bnerv_conv_desc* d, void* w
     const size_t grid = (size_t)d->B * ka.tiles_y * ka.tiles_x * ka.ngroup;
     BNERV_REQUIRE(grid < (1ull << 31), "conv5_igemm: grid too large");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    return c5_mode() == SP_BF16X3 ? conv5_launch<SP_BF16X3>(st, ka, reinterpret_cast<u32x4*>(ws)) : conv5_launch<SP_BF16X6>(st, ka, reinterpret_cast<u32x4*>(ws));
+    return c5_x3() ? conv5_launch<SP_BF16X3>(st, ka, reinterpret_cast<u32x4*>(ws)) : conv5_launch<SP_BF16X6>(st, ka, reinterpret_cast<u32x4*>(ws));
 }
 
 extern "C" size_t bnerv_conv5_wgrad_ws_bytes(int B, int Cin, int Cout, int H, int W) {
@@ -496,7 +489,7 @@ extern "C" int bnerv_conv5_wgrad(void* stream, const bnerv_wgrad_desc* d) {
     wa.nslab = w5_nslab(d->B, d->Cin, d->Cout, d->H, d->W);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const unsigned grid = (unsigned)(wa.ncic * wa.ncog * wa.nslab);
-    if (c5_mode() == SP_BF16X3) hipLaunchKernelGGL(wgrad5_kernel<SP_BF16X3>, dim3(grid), dim3(256), 2 * W5_PIECE, st, wa);
+    if (c5_x3()) hipLaunchKernelGGL(wgrad5_kernel<SP_BF16X3>, dim3(grid), dim3(256), 2 * W5_PIECE, st, wa);
     else hipLaunchKernelGGL(wgrad5_kernel<SP_BF16X6>, dim3(grid), dim3(256), 3 * W5_PIECE, st, wa);
     BNERV_LAUNCH_CHECK("wgrad5");
     const int n = C5_T * d->Cout * d->Cin + d->Cout;

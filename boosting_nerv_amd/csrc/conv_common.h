@@ -60,7 +60,7 @@ __device__ __forceinline__ f32x4 bload(__amdgpu_buffer_rsrc_t r, unsigned voff, 
 }
 __device__ __forceinline__ void bstore(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, f32x4 v) {
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v), r, (int)voff, (int)soff, 0);
-    // Measured on gfx950 (tools/klean2.py, ROCm 7.2): a VALU write of the store's data VGPRs two instructions after a 128-bit
+    // Measured on gfx950 (ROCm 7.2): a VALU write of the store's data VGPRs two instructions after a 128-bit
     // buffer store WITH AN SGPR soffset corrupts lanes 12..15 of every row of 16 (the store reads its upper data late).  LLVM's
     // hazard recognizer pads this case only when soffset is not a register, so the wait states are inserted here, fenced so that
     // the scheduler cannot move a VALU instruction in between.

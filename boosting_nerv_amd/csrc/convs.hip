@@ -16,6 +16,7 @@
 // Scope: k = 3, Cin <= 32 (64 for the unshuffle(2) prologue: the data gradient of a PixelShuffle(2) up-conv), any Cout (16 per block),
 // H * W <= 16384 (65536 for the up-convs and their data gradients), float4-aligned rows.
 #include "convs_body.h"
+#include "launch.h"
 
 namespace {
 using namespace bnerv_conv;
@@ -36,11 +37,7 @@ template <int IN, int EP>
 int launch_small96(hipStream_t st, const SArgs& sa) {
     const bnerv_conv_desc& d = sa.d;
     const size_t lds = convs_lds_bytes<24>();
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_small96_kernel<IN, EP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
+    if (const int rc = dyn_lds<&conv_small96_kernel<IN, EP>>(lds, "conv_small96")) return rc;
     hipLaunchKernelGGL((conv_small96_kernel<IN, EP>), dim3(sa.tiles_x * sa.tiles_y, cdiv(d.Cout, 16), d.B), dim3(256), lds, st, sa);
     BNERV_LAUNCH_CHECK("conv_small96");
     return BNERV_OK;
@@ -52,8 +49,7 @@ constexpr bool small96_combo() {
            (IN == BNERV_IN_PLAIN && (EP == BNERV_EP_DGELU_SAVED || EP == BNERV_EP_DSIN));
 }
 static bool small96_shape(const bnerv_conv_desc& d) {
-    static const bool off = [] { const char* e = getenv("BNERV_SMALL96"); return e && e[0] == '0'; }();     // A/B switch
-    if (off || d.in_mode == BNERV_IN_UNSHUFFLE || d.Cin <= 32 || d.Cin > 96 || d.out_s != 1 || d.in_s != 1 || (size_t)d.H * d.W > 1024) return false;
+    if (d.in_mode == BNERV_IN_UNSHUFFLE || d.Cin <= 32 || d.Cin > 96 || d.out_s != 1 || d.in_s != 1 || (size_t)d.H * d.W > 1024) return false;
     const int i = d.in_mode, e = d.ep_mode;
     return (i == BNERV_IN_AFFINE && (e == BNERV_EP_BIAS_GELU || e == BNERV_EP_BIAS_RES)) || (i == BNERV_IN_PLAIN && (e == BNERV_EP_DGELU_SAVED || e == BNERV_EP_DSIN));
 }
@@ -62,11 +58,7 @@ template <int IN, int EP, int NQ>
 int launch_small(hipStream_t st, const SArgs& sa) {
     const bnerv_conv_desc& d = sa.d;
     const size_t lds = convs_lds_bytes<NQ>();
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_small_kernel<IN, EP, NQ>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
+    if (const int rc = dyn_lds<&conv_small_kernel<IN, EP, NQ>>(lds, "conv_small")) return rc;
     hipLaunchKernelGGL((conv_small_kernel<IN, EP, NQ>), dim3(sa.tiles_x * sa.tiles_y, cdiv(d.Cout, 16), d.B), dim3(256), lds, st, sa);
     BNERV_LAUNCH_CHECK("conv_small");
     return BNERV_OK;
@@ -85,12 +77,11 @@ int launch_small_nq(hipStream_t st, const SArgs& sa) {
 
 // shapes of this family: small images whose 8x32 tiling leaves the chip idle (the threshold keeps 180x320 and above on the persistent kernels)
 bool bnerv_convs_shape_ok(const bnerv_conv_desc& d, int vec) {
-    { const char* e = getenv("BNERV_SMALL"); if (e && e[0] == '0') return false; }      // A/B switch, read per call (tests reach the other families with it)
+    if (switch_off("BNERV_SMALL")) return false;           // read per call (tests reach the other families with it)
     // small images; an up-conv (several cout groups per tile) pays up to 180x320, where the persistent split kernel still runs one tile per block
     const bool uns = d.in_mode == BNERV_IN_UNSHUFFLE;          // the data gradient of a PixelShuffle(2) up-conv: its input is the shuffled gradient
-    static const size_t px_up = [] { const char* e = getenv("BNERV_SMALL_MAXPX_UP"); return e ? (size_t)atol(e) : (size_t)65536; }();     // (A/B switches)
-    static const size_t px_uns = [] { const char* e = getenv("BNERV_SMALL_MAXPX_UNS"); return e ? (size_t)atol(e) : (size_t)65536; }();
-    const size_t max_px = uns ? px_uns : (d.out_s == 2 && d.Cout >= 32) ? px_up : 16384;
+    constexpr size_t MAXPX_UP = 65536, MAXPX_UNS = 65536;
+    const size_t max_px = uns ? MAXPX_UNS : (d.out_s == 2 && d.Cout >= 32) ? MAXPX_UP : 16384;
     // (33..96 input channels on an image of <= 1024 pixels: the 96-channel staging of conv_small96_kernel -- round 5 ran HNeRV-boost's
     //  95 -> 95 TAT convs at 9 x 16 on the generic kernel's 12 blocks: 47-53 us per launch for 0.2 GFLOP)
     const int cin_max = uns ? 64 : (small96_shape(d) ? 96 : 32);

@@ -5,6 +5,7 @@
 // work; what matters is launching ALL of one depth in one kernel (grouped descriptors) instead of ~70 tiny launches.
 #include "common.h"
 #include "sidejob.h"
+#include "launch.h"
 
 namespace {
 
@@ -519,15 +520,14 @@ extern "C" int bnerv_time_branch_fwd(void* stream, const bnerv_time_branch_desc*
     BNERV_REQUIRE(d.pos && d.bases && d.pe && d.sw0 && d.sy0 && d.saux0 && d.tw0 && d.tw1 && d.ty0 && d.taux0 && d.ty1 && d.taux1, "time_branch_fwd: null tensor");
     BNERV_REQUIRE(d.B > 0 && d.L > 0 && d.SH > 0 && d.TH > 0 && d.TO > 0 && d.n_mlp >= 0, "time_branch_fwd: bad shape");
     if (d.B > TB_MAXB || 2 * d.L > TB_MAXI || d.SH > 4096 || d.TH > TB_MAXT || d.TO > TB_MAXO || d.n_mlp > BNERV_MAX_DENSE_GROUPS) return 1;
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-    if ((2 * d.L) % 4 || d.TH % 4 || d.TO % 4 || !al16(d.tw0) || !al16(d.tw1)) return 1;                 // 16-byte staging of the chain's weights
+    if ((2 * d.L) % 4 || d.TH % 4 || d.TO % 4 || !aligned16(d.tw0, d.tw1)) return 1;                 // 16-byte staging of the chain's weights
     TBArgs a;
     a.d = d;
     a.cmax = 4;
     for (int i = 0; i < d.n_mlp; ++i) {
         BNERV_REQUIRE(mlps[i].w1 && mlps[i].w2 && mlps[i].hs && mlps[i].out && mlps[i].C > 0, "time_branch_fwd: bad modulation MLP %d", i);
         if (((mlps[i].C + 3) & ~3) > a.cmax) a.cmax = (mlps[i].C + 3) & ~3;
-        if (mlps[i].C > TB_MAXC || !al16(mlps[i].w1) || !al16(mlps[i].w2)) return 1;
+        if (mlps[i].C > TB_MAXC || !aligned16(mlps[i].w1, mlps[i].w2)) return 1;
         a.m[i].w1 = mlps[i].w1; a.m[i].b1 = mlps[i].b1; a.m[i].w2 = mlps[i].w2; a.m[i].b2 = mlps[i].b2; a.m[i].hs = mlps[i].hs; a.m[i].out = mlps[i].out;
         a.m[i].C = mlps[i].C; a.m[i]._pad = 0;
     }
@@ -537,11 +537,7 @@ extern "C" int bnerv_time_branch_fwd(void* stream, const bnerv_time_branch_desc*
     a.nb_chain = d.n_mlp > 0 ? cdiv(d.n_mlp, a.mlps_per_block) : 1;
     const size_t lds = ((size_t)d.TH * 2 * d.L + (size_t)d.TO * d.TH + (size_t)a.mlps_per_block * ((size_t)d.TO * d.TO + (size_t)a.cmax * d.TO)) * sizeof(float);
     if (lds > 100 * 1024) return 1;
-    static size_t attr_lds = 0;
-    if (lds > attr_lds) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&time_branch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_lds = lds;
-    }
+    if (const int rc = dyn_lds<&time_branch_kernel>(lds, "time_branch")) return rc;
     hipLaunchKernelGGL(time_branch_kernel, dim3(a.nb_stem + a.nb_chain), dim3(TB_NT), lds, (hipStream_t)stream, a);
     BNERV_LAUNCH_CHECK("time_branch");
     return BNERV_OK;

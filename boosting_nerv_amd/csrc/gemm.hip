@@ -11,6 +11,7 @@
 //      hidden activations never leave registers: the D fragments of GEMM 1 (4 consecutive hidden units of one pixel per lane)
 //      ARE the B fragments of GEMM 2 once its K index is walked in the order (hidden tile, register) -- no shuffle, no LDS.
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -384,13 +385,9 @@ int launch_mlp_nt(hipStream_t st, const MlpArgs& a, bool bwd) {
     int grid = cdiv(total, 4);
     const int cap = 256 * (lds > 80 * 1024 ? 1 : 2);
     if (grid > cap) grid = cap;
-    if (bwd) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cnx_mlp_bwd_kernel<C, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((cnx_mlp_bwd_kernel<C, NT>), dim3(grid), dim3(256), lds, st, a);
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cnx_mlp_fwd_kernel<C, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((cnx_mlp_fwd_kernel<C, NT>), dim3(grid), dim3(256), lds, st, a);
-    }
+    if (const int rc = bwd ? dyn_lds<&cnx_mlp_bwd_kernel<C, NT>>(lds, "cnx_mlp_bwd") : dyn_lds<&cnx_mlp_fwd_kernel<C, NT>>(lds, "cnx_mlp_fwd")) return rc;
+    if (bwd) hipLaunchKernelGGL((cnx_mlp_bwd_kernel<C, NT>), dim3(grid), dim3(256), lds, st, a);
+    else hipLaunchKernelGGL((cnx_mlp_fwd_kernel<C, NT>), dim3(grid), dim3(256), lds, st, a);
     BNERV_LAUNCH_CHECK(bwd ? "cnx_mlp_bwd" : "cnx_mlp_fwd");
     return BNERV_OK;
 }
@@ -398,8 +395,8 @@ int launch_mlp_nt(hipStream_t st, const MlpArgs& a, bool bwd) {
 template <int C>
 int launch_mlp(hipStream_t st, const MlpArgs& a, bool bwd) {
     // one 16-pixel tile per wave while that still leaves every wave at most one item (1024 wave slots at one block per CU)
-    static const int nt1_max = [] { const char* e = getenv("BNERV_CNX_NT1_MAX"); return e ? atoi(e) : 16384; }();     // (A/B switch: pixels)
-    if ((long)a.B * a.HW <= nt1_max) return launch_mlp_nt<C, 1>(st, a, bwd);
+    constexpr long NT1_MAX_PX = 16384;
+    if ((long)a.B * a.HW <= NT1_MAX_PX) return launch_mlp_nt<C, 1>(st, a, bwd);
     return launch_mlp_nt<C, 2>(st, a, bwd);
 }
 

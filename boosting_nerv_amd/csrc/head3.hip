@@ -13,6 +13,7 @@
 //                  weights (the same table) x 4 pixels and one 16-byte store.
 // Both are exact fp32 (fma chains in a fixed order).  The weight gradient of the same layer runs with swapped roles (ops._HeadTanh.backward).
 #include "conv_common.h"
+#include "launch.h"
 
 namespace {
 using namespace bnerv_conv;
@@ -191,10 +192,8 @@ __global__ __launch_bounds__(256) void head3x3_dgrad_kernel(const H3Args a) {
 }
 
 static bool h3_common(const bnerv_conv_desc& d) {
-    static const bool off = [] { const char* e = getenv("BNERV_HEAD3"); return e && e[0] == '0'; }();       // A/B switch
-    if (off || d.k != 3 || d.out_s != 1 || d.in_s > 1 || (d.W & 3) || d.B > 65535) return false;
-    auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    return al(d.x) && al(d.out) && al(d.aux0) && (size_t)d.H * d.W >= 4096 && d.Cin <= H3_MAXC && d.Cout <= H3_MAXC;
+    if (d.k != 3 || d.out_s != 1 || d.in_s > 1 || (d.W & 3) || d.B > 65535) return false;
+    return aligned16(d.x, d.out, d.aux0) && (size_t)d.H * d.W >= 4096 && d.Cin <= H3_MAXC && d.Cout <= H3_MAXC;
 }
 
 }  // namespace

@@ -20,6 +20,7 @@
 //
 // MS-SSIM follows pytorch_msssim 0.2.1 (third-party; PARITY UNPINNED).
 #include "common.h"
+#include "launch.h"
 #include <vector>
 #include <math.h>
 #include <string.h>
@@ -1096,8 +1097,7 @@ static WsLayout make_layout(int B, int C, int H, int W, bool use_ms, bool use_ff
 }
 
 static bool loss_fused() {                              // BNERV_LOSS_FUSED=0: the level-by-level MS-SSIM launches (A/B switch, read per call: tests compare the forms)
-    const char* e = getenv("BNERV_LOSS_FUSED");
-    return !(e && e[0] == '0');
+    return !switch_off("BNERV_LOSS_FUSED");
 }
 static bool even_pyramid(const WsLayout& L) {         // every pooled level has even sides: no padding anywhere, aligned 2x2 cells
     if (!loss_fused()) return false;
@@ -1105,7 +1105,7 @@ static bool even_pyramid(const WsLayout& L) {         // every pooled level has 
     return true;
 }
 static bool adj_late() {                                // BNERV_LOSS_ADJ=late: round 4's order -- the adjoint row pass as the LAST launch, accumulating
-    const char* e = getenv("BNERV_LOSS_ADJ");           // onto the finished SSIM gradient (A/B switch, read per call; the gradient differs in the last bit:
+    const char* e = switch_str("BNERV_LOSS_ADJ");       // onto the finished SSIM gradient (A/B switch, read per call; the gradient differs in the last bit:
     return e && !strcmp(e, "late");                     // fma(k, r, d) there, d + k r here)
 }
 // the 2x2 means of an ODD pyramid, level by level (zero padding where a side is odd, count_include_pad)
@@ -1123,8 +1123,7 @@ static int launch_pools(hipStream_t st, const float* X, const float* Y, float* w
 }
 
 static bool loss_merged() {                             // BNERV_LOSS_MERGED=0: every launch of the even-pyramid form on its own (A/B switch, read per call)
-    const char* e = getenv("BNERV_LOSS_MERGED");
-    return !(e && e[0] == '0');
+    return !switch_off("BNERV_LOSS_MERGED");
 }
 
 // arguments of the even-pyramid forward launches (pyramid, every level's statistics, coefficients)
@@ -1193,8 +1192,7 @@ static int run_ms_forward(hipStream_t st, const float* X, const float* Y, float*
         // odd pyramid (1080 -> 540 -> 270 -> 135 -> 68: the 1080p configs): the padded 2x2 means level by level, then EVERY level's statistics in
         // ONE launch (the levels only depend on the pyramid; the same body per tile as the level-by-level launches, so the same bits) and the
         // coefficients: 6 launches instead of 10.  BNERV_LOSS_FUSED=0 keeps the level-by-level form.
-        const char* e = getenv("BNERV_LOSS_FUSED");
-        if (!(e && e[0] == '0')) {
+        if (loss_fused()) {
             PyrArgs pa{}; SsimAllArgs sa{}; CoefArgs ca{};
             int rc = fill_even_forward(X, Y, ws, L, BC, chain, want_g, pa, sa, ca);
             if (rc) return rc;
@@ -1332,14 +1330,14 @@ extern "C" int bnerv_loss_fwd_bwd(void* stream, const bnerv_loss_desc* dp) {
         if (rc) return rc;
         ha.f = a; ha.pred = d.pred; ha.target = d.target; ha.stats_part = ws + L.stats_part; ha.nps = nps;
         ha.n_fft = nrowblk; ha.pyr_gx = cdiv(L.pyr.W[1], 16); ha.pyr_gy = cdiv(L.pyr.H[1], 16); ha.n_pyr = even ? ha.pyr_gx * ha.pyr_gy * 2 * BC : 0;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&loss_head_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_row);
+        if (const int rc_lds = dyn_lds<&loss_head_kernel>(lds_row, "loss_head")) return rc_lds;
         hipLaunchKernelGGL(loss_head_kernel, dim3(ha.n_fft + ha.n_pyr + NSB * d.B), dim3(256), lds_row, st, ha);
         BNERV_LAUNCH_CHECK("loss_head");
         if (!even) { rc = launch_pools(st, d.pred, d.target, ws, L, BC); if (rc) return rc; }
         hipLaunchKernelGGL(ssim_fwd_all_kernel, dim3(sf.first[LV], BC), dim3(256), 0, st, sf);
         BNERV_LAUNCH_CHECK("ssim_fwd_all");
         ma.f = a; ma.ncolblk = L.ncolblk; ma.n_cols = L.ncolblk * BC;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&loss_mid_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_col);
+        if (const int rc_lds = dyn_lds<&loss_mid_kernel>(lds_col, "loss_mid")) return rc_lds;
         hipLaunchKernelGGL(loss_mid_kernel, dim3(ma.n_cols + BC), dim3(256), lds_col, st, ma);
         BNERV_LAUNCH_CHECK("loss_mid");
         SsimAllArgs sb{};
@@ -1351,7 +1349,7 @@ extern "C" int bnerv_loss_fwd_bwd(void* stream, const bnerv_loss_desc* dp) {
             LossCoarseArgs ca{};
             ca.f = a; ca.f.accumulate = 0; ca.s = sb; ca.n_adj = nrowblk; ca.gx = sb.first[LV]; ca.BC = BC;
             const size_t lds_c = lds_row > SSIM_BWD_LDS * sizeof(float) ? lds_row : SSIM_BWD_LDS * sizeof(float);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&loss_coarse_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
+            if (const int rc_lds = dyn_lds<&loss_coarse_kernel>(lds_c, "loss_coarse")) return rc_lds;
             hipLaunchKernelGGL(loss_coarse_kernel, dim3(ca.n_adj + ca.gx * BC), dim3(256), lds_c, st, ca);
             BNERV_LAUNCH_CHECK("loss_coarse");
         }
@@ -1359,7 +1357,7 @@ extern "C" int bnerv_loss_fwd_bwd(void* stream, const bnerv_loss_desc* dp) {
         hipLaunchKernelGGL(loss_tail_kernel, dim3(ta.n0 + 1), dim3(256), 0, st, ta);
         BNERV_LAUNCH_CHECK("loss_tail");
         if (late) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fft_rows_adj_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_row);
+            if (const int rc_lds = dyn_lds<&fft_rows_adj_kernel>(lds_row, "fft_rows_adj")) return rc_lds;
             hipLaunchKernelGGL(fft_rows_adj_kernel, dim3(nrowblk), dim3(256), lds_row, st, a);
             BNERV_LAUNCH_CHECK("fft_rows_adj");
         }
@@ -1373,9 +1371,9 @@ extern "C" int bnerv_loss_fwd_bwd(void* stream, const bnerv_loss_desc* dp) {
     if (rc) return rc;
     auto run_fft = [&](int accumulate) -> int {
         FftArgs fa = a; fa.accumulate = accumulate;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fft_rows_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_row);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fft_rows_adj_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_row);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fft_cols_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_col);
+        if (const int rc_lds = dyn_lds<&fft_rows_fwd_kernel>(lds_row, "fft_rows_fwd")) return rc_lds;
+        if (const int rc_lds = dyn_lds<&fft_rows_adj_kernel>(lds_row, "fft_rows_adj")) return rc_lds;
+        if (const int rc_lds = dyn_lds<&fft_cols_kernel>(lds_col, "fft_cols")) return rc_lds;
         hipLaunchKernelGGL(fft_rows_fwd_kernel, dim3(nrowblk), dim3(256), lds_row, st, fa);
         BNERV_LAUNCH_CHECK("fft_rows_fwd");
         hipLaunchKernelGGL(fft_cols_kernel, dim3(L.ncolblk, BC), dim3(256), lds_col, st, fa);

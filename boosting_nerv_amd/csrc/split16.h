@@ -3,34 +3,22 @@
 #include "common.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-enum { SP_BF16X6 = 0, SP_BF16X3 = 1, SP_F16X3 = 2 };
+enum { SP_BF16X6 = 0, SP_BF16X3 = 1 };
 template <int SP> struct Split {
     static constexpr int NS = (SP == SP_BF16X6) ? 3 : 2;
-    static constexpr bool SCALED = (SP == SP_F16X3);
 };
 
 template <int SP>
 __device__ __forceinline__ unsigned pk16(float a, float b) {
-    if constexpr (SP == SP_F16X3) {
-        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, h2));
-    } else {
-        typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, b2));
-    }
+    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, b2));
 }
 template <int SP>
 __device__ __forceinline__ f32x2 unpk16(unsigned pk) {
-    if constexpr (SP == SP_F16X3) {
-        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-        return __builtin_convertvector(__builtin_bit_cast(h2, pk), f32x2);
-    } else {
-        return f32x2{__builtin_bit_cast(float, pk << 16), __builtin_bit_cast(float, pk & 0xffff0000u)};
-    }
+    return f32x2{__builtin_bit_cast(float, pk << 16), __builtin_bit_cast(float, pk & 0xffff0000u)};
 }
 // NE (<= 8, even) floats -> NS packed 8-element pieces, round to nearest even at every level (the residuals are exact in f32);
 // elements NE..7 of every piece are zero
@@ -57,6 +45,5 @@ __device__ __forceinline__ void split8(const float (&x)[8], u32x4 (&out)[Split<S
 
 template <int SP>
 __device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
-    if constexpr (SP == SP_F16X3) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }

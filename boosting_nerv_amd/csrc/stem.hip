@@ -14,7 +14,7 @@
 // Both read the gradient through the pixel-unshuffle gather (g stored shuffled by s in {1, 2, 3, 5}) with 4-byte loads -- the image
 // is tiny, the loads are few.  v_mfma_f32_16x16x4_f32, exact f32 products like every f32 kernel of this build.
 #include "common.h"
-#include <stdlib.h>
+#include "launch.h"
 
 namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -233,28 +233,28 @@ __global__ __launch_bounds__(256) void stem_pair_kernel(const WTArgs wa, const D
     else dgrad_tiny_body<NTN>(da, b - n_w);
 }
 
-bool stem_switch() {                                      // BNERV_STEM=0: the tiled kernels (A/B switch, read per call)
-    const char* e = getenv("BNERV_STEM");
-    return !(e && e[0] == '0');
-}
 bool tiny_s_ok(int s, int C) { return (s == 1 || s == 2 || s == 3 || s == 5) && C % (s * s) == 0; }
+// dynamic LDS of the two bodies (the paired launch needs the larger)
+size_t wgrad_tiny_lds_bytes(int Cin, int H, int W) {
+    const int PL = (H + 2) * (W + 2), HW = H * W, HWp = (HW + 3) & ~3;
+    return ((size_t)((Cin * PL + 3) & ~3) + 16 * (size_t)row_stride4(HW) + 2 * HWp) * sizeof(float);
+}
+size_t dgrad_tiny_lds_bytes(int Cout, int H, int W) {
+    const int PL = (H + 2) * (W + 2), NW = Cout * 9, MT = cdiv(H * W, 16);
+    return ((size_t)((DT_CS * PL + 3) & ~3) + (size_t)((DT_CS * NW + 3) & ~3) + 2 * MT * 16) * sizeof(float);
+}
 
 }  // namespace
 
 // ---- weight gradient.  1: not this kernel's layer; BNERV_OK: dw / db written (nothing deferred, no workspace used)
 int bnerv_stem_wgrad_try(hipStream_t st, const bnerv_wgrad_desc& d) {
-    if (!stem_switch() || d.k != 3 || d.in_mode != BNERV_IN_PLAIN || d.g_mode == BNERV_IN_TANHGRAD) return 1;
+    if (d.k != 3 || d.in_mode != BNERV_IN_PLAIN || d.g_mode == BNERV_IN_TANHGRAD) return 1;
     if ((size_t)d.H * d.W > TINY_MAX_PX || !tiny_s_ok(d.g_s, d.Cout)) return 1;
     const int PL = (d.H + 2) * (d.W + 2);
     if ((size_t)d.Cin * PL > WT_MAX_XFLOATS || d.Cout < 64) return 1;          // (few output channels: the tiled kernels' split over pixels is as good)
     if ((size_t)d.B * (d.Cin > d.Cout ? d.Cin : d.Cout) * d.H * d.W >= (size_t)1 << 30) return 1;
-    const int HW = d.H * d.W, HWp = (HW + 3) & ~3;
-    const size_t lds = ((size_t)((d.Cin * PL + 3) & ~3) + 16 * (size_t)row_stride4(HW) + 2 * HWp) * sizeof(float);
-    static size_t attr_lds = 0;
-    if (lds > attr_lds) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_tiny_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_lds = lds;
-    }
+    const size_t lds = wgrad_tiny_lds_bytes(d.Cin, d.H, d.W);
+    if (const int rc = dyn_lds<&wgrad_tiny_kernel>(lds, "wgrad_tiny")) return rc;
     WTArgs a{d.x, d.g, d.dw, d.db, d.B, d.Cin, d.Cout, d.H, d.W, d.g_s};
     const int nt = cdiv(d.Cin * 9, 16);
     hipLaunchKernelGGL(wgrad_tiny_kernel, dim3(cdiv(d.Cout, 16), cdiv(nt, WT_NTG)), dim3(256), lds, st, a);
@@ -273,13 +273,12 @@ static bool stem_dgrad_shape(const bnerv_conv_desc& d) {
     return (size_t)d.B * d.Cin * d.H * d.W < (size_t)1 << 30;
 }
 size_t bnerv_stem_dgrad_ws_bytes(const bnerv_conv_desc& d) {
-    if (!stem_switch() || !stem_dgrad_shape(d)) return 0;
+    if (!stem_dgrad_shape(d)) return 0;
     return (size_t)cdiv(d.Cin, DT_CS) * d.B * d.Cout * d.H * d.W * sizeof(float);
 }
 int bnerv_stem_dgrad_try(hipStream_t st, const bnerv_conv_desc& d) {
-    if (!stem_switch() || !stem_dgrad_shape(d) || !d.partial) return 1;
-    const int PL = (d.H + 2) * (d.W + 2), NW = d.Cout * 9, MT = cdiv(d.H * d.W, 16);
-    const size_t lds = ((size_t)((DT_CS * PL + 3) & ~3) + (size_t)((DT_CS * NW + 3) & ~3) + 2 * MT * 16) * sizeof(float);
+    if (!stem_dgrad_shape(d) || !d.partial) return 1;
+    const size_t lds = dgrad_tiny_lds_bytes(d.Cout, d.H, d.W);
     DTArgs a{d.x, d.w, d.partial, d.B, d.Cin, d.Cout, d.H, d.W, d.in_mode == BNERV_IN_UNSHUFFLE ? d.in_s : 1};
     const int nblk = cdiv(d.Cin, DT_CS);
     if (d.Cout <= 32) hipLaunchKernelGGL(dgrad_tiny_kernel<2>, dim3(nblk), dim3(256), lds, st, a);
@@ -291,8 +290,7 @@ int bnerv_stem_dgrad_try(hipStream_t st, const bnerv_conv_desc& d) {
 // ---- both at once (bnerv_conv_wgrad_pair, form 0).  1: not this pair; BNERV_OK: dw / db written, dx's slabs in c.partial and *n_slabs > 0
 // slabs of c.B * c.Cout * c.H * c.W floats for the caller to reduce into c.out (deferred or at once).
 int bnerv_stem_pair_try(hipStream_t st, const bnerv_conv_desc& c, const bnerv_wgrad_desc& d, int* n_slabs) {
-    { const char* e = getenv("BNERV_PAIR_STEM"); if (e && e[0] == '0') return 1; }      // A/B switch, read per call
-    if (!stem_switch() || !stem_dgrad_shape(c) || !c.partial) return 1;
+    if (!stem_dgrad_shape(c) || !c.partial) return 1;
     if (d.k != 3 || d.in_mode != BNERV_IN_PLAIN || d.g_mode == BNERV_IN_TANHGRAD) return 1;
     if ((size_t)d.H * d.W > TINY_MAX_PX || !tiny_s_ok(d.g_s, d.Cout)) return 1;
     const int PL = (d.H + 2) * (d.W + 2);
@@ -300,19 +298,10 @@ int bnerv_stem_pair_try(hipStream_t st, const bnerv_conv_desc& c, const bnerv_wg
     if ((size_t)d.B * (d.Cin > d.Cout ? d.Cin : d.Cout) * d.H * d.W >= (size_t)1 << 30) return 1;
     const int cs = c.in_mode == BNERV_IN_UNSHUFFLE ? c.in_s : 1;
     if (!(c.x == d.g && c.Cin == d.Cout && c.Cout == d.Cin && c.B == d.B && c.H == d.H && c.W == d.W && cs == d.g_s)) return 1;   // one layer, one gradient
-    const int HW = d.H * d.W, HWp = (HW + 3) & ~3;
-    const size_t lds_w = ((size_t)((d.Cin * PL + 3) & ~3) + 16 * (size_t)row_stride4(HW) + 2 * HWp) * sizeof(float);
-    const int NW = c.Cout * 9, MT = cdiv(HW, 16);
-    const size_t lds_d = ((size_t)((DT_CS * PL + 3) & ~3) + (size_t)((DT_CS * NW + 3) & ~3) + 2 * MT * 16) * sizeof(float);
+    const size_t lds_w = wgrad_tiny_lds_bytes(d.Cin, d.H, d.W), lds_d = dgrad_tiny_lds_bytes(c.Cout, c.H, c.W);
     const size_t lds = lds_w > lds_d ? lds_w : lds_d;
-    static size_t attr2 = 0, attr6 = 0;
     const bool small = c.Cout <= 32;
-    size_t& attr = small ? attr2 : attr6;
-    if (lds > attr) {
-        if (small) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_pair_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        else (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_pair_kernel<6>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = lds;
-    }
+    if (const int rc = small ? dyn_lds<&stem_pair_kernel<2>>(lds, "stem_pair") : dyn_lds<&stem_pair_kernel<6>>(lds, "stem_pair")) return rc;
     WTArgs wa{d.x, d.g, d.dw, d.db, d.B, d.Cin, d.Cout, d.H, d.W, d.g_s};
     DTArgs da{c.x, c.w, c.partial, c.B, c.Cin, c.Cout, c.H, c.W, cs};
     const int wx = cdiv(d.Cout, 16), wy = cdiv(cdiv(d.Cin * 9, 16), WT_NTG), n_w = wx * wy, n_d = cdiv(c.Cin, DT_CS);

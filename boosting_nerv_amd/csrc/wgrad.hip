@@ -33,9 +33,8 @@ int bnerv_stem_wgrad_try(hipStream_t st, const bnerv_wgrad_desc& d);   // stem.h
 int bnerv_stem_pair_try(hipStream_t st, const bnerv_conv_desc& c, const bnerv_wgrad_desc& d, int* n_slabs);   // stem.hip: the stem stage's (dW | d input) as one launch
 int bnerv_wgrad1x1_slabs(const bnerv_wgrad_desc& d);                                   // wgrad1.hip: pointwise (k = 1) layers as a plain GEMM over the pixels
 int bnerv_wgrad1x1_try(hipStream_t st, const bnerv_wgrad_desc& d, int* n_slabs);
-#include <stdlib.h>
+#include "launch.h"
 #include <type_traits>
-#include <string.h>
 
 namespace {
 using namespace bnerv_wb;
@@ -817,6 +816,15 @@ int launch_wlean_modes(hipStream_t st, const WArgs& wa) {
 // (38 ch: 3x6 -> 4 groups of 96 for 343 columns; 46 ch: 3x7 -> 4 groups of 112 for 415), within the 256-VGPR budget.
 // GM2: 0 = g as is, 1 = g is the pixel-shuffled (x2) gradient (two float4 per cout PAIR), 2 = tanh-grad (g, gaux),
 //      3 = pixel-shuffled by g_s (3, 5): one dword per pixel, g_s apart
+// dynamic LDS of the body: gradient rows + input planes while it accumulates, never less than the rows the A reads and the reduction touch
+template <int MTW, int NTW>
+size_t wgrad_wide_lds_bytes(int Cout) {
+    const int g_rows = Cout < MTW * 16 ? Cout : MTW * 16;
+    size_t fl = (size_t)g_rows * CSG + (size_t)(wgrad_npl<3, NTW>() + 2) * Geo<3>::PLANE + 64;
+    if (fl < (size_t)MTW * 16 * CSG) fl = (size_t)MTW * 16 * CSG;
+    if (fl < (size_t)MTW * 16 * NTW * 16) fl = (size_t)MTW * 16 * NTW * 16;
+    return fl * sizeof(float);
+}
 template <int IN, int GM2, int MTW, int NTW>
 __device__ __forceinline__ void wgrad_wide_body(const WArgs& wa, const int slots, const SidePack& side, const int vb, const int vgrid) {
     // (vb of vgrid: this launch's block index / size, or the weight-gradient part of a paired launch)
@@ -1144,8 +1152,7 @@ __global__ __launch_bounds__(256, (MTW * NTW <= 8 ? 3 : 2)) void wgrad_wide_kern
 
 static bool wide_ok(const WArgs& wa) {
     const bnerv_wgrad_desc& d = wa.d;
-    static const bool off = getenv("BNERV_NO_WIDE") != nullptr;            // A/B switch for tools/kwide.py
-    if (off || !wa.vec || d.k != 3) return false;
+    if (!wa.vec || d.k != 3) return false;
     if (d.g_s > 2 && (d.g_mode != BNERV_IN_UNSHUFFLE || d.in_mode != BNERV_IN_PLAIN || d.Cout % (d.g_s * d.g_s) != 0 || d.Cout <= 16)) return false;
     if (d.g_s == 2 && (d.g_mode != BNERV_IN_UNSHUFFLE || d.in_mode != BNERV_IN_PLAIN || d.Cout % 4 != 0 || d.Cout <= 16)) return false;
     if (d.in_mode != BNERV_IN_PLAIN && d.in_mode != BNERV_IN_AFFINE) return false;
@@ -1156,18 +1163,8 @@ static bool wide_ok(const WArgs& wa) {
 
 template <int IN, int GM2, int MTW, int NTW>
 int launch_wide(hipStream_t st, const WArgs& wa, const WidePlan& p) {
-    using G = Geo<3>;
-    constexpr int NPL = wgrad_npl<3, NTW>();
-    const int g_rows = wa.d.Cout < MTW * 16 ? wa.d.Cout : MTW * 16;
-    size_t lds_fl = (size_t)g_rows * CSG + (size_t)(NPL + 2) * G::PLANE + 64;
-    if (lds_fl < (size_t)MTW * 16 * CSG) lds_fl = (size_t)MTW * 16 * CSG;
-    if (lds_fl < (size_t)MTW * 16 * NTW * 16) lds_fl = (size_t)MTW * 16 * NTW * 16;
-    const size_t lds = lds_fl * sizeof(float);
-    static size_t attr_lds = 0;
-    if (lds > attr_lds) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_wide_kernel<IN, GM2, MTW, NTW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_lds = lds;
-    }
+    const size_t lds = wgrad_wide_lds_bytes<MTW, NTW>(wa.d.Cout);
+    if (const int rc = dyn_lds<&wgrad_wide_kernel<IN, GM2, MTW, NTW>>(lds, "wgrad_wide")) return rc;
     const int grid = 8 * p.slots * p.ngroups * p.mgroups;
     SidePack side;
     bnerv_side_take(wa.d.ctx, &side, 2 * grid);
@@ -1208,13 +1205,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_bfw_kernel(const WArgs wa, const
 
 static bool bw_ok(const WArgs& wa) {
     const bnerv_wgrad_desc& d = wa.d;
-    if (bw_mode() < 0 || !wa.vec || d.k != 3 || (d.g_s > 3 && d.g_s != 5) || d.g_mode == BNERV_IN_TANHGRAD) return false;
+    if (split_wide_mode() < 0 || !wa.vec || d.k != 3 || (d.g_s > 3 && d.g_s != 5) || d.g_mode == BNERV_IN_TANHGRAD) return false;
     if (d.in_mode != BNERV_IN_PLAIN && d.in_mode != BNERV_IN_AFFINE) return false;
     if (d.g_s >= 2 && d.in_mode != BNERV_IN_PLAIN) return false;
     if (d.Cout <= 16) return false;                        // (one cout tile: the f32 kernels are as fast or faster -- 64 -> 16 @540x960: 108 vs 115 us)
-    int min_tiles = 16;
-    if (const char* e = getenv("BNERV_SPLIT_WIDE_MIN_TILES")) min_tiles = atoi(e);
-    if (d.B * cdiv(d.H, TH) * cdiv(d.W, TW) < min_tiles) return false;
+    if (d.B * cdiv(d.H, TH) * cdiv(d.W, TW) < split_wide_min_tiles()) return false;
     const size_t cmax = (size_t)(d.Cin > d.Cout ? d.Cin : d.Cout);
     return (size_t)d.B * cmax * d.H * d.W * 4 + (size_t)(d.W + 8) * 4 < WLEAN_MAX_BYTES;
 }
@@ -1234,15 +1229,8 @@ static BwPlan bw_plan(const bnerv_wgrad_desc& d) {
 }
 template <int IN, int SP, int MTW, int GM2>
 int launch_bw(hipStream_t st, const WArgs& wa, const BwPlan& p) {
-    constexpr int NS = Split<SP>::NS;
-    size_t lds = (size_t)NS * BW_PIECE + 2 * BW_NPL * sizeof(float);
-    const size_t red = (size_t)MTW * 16 * BW_NTW * 16 * sizeof(float);
-    if (lds < red) lds = red;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bfw_kernel<IN, SP, MTW, GM2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
+    constexpr size_t lds = wgrad_bfw_lds_bytes<SP, MTW>();
+    if (const int rc = dyn_lds<&wgrad_bfw_kernel<IN, SP, MTW, GM2>>(lds, "wgrad_bfw")) return rc;
     const int grid = 8 * p.slots * p.ngroups_n * p.ngroups_m;
     SidePack side;
     bnerv_side_take(wa.d.ctx, &side, 2 * grid);
@@ -1257,7 +1245,7 @@ int launch_bw_m(hipStream_t st, const WArgs& wa, const BwPlan& p) {
     return launch_bw<IN, SP, 3, GM2>(st, wa, p);
 }
 static int launch_bw_modes(hipStream_t st, const WArgs& wa, const BwPlan& p) {
-    const bool x3 = bw_mode() == SP_BF16X3;
+    const bool x3 = split_wide_mode() == SP_BF16X3;
     if (wa.d.g_s == 3 || wa.d.g_s == 5)                    // (x3 / x5 up-convs: strided 4-B gradient loads)
         return x3 ? launch_bw_m<BNERV_IN_PLAIN, SP_BF16X3, 3>(st, wa, p) : launch_bw_m<BNERV_IN_PLAIN, SP_BF16X6, 3>(st, wa, p);
     if (wa.d.g_s == 2)                                     // (the up-convs: plain input, shuffled gradient)
@@ -1302,12 +1290,7 @@ int launch_w(hipStream_t st, const WArgs& wa, const Plan& p) {
     if (lds_fl < (size_t)MTW * 16 * CSG) lds_fl = (size_t)MTW * 16 * CSG;         // the A reads of the dropped rows stay inside the block's LDS
     if (lds_fl < (size_t)MTW * 16 * NTW * 16) lds_fl = (size_t)MTW * 16 * NTW * 16;
     const size_t lds = lds_fl * sizeof(float);
-    static size_t attr_lds = 0;
-    if (lds > attr_lds) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<KS, IN, GM, MTW, NTW>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_lds = lds;
-    }
+    if (const int rc = dyn_lds<&conv_wgrad_kernel<KS, IN, GM, MTW, NTW>>(lds, "conv_wgrad")) return rc;
     dim3 grid(p.nsplit, p.n_mgroups * p.n_ngroups);
     hipLaunchKernelGGL((conv_wgrad_kernel<KS, IN, GM, MTW, NTW>), grid, dim3(256), lds, st, wa);
     BNERV_LAUNCH_CHECK("conv_wgrad");
@@ -1389,8 +1372,7 @@ extern "C" int bnerv_conv_wgrad(void* stream, const bnerv_wgrad_desc* dp) {
     wa.n_mgroups = p.n_mgroups;
     wa.n_ngroups = p.n_ngroups;
     wa.ncols = d.Cin * d.k * d.k + 1;
-    auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    wa.vec = ((d.W % 4 == 0) && al(d.x) && al(d.g) && al(d.gaux)) ? 1 : 0;
+    wa.vec = ((d.W % 4 == 0) && aligned16(d.x, d.g, d.gaux)) ? 1 : 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     {   // the stem stage (an image of <= 256 pixels, many output channels): written directly, no slabs
         const int rs = bnerv_stem_wgrad_try(st, d);
@@ -1445,8 +1427,7 @@ int launch_pair(hipStream_t st, bnerv_conv::KArgs& ka, const WArgs& wa, int* n_w
         // MI355X, C1 (profiles/r05_pair_fused.md): 720p DSIN pair 81.0 against 83.5 us, DGELU_SAVED 76.5 against 74.5, PLAIN 68.5 against
         // 66.7 (kept on the interleaved pair); at 360x640 (900 tiles) the interleaved pair's three blocks per CU win (27 against 29 us).
         // HBM traffic of the DSIN pair: see the same file.  BNERV_PAIR_FUSED=<tiles>: every pair from that many tiles on; 0: off.
-        const char* fe = getenv("BNERV_PAIR_FUSED");         // (read per call: the parity tests switch forms inside one process)
-        const int fused_env = fe ? atoi(fe) : -1;
+        const int fused_env = switch_int("BNERV_PAIR_FUSED", -1);      // (read per call: the parity tests switch forms inside one process)
         constexpr bool red_ep = EP == BNERV_EP_DGELU_SAVED || EP == BNERV_EP_DSIN;
         const int fused_min = fused_env >= 0 ? fused_env : (red_ep ? 1024 : 0);
         const bnerv_conv_desc& c = ka.d;
@@ -1454,11 +1435,7 @@ int launch_pair(hipStream_t st, bnerv_conv::KArgs& ka, const WArgs& wa, int* n_w
         if (fused_min > 0 && ka.total_items >= fused_min && ka.total_items >= 8 && c.x == w.g && c.Cin == w.Cout && c.Cout == w.Cin && c.B == w.B &&
             w.g_s == 1 && (w.g_mode == BNERV_IN_PLAIN || w.g_mode == BNERV_IN_UNSHUFFLE)) {
             const size_t ldsf = pair_fused_lds_bytes();
-            static bool attrf = false;
-            if (!attrf) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_fused_kernel<EP, WIN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsf);
-                attrf = true;
-            }
+            if (const int rc = dyn_lds<&pair_fused_kernel<EP, WIN>>(ldsf, "pair_fused")) return rc;
             int grid = ka.total_items < 512 ? (ka.total_items & ~7) : 512;
             if (n_w_out) *n_w_out = grid;
             SidePack side;
@@ -1467,16 +1444,11 @@ int launch_pair(hipStream_t st, bnerv_conv::KArgs& ka, const WArgs& wa, int* n_w
                 // fold form (pairf_body.h pair_fold_body): the input tile staged raw by LDS-DMA, the affine applied by the slab reduction.  One sample
                 // per launch (the fold is per sample), the reducing epilogue's raw-input operand must BE the weight gradient's input, and the
                 // workspace must hold `grid` slabs of Cout x (ncols + 8).  BNERV_PAIR_FOLD=0: the transforming form above.
-                const char* ff = getenv("BNERV_PAIR_FOLD");
                 const float* raw_aux = EP == BNERV_EP_DSIN ? c.aux0 : c.aux1;
-                if (!(ff && ff[0] == '0') && c.B == 1 && raw_aux == w.x && w.scale && w.shift && (reinterpret_cast<uintptr_t>(w.x) & 15) == 0 &&
+                if (!switch_off("BNERV_PAIR_FOLD") && c.B == 1 && raw_aux == w.x && w.scale && w.shift && aligned16(w.x) &&
                     (size_t)grid * w.Cout * (wa.ncols + 8) * sizeof(float) <= w.ws_bytes) {
                     const size_t ldsd = pair_fold_lds_bytes();
-                    static bool attrd = false;
-                    if (!attrd) {
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_fold_kernel<EP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsd);
-                        attrd = true;
-                    }
+                    if (const int rc = dyn_lds<&pair_fold_kernel<EP>>(ldsd, "pair_fold")) return rc;
                     hipLaunchKernelGGL((pair_fold_kernel<EP>), dim3(grid), dim3(256), ldsd, st, ka, wa, side);
                     BNERV_LAUNCH_CHECK("pair_fold");
                     if (n_w_out) *n_w_out = -grid;         // negative: the caller queues a FOLD slab reduction
@@ -1492,30 +1464,24 @@ int launch_pair(hipStream_t st, bnerv_conv::KArgs& ka, const WArgs& wa, int* n_w
     size_t lds = bnerv_q4::q4_lds_bytes();
     const size_t lw = wlean_lds_bytes<3>(n_grows);
     if (lw > lds) lds = lw;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_pair_kernel<EP, WIN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
+    if (const int rc = dyn_lds<&conv_wgrad_pair_kernel<EP, WIN>>(lds, "conv_wgrad_pair")) return rc;
     int n_conv = ka.total_items < 768 ? ka.total_items : 768;          // 3 conv blocks per CU when the layer is large
     n_conv = (n_conv + 7) & ~7;                                        // multiple of 8: block b runs on XCD b % 8 for BOTH halves' slices
     int n_w = wlean_blocks(wa.d);
     int grid = n_conv + n_w;
     if (n_w_out) *n_w_out = n_w;
-    // BNERV_PAIR_MIX: blocks per role of the interleaved form (0: conv blocks first, then the weight gradient's); BNERV_PAIR_PAT: the
-    // role of XCD-local slot s is (s + (s >> PAT)) & 1 (0: s & 1).  Measured on C1 (1.745 ms with the roles one after the other):
-    // 384 blocks per role 1.680 (PAT 0), 1.642 (PAT 5: the parity flips every 32 slots = the CUs of an XCD, so every CU holds both
-    // roles), 1.664 (6), 1.68 (3, 4, 7); 376 / 368 per role as 384, 512 per role (not all resident) 1.783.
-    static const int mix3 = [] { const char* e = getenv("BNERV_PAIR_MIX"); return e ? atoi(e) : 384; }();
-    static const int pat = [] { const char* e = getenv("BNERV_PAIR_PAT"); return e ? atoi(e) : 5; }();
-    const int mix = mix3;
-    if (mix > 0 && ka.total_items >= 2 * mix && n_w >= mix) {          // large layer: mix blocks per role, all resident, roles interleaved
-        n_w = mix; n_conv = -mix; grid = 2 * mix;
+    // PAIR_MIX: blocks per role of the interleaved form; PAIR_PAT: the role of XCD-local slot s is (s + (s >> PAT)) & 1.  Measured on C1
+    // (1.745 ms with the roles one after the other): 384 blocks per role 1.680 (PAT 0), 1.642 (PAT 5: the parity flips every 32 slots =
+    // the CUs of an XCD, so every CU holds both roles), 1.664 (6), 1.68 (3, 4, 7); 376 / 368 per role as 384, 512 per role (not all
+    // resident) 1.783.
+    constexpr int PAIR_MIX = 384, PAIR_PAT = 5;
+    if (ka.total_items >= 2 * PAIR_MIX && n_w >= PAIR_MIX) {           // large layer: PAIR_MIX blocks per role, all resident, roles interleaved
+        n_w = PAIR_MIX; n_conv = -PAIR_MIX; grid = 2 * PAIR_MIX;
         if (n_w_out) *n_w_out = n_w;
     }
     SidePack side;
     bnerv_side_take(wa.d.ctx, &side, 2 * n_w);
-    hipLaunchKernelGGL((conv_wgrad_pair_kernel<EP, WIN>), dim3(grid), dim3(256), lds, st, ka, wa, n_grows, n_conv, side, pat);
+    hipLaunchKernelGGL((conv_wgrad_pair_kernel<EP, WIN>), dim3(grid), dim3(256), lds, st, ka, wa, n_grows, n_conv, side, PAIR_PAT);
     BNERV_LAUNCH_CHECK("conv_wgrad_pair");
     return BNERV_OK;
 }
@@ -1529,25 +1495,12 @@ struct WideRoleArgs { int slots, ngn, ngm; };
 template <int IN, int GM2, int MTW, int NTW>
 struct WideRole {
     static __device__ __forceinline__ void run(const WArgs& wa, const WideRoleArgs& r, const SidePack& side, int vb, int vgrid) { wgrad_wide_body<IN, GM2, MTW, NTW>(wa, r.slots, side, vb, vgrid); }
-    static size_t lds(const WArgs& wa) {
-        using G = Geo<3>;
-        constexpr int NPL = wgrad_npl<3, NTW>();
-        const int g_rows = wa.d.Cout < MTW * 16 ? wa.d.Cout : MTW * 16;
-        size_t lds_fl = (size_t)g_rows * CSG + (size_t)(NPL + 2) * G::PLANE + 64;
-        if (lds_fl < (size_t)MTW * 16 * CSG) lds_fl = (size_t)MTW * 16 * CSG;
-        if (lds_fl < (size_t)MTW * 16 * NTW * 16) lds_fl = (size_t)MTW * 16 * NTW * 16;
-        return lds_fl * sizeof(float);
-    }
+    static size_t lds(const WArgs& wa) { return wgrad_wide_lds_bytes<MTW, NTW>(wa.d.Cout); }
 };
 template <int IN, int SP, int MTW, int GM2>
 struct BfwRole {
     static __device__ __forceinline__ void run(const WArgs& wa, const WideRoleArgs& r, const SidePack& side, int vb, int vgrid) { wgrad_bfw_body<IN, SP, MTW, GM2>(wa, r.slots, r.ngn, r.ngm, side, vb, vgrid); }
-    static size_t lds(const WArgs&) {
-        constexpr int NS = Split<SP>::NS;
-        size_t lds = (size_t)NS * BW_PIECE + 2 * BW_NPL * sizeof(float);
-        const size_t red = (size_t)MTW * 16 * BW_NTW * 16 * sizeof(float);
-        return lds < red ? red : lds;
-    }
+    static size_t lds(const WArgs&) { return wgrad_bfw_lds_bytes<SP, MTW>(); }
 };
 template <class WR, int CIN, int CEP, int CNQ>
 __global__ __launch_bounds__(256, 2) void small_pair_kernel(const bnerv_convs::SArgs sa, const WArgs wa, const WideRoleArgs r, const int n_c, const int n_c8,
@@ -1566,11 +1519,7 @@ int launch_small_pair(hipStream_t st, const bnerv_convs::SArgs& sa, const WArgs&
     size_t lds = bnerv_convs::convs_lds_bytes<CNQ>();
     const size_t lw = WR::lds(wa);
     if (lw > lds) lds = lw;
-    static size_t attr_lds = 0;
-    if (lds > attr_lds) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_pair_kernel<WR, CIN, CEP, CNQ>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_lds = lds;
-    }
+    if (const int rc = dyn_lds<&small_pair_kernel<WR, CIN, CEP, CNQ>>(lds, "small_pair")) return rc;
     const int c_tiles = sa.tiles_x * sa.tiles_y, c_groups = cdiv(sa.d.Cout, 16);
     const int n_c = c_tiles * c_groups * sa.d.B, n_c8 = (n_c + 7) & ~7;
     SidePack side;
@@ -1583,10 +1532,7 @@ int launch_small_pair(hipStream_t st, const bnerv_convs::SArgs& sa, const WArgs&
 // 1: not a pair of this form.  On BNERV_OK *n_slabs is the weight gradient's slab count (the caller queues its reduction).
 static int small_pair_try(hipStream_t st, const bnerv_conv_desc& c, WArgs& wa, int* n_slabs) {
     const bnerv_wgrad_desc& w = wa.d;
-    { static const bool off = [] { const char* e = getenv("BNERV_PAIR_SMALL"); return e && e[0] == '0'; }(); if (off) return 1; }
-    auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const int cvec = ((c.W % 4 == 0) && al(c.x) && al(c.out) && al(c.out2) && al(c.aux0) && al(c.aux1) && al(c.aux2)) ? 1 : 0;
-    if (!bnerv_convs_shape_ok(c, cvec)) return 1;
+    if (!bnerv_convs_shape_ok(c, conv_vec_ok(c))) return 1;
     if (c.in_mode != BNERV_IN_UNSHUFFLE && c.Cin > 32) return 1;                           // (convs.hip's 96-channel form has no paired instantiation)
     if (c.ep_mode == BNERV_EP_PLAIN && bnerv_conv_splitk_ws_bytes(&c) != 0) return 1;     // (a split-K layer: its own launches)
     if (!(w.k == 3 && w.B == c.B && w.H == c.H && w.W == c.W && w.defer_finish && w.ctx && w.ctx == c.ctx)) return 1;
@@ -1600,7 +1546,7 @@ static int small_pair_try(hipStream_t st, const bnerv_conv_desc& c, WArgs& wa, i
     if (wlean_ok(wa)) return 1;                            // (the lean weight gradient pairs with conv4.hip's family)
 #define BNERV_SP(WR, I, E, Q) if (c.in_mode == I && c.ep_mode == E && cnq == Q) rc = launch_small_pair<WR, I, E, Q>(st, sa, wa, r, n_w);
     if (bw_ok(wa)) {
-        if (bw_mode() != (int)SP_BF16X6) return 1;
+        if (split_wide_mode() != (int)SP_BF16X6) return 1;
         const BwPlan bp = bw_plan(w);
         r.slots = bp.slots; r.ngn = bp.ngroups_n; r.ngm = bp.ngroups_m;
         const int n_w = 8 * bp.slots * bp.ngroups_n * bp.ngroups_m;
@@ -1702,15 +1648,13 @@ __global__ __launch_bounds__(256) void head1x1_bwd_kernel(const HeadBwdArgs a) {
 
 // 1: not the head's pair; BNERV_OK: launched, *n_slabs slabs of K x (C + 1) floats in w.ws
 static int head_pair_try(hipStream_t st, const bnerv_conv_desc& c, const bnerv_wgrad_desc& w, int* n_slabs) {
-    { const char* e = getenv("BNERV_PAIR_HEAD"); if (e && e[0] == '0') return 1; }      // A/B switch, read per call
     if (!(c.k == 1 && w.k == 1 && c.in_mode == BNERV_IN_TANHGRAD && c.ep_mode == BNERV_EP_PLAIN && c.out_s == 1 && w.g_mode == BNERV_IN_TANHGRAD && w.in_mode == BNERV_IN_PLAIN)) return 1;
     if (!(c.x && c.aux0 && c.w && c.out && w.x && w.g && w.gaux && w.dw && w.ws && w.defer_finish && w.ctx && w.ctx == c.ctx)) return 1;
     if (!(c.x == w.g && c.aux0 == w.gaux && c.Cin == w.Cout && c.Cout == w.Cin && c.B == w.B && c.H == w.H && c.W == w.W)) return 1;     // one head, one gradient
     const int K = c.Cin, C = c.Cout;
     if (K != 3 || C != 12 || ((size_t)c.H * c.W) % 4 != 0) return 1;            // (instantiated for the reference's heads: 12 -> 3; HNeRV's heads are 3x3)
     if (c.transposed ? !(c.wCo == K && c.wCi == C) : !(c.wCo == C && c.wCi == K)) return 1;
-    auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if (!(al(c.x) && al(c.aux0) && al(c.out) && al(w.x))) return 1;
+    if (!aligned16(c.x, c.aux0, c.out, w.x)) return 1;
     const size_t HW = (size_t)c.H * c.W;
     const int nq = (int)(HW / 4);
     // one quad per thread up to 1024 blocks (every load of a thread is in flight at once: the pass is one memory round trip per wave; a
@@ -1730,8 +1674,6 @@ static int head_pair_try(hipStream_t st, const bnerv_conv_desc& c, const bnerv_w
 // bnerv_conv_wgrad and bnerv_conv_igemm separately, in that order), a negative BNERV_E_* on error.
 extern "C" int bnerv_conv_wgrad_pair(void* stream, const bnerv_conv_desc* cdp, const bnerv_wgrad_desc* wdp) {
     BNERV_REQUIRE(cdp != nullptr && wdp != nullptr, "conv_wgrad_pair: null descriptor");
-    static const bool off = [] { const char* e = getenv("BNERV_PAIR"); return e && e[0] == '0'; }();
-    if (off) return 1;
     bnerv_conv::KArgs ka;
     ka.d = *cdp;
     bnerv_conv_desc& c = ka.d;
@@ -1770,7 +1712,6 @@ extern "C" int bnerv_conv_wgrad_pair(void* stream, const bnerv_conv_desc* cdp, c
     if (w.in_mode == BNERV_IN_AFFINE && !(w.scale && w.shift)) return 1;
     if (!(w.g_s == 1 || (w.g_s == 2 && w.g_mode == BNERV_IN_UNSHUFFLE && w.Cout % 4 == 0))) return 1;
     if (w.ws_bytes < bnerv_conv_wgrad_ws_bytes(w.B, w.Cin, w.Cout, w.H, w.W, w.k)) return bnerv_set_error(BNERV_E_WS, "conv_wgrad_pair: weight-gradient workspace too small");
-    auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     const Plan p = make_plan(w.B, w.Cin, w.Cout, w.H, w.W, w.k);
     wa.slab = reinterpret_cast<float*>(w.ws);
     wa.tiles_x = cdiv(w.W, TW);
@@ -1778,19 +1719,18 @@ extern "C" int bnerv_conv_wgrad_pair(void* stream, const bnerv_conv_desc* cdp, c
     wa.n_mgroups = p.n_mgroups;
     wa.n_ngroups = p.n_ngroups;
     wa.ncols = w.Cin * 9 + 1;
-    wa.vec = ((w.W % 4 == 0) && al(w.x) && al(w.g)) ? 1 : 0;
+    wa.vec = ((w.W % 4 == 0) && aligned16(w.x, w.g)) ? 1 : 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     int rc = 1, n_slabs = 0;
 
     // form 1: conv4.hip's 12-channel family next to the lean weight gradient (roles interleaved per XCD on large layers)
     ka.tiles_x = cdiv(c.W, bnerv_conv::TW);
     ka.tiles_y = cdiv(c.H, bnerv_conv::TH);
-    ka.vec = ((c.W % 4 == 0) && al(c.x) && al(c.out) && al(c.aux0) && al(c.aux1) && al(c.aux2)) ? 1 : 0;
+    ka.vec = conv_vec_ok(c);                               // (includes out2, which no epilogue of a pair writes: the callers leave it NULL)
     ka.ksplit = 1;
     ka.chunks_per_split = 0;
     ka.magic_tiles = ka.magic_tiles_x = 0;
-    static const bool q4off = [] { const char* e = getenv("BNERV_Q4"); return e && e[0] == '0'; }();
-    if (!q4off && c.in_mode == BNERV_IN_PLAIN && w.g_s == 1 && bnerv_q4::q4_shape_ok(ka) && wlean_ok(wa)) {
+    if (c.in_mode == BNERV_IN_PLAIN && w.g_s == 1 && bnerv_q4::q4_shape_ok(ka) && wlean_ok(wa)) {
 #define BNERV_PAIR_CASE(E, I) if (c.ep_mode == E && w.in_mode == I) rc = launch_pair<E, I>(st, ka, wa, &n_slabs);
         BNERV_PAIR_CASE(BNERV_EP_DGELU_SAVED, BNERV_IN_AFFINE)
         BNERV_PAIR_CASE(BNERV_EP_DSIN, BNERV_IN_AFFINE)
@@ -1798,7 +1738,7 @@ extern "C" int bnerv_conv_wgrad_pair(void* stream, const bnerv_conv_desc* cdp, c
 #undef BNERV_PAIR_CASE
     }
     // form 3: the wide split conv next to the wide split weight gradient, roles interleaved (layers that fill the chip in both roles)
-    if (rc == 1 && !wlean_ok(wa) && bw_ok(wa) && bw_mode() == (int)SP_BF16X6) {
+    if (rc == 1 && !wlean_ok(wa) && bw_ok(wa) && split_wide_mode() == (int)SP_BF16X6) {
         const BwPlan bp = bw_plan(w);
         rc = bnerv_convbf_pair_try(st, c, ka.vec, wa, bp.mtw, bp.ngroups_n, bp.ngroups_m, bp.slots, &n_slabs);
     }

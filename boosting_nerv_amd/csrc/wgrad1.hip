@@ -12,6 +12,7 @@
 // writes its [rows][cols] part of slab z coalesced.  Slabs [z][Cout][Cin + 1] (bias gradient = last column) are summed by the usual
 // finish / deferred reduction (wgrad.hip, sidejob.h): deterministic, no atomics.
 #include "conv_common.h"
+#include "launch.h"
 #include "sidejob.h"
 
 namespace {
@@ -145,12 +146,11 @@ static W1Plan w1_plan(int B, int Cin, int Cout, int HW) {
 }
 
 static bool w1_ok(const bnerv_wgrad_desc& d) {
-    static const bool off = [] { const char* e = getenv("BNERV_WGRAD1"); return e && e[0] == '0'; }();   // A/B switch
-    if (off || d.k != 1 || d.g_s != 1) return false;
+    if (d.k != 1 || d.g_s != 1) return false;
     if (d.in_mode != BNERV_IN_PLAIN || !(d.g_mode == BNERV_IN_PLAIN || d.g_mode == BNERV_IN_UNSHUFFLE)) return false;
     const size_t HW = (size_t)d.H * d.W;
     // (measured: 36 x 64 = 2304 pixels is faster on the general kernel, 12.6 against 18.7 us; 72 x 128 is faster here, 20 against 29)
-    if ((HW & 3) || HW < 4096 || (reinterpret_cast<uintptr_t>(d.x) & 15) || (reinterpret_cast<uintptr_t>(d.g) & 15)) return false;
+    if ((HW & 3) || HW < 4096 || !aligned16(d.x, d.g)) return false;
     if (d.Cin < 16 || d.Cout < 16) return false;               // (the lean kernel serves the few-channel layers: 1x1 heads)
     const size_t big = (size_t)d.B * (d.Cin > d.Cout ? d.Cin : d.Cout) * HW * 4;
     return big < LEAN_MAX_BYTES;

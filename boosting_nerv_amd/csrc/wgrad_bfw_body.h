@@ -5,8 +5,6 @@
 #include "common.h"
 #include "sidejob.h"
 #include "split16.h"
-#include <stdlib.h>
-#include <string.h>
 #ifndef BTRACE
 #define BTRACE(it_, slot) do {} while (0)
 #endif
@@ -384,15 +382,11 @@ __device__ __forceinline__ void wgrad_bfw_body(const WArgs& wa, const int slots,
 }
 
 struct BwPlan { int mtw, ngroups_n, ngroups_m, slots; };
-static int bw_mode() {                                     // BNERV_SPLIT_WIDE = bf16x6 (default) | bf16x3 | off   (shared with convbf.hip)
-    static const int v = [] {
-        const char* e = getenv("BNERV_SPLIT_WIDE");
-        if (!e) return (int)SP_BF16X6;
-        if (!strcmp(e, "off") || !strcmp(e, "0")) return -1;
-        if (!strcmp(e, "bf16x3")) return (int)SP_BF16X3;
-        return (int)SP_BF16X6;
-    }();
-    return v;
+// dynamic LDS of wgrad_bfw_body: the input pieces + affine table while it accumulates, the block's output rows while it reduces
+template <int SP, int MTW>
+constexpr size_t wgrad_bfw_lds_bytes() {
+    const size_t acc = (size_t)Split<SP>::NS * BW_PIECE + 2 * BW_NPL * sizeof(float), red = (size_t)MTW * 16 * BW_NTW * 16 * sizeof(float);
+    return acc > red ? acc : red;
 }
 
 }  // namespace bnerv_wb

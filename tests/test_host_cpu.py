@@ -678,3 +678,23 @@ def test_hard_exit_leaves_the_regular_way_under_a_profiler():
         assert plain.returncode == 3 and "result line" in plain.stdout and "C-LEVEL-EXIT-HANDLER" not in plain.stdout, (plain.returncode, plain.stdout, plain.stderr[-300:])
         tool = subprocess.run([sys.executable, path], env=dict(hard, ROCPROF_OUTPUT_PATH=td), capture_output=True, text=True, timeout=120)
         assert tool.returncode == 3 and "result line" in tool.stdout and "C-LEVEL-EXIT-HANDLER" in tool.stdout, (tool.returncode, tool.stdout, tool.stderr[-300:])
+
+
+def test_library_switches_are_the_documented_nine_and_launch_plumbing_lives_in_one_header():
+    """Every environment switch the library reads goes through csrc/launch.h and is a row of INTEGRATION.md's "Library switches" table; the
+    per-kernel attribute and occupancy calls exist in launch.h alone (no launcher keeps a cache of its own)."""
+    csrc = os.path.join(ROOT, "boosting_nerv_amd", "csrc")
+    read, raw = set(), {}
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".hip", ".h", ".cpp")):
+            continue
+        text = open(os.path.join(csrc, name)).read()
+        read |= set(re.findall(r'\b(?:switch_\w+|getenv)\(\s*"(BNERV_\w+)"', text))
+        for call in ("getenv(", "hipFuncSetAttribute", "hipOccupancyMaxActiveBlocksPerMultiprocessor"):
+            if call in text:
+                raw.setdefault(call, []).append(name)
+    assert raw == {c: ["launch.h"] for c in ("getenv(", "hipFuncSetAttribute", "hipOccupancyMaxActiveBlocksPerMultiprocessor")}, raw
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    table = doc[doc.index("## Library switches"):]
+    documented = set(re.findall(r"^\| `(BNERV_\w+)` \|", table, re.M))
+    assert len(documented) == 9 and read == documented, (sorted(read - documented), sorted(documented - read))

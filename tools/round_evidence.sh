@@ -28,6 +28,4 @@ python $R/tools/pmc_parse.py /tmp/pmc_wgrad wgrad_lean_kernel >> $O/${TAG}_pmc.t
 python $R/tools/pmc_parse.py /tmp/pmc_conv38 conv_lean2_kernel >> $O/${TAG}_pmc.txt 2>&1
 python $R/tools/pmc_parse.py /tmp/pmc_wgrad38 wgrad_wide_kernel >> $O/${TAG}_pmc.txt 2>&1
 python $R/tools/kbench.py 30 > $O/${TAG}_kbench.txt 2>&1
-python $R/tools/klean2.py 2>&1 | grep -v amdgpu.ids > $O/${TAG}_klean2.txt
-python $R/tools/kwide.py 2>&1 | grep -v amdgpu.ids > $O/${TAG}_kwide.txt
 echo done

@@ -51,9 +51,7 @@ for c, name in (("c3", "HNeRV-boost 3M, 1080x1920"), ("c4", "E-NeRV-boost 3M, 10
     open(P + f"{c}_step_kerneltrace.md", "w").write(hdr(f"{c.upper()} train step ({name}); rocprofv3 --kernel-trace --stats (20+5 steps incl. graph capture warm-up), MI355X",
         f"rocprofv3 --kernel-trace --stats -d /tmp/kt_{c} -- python bench.py --config {c} --steps 20 --warmup 5 --no_cpu_baseline",
         f"Bench line of the same build (profiles/r01_{tag}_bench_{c}.json): {b['value']} frames/s, {b['ms_per_step']} ms/step.\n") + open(O + f"{c}_trace.md").read())
-open(P + "kernel_microbench.md", "w").write(f"# Round 1 ({tag}) — hot kernels through the C-ABI (HIP events), MI355X\n\n## C1 shapes (tools/kbench.py 30)\n\n```\n" + open(O + "kbench.txt").read() +
-    "```\n\n## Wide conv kernel vs the generic kernel (tools/klean2.py; same inputs, outputs compared)\n\n```\n" + open(O + "klean2.txt").read() +
-    "```\n\n## Wide weight-gradient kernel vs the general kernel (tools/kwide.py; same inputs, dw/db compared)\n\n```\n" + open(O + "kwide.txt").read() + "```\n")
+open(P + "kernel_microbench.md", "w").write(f"# Round 1 ({tag}) — hot kernels through the C-ABI (HIP events), MI355X\n\n## C1 shapes (tools/kbench.py 30)\n\n```\n" + open(O + "kbench.txt").read() + "```\n")
 for c in ("c1", "c3", "c4", "c5"):
     b = json.load(open(O + f"bench_{c}.json"))
     print(c, b["value"], b["ms_per_step"], (b.get("roofline") or {}).get("achieved"), (b.get("cpu_baseline") or {}).get("value"))
