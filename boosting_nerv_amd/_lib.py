@@ -167,6 +167,10 @@ SYMBOLS = {
     "bnerv_fft_prepare": (_I, [_I, _I]),
     "bnerv_loss_fwd_bwd": (_I, [_V, C.POINTER(LossDesc)]),
     "bnerv_msssim": (_I, [_V, _V, _V, _V, _V, _Z, _I, _I, _I, _I]),
+    "bnerv_loss_ssim_ws_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "bnerv_loss_ssim_prepare": (_I, [_I, _I]),
+    "bnerv_loss_ssim_fwd_bwd": (_I, [_V, C.POINTER(LossDesc), _F]),
+    "bnerv_ssim": (_I, [_V, _V, _V, _V, _V, _Z, _I, _I, _I, _I]),
     "bnerv_tanh_grad_blocks": (_I, [_I]),
     "bnerv_tanh_grad": (_I, [_V, _V, _V, _V, _V, _I, _I, _I]),
     "bnerv_psnr_ws_bytes": (_Z, [_I, _I, _I, _I]),
@@ -189,9 +193,10 @@ class BnervError(RuntimeError):
     pass
 
 
-def load():
+def load(optional=()):
     """Load the shared object (once) and bind every symbol.  Raises if the library is missing: the HIP path is the
-    product, there is nothing to fall back to."""
+    product, there is nothing to fall back to.  `optional`: names that an OLDER build of the same ABI may lack (additive entry
+    points); they are left unbound there instead of failing the load -- for tools that compare two builds, first call only."""
     global _lib
     if _lib is not None:
         return _lib
@@ -200,6 +205,8 @@ def load():
                          f"(or `python -c 'import __graft_entry__ as g; g.build()'`)")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SYMBOLS.items():
+        if name in optional and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)          # AttributeError here = header and library out of sync
         fn.restype = res
         fn.argtypes = args

@@ -15,6 +15,8 @@
 //   fft_rows_fwd    in-place mixed-radix DIF FFT of every row in LDS (digit-reversed output order -- irrelevant, see below)
 //   fft_cols        column DIF FFT, sum(|Re|+|Im|), S = sign(F), then the ADJOINT transform of S, all in LDS
 //   fft_rows_adj    adjoint row transform, real part, accumulated into `grad`
+//   ssim_head/tail  the single-scale SSIM losses (SSIM, Fusion1-6, Fusion9, L1_ssim_freq): level 0 of the above without a pyramid, as block
+//                   ranges of two grids (plus three FFT launches with the spectral term) -- see "single-scale SSIM losses" below
 // The forward FFT leaves its output digit-reversed; the L1 norm does not care about order and the adjoint network is the
 // exact transpose-conjugate of the forward network, so no reordering pass exists anywhere.
 //
@@ -194,7 +196,8 @@ __global__ __launch_bounds__(256) void pyramid_kernel(const PyrArgs a) { pyramid
 struct SsimArgs {
     const float* X; const float* Y;
     float* partial;            // fwd: [BC][tiles]
-    const float* coef;         // bwd: [BC] for this level (already includes 1/Nvalid and the loss chain)
+    const float* coef;         // bwd: [BC] for this level (already includes 1/Nvalid and the loss chain); NULL = coef_k for every plane
+    float coef_k;              // bwd: the single-scale SSIM losses' constant chain coefficient -c_ss / (B*C*Nvalid) (the term is linear in the map)
     const float* dcoarse;      // bwd: [BC][Hc][Wc] gradient wrt the next (coarser) level's pooled image, or NULL
     float* dX;                 // bwd: [BC][H][W] written
     float* G;                  // fwd writes / bwd reads: [3][BC][H][W] UNSCALED statistic gradients (d mu1-ish, d E[xx], d E[xy]) at
@@ -338,25 +341,27 @@ struct CoefArgs {
     int BC;
     float chain;                // -c_ms / (B*C)
 };
+// sum of one plane's tile partials on ONE wave: 8 loads in flight per lane (a level-0 row of 1800 partials was 29 serialised L2 round trips:
+// 12 us for 3 blocks), added in fp64 in the same order as one by one, then a wave reduction; every lane returns the sum
+__device__ __forceinline__ double tile_sum_d(const float* __restrict__ part, const int nt) {
+    const int lane = threadIdx.x & 63;
+    double s = 0.0;
+    for (int i0 = lane; i0 < nt; i0 += 8 * 64) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { const int i = i0 + u * 64; v[u] = i < nt ? part[i] : 0.f; }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) if (i0 + u * 64 < nt) s += (double)v[u];
+    }
+    return wave_sum_d(s);
+}
 // one wave per level (a block of 5 waves) or, inside a 256-thread launch, waves 0..3 with wave 0 taking level 4 as well: the per-level
 // sums never mix, so both forms add the same numbers in the same order
 __device__ __forceinline__ void ms_coef_body(const CoefArgs& a, const int bc) {
     const int lane = threadIdx.x & 63, nw = (int)blockDim.x >> 6;
     __shared__ float stat[LV];
     for (int l = threadIdx.x >> 6; l < LV; l += nw) {
-        double s = 0.0;
-        // 8 loads in flight per lane (a level-0 row of 1800 partials was 29 serialised L2 round trips: 12 us for 3 blocks), added in
-        // the same order as one by one
-        const float* part = a.partial[l] + (size_t)bc * a.tiles[l];
-        const int nt = a.tiles[l];
-        for (int i0 = lane; i0 < nt; i0 += 8 * 64) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { const int i = i0 + u * 64; v[u] = i < nt ? part[i] : 0.f; }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) if (i0 + u * 64 < nt) s += (double)v[u];
-        }
-        s = wave_sum_d(s);
+        const double s = tile_sum_d(a.partial[l] + (size_t)bc * a.tiles[l], a.tiles[l]);
         if (lane == 0) stat[l] = (float)(s * (double)a.inv_nvalid[l]);
     }
     __syncthreads();
@@ -426,7 +431,7 @@ __device__ __forceinline__ void ssim_bwd_body(const SsimArgs& a, const CoarseCha
         sA01[r][c] = a01; sA2[r][c] = a2;
     }
     __syncthreads();
-    const float coef = a.coef[bc];
+    const float coef = a.coef ? a.coef[bc] : a.coef_k;
     const float* X = a.X + (size_t)bc * plane;
     const float* Y = a.Y + (size_t)bc * plane;
     for (int i = tid; i < STH * STW; i += 256) {
@@ -548,7 +553,8 @@ static const int* get_positions(const FftPlan& pl) {
     return d;
 }
 
-static bool make_plan(int N, FftPlan* p) {
+// maxr: the largest prime the caller's kernels hold register arrays for (butterfly_generic<.., MAXR>)
+static bool make_plan(int N, FftPlan* p, int maxr = BNERV_FFT_MAX_RADIX) {
     p->N = N; p->nrad = 0;
     int n = N;
     auto push = [&](int r) { if (p->nrad < MAXRAD) p->rad[p->nrad++] = r; };
@@ -556,7 +562,7 @@ static bool make_plan(int N, FftPlan* p) {
     while (n % 2 == 0) { push(2); n /= 2; }
     while (n % 3 == 0) { push(3); n /= 3; }
     while (n % 5 == 0) { push(5); n /= 5; }
-    for (int r = 7; r <= BNERV_FFT_MAX_RADIX && n > 1; r += 2)
+    for (int r = 7; r <= maxr && n > 1; r += 2)
         while (n % r == 0) { push(r); n /= r; }
     if (n != 1 || p->nrad >= MAXRAD) return false;
     if (N == 1) { p->nrad = 0; }
@@ -626,10 +632,10 @@ __device__ __forceinline__ void butterfly(float2* buf, int base, int M, int j, i
     for (int q = 0; q < R; ++q) buf[base + __mul24(q, M)] = o[q];
 }
 
-// generic radix (primes 7..31): O(R^2) with the table, operands staged in registers one output at a time
-template <bool ADJ>
+// generic radix (primes 7..MAXR: BNERV_FFT_MAX_RADIX, or SSIM_FFT_MAX_RADIX in the single-scale SSIM path's own instantiations): O(R^2) with the table, operands staged in registers one output at a time
+template <bool ADJ, int MAXR>
 __device__ void butterfly_generic(float2* buf, int base, int M, int j, int tstride, int R, const FftPlan& pl, const float2* tw) {
-    float2 v[BNERV_FFT_MAX_RADIX], o[BNERV_FFT_MAX_RADIX];
+    float2 v[MAXR], o[MAXR];
     const int rstep = pl.N / R;
     for (int m = 0; m < R; ++m) {
         v[m] = buf[base + m * M];
@@ -698,7 +704,7 @@ __device__ __forceinline__ void fft_stage_r(float2* buf, int nlines, int lstride
     __syncthreads();
 }
 
-template <bool ADJ>
+template <bool ADJ, int MAXR>
 __device__ void fft_stage(float2* buf, int nlines, int lstride, int Ns, int R, const FftPlan& pl, const float2* tw) {
     switch (R) {
         case 2: fft_stage_r<2, ADJ>(buf, nlines, lstride, Ns, pl, tw); return;
@@ -713,7 +719,7 @@ __device__ void fft_stage(float2* buf, int nlines, int lstride, int Ns, int R, c
         const int line = (int)(((float)bf + 0.5f) * inv_pl), rem = bf - __mul24(line, per_line);
         const int blk = (int)(((float)rem + 0.5f) * inv_M), j = rem - __mul24(blk, M);
         const int base = __mul24(line, lstride) + __mul24(blk, Ns) + j;
-        butterfly_generic<ADJ>(buf, base, M, j, tstride, R, pl, tw);
+        butterfly_generic<ADJ, MAXR>(buf, base, M, j, tstride, R, pl, tw);
     }
     __syncthreads();
 }
@@ -742,13 +748,15 @@ __device__ __forceinline__ void tables_commit(const TabRegs& r, float2* tw, int*
     }
     for (int i = threadIdx.x + TAB_U * blockDim.x; i < pl.N; i += blockDim.x) { tw[i] = pl.tw[i]; if (POS) lpos[i] = pl.pos[i]; }   // (N > 2048)
 }
+template <int MAXR = BNERV_FFT_MAX_RADIX>
 __device__ void fft_forward(float2* buf, int nlines, int lstride, const FftPlan& pl, const float2* tw) {
     int Ns = pl.N;
-    for (int s = 0; s < pl.nrad; ++s) { fft_stage<false>(buf, nlines, lstride, Ns, pl.rad[s], pl, tw); Ns /= pl.rad[s]; }
+    for (int s = 0; s < pl.nrad; ++s) { fft_stage<false, MAXR>(buf, nlines, lstride, Ns, pl.rad[s], pl, tw); Ns /= pl.rad[s]; }
 }
+template <int MAXR = BNERV_FFT_MAX_RADIX>
 __device__ void fft_adjoint(float2* buf, int nlines, int lstride, const FftPlan& pl, const float2* tw) {
     int Ns = 1;
-    for (int s = pl.nrad - 1; s >= 0; --s) { Ns *= pl.rad[s]; fft_stage<true>(buf, nlines, lstride, Ns, pl.rad[s], pl, tw); }
+    for (int s = pl.nrad - 1; s >= 0; --s) { Ns *= pl.rad[s]; fft_stage<true, MAXR>(buf, nlines, lstride, Ns, pl.rad[s], pl, tw); }
 }
 
 // The row transforms work on PAIRS of real rows: z = a + i b is ONE complex transform, and the two real rows' spectra are its
@@ -778,6 +786,7 @@ struct FftArgs {
     FftPlan prow, pcol;
 };
 
+template <int MAXR = BNERV_FFT_MAX_RADIX>
 __device__ __forceinline__ void fft_rows_fwd_body(const FftArgs& a, const int bx) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float2* buf = reinterpret_cast<float2*>(sm);
@@ -811,7 +820,7 @@ __device__ __forceinline__ void fft_rows_fwd_body(const FftArgs& a, const int bx
     }
     if (!tabs_done) tables_commit<true>(tr, tw, lpos, a.prow);            // (a thread without input elements still owns table entries)
     __syncthreads();
-    fft_forward(buf, nlines, W, a.prow, tw);
+    fft_forward<MAXR>(buf, nlines, W, a.prow, tw);
     const int Wh = a.Wh;
     for (int i = threadIdx.x; i < nl * Wh; i += blockDim.x) {
         const int row = i / Wh, f = i - row * Wh;
@@ -823,6 +832,7 @@ __device__ __forceinline__ void fft_rows_fwd_body(const FftArgs& a, const int bx
 }
 __global__ __launch_bounds__(256) void fft_rows_fwd_kernel(const FftArgs a) { fft_rows_fwd_body(a, blockIdx.x); }
 
+template <int MAXR = BNERV_FFT_MAX_RADIX>
 __device__ __forceinline__ void fft_cols_body(const FftArgs& a, const int bx, const int bc, const int ncolblk) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float2* buf = reinterpret_cast<float2*>(sm);                          // [COLS_PER_BLOCK][H]
@@ -853,7 +863,7 @@ __device__ __forceinline__ void fft_cols_body(const FftArgs& a, const int bx, co
     }
     if (!tabs_done) tables_commit<false>(tr, tw, nullptr, a.pcol);
     __syncthreads();
-    fft_forward(buf, nc, H, a.pcol, tw);
+    fft_forward<MAXR>(buf, nc, H, a.pcol, tw);
     float acc = 0.f;
     for (int i = threadIdx.x; i < H * nc; i += blockDim.x) {
         const float2 f = buf[i];           // lines are contiguous: nc*H elements
@@ -867,7 +877,7 @@ __device__ __forceinline__ void fft_cols_body(const FftArgs& a, const int bx, co
     __syncthreads();
     if (threadIdx.x == 0) a.partial[(size_t)bc * ncolblk + bx] = red[0] + red[1] + red[2] + red[3];
     if (a.grad == nullptr) return;
-    fft_adjoint(buf, nc, H, a.pcol, tw);
+    fft_adjoint<MAXR>(buf, nc, H, a.pcol, tw);
     for (int i = threadIdx.x; i < H * nc; i += blockDim.x) {
         const int y = i / nc, c = i - y * nc;
         T[(size_t)y * W + v0 + c] = buf[c * H + y];
@@ -878,6 +888,7 @@ __global__ __launch_bounds__(256) void fft_cols_kernel(const FftArgs a) {      /
     fft_cols_body(a, lb % (int)gridDim.x, lb / (int)gridDim.x, gridDim.x);
 }
 
+template <int MAXR = BNERV_FFT_MAX_RADIX>
 __device__ __forceinline__ void fft_rows_adj_body(const FftArgs& a, const int bx) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float2* buf = reinterpret_cast<float2*>(sm);
@@ -933,7 +944,7 @@ __device__ __forceinline__ void fft_rows_adj_body(const FftArgs& a, const int bx
         }
     }
     __syncthreads();
-    fft_adjoint(buf, nlines, W, a.prow, tw);
+    fft_adjoint<MAXR>(buf, nlines, W, a.prow, tw);
     for (int i0 = threadIdx.x; i0 < nlines * W; i0 += blockDim.x * 2 * ROW_U) {
         if (!one_batch) {
 #pragma unroll
@@ -1060,6 +1071,77 @@ __global__ void msssim_final_kernel(const float* __restrict__ msval, float* __re
 }
 
 // =====================================================================================================================
+// single-scale SSIM losses (hnerv_utils.py:342-361, :387-395: SSIM, Fusion1-6, Fusion9, L1_ssim_freq)
+// =====================================================================================================================
+// loss_b = c_l1 mean|d| + c_l2 mean d^2 + c_ss (1 - mean_c ssim_{b,c}) + c_fft (spectral term); ssim_{b,c} = mean of lum * cs over the valid
+// window positions of level 0 -- ssim_fwd_body(LAST = true) and ssim_bwd_body<true> as they stand, without a pyramid.  The term is LINEAR in
+// the map, so the chain coefficient is the constant SsimArgs::coef_k: no coefficient launch, and the gradient tiles wait for no reduction.
+//   head:  the L1 / L2 partial sums | the statistics tiles
+//   tail:  the gradient tiles (+ L1 / L2 terms, added to the spectral gradient where there is one) | the final block
+// 2 launches per value + gradient call; 5 with the spectral term (row FFTs, head, column FFTs, adjoint row FFTs writing `grad`, tail).
+
+// ssim_{b,c} of one plane from its tile partials: ONE wave (tile_sum_d, the reduction of ms_coef_body)
+__device__ __forceinline__ void ssim_plane_body(const float* __restrict__ part, const int nt, const float inv_nvalid, float* val, const int bc) {
+    const double s = tile_sum_d(part + (size_t)bc * nt, nt);
+    if ((threadIdx.x & 63) == 0) val[bc] = (float)(s * (double)inv_nvalid);
+}
+struct SsimFinalArgs { const float* part; float* val; float inv_nvalid; int tiles, BC; FinalArgs fin; };
+// every plane's value, the planes over the block's waves; the block may read a.val afterwards
+__device__ __forceinline__ void ssim_planes_body(const SsimFinalArgs& a) {
+    const int nw = (int)blockDim.x >> 6;
+    for (int bc = threadIdx.x >> 6; bc < a.BC; bc += nw) ssim_plane_body(a.part, a.tiles, a.inv_nvalid, a.val, bc);
+    __threadfence();
+    __syncthreads();
+}
+// ... then loss_final_body on wave 0 with (msval, c_ms) = (the planes' SSIM, c_ss): the same combine
+__device__ __forceinline__ void ssim_final_body(const SsimFinalArgs& a) {
+    ssim_planes_body(a);
+    if (threadIdx.x < 64) loss_final_body(a.fin);
+}
+__global__ __launch_bounds__(256) void ssim_final_kernel(const SsimFinalArgs a) { ssim_final_body(a); }
+
+// The spectral term of this path holds its own instantiations of the FFT bodies with generic-radix arrays of SSIM_FFT_MAX_RADIX entries: an
+// 11 x 37 frame is a legal size here (no min(H, W) > 160), and 37 is prime.  The kernels of bnerv_loss_fwd_bwd keep BNERV_FFT_MAX_RADIX.
+constexpr int SSIM_FFT_MAX_RADIX = 37;
+__global__ __launch_bounds__(256) void ssim_fft_cols_kernel(const FftArgs a) {
+    const int lb = xcd_remap((int)(blockIdx.x + gridDim.x * blockIdx.y), (int)(gridDim.x * gridDim.y));
+    fft_cols_body<SSIM_FFT_MAX_RADIX>(a, lb % (int)gridDim.x, lb / (int)gridDim.x, gridDim.x);
+}
+__global__ __launch_bounds__(256) void ssim_fft_rows_fwd_kernel(const FftArgs a) { fft_rows_fwd_body<SSIM_FFT_MAX_RADIX>(a, blockIdx.x); }
+__global__ __launch_bounds__(256) void ssim_fft_rows_adj_kernel(const FftArgs a) { fft_rows_adj_body<SSIM_FFT_MAX_RADIX>(a, blockIdx.x); }
+
+// [L1 / L2 partial sums | level-0 statistics tiles].  The row FFTs of the spectral term are NOT a block range of this grid (as they are in
+// loss_head_kernel): their dynamic LDS (25.6 KB at W = 1280) next to the tiles' 22 KB leaves 3 blocks per CU, and the merged kernel measured
+// 5 % (720p) to 16 % (1080p) of the whole call slower than the row FFTs in a launch of their own (profiles/ssim_loss.md).
+struct SsimHeadArgs { SsimArgs s; const float* pred; const float* target; float* stats_part; int nps, n_sums, BC; };
+__global__ __launch_bounds__(256) void ssim_head_kernel(const SsimHeadArgs a) {
+    int b = blockIdx.x;
+    if (b < a.n_sums) { diff_stats_body(a.pred, a.target, a.stats_part, a.nps, b % NSB, b / NSB); return; }   // (NSB is a multiple of 8)
+    b -= a.n_sums;
+    const int nt = a.s.tiles_x * a.s.tiles_y;
+    const int t = xcd_remap(b, nt * a.BC);
+    const int bc = t / nt, r = t - bc * nt;
+    ssim_fwd_body(a.s, true, r % a.s.tiles_x, r / a.s.tiles_x, bc, a.BC);
+}
+
+struct SsimTailArgs { SsimArgs s; SsimFinalArgs fin; int gx, gy, n0, BC; };
+__global__ __launch_bounds__(256) void ssim_tail_kernel(const SsimTailArgs a) {
+    __shared__ __attribute__((aligned(16))) float sl[SSIM_BWD_LDS];
+    if ((int)blockIdx.x < a.n0) { const int b = xcd_remap((int)blockIdx.x, a.n0); const int bx = b % a.gx, r = b / a.gx; ssim_bwd_body<true>(a.s, nullptr, sl, bx, r % a.gy, r / a.gy, a.BC); }
+    else ssim_final_body(a.fin);
+}
+// the metric: out[b] = mean_c ssim_{b,c}, the same sums as stats_out column 3 of the loss (loss_final_body)
+__global__ __launch_bounds__(256) void ssim_metric_kernel(const SsimFinalArgs a, float* __restrict__ out, int B, int C) {
+    ssim_planes_body(a);
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+        double ms = 0.0;
+        for (int c = 0; c < C; ++c) ms += (double)a.val[b * C + c];
+        ms /= C;
+        out[b] = (float)ms;
+    }
+}
+
+// =====================================================================================================================
 // workspace layout
 // =====================================================================================================================
 struct WsLayout {
@@ -1094,6 +1176,35 @@ static WsLayout make_layout(int B, int C, int H, int W, bool use_ms, bool use_ff
     }
     L.total = off;
     return L;
+}
+
+// the single-scale SSIM losses: level 0 only -- three statistic-gradient maps, tile partials, the planes' values, the L1 / L2 and FFT scratch
+static WsLayout make_layout_ssim(int B, int C, int H, int W, bool use_fft) {
+    WsLayout L{};
+    size_t off = 0;
+    auto take = [&](size_t n) { size_t o = off; off = align64(off + n); return o; };
+    const size_t BC = (size_t)B * C;
+    L.stats_part = take((size_t)B * NSB * 2);
+    L.pyr.H[0] = H; L.pyr.W[0] = W;
+    L.Gl[0] = take(3 * BC * H * W);
+    L.tiles[0] = cdiv(H - HW_, STH) * cdiv(W - HW_, STW);
+    L.ssim_part[0] = take(BC * L.tiles[0]);
+    L.msval = take(BC);
+    if (use_fft) {
+        L.ncolblk = cdiv(W / 2 + 1, COLS_PER_BLOCK);
+        L.T = take(BC * H * (size_t)(W / 2 + 1) * 2);
+        L.fft_part = take(BC * L.ncolblk);
+    }
+    L.total = off;
+    return L;
+}
+// level-0 arguments of both passes; G = NULL: value only, the statistic-gradient maps are not written
+static SsimArgs fill_ssim_level0(const float* X, const float* Y, float* ws, const WsLayout& L, float* G, float* grad, float coef_k, float k_l1, float k_l2, int acc) {
+    SsimArgs a{};
+    a.X = X; a.Y = Y; a.partial = ws + L.ssim_part[0]; a.G = G; a.dX = grad; a.H = L.pyr.H[0]; a.W = L.pyr.W[0];
+    a.tiles_x = cdiv(a.W - HW_, STW); a.tiles_y = cdiv(a.H - HW_, STH); a.C1 = 0.01f * 0.01f; a.C2 = 0.03f * 0.03f; a.win = make_win();
+    a.coef = nullptr; a.coef_k = coef_k; a.k_l1 = k_l1; a.k_l2 = k_l2; a.acc = acc;
+    return a;
 }
 
 static bool loss_fused() {                              // BNERV_LOSS_FUSED=0: the level-by-level MS-SSIM launches (A/B switch, read per call: tests compare the forms)
@@ -1415,6 +1526,102 @@ extern "C" int bnerv_msssim(void* stream, const float* x, const float* y, float*
     return BNERV_OK;
 }
 
+extern "C" size_t bnerv_loss_ssim_ws_bytes(int B, int C, int H, int W, int use_fft) {
+    if (B <= 0 || C <= 0 || H <= HW_ || W <= HW_) return 0;
+    return make_layout_ssim(B, C, H, W, use_fft != 0).total * sizeof(float);
+}
+
+// The single-scale SSIM losses: the descriptor of bnerv_loss_fwd_bwd plus c_ssim (c_ms must be 0).  2 launches (4 with a spectral term).
+extern "C" int bnerv_loss_ssim_fwd_bwd(void* stream, const bnerv_loss_desc* dp, float c_ssim) {
+    BNERV_REQUIRE(dp != nullptr, "loss_ssim: null descriptor");
+    const bnerv_loss_desc d = *dp;
+    BNERV_REQUIRE(d.pred && d.target && d.loss_out && d.stats_out && d.ws, "loss_ssim: null tensor");
+    BNERV_REQUIRE(d.B > 0 && d.C > 0 && d.H > 0 && d.W > 0 && d.B <= 65535, "loss_ssim: bad dims");
+    BNERV_REQUIRE((size_t)d.C * d.H * d.W < (size_t)1 << 31, "loss_ssim: sample too large");
+    BNERV_REQUIRE(d.c_ms == 0.f, "loss_ssim: c_ms must be 0 (the MS-SSIM losses go through bnerv_loss_fwd_bwd)");
+    BNERV_REQUIRE(c_ssim != 0.f, "loss_ssim: c_ssim is 0 (losses without an SSIM term go through bnerv_loss_fwd_bwd)");
+    if (d.H <= HW_ || d.W <= HW_) return bnerv_set_error(BNERV_E_ARG, "loss_ssim: SSIM needs min(H,W) >= %d (got %dx%d)", WS_, d.H, d.W);
+    const bool use_fft = d.c_fft != 0.f;
+    const WsLayout L = make_layout_ssim(d.B, d.C, d.H, d.W, use_fft);
+    if (d.ws_bytes < L.total * sizeof(float)) return bnerv_set_error(BNERV_E_WS, "loss_ssim: workspace %zu < %zu", d.ws_bytes, L.total * sizeof(float));
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = reinterpret_cast<float*>(d.ws);
+    const int nps = d.C * d.H * d.W, BC = d.B * d.C;
+    BNERV_REQUIRE((size_t)L.tiles[0] * BC + (size_t)BC * d.H + (size_t)NSB * d.B < (size_t)1 << 30, "loss_ssim: batch too large for one grid");
+    const float k_l1 = d.c_l1 / ((float)d.B * (float)nps), k_l2 = 2.0f * d.c_l2 / ((float)d.B * (float)nps);
+    const float inv_nvalid = 1.0f / ((float)(d.H - HW_) * (float)(d.W - HW_));
+    SsimHeadArgs ha{};
+    FftArgs fa{};
+    size_t lds_row = 0, lds_col = 0;
+    int n_fft = 0;
+    if (use_fft) {
+        FftArgs& a = fa;
+        if (!make_plan(d.W, &a.prow, SSIM_FFT_MAX_RADIX) || !make_plan(d.H, &a.pcol, SSIM_FFT_MAX_RADIX))
+            return bnerv_set_error(BNERV_E_ARG, "loss_ssim: FFT size %dx%d has a prime factor > %d", d.H, d.W, SSIM_FFT_MAX_RADIX);
+        BNERV_REQUIRE(BC <= 65535, "loss_ssim: B * C > 65535 with a spectral term");
+        a.pred = d.pred; a.target = d.target; a.T = reinterpret_cast<float2*>(ws + L.T); a.Wh = d.W / 2 + 1; a.partial = ws + L.fft_part; a.grad = d.grad;
+        a.BC = BC; a.H = d.H; a.W = d.W; a.gscale = d.c_fft / ((float)d.B * (float)nps * 2.0f); a.accumulate = 0;
+        lds_row = (size_t)(LINES_PER_BLOCK + 1) * d.W * sizeof(float2) + (size_t)d.W * sizeof(int); lds_col = (size_t)(COLS_PER_BLOCK + 1) * d.H * sizeof(float2);
+        BNERV_REQUIRE(lds_row <= 128 * 1024 && lds_col <= 160 * 1024, "loss_ssim: frame %dx%d too large for the LDS FFT", d.H, d.W);
+        n_fft = cdiv(BC * d.H, ROWS_PER_BLOCK);
+        if (const int rc_lds = dyn_lds<&ssim_fft_rows_fwd_kernel>(lds_row, "ssim_fft_rows_fwd")) return rc_lds;
+        hipLaunchKernelGGL(ssim_fft_rows_fwd_kernel, dim3(n_fft), dim3(256), lds_row, st, fa);
+        BNERV_LAUNCH_CHECK("ssim_fft_rows_fwd");
+    }
+    // the statistic-gradient maps are written only where a gradient is asked for
+    ha.s = fill_ssim_level0(d.pred, d.target, ws, L, d.grad ? ws + L.Gl[0] : nullptr, d.grad, (-c_ssim / (float)BC) * inv_nvalid, k_l1, k_l2, use_fft ? 1 : 0);
+    ha.pred = d.pred; ha.target = d.target; ha.stats_part = ws + L.stats_part; ha.nps = nps; ha.n_sums = NSB * d.B; ha.BC = BC;
+    hipLaunchKernelGGL(ssim_head_kernel, dim3(ha.n_sums + L.tiles[0] * BC), dim3(256), 0, st, ha);
+    BNERV_LAUNCH_CHECK("ssim_head");
+    if (use_fft) {
+        if (const int rc_lds = dyn_lds<&ssim_fft_cols_kernel>(lds_col, "ssim_fft_cols")) return rc_lds;
+        hipLaunchKernelGGL(ssim_fft_cols_kernel, dim3(L.ncolblk, BC), dim3(256), lds_col, st, fa);
+        BNERV_LAUNCH_CHECK("ssim_fft_cols");
+        if (d.grad) {                                                      // the spectral gradient, WRITTEN: the tail adds to it
+            if (const int rc_lds = dyn_lds<&ssim_fft_rows_adj_kernel>(lds_row, "ssim_fft_rows_adj")) return rc_lds;
+            hipLaunchKernelGGL(ssim_fft_rows_adj_kernel, dim3(n_fft), dim3(256), lds_row, st, fa);
+            BNERV_LAUNCH_CHECK("ssim_fft_rows_adj");
+        }
+    }
+    SsimTailArgs ta{};
+    ta.s = ha.s;
+    SsimFinalArgs& sf = ta.fin;
+    sf.part = ws + L.ssim_part[0]; sf.val = ws + L.msval; sf.inv_nvalid = inv_nvalid; sf.tiles = L.tiles[0]; sf.BC = BC;
+    FinalArgs& f = sf.fin;
+    f.stats_part = ws + L.stats_part; f.msval = ws + L.msval; f.fft_part = use_fft ? ws + L.fft_part : nullptr;
+    f.loss_out = d.loss_out; f.stats_out = d.stats_out; f.B = d.B; f.C = d.C; f.n_per_sample = nps; f.ncolblk = L.ncolblk;
+    f.c_l1 = d.c_l1; f.c_l2 = d.c_l2; f.c_ms = c_ssim; f.c_fft = d.c_fft;
+    if (d.grad) {
+        ta.gx = cdiv(d.W, STW); ta.gy = cdiv(d.H, STH); ta.BC = BC; ta.n0 = ta.gx * ta.gy * BC;
+        hipLaunchKernelGGL(ssim_tail_kernel, dim3(ta.n0 + 1), dim3(256), 0, st, ta);
+        BNERV_LAUNCH_CHECK("ssim_tail");
+    } else {
+        hipLaunchKernelGGL(ssim_final_kernel, dim3(1), dim3(256), 0, st, ta.fin);
+        BNERV_LAUNCH_CHECK("ssim_final");
+    }
+    return BNERV_OK;
+}
+
+// per-sample SSIM only: out [B]; ws: bnerv_loss_ssim_ws_bytes(B, C, H, W, 0)
+extern "C" int bnerv_ssim(void* stream, const float* x, const float* y, float* out, void* wsv, size_t ws_bytes, int B, int C, int H, int W) {
+    BNERV_REQUIRE(x && y && out && wsv && B > 0 && C > 0, "ssim: bad args");
+    if (H <= HW_ || W <= HW_) return bnerv_set_error(BNERV_E_ARG, "ssim: needs min(H,W) >= %d (got %dx%d)", WS_, H, W);
+    const WsLayout L = make_layout_ssim(B, C, H, W, false);
+    if (ws_bytes < L.total * sizeof(float)) return bnerv_set_error(BNERV_E_WS, "ssim: workspace %zu < %zu", ws_bytes, L.total * sizeof(float));
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = reinterpret_cast<float*>(wsv);
+    const int BC = B * C;
+    BNERV_REQUIRE(BC <= 65535, "ssim: batch too large");
+    const SsimArgs a = fill_ssim_level0(x, y, ws, L, nullptr, nullptr, 0.f, 0.f, 0.f, 0);
+    hipLaunchKernelGGL(ssim_fwd_kernel<true>, dim3(a.tiles_x, a.tiles_y, BC), dim3(256), 0, st, a);
+    BNERV_LAUNCH_CHECK("ssim_fwd");
+    SsimFinalArgs sf{};
+    sf.part = ws + L.ssim_part[0]; sf.val = ws + L.msval; sf.inv_nvalid = 1.0f / ((float)(H - HW_) * (float)(W - HW_)); sf.tiles = L.tiles[0]; sf.BC = BC;
+    hipLaunchKernelGGL(ssim_metric_kernel, dim3(1), dim3(256), 0, st, sf, out, B, C);
+    BNERV_LAUNCH_CHECK("ssim_metric");
+    return BNERV_OK;
+}
+
 extern "C" size_t bnerv_psnr_ws_bytes(int B, int C, int H, int W) { (void)C; (void)H; (void)W; return B > 0 ? (size_t)B * NSB * 2 * sizeof(float) : 0; }
 
 extern "C" int bnerv_psnr(void* stream, const float* o, const float* gt, float* psnr, void* ws, size_t ws_bytes, int B, int C, int H, int W) {
@@ -1434,5 +1641,13 @@ extern "C" int bnerv_psnr(void* stream, const float* o, const float* gt, float* 
 extern "C" int bnerv_fft_prepare(int H, int W) {
     FftPlan p;
     if (!make_plan(H, &p) || !make_plan(W, &p)) return bnerv_set_error(BNERV_E_ARG, "fft_prepare: %dx%d unsupported", H, W);
+    return BNERV_OK;
+}
+
+// The same for bnerv_loss_ssim_fwd_bwd with a spectral term, whose instantiations take prime factors up to SSIM_FFT_MAX_RADIX.
+extern "C" int bnerv_loss_ssim_prepare(int H, int W) {
+    FftPlan p;
+    if (!make_plan(H, &p, SSIM_FFT_MAX_RADIX) || !make_plan(W, &p, SSIM_FFT_MAX_RADIX))
+        return bnerv_set_error(BNERV_E_ARG, "loss_ssim_prepare: %dx%d has a prime factor > %d", H, W, SSIM_FFT_MAX_RADIX);
     return BNERV_OK;
 }

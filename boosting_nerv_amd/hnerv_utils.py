@@ -227,8 +227,10 @@ def adjust_lr(optimizer, cur_epoch, cur_iter, args):
 # loss and metrics                                                           reference hnerv_utils.py:335-419
 # ----------------------------------------------------------------------------------------------------------------------
 def loss_fn(pred, target, loss_type="L2", batch_average=True):
-    """Value + gradient come from one fused HIP call (bnerv_loss_fwd_bwd).  Supported: the variants the recipes use
-    (Fusion10_freq for the boost models) plus L1, L2, L1_freq, Fusion10/11/12."""
+    """Value + gradient come from one fused HIP call.  Every variant of the reference is built: L1, L2, L1_freq, Fusion7/8 and the
+    MS-SSIM mixes Fusion10/11/12, Fusion10_freq (bnerv_loss_fwd_bwd; MS-SSIM needs min(H, W) > 160), and the single-scale SSIM mixes
+    SSIM, Fusion1-6, Fusion9, L1_ssim_freq (bnerv_loss_ssim_fwd_bwd; min(H, W) >= 11 -- a smaller frame raises NotImplementedError,
+    where the reference skips the filter along the short side)."""
     loss, stats = ops.loss_with_stats(pred, target, loss_type)
     if batch_average:
         return loss

@@ -1029,46 +1029,82 @@ LOSS_COEFFS = {            # (c_l1, c_l2, c_ms, c_fft) per hnerv_utils.py:338-38
     "L1": (1.0, 0.0, 0.0, 0.0),
     "L2": (0.0, 1.0, 0.0, 0.0),
     "L1_freq": (60.0, 0.0, 0.0, 1.0),
+    "Fusion7": (0.3, 0.7, 0.0, 0.0),
+    "Fusion8": (0.5, 0.5, 0.0, 0.0),
     "Fusion10": (0.7, 0.0, 0.3, 0.0),
     "Fusion11": (0.9, 0.0, 0.1, 0.0),
     "Fusion12": (0.8, 0.0, 0.2, 0.0),
     "Fusion10_freq": (60 * 0.7, 0.0, 60 * 0.3, 1.0),
 }
+SSIM_LOSS_COEFFS = {       # (c_l1, c_l2, c_ss, c_fft) per hnerv_utils.py:342-361, :387-395: the single-scale SSIM term (bnerv_loss_ssim_fwd_bwd)
+    "SSIM": (0.0, 0.0, 1.0, 0.0),
+    "Fusion1": (0.0, 0.3, 0.7, 0.0),
+    "Fusion2": (0.3, 0.0, 0.7, 0.0),
+    "Fusion3": (0.0, 0.5, 0.5, 0.0),
+    "Fusion4": (0.5, 0.0, 0.5, 0.0),
+    "Fusion5": (0.0, 0.7, 0.3, 0.0),
+    "Fusion6": (0.7, 0.0, 0.3, 0.0),
+    "Fusion9": (0.9, 0.0, 0.1, 0.0),
+    "L1_ssim_freq": (60 * 0.7, 0.0, 60 * 0.3, 1.0),
+}
+SSIM_MIN_SIDE = 11         # the 11-tap window.  The reference skips the filter along a shorter side; this path declines such frames
+
+
+def loss_coeffs(loss_type):
+    """(c_l1, c_l2, c_ms, c_ss, c_fft) of a loss type; NotImplementedError for a name the HIP path does not build."""
+    if loss_type in LOSS_COEFFS:
+        c1, c2, cm, cf = LOSS_COEFFS[loss_type]
+        return (c1, c2, cm, 0.0, cf)
+    if loss_type in SSIM_LOSS_COEFFS:
+        c1, c2, cs, cf = SSIM_LOSS_COEFFS[loss_type]
+        return (c1, c2, 0.0, cs, cf)
+    raise NotImplementedError(f"loss type {loss_type!r} is not on the HIP path; supported: {sorted(LOSS_COEFFS) + sorted(SSIM_LOSS_COEFFS)}")
+
+
+def _loss_plan(pred, loss_type):
+    """Coefficients of `loss_type` for this frame size -- checked BEFORE anything touches the device."""
+    coeffs = loss_coeffs(loss_type)
+    if coeffs[3] and min(pred.shape[-2:]) < SSIM_MIN_SIDE:
+        raise NotImplementedError(f"loss type {loss_type!r}: the SSIM window needs min(H, W) >= {SSIM_MIN_SIDE}, got {tuple(pred.shape[-2:])}")
+    return coeffs
 
 _fft_ready = set()
 
 
-def prepare_loss(H, W):
-    """Build the FFT twiddle tables for HxW frames (must happen outside hipGraph capture)."""
-    if (H, W) not in _fft_ready:
-        L.check(L.load().bnerv_fft_prepare(H, W), "bnerv_fft_prepare")
-        _fft_ready.add((H, W))
+def prepare_loss(H, W, ssim=False):
+    """Build the FFT twiddle tables for HxW frames (must happen outside hipGraph capture).  ssim: for the single-scale SSIM path, whose
+    FFT kernels take prime factors up to 37."""
+    if (H, W, ssim) not in _fft_ready:
+        name = "bnerv_loss_ssim_prepare" if ssim else "bnerv_fft_prepare"
+        L.check(getattr(L.load(), name)(H, W), name)
+        _fft_ready.add((H, W, ssim))
 
 
 def _loss_launch(pred, target, coeffs, need_grad):
     """One fused call: loss value, per-sample stats and (optionally) d loss / d pred."""
     pred = L.f32c(L.require_device(pred, "pred")); target = L.f32c(target.detach())
     B, Cc, H, W = pred.shape
-    c1, c2, cm, cf = coeffs
+    c1, c2, cm, cs, cf = coeffs
     lib = L.load()
     if cf:
-        prepare_loss(H, W)
-    nbytes = lib.bnerv_loss_ws_bytes(B, Cc, H, W, int(cm != 0), int(cf != 0))
+        prepare_loss(H, W, ssim=bool(cs))
+    nbytes = lib.bnerv_loss_ssim_ws_bytes(B, Cc, H, W, int(cf != 0)) if cs else lib.bnerv_loss_ws_bytes(B, Cc, H, W, int(cm != 0), int(cf != 0))
     ws = _ws(nbytes, pred.device)
     grad = torch.empty_like(pred) if need_grad else None
     loss = torch.empty(1, dtype=torch.float32, device=pred.device)
     stats = torch.empty(B, L.LOSS_STATS, dtype=torch.float32, device=pred.device)
     d = L.LossDesc(L.ptr(pred), L.ptr(target), L.ptr(grad), L.ptr(loss), L.ptr(stats), L.ptr(ws), nbytes, B, Cc, H, W, c1, c2, cm, cf)
-    L.check(lib.bnerv_loss_fwd_bwd(L.stream(), C.byref(d)), "bnerv_loss_fwd_bwd")
+    if cs:      # the single-scale SSIM losses: level 0 only, two launches (five with the spectral term)
+        L.check(lib.bnerv_loss_ssim_fwd_bwd(L.stream(), C.byref(d), cs), "bnerv_loss_ssim_fwd_bwd")
+    else:
+        L.check(lib.bnerv_loss_fwd_bwd(L.stream(), C.byref(d)), "bnerv_loss_fwd_bwd")
     return loss, stats, grad
 
 
 def loss_value_grad_stats(pred, target, loss_type="Fusion10_freq"):
     """(loss [scalar], stats [B,5], d loss/d pred) without an autograd node: the train step seeds pred.backward(grad) with
     the gradient directly (no ones-fill, no grad * 1 pass over the frame) and reads the per-sample PSNR from stats[:, 4]."""
-    if loss_type not in LOSS_COEFFS:
-        raise NotImplementedError(f"loss type {loss_type!r} is not on the HIP path; supported: {sorted(LOSS_COEFFS)}")
-    loss, stats, grad = _loss_launch(pred.detach(), target, LOSS_COEFFS[loss_type], True)
+    loss, stats, grad = _loss_launch(pred.detach(), target, _loss_plan(pred, loss_type), True)
     return loss.reshape(()), stats, grad
 
 
@@ -1088,10 +1124,9 @@ class _Loss(torch.autograd.Function):
 
 
 def loss_with_stats(pred, target, loss_type="Fusion10_freq"):
-    """Returns (batch-mean loss [scalar tensor], stats [B,5] = {loss_b, sum|d|, sum d^2, ms_ssim_b, psnr_b})."""
-    if loss_type not in LOSS_COEFFS:
-        raise NotImplementedError(f"loss type {loss_type!r} is not on the HIP path; supported: {sorted(LOSS_COEFFS)}")
-    return _Loss.apply(pred, target, LOSS_COEFFS[loss_type])
+    """Returns (batch-mean loss [scalar tensor], stats [B,5] = {loss_b, sum|d|, sum d^2, ms_ssim_b, psnr_b}); column 3 carries ssim_b for
+    the single-scale SSIM losses (SSIM_LOSS_COEFFS)."""
+    return _Loss.apply(pred, target, _loss_plan(pred, loss_type))
 
 
 def psnr(output, gt):
@@ -1115,4 +1150,18 @@ def msssim(x, y):
     ws = _ws(nbytes, x.device)
     out = torch.empty(B, dtype=torch.float32, device=x.device)
     L.check(lib.bnerv_msssim(L.stream(), L.ptr(x), L.ptr(y), L.ptr(out), L.ptr(ws), nbytes, B, Cc, H, W), "bnerv_msssim")
+    return out
+
+
+def ssim(x, y):
+    """ssim(x, y, data_range=1, size_average=False) per sample, on the device: the bits of stats[:, 3] of the SSIM losses."""
+    if min(x.shape[-2:]) < SSIM_MIN_SIDE:
+        raise NotImplementedError(f"ssim: the window needs min(H, W) >= {SSIM_MIN_SIDE}, got {tuple(x.shape[-2:])}")
+    x = L.f32c(L.require_device(x.detach(), "x")); y = L.f32c(y.detach())
+    B, Cc, H, W = x.shape
+    lib = L.load()
+    nbytes = lib.bnerv_loss_ssim_ws_bytes(B, Cc, H, W, 0)
+    ws = _ws(nbytes, x.device)
+    out = torch.empty(B, dtype=torch.float32, device=x.device)
+    L.check(lib.bnerv_ssim(L.stream(), L.ptr(x), L.ptr(y), L.ptr(out), L.ptr(ws), nbytes, B, Cc, H, W), "bnerv_ssim")
     return out

@@ -364,14 +364,23 @@ size_t bnerv_dwconv_wgrad_ws_bytes(int B, int C, int H, int W, int K);
 int bnerv_dwconv_wgrad(void* stream, const float* x, const float* g, float* dwb, void* ws, size_t ws_bytes, int B, int C, int H, int W, int K, bnerv_ctx* defer_ctx);
 
 /* ------------------------------------------------------------------------------------------------------------------
- * Loss and metrics.  Replaces loss_fn (hnerv_utils.py:335-397; variants L1, L2, L1_freq, Fusion10, Fusion10_freq)
- * including its autograd backward, and psnr_fn_single (hnerv_utils.py:400-403).
- *   loss_b = c_l1 * mean|d| + c_l2 * mean d^2 + c_ms * (1 - ms_ssim_b) + c_fft * mean|FFT2(pred)-FFT2(target)|_{re,im}
+ * Loss and metrics.  Replaces loss_fn (hnerv_utils.py:335-397; every variant) including its autograd backward, and
+ * psnr_fn_single (hnerv_utils.py:400-403).
+ *   loss_b = c_l1 * mean|d| + c_l2 * mean d^2 + c_ms * (1 - ms_ssim_b) + c_ss * (1 - ssim_b)
+ *            + c_fft * mean|FFT2(pred)-FFT2(target)|_{re,im}
  * with d = pred - target; the reported loss is mean_b loss_b (batch_average=True) and `grad` = d(loss)/d(pred).
- *   L1: c_l1=1   L2: c_l2=1   L1_freq: c_l1=60,c_fft=1   Fusion10: c_l1=.7,c_ms=.3   Fusion10_freq: c_l1=42,c_ms=18,c_fft=1
- * MS-SSIM follows pytorch_msssim 0.2.1 (win 11, sigma 1.5, 5 levels) -- third-party, PARITY UNPINNED.
+ *   bnerv_loss_fwd_bwd (c_ss = 0):
+ *     L1: c_l1=1   L2: c_l2=1   L1_freq: c_l1=60,c_fft=1   Fusion7: c_l1=.3,c_l2=.7   Fusion8: c_l1=.5,c_l2=.5
+ *     Fusion10/11/12: c_l1=.7/.9/.8,c_ms=.3/.1/.2   Fusion10_freq: c_l1=42,c_ms=18,c_fft=1
+ *   bnerv_loss_ssim_fwd_bwd (c_ms = 0, c_ss = its c_ssim argument):
+ *     SSIM: c_ss=1   Fusion1/3/5: c_l2=.3/.5/.7,c_ss=.7/.5/.3   Fusion2/4/6/9: c_l1=.3/.5/.7/.9,c_ss=.7/.5/.3/.1
+ *     L1_ssim_freq: c_l1=42,c_ss=18,c_fft=1
+ * MS-SSIM and SSIM follow pytorch_msssim 0.2.1 (win 11, sigma 1.5; 5 levels / one level, ssim_b = mean over channels and valid window
+ * positions of lum * cs, no relu) -- third-party, PARITY UNPINNED.  MS-SSIM needs min(H, W) > 160, SSIM min(H, W) >= 11.
  * The 2-D DFT is a mixed-radix LDS FFT; H and W may have any prime factors <= BNERV_FFT_MAX_RADIX.
- * stats_out: [B, BNERV_LOSS_STATS] = {loss_b, sum|d|, sum d^2, ms_ssim_b, psnr_b (hnerv_utils.py:400-403)};  loss_out: [1].
+ * (bnerv_loss_ssim_fwd_bwd, whose frames may be as small as 11 x 11: <= 37, its own kernel instantiations).
+ * stats_out: [B, BNERV_LOSS_STATS] = {loss_b, sum|d|, sum d^2, ms_ssim_b (bnerv_loss_ssim_fwd_bwd: ssim_b), psnr_b (hnerv_utils.py:400-403)};
+ * loss_out: [1].
  * ------------------------------------------------------------------------------------------------------------------ */
 #define BNERV_FFT_MAX_RADIX 31
 #define BNERV_MSSSIM_LEVELS 5
@@ -395,6 +404,16 @@ int bnerv_fft_prepare(int H, int W);
 int bnerv_loss_fwd_bwd(void* stream, const bnerv_loss_desc* d);
 /* per-sample MS-SSIM only (evaluate(): msssim_fn_single, hnerv_utils.py:410-412); out [B] */
 int bnerv_msssim(void* stream, const float* x, const float* y, float* out, void* ws, size_t ws_bytes, int B, int C, int H, int W);
+/* The single-scale SSIM losses (an additive entry of ABI 9): the descriptor of bnerv_loss_fwd_bwd with c_ms == 0, plus c_ssim != 0.  Level 0
+ * only, no pyramid: two launches per value + gradient call, five with a spectral term.  grad == NULL: value and stats only.
+ * ws: bnerv_loss_ssim_ws_bytes(B, C, H, W, c_fft != 0).  bnerv_loss_ssim_prepare(H, W) is this path's bnerv_fft_prepare (prime factors
+ * <= 37): call it before a capture when c_fft != 0.  bnerv_fft_prepare itself keeps the BNERV_FFT_MAX_RADIX limit. */
+size_t bnerv_loss_ssim_ws_bytes(int B, int C, int H, int W, int use_fft);
+int bnerv_loss_ssim_prepare(int H, int W);
+int bnerv_loss_ssim_fwd_bwd(void* stream, const bnerv_loss_desc* d, float c_ssim);
+/* per-sample SSIM only (ssim(x, y, data_range=1, size_average=False)); out [B], the bits of stats_out column 3 above;
+ * ws: bnerv_loss_ssim_ws_bytes(B, C, H, W, 0) */
+int bnerv_ssim(void* stream, const float* x, const float* y, float* out, void* ws, size_t ws_bytes, int B, int C, int H, int W);
 /* (ABI 9) The output head's tanh-gradient as a tensor: gt = g * 0.5 (1 - (2 img - 1)^2), the derivative of OutImg's tanh(v) * 0.5 + 0.5
  * (reference model_blocks.py:57-63) applied to the incoming gradient -- what the IN_TANHGRAD prologue computes on the fly -- with the
  * per-block channel sums of gt in part [B * bnerv_tanh_grad_blocks(HW)][C] (sum over the first index = the head's bias gradient:

@@ -3,7 +3,8 @@ the captured HIP step (encoder, decoder, L2, backward, fused Adam on a resident 
 (tests/hnerv_ref.py, fp32, no TF32-style downgrade), each measurement in a FRESH child process, alternated, `--repeats` times.
 Prints ms/step for both, the spread over the repeats and algorithmic FLOP over time; exits 1 if the HIP step is slower than the
 stock-ops step by more than the measured spread.
-usage: python tools/khnerv.py [--steps 200] [--repeats 3]        (needs the GPU; `--role hip|stock` is the child form)"""
+usage: python tools/khnerv.py [--steps 200] [--repeats 3] [--loss L2]   (needs the GPU; `--role hip|stock` is the child form; --loss: the HIP
+step's loss, e.g. Fusion6 -- the stock-ops step stays L2)"""
 import argparse
 import json
 import os
@@ -31,7 +32,7 @@ def step_gflop(sd):
     return 3 * total / 1e9
 
 
-def child(role, steps):
+def child(role, steps, loss="L2"):
     import torch
     import hnerv_ref
     from boosting_nerv_amd.model_hnerv import HNeRV
@@ -48,7 +49,7 @@ def child(role, steps):
         from boosting_nerv_amd.optimizer import Adam
         model = model.to(dev)
         opt = Adam(model.parameters(), lr=1e-3)
-        step = TrainStep(model, opt, "L2", True, (1, 3, 720, 1280), dev, use_graph=True, warmup_eager=3)
+        step = TrainStep(model, opt, loss, True, (1, 3, 720, 1280), dev, use_graph=True, warmup_eager=3)
         step.bind_clip(frames, torch.tensor([(i + 1) / N_FRAMES for i in range(N_FRAMES)], dtype=torch.float64, device=dev))
         run = lambda s: step.step_frame(s % N_FRAMES)
         for s in range(10):
@@ -73,7 +74,7 @@ def child(role, steps):
         run(10 + s)
     torch.cuda.synchronize()
     ms = (time.time() - t0) / steps * 1e3
-    print(json.dumps({"role": role, "ms_per_step": ms, "steps": steps, "step_gflop": gf, "tflops": gf / ms, "psnr_last": last()}), flush=True)
+    print(json.dumps({"role": role, "loss": loss if role == "hip" else "L2", "ms_per_step": ms, "steps": steps, "step_gflop": gf, "tflops": gf / ms, "psnr_last": last()}), flush=True)
 
 
 def main():
@@ -81,14 +82,15 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--role", choices=["hip", "stock"], default=None)
+    ap.add_argument("--loss", default="L2", help="loss of the HIP step (the stock-ops step is always L2)")
     a = ap.parse_args()
     if a.role:
-        child(a.role, a.steps)
+        child(a.role, a.steps, a.loss)
         return 0
     res = {"hip": [], "stock": []}
     for r in range(a.repeats):
         for role in ("hip", "stock"):
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--role", role, "--steps", str(a.steps)], capture_output=True, text=True, timeout=900)
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--role", role, "--steps", str(a.steps), "--loss", a.loss], capture_output=True, text=True, timeout=900)
             if p.returncode != 0:
                 print(p.stdout[-2000:] + p.stderr[-4000:])
                 print(f"khnerv: the {role} child failed (exit {p.returncode}); nothing more is started")
