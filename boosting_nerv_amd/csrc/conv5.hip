@@ -434,7 +434,7 @@ static int conv5_validate(const bnerv_conv_desc* d) {
     BNERV_REQUIRE(d->Cin % (in_s * in_s) == 0, "conv5_igemm: Cin=%d not divisible by in_s^2", d->Cin);
     if (d->transposed) BNERV_REQUIRE(d->wCi == d->Cout && d->wCo == d->Cin, "conv5_igemm: transposed weight shape [%d,%d] vs Cin=%d Cout=%d", d->wCo, d->wCi, d->Cin, d->Cout);
     else BNERV_REQUIRE(d->wCo == d->Cout && d->wCi == d->Cin, "conv5_igemm: weight shape [%d,%d] vs Cout=%d Cin=%d", d->wCo, d->wCi, d->Cout, d->Cin);
-    if (d->out_s == 2) BNERV_REQUIRE((reinterpret_cast<uintptr_t>(d->out) & 7) == 0 && (reinterpret_cast<uintptr_t>(d->out2) & 7) == 0, "conv5_igemm: shuffled outputs must be 8-byte aligned");
+    if (d->out_s == 2) BNERV_REQUIRE((reinterpret_cast<uintptr_t>(d->out) & 7) == 0 && (reinterpret_cast<uintptr_t>(d->out2) & 7) == 0, "conv5_igemm: out and out2 must be 8-byte aligned when out_s == 2");
     return BNERV_OK;
 }
 
@@ -448,7 +448,7 @@ extern "C" size_t bnerv_conv5_ws_bytes(int Cin, int Cout) {
 extern "C" int bnerv_conv5_igemm(void* stream, const bnerv_conv_desc* d, void* ws, size_t ws_bytes) {
     const int rc = conv5_validate(d);
     if (rc) return rc;
-    BNERV_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "conv5_igemm: workspace must be a 16-byte aligned device buffer");
+    BNERV_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "conv5_igemm: workspace ws must be a 16-byte aligned device buffer");
     if (ws_bytes < bnerv_conv5_ws_bytes(d->Cin, d->Cout)) return bnerv_set_error(BNERV_E_WS, "conv5_igemm: workspace %zu < %zu bytes", ws_bytes, bnerv_conv5_ws_bytes(d->Cin, d->Cout));
     C5Args ka;
     ka.d = *d;

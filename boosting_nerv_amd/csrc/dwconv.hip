@@ -16,7 +16,7 @@ constexpr int KMAX = 7, PMAX = KMAX / 2;
 
 template <bool FLIP>
 __global__ __launch_bounds__(256) void dwconv_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                                     float* __restrict__ y, int C, int H, int W, int K) {
+                                                     float* __restrict__ y, int C, int H, int W, int K, const int vec) {
     __shared__ float s_x[DTH + 2 * PMAX][DTW + 2 * PMAX + 2];
     __shared__ float s_w[KMAX * KMAX];
     const int P = K / 2, T = K * K;
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const float* __restrict__ x
     const int gy = y0 + ty, gx = x0 + tx;
     if (gy < H) {
         float* yp = y + (size_t)bc * H * W + (size_t)gy * W + gx;
-        if (gx + 3 < W && (W & 3) == 0) {
+        if (vec && gx + 3 < W) {
             *reinterpret_cast<f32x4*>(yp) = f32x4{a0 + bv, a1 + bv, a2 + bv, a3 + bv};
         } else {
             if (gx < W) yp[0] = a0 + bv;
@@ -147,8 +147,9 @@ extern "C" int bnerv_dwconv_fwd(void* stream, const float* x, const float* w, co
     BNERV_REQUIRE(K >= 1 && K <= KMAX && (K & 1) == 1, "dwconv_fwd: K must be odd and <= %d (got %d)", KMAX, K);
     BNERV_REQUIRE((size_t)B * C <= 65535, "dwconv_fwd: B*C too large");
     dim3 grid(cdiv(W, DTW), cdiv(H, DTH), B * C);
-    if (flip) hipLaunchKernelGGL(dwconv_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, w, bias, y, C, H, W, K);
-    else hipLaunchKernelGGL(dwconv_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, w, bias, y, C, H, W, K);
+    const int vec = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(y) & 15) == 0;          // float4 stores need 16-byte aligned rows of y
+    if (flip) hipLaunchKernelGGL(dwconv_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, w, bias, y, C, H, W, K, vec);
+    else hipLaunchKernelGGL(dwconv_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, w, bias, y, C, H, W, K, vec);
     BNERV_LAUNCH_CHECK("dwconv");
     return BNERV_OK;
 }

@@ -11,13 +11,12 @@ namespace {
 constexpr int TG_PER_BLOCK = 8192;      // elements of one plane per block (256 threads x 8 float4)
 
 __global__ __launch_bounds__(256) void tanh_grad_kernel(const float* __restrict__ g, const float* __restrict__ img, float* __restrict__ gt,
-                                                        float* __restrict__ part, int C, int HW, int nblk) {
+                                                        float* __restrict__ part, int C, int HW, int nblk, const int vec) {
     __shared__ float s_red[4];
     const int bc = blockIdx.y, blk = blockIdx.x;
     const size_t base = (size_t)bc * HW;
     const int e0 = blk * TG_PER_BLOCK;
     float acc = 0.f;
-    const bool vec = (HW & 3) == 0;
     if (vec) {
 #pragma unroll
         for (int u = 0; u < TG_PER_BLOCK / 1024; ++u) {
@@ -103,9 +102,10 @@ extern "C" int bnerv_tanh_grad_blocks(int HW) { return HW > 0 ? cdiv(HW, TG_PER_
 extern "C" int bnerv_tanh_grad(void* stream, const float* g, const float* img, float* gt, float* part, int B, int C, int HW) {
     BNERV_REQUIRE(g && img && gt && part && B > 0 && C > 0 && HW > 0, "tanh_grad: bad args");
     BNERV_REQUIRE((size_t)B * C <= 65535, "tanh_grad: B * C too large");
-    if ((HW & 3) == 0) BNERV_REQUIRE(((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(gt)) & 15) == 0, "tanh_grad: tensors must be 16-byte aligned");
+    // float4 form: every plane starts on a 16-byte boundary (HW % 4 == 0 and aligned tensors); otherwise the scalar loop
+    const int vec = (HW % 4 == 0) && ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(gt)) & 15) == 0;
     const int nblk = cdiv(HW, TG_PER_BLOCK);
-    hipLaunchKernelGGL(tanh_grad_kernel, dim3(nblk, B * C), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), g, img, gt, part, C, HW, nblk);
+    hipLaunchKernelGGL(tanh_grad_kernel, dim3(nblk, B * C), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), g, img, gt, part, C, HW, nblk, vec);
     BNERV_LAUNCH_CHECK("tanh_grad");
     return BNERV_OK;
 }

@@ -155,6 +155,7 @@ struct MlpArgs {
     float* out; float* hsave;                              // forward (hsave: [B, 4C, HW] pre-activations kept for backward, or NULL)
     const float* dout; const float* hin; float* dx; float* gbuf; float* dhbuf;   // backward
     int B, C, HW;
+    int b1_vec;                                            // forward: b1 is 16-byte aligned (launcher-side flag for its float4 loads)
 };
 
 // A fragments of W1 for hidden tile t, k step s (input channels 4s .. 4s+3): lane (m = li, kq) <- w1[16 t + li][4 s + kq]
@@ -229,7 +230,8 @@ __global__ __launch_bounds__(256) void cnx_mlp_fwd_kernel(const MlpArgs a) {
             // lane holds hidden units 16 t + 4 kq + r of pixel li: bias, GELU, then straight into GEMM 2 as B fragments
             // (GELU through common.h's packed pair form -- one exp2 + one rcp per element, |error| <= 1.5e-7 on erf, the TAT conv0 epilogue's
             //  arithmetic -- instead of erff: 64 erff per 16-pixel tile were ~5 us of a wave's ~30 us chain)
-            const f32x4 bb4 = *reinterpret_cast<const f32x4*>(a.b1 + 16 * t + 4 * kq);
+            const float* b1p = a.b1 + 16 * t + 4 * kq;
+            const f32x4 bb4 = a.b1_vec ? *reinterpret_cast<const f32x4*>(b1p) : f32x4{b1p[0], b1p[1], b1p[2], b1p[3]};
 #pragma unroll
             for (int n = 0; n < CNX_NT; ++n) {
                 const f32x4 pre = h[n] + bb4;
@@ -497,10 +499,11 @@ extern "C" int bnerv_dense_gemm_bwd(void* stream, const float* x, const float* w
 extern "C" int bnerv_cnx_mlp_fwd(void* stream, const float* x, const float* inp, const float* w1, const float* b1, const float* w2, const float* b2,
                                  const float* gamma, float* out, float* hsave, int B, int C, int HW) {
     BNERV_REQUIRE(x && inp && w1 && b1 && w2 && b2 && out && B > 0 && HW > 0, "cnx_mlp_fwd: bad args");
-    BNERV_REQUIRE(((reinterpret_cast<uintptr_t>(w1) | reinterpret_cast<uintptr_t>(w2)) & 15) == 0, "cnx_mlp_fwd: weights must be 16-byte aligned");
+    BNERV_REQUIRE(((reinterpret_cast<uintptr_t>(w1) | reinterpret_cast<uintptr_t>(w2)) & 15) == 0, "cnx_mlp_fwd: w1 and w2 must be 16-byte aligned (staged with 16-byte loads)");
     MlpArgs a{};
     a.x = x; a.inp = inp; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.gamma = gamma; a.out = out; a.hsave = hsave;
     a.B = B; a.C = C; a.HW = HW;
+    a.b1_vec = (reinterpret_cast<uintptr_t>(b1) & 15) == 0 ? 1 : 0;
     return launch_mlp_c(reinterpret_cast<hipStream_t>(stream), a, false);
 }
 
@@ -509,7 +512,7 @@ extern "C" int bnerv_cnx_mlp_fwd(void* stream, const float* x, const float* inp,
 extern "C" int bnerv_cnx_mlp_bwd(void* stream, const float* h1, const float* dout, const float* w1, const float* w2, const float* gamma,
                                  float* dx, float* gbuf, float* dhbuf, int B, int C, int HW) {
     BNERV_REQUIRE(h1 && dout && w1 && w2 && dx && gbuf && dhbuf && B > 0 && HW > 0, "cnx_mlp_bwd: bad args");
-    BNERV_REQUIRE(((reinterpret_cast<uintptr_t>(w1) | reinterpret_cast<uintptr_t>(w2)) & 15) == 0, "cnx_mlp_bwd: weights must be 16-byte aligned");
+    BNERV_REQUIRE(((reinterpret_cast<uintptr_t>(w1) | reinterpret_cast<uintptr_t>(w2)) & 15) == 0, "cnx_mlp_bwd: w1 and w2 must be 16-byte aligned (staged with 16-byte loads)");
     MlpArgs a{};
     a.hin = h1; a.dout = dout; a.w1 = w1; a.w2 = w2; a.gamma = gamma; a.dx = dx; a.gbuf = gbuf; a.dhbuf = dhbuf;
     a.B = B; a.C = C; a.HW = HW;

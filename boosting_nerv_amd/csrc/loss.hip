@@ -153,7 +153,7 @@ __global__ void avgpool2_kernel(const float* __restrict__ x0, const float* __res
 // All four coarser levels of BOTH images in one launch, for frames whose sides stay even down to level 3 (720x1280: 360, 180, 90 |
 // 640, 320, 160): a block owns a 32x32 patch of level 0 = 16x16 of level 1 = ... = 2x2 of level 4, the intermediate levels pass
 // through LDS.  Same arithmetic as avgpool2_kernel level by level (0.25 * (((a + b) + c) + d)), so the pyramid is bit-identical.
-struct PyrArgs { const float* src[2]; float* dst[2][LV]; int H[LV], W[LV]; int planes; };
+struct PyrArgs { const float* src[2]; float* dst[2][LV]; int H[LV], W[LV]; int planes; int vec2; };      // vec2: launcher-side flag, both sources 8-byte aligned
 __device__ __forceinline__ void pyramid_body(const PyrArgs& a, const int bx, const int by, const int bz) {
     __shared__ float s1[16][17], s2[8][9], s3[4][5];
     const int img = bz & 1, pl = bz >> 1;
@@ -163,8 +163,16 @@ __device__ __forceinline__ void pyramid_body(const PyrArgs& a, const int bx, con
         const int oy = by * 16 + ty, ox = bx * 16 + tx;
         float v = 0.f;
         if (oy < a.H[1] && ox < a.W[1]) {
-            const float2 r0 = *reinterpret_cast<const float2*>(x + (size_t)(2 * oy) * a.W[0] + 2 * ox);
-            const float2 r1 = *reinterpret_cast<const float2*>(x + (size_t)(2 * oy + 1) * a.W[0] + 2 * ox);
+            const float* p0 = x + (size_t)(2 * oy) * a.W[0] + 2 * ox;
+            const float* p1 = p0 + a.W[0];
+            float2 r0, r1;
+            if (a.vec2) {                                  // both images 8-byte aligned (W[0] is even here): one 8-byte load per row
+                r0 = *reinterpret_cast<const float2*>(p0);
+                r1 = *reinterpret_cast<const float2*>(p1);
+            } else {                                       // a caller's image at an odd 4-byte boundary: the same four floats one by one
+                r0 = float2{p0[0], p0[1]};
+                r1 = float2{p1[0], p1[1]};
+            }
             v = 0.25f * (((r0.x + r0.y) + r1.x) + r1.y);
             a.dst[img][1][((size_t)pl * a.H[1] + oy) * a.W[1] + ox] = v;
         }
@@ -1243,6 +1251,7 @@ static int fill_even_forward(const float* X, const float* Y, float* ws, const Ws
     const Win win = make_win();
     const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
     pa.src[0] = X; pa.src[1] = Y; pa.planes = BC;
+    pa.vec2 = ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 7) == 0 ? 1 : 0;
     for (int l = 0; l < LV; ++l) {
         pa.H[l] = L.pyr.H[l]; pa.W[l] = L.pyr.W[l];
         if (L.pyr.H[l] <= HW_ || L.pyr.W[l] <= HW_) return bnerv_set_error(BNERV_E_ARG, "ms_ssim: level %d is %dx%d, needs > %d on both sides", l, L.pyr.H[l], L.pyr.W[l], HW_);
@@ -1402,6 +1411,7 @@ extern "C" int bnerv_loss_fwd_bwd(void* stream, const bnerv_loss_desc* dp) {
     BNERV_REQUIRE(dp != nullptr, "loss: null descriptor");
     const bnerv_loss_desc d = *dp;
     BNERV_REQUIRE(d.pred && d.target && d.loss_out && d.stats_out && d.ws, "loss: null tensor");
+    BNERV_REQUIRE((reinterpret_cast<uintptr_t>(d.ws) & 7) == 0, "loss: ws must be 8-byte aligned (the spectral term keeps its float2 spectra in it)");
     BNERV_REQUIRE(d.B > 0 && d.C > 0 && d.H > 0 && d.W > 0 && d.B <= 65535, "loss: bad dims");
     BNERV_REQUIRE((size_t)d.C * d.H * d.W < (size_t)1 << 31, "loss: sample too large");
     const bool use_ms = d.c_ms != 0.f, use_fft = d.c_fft != 0.f;
@@ -1536,6 +1546,7 @@ extern "C" int bnerv_loss_ssim_fwd_bwd(void* stream, const bnerv_loss_desc* dp, 
     BNERV_REQUIRE(dp != nullptr, "loss_ssim: null descriptor");
     const bnerv_loss_desc d = *dp;
     BNERV_REQUIRE(d.pred && d.target && d.loss_out && d.stats_out && d.ws, "loss_ssim: null tensor");
+    BNERV_REQUIRE((reinterpret_cast<uintptr_t>(d.ws) & 7) == 0, "loss_ssim: ws must be 8-byte aligned (the spectral term keeps its float2 spectra in it)");
     BNERV_REQUIRE(d.B > 0 && d.C > 0 && d.H > 0 && d.W > 0 && d.B <= 65535, "loss_ssim: bad dims");
     BNERV_REQUIRE((size_t)d.C * d.H * d.W < (size_t)1 << 31, "loss_ssim: sample too large");
     BNERV_REQUIRE(d.c_ms == 0.f, "loss_ssim: c_ms must be 0 (the MS-SSIM losses go through bnerv_loss_fwd_bwd)");

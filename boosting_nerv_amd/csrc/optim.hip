@@ -204,8 +204,8 @@ extern "C" int bnerv_adam_table(void* stream, const bnerv_adan_entry* table_dev,
 extern "C" int bnerv_fetch_frame(void* stream, const float* clip, const double* norms, const float* sel_dev, int n_frames, size_t frame_elems,
                                  float* dst_img, double* dst_norm) {
     BNERV_REQUIRE(clip && sel_dev && dst_img && n_frames > 0 && frame_elems > 0, "fetch_frame: bad args");
-    BNERV_REQUIRE((reinterpret_cast<uintptr_t>(clip) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst_img) & 15) == 0 && (frame_elems % 4 == 0 || n_frames == 1),
-                  "fetch_frame: 16-byte aligned frames required");
+    BNERV_REQUIRE((reinterpret_cast<uintptr_t>(clip) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst_img) & 15) == 0, "fetch_frame: clip and dst_img must be 16-byte aligned");
+    BNERV_REQUIRE(frame_elems % 4 == 0 || n_frames == 1, "fetch_frame: frame_elems must be a multiple of 4 when n_frames > 1 (16-byte aligned frames)");
     const size_t n4 = frame_elems / 4;
     int blocks = (int)((n4 + 255) / 256);
     if (blocks > 2048) blocks = 2048;

@@ -1,5 +1,6 @@
 """Autograd operators of the decoder path.  Every forward/backward here is a sequence of C-ABI calls into
 libbnerv_hip.so on torch's current HIP stream; torch supplies device memory, the stream and the autograd graph only.
+Every operator accepts any contiguous fp32 tensor, whatever its data_ptr() % 16 (INTEGRATION.md "Pointer alignment").
 
 Operator <-> reference map (the Python modules in this package call these from the same places the reference calls
 ATen):
@@ -980,6 +981,8 @@ class _CnxMlp(torch.autograd.Function):
     def forward(ctx, x, inp, w1, b1, w2, b2, gamma):
         x = L.f32c(L.require_device(x, "x")); inp = L.f32c(inp)
         w1, b1, w2, b2 = (L.f32c(t) for t in (w1, b1, w2, b2))
+        # the kernels stage the two [4C x C] matrices with float4 loads and refuse a misaligned one: hand them an aligned copy
+        w1, w2 = (t.clone() if t.data_ptr() % 16 else t for t in (w1, w2))
         gm = None if gamma is None else L.f32c(gamma)
         B, Cc, H, W = x.shape
         train = any(ctx.needs_input_grad)
@@ -1018,7 +1021,9 @@ class _CnxMlp(torch.autograd.Function):
 
 
 def cnx_mlp(x, inp, w1, b1, w2, b2, gamma):
-    """inp + gamma * (w2 gelu(w1 x + b1) + b2) per pixel; x, inp [B, C, H, W], w1 [4C, C], w2 [C, 4C]; C in CNX_MLP_DIMS."""
+    """inp + gamma * (w2 gelu(w1 x + b1) + b2) per pixel; x, inp [B, C, H, W], w1 [4C, C], w2 [C, 4C]; C in CNX_MLP_DIMS.
+    A w1 / w2 whose data_ptr() is not 16-byte aligned (a view into a flat parameter buffer) is cloned on EVERY forward -- 4C * C floats
+    and one copy launch per call; keep these two parameters in allocations of their own if that matters."""
     return _CnxMlp.apply(x, inp, w1, b1, w2, b2, gamma)
 
 

@@ -330,6 +330,7 @@ int bnerv_dense_gemm_bwd(void* stream, const float* x, const float* w, const flo
  *        gbuf = gelu(h1), dhbuf = d loss / d h1 ([B,4C,HW] each).  The weight / bias / gamma gradients follow from two
  *        bnerv_conv_wgrad (k = 1) calls: (x, dhbuf) -> dw1, db1 and (gbuf, dout) -> S, t with dw2 = gamma S, db2 = gamma t,
  *        dgamma = rowsum(w2 * S) + b2 * t.  (d loss / d inp is dout itself.) */
+/* Alignment: w1 and w2 must be 16-byte aligned (BNERV_E_ARG otherwise: they are staged with 16-byte loads); every other operand: any fp32 pointer. */
 int bnerv_cnx_mlp_fwd(void* stream, const float* x, const float* inp, const float* w1, const float* b1, const float* w2, const float* b2,
                       const float* gamma, float* out, float* hsave, int B, int C, int HW);
 int bnerv_cnx_mlp_bwd(void* stream, const float* h1, const float* dout, const float* w1, const float* w2, const float* gamma,
@@ -359,6 +360,7 @@ int bnerv_ans_decode_categorical(const uint32_t* words, size_t n_words, size_t n
  *   bnerv_dwconv_fwd(flip=0): y = conv(x, w) + bias;   flip=1: the data gradient (taps flipped, bias ignored: pass g as x)
  *   bnerv_dwconv_wgrad: dwb[C][K*K+1] = weight gradient rows with the bias gradient in the last column (slabs in ws;
  *   defer_ctx != NULL queues the slab reduction there, see bnerv_reduce_slabs_deferred).  x, y, g: [B, C, H, W];  w: [C, 1, K, K]. */
+/* Alignment: 16-byte stores to y when y is 16-byte aligned and W % 4 == 0, scalar stores (same bits) otherwise; x, w, bias: any fp32 pointer. */
 int bnerv_dwconv_fwd(void* stream, const float* x, const float* w, const float* bias, float* y, int B, int C, int H, int W, int K, int flip);
 size_t bnerv_dwconv_wgrad_ws_bytes(int B, int C, int H, int W, int K);
 int bnerv_dwconv_wgrad(void* stream, const float* x, const float* g, float* dwb, void* ws, size_t ws_bytes, int B, int C, int H, int W, int K, bnerv_ctx* defer_ctx);
@@ -401,6 +403,8 @@ size_t bnerv_loss_ws_bytes(int B, int C, int H, int W, int use_ms, int use_fft);
 /* Build the read-only FFT twiddle tables for H x W frames ahead of time.  Tables are otherwise built on first use,
  * which allocates and copies synchronously -- not allowed while `stream` is being captured into a hipGraph. */
 int bnerv_fft_prepare(int H, int W);
+/* Alignment: pred, target and grad may sit at any 4-byte boundary (the MS-SSIM pyramid takes 8-byte loads only when pred and target are
+ * 8-byte aligned, same bits either way); ws must be 8-byte aligned (float2 spectra; BNERV_E_ARG otherwise); the same holds for bnerv_loss_ssim_fwd_bwd. */
 int bnerv_loss_fwd_bwd(void* stream, const bnerv_loss_desc* d);
 /* per-sample MS-SSIM only (evaluate(): msssim_fn_single, hnerv_utils.py:410-412); out [B] */
 int bnerv_msssim(void* stream, const float* x, const float* y, float* out, void* ws, size_t ws_bytes, int B, int C, int H, int W);
@@ -419,6 +423,7 @@ int bnerv_ssim(void* stream, const float* x, const float* y, float* out, void* w
  * per-block channel sums of gt in part [B * bnerv_tanh_grad_blocks(HW)][C] (sum over the first index = the head's bias gradient:
  * bnerv_reduce_slabs(part, B * blocks, C, db)).  Used by the 3x3 head of HNeRV_Boost (model_hnerv.py:214), whose weight gradient runs
  * with input and gradient swapped (38 input channels on the MFMA M side). */
+/* Alignment: the 16-byte form needs g, img, gt 16-byte aligned and HW % 4 == 0; otherwise the scalar form runs (same gt; no refusal). */
 int bnerv_tanh_grad_blocks(int HW);
 int bnerv_tanh_grad(void* stream, const float* g, const float* img, float* gt, float* part, int B, int C, int HW);
 
@@ -494,6 +499,8 @@ int bnerv_adam_table(void* stream, const bnerv_adan_entry* table_dev, int n_tens
 /* Frame fetch of a step whose clip is resident in device memory (train_nerv_all.py:329 moves one frame host -> device per step; with
  * the clip in HBM the step only needs to know WHICH frame): copies frame k = (int)sel_dev[0] of clip [N][frame_elems] to dst_img
  * and norm[k] (fp64, hnerv_utils.py:47) to dst_norm.  sel_dev is device memory, so a captured step replays with a moving index. */
+/* Alignment: clip and dst_img must be 16-byte aligned and, for n_frames > 1, frame_elems % 4 == 0 (every frame on the 16-byte grid):
+ * BNERV_E_ARG otherwise -- a clip with an odd frame size is refused, not copied element-wise. */
 int bnerv_fetch_frame(void* stream, const float* clip, const double* norms, const float* sel_dev, int n_frames, size_t frame_elems,
                       float* dst_img, double* dst_norm);
 
