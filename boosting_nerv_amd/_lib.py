@@ -287,14 +287,17 @@ def f32c(t):
 
 
 class StreamContext:
-    """The deferred-reduction context (include/bnerv.h, bnerv_ctx) of one HIP stream, plus the workspaces its queued jobs still
-    read.  The library keeps no global queue: whoever launches on a stream passes that stream's context."""
+    """The deferred-reduction context (include/bnerv.h, bnerv_ctx) of one HIP stream, plus what the host knows about its queue:
+    `keep`, the workspaces its queued jobs still read, and `dx_queued`, whether a DATA gradient that ops has already handed to
+    autograd is among those jobs (set by ops._end_block, cleared with `keep` by every flush: ops._flush_deferred).  The library
+    keeps no global queue: whoever launches on a stream passes that stream's context."""
 
     def __init__(self):
         h = C.c_void_p()
         check(load().bnerv_ctx_create(C.byref(h)), "bnerv_ctx_create")
         self.handle = h
         self.keep = []
+        self.dx_queued = False
 
     def __del__(self):
         try:
@@ -342,16 +345,16 @@ class use_ctx:
         _ctx_override.pop()
 
 
-def ctx():
+def ctx(create=True):
     """Context of torch's current stream (created on first use; one per (device, stream)) unless a use_ctx block is open.  A new
     context reserves the scratch the other contexts of its device have grown to: a stream that is about to be captured into a
-    graph cannot allocate."""
+    graph cannot allocate.  create=False: None for a stream that has no context yet (nothing can be queued on it)."""
     if _ctx_override:
         return _ctx_override[-1]
     st = torch.cuda.current_stream()
     key = (st.device_index, st.cuda_stream)
     c = _contexts.get(key)
-    if c is None:
+    if c is None and create:
         want = _device_scratch_bytes(st.device_index)
         c = _contexts[key] = StreamContext()
         if want:

@@ -88,7 +88,7 @@ class TrainStep:
         # gradient seeds backward directly and the per-sample PSNR comes from the same L2 sums (stats[:, 4])
         loss, stats, grad = ops.loss_value_grad_stats(img_out, self.static_img, self.loss_type)
         if self._lazy_flush_valid():
-            # (dx_ok: the model's first block hands its queued input gradient to a flushing operator of this package -- ops._flush_deferred)
+            # (dx_ok: the model's first block hands its queued input gradient to an operator of this package, which flushes on entry -- ops._end_block)
             with ops.lazy_flush(dx_ok=getattr(self.model, "lazy_dx_ok", False)):      # slab reductions are flushed by their first reader, not per block
                 img_out.backward(grad)
         else:
@@ -174,7 +174,7 @@ class TrainStep:
         have run -- flush them, then start the early segment's all-reduce."""
         if self._early_ok:
             from . import ops
-            ops._flush_deferred(force=True)
+            ops._flush_deferred()
             self.bucket.exchange_early()
         return None
 

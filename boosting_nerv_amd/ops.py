@@ -30,27 +30,61 @@ def _ws(nbytes, device):
 # ----------------------------------------------------------------------------------------------------------------------
 # raw kernel wrappers
 # ----------------------------------------------------------------------------------------------------------------------
+_STREAM_CTX = object()      # descriptor builders: "the context of the current stream" (the 5x5 kernels take none: ctx=None)
+_SUMS_EP = (L.EP_DGELU, L.EP_DSIN, L.EP_DGELU_SAVED)      # epilogues that also write per-tile (ds, dt) partial sums
+
+
+def _conv_desc(x, w, bias, out, *, B, Cin, Cout, H, W, k, in_mode, ep_mode, in_s=1, out_s=1, transposed=0, out2=None,
+               aux0=None, aux1=None, aux2=None, scale=None, shift=None, partial=None, ctx=_STREAM_CTX):
+    """The ConvDesc of include/bnerv.h for one conv launch -- the only place that knows the field order."""
+    return L.ConvDesc(L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(out), L.ptr(out2), L.ptr(aux0), L.ptr(aux1), L.ptr(aux2),
+                      L.ptr(scale), L.ptr(shift), L.ptr(partial), B, Cin, Cout, H, W, k, in_mode, ep_mode, in_s, out_s,
+                      transposed, w.shape[0], w.shape[1], L.ctx().handle if ctx is _STREAM_CTX else ctx)
+
+
+def _wgrad_desc(x, g, dw, db, ws, ws_bytes, *, B, Cin, Cout, H, W, k, in_mode, g_mode, g_s=1, gaux=None, scale=None, shift=None,
+                defer=False, ctx=_STREAM_CTX):
+    """The WgradDesc of include/bnerv.h for one weight-gradient launch -- the only place that knows the field order."""
+    return L.WgradDesc(L.ptr(x), L.ptr(g), L.ptr(gaux), L.ptr(scale), L.ptr(shift), L.ptr(dw), L.ptr(db), L.ptr(ws), ws_bytes,
+                       B, Cin, Cout, H, W, k, in_mode, g_mode, g_s, 1 if defer else 0, L.ctx().handle if ctx is _STREAM_CTX else ctx)
+
+
+def _sums_partial(d, device):
+    """The [rows, B, 2, Cout] partial-sum buffer of an EP_DGELU / EP_DSIN / EP_DGELU_SAVED launch, hooked into d.  The kernel (hence
+    its tile height) is chosen from shape + alignment -> ask the library for the row count of THIS descriptor."""
+    rows = L.load().bnerv_conv_partial_rows(C.byref(d))
+    part = torch.empty(rows, d.B, 2, d.Cout, dtype=torch.float32, device=device)
+    d.partial = part.data_ptr()
+    return part, rows
+
+
+def _splitk_ws(d, device):
+    """The split-K slab workspace of an EP_PLAIN launch (low-resolution, long-K layers), hooked into d; None where the layer wants none."""
+    nbytes = L.load().bnerv_conv_splitk_ws_bytes(C.byref(d))
+    if not nbytes:
+        return None
+    ws = _ws(nbytes, device)
+    d.partial = ws.data_ptr()
+    return ws
+
+
+def _reduced_sums(part, rows, d, device, defer):
+    st = torch.empty(d.B, 2, d.Cout, dtype=torch.float32, device=device)
+    _reduce_slabs(part, rows, d.B * 2 * d.Cout, st, defer=defer)
+    return st
+
+
 def _conv(x, w, bias, out, *, B, Cin, Cout, H, W, k, in_mode, ep_mode, in_s=1, out_s=1, transposed=0, out2=None,
           aux0=None, aux1=None, aux2=None, scale=None, shift=None, partial=None, defer=False):
-    d = L.ConvDesc(L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(out), L.ptr(out2), L.ptr(aux0), L.ptr(aux1), L.ptr(aux2),
-                   L.ptr(scale), L.ptr(shift), L.ptr(partial), B, Cin, Cout, H, W, k, in_mode, ep_mode, in_s, out_s,
-                   transposed, w.shape[0], w.shape[1], L.ctx().handle)
+    """One conv launch.  Returns the [B, 2, Cout] channel sums for the _SUMS_EP epilogues, else None."""
+    d = _conv_desc(x, w, bias, out, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=k, in_mode=in_mode, ep_mode=ep_mode, in_s=in_s, out_s=out_s,
+                   transposed=transposed, out2=out2, aux0=aux0, aux1=aux1, aux2=aux2, scale=scale, shift=shift, partial=partial)
     lib = L.load()
-    ws = None
-    if ep_mode in (L.EP_DGELU, L.EP_DSIN, L.EP_DGELU_SAVED):
-        # per-tile (ds, dt) partial sums: the kernel (hence its tile height) is chosen from shape + alignment -> ask, allocate, reduce
-        rows = lib.bnerv_conv_partial_rows(C.byref(d))
-        part = torch.empty(rows, B, 2, Cout, dtype=torch.float32, device=x.device)
-        d.partial = part.data_ptr()
+    if ep_mode in _SUMS_EP:
+        part, rows = _sums_partial(d, x.device)
         L.check(lib.bnerv_conv_igemm(L.stream(), C.byref(d)), "bnerv_conv_igemm")
-        st = torch.empty(B, 2, Cout, dtype=torch.float32, device=x.device)
-        _reduce_slabs(part, rows, B * 2 * Cout, st, defer=defer)
-        return st
-    if ep_mode == L.EP_PLAIN and partial is None:
-        nbytes = lib.bnerv_conv_splitk_ws_bytes(C.byref(d))      # low-resolution, long-K layers want a split-K workspace
-        if nbytes:
-            ws = _ws(nbytes, x.device)
-            d.partial = ws.data_ptr()
+        return _reduced_sums(part, rows, d, x.device, defer)
+    ws = _splitk_ws(d, x.device) if ep_mode == L.EP_PLAIN and partial is None else None      # (held only so the buffer lives until the launch is enqueued)
     L.check(lib.bnerv_conv_igemm(L.stream(), C.byref(d)), "bnerv_conv_igemm")
 
 
@@ -58,8 +92,8 @@ def _wgrad(x, g, dw, db, *, B, Cin, Cout, H, W, k, in_mode, g_mode, g_s=1, gaux=
     lib = L.load()
     nbytes = lib.bnerv_conv_wgrad_ws_bytes(B, Cin, Cout, H, W, k)
     ws = _ws(nbytes, x.device)
-    d = L.WgradDesc(L.ptr(x), L.ptr(g), L.ptr(gaux), L.ptr(scale), L.ptr(shift), L.ptr(dw), L.ptr(db), L.ptr(ws), nbytes,
-                    B, Cin, Cout, H, W, k, in_mode, g_mode, g_s, 1 if defer else 0, L.ctx().handle)
+    d = _wgrad_desc(x, g, dw, db, ws, nbytes, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=k, in_mode=in_mode, g_mode=g_mode, g_s=g_s, gaux=gaux,
+                    scale=scale, shift=shift, defer=defer)
     L.check(lib.bnerv_conv_wgrad(L.stream(), C.byref(d)), "bnerv_conv_wgrad")
     if defer:
         L.ctx().keep.append(ws)
@@ -69,54 +103,38 @@ def _wgrad_conv_pair(wg, cv):
     """One weight gradient and one data gradient that read the same incoming gradient and do not depend on each other, as ONE launch
     when the library takes the pair (include/bnerv.h bnerv_conv_wgrad_pair: 12-channel 3x3 layers), as the two usual launches
     otherwise.  wg: keyword arguments of _wgrad (x, g, dw, db first), always deferred; cv: keyword arguments of _conv (x, w, bias, out
-    first) for an EP_DGELU_SAVED / EP_DSIN / EP_PLAIN epilogue.  Returns what _conv returns (the [B, 2, C] channel sums, or None).
-    Side effect: `_pair_dx_deferred` says whether the DATA gradient itself (cv's `out`) is still a queued slab reduction when the call
-    returns (the stem pair, csrc/stem.hip: its K-slice slabs are summed by a deferred job) -- every other form writes `out` directly."""
-    global _pair_dx_deferred
-    _pair_dx_deferred = False
+    first) for an EP_DGELU_SAVED / EP_DSIN / EP_PLAIN epilogue; neither dict is modified.  Returns (what _conv returns: the [B, 2, C]
+    channel sums or None, dx_queued: the DATA gradient itself (cv's `out`) is still a queued slab reduction when the call returns --
+    the stem pair, csrc/stem.hip; every other form writes `out` directly)."""
     lib = L.load()
-    x, g, dw, db = wg.pop("x"), wg.pop("g"), wg.pop("dw"), wg.pop("db")
+    dev = wg["x"].device
     nbytes = lib.bnerv_conv_wgrad_ws_bytes(wg["B"], wg["Cin"], wg["Cout"], wg["H"], wg["W"], wg["k"])
-    ws = _ws(nbytes, x.device)
-    wd = L.WgradDesc(L.ptr(x), L.ptr(g), L.ptr(wg.get("gaux")), L.ptr(wg.get("scale")), L.ptr(wg.get("shift")), L.ptr(dw), L.ptr(db), L.ptr(ws), nbytes,
-                     wg["B"], wg["Cin"], wg["Cout"], wg["H"], wg["W"], wg["k"], wg["in_mode"], wg["g_mode"], wg.get("g_s", 1), 1, L.ctx().handle)
-    cx, cw, cb, cout = cv.pop("x"), cv.pop("w"), cv.pop("bias"), cv.pop("out")
-    cd = L.ConvDesc(L.ptr(cx), L.ptr(cw), L.ptr(cb), L.ptr(cout), L.ptr(cv.get("out2")), L.ptr(cv.get("aux0")), L.ptr(cv.get("aux1")), L.ptr(cv.get("aux2")),
-                    L.ptr(cv.get("scale")), L.ptr(cv.get("shift")), None, cv["B"], cv["Cin"], cv["Cout"], cv["H"], cv["W"], cv["k"], cv["in_mode"], cv["ep_mode"],
-                    cv.get("in_s", 1), cv.get("out_s", 1), cv.get("transposed", 0), cw.shape[0], cw.shape[1], L.ctx().handle)
-    red = cv["ep_mode"] in (L.EP_DGELU, L.EP_DSIN, L.EP_DGELU_SAVED)
-    part = None
-    if red:
-        rows = lib.bnerv_conv_partial_rows(C.byref(cd))
-        part = torch.empty(rows, cv["B"], 2, cv["Cout"], dtype=torch.float32, device=cx.device)
-        cd.partial = part.data_ptr()
+    ws = _ws(nbytes, dev)
+    wd = _wgrad_desc(ws=ws, ws_bytes=nbytes, **{**wg, "defer": True})
+    cd = _conv_desc(**cv)
+    red = cv["ep_mode"] in _SUMS_EP
     skw = None
-    if not red and cv["ep_mode"] == L.EP_PLAIN:            # a split-K layer (the stem stage's long-K data gradient): its slab workspace
-        nb = lib.bnerv_conv_splitk_ws_bytes(C.byref(cd))
-        if nb:
-            skw = _ws(nb, cx.device)
-            cd.partial = skw.data_ptr()
+    if red:
+        part, rows = _sums_partial(cd, dev)
+    elif cv["ep_mode"] == L.EP_PLAIN:                      # a split-K layer (the stem stage's long-K data gradient): its slab workspace
+        skw = _splitk_ws(cd, dev)
     rc = lib.bnerv_conv_wgrad_pair(L.stream(), C.byref(cd), C.byref(wd))
     if rc == 1:                                            # not a pair the launch takes: the two usual calls, weight gradient first
         L.check(lib.bnerv_conv_wgrad(L.stream(), C.byref(wd)), "bnerv_conv_wgrad")
         L.check(lib.bnerv_conv_igemm(L.stream(), C.byref(cd)), "bnerv_conv_igemm")
     else:
         L.check(rc, "bnerv_conv_wgrad_pair")
-        if skw is not None:
-            L.ctx().keep.append(skw)                       # (the stem pair sums its slabs in a deferred reduction: alive until the flush)
-            _pair_dx_deferred = True                       # cv's `out` is complete only after the next flush
+    dx_queued = rc != 1 and skw is not None                # the stem pair sums its slabs in a deferred reduction: `out` is complete
+    if dx_queued:                                          # only after the next flush, and the slabs stay alive until then
+        L.ctx().keep.append(skw)
     L.ctx().keep.append(ws)
-    if red:
-        st = torch.empty(cv["B"], 2, cv["Cout"], dtype=torch.float32, device=cx.device)
-        _reduce_slabs(part, rows, cv["B"] * 2 * cv["Cout"], st, defer=True)
-        return st
-    return None
+    return (_reduced_sums(part, rows, cd, dev, True) if red else None), dx_queued
 
 
 # Deferred slab reductions (include/bnerv.h, bnerv_reduce_slabs_deferred): inside one backward the reductions are queued in the
-# CONTEXT of the current stream (L.ctx()) and ride on the next lean conv / weight-gradient launch of that stream;
-# _flush_deferred() at the end of the backward launches the leftovers, so every tensor a backward returns is complete on the
-# stream.  The workspaces of queued jobs are kept alive by the context until then.
+# CONTEXT of the current stream (L.ctx()) and ride on the next lean conv / weight-gradient launch of that stream; the flush that
+# ends the block's backward (_end_block) launches the leftovers, so every tensor a backward returns is complete on the stream.
+# The workspaces of queued jobs are kept alive by the context until then.
 def _reduce_slabs(slabs, n_slabs, count, out, defer=False):
     if defer:
         c = L.ctx()
@@ -126,52 +144,61 @@ def _reduce_slabs(slabs, n_slabs, count, out, defer=False):
     L.check(L.load().bnerv_reduce_slabs(L.stream(), L.ptr(slabs), n_slabs, count, L.ptr(out)), "bnerv_reduce_slabs")
 
 
-_lazy_depth = 0       # > 0: inside lazy_flush() -- the per-block flushes are postponed to the first consumer of a deferred result
-_lazy_dx_ok = False   # inside lazy_flush(dx_ok=True): a block may also RETURN a data gradient whose slab reduction is still queued
-_pair_dx_deferred = False   # set by _wgrad_conv_pair: the data gradient of the last pair is a queued slab reduction (the stem pair)
+# What is still queued is recorded on the stream context (_lib.StreamContext: keep, dx_queued); here only whether laziness is on
+_lazy = []      # one dx_ok per open lazy_flush(), innermost last; empty: every block's backward ends with a flush
 
 
-def _flush_deferred(force=True, block_end=False, dx_deferred=False):
-    """Launch whatever slab reductions are still queued on this stream's context.  `block_end`: the call that closes a block's
-    backward -- inside lazy_flush() it is skipped, because the queued results (weight / bias gradients, the per-channel TAT sums) have
-    no reader until the grouped dense backward or the optimizer, and both flush first: ~5 small dependent launches per step less.
-    `dx_deferred`: the block returns a DATA gradient that is itself queued (the stem pair): autograd hands it to whatever produced the
-    block's input -- skipped only where the model vouches that this reader is a flushing operator of this package (lazy_flush(dx_ok=True):
-    NeRV_Boost, whose first block is fed by the stem MLP; E-NeRV's first up-conv is fed by a stock torch.sin, which would read the
-    unreduced buffer)."""
-    if block_end and _lazy_depth > 0 and (not dx_deferred or _lazy_dx_ok):
-        return
+def _flush_deferred():
+    """Launch whatever slab reductions are still queued on this stream's context (an empty queue launches nothing: bnerv_side_flush)."""
     c = L.ctx()
     L.check(L.load().bnerv_flush_deferred(c.handle, L.stream()), "bnerv_flush_deferred")
     c.keep.clear()
+    c.dx_queued = False
+
+
+def _end_block(dx_queued=False):
+    """Close a block's backward with a flush -- skipped inside lazy_flush(), because the queued results (weight / bias gradients, the
+    per-channel TAT sums) have no reader until the grouped dense backward or the optimizer, and both flush first: ~5 small dependent
+    launches per step less.  `dx_queued`: the block returns a DATA gradient that is itself queued (the stem pair).  Whatever produced
+    the block's input reads it: an operator of this package flushes on entry (_enter_backward), a stock torch operator would read the
+    unreduced buffer -- so that flush is skipped only under lazy_flush(dx_ok=True), and the context is told.  dx_ok therefore covers
+    EVERY block that may take the stem pair: it is right only where the immediate reader of each such gradient is an operator of this
+    package (B -> torch.sin -> A would hand sin's backward the unreduced buffer before A's entry flush)."""
+    if _lazy and (not dx_queued or _lazy[-1]):
+        if dx_queued:
+            L.ctx().dx_queued = True
+        return
+    _flush_deferred()
+
+
+def _enter_backward(reads_sums=False):
+    """First line of every backward of this package: flush if a data gradient was returned queued (_end_block), whoever reads it, and
+    -- `reads_sums`: the incoming gradients are themselves deferred results inside lazy_flush(), the TAT blocks' channel sums --
+    whenever laziness is on.  Invariant: a flush with an empty queue launches nothing, and in every shipped config the only reader
+    of a queued data gradient is a reads_sums operator -- so no shipped config gains or moves a launch through this line."""
+    c = L.ctx(create=False)
+    if (c is not None and c.dx_queued) or (reads_sums and _lazy):
+        _flush_deferred()
 
 
 class lazy_flush:
     """with lazy_flush(): backward()  -- postpone the end-of-block flushes of the deferred slab reductions; every consumer inside this
-    package (grouped dense / dense GEMM / stand-alone affine backward) flushes on entry, and leaving the context flushes the rest.
-    dx_ok: the model's promise that a block's INPUT gradient may stay queued too (see _flush_deferred)."""
+    package flushes on entry where it has to (_enter_backward), and leaving the outermost context flushes the rest.
+    dx_ok: the model's word that a block whose INPUT gradient may stay queued (_end_block: the stem pair, in shipped configs the first
+    block only) is fed directly by an operator of this package."""
 
     def __init__(self, dx_ok=False):
         self.dx_ok = bool(dx_ok)
 
     def __enter__(self):
-        global _lazy_depth, _lazy_dx_ok
-        _lazy_depth += 1
-        self._prev = _lazy_dx_ok
-        _lazy_dx_ok = self.dx_ok
+        _lazy.append(self.dx_ok)
         return self
 
     def __exit__(self, *exc):
-        global _lazy_depth, _lazy_dx_ok
-        _lazy_depth -= 1
-        _lazy_dx_ok = self._prev
-        if _lazy_depth == 0:
+        _lazy.pop()
+        if not _lazy:
             _flush_deferred()
         return False
-
-
-def _tiles(H, W):
-    return L.load().bnerv_conv_tiles(H, W)
 
 
 def _bc(t, B, Cc):
@@ -241,8 +268,7 @@ class _DenseGrouped(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *dys):
-        if _lazy_depth > 0:
-            _flush_deferred()               # the incoming gradients may be deferred slab reductions (the TAT blocks' channel sums)
+        _enter_backward(reads_sums=True)    # the incoming gradients may be deferred slab reductions (the TAT blocks' channel sums)
         n = ctx.n
         sv = ctx.saved_tensors
         xc, wc, ys, auxs = sv[:n], sv[n:2 * n], sv[2 * n:3 * n], sv[3 * n:4 * n]
@@ -334,8 +360,7 @@ class _DenseGemm(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        if _lazy_depth > 0:
-            _flush_deferred()
+        _enter_backward(reads_sums=True)
         x2, w2, y, aux = ctx.saved_tensors
         B, I = x2.shape
         O = w2.shape[0]
@@ -401,8 +426,7 @@ class _TimeBranch(torch.autograd.Function):
         grouped by what is READY, not by which forward launch they came from --
             [every modulation MLP's layer 1 | the stem's layer 1]  ->  [every MLP's layer 0]  ->  ONE flush of both pending input-gradient
             reductions (z_t's over the 32 MLPs, the stem's 68 chunks)  ->  [stem_t layer 1 | stem layer 0]  ->  [stem_t layer 0]."""
-        if _lazy_depth > 0:
-            _flush_deferred()               # the modulation gradients are deferred slab reductions of the TAT blocks
+        _enter_backward(reads_sums=True)    # the modulation gradients are deferred slab reductions of the TAT blocks
         n, B = ctx.n_mlp, ctx.B
         sv = ctx.saved_tensors
         pe, sy0, saux0, sy1, saux1, ty0, taux0, ty1, taux1 = sv[:9]
@@ -494,13 +518,15 @@ class _Conv2dPS(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        _enter_backward()
         x, w = ctx.saved_tensors
         dx, dw, db = _conv_ps_backward(x, w, L.f32c(g), ctx.s, ctx.has_b, ctx.needs_input_grad[0])
         return dx, dw, db, None
 
 
 def _conv_ps_backward(x, w, g, s, has_b, need_dx):
-    """Backward of conv (k in {1,3}) + bias + PixelShuffle(s) from the gradient g of the shuffled output: (dx or None, dw, db or None)."""
+    """Backward of conv (k in {1,3}) + bias + PixelShuffle(s) from the gradient g of the shuffled output: (dx or None, dw, db or None).
+    The one place that chooses between the (dW | dx) pair and the two launches; it ENDS the block's backward (_end_block)."""
     B, Cin, H, W = x.shape
     Cout, k = w.shape[0], w.shape[-1]
     dw = torch.empty_like(w)
@@ -509,15 +535,14 @@ def _conv_ps_backward(x, w, g, s, has_b, need_dx):
     dxq = False
     if need_dx and k == 3:                                     # (dW | dx): one launch where the library pairs them
         dx = torch.empty_like(x)
-        _wgrad_conv_pair(dict(x=x, g=g, dw=dw, db=db, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=k, in_mode=L.IN_PLAIN, g_mode=L.IN_UNSHUFFLE, g_s=s),
-                         dict(x=g, w=w, bias=None, out=dx, B=B, Cin=Cout, Cout=Cin, H=H, W=W, k=k, in_mode=L.IN_UNSHUFFLE, ep_mode=L.EP_PLAIN, in_s=s, transposed=1))
-        dxq = _pair_dx_deferred
+        _, dxq = _wgrad_conv_pair(dict(x=x, g=g, dw=dw, db=db, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=k, in_mode=L.IN_PLAIN, g_mode=L.IN_UNSHUFFLE, g_s=s),
+                                  dict(x=g, w=w, bias=None, out=dx, B=B, Cin=Cout, Cout=Cin, H=H, W=W, k=k, in_mode=L.IN_UNSHUFFLE, ep_mode=L.EP_PLAIN, in_s=s, transposed=1))
     else:
         _wgrad(x, g, dw, db, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=k, in_mode=L.IN_PLAIN, g_mode=L.IN_UNSHUFFLE, g_s=s, defer=True)
         if need_dx:
             dx = torch.empty_like(x)
             _conv(g, w, None, dx, B=B, Cin=Cout, Cout=Cin, H=H, W=W, k=k, in_mode=L.IN_UNSHUFFLE, ep_mode=L.EP_PLAIN, in_s=s, transposed=1)
-    _flush_deferred(block_end=True, dx_deferred=dxq)
+    _end_block(dxq)
     return dx, dw, db
 
 
@@ -535,8 +560,8 @@ def _conv5(x, w, bias, out, *, B, Cin, Cout, H, W, in_mode=L.IN_PLAIN, ep_mode, 
     lib = L.load()
     nbytes = lib.bnerv_conv5_ws_bytes(Cin, Cout)
     ws = _ws(nbytes, x.device)
-    d = L.ConvDesc(L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(out), L.ptr(out2), L.ptr(aux0), None, None, None, None, None,
-                   B, Cin, Cout, H, W, 5, in_mode, ep_mode, in_s, out_s, transposed, w.shape[0], w.shape[1], None)
+    d = _conv_desc(x, w, bias, out, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=5, in_mode=in_mode, ep_mode=ep_mode, in_s=in_s, out_s=out_s,
+                   transposed=transposed, out2=out2, aux0=aux0, ctx=None)
     L.check(lib.bnerv_conv5_igemm(L.stream(), C.byref(d), L.ptr(ws), nbytes), "bnerv_conv5_igemm")
 
 
@@ -544,8 +569,8 @@ def _wgrad5(x, g, dw, db, *, B, Cin, Cout, H, W, g_s=1, gaux=None):
     lib = L.load()
     nbytes = lib.bnerv_conv5_wgrad_ws_bytes(B, Cin, Cout, H, W)
     ws = _ws(nbytes, x.device)
-    d = L.WgradDesc(L.ptr(x), L.ptr(g), L.ptr(gaux), None, None, L.ptr(dw), L.ptr(db), L.ptr(ws), nbytes,
-                    B, Cin, Cout, H, W, 5, L.IN_PLAIN, L.IN_UNSHUFFLE if g_s > 1 else L.IN_PLAIN, g_s, 0, None)
+    d = _wgrad_desc(x, g, dw, db, ws, nbytes, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=5, in_mode=L.IN_PLAIN,
+                    g_mode=L.IN_UNSHUFFLE if g_s > 1 else L.IN_PLAIN, g_s=g_s, gaux=gaux, ctx=None)
     L.check(lib.bnerv_conv5_wgrad(L.stream(), C.byref(d)), "bnerv_conv5_wgrad")
 
 
@@ -575,6 +600,7 @@ class _UpConvAct(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        _enter_backward()
         x, w, gp = ctx.saved_tensors
         s = ctx.s
         g = L.f32c(g)
@@ -635,14 +661,14 @@ def _tat_backward(dout, y0, c0, h, gp, s0, t0, s1, t1, w0, w1):
     # every slab reduction below is deferred: it rides on the next launch of this chain; the CALLER flushes the leftovers
     # (dW1 | d conv1) and (dW0 | d conv0): each pair reads one incoming gradient and is ONE launch where the library pairs them
     dv = torch.empty_like(y0)
-    st1 = _wgrad_conv_pair(dict(x=h, g=dout, dw=dw1, db=db1, B=B, Cin=Cc, Cout=Cc, H=H, W=W, k=3, in_mode=L.IN_AFFINE, g_mode=L.IN_UNSHUFFLE, scale=s1, shift=t1),
-                           dict(x=dout, w=w1, bias=None, out=dv, B=B, Cin=Cc, Cout=Cc, H=H, W=W, k=3, in_mode=L.IN_PLAIN, ep_mode=L.EP_DGELU_SAVED,
-                                transposed=1, aux0=gp, aux1=h, scale=s1))
+    st1, _ = _wgrad_conv_pair(dict(x=h, g=dout, dw=dw1, db=db1, B=B, Cin=Cc, Cout=Cc, H=H, W=W, k=3, in_mode=L.IN_AFFINE, g_mode=L.IN_UNSHUFFLE, scale=s1, shift=t1),
+                              dict(x=dout, w=w1, bias=None, out=dv, B=B, Cin=Cc, Cout=Cc, H=H, W=W, k=3, in_mode=L.IN_PLAIN, ep_mode=L.EP_DGELU_SAVED,
+                                   transposed=1, aux0=gp, aux1=h, scale=s1))
     dw0 = torch.empty_like(w0); db0 = torch.empty(Cc, dtype=torch.float32, device=dev)
     du = torch.empty_like(y0)
-    st0 = _wgrad_conv_pair(dict(x=y0, g=dv, dw=dw0, db=db0, B=B, Cin=Cc, Cout=Cc, H=H, W=W, k=3, in_mode=L.IN_AFFINE, g_mode=L.IN_UNSHUFFLE, scale=s0, shift=t0),
-                           dict(x=dv, w=w0, bias=None, out=du, B=B, Cin=Cc, Cout=Cc, H=H, W=W, k=3, in_mode=L.IN_PLAIN, ep_mode=L.EP_DSIN,
-                                transposed=1, aux0=y0, aux1=dout, aux2=c0, scale=s0))
+    st0, _ = _wgrad_conv_pair(dict(x=y0, g=dv, dw=dw0, db=db0, B=B, Cin=Cc, Cout=Cc, H=H, W=W, k=3, in_mode=L.IN_AFFINE, g_mode=L.IN_UNSHUFFLE, scale=s0, shift=t0),
+                              dict(x=dv, w=w0, bias=None, out=du, B=B, Cin=Cc, Cout=Cc, H=H, W=W, k=3, in_mode=L.IN_PLAIN, ep_mode=L.EP_DSIN,
+                                   transposed=1, aux0=y0, aux1=dout, aux2=c0, scale=s0))
     return du, st0[:, 0], st0[:, 1], st1[:, 0], st1[:, 1], dw0, db0, dw1, db1
 
 
@@ -662,9 +688,10 @@ class _TATBlock(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
+        _enter_backward()
         x0, h, gp, s0, t0, s1, t1, w0, w1 = ctx.saved_tensors
         dx0, ds0, dt0, ds1, dt1, dw0, db0, dw1, db1 = _tat_backward(L.f32c(dout), x0, None, h, gp, s0, t0, s1, t1, w0, w1)
-        _flush_deferred(block_end=True)
+        _end_block()
         m = ctx.mshape
         return dx0, ds0.reshape(m), dt0.reshape(m), ds1.reshape(m), dt1.reshape(m), dw0, db0, dw1, db1
 
@@ -697,26 +724,10 @@ class _SNeRVBlock(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
+        _enter_backward()
         x, y0, c0, h, gp, s0, t0, s1, t1, wu, w0, w1 = ctx.saved_tensors
-        s = ctx.s
         du, ds0, dt0, ds1, dt1, dw0, db0, dw1, db1 = _tat_backward(L.f32c(dout), y0, c0, h, gp, s0, t0, s1, t1, w0, w1)
-        B, Cin, H, W = x.shape
-        Ct, k = wu.shape[0], wu.shape[-1]
-        dwu = torch.empty_like(wu)
-        dbu = torch.empty(Ct, dtype=torch.float32, device=x.device) if ctx.has_bu else None
-        dx = None
-        dxq = False
-        if ctx.needs_input_grad[0] and k == 3:      # (dW_block | d block conv): one launch where the library pairs them
-            dx = torch.empty_like(x)
-            _wgrad_conv_pair(dict(x=x, g=du, dw=dwu, db=dbu, B=B, Cin=Cin, Cout=Ct, H=H, W=W, k=k, in_mode=L.IN_PLAIN, g_mode=L.IN_UNSHUFFLE, g_s=s),
-                             dict(x=du, w=wu, bias=None, out=dx, B=B, Cin=Ct, Cout=Cin, H=H, W=W, k=k, in_mode=L.IN_UNSHUFFLE, ep_mode=L.EP_PLAIN, in_s=s, transposed=1))
-            dxq = _pair_dx_deferred
-        else:
-            _wgrad(x, du, dwu, dbu, B=B, Cin=Cin, Cout=Ct, H=H, W=W, k=k, in_mode=L.IN_PLAIN, g_mode=L.IN_UNSHUFFLE, g_s=s, defer=True)
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-                _conv(du, wu, None, dx, B=B, Cin=Ct, Cout=Cin, H=H, W=W, k=k, in_mode=L.IN_UNSHUFFLE, ep_mode=L.EP_PLAIN, in_s=s, transposed=1)
-        _flush_deferred(block_end=True, dx_deferred=dxq)
+        dx, dwu, dbu = _conv_ps_backward(x, wu, du, ctx.s, ctx.has_bu, ctx.needs_input_grad[0])
         m = ctx.mshape
         return dx, dwu, dbu, ds0.reshape(m), dt0.reshape(m), ds1.reshape(m), dt1.reshape(m), dw0, db0, dw1, db1, None
 
@@ -744,8 +755,7 @@ class _SFTAffine(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        if _lazy_depth > 0:
-            _flush_deferred()
+        _enter_backward(reads_sums=True)
         x, sc = ctx.saved_tensors
         g = L.f32c(g)
         B, Cc = x.shape[:2]
@@ -779,6 +789,7 @@ class _HeadTanh(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        _enter_backward()
         x, w, img = ctx.saved_tensors
         g = L.f32c(g)
         B, Cin, H, W = x.shape
@@ -809,12 +820,13 @@ class _HeadTanh(torch.autograd.Function):
                 _conv(gt, w, None, dx, B=B, Cin=Cout, Cout=Cin, H=H, W=W, k=k, in_mode=L.IN_PLAIN, ep_mode=L.EP_PLAIN, transposed=1)
         elif ctx.needs_input_grad[0]:
             # (dW | dx) of the head: one streaming pass where the library pairs them (1x1, tanh-grad prologue), the two launches otherwise
+            # (never the stem pair, which takes no tanh-grad prologue: this dx is written directly)
             dx = torch.empty_like(x)
             _wgrad_conv_pair(dict(x=x, g=g, dw=dw, db=db, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=k, in_mode=L.IN_PLAIN, g_mode=L.IN_TANHGRAD, gaux=img),
                              dict(x=g, w=w, bias=None, out=dx, B=B, Cin=Cout, Cout=Cin, H=H, W=W, k=k, in_mode=L.IN_TANHGRAD, ep_mode=L.EP_PLAIN, transposed=1, aux0=img))
         else:
             _wgrad(x, g, dw, db, B=B, Cin=Cin, Cout=Cout, H=H, W=W, k=k, in_mode=L.IN_PLAIN, g_mode=L.IN_TANHGRAD, gaux=img, defer=True)
-        _flush_deferred(block_end=True)
+        _end_block()
         return dx, dw, db
 
 
@@ -859,6 +871,7 @@ class _CemScaleRate(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_bits, _d_stats, *d_deq):
+        _enter_backward()
         n = ctx.n
         sv = ctx.saved_tensors
         stats, wc, sc = sv[0], sv[1:1 + n], sv[1 + n:1 + 2 * n]
@@ -912,6 +925,7 @@ class _DWConv(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        _enter_backward()
         x, w = ctx.saved_tensors
         g = L.f32c(g)
         B, Cc, H, W = x.shape
@@ -952,6 +966,7 @@ class _LayerNormCF(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        _enter_backward()
         x, w = ctx.saved_tensors
         g = L.f32c(g)
         B, Cc = x.shape[:2]
@@ -997,6 +1012,7 @@ class _CnxMlp(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
+        _enter_backward()
         x, h1, w1, w2, b2, gm = ctx.saved_tensors
         dout = L.f32c(dout)
         B, Cc, H, W = x.shape
@@ -1123,6 +1139,7 @@ class _Loss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gl, _gs):
+        _enter_backward()
         g = ctx.grad
         ctx.grad = None
         return (g * gl if g is not None else None), None, None

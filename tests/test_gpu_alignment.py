@@ -774,7 +774,7 @@ def test_partial_buffer_sized_by_the_library_fits_the_kernel_that_runs(ops, laye
     [rows, B, 2, Cout] partial buffer is sized from bnerv_conv_partial_rows for THAT descriptor -- 4x16 tiles for the low-resolution family,
     8x32 tiles for everything else, and alignment decides which runs (conv.hip bnerv_conv_partial_rows) -- and over-allocated by one
     NaN row: every row the library asked for is written, the extra row stays NaN, and output and reduced sums match float64.  (The
-    descriptor is filled as ops._conv fills it; _conv allocates the buffer itself, so the guarded call is made here.)  Then the same
+    descriptor is built by ops._conv_desc, as ops._conv builds it; _conv allocates the buffer itself, so the guarded call is made here.)  Then the same
     launch through ops._conv, whose own buffer must be sized from the descriptor it launches with: output and reduced sums again."""
     from boosting_nerv_amd import _lib as L
     Cc, H, W = layer
@@ -790,8 +790,8 @@ def test_partial_buffer_sized_by_the_library_fits_the_kernel_that_runs(ops, laye
         gd, gbuf = shifted(gd, k)
         check_shifted(gd, k)
     out = torch.full((1, Cc, H, W), NAN, device=DEV)
-    d = L.ConvDesc(L.ptr(gd), L.ptr(wd), None, L.ptr(out), None, L.ptr(gpd), L.ptr(hd), None, L.ptr(scd), None, None,
-                   1, Cc, Cc, H, W, 3, L.IN_PLAIN, L.EP_DGELU_SAVED, 1, 1, 1, Cc, Cc, L.ctx().handle)
+    d = ops._conv_desc(gd, wd, None, out, B=1, Cin=Cc, Cout=Cc, H=H, W=W, k=3, in_mode=L.IN_PLAIN, ep_mode=L.EP_DGELU_SAVED, transposed=1,
+                       aux0=gpd, aux1=hd, scale=scd)
     rows = lib.bnerv_conv_partial_rows(C.byref(d))
     small = Cc == 30 and k == 0                                                    # the low-resolution family takes 30 -> 30 at 9x16 only when aligned
     assert rows == (((H + 3) // 4) * ((W + 15) // 16) if small else lib.bnerv_conv_tiles(H, W))

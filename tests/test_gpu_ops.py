@@ -185,6 +185,63 @@ def test_stem_pair_input_gradient_is_complete_for_a_stock_consumer(ops, dx_ok):
     close(gb, rb.float(), msg="stem pair db")
 
 
+def _chain_consumer(kind, fn, x, p):
+    """Consumer A of the chained stem-pair test on x [1, 24, 4, 8] -> [1, 32, 8, 16]: `fn` is the ops module or None (float64 reference)."""
+    if kind == "conv2d_ps":
+        return fn.conv2d_ps(x, p[0], p[1], 2) if fn else F.pixel_shuffle(F.conv2d(x, p[0], p[1], padding=1), 2)
+    if kind == "upconv_gelu":
+        return fn.upconv_act(x, p[0], p[1], 2, "gelu") if fn else F.gelu(F.pixel_shuffle(F.conv2d(x, p[0], p[1], padding=1), 2))
+    if fn:
+        return fn.snerv_block(x, *p, 2)
+    wu, bu, s0, t0, s1, t1, w0, b0, w1, b1 = p
+    y0 = torch.sin(F.pixel_shuffle(F.conv2d(x, wu, bu, padding=1), 2))
+    h = F.gelu(F.conv2d(y0 * (s0 + 1) + t0, w0, b0, padding=1))
+    return y0 + F.conv2d(h * (s1 + 1) + t1, w1, b1, padding=1)
+
+
+@pytest.mark.parametrize("kind", ["conv2d_ps", "snerv_block", "upconv_gelu"])
+def test_stem_pair_input_gradient_is_complete_for_the_next_block_of_this_package(ops, kind):
+    """Two consecutive blocks that BOTH take the stem pair (a decoder whose second stage still has <= 256 pixels): block B (conv2d_ps
+    32 -> 128, PixelShuffle(2) at 8x16) returns its input gradient as a queued slab reduction under lazy_flush(dx_ok=True), and block
+    A (24 -> 128, PixelShuffle(2) at 4x8: conv2d_ps | snerv_block with a 32-channel TAT | upconv_act gelu) reads it -- A's backward
+    must flush before its first launch.  These are the smallest shapes stem.hip's stem_dgrad_shape / bnerv_stem_pair_try take.
+    Every gradient against float64 autograd, with NaN in the pool blocks both input gradients are carved from."""
+    from boosting_nerv_amd import _lib as L
+    g = torch.Generator().manual_seed(17)
+    rn = lambda *sh, sc=1.0: torch.randn(*sh, generator=g) * sc
+    x = rn(1, 24, 4, 8)
+    pa = [rn(128, 24, 3, 3, sc=1 / math.sqrt(24 * 9)), rn(128, sc=0.1)]
+    if kind == "snerv_block":
+        pa += [rn(1, 32, 1, 1, sc=0.2) for _ in range(4)] + [rn(32, 32, 3, 3, sc=1 / math.sqrt(32 * 9)), rn(32, sc=0.1),
+                                                             rn(32, 32, 3, 3, sc=1 / math.sqrt(32 * 9)), rn(32, sc=0.1)]
+    pb = [rn(128, 32, 3, 3, sc=1 / math.sqrt(32 * 9)), rn(128, sc=0.1)]
+    cot = rn(1, 32, 16, 32)
+    leaves = [x] + pa + pb
+    rl = [t.double().requires_grad_(True) for t in leaves]
+    ref = F.pixel_shuffle(F.conv2d(_chain_consumer(kind, None, rl[0], rl[1:1 + len(pa)]), rl[-2], rl[-1], padding=1), 2)
+    rgrads = torch.autograd.grad(ref, rl, cot.double())
+    gl = [t.to(DEV).requires_grad_(True) for t in leaves]
+
+    # layer B alone: the library must take the queued form for this shape, or the chained case below proves nothing.  The stem pair
+    # writes dW / db directly, so what is pending inside the block is the reduction of the input gradient.
+    xb = rn(1, 32, 8, 16).to(DEV).requires_grad_(True)
+    with ops.lazy_flush(dx_ok=True):
+        torch.autograd.grad(ops.conv2d_ps(xb, gl[-2], gl[-1], 2), [xb], cot.to(DEV))
+        assert L.load().bnerv_deferred_pending(L.ctx().handle) >= 1, "layer B's input gradient is no longer a queued reduction"
+
+    mid = _chain_consumer(kind, ops, gl[0], gl[1:1 + len(pa)])
+    out = ops.conv2d_ps(mid, gl[-2], gl[-1], 2)
+    close(out, ref.float(), msg="stem pair chain fwd")
+    _poison_pool([(1, 24, 4, 8), (1, 32, 8, 16)])
+    hook = gl[0].register_hook(lambda gr: ops._flush_deferred())      # the flushing reader the model vouches for (of the FIRST block only)
+    with ops.lazy_flush(dx_ok=True):
+        grads = torch.autograd.grad(out, gl, cot.to(DEV))
+    hook.remove()
+    for i, (a, r) in enumerate(zip(grads, rgrads)):
+        assert torch.isfinite(a).all(), f"stem pair chain [{kind}] grad {i}: non-finite (an unreduced buffer was read)"
+        close(a, r.float(), msg=f"stem pair chain [{kind}] grad {i}")
+
+
 # ---------------------------------------------------------------------------------------------------------------- conv
 CONV_CASES = [  # B, Cin, Cout_total, H, W, k, s
     (1, 12, 12, 16, 64, 3, 1), (2, 12, 48, 9, 33, 3, 2), (1, 15, 48, 11, 40, 3, 2), (2, 30, 750, 9, 16, 3, 5),
