@@ -17,6 +17,10 @@ DENSE_DX_CHUNK = 64
 ACT_NONE, ACT_RELU, ACT_SIN = 0, 1, 2
 IN_PLAIN, IN_AFFINE, IN_GELU_AFFINE, IN_UNSHUFFLE, IN_TANHGRAD = 0, 1, 2, 3, 4
 EP_BIAS, EP_BIAS_SIN, EP_BIAS_RES, EP_BIAS_TANH, EP_PLAIN, EP_DGELU, EP_DSIN, EP_BIAS_GELU, EP_DGELU_SAVED = 0, 1, 2, 3, 4, 5, 6, 7, 8
+# kernel families / pair forms reported by bnerv_conv_family, bnerv_conv_wgrad_family, bnerv_conv_wgrad_pair_form (BNERV_CONV_FAM_* ...)
+CONV_FAM = ("head1_fwd", "head1_dgrad", "head3", "stem_dgrad", "small", "small96", "wide_bf16", "q4", "generic")
+WGRAD_FAM = ("stem", "gemm1x1", "lean", "wide_bf16", "wide_f32", "generic")
+PAIR_FORM = ("stem", "q4_lean", "small_wide", "bf16_wide", "head")      # -1: none
 
 _fp = C.c_void_p     # device pointers travel as void* (data_ptr())
 
@@ -135,9 +139,12 @@ SYMBOLS = {
     "bnerv_conv_igemm": (_I, [_V, C.POINTER(ConvDesc)]),
     "bnerv_conv_splitk_ws_bytes": (_Z, [C.POINTER(ConvDesc)]),
     "bnerv_conv_partial_rows": (_I, [C.POINTER(ConvDesc)]),
+    "bnerv_conv_family": (_I, [C.POINTER(ConvDesc), C.POINTER(C.c_int)]),
     "bnerv_conv_wgrad_ws_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
     "bnerv_conv_wgrad_pair": (_I, [_V, C.POINTER(ConvDesc), C.POINTER(WgradDesc)]),
+    "bnerv_conv_wgrad_pair_form": (_I, [C.POINTER(ConvDesc), C.POINTER(WgradDesc), C.POINTER(C.c_int)]),
     "bnerv_conv_wgrad": (_I, [_V, C.POINTER(WgradDesc)]),
+    "bnerv_conv_wgrad_family": (_I, [C.POINTER(WgradDesc), C.POINTER(C.c_int)]),
     "bnerv_conv5_ws_bytes": (_Z, [_I, _I]),
     "bnerv_conv5_igemm": (_I, [_V, C.POINTER(ConvDesc), _V, _Z]),
     "bnerv_conv5_wgrad_ws_bytes": (_Z, [_I, _I, _I, _I, _I]),

@@ -20,18 +20,7 @@
 // Each wave owns 2 rows x 32 px = 4 M-tiles; acc[4][NTB] (f32x4) stays in registers for the whole K loop.
 #include "common.h"
 #include "sidejob.h"
-#include "conv_common.h"
-#include "launch.h"
-
-int bnerv_convbf_try(hipStream_t st, const bnerv_conv_desc& d, int vec, int ksplit, int chunks_per_split);   // convbf.hip
-namespace bnerv_conv { struct KArgs; }
-int bnerv_conv4_try(hipStream_t st, bnerv_conv::KArgs& ka);   // conv4.hip: 1 = not that family's layer
-int bnerv_convs_try(hipStream_t st, const bnerv_conv_desc& d, int vec, int ksplit);   // convs.hip (low-resolution stages): 1 = not that family's layer
-int bnerv_head3_try(hipStream_t st, const bnerv_conv_desc& d);            // head3.hip (3x3 head with 3 outputs: forward + tanh, data gradient): 1 = not that layer
-bool bnerv_convs_shape_ok(const bnerv_conv_desc& d, int vec);
-int bnerv_stem_dgrad_try(hipStream_t st, const bnerv_conv_desc& d);       // stem.hip (images of <= 256 pixels, long K): 1 = not that layer
-size_t bnerv_stem_dgrad_ws_bytes(const bnerv_conv_desc& d);
-int bnerv_convs_tiles(int H, int W);
+#include "route.h"
 
 namespace {
 using namespace bnerv_conv;
@@ -1560,17 +1549,15 @@ int launch_mode(hipStream_t st, KArgs& ka) {
     return bnerv_set_error(BNERV_E_ARG, "conv_igemm: unsupported (k=%d, in_mode=%d, ep_mode=%d)", KS, in, ep);
 }
 
-// Split-K policy: layers with a long K loop and almost no spatial parallelism (the low-resolution data gradients:
-// Cin = 750 or 1975 at 9x16 = 2 tiles) spread the input-channel chunks over work items.  Only for EP_PLAIN, out_s == 1.
-struct SplitPlan { int ksplit, chunks_per_split; };
-SplitPlan plan_split(const bnerv_conv_desc& d) {
-    SplitPlan p{1, 0};
+// Split-K policy (route.h bnerv_split_plan)
+bnerv_split_plan plan_split(const bnerv_conv_desc& d) {
+    bnerv_split_plan p{1, 0};
     if (d.ep_mode != BNERV_EP_PLAIN || d.out_s != 1) return p;
     const int nchunks = cdiv(d.Cin, CC);
     const int nt = cdiv(d.Cout, 16);
     const int ngroups = cdiv(nt, nt >= 4 ? 4 : nt);
     const int items = ngroups * d.B * cdiv(d.H, TH) * cdiv(d.W, TW);
-    if (nchunks < 8 || items >= 128) return p;
+    if (nchunks < 8 || items >= 128 || items < 1) return p;      // (< 1: bnerv_conv_partial_rows routes a descriptor of which it validated H and W only)
     int ks = 512 / items;
     if (ks > nchunks) ks = nchunks;
     if (ks < 2) return p;
@@ -1585,14 +1572,6 @@ SplitPlan plan_split(const bnerv_conv_desc& d) {
 extern "C" int bnerv_debug_trace_read(void* host) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_trace), sizeof(g_trace)); }
 #endif
 extern "C" int bnerv_conv_tiles(int H, int W) { return cdiv(H, TH) * cdiv(W, TW); }
-
-extern "C" int bnerv_conv_partial_rows(const bnerv_conv_desc* dp) {
-    if (!dp || dp->H <= 0 || dp->W <= 0) return 0;
-    bnerv_conv_desc d = *dp;
-    if (d.in_mode == BNERV_IN_UNSHUFFLE && d.in_s == 1) d.in_mode = BNERV_IN_PLAIN;
-    if (bnerv_convs_shape_ok(d, conv_vec_ok(d))) return bnerv_convs_tiles(d.H, d.W);      // the low-resolution family (convs.hip): 4x16 tiles
-    return cdiv(d.H, TH) * cdiv(d.W, TW);     // every other kernel of this build uses 8x32 tiles; callers must still ask
-}
 
 // Data gradient of a 1x1 head (reference: head_layer 1x1 C->3 + OutImg tanh, model_nerv.py:41,56-57): 3 -> C channels with the
 // tanh-grad prologue is 9*C FMAs per pixel against 6 loaded and C stored floats -- a streaming kernel, not a GEMM (the MFMA
@@ -1665,19 +1644,100 @@ __global__ __launch_bounds__(256) void head1x1_fwd_kernel(const bnerv_conv_desc 
 }
 }  // namespace
 
+// the 1x1 head's streaming kernels: 12 -> 3 + tanh forward, and the data gradient of a head with <= 4 outputs
+static bool head1_fwd_ok(const bnerv_conv_desc& d, int vec) {
+    return d.k == 1 && d.in_mode == BNERV_IN_PLAIN && d.ep_mode == BNERV_EP_BIAS_TANH && d.out_s == 1 && vec && !d.transposed &&
+           d.Cin == 12 && d.Cout == 3 && d.wCo == 3 && d.wCi == 12 && ((size_t)d.H * d.W) % 4 == 0 && d.B <= 65535;
+}
+static bool head1_dgrad_ok(const bnerv_conv_desc& d, int vec) {
+    return d.k == 1 && d.in_mode == BNERV_IN_TANHGRAD && d.ep_mode == BNERV_EP_PLAIN && d.out_s == 1 && vec &&
+           d.Cin <= HEAD_KMAX && d.Cout <= HEAD_CMAX && ((size_t)d.H * d.W) % 4 == 0 && d.B <= 65535;
+}
+
+// THE order of the conv families.  Pure: reads the descriptor (pointer values included) and the environment switches, touches no device.
+bnerv_conv_route_t bnerv_conv_route(const bnerv_conv_desc& din, int skip) {
+    bnerv_conv_route_t r{};
+    r.d = din;
+    bnerv_conv_desc& d = r.d;
+    if (d.in_mode == BNERV_IN_UNSHUFFLE && d.in_s == 1) d.in_mode = BNERV_IN_PLAIN;       // same gather, faster staging
+    r.vec = conv_vec_ok(d);
+    r.th = TH;
+    r.tw = TW;
+    r.split = {1, 0};
+    const bool ws = d.ep_mode == BNERV_EP_PLAIN && d.partial != nullptr;      // the caller supplied an EP_PLAIN workspace: split-K or the stem's slabs
+    const bnerv_split_plan sp = ws ? plan_split(d) : r.split;
+    auto is = [&](int family, bool ok) { if (family == skip || !ok) return false; r.family = family; return true; };
+    if (is(BNERV_CONV_FAM_HEAD1_FWD, head1_fwd_ok(d, r.vec))) return r;
+    if (is(BNERV_CONV_FAM_HEAD1_DGRAD, sp.ksplit == 1 && head1_dgrad_ok(d, r.vec))) return r;
+    if (is(BNERV_CONV_FAM_HEAD3, sp.ksplit == 1 && bnerv_head3_ok(d))) return r;          // HNeRV-boost's 3x3 head and its data gradient: streaming VALU kernels
+    if (is(BNERV_CONV_FAM_STEM_DGRAD, ws && bnerv_stem_dgrad_ok(d))) {                    // tiny image, long K (the stem up-conv's data gradient)
+        r.ws_bytes = bnerv_stem_dgrad_ws_bytes(d);
+        return r;
+    }
+    if (is(BNERV_CONV_FAM_SMALL, sp.ksplit == 1 && bnerv_convs_ok(d, r.vec))) {           // the low-resolution stages: small images, <= 32 (96) input channels
+        if (bnerv_convs_nq(d) == 24) r.family = BNERV_CONV_FAM_SMALL96;
+        r.th = BNERV_CONVS_TH;
+        r.tw = BNERV_CONVS_TW;
+        return r;
+    }
+    // the remaining families honour the split-K plan: its slabs are reduced by the entry point
+    r.split = sp;
+    if (sp.ksplit > 1) r.ws_bytes = (size_t)sp.ksplit * d.B * d.Cout * d.H * d.W * sizeof(float);
+    if (is(BNERV_CONV_FAM_WIDE_BF16, bnerv_convbf_ok(d, r.vec, sp.ksplit))) return r;     // split-bf16 kernels: the wide layers
+    if (is(BNERV_CONV_FAM_Q4, bnerv_conv4_ok(bnerv_conv_kargs(d, r.vec, sp)))) return r;  // <= 12-channel 3x3 layers on the 4x4x1 MFMA family
+    r.family = BNERV_CONV_FAM_GENERIC;
+    return r;
+}
+
+static int conv_launch(hipStream_t st, const bnerv_conv_route_t& r) {
+    const bnerv_conv_desc& d = r.d;
+    switch (r.family) {
+    case BNERV_CONV_FAM_HEAD1_FWD: {
+        const int hw4 = (int)(((size_t)d.H * d.W) / 4);
+        hipLaunchKernelGGL((head1x1_fwd_kernel<3, 12>), dim3(cdiv(hw4, 256), d.B), dim3(256), 0, st, d, hw4);
+        BNERV_LAUNCH_CHECK("head1x1_fwd");
+        return BNERV_OK;
+    }
+    case BNERV_CONV_FAM_HEAD1_DGRAD: {
+        const int hw4 = (int)(((size_t)d.H * d.W) / 4);
+        hipLaunchKernelGGL(head1x1_dgrad_kernel, dim3(cdiv(hw4, 256), d.B), dim3(256), 0, st, d, hw4);
+        BNERV_LAUNCH_CHECK("head1x1_dgrad");
+        return BNERV_OK;
+    }
+    case BNERV_CONV_FAM_HEAD3: return bnerv_head3_launch(st, d);
+    case BNERV_CONV_FAM_STEM_DGRAD: return bnerv_stem_dgrad_launch(st, d);
+    case BNERV_CONV_FAM_SMALL:
+    case BNERV_CONV_FAM_SMALL96: return bnerv_convs_launch(st, d);
+    case BNERV_CONV_FAM_WIDE_BF16: return bnerv_convbf_launch(st, d, r.split);
+    default: break;
+    }
+    KArgs ka = bnerv_conv_kargs(d, r.vec, r.split);
+    if (r.family == BNERV_CONV_FAM_Q4) return bnerv_conv4_launch(st, ka);
+    return d.k == 1 ? launch_mode<1>(st, ka) : launch_mode<3>(st, ka);
+}
+
+static bool conv_dims_ok(const bnerv_conv_desc* d) { return d && d->B > 0 && d->Cin > 0 && d->Cout > 0 && d->H > 0 && d->W > 0; }
+
+extern "C" int bnerv_conv_partial_rows(const bnerv_conv_desc* dp) {
+    return (dp && dp->H > 0 && dp->W > 0) ? bnerv_conv_route(*dp).rows() : 0;      // the tiles of the family that runs: callers must ask, never assume 8x32
+}
+
+extern "C" int bnerv_conv_family(const bnerv_conv_desc* dp, int* rows) {
+    const bool ok = conv_dims_ok(dp) && (dp->k == 1 || dp->k == 3);
+    if (rows) *rows = ok ? bnerv_conv_partial_rows(dp) : 0;
+    return ok ? bnerv_conv_route(*dp).family : -1;
+}
+
 extern "C" size_t bnerv_conv_splitk_ws_bytes(const bnerv_conv_desc* dp) {
-    if (!dp || dp->B <= 0 || dp->Cin <= 0 || dp->Cout <= 0 || dp->H <= 0 || dp->W <= 0) return 0;
-    const SplitPlan p = plan_split(*dp);
-    const size_t a = p.ksplit > 1 ? (size_t)p.ksplit * dp->B * dp->Cout * dp->H * dp->W * sizeof(float) : 0;
-    const size_t b = bnerv_stem_dgrad_ws_bytes(*dp);       // the stem stage's data gradient (stem.hip) keeps one slab per 8 input channels
-    return a > b ? a : b;
+    if (!conv_dims_ok(dp)) return 0;
+    bnerv_conv_desc d = *dp;
+    if (!d.partial) d.partial = d.out ? d.out : reinterpret_cast<float*>(&d);     // "were a workspace given": the route only tests it against NULL
+    return bnerv_conv_route(d).ws_bytes;
 }
 
 extern "C" int bnerv_conv_igemm(void* stream, const bnerv_conv_desc* dp) {
     BNERV_REQUIRE(dp != nullptr, "conv_igemm: null descriptor");
-    KArgs ka;
-    ka.d = *dp;
-    bnerv_conv_desc& d = ka.d;
+    const bnerv_conv_desc& d = *dp;
     BNERV_REQUIRE(d.k == 1 || d.k == 3, "conv_igemm: k must be 1 or 3 (got %d)", d.k);
     BNERV_REQUIRE(d.B > 0 && d.Cin > 0 && d.Cout > 0 && d.H > 0 && d.W > 0, "conv_igemm: bad dims");
     BNERV_REQUIRE(d.x && d.w && d.out, "conv_igemm: null tensor");
@@ -1693,52 +1753,16 @@ extern "C" int bnerv_conv_igemm(void* stream, const bnerv_conv_desc* dp) {
     if (d.ep_mode == BNERV_EP_DSIN) BNERV_REQUIRE(d.aux0 && d.aux1 && d.scale && d.partial && d.out_s == 1, "conv_igemm: DSIN epilogue args");
     if (d.ep_mode == BNERV_EP_DGELU_SAVED) BNERV_REQUIRE(d.aux0 && d.aux1 && d.scale && d.partial && d.out_s == 1, "conv_igemm: DGELU_SAVED epilogue args");
     if (d.ep_mode == BNERV_EP_BIAS_GELU) BNERV_REQUIRE(d.out_s == 1, "conv_igemm: BIAS_GELU epilogue needs a stride-1 output");   // out2 NULL: gelu only
-    if (d.in_mode == BNERV_IN_UNSHUFFLE && d.in_s == 1) d.in_mode = BNERV_IN_PLAIN;       // same gather, faster staging
-    ka.tiles_x = cdiv(d.W, TW);
-    ka.tiles_y = cdiv(d.H, TH);
-    ka.vec = conv_vec_ok(d);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    ka.ksplit = 1;
-    ka.chunks_per_split = 0;
-    ka.magic_tiles = ka.magic_tiles_x = 0;
-    if (d.ep_mode == BNERV_EP_PLAIN && d.partial != nullptr) {            // caller supplied a split-K workspace
-        const SplitPlan p = plan_split(d);
-        ka.ksplit = p.ksplit;
-        ka.chunks_per_split = p.chunks_per_split;
+    bnerv_conv_route_t r = bnerv_conv_route(d);
+    int rc = conv_launch(st, r);
+    if (rc == BNERV_DECLINED) {                            // a resource reason (no scratch for the wide kernels' weight fragments): the next family in order,
+        const bnerv_conv_route_t next = bnerv_conv_route(d, r.family);      // which must write the rows the first answer promised the caller
+        if (next.th != r.th || next.tw != r.tw)
+            return bnerv_set_error(BNERV_E_ARG, "conv_igemm: family %d declined and family %d has other tiles (%dx%d, not %dx%d)", r.family, next.family, next.th, next.tw, r.th, r.tw);
+        r = next;
+        rc = conv_launch(st, r);
     }
-    if (d.k == 1 && d.in_mode == BNERV_IN_PLAIN && d.ep_mode == BNERV_EP_BIAS_TANH && d.out_s == 1 && ka.vec && !d.transposed &&
-        d.Cin == 12 && d.Cout == 3 && d.wCo == 3 && d.wCi == 12 && ((size_t)d.H * d.W) % 4 == 0 && d.B <= 65535) {
-        const int hw4 = (int)(((size_t)d.H * d.W) / 4);
-        hipLaunchKernelGGL((head1x1_fwd_kernel<3, 12>), dim3(cdiv(hw4, 256), d.B), dim3(256), 0, st, d, hw4);
-        BNERV_LAUNCH_CHECK("head1x1_fwd");
-        return BNERV_OK;
-    }
-    if (d.k == 1 && d.in_mode == BNERV_IN_TANHGRAD && d.ep_mode == BNERV_EP_PLAIN && d.out_s == 1 && ka.vec && ka.ksplit == 1 &&
-        d.Cin <= HEAD_KMAX && d.Cout <= HEAD_CMAX && ((size_t)d.H * d.W) % 4 == 0 && d.B <= 65535) {
-        const int hw4 = (int)(((size_t)d.H * d.W) / 4);
-        hipLaunchKernelGGL(head1x1_dgrad_kernel, dim3(cdiv(hw4, 256), d.B), dim3(256), 0, st, d, hw4);
-        BNERV_LAUNCH_CHECK("head1x1_dgrad");
-        return BNERV_OK;
-    }
-    if (d.k == 3 && (d.Cout == 3 || d.Cin == 3) && ka.ksplit == 1) {      // HNeRV-boost's 3x3 head and its data gradient: streaming VALU kernels
-        const int rh = bnerv_head3_try(st, d);
-        if (rh != 1) return rh;
-    }
-    if (d.ep_mode == BNERV_EP_PLAIN && d.partial != nullptr) {            // tiny image, long K (the stem up-conv's data gradient)
-        const int rs = bnerv_stem_dgrad_try(st, d);
-        if (rs != 1) return rs;
-    }
-    {   // the low-resolution stages (convs.hip) first: small images, <= 32 input channels
-        const int rs = bnerv_convs_try(st, d, ka.vec, ka.ksplit);
-        if (rs != 1) return rs;
-    }
-    // split-bf16 kernels (convbf.hip) next: the wide layers (with the same split-K plan: its slabs are reduced below)
-    int rc = bnerv_convbf_try(st, d, ka.vec, ka.ksplit, ka.chunks_per_split);
-    if (rc == 1) {                                         // +1: not the split kernels' layer (negative values are real errors)
-        ka.magic_tiles = ka.magic_tiles_x = 0;
-        rc = bnerv_conv4_try(st, ka);                      // <= 12-channel 3x3 layers on the 4x4x1 MFMA family
-        if (rc == 1) rc = d.k == 1 ? launch_mode<1>(st, ka) : launch_mode<3>(st, ka);
-    }
-    if (rc != BNERV_OK || ka.ksplit == 1) return rc;
-    return bnerv_reduce_slabs(stream, d.partial, ka.ksplit, d.B * d.Cout * d.H * d.W, d.out);
+    if (rc != BNERV_OK || r.split.ksplit == 1) return rc;
+    return bnerv_reduce_slabs(stream, r.d.partial, r.split.ksplit, r.d.B * r.d.Cout * r.d.H * r.d.W, r.d.out);
 }

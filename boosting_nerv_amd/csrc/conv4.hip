@@ -19,7 +19,7 @@
 // Tile geometry, staging (raw buffer loads prefetched under the matrix phase, prologue applied on the way into LDS), item
 // partition, epilogues and the hosted slab reductions are those of conv_lean_kernel (conv.hip).
 #include "conv4_body.h"
-#include "launch.h"
+#include "route.h"
 
 namespace {
 using namespace bnerv_conv;
@@ -43,22 +43,27 @@ int launch_q4(hipStream_t st, KArgs& ka) {
     return BNERV_OK;
 }
 
-}  // namespace
-
-#ifdef BNERV_TRACE
-extern "C" int bnerv_debug_trace4_read(void* host) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_trace4), sizeof(g_trace4)); }
-#endif
-// 1: not this family's layer (the caller goes on to the 16x16x4 kernels); BNERV_OK / negative BNERV_E_*: handled.
-int bnerv_conv4_try(hipStream_t st, bnerv_conv::KArgs& ka) {
-    const bnerv_conv_desc& d = ka.d;
-    if (!q4_shape_ok(ka)) return 1;
-    const int in = d.in_mode, ep = d.ep_mode;
-#define BNERV_CASE(I, E) if (in == I && ep == E) return launch_q4<I, E>(st, ka);
+// The (in, ep) pairs this family is instantiated for, written once: f(mode_c<IN>, mode_c<EP>) is called for the descriptor's pair; -1 for any other.
+template <class F>
+int q4_modes(const bnerv_conv_desc& d, F&& f) {
+#define BNERV_CASE(I, E) if (d.in_mode == I && d.ep_mode == E) return f(mode_c<I>{}, mode_c<E>{});
     BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_BIAS)
     BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_BIAS_SIN)
     BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_PLAIN)
     BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_DGELU_SAVED)
     BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_DSIN)
 #undef BNERV_CASE
-    return 1;
+    return -1;
+}
+
+}  // namespace
+
+#ifdef BNERV_TRACE
+extern "C" int bnerv_debug_trace4_read(void* host) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_trace4), sizeof(g_trace4)); }
+#endif
+bool bnerv_conv4_ok(const bnerv_conv::KArgs& ka) {
+    return q4_shape_ok(ka) && q4_modes(ka.d, [](auto, auto) { return 0; }) == 0;
+}
+int bnerv_conv4_launch(hipStream_t st, bnerv_conv::KArgs& ka) {
+    return q4_modes(ka.d, [&](auto in, auto ep) { return launch_q4<decltype(in)::value, decltype(ep)::value>(st, ka); });
 }

@@ -8,9 +8,7 @@
 #include "sidejob.h"
 #include "split16.h"
 #include "wgrad_bfw_body.h"   // the wide weight-gradient body: one role of the paired launch at the bottom of this file
-#include "launch.h"
-
-constexpr int BF_NOT_HANDLED = 1;     // "not this family's layer" (bnerv_convbf_try and the launchers below); errors stay negative
+#include "route.h"
 
 namespace {
 
@@ -712,7 +710,7 @@ int launch_bfw(hipStream_t st, KArgs& ka) {
     const bnerv_conv_desc& d = ka.d;
     const int nck = cdiv(d.Cin, 16), ngroups = cdiv(cdiv(d.Cout, 16), NTB);
     const void* scratch = weight_fragments<NS>(st, d, nck, NTB, ngroups);
-    if (!scratch) return BF_NOT_HANDLED;
+    if (!scratch) return BNERV_DECLINED;
     ka.total_items = ka.ksplit * ngroups * d.B * ka.tiles_x * ka.tiles_y;
     ka.magic_tiles = div_magic(ka.tiles_x * ka.tiles_y);
     ka.magic_tiles_x = div_magic(ka.tiles_x);
@@ -772,7 +770,7 @@ int launch_bfw_pair(hipStream_t st, KArgs& ka, const bnerv_wb::WArgs& wa, int sl
     const bnerv_conv_desc& d = ka.d;
     const int nck = cdiv(d.Cin, 16), ngroups = cdiv(cdiv(d.Cout, 16), NTB);
     const void* scratch = weight_fragments<NS>(st, d, nck, NTB, ngroups);
-    if (!scratch) return BF_NOT_HANDLED;
+    if (!scratch) return BNERV_DECLINED;
     ka.total_items = ngroups * d.B * ka.tiles_x * ka.tiles_y;
     ka.magic_tiles = div_magic(ka.tiles_x * ka.tiles_y);
     ka.magic_tiles_x = div_magic(ka.tiles_x);
@@ -787,32 +785,59 @@ int launch_bfw_pair(hipStream_t st, KArgs& ka, const bnerv_wb::WArgs& wa, int sl
     return BNERV_OK;
 }
 
-int launch_wide_mode(hipStream_t st, KArgs& ka) {
-    const int in = ka.d.in_mode, ep = ka.d.ep_mode;
-    if (ka.d.out_s == 3 || ka.d.out_s == 5) {              // up-conv forward through PixelShuffle(3 / 5): scatter stores
-        if (in == BNERV_IN_PLAIN && ep == BNERV_EP_BIAS_SIN) return launch_bfw_sp<BNERV_IN_PLAIN, BNERV_EP_BIAS_SIN, 3>(st, ka);
-        if (in == BNERV_IN_PLAIN && ep == BNERV_EP_BIAS) return launch_bfw_sp<BNERV_IN_PLAIN, BNERV_EP_BIAS, 3>(st, ka);
-        return BF_NOT_HANDLED;
+// The (in, ep, output shuffle) triples this family is instantiated for, written once: f(mode_c<IN>, mode_c<EP>, mode_c<PS2>) is called for
+// the descriptor's triple; -1 for any other (bnerv_convbf_ok asks with an f that launches nothing).
+template <class F>
+int wide_modes(const bnerv_conv_desc& d, F&& f) {
+    const int in = d.in_mode, ep = d.ep_mode;
+#define BNERV_CASE(I, E, P) if (in == I && ep == E) return f(mode_c<I>{}, mode_c<E>{}, mode_c<P>{});
+    if (d.out_s == 3 || d.out_s == 5) {                    // up-conv forward through PixelShuffle(3 / 5): scatter stores
+        BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_BIAS_SIN, 3)
+        BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_BIAS, 3)
+    } else if (d.out_s == 2) {                             // up-conv forward: conv -> bias -> PixelShuffle(2) [-> sin, cos]
+        BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_BIAS_SIN, 2)
+        BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_BIAS, 2)
+    } else if (d.out_s == 1) {
+        BNERV_CASE(BNERV_IN_UNSHUFFLE, BNERV_EP_PLAIN, 0)
+        BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_BIAS, 0)
+        BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_BIAS_SIN, 0)
+        BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_BIAS_TANH, 0)
+        BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_PLAIN, 0)
+        BNERV_CASE(BNERV_IN_AFFINE, BNERV_EP_BIAS, 0)
+        BNERV_CASE(BNERV_IN_GELU_AFFINE, BNERV_EP_BIAS_RES, 0)
+        BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_DSIN, 0)
+        BNERV_CASE(BNERV_IN_AFFINE, BNERV_EP_BIAS_GELU, 0)
+        BNERV_CASE(BNERV_IN_AFFINE, BNERV_EP_BIAS_RES, 0)
+        BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_DGELU_SAVED, 0)
     }
-    if (ka.d.out_s == 2) {                                 // up-conv forward: conv -> bias -> PixelShuffle(2) [-> sin, cos]
-        if (in == BNERV_IN_PLAIN && ep == BNERV_EP_BIAS_SIN) return launch_bfw_sp<BNERV_IN_PLAIN, BNERV_EP_BIAS_SIN, 2>(st, ka);
-        if (in == BNERV_IN_PLAIN && ep == BNERV_EP_BIAS) return launch_bfw_sp<BNERV_IN_PLAIN, BNERV_EP_BIAS, 2>(st, ka);
-        return BF_NOT_HANDLED;
-    }
-    if (in == BNERV_IN_UNSHUFFLE) return ep == BNERV_EP_PLAIN ? launch_bfw_sp<BNERV_IN_UNSHUFFLE, BNERV_EP_PLAIN>(st, ka) : -1;
-#define BNERV_CASE(I, E) if (in == I && ep == E) return launch_bfw_sp<I, E>(st, ka);
-    BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_BIAS)
-    BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_BIAS_SIN)
-    BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_BIAS_TANH)
-    BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_PLAIN)
-    BNERV_CASE(BNERV_IN_AFFINE, BNERV_EP_BIAS)
-    BNERV_CASE(BNERV_IN_GELU_AFFINE, BNERV_EP_BIAS_RES)
-    BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_DSIN)
-    BNERV_CASE(BNERV_IN_AFFINE, BNERV_EP_BIAS_GELU)
-    BNERV_CASE(BNERV_IN_AFFINE, BNERV_EP_BIAS_RES)
-    BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_DGELU_SAVED)
 #undef BNERV_CASE
-    return BF_NOT_HANDLED;
+    return -1;
+}
+
+// the host-side part of KArgs (the launchers add their item bookkeeping)
+KArgs bf_kargs(const bnerv_conv_desc& d, bnerv_split_plan sp) {
+    KArgs ka{};
+    ka.d = d;
+    ka.tiles_x = cdiv(d.W, TW);
+    ka.tiles_y = cdiv(d.H, TH);
+    ka.ksplit = sp.ksplit > 1 ? sp.ksplit : 1;
+    ka.cps = sp.ksplit > 1 ? sp.chunks_per_split : cdiv(d.Cin, 16);
+    return ka;
+}
+
+// The paired form's instantiations (conv role: in, ep, cout tiles per block | weight-gradient role: in, cout tiles, shuffled gradient), written
+// once.  An up-conv's (dW | d input) where the data gradient has ONE output tile (<= 16 channels: the 12 -> 48 up-convs of the 12-channel
+// stages): unshuffle(2) prologue | plain input, shuffled gradient.  Measured and NOT instantiated: the 38-channel TAT / block convs of C3
+// (both roles three tiles wide, matrix-bound) ran 18.54 ms per step paired against 18.21 ms with their own launches.
+template <class F>
+int bf_pair_modes(const bnerv_conv_desc& d, const bnerv_wgrad_desc& w, int ntb, int w_mtw, F&& f) {
+    const int gm2 = w.g_s == 2 ? 1 : 0;
+#define BNERV_BP(CI, CE, NT, WI, MT, G2) if (d.in_mode == CI && d.ep_mode == CE && ntb == NT && w.in_mode == WI && w_mtw == MT && gm2 == G2) \
+        return f(mode_c<CI>{}, mode_c<CE>{}, mode_c<NT>{}, mode_c<WI>{}, mode_c<MT>{}, mode_c<G2>{});
+    BNERV_BP(BNERV_IN_UNSHUFFLE, BNERV_EP_PLAIN, 1, BNERV_IN_PLAIN, 3, 1)
+    BNERV_BP(BNERV_IN_UNSHUFFLE, BNERV_EP_PLAIN, 1, BNERV_IN_PLAIN, 2, 1)
+#undef BNERV_BP
+    return -1;
 }
 
 }  // namespace
@@ -911,73 +936,64 @@ extern "C" int bnerv_ctx_wplan_entries(const bnerv_ctx* ctx) { return (ctx && ct
 extern "C" int bnerv_debug_trace_read_bfw(void* host) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_trace_bfw), sizeof(g_trace_bfw)); }
 #endif
 
-// Called by bnerv_conv_igemm (conv.hip) after argument validation.  Returns BF_NOT_HANDLED (+1: not a BNERV_E_* value, so a real
-// argument / launch error raised on this path is never mistaken for it) when the shape / mode is not this kernel's -- the caller
-// then takes its f32-MFMA kernels -- otherwise the launch status.
-int bnerv_convbf_try(hipStream_t st, const bnerv_conv_desc& d, int vec, int ksplit, int chunks_per_split) {
-    if (!vec || d.in_mode == BNERV_IN_TANHGRAD) return BF_NOT_HANDLED;
-    if (ksplit > 1 && (d.ep_mode != BNERV_EP_PLAIN || !d.partial || d.out_s != 1)) return BF_NOT_HANDLED;
+// The wide kernels' layers: several cout tiles and / or K chunks (or an up-conv's shuffle), a 3x3 layer with float4 rows and a stream context,
+// an image big enough to fill the chip with its work items, and an instantiated mode.  `ksplit`: the route's split-K plan.
+bool bnerv_convbf_ok(const bnerv_conv_desc& d, int vec, int ksplit) {
+    if (!vec || d.in_mode == BNERV_IN_TANHGRAD) return false;
+    if (ksplit > 1 && (d.ep_mode != BNERV_EP_PLAIN || !d.partial || d.out_s != 1)) return false;
     const bool shuffled = d.out_s != 1 || d.in_mode == BNERV_IN_UNSHUFFLE;                // up-conv forward / its data gradient
-    if (d.out_s != 1 && !((d.out_s == 2 || d.out_s == 3 || d.out_s == 5) && d.Cout % (d.out_s * d.out_s) == 0)) return BF_NOT_HANDLED;
-    if ((size_t)d.B * d.Cout * d.H * d.W * 4 >= LEAN_MAX_BYTES) return BF_NOT_HANDLED;      // (the shuffled output is addressed as one buffer)
-    if (d.in_mode == BNERV_IN_UNSHUFFLE && (!(d.in_s == 2 || d.in_s == 3 || d.in_s == 5) || d.Cin % (d.in_s * d.in_s) != 0 || d.out_s != 1)) return BF_NOT_HANDLED;
+    if (d.out_s != 1 && !((d.out_s == 2 || d.out_s == 3 || d.out_s == 5) && d.Cout % (d.out_s * d.out_s) == 0)) return false;
+    if ((size_t)d.B * d.Cout * d.H * d.W * 4 >= LEAN_MAX_BYTES) return false;      // (the shuffled output is addressed as one buffer)
+    if (d.in_mode == BNERV_IN_UNSHUFFLE && (!(d.in_s == 2 || d.in_s == 3 || d.in_s == 5) || d.Cin % (d.in_s * d.in_s) != 0 || d.out_s != 1)) return false;
     const size_t cmax = (size_t)(d.Cin > d.Cout ? d.Cin : d.Cout);
-    if ((size_t)d.B * cmax * d.H * d.W * 4 + (size_t)(d.W + 4) * 4 >= LEAN_MAX_BYTES) return BF_NOT_HANDLED;
-    KArgs ka;
-    ka.d = d;
-    ka.tiles_x = cdiv(d.W, TW);
-    ka.tiles_y = cdiv(d.H, TH);
-    ka.ksplit = ksplit > 1 ? ksplit : 1;
-    ka.cps = ksplit > 1 ? chunks_per_split : cdiv(d.Cin, 16);
-    if ((size_t)ka.ksplit * d.B * d.Cout * d.H * d.W * 4 >= LEAN_MAX_BYTES) return BF_NOT_HANDLED;
-    if (d.Cout <= 16 && d.Cin <= 16 && !shuffled) return BF_NOT_HANDLED;       // one cout tile, one K chunk: the f32 kernels' layer
-    // several cout tiles and / or K chunks: the wide kernel, where the image is big enough to fill the chip with its work items
-    if (split_wide_mode() < 0 || d.k != 3 || !d.ctx) return BF_NOT_HANDLED;
+    if ((size_t)d.B * cmax * d.H * d.W * 4 + (size_t)(d.W + 4) * 4 >= LEAN_MAX_BYTES) return false;
+    if ((size_t)(ksplit > 1 ? ksplit : 1) * d.B * d.Cout * d.H * d.W * 4 >= LEAN_MAX_BYTES) return false;
+    if (d.Cout <= 16 && d.Cin <= 16 && !shuffled) return false;       // one cout tile, one K chunk: the f32 kernels' layer
+    if (split_wide_mode() < 0 || d.k != 3 || !d.ctx) return false;
     const bool affine = d.in_mode == BNERV_IN_AFFINE || d.in_mode == BNERV_IN_GELU_AFFINE;
-    if (affine && d.Cin > AFF_MAX) return BF_NOT_HANDLED;
-    if (d.B * ka.tiles_x * ka.tiles_y < split_wide_min_tiles()) return BF_NOT_HANDLED;
-    return launch_wide_mode(st, ka);
+    if (affine && d.Cin > AFF_MAX) return false;
+    if (d.B * cdiv(d.W, TW) * cdiv(d.H, TH) < split_wide_min_tiles()) return false;
+    return wide_modes(d, [](auto, auto, auto) { return 0; }) == 0;
 }
 
-// 1: not a pair of this form (the caller goes on).  On BNERV_OK *n_slabs is the weight gradient's slab count.
-// w_mtw / ngn / ngm / nat_slots: the weight gradient's plan for its own launch (wgrad.hip::bw_plan).
-int bnerv_convbf_pair_try(hipStream_t st, const bnerv_conv_desc& d, int vec, const bnerv_wb::WArgs& wa, int w_mtw, int ngn, int ngm, int nat_slots, int* n_slabs) {
-    if (split_wide_mode() != (int)SP_BF16X6 || !vec || d.k != 3 || !d.ctx || d.out_s != 1) return 1;
+// BNERV_DECLINED: no scratch for the weight fragments (weight_fragments) -- the caller takes the next family of its route
+int bnerv_convbf_launch(hipStream_t st, const bnerv_conv_desc& d, bnerv_split_plan sp) {
+    KArgs ka = bf_kargs(d, sp);
+    return wide_modes(d, [&](auto in, auto ep, auto ps2) { return launch_bfw_sp<decltype(in)::value, decltype(ep)::value, decltype(ps2)::value>(st, ka); });
+}
+
+// ---- the pair's wide form (bnerv_conv_wgrad_pair, form 3).  bp: the weight gradient's plan for its own launch (wgrad.hip::bw_plan).
+bnerv_bfpair_plan bnerv_convbf_pair_plan(const bnerv_conv_desc& d, int vec, const bnerv_wgrad_desc& w, const bnerv_wb::BwPlan& bp) {
+    bnerv_bfpair_plan p{false, 0, 0, 0};
+    if (split_wide_mode() != (int)SP_BF16X6 || !vec || d.k != 3 || !d.ctx || d.out_s != 1) return p;
     const bool uns = d.in_mode == BNERV_IN_UNSHUFFLE;
-    if (!(d.in_mode == BNERV_IN_PLAIN || (uns && d.in_s == 2 && d.Cin % 4 == 0))) return 1;
-    if (d.Cout <= 16 && d.Cin <= 16 && !uns) return 1;                                     // (the one-tile kernels' layer)
+    if (!(d.in_mode == BNERV_IN_PLAIN || (uns && d.in_s == 2 && d.Cin % 4 == 0))) return p;
+    if (d.Cout <= 16 && d.Cin <= 16 && !uns) return p;                                     // (the one-tile kernels' layer)
     const size_t cmax = (size_t)(d.Cin > d.Cout ? d.Cin : d.Cout);
-    if ((size_t)d.B * cmax * d.H * d.W * 4 + (size_t)(d.W + 4) * 4 >= LEAN_MAX_BYTES) return 1;
-    const bnerv_wgrad_desc& w = wa.d;
-    KArgs ka;
-    ka.d = d;
-    ka.tiles_x = cdiv(d.W, TW);
-    ka.tiles_y = cdiv(d.H, TH);
-    ka.ksplit = 1;
-    ka.cps = cdiv(d.Cin, 16);
-    const int nt = cdiv(d.Cout, 16), ntb = nt <= 3 ? nt : (nt == 4 ? 2 : 3), ngroups = cdiv(nt, ntb);
-    const int wg = ngn * ngm;
-    const int slots = wg <= 32 ? 32 / wg : 0;              // 8 x wg x slots = the blocks per role (<= 256: two blocks per CU in all)
-    if (slots < 1) return 1;
-    const int nr = 8 * wg * slots;
-    // both roles must fill the chip on their own: the conv has at least two items per block, the weight gradient's own plan at least twice the slots
+    if ((size_t)d.B * cmax * d.H * d.W * 4 + (size_t)(d.W + 4) * 4 >= LEAN_MAX_BYTES) return p;
+    const int nt = cdiv(d.Cout, 16);
+    p.ntb = nt <= 3 ? nt : (nt == 4 ? 2 : 3);
+    const int ngroups = cdiv(nt, p.ntb);
+    const int wg = bp.ngroups_n * bp.ngroups_m;
+    p.slots = wg <= 32 ? 32 / wg : 0;                      // 8 x wg x slots = the blocks per role (<= 256: two blocks per CU in all)
+    if (p.slots < 1) return p;
+    p.nr = 8 * wg * p.slots;
     // both roles must fill the chip on their own: about one item per resident block or more (7/8 of the blocks busy).  Round 5: the
     // threshold was two items per block, which sent C1's 12 -> 48 up-conv backward at 180x320 (230 tiles for 256 blocks per role) to the
     // low-resolution pair -- 46.6 us there against 25.3 us here (profiles/r05_timeline_c1.md); at 90x160 (60 tiles) the low-resolution
     // pair stays faster (17.0 against 20.1 us).
     constexpr int PAIR_FILL = 7;                           // eighths of the blocks that must be busy
-    if (ngroups * d.B * ka.tiles_x * ka.tiles_y * 8 < PAIR_FILL * nr || nat_slots * 8 < PAIR_FILL * slots) return 1;
-    int rc = 1;
-#define BNERV_BP(CI, CE, NT, WI, MT, G2) if (d.in_mode == CI && d.ep_mode == CE && ntb == NT && w.in_mode == WI && w_mtw == MT && gm2 == G2) \
-        rc = launch_bfw_pair<CI, CE, NT, WI, MT, G2>(st, ka, wa, slots, ngn, ngm, nr);
-    const int gm2 = w.g_s == 2 ? 1 : 0;
-    if (w.g_s > 2 || w.g_mode == BNERV_IN_TANHGRAD) return 1;
-    // an up-conv's (dW | d input) where the data gradient has ONE output tile (<= 16 channels: the 12 -> 48 up-convs of the 12-channel
-    // stages): unshuffle(2) prologue | plain input, shuffled gradient.  Measured and NOT instantiated: the 38-channel TAT / block convs
-    // of C3 (both roles three tiles wide, matrix-bound) ran 18.54 ms per step paired against 18.21 ms with their own launches.
-    BNERV_BP(BNERV_IN_UNSHUFFLE, BNERV_EP_PLAIN, 1, BNERV_IN_PLAIN, 3, 1)
-    BNERV_BP(BNERV_IN_UNSHUFFLE, BNERV_EP_PLAIN, 1, BNERV_IN_PLAIN, 2, 1)
-#undef BNERV_BP
-    if (rc == BNERV_OK) *n_slabs = 8 * slots;
-    return rc == BF_NOT_HANDLED ? 1 : rc;
+    if (ngroups * d.B * cdiv(d.W, TW) * cdiv(d.H, TH) * 8 < PAIR_FILL * p.nr || bp.slots * 8 < PAIR_FILL * p.slots) return p;
+    if (w.g_s > 2 || w.g_mode == BNERV_IN_TANHGRAD) return p;
+    p.take = bf_pair_modes(d, w, p.ntb, bp.mtw, [](auto...) { return 0; }) == 0;
+    return p;
+}
+
+// BNERV_DECLINED: no scratch for the weight fragments.  On BNERV_OK the weight gradient wrote 8 * p.slots slabs.
+int bnerv_convbf_pair_launch(hipStream_t st, const bnerv_conv_desc& d, const bnerv_wb::WArgs& wa, const bnerv_wb::BwPlan& bp, const bnerv_bfpair_plan& p) {
+    KArgs ka = bf_kargs(d, {1, 0});
+    return bf_pair_modes(d, wa.d, p.ntb, bp.mtw, [&](auto ci, auto ce, auto nt, auto wi, auto mt, auto g2) {
+        return launch_bfw_pair<decltype(ci)::value, decltype(ce)::value, decltype(nt)::value, decltype(wi)::value, decltype(mt)::value, decltype(g2)::value>(
+            st, ka, wa, p.slots, bp.ngroups_n, bp.ngroups_m, p.nr);
+    });
 }

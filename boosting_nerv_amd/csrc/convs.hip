@@ -16,11 +16,12 @@
 // Scope: k = 3, Cin <= 32 (64 for the unshuffle(2) prologue: the data gradient of a PixelShuffle(2) up-conv), any Cout (16 per block),
 // H * W <= 16384 (65536 for the up-convs and their data gradients), float4-aligned rows.
 #include "convs_body.h"
-#include "launch.h"
+#include "route.h"
 
 namespace {
 using namespace bnerv_conv;
 using namespace bnerv_convs;
+static_assert(STH == BNERV_CONVS_TH && STW == BNERV_CONVS_TW, "route.h names this family's tile");
 
 // NQ = ceil(Cin / 4) rounded to 4 or 8 (16 or 32 staged channels; 16 = 64 channels for the unshuffle prologue)
 template <int IN, int EP, int NQ>
@@ -43,15 +44,12 @@ int launch_small96(hipStream_t st, const SArgs& sa) {
     return BNERV_OK;
 }
 // (instantiated for the TAT convs and their data gradients only: HNeRV-boost's decoder[0], 95 -> 95 at 9 x 16, model_hnerv.py:200-202)
-template <int IN, int EP>
-constexpr bool small96_combo() {
-    return (IN == BNERV_IN_AFFINE && (EP == BNERV_EP_BIAS_GELU || EP == BNERV_EP_BIAS_RES)) ||
-           (IN == BNERV_IN_PLAIN && (EP == BNERV_EP_DGELU_SAVED || EP == BNERV_EP_DSIN));
+constexpr bool small96_combo(int in, int ep) {
+    return (in == BNERV_IN_AFFINE && (ep == BNERV_EP_BIAS_GELU || ep == BNERV_EP_BIAS_RES)) ||
+           (in == BNERV_IN_PLAIN && (ep == BNERV_EP_DGELU_SAVED || ep == BNERV_EP_DSIN));
 }
 static bool small96_shape(const bnerv_conv_desc& d) {
-    if (d.in_mode == BNERV_IN_UNSHUFFLE || d.Cin <= 32 || d.Cin > 96 || d.out_s != 1 || d.in_s != 1 || (size_t)d.H * d.W > 1024) return false;
-    const int i = d.in_mode, e = d.ep_mode;
-    return (i == BNERV_IN_AFFINE && (e == BNERV_EP_BIAS_GELU || e == BNERV_EP_BIAS_RES)) || (i == BNERV_IN_PLAIN && (e == BNERV_EP_DGELU_SAVED || e == BNERV_EP_DSIN));
+    return d.Cin > 32 && d.Cin <= 96 && d.out_s == 1 && d.in_s == 1 && (size_t)d.H * d.W <= 1024 && small96_combo(d.in_mode, d.ep_mode);
 }
 
 template <int IN, int EP, int NQ>
@@ -66,17 +64,43 @@ int launch_small(hipStream_t st, const SArgs& sa) {
 
 template <int IN, int EP>
 int launch_small_nq(hipStream_t st, const SArgs& sa) {
-    if constexpr (IN == BNERV_IN_UNSHUFFLE) return sa.d.Cin <= 32 ? launch_small<IN, EP, 8>(st, sa) : launch_small<IN, EP, 16>(st, sa);
+    const int nq = bnerv_convs_nq(sa.d);
+    if constexpr (IN == BNERV_IN_UNSHUFFLE) return nq == 8 ? launch_small<IN, EP, 8>(st, sa) : launch_small<IN, EP, 16>(st, sa);
     else {
-        if constexpr (small96_combo<IN, EP>()) { if (sa.d.Cin > 32) return launch_small96<IN, EP>(st, sa); }
-        return sa.d.Cin <= 16 ? launch_small<IN, EP, 4>(st, sa) : launch_small<IN, EP, 8>(st, sa);
+        if constexpr (small96_combo(IN, EP)) { if (nq == 24) return launch_small96<IN, EP>(st, sa); }
+        return nq == 4 ? launch_small<IN, EP, 4>(st, sa) : launch_small<IN, EP, 8>(st, sa);
     }
+}
+
+// The (in, ep) pairs of this family, ONCE: predicate (f launches nothing) and instantiation list.  -1: not in the table.
+template <class F>
+int small_modes(const bnerv_conv_desc& d, F&& f) {
+    const int in = d.in_mode, ep = d.ep_mode;
+#define BNERV_CASE(I, E) if (in == I && ep == E) return f(mode_c<I>{}, mode_c<E>{});
+    BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_BIAS)
+    BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_BIAS_SIN)
+    if (d.out_s != 1) return -1;                           // (PixelShuffle scatter stores: the up-conv forwards above only)
+    BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_PLAIN)
+    BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_DGELU_SAVED)
+    BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_DSIN)
+    BNERV_CASE(BNERV_IN_AFFINE, BNERV_EP_BIAS)
+    BNERV_CASE(BNERV_IN_AFFINE, BNERV_EP_BIAS_GELU)
+    BNERV_CASE(BNERV_IN_AFFINE, BNERV_EP_BIAS_RES)
+    BNERV_CASE(BNERV_IN_UNSHUFFLE, BNERV_EP_PLAIN)
+#undef BNERV_CASE
+    return -1;
 }
 
 }  // namespace
 
-// shapes of this family: small images whose 8x32 tiling leaves the chip idle (the threshold keeps 180x320 and above on the persistent kernels)
-bool bnerv_convs_shape_ok(const bnerv_conv_desc& d, int vec) {
+// staged channel quads of a layer of this family: 16 or 32 channels (32 or 64 for the unshuffle prologue), 96 for conv_small96_kernel
+int bnerv_convs_nq(const bnerv_conv_desc& d) {
+    if (d.in_mode == BNERV_IN_UNSHUFFLE) return d.Cin <= 32 ? 8 : 16;
+    return d.Cin > 32 ? 24 : (d.Cin <= 16 ? 4 : 8);
+}
+
+// shapes and modes of this family: small images whose 8x32 tiling leaves the chip idle (the threshold keeps 180x320 and above on the persistent kernels)
+bool bnerv_convs_ok(const bnerv_conv_desc& d, int vec) {
     if (switch_off("BNERV_SMALL")) return false;           // read per call (tests reach the other families with it)
     // small images; an up-conv (several cout groups per tile) pays up to 180x320, where the persistent split kernel still runs one tile per block
     const bool uns = d.in_mode == BNERV_IN_UNSHUFFLE;          // the data gradient of a PixelShuffle(2) up-conv: its input is the shuffled gradient
@@ -86,35 +110,22 @@ bool bnerv_convs_shape_ok(const bnerv_conv_desc& d, int vec) {
     //  95 -> 95 TAT convs at 9 x 16 on the generic kernel's 12 blocks: 47-53 us per launch for 0.2 GFLOP)
     const int cin_max = uns ? 64 : (small96_shape(d) ? 96 : 32);
     if (!(vec && d.k == 3 && d.Cin <= cin_max && (size_t)d.H * d.W <= max_px && d.B <= 65535 && cdiv(d.Cout, 16) <= 65535)) return false;
-    if (uns) return d.in_s == 2 && (d.Cin & 3) == 0 && d.ep_mode == BNERV_EP_PLAIN && d.out_s == 1 && (size_t)d.B * d.Cin * d.H * d.W * 4 < LEAN_MAX_BYTES;
-    if (d.in_s != 1) return false;
-    if (d.Cin <= 12 && d.Cout <= 12) return false;                 // the 12-channel layers have their own family (conv4.hip)
-    if (!(d.in_mode == BNERV_IN_PLAIN || d.in_mode == BNERV_IN_AFFINE)) return false;
-    const int e = d.ep_mode;
-    if (d.out_s != 1) return d.in_mode == BNERV_IN_PLAIN && (e == BNERV_EP_BIAS || e == BNERV_EP_BIAS_SIN) && (d.out_s == 2 || d.out_s == 3 || d.out_s == 5);
-    if (d.in_mode == BNERV_IN_AFFINE) return e == BNERV_EP_BIAS || e == BNERV_EP_BIAS_GELU || e == BNERV_EP_BIAS_RES;
-    return e == BNERV_EP_BIAS || e == BNERV_EP_BIAS_SIN || e == BNERV_EP_PLAIN || e == BNERV_EP_DGELU_SAVED || e == BNERV_EP_DSIN;
+    if (uns ? !(d.in_s == 2 && (d.Cin & 3) == 0 && (size_t)d.B * d.Cin * d.H * d.W * 4 < LEAN_MAX_BYTES) : d.in_s != 1) return false;
+    if (!uns && d.Cin <= 12 && d.Cout <= 12) return false;         // the 12-channel layers have their own family (conv4.hip)
+    if (!(d.out_s == 1 || d.out_s == 2 || d.out_s == 3 || d.out_s == 5)) return false;
+    return small_modes(d, [](auto, auto) { return 0; }) == 0;
 }
-int bnerv_convs_tiles(int H, int W) { return cdiv(H, STH) * cdiv(W, STW); }
 
-// 1: not this family's layer; BNERV_OK / negative BNERV_E_*: handled
-int bnerv_convs_try(hipStream_t st, const bnerv_conv_desc& d, int vec, int ksplit) {
-    if (ksplit > 1 || !bnerv_convs_shape_ok(d, vec)) return 1;
-    SArgs sa;
+bnerv_convs::SArgs bnerv_convs_sargs(const bnerv_conv_desc& d) {
+    SArgs sa{};
     sa.d = d;
     sa.tiles_x = cdiv(d.W, STW);
     sa.tiles_y = cdiv(d.H, STH);
-    const int in = d.in_mode, ep = d.ep_mode;
-#define BNERV_CASE(I, E) if (in == I && ep == E) return launch_small_nq<I, E>(st, sa);
-    BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_BIAS)
-    BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_BIAS_SIN)
-    BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_PLAIN)
-    BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_DGELU_SAVED)
-    BNERV_CASE(BNERV_IN_PLAIN, BNERV_EP_DSIN)
-    BNERV_CASE(BNERV_IN_AFFINE, BNERV_EP_BIAS)
-    BNERV_CASE(BNERV_IN_AFFINE, BNERV_EP_BIAS_GELU)
-    BNERV_CASE(BNERV_IN_AFFINE, BNERV_EP_BIAS_RES)
-    BNERV_CASE(BNERV_IN_UNSHUFFLE, BNERV_EP_PLAIN)
-#undef BNERV_CASE
-    return 1;
+    return sa;
+}
+
+// called after bnerv_convs_ok said yes
+int bnerv_convs_launch(hipStream_t st, const bnerv_conv_desc& d) {
+    const SArgs sa = bnerv_convs_sargs(d);
+    return small_modes(d, [&](auto in, auto ep) { return launch_small_nq<decltype(in)::value, decltype(ep)::value>(st, sa); });
 }

@@ -12,8 +12,7 @@
 //                  passes the raw gradient + the image) in LDS, a lane's 3 x 3 x 6 window in registers once, then per input channel 27
 //                  weights (the same table) x 4 pixels and one 16-byte store.
 // Both are exact fp32 (fma chains in a fixed order).  The weight gradient of the same layer runs with swapped roles (ops._HeadTanh.backward).
-#include "conv_common.h"
-#include "launch.h"
+#include "route.h"
 
 namespace {
 using namespace bnerv_conv;
@@ -195,28 +194,31 @@ static bool h3_common(const bnerv_conv_desc& d) {
     if (d.k != 3 || d.out_s != 1 || d.in_s > 1 || (d.W & 3) || d.B > 65535) return false;
     return aligned16(d.x, d.out, d.aux0) && (size_t)d.H * d.W >= 4096 && d.Cin <= H3_MAXC && d.Cout <= H3_MAXC;
 }
+static bool h3_fwd(const bnerv_conv_desc& d) {
+    return !d.transposed && d.in_mode == BNERV_IN_PLAIN && d.ep_mode == BNERV_EP_BIAS_TANH && d.Cout == 3 && d.Cin >= 16 && d.wCo == 3 && d.wCi == d.Cin;
+}
+static bool h3_dgrad(const bnerv_conv_desc& d) {       // (no split-K workspace: d.partial NULL)
+    return d.transposed && d.ep_mode == BNERV_EP_PLAIN && d.partial == nullptr && d.Cin == 3 && d.Cout >= 16 && d.wCo == 3 && d.wCi == d.Cout &&
+           (d.in_mode == BNERV_IN_PLAIN || (d.in_mode == BNERV_IN_TANHGRAD && d.aux0));
+}
 
 }  // namespace
 
-// 1: not this kernel's layer; BNERV_OK: launched
-int bnerv_head3_try(hipStream_t st, const bnerv_conv_desc& d) {
-    if (!h3_common(d)) return 1;
+bool bnerv_head3_ok(const bnerv_conv_desc& d) { return h3_common(d) && (h3_fwd(d) || h3_dgrad(d)); }
+
+int bnerv_head3_launch(hipStream_t st, const bnerv_conv_desc& d) {
     H3Args a{};
     a.x = d.x; a.w = d.w; a.out = d.out; a.B = d.B; a.H = d.H; a.W = d.W;
     a.tiles_x = cdiv(d.W, HT_W);
     const dim3 grid(a.tiles_x * cdiv(d.H, HT_H), d.B);
-    if (!d.transposed && d.in_mode == BNERV_IN_PLAIN && d.ep_mode == BNERV_EP_BIAS_TANH && d.Cout == 3 && d.Cin >= 16 && d.wCo == 3 && d.wCi == d.Cin) {
+    if (h3_fwd(d)) {
         a.Cin = d.Cin; a.Cout = 3; a.bias = d.bias;
         hipLaunchKernelGGL(head3x3_fwd_kernel<3>, grid, dim3(256), 0, st, a);
         BNERV_LAUNCH_CHECK("head3x3_fwd");
         return BNERV_OK;
     }
-    if (d.transposed && d.ep_mode == BNERV_EP_PLAIN && d.partial == nullptr && d.Cin == 3 && d.Cout >= 16 && d.wCo == 3 && d.wCi == d.Cout &&
-        (d.in_mode == BNERV_IN_PLAIN || (d.in_mode == BNERV_IN_TANHGRAD && d.aux0))) {
-        a.Cin = d.Cout; a.Cout = 3; a.img = d.in_mode == BNERV_IN_TANHGRAD ? d.aux0 : nullptr;
-        hipLaunchKernelGGL(head3x3_dgrad_kernel<3>, grid, dim3(256), 0, st, a);
-        BNERV_LAUNCH_CHECK("head3x3_dgrad");
-        return BNERV_OK;
-    }
-    return 1;
+    a.Cin = d.Cout; a.Cout = 3; a.img = d.in_mode == BNERV_IN_TANHGRAD ? d.aux0 : nullptr;
+    hipLaunchKernelGGL(head3x3_dgrad_kernel<3>, grid, dim3(256), 0, st, a);
+    BNERV_LAUNCH_CHECK("head3x3_dgrad");
+    return BNERV_OK;
 }

@@ -14,7 +14,7 @@
 // Both read the gradient through the pixel-unshuffle gather (g stored shuffled by s in {1, 2, 3, 5}) with 4-byte loads -- the image
 // is tiny, the loads are few.  v_mfma_f32_16x16x4_f32, exact f32 products like every f32 kernel of this build.
 #include "common.h"
-#include "launch.h"
+#include "route.h"
 
 namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -246,13 +246,15 @@ size_t dgrad_tiny_lds_bytes(int Cout, int H, int W) {
 
 }  // namespace
 
-// ---- weight gradient.  1: not this kernel's layer; BNERV_OK: dw / db written (nothing deferred, no workspace used)
-int bnerv_stem_wgrad_try(hipStream_t st, const bnerv_wgrad_desc& d) {
-    if (d.k != 3 || d.in_mode != BNERV_IN_PLAIN || d.g_mode == BNERV_IN_TANHGRAD) return 1;
-    if ((size_t)d.H * d.W > TINY_MAX_PX || !tiny_s_ok(d.g_s, d.Cout)) return 1;
+// ---- weight gradient: dw / db written directly (nothing deferred, no workspace used)
+bool bnerv_stem_wgrad_ok(const bnerv_wgrad_desc& d) {
+    if (d.k != 3 || d.in_mode != BNERV_IN_PLAIN || d.g_mode == BNERV_IN_TANHGRAD) return false;
+    if ((size_t)d.H * d.W > TINY_MAX_PX || !tiny_s_ok(d.g_s, d.Cout)) return false;
     const int PL = (d.H + 2) * (d.W + 2);
-    if ((size_t)d.Cin * PL > WT_MAX_XFLOATS || d.Cout < 64) return 1;          // (few output channels: the tiled kernels' split over pixels is as good)
-    if ((size_t)d.B * (d.Cin > d.Cout ? d.Cin : d.Cout) * d.H * d.W >= (size_t)1 << 30) return 1;
+    if ((size_t)d.Cin * PL > WT_MAX_XFLOATS || d.Cout < 64) return false;      // (few output channels: the tiled kernels' split over pixels is as good)
+    return (size_t)d.B * (d.Cin > d.Cout ? d.Cin : d.Cout) * d.H * d.W < (size_t)1 << 30;
+}
+int bnerv_stem_wgrad_launch(hipStream_t st, const bnerv_wgrad_desc& d) {
     const size_t lds = wgrad_tiny_lds_bytes(d.Cin, d.H, d.W);
     if (const int rc = dyn_lds<&wgrad_tiny_kernel>(lds, "wgrad_tiny")) return rc;
     WTArgs a{d.x, d.g, d.dw, d.db, d.B, d.Cin, d.Cout, d.H, d.W, d.g_s};
@@ -272,43 +274,40 @@ static bool stem_dgrad_shape(const bnerv_conv_desc& d) {
     if (!(d.wCo == d.Cin && d.wCi == d.Cout)) return false;
     return (size_t)d.B * d.Cin * d.H * d.W < (size_t)1 << 30;
 }
+bool bnerv_stem_dgrad_ok(const bnerv_conv_desc& d) { return d.partial && stem_dgrad_shape(d); }
+int bnerv_stem_dgrad_slabs(const bnerv_conv_desc& d) { return cdiv(d.Cin, DT_CS); }
 size_t bnerv_stem_dgrad_ws_bytes(const bnerv_conv_desc& d) {
     if (!stem_dgrad_shape(d)) return 0;
-    return (size_t)cdiv(d.Cin, DT_CS) * d.B * d.Cout * d.H * d.W * sizeof(float);
+    return (size_t)bnerv_stem_dgrad_slabs(d) * d.B * d.Cout * d.H * d.W * sizeof(float);
 }
-int bnerv_stem_dgrad_try(hipStream_t st, const bnerv_conv_desc& d) {
-    if (!stem_dgrad_shape(d) || !d.partial) return 1;
+int bnerv_stem_dgrad_launch(hipStream_t st, const bnerv_conv_desc& d) {
     const size_t lds = dgrad_tiny_lds_bytes(d.Cout, d.H, d.W);
     DTArgs a{d.x, d.w, d.partial, d.B, d.Cin, d.Cout, d.H, d.W, d.in_mode == BNERV_IN_UNSHUFFLE ? d.in_s : 1};
-    const int nblk = cdiv(d.Cin, DT_CS);
+    const int nblk = bnerv_stem_dgrad_slabs(d);
     if (d.Cout <= 32) hipLaunchKernelGGL(dgrad_tiny_kernel<2>, dim3(nblk), dim3(256), lds, st, a);
     else hipLaunchKernelGGL(dgrad_tiny_kernel<6>, dim3(nblk), dim3(256), lds, st, a);
     BNERV_LAUNCH_CHECK("dgrad_tiny");
     return bnerv_reduce_slabs(st, d.partial, nblk, d.B * d.Cout * d.H * d.W, d.out);
 }
 
-// ---- both at once (bnerv_conv_wgrad_pair, form 0).  1: not this pair; BNERV_OK: dw / db written, dx's slabs in c.partial and *n_slabs > 0
-// slabs of c.B * c.Cout * c.H * c.W floats for the caller to reduce into c.out (deferred or at once).
-int bnerv_stem_pair_try(hipStream_t st, const bnerv_conv_desc& c, const bnerv_wgrad_desc& d, int* n_slabs) {
-    if (!stem_dgrad_shape(c) || !c.partial) return 1;
-    if (d.k != 3 || d.in_mode != BNERV_IN_PLAIN || d.g_mode == BNERV_IN_TANHGRAD) return 1;
-    if ((size_t)d.H * d.W > TINY_MAX_PX || !tiny_s_ok(d.g_s, d.Cout)) return 1;
-    const int PL = (d.H + 2) * (d.W + 2);
-    if ((size_t)d.Cin * PL > WT_MAX_XFLOATS || d.Cout < 64) return 1;
-    if ((size_t)d.B * (d.Cin > d.Cout ? d.Cin : d.Cout) * d.H * d.W >= (size_t)1 << 30) return 1;
+// ---- both at once (bnerv_conv_wgrad_pair, form 0): dw / db written, dx's bnerv_stem_dgrad_slabs(c) slabs of c.B * c.Cout * c.H * c.W floats
+// in c.partial for the caller to reduce into c.out (deferred or at once).
+bool bnerv_stem_pair_ok(const bnerv_conv_desc& c, const bnerv_wgrad_desc& d) {
+    if (!bnerv_stem_dgrad_ok(c) || !bnerv_stem_wgrad_ok(d)) return false;
     const int cs = c.in_mode == BNERV_IN_UNSHUFFLE ? c.in_s : 1;
-    if (!(c.x == d.g && c.Cin == d.Cout && c.Cout == d.Cin && c.B == d.B && c.H == d.H && c.W == d.W && cs == d.g_s)) return 1;   // one layer, one gradient
+    return c.x == d.g && c.Cin == d.Cout && c.Cout == d.Cin && c.B == d.B && c.H == d.H && c.W == d.W && cs == d.g_s;     // one layer, one gradient
+}
+int bnerv_stem_pair_launch(hipStream_t st, const bnerv_conv_desc& c, const bnerv_wgrad_desc& d) {
+    const int cs = c.in_mode == BNERV_IN_UNSHUFFLE ? c.in_s : 1;
     const size_t lds_w = wgrad_tiny_lds_bytes(d.Cin, d.H, d.W), lds_d = dgrad_tiny_lds_bytes(c.Cout, c.H, c.W);
     const size_t lds = lds_w > lds_d ? lds_w : lds_d;
     const bool small = c.Cout <= 32;
     if (const int rc = small ? dyn_lds<&stem_pair_kernel<2>>(lds, "stem_pair") : dyn_lds<&stem_pair_kernel<6>>(lds, "stem_pair")) return rc;
     WTArgs wa{d.x, d.g, d.dw, d.db, d.B, d.Cin, d.Cout, d.H, d.W, d.g_s};
     DTArgs da{c.x, c.w, c.partial, c.B, c.Cin, c.Cout, c.H, c.W, cs};
-    const int wx = cdiv(d.Cout, 16), wy = cdiv(cdiv(d.Cin * 9, 16), WT_NTG), n_w = wx * wy, n_d = cdiv(c.Cin, DT_CS);
+    const int wx = cdiv(d.Cout, 16), wy = cdiv(cdiv(d.Cin * 9, 16), WT_NTG), n_w = wx * wy, n_d = bnerv_stem_dgrad_slabs(c);
     if (small) hipLaunchKernelGGL(stem_pair_kernel<2>, dim3(n_w + n_d), dim3(256), lds, st, wa, da, wx, n_w);
     else hipLaunchKernelGGL(stem_pair_kernel<6>, dim3(n_w + n_d), dim3(256), lds, st, wa, da, wx, n_w);
     BNERV_LAUNCH_CHECK("stem_pair");
-    *n_slabs = n_d;
     return BNERV_OK;
 }
-

@@ -27,14 +27,13 @@ static __device__ unsigned long long g_trace_w[1024 * 4 * 8 * 8];
 #define BTRACE(it_, slot) do { if (lane == 0 && blockIdx.x < 1024 && (unsigned)(it_) < 8u) g_trace_w[((blockIdx.x * 4 + wave) * 8 + (it_)) * 8 + (slot)] = __builtin_amdgcn_s_memtime(); } while (0)
 #endif
 #include "wgrad_bfw_body.h" // WArgs, the buffer-load helpers and the split wide weight-gradient body (also one role of convbf.hip's paired launch)
-int bnerv_convbf_pair_try(hipStream_t st, const bnerv_conv_desc& d, int vec, const bnerv_wb::WArgs& wa, int w_mtw, int ngn, int ngm, int nat_slots, int* n_slabs);   // convbf.hip
-bool bnerv_convs_shape_ok(const bnerv_conv_desc& d, int vec);     // convs.hip
-int bnerv_stem_wgrad_try(hipStream_t st, const bnerv_wgrad_desc& d);   // stem.hip (images of <= 256 pixels): 1 = not that layer
-int bnerv_stem_pair_try(hipStream_t st, const bnerv_conv_desc& c, const bnerv_wgrad_desc& d, int* n_slabs);   // stem.hip: the stem stage's (dW | d input) as one launch
+#include "route.h"           // the conv half of a pair: its families' predicates, the wide pair's plan
+bool bnerv_stem_wgrad_ok(const bnerv_wgrad_desc& d);                                   // stem.hip (images of <= 256 pixels): dw / db written directly
+int bnerv_stem_wgrad_launch(hipStream_t st, const bnerv_wgrad_desc& d);
+bool bnerv_stem_pair_ok(const bnerv_conv_desc& c, const bnerv_wgrad_desc& d);          // stem.hip: the stem stage's (dW | d input) as one launch
+int bnerv_stem_pair_launch(hipStream_t st, const bnerv_conv_desc& c, const bnerv_wgrad_desc& d);
 int bnerv_wgrad1x1_slabs(const bnerv_wgrad_desc& d);                                   // wgrad1.hip: pointwise (k = 1) layers as a plain GEMM over the pixels
-int bnerv_wgrad1x1_try(hipStream_t st, const bnerv_wgrad_desc& d, int* n_slabs);
-#include "launch.h"
-#include <type_traits>
+int bnerv_wgrad1x1_launch(hipStream_t st, const bnerv_wgrad_desc& d);
 
 namespace {
 using namespace bnerv_wb;
@@ -751,15 +750,30 @@ __global__ __launch_bounds__(256, 2) void pair_fold_kernel(const bnerv_conv::KAr
 
 constexpr size_t WLEAN_MAX_BYTES = 0x7ff00000;
 
-static bool wlean_ok(const WArgs& wa) {
-    const bnerv_wgrad_desc& d = wa.d;
-    if (!wa.vec || d.Cout > 16) return false;
+// The (x prologue, gradient form GM2) pairs the lean kernel is instantiated for, written once: f(mode_c<IN>, mode_c<GM2>) is called for the
+// descriptor's pair; -1 for any other.
+template <class F>
+int wlean_modes(const bnerv_wgrad_desc& d, F&& f) {
+    const int in = d.in_mode, gm = d.g_mode;
+    if (gm == BNERV_IN_TANHGRAD && in == BNERV_IN_PLAIN) return f(mode_c<BNERV_IN_PLAIN>{}, mode_c<2>{});
+    if (gm == BNERV_IN_PLAIN || gm == BNERV_IN_UNSHUFFLE) {
+        const bool pair = gm == BNERV_IN_UNSHUFFLE && d.g_s == 2;
+        if (in == BNERV_IN_PLAIN) return pair ? f(mode_c<BNERV_IN_PLAIN>{}, mode_c<1>{}) : f(mode_c<BNERV_IN_PLAIN>{}, mode_c<0>{});
+        if (d.k == 3 && !pair && in == BNERV_IN_AFFINE) return f(mode_c<BNERV_IN_AFFINE>{}, mode_c<0>{});
+        if (d.k == 3 && !pair && in == BNERV_IN_GELU_AFFINE) return f(mode_c<BNERV_IN_GELU_AFFINE>{}, mode_c<0>{});
+    }
+    return -1;
+}
+
+static bool wlean_ok(const bnerv_wgrad_desc& d, int vec) {
+    if (!vec || d.Cout > 16) return false;
     if (d.k == 3 && d.Cin > 12) return false;
     if (d.k == 1 && d.Cin > 15) return false;
     if (d.g_mode == BNERV_IN_UNSHUFFLE && d.g_s > 2) return false;
     if (d.g_mode == BNERV_IN_UNSHUFFLE && d.g_s == 2 && (d.Cout % 4 != 0)) return false;
     const size_t cmax = (size_t)(d.Cin > d.Cout ? d.Cin : d.Cout);
-    return (size_t)d.B * cmax * d.H * d.W * 4 + (size_t)(d.W + 4) * 4 < WLEAN_MAX_BYTES;
+    if ((size_t)d.B * cmax * d.H * d.W * 4 + (size_t)(d.W + 4) * 4 >= WLEAN_MAX_BYTES) return false;
+    return wlean_modes(d, [](auto, auto) { return 0; }) == 0;
 }
 
 static int wlean_blocks(const bnerv_wgrad_desc& d) {
@@ -792,19 +806,12 @@ int launch_wlean(hipStream_t st, const WArgs& wa) {
     return BNERV_OK;
 }
 
-template <int KS>
-int launch_wlean_modes(hipStream_t st, const WArgs& wa) {
-    const int in = wa.d.in_mode, gm = wa.d.g_mode;
-    if (gm == BNERV_IN_TANHGRAD && in == BNERV_IN_PLAIN) return launch_wlean<KS, BNERV_IN_PLAIN, 2>(st, wa);
-    if (gm == BNERV_IN_PLAIN || gm == BNERV_IN_UNSHUFFLE) {
-        const bool pair = gm == BNERV_IN_UNSHUFFLE && wa.d.g_s == 2;
-        if (in == BNERV_IN_PLAIN) return pair ? launch_wlean<KS, BNERV_IN_PLAIN, 1>(st, wa) : launch_wlean<KS, BNERV_IN_PLAIN, 0>(st, wa);
-        if constexpr (KS == 3) {
-            if (!pair && in == BNERV_IN_AFFINE) return launch_wlean<KS, BNERV_IN_AFFINE, 0>(st, wa);
-            if (!pair && in == BNERV_IN_GELU_AFFINE) return launch_wlean<KS, BNERV_IN_GELU_AFFINE, 0>(st, wa);
-        }
-    }
-    return -1;                                            // not covered: the caller falls back to the general kernel
+static int launch_wlean_modes(hipStream_t st, const WArgs& wa) {
+    return wlean_modes(wa.d, [&](auto in, auto gm2) {
+        constexpr int IN = decltype(in)::value, GM2 = decltype(gm2)::value;
+        if constexpr (IN == BNERV_IN_PLAIN) { if (wa.d.k == 1) return launch_wlean<1, IN, GM2>(st, wa); }       // (the affine prologues: k = 3 only)
+        return launch_wlean<3, IN, GM2>(st, wa);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------------- wide kernel
@@ -1150,9 +1157,8 @@ __global__ __launch_bounds__(256, (MTW * NTW <= 8 ? 3 : 2)) void wgrad_wide_kern
     wgrad_wide_body<IN, GM2, MTW, NTW>(wa, slots, side, (int)blockIdx.x, (int)gridDim.x);
 }
 
-static bool wide_ok(const WArgs& wa) {
-    const bnerv_wgrad_desc& d = wa.d;
-    if (!wa.vec || d.k != 3) return false;
+static bool wide_ok(const bnerv_wgrad_desc& d, int vec) {
+    if (!vec || d.k != 3) return false;
     if (d.g_s > 2 && (d.g_mode != BNERV_IN_UNSHUFFLE || d.in_mode != BNERV_IN_PLAIN || d.Cout % (d.g_s * d.g_s) != 0 || d.Cout <= 16)) return false;
     if (d.g_s == 2 && (d.g_mode != BNERV_IN_UNSHUFFLE || d.in_mode != BNERV_IN_PLAIN || d.Cout % 4 != 0 || d.Cout <= 16)) return false;
     if (d.in_mode != BNERV_IN_PLAIN && d.in_mode != BNERV_IN_AFFINE) return false;
@@ -1179,7 +1185,6 @@ int launch_wide_shape(hipStream_t st, const WArgs& wa, const WidePlan& p) {
         if (p.mtw == 2) return p.ntw == 9 ? launch_wide<IN, GM2, 2, 9>(st, wa, p) : launch_wide<IN, GM2, 2, 7>(st, wa, p);
         if (p.mtw == 3) return p.ntw == 7 ? launch_wide<IN, GM2, 3, 7>(st, wa, p) : launch_wide<IN, GM2, 3, 6>(st, wa, p);
         if (p.mtw == 4) return launch_wide<IN, GM2, 4, 4>(st, wa, p);
-        return -1;
     }
     if (p.mtw == 1) return launch_wide<IN, GM2, 1, 8>(st, wa, p);
     if constexpr (GM2 == 0) {
@@ -1187,7 +1192,8 @@ int launch_wide_shape(hipStream_t st, const WArgs& wa, const WidePlan& p) {
         if (p.mtw == 3) return p.ntw == 7 ? launch_wide<IN, GM2, 3, 7>(st, wa, p) : launch_wide<IN, GM2, 3, 6>(st, wa, p);
         if (p.mtw == 4) return launch_wide<IN, GM2, 4, 4>(st, wa, p);
     }
-    return -1;
+    // (not reached after wide_ok: a shuffled gradient has more than 16 output channels, a tanh-grad one at most 16)
+    return bnerv_set_error(BNERV_E_ARG, "wgrad_wide: no instantiation for (g form %d, %d x %d tiles)", GM2, p.mtw, p.ntw);
 }
 
 static int launch_wide_modes(hipStream_t st, const WArgs& wa, const WidePlan& p) {
@@ -1203,9 +1209,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_bfw_kernel(const WArgs wa, const
     wgrad_bfw_body<IN, SP, MTW, GM2>(wa, slots, ngroups_n, ngroups_m, side, (int)blockIdx.x, (int)gridDim.x);
 }
 
-static bool bw_ok(const WArgs& wa) {
-    const bnerv_wgrad_desc& d = wa.d;
-    if (split_wide_mode() < 0 || !wa.vec || d.k != 3 || (d.g_s > 3 && d.g_s != 5) || d.g_mode == BNERV_IN_TANHGRAD) return false;
+static bool bw_ok(const bnerv_wgrad_desc& d, int vec) {
+    if (split_wide_mode() < 0 || !vec || d.k != 3 || (d.g_s > 3 && d.g_s != 5) || d.g_mode == BNERV_IN_TANHGRAD) return false;
     if (d.in_mode != BNERV_IN_PLAIN && d.in_mode != BNERV_IN_AFFINE) return false;
     if (d.g_s >= 2 && d.in_mode != BNERV_IN_PLAIN) return false;
     if (d.Cout <= 16) return false;                        // (one cout tile: the f32 kernels are as fast or faster -- 64 -> 16 @540x960: 108 vs 115 us)
@@ -1330,158 +1335,201 @@ extern "C" int bnerv_debug_trace_read_w(void* host) { return (int)hipMemcpyFromS
 extern "C" int bnerv_debug_trace_read_pairf(void* host) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(bnerv_q4::g_trace4), sizeof(bnerv_q4::g_trace4)); }   // this translation unit's copy (pairf_body.h stamps)
 #endif
 #endif
+// ---------------------------------------------------------------------------------------------------------------- route
+// Kernel selection of bnerv_conv_wgrad as data: wgrad_route names the order of the families ONCE; the entry point
+// switches on it, the paired launch and the host queries read it.
+namespace {
+// slabs each tiled family writes for a layer (what its launcher's grid makes): the route and the workspace bound both use these
+int wlean_slabs(const bnerv_wgrad_desc& d) { return wlean_blocks(d); }
+int bw_slabs(const BwPlan& p) { return 8 * p.slots; }
+int wide_slabs(const WidePlan& p) { return 8 * p.slots; }
+int generic_slabs(const Plan& p) { return p.nsplit; }
+
+struct WRoute {
+    int family;             // BNERV_WGRAD_FAM_*
+    int n_slabs;            // slabs of Cout x ncols floats the family writes into d.ws (0: the stem kernel writes dw / db itself)
+    Plan gen;               // the family's plan: generic (always filled in: WArgs' column groups default to it), split bf16, wide f32
+    BwPlan bw;
+    WidePlan wide;
+};
+
+// the float4 paths need 16-byte aligned rows.  The stand-alone call counts gaux (the tanh-grad gradient form reads it); a pair has no such form
+int wgrad_vec(const bnerv_wgrad_desc& d, bool with_gaux) { return (d.W % 4 == 0 && aligned16(d.x, d.g) && (!with_gaux || aligned16(d.gaux))) ? 1 : 0; }
+
+// `first`: the family the order starts at -- a pair's weight-gradient role is one of the tiled families (BNERV_WGRAD_FAM_LEAN on).
+// Pure: reads the descriptor and the environment switches, touches no device.  Dimensions must be positive, k 1 or 3.
+WRoute wgrad_route(const bnerv_wgrad_desc& d, int vec, int first = BNERV_WGRAD_FAM_STEM) {
+    WRoute r{};
+    r.gen = make_plan(d.B, d.Cin, d.Cout, d.H, d.W, d.k);
+    auto is = [&](int family, bool ok) { if (family < first || !ok) return false; r.family = family; return true; };
+    if (is(BNERV_WGRAD_FAM_STEM, bnerv_stem_wgrad_ok(d))) return r;                       // an image of <= 256 pixels, many output channels: written directly, no slabs
+    if (is(BNERV_WGRAD_FAM_GEMM1X1, bnerv_wgrad1x1_slabs(d) > 0)) { r.n_slabs = bnerv_wgrad1x1_slabs(d); return r; }   // pointwise, >= 16 channels on both sides
+    if (is(BNERV_WGRAD_FAM_LEAN, wlean_ok(d, vec))) { r.n_slabs = wlean_slabs(d); return r; }
+    if (is(BNERV_WGRAD_FAM_WIDE_BF16, bw_ok(d, vec))) { r.bw = bw_plan(d); r.n_slabs = bw_slabs(r.bw); return r; }     // split 16-bit kernel for the multi-tile plain gradients
+    if (is(BNERV_WGRAD_FAM_WIDE_F32, wide_ok(d, vec))) { r.wide = wide_plan(d); r.n_slabs = wide_slabs(r.wide); return r; }
+    r.family = BNERV_WGRAD_FAM_GENERIC;
+    r.n_slabs = generic_slabs(r.gen);
+    return r;
+}
+
+// the kernels' arguments for a routed layer (both entry points)
+WArgs wgrad_args(const bnerv_wgrad_desc& d, const WRoute& r, int vec) {
+    WArgs wa;
+    wa.d = d;
+    wa.slab = reinterpret_cast<float*>(d.ws);
+    wa.tiles_x = cdiv(d.W, TW);
+    wa.tiles_y = cdiv(d.H, TH);
+    const bool wide = r.family == BNERV_WGRAD_FAM_WIDE_F32;
+    wa.n_mgroups = wide ? r.wide.mgroups : r.gen.n_mgroups;
+    wa.n_ngroups = wide ? r.wide.ngroups : r.gen.n_ngroups;
+    wa.ncols = d.Cin * d.k * d.k + 1;
+    wa.vec = vec;
+    return wa;
+}
+}  // namespace
+
+// Mode-free (the caller sizes the workspace before it knows the prologues): the largest slab count over the families a layer of these
+// dimensions can land on.
 extern "C" size_t bnerv_conv_wgrad_ws_bytes(int B, int Cin, int Cout, int H, int W, int k) {
     if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (k != 1 && k != 3)) return 0;
-    const Plan p = make_plan(B, Cin, Cout, H, W, k);
     bnerv_wgrad_desc t{};
-    t.B = B; t.H = H; t.W = W; t.k = k;
-    int nb = wlean_blocks(t) > p.nsplit ? wlean_blocks(t) : p.nsplit;           // covers whichever kernel the launcher picks
-    if (k == 1) {
-        bnerv_wgrad_desc t1{};
-        t1.B = B; t1.Cin = Cin; t1.Cout = Cout; t1.H = H; t1.W = W; t1.k = 1; t1.g_s = 1;
-        const int n1 = bnerv_wgrad1x1_slabs(t1);
-        if (n1 > nb) nb = n1;
-    }
-    if (k == 3) {
-        t.Cin = Cin; t.Cout = Cout;
-        const WidePlan wp = wide_plan(t);
-        if (8 * wp.slots > nb) nb = 8 * wp.slots;
-        const BwPlan bp = bw_plan(t);
-        if (8 * bp.slots > nb) nb = 8 * bp.slots;
-    }
+    t.B = B; t.Cin = Cin; t.Cout = Cout; t.H = H; t.W = W; t.k = k; t.g_s = 1;
+    int nb = wlean_slabs(t);
+    auto cover = [&](int n) { if (n > nb) nb = n; };
+    cover(generic_slabs(make_plan(B, Cin, Cout, H, W, k)));
+    if (k == 1) cover(bnerv_wgrad1x1_slabs(t));
+    if (k == 3) { cover(wide_slabs(wide_plan(t))); cover(bw_slabs(bw_plan(t))); }
     return (size_t)nb * Cout * (Cin * k * k + 1) * sizeof(float);
+}
+
+extern "C" int bnerv_conv_wgrad_family(const bnerv_wgrad_desc* dp, int* n_slabs) {
+    const bool ok = dp && dp->B > 0 && dp->Cin > 0 && dp->Cout > 0 && dp->H > 0 && dp->W > 0 && (dp->k == 1 || dp->k == 3) && dp->g_s >= 1;
+    const WRoute r = ok ? wgrad_route(*dp, wgrad_vec(*dp, true)) : WRoute{};
+    if (n_slabs) *n_slabs = r.n_slabs;
+    return ok ? r.family : -1;
 }
 
 extern "C" int bnerv_conv_wgrad(void* stream, const bnerv_wgrad_desc* dp) {
     BNERV_REQUIRE(dp != nullptr, "conv_wgrad: null descriptor");
-    WArgs wa;
-    wa.d = *dp;
-    const bnerv_wgrad_desc& d = wa.d;
+    const bnerv_wgrad_desc& d = *dp;
     BNERV_REQUIRE(d.k == 1 || d.k == 3, "conv_wgrad: k must be 1 or 3 (got %d)", d.k);
     BNERV_REQUIRE(d.B > 0 && d.Cin > 0 && d.Cout > 0 && d.H > 0 && d.W > 0, "conv_wgrad: bad dims");
     BNERV_REQUIRE(d.x && d.g && d.dw && d.ws, "conv_wgrad: null tensor");
     BNERV_REQUIRE(d.g_s >= 1 && d.Cout % (d.g_s * d.g_s) == 0, "conv_wgrad: bad g_s");
     if (d.in_mode == BNERV_IN_AFFINE || d.in_mode == BNERV_IN_GELU_AFFINE) BNERV_REQUIRE(d.scale && d.shift, "conv_wgrad: affine prologue needs scale/shift");
     if (d.g_mode == BNERV_IN_TANHGRAD) BNERV_REQUIRE(d.gaux && d.g_s == 1, "conv_wgrad: tanh-grad needs gaux");
-    const Plan p = make_plan(d.B, d.Cin, d.Cout, d.H, d.W, d.k);
     const size_t need = bnerv_conv_wgrad_ws_bytes(d.B, d.Cin, d.Cout, d.H, d.W, d.k);
     if (d.ws_bytes < need) return bnerv_set_error(BNERV_E_WS, "conv_wgrad: workspace %zu < %zu", d.ws_bytes, need);
-    wa.slab = reinterpret_cast<float*>(d.ws);
-    wa.tiles_x = cdiv(d.W, TW);
-    wa.tiles_y = cdiv(d.H, TH);
-    wa.n_mgroups = p.n_mgroups;
-    wa.n_ngroups = p.n_ngroups;
-    wa.ncols = d.Cin * d.k * d.k + 1;
-    wa.vec = ((d.W % 4 == 0) && aligned16(d.x, d.g, d.gaux)) ? 1 : 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    {   // the stem stage (an image of <= 256 pixels, many output channels): written directly, no slabs
-        const int rs = bnerv_stem_wgrad_try(st, d);
-        if (rs != 1) return rs;
+    const int vec = wgrad_vec(d, true);
+    const WRoute r = wgrad_route(d, vec);
+    const WArgs wa = wgrad_args(d, r, vec);
+    int rc;
+    switch (r.family) {
+    case BNERV_WGRAD_FAM_STEM: return bnerv_stem_wgrad_launch(st, d);                     // (nothing to finish)
+    case BNERV_WGRAD_FAM_GEMM1X1: rc = bnerv_wgrad1x1_launch(st, d); break;
+    case BNERV_WGRAD_FAM_LEAN: rc = launch_wlean_modes(st, wa); break;
+    case BNERV_WGRAD_FAM_WIDE_BF16: rc = launch_bw_modes(st, wa, r.bw); break;
+    case BNERV_WGRAD_FAM_WIDE_F32: rc = launch_wide_modes(st, wa, r.wide); break;
+    default: rc = d.k == 1 ? launch_modes<1>(st, wa, r.gen) : launch_modes<3>(st, wa, r.gen); break;
     }
-    int rc = -1, n_slabs = p.nsplit;
-    if (d.k == 1) {                                       // pointwise layers with 16 or more channels on both sides: the plain GEMM over pixels (wgrad1.hip)
-        int n1 = 0;
-        const int r1 = bnerv_wgrad1x1_try(st, d, &n1);
-        if (r1 < 0) return r1;
-        if (r1 == BNERV_OK) { rc = BNERV_OK; n_slabs = n1; }
-    }
-    if (rc == -1 && wlean_ok(wa)) {
-        rc = d.k == 1 ? launch_wlean_modes<1>(st, wa) : launch_wlean_modes<3>(st, wa);
-        if (rc == BNERV_OK) n_slabs = wlean_blocks(d);
-    }
-    if (rc == -1 && bw_ok(wa)) {                          // split 16-bit kernel for the multi-tile plain gradients
-        const BwPlan bp = bw_plan(d);
-        rc = launch_bw_modes(st, wa, bp);
-        if (rc == BNERV_OK) n_slabs = 8 * bp.slots;
-    }
-    if (rc == -1 && wide_ok(wa)) {
-        const WidePlan wp = wide_plan(d);
-        if (wp.mtw) {
-            wa.n_ngroups = wp.ngroups;
-            wa.n_mgroups = wp.mgroups;
-            rc = launch_wide_modes(st, wa, wp);
-            if (rc == BNERV_OK) n_slabs = 8 * wp.slots;
-            else { wa.n_ngroups = p.n_ngroups; wa.n_mgroups = p.n_mgroups; }
-        }
-    }
-    if (rc == -1) rc = d.k == 1 ? launch_modes<1>(st, wa, p) : launch_modes<3>(st, wa, p);
     if (rc != BNERV_OK) return rc;
     const int count = d.Cout * wa.ncols;
     if (d.defer_finish && d.ctx) {                                  // (queued AFTER the launch: this launch may host older jobs, never its own)
-        bnerv_side_push(d.ctx, st, wa.slab, n_slabs, count, wa.ncols, d.dw, d.db);
+        bnerv_side_push(d.ctx, st, wa.slab, r.n_slabs, count, wa.ncols, d.dw, d.db);
         return BNERV_OK;
     }
-    hipLaunchKernelGGL(wgrad_finish_kernel, dim3(cdiv(count, 32)), dim3(1024), 0, st, wa.slab, n_slabs, d.Cout, wa.ncols, d.dw, d.db);
+    hipLaunchKernelGGL(wgrad_finish_kernel, dim3(cdiv(count, 32)), dim3(1024), 0, st, wa.slab, r.n_slabs, d.Cout, wa.ncols, d.dw, d.db);
     BNERV_LAUNCH_CHECK("wgrad_finish");
     return BNERV_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------------------ paired launch
 namespace {
+// Form 1's three shapes of grid.  Shared-tile form (pairf_body.h): one block runs both roles on its tile from ONE staged copy of the gradient.
+// Default: the pairs with a reducing epilogue (TAT convs: DGELU_SAVED / DSIN) from 1024 tiles on (two tiles per block at 512 blocks).  Measured
+// on MI355X, C1 (profiles/r05_pair_fused.md): 720p DSIN pair 81.0 against 83.5 us, DGELU_SAVED 76.5 against 74.5, PLAIN 68.5 against 66.7 (kept on
+// the interleaved pair); at 360x640 (900 tiles) the interleaved pair's three blocks per CU win (27 against 29 us).  HBM traffic of the DSIN
+// pair: see the same file.  BNERV_PAIR_FUSED=<tiles>: every pair from that many tiles on; 0: off.
+// Fold form (pairf_body.h pair_fold_body): the input tile staged raw by LDS-DMA, the affine applied by the slab reduction.  One sample per
+// launch (the fold is per sample), the reducing epilogue's raw-input operand must BE the weight gradient's input, and the workspace must
+// hold `grid` slabs of Cout x (ncols + 8).  BNERV_PAIR_FOLD=0: the transforming shared-tile form.
+// Interleaved form: PAIR_MIX blocks per role; PAIR_PAT: the role of XCD-local slot s is (s + (s >> PAT)) & 1.  Measured on C1 (1.745 ms with
+// the roles one after the other): 384 blocks per role 1.680 (PAT 0), 1.642 (PAT 5: the parity flips every 32 slots = the CUs of an XCD, so
+// every CU holds both roles), 1.664 (6), 1.68 (3, 4, 7); 376 / 368 per role as 384, 512 per role (not all resident) 1.783.
+enum { Q4P_INTERLEAVED, Q4P_SHARED, Q4P_FOLD };
+struct Q4PairPlan { int kind, grid, n_conv, n_w; };     // n_w: the weight gradient's slabs
+constexpr int PAIR_MIX = 384, PAIR_PAT = 5;
+
+Q4PairPlan q4_pair_plan(const bnerv_conv_desc& c, const bnerv_wgrad_desc& w) {
+    Q4PairPlan p{};
+    const int total_items = c.B * cdiv(c.W, bnerv_conv::TW) * cdiv(c.H, bnerv_conv::TH), ncols = w.Cin * 9 + 1;
+    const int fused_env = switch_int("BNERV_PAIR_FUSED", -1);      // (read per call: the parity tests switch forms inside one process)
+    const bool red_ep = c.ep_mode == BNERV_EP_DGELU_SAVED || c.ep_mode == BNERV_EP_DSIN;
+    const int fused_min = fused_env >= 0 ? fused_env : (red_ep ? 1024 : 0);
+    if (fused_min > 0 && total_items >= fused_min && total_items >= 8 && c.x == w.g && c.Cin == w.Cout && c.Cout == w.Cin && c.B == w.B &&
+        w.g_s == 1 && (w.g_mode == BNERV_IN_PLAIN || w.g_mode == BNERV_IN_UNSHUFFLE)) {
+        p.kind = Q4P_SHARED;
+        p.grid = p.n_w = total_items < 512 ? (total_items & ~7) : 512;
+        const float* raw_aux = c.ep_mode == BNERV_EP_DSIN ? c.aux0 : c.aux1;
+        if (red_ep && w.in_mode == BNERV_IN_AFFINE && !switch_off("BNERV_PAIR_FOLD") && c.B == 1 && raw_aux == w.x && w.scale && w.shift && aligned16(w.x) &&
+            (size_t)p.grid * w.Cout * (ncols + 8) * sizeof(float) <= w.ws_bytes)
+            p.kind = Q4P_FOLD;
+        return p;
+    }
+    p.kind = Q4P_INTERLEAVED;
+    p.n_conv = total_items < 768 ? total_items : 768;                  // 3 conv blocks per CU when the layer is large
+    p.n_conv = (p.n_conv + 7) & ~7;                                    // multiple of 8: block b runs on XCD b % 8 for BOTH halves' slices
+    p.n_w = wlean_blocks(w);
+    p.grid = p.n_conv + p.n_w;
+    if (total_items >= 2 * PAIR_MIX && p.n_w >= PAIR_MIX) {            // large layer: PAIR_MIX blocks per role, all resident, roles interleaved
+        p.n_w = PAIR_MIX; p.n_conv = -PAIR_MIX; p.grid = 2 * PAIR_MIX;
+    }
+    return p;
+}
+
+// The (conv epilogue, weight-gradient prologue) pairs form 1 is instantiated for, written once
+template <class F>
+int q4_pair_modes(const bnerv_conv_desc& c, const bnerv_wgrad_desc& w, F&& f) {
+#define BNERV_PAIR_CASE(E, I) if (c.ep_mode == E && w.in_mode == I) return f(mode_c<E>{}, mode_c<I>{});
+    BNERV_PAIR_CASE(BNERV_EP_DGELU_SAVED, BNERV_IN_AFFINE)
+    BNERV_PAIR_CASE(BNERV_EP_DSIN, BNERV_IN_AFFINE)
+    BNERV_PAIR_CASE(BNERV_EP_PLAIN, BNERV_IN_PLAIN)
+#undef BNERV_PAIR_CASE
+    return -1;
+}
+
 template <int EP, int WIN>
-int launch_pair(hipStream_t st, bnerv_conv::KArgs& ka, const WArgs& wa, int* n_w_out) {
+int launch_pair(hipStream_t st, bnerv_conv::KArgs& ka, const WArgs& wa, const Q4PairPlan& p) {
     bnerv_q4::q4_prepare(ka);
-    {
-        // shared-tile form (pairf_body.h): one block runs both roles on its tile from ONE staged copy of the gradient.  Default: the pairs
-        // with a reducing epilogue (TAT convs: DGELU_SAVED / DSIN) from 1024 tiles on (two tiles per block at 512 blocks).  Measured on
-        // MI355X, C1 (profiles/r05_pair_fused.md): 720p DSIN pair 81.0 against 83.5 us, DGELU_SAVED 76.5 against 74.5, PLAIN 68.5 against
-        // 66.7 (kept on the interleaved pair); at 360x640 (900 tiles) the interleaved pair's three blocks per CU win (27 against 29 us).
-        // HBM traffic of the DSIN pair: see the same file.  BNERV_PAIR_FUSED=<tiles>: every pair from that many tiles on; 0: off.
-        const int fused_env = switch_int("BNERV_PAIR_FUSED", -1);      // (read per call: the parity tests switch forms inside one process)
-        constexpr bool red_ep = EP == BNERV_EP_DGELU_SAVED || EP == BNERV_EP_DSIN;
-        const int fused_min = fused_env >= 0 ? fused_env : (red_ep ? 1024 : 0);
-        const bnerv_conv_desc& c = ka.d;
-        const bnerv_wgrad_desc& w = wa.d;
-        if (fused_min > 0 && ka.total_items >= fused_min && ka.total_items >= 8 && c.x == w.g && c.Cin == w.Cout && c.Cout == w.Cin && c.B == w.B &&
-            w.g_s == 1 && (w.g_mode == BNERV_IN_PLAIN || w.g_mode == BNERV_IN_UNSHUFFLE)) {
+    SidePack side;
+    if (p.kind == Q4P_FOLD) {
+        if constexpr ((EP == BNERV_EP_DGELU_SAVED || EP == BNERV_EP_DSIN) && WIN == BNERV_IN_AFFINE) {
             const size_t ldsf = pair_fused_lds_bytes();
             if (const int rc = dyn_lds<&pair_fused_kernel<EP, WIN>>(ldsf, "pair_fused")) return rc;
-            int grid = ka.total_items < 512 ? (ka.total_items & ~7) : 512;
-            if (n_w_out) *n_w_out = grid;
-            SidePack side;
-            bnerv_side_take(w.ctx, &side, 2 * grid);
-            if constexpr (red_ep && WIN == BNERV_IN_AFFINE) {
-                // fold form (pairf_body.h pair_fold_body): the input tile staged raw by LDS-DMA, the affine applied by the slab reduction.  One sample
-                // per launch (the fold is per sample), the reducing epilogue's raw-input operand must BE the weight gradient's input, and the
-                // workspace must hold `grid` slabs of Cout x (ncols + 8).  BNERV_PAIR_FOLD=0: the transforming form above.
-                const float* raw_aux = EP == BNERV_EP_DSIN ? c.aux0 : c.aux1;
-                if (!switch_off("BNERV_PAIR_FOLD") && c.B == 1 && raw_aux == w.x && w.scale && w.shift && aligned16(w.x) &&
-                    (size_t)grid * w.Cout * (wa.ncols + 8) * sizeof(float) <= w.ws_bytes) {
-                    const size_t ldsd = pair_fold_lds_bytes();
-                    if (const int rc = dyn_lds<&pair_fold_kernel<EP>>(ldsd, "pair_fold")) return rc;
-                    hipLaunchKernelGGL((pair_fold_kernel<EP>), dim3(grid), dim3(256), ldsd, st, ka, wa, side);
-                    BNERV_LAUNCH_CHECK("pair_fold");
-                    if (n_w_out) *n_w_out = -grid;         // negative: the caller queues a FOLD slab reduction
-                    return BNERV_OK;
-                }
-            }
-            hipLaunchKernelGGL((pair_fused_kernel<EP, WIN>), dim3(grid), dim3(256), ldsf, st, ka, wa, side);
-            BNERV_LAUNCH_CHECK("pair_fused");
+            const size_t ldsd = pair_fold_lds_bytes();
+            if (const int rc = dyn_lds<&pair_fold_kernel<EP>>(ldsd, "pair_fold")) return rc;
+            bnerv_side_take(wa.d.ctx, &side, 2 * p.n_w);
+            hipLaunchKernelGGL((pair_fold_kernel<EP>), dim3(p.grid), dim3(256), ldsd, st, ka, wa, side);
+            BNERV_LAUNCH_CHECK("pair_fold");
             return BNERV_OK;
         }
+    }
+    if (p.kind != Q4P_INTERLEAVED) {
+        const size_t ldsf = pair_fused_lds_bytes();
+        if (const int rc = dyn_lds<&pair_fused_kernel<EP, WIN>>(ldsf, "pair_fused")) return rc;
+        bnerv_side_take(wa.d.ctx, &side, 2 * p.n_w);
+        hipLaunchKernelGGL((pair_fused_kernel<EP, WIN>), dim3(p.grid), dim3(256), ldsf, st, ka, wa, side);
+        BNERV_LAUNCH_CHECK("pair_fused");
+        return BNERV_OK;
     }
     const int n_grows = wa.d.Cout <= 12 ? 12 : 16;
     size_t lds = bnerv_q4::q4_lds_bytes();
     const size_t lw = wlean_lds_bytes<3>(n_grows);
     if (lw > lds) lds = lw;
     if (const int rc = dyn_lds<&conv_wgrad_pair_kernel<EP, WIN>>(lds, "conv_wgrad_pair")) return rc;
-    int n_conv = ka.total_items < 768 ? ka.total_items : 768;          // 3 conv blocks per CU when the layer is large
-    n_conv = (n_conv + 7) & ~7;                                        // multiple of 8: block b runs on XCD b % 8 for BOTH halves' slices
-    int n_w = wlean_blocks(wa.d);
-    int grid = n_conv + n_w;
-    if (n_w_out) *n_w_out = n_w;
-    // PAIR_MIX: blocks per role of the interleaved form; PAIR_PAT: the role of XCD-local slot s is (s + (s >> PAT)) & 1.  Measured on C1
-    // (1.745 ms with the roles one after the other): 384 blocks per role 1.680 (PAT 0), 1.642 (PAT 5: the parity flips every 32 slots =
-    // the CUs of an XCD, so every CU holds both roles), 1.664 (6), 1.68 (3, 4, 7); 376 / 368 per role as 384, 512 per role (not all
-    // resident) 1.783.
-    constexpr int PAIR_MIX = 384, PAIR_PAT = 5;
-    if (ka.total_items >= 2 * PAIR_MIX && n_w >= PAIR_MIX) {           // large layer: PAIR_MIX blocks per role, all resident, roles interleaved
-        n_w = PAIR_MIX; n_conv = -PAIR_MIX; grid = 2 * PAIR_MIX;
-        if (n_w_out) *n_w_out = n_w;
-    }
-    SidePack side;
-    bnerv_side_take(wa.d.ctx, &side, 2 * n_w);
-    hipLaunchKernelGGL((conv_wgrad_pair_kernel<EP, WIN>), dim3(grid), dim3(256), lds, st, ka, wa, n_grows, n_conv, side, PAIR_PAT);
+    bnerv_side_take(wa.d.ctx, &side, 2 * p.n_w);
+    hipLaunchKernelGGL((conv_wgrad_pair_kernel<EP, WIN>), dim3(p.grid), dim3(256), lds, st, ka, wa, n_grows, p.n_conv, side, PAIR_PAT);
     BNERV_LAUNCH_CHECK("conv_wgrad_pair");
     return BNERV_OK;
 }
@@ -1529,54 +1577,45 @@ int launch_small_pair(hipStream_t st, const bnerv_convs::SArgs& sa, const WArgs&
     return BNERV_OK;
 }
 
-// 1: not a pair of this form.  On BNERV_OK *n_slabs is the weight gradient's slab count (the caller queues its reduction).
-static int small_pair_try(hipStream_t st, const bnerv_conv_desc& c, WArgs& wa, int* n_slabs) {
-    const bnerv_wgrad_desc& w = wa.d;
-    if (!bnerv_convs_shape_ok(c, conv_vec_ok(c))) return 1;
-    if (c.in_mode != BNERV_IN_UNSHUFFLE && c.Cin > 32) return 1;                           // (convs.hip's 96-channel form has no paired instantiation)
-    if (c.ep_mode == BNERV_EP_PLAIN && bnerv_conv_splitk_ws_bytes(&c) != 0) return 1;     // (a split-K layer: its own launches)
-    if (!(w.k == 3 && w.B == c.B && w.H == c.H && w.W == c.W && w.defer_finish && w.ctx && w.ctx == c.ctx)) return 1;
-    bnerv_convs::SArgs sa;
-    sa.d = c;
-    sa.tiles_x = cdiv(c.W, bnerv_convs::STW);
-    sa.tiles_y = cdiv(c.H, bnerv_convs::STH);
-    const int cnq = c.in_mode == BNERV_IN_UNSHUFFLE ? (c.Cin <= 32 ? 8 : 16) : (c.Cin <= 16 ? 4 : 8);
-    WideRoleArgs r{0, 0, 0};
-    int rc = 1;
-    if (wlean_ok(wa)) return 1;                            // (the lean weight gradient pairs with conv4.hip's family)
-#define BNERV_SP(WR, I, E, Q) if (c.in_mode == I && c.ep_mode == E && cnq == Q) rc = launch_small_pair<WR, I, E, Q>(st, sa, wa, r, n_w);
-    if (bw_ok(wa)) {
-        if (split_wide_mode() != (int)SP_BF16X6) return 1;
-        const BwPlan bp = bw_plan(w);
-        r.slots = bp.slots; r.ngn = bp.ngroups_n; r.ngm = bp.ngroups_m;
-        const int n_w = 8 * bp.slots * bp.ngroups_n * bp.ngroups_m;
-        *n_slabs = 8 * bp.slots;
-        if (w.g_s == 2 && w.in_mode == BNERV_IN_PLAIN && w.g_mode == BNERV_IN_UNSHUFFLE) {          // an up-conv's (dW | d input)
-            if (bp.mtw == 2) { using WR = BfwRole<BNERV_IN_PLAIN, SP_BF16X6, 2, 1>; BNERV_SP(WR, BNERV_IN_UNSHUFFLE, BNERV_EP_PLAIN, 8) BNERV_SP(WR, BNERV_IN_UNSHUFFLE, BNERV_EP_PLAIN, 16) }
-            if (bp.mtw == 3) { using WR = BfwRole<BNERV_IN_PLAIN, SP_BF16X6, 3, 1>; BNERV_SP(WR, BNERV_IN_UNSHUFFLE, BNERV_EP_PLAIN, 16) }
-        } else if (w.g_s == 1 && w.in_mode == BNERV_IN_AFFINE && w.g_mode != BNERV_IN_TANHGRAD) {  // a TAT conv's (dW | d input), 17..32 channels
-            if (bp.mtw == 2) { using WR = BfwRole<BNERV_IN_AFFINE, SP_BF16X6, 2, 0>; BNERV_SP(WR, BNERV_IN_PLAIN, BNERV_EP_DGELU_SAVED, 8) BNERV_SP(WR, BNERV_IN_PLAIN, BNERV_EP_DSIN, 8) }
-        }
-        return rc;
+// The (weight-gradient role, conv prologue, conv epilogue, conv channel quads) form 2 is instantiated for, written once: f(type_c<role>,
+// mode_c<IN>, mode_c<EP>, mode_c<NQ>) for the pair's entry, -1 for any other.  wr: the weight gradient's route.
+template <class T> struct type_c { using type = T; };
+template <class F>
+int small_pair_modes(const bnerv_conv_desc& c, const bnerv_wgrad_desc& w, const WRoute& wr, F&& f) {
+    const int cnq = bnerv_convs_nq(c);
+    const bool up = w.g_s == 2 && w.in_mode == BNERV_IN_PLAIN && w.g_mode == BNERV_IN_UNSHUFFLE;          // an up-conv's (dW | d input)
+    const bool tat = w.g_s == 1 && w.in_mode == BNERV_IN_AFFINE && w.g_mode != BNERV_IN_TANHGRAD;         // a TAT conv's (dW | d input)
+#define BNERV_SP(WR, I, E, Q) if (c.in_mode == I && c.ep_mode == E && cnq == Q) return f(type_c<WR>{}, mode_c<I>{}, mode_c<E>{}, mode_c<Q>{});
+    if (wr.family == BNERV_WGRAD_FAM_WIDE_BF16 && split_wide_mode() == (int)SP_BF16X6) {
+        if (up && wr.bw.mtw == 2) { using WR = BfwRole<BNERV_IN_PLAIN, SP_BF16X6, 2, 1>; BNERV_SP(WR, BNERV_IN_UNSHUFFLE, BNERV_EP_PLAIN, 8) BNERV_SP(WR, BNERV_IN_UNSHUFFLE, BNERV_EP_PLAIN, 16) }
+        if (up && wr.bw.mtw == 3) { using WR = BfwRole<BNERV_IN_PLAIN, SP_BF16X6, 3, 1>; BNERV_SP(WR, BNERV_IN_UNSHUFFLE, BNERV_EP_PLAIN, 16) }
+        if (tat && wr.bw.mtw == 2) { using WR = BfwRole<BNERV_IN_AFFINE, SP_BF16X6, 2, 0>; BNERV_SP(WR, BNERV_IN_PLAIN, BNERV_EP_DGELU_SAVED, 8) BNERV_SP(WR, BNERV_IN_PLAIN, BNERV_EP_DSIN, 8) }   // 17..32 channels
     }
-    if (wide_ok(wa)) {
-        const WidePlan wp = wide_plan(w);
-        if (!(wp.mtw == 1 && wp.ntw == 8)) return 1;
-        const int ng0 = wa.n_ngroups, mg0 = wa.n_mgroups;
-        wa.n_ngroups = wp.ngroups;
-        wa.n_mgroups = wp.mgroups;
-        r.slots = wp.slots;
-        const int n_w = 8 * wp.slots * wp.ngroups * wp.mgroups;
-        *n_slabs = 8 * wp.slots;
-        if (w.g_s == 1 && w.in_mode == BNERV_IN_AFFINE && w.g_mode != BNERV_IN_TANHGRAD) {         // a TAT conv's (dW | d input), 13..16 channels
-            using WR = WideRole<BNERV_IN_AFFINE, 0, 1, 8>;
-            BNERV_SP(WR, BNERV_IN_PLAIN, BNERV_EP_DGELU_SAVED, 4) BNERV_SP(WR, BNERV_IN_PLAIN, BNERV_EP_DSIN, 4)
-        }
-        if (rc == 1) { wa.n_ngroups = ng0; wa.n_mgroups = mg0; }
-        return rc;
+    if (wr.family == BNERV_WGRAD_FAM_WIDE_F32 && wr.wide.mtw == 1 && wr.wide.ntw == 8 && tat) {          // 13..16 channels
+        using WR = WideRole<BNERV_IN_AFFINE, 0, 1, 8>;
+        BNERV_SP(WR, BNERV_IN_PLAIN, BNERV_EP_DGELU_SAVED, 4) BNERV_SP(WR, BNERV_IN_PLAIN, BNERV_EP_DSIN, 4)
     }
 #undef BNERV_SP
-    return 1;
+    return -1;
+}
+
+// form 2's conv half: convs.hip's family (its 96-channel form has no paired instantiation), not a split-K layer, next to a deferred weight
+// gradient of the same image and context
+bool small_pair_ok(const bnerv_conv_desc& c, int cvec, const bnerv_wgrad_desc& w, const WRoute& wr) {
+    if (!bnerv_convs_ok(c, cvec) || bnerv_convs_nq(c) == 24) return false;
+    if (c.ep_mode == BNERV_EP_PLAIN && bnerv_conv_splitk_ws_bytes(&c) != 0) return false;     // (a split-K layer: its own launches)
+    if (!(w.k == 3 && w.B == c.B && w.H == c.H && w.W == c.W && w.defer_finish && w.ctx && w.ctx == c.ctx)) return false;
+    return small_pair_modes(c, w, wr, [](auto...) { return 0; }) == 0;
+}
+
+int small_pair_launch(hipStream_t st, const bnerv_conv_desc& c, const WArgs& wa, const WRoute& wr) {
+    const bnerv_convs::SArgs sa = bnerv_convs_sargs(c);
+    const bool bf = wr.family == BNERV_WGRAD_FAM_WIDE_BF16;
+    const WideRoleArgs r = bf ? WideRoleArgs{wr.bw.slots, wr.bw.ngroups_n, wr.bw.ngroups_m} : WideRoleArgs{wr.wide.slots, 0, 0};
+    const int n_w = bf ? 8 * wr.bw.slots * wr.bw.ngroups_n * wr.bw.ngroups_m : 8 * wr.wide.slots * wr.wide.ngroups * wr.wide.mgroups;
+    return small_pair_modes(c, wa.d, wr, [&](auto role, auto in, auto ep, auto nq) {
+        return launch_small_pair<typename decltype(role)::type, decltype(in)::value, decltype(ep)::value, decltype(nq)::value>(st, sa, wa, r, n_w);
+    });
 }
 }  // namespace
 
@@ -1646,108 +1685,175 @@ __global__ __launch_bounds__(256) void head1x1_bwd_kernel(const HeadBwdArgs a) {
     }
 }
 
-// 1: not the head's pair; BNERV_OK: launched, *n_slabs slabs of K x (C + 1) floats in w.ws
-static int head_pair_try(hipStream_t st, const bnerv_conv_desc& c, const bnerv_wgrad_desc& w, int* n_slabs) {
-    if (!(c.k == 1 && w.k == 1 && c.in_mode == BNERV_IN_TANHGRAD && c.ep_mode == BNERV_EP_PLAIN && c.out_s == 1 && w.g_mode == BNERV_IN_TANHGRAD && w.in_mode == BNERV_IN_PLAIN)) return 1;
-    if (!(c.x && c.aux0 && c.w && c.out && w.x && w.g && w.gaux && w.dw && w.ws && w.defer_finish && w.ctx && w.ctx == c.ctx)) return 1;
-    if (!(c.x == w.g && c.aux0 == w.gaux && c.Cin == w.Cout && c.Cout == w.Cin && c.B == w.B && c.H == w.H && c.W == w.W)) return 1;     // one head, one gradient
+// the head's pair: blocks (= slabs of K x (C + 1) floats in w.ws) of its one streaming pass; 0: not this pair
+static int head_pair_blocks(const bnerv_conv_desc& c, const bnerv_wgrad_desc& w) {
+    if (!(c.k == 1 && w.k == 1 && c.in_mode == BNERV_IN_TANHGRAD && c.ep_mode == BNERV_EP_PLAIN && c.out_s == 1 && w.g_mode == BNERV_IN_TANHGRAD && w.in_mode == BNERV_IN_PLAIN)) return 0;
+    if (!(c.x && c.aux0 && c.w && c.out && w.x && w.g && w.gaux && w.dw && w.ws && w.defer_finish && w.ctx && w.ctx == c.ctx)) return 0;
+    if (!(c.x == w.g && c.aux0 == w.gaux && c.Cin == w.Cout && c.Cout == w.Cin && c.B == w.B && c.H == w.H && c.W == w.W)) return 0;     // one head, one gradient
     const int K = c.Cin, C = c.Cout;
-    if (K != 3 || C != 12 || ((size_t)c.H * c.W) % 4 != 0) return 1;            // (instantiated for the reference's heads: 12 -> 3; HNeRV's heads are 3x3)
-    if (c.transposed ? !(c.wCo == K && c.wCi == C) : !(c.wCo == C && c.wCi == K)) return 1;
-    if (!aligned16(c.x, c.aux0, c.out, w.x)) return 1;
-    const size_t HW = (size_t)c.H * c.W;
-    const int nq = (int)(HW / 4);
+    if (K != 3 || C != 12 || ((size_t)c.H * c.W) % 4 != 0) return 0;            // (instantiated for the reference's heads: 12 -> 3; HNeRV's heads are 3x3)
+    if (c.transposed ? !(c.wCo == K && c.wCi == C) : !(c.wCo == C && c.wCi == K)) return 0;
+    if (!aligned16(c.x, c.aux0, c.out, w.x)) return 0;
     // one quad per thread up to 1024 blocks (every load of a thread is in flight at once: the pass is one memory round trip per wave; a
     // first version with four quads per thread on 225 blocks ran 36.8 us -- four serialised round trips on less than one wave per SIMD)
-    int blocks = cdiv(c.B * nq, 256);
+    int blocks = cdiv(c.B * (int)(((size_t)c.H * c.W) / 4), 256);
     if (blocks > 1024) blocks = 1024;
     if (blocks < 1) blocks = 1;
-    if ((size_t)blocks * K * (C + 1) * sizeof(float) > w.ws_bytes) return 1;
-    HeadBwdArgs a{c.x, c.aux0, w.x, c.w, c.out, reinterpret_cast<float*>(w.ws), c.B, K, C, c.transposed, HW, nq};
+    return (size_t)blocks * K * (C + 1) * sizeof(float) > w.ws_bytes ? 0 : blocks;
+}
+static int head_pair_launch(hipStream_t st, const bnerv_conv_desc& c, const bnerv_wgrad_desc& w, int blocks) {
+    const size_t HW = (size_t)c.H * c.W;
+    HeadBwdArgs a{c.x, c.aux0, w.x, c.w, c.out, reinterpret_cast<float*>(w.ws), c.B, c.Cin, c.Cout, c.transposed, HW, (int)(HW / 4)};
     hipLaunchKernelGGL((head1x1_bwd_kernel<3, 12>), dim3(blocks), dim3(256), 0, st, a);
     BNERV_LAUNCH_CHECK("head1x1_bwd");
-    *n_slabs = blocks;
     return BNERV_OK;
+}
+
+// ---- the pair's plan: which form takes (conv, wgrad), with which conv tiles, how many slabs, and whether the slab reduction folds the affine.
+// THE order of the forms: H, 0, 1, 3, 2.  Pure.  `c`: normalised (IN_UNSHUFFLE with in_s == 1 is IN_PLAIN).
+namespace {
+struct PairPlan {
+    int form;               // BNERV_PAIR_*
+    int rc;                 // what the entry point returns where form is NONE: 1 (issue the two calls), or a BNERV_E_*
+    int th, tw;             // the conv half's tiles: a sums epilogue writes one row of c.partial per tile
+    int n_slabs;            // slabs for the deferred reduction: the weight gradient's (form 0: the data gradient's K slices)
+    bool fold;              // form 1's fold form: slabs of ncols + 8 columns, the affine applied by the reduction
+    int cvec, wvec;
+    WRoute wr;              // the weight-gradient role (forms 1, 3, 2)
+    Q4PairPlan q4;          // form 1
+    bnerv_bfpair_plan bf;   // form 3
+};
+
+PairPlan pair_form(const bnerv_conv_desc& c, const bnerv_wgrad_desc& w, bool no_bf16) {
+    PairPlan p{};
+    p.form = BNERV_PAIR_NONE;
+    p.rc = 1;
+    p.th = bnerv_conv::TH;
+    p.tw = bnerv_conv::TW;
+    if (c.k == 1) {                                        // form H: the 1x1 output head (tanh-grad prologue), one streaming pass
+        p.n_slabs = head_pair_blocks(c, w);
+        if (p.n_slabs) p.form = BNERV_PAIR_HEAD;
+        return p;
+    }
+    // the conv half: a 3x3 stride-1 data gradient (plain input, or the unshuffle(2) prologue of an up-conv's), epilogue PLAIN / DGELU_SAVED / DSIN
+    if (!(c.k == 3 && c.out_s == 1 && c.x && c.w && c.out && c.B > 0 && c.H > 0 && c.W > 0)) return p;
+    // form 0: the stem stage (an image of <= 256 pixels: stem.hip) -- dW / db are written directly, the data gradient's K-slice slabs
+    // (c.partial, bnerv_conv_splitk_ws_bytes) are summed by a deferred reduction on the same context
+    if (c.ep_mode == BNERV_EP_PLAIN && c.partial && w.k == 3 && w.x && w.g && w.dw && w.ctx && w.ctx == c.ctx && bnerv_stem_pair_ok(c, w)) {
+        p.form = BNERV_PAIR_STEM;
+        p.n_slabs = bnerv_stem_dgrad_slabs(c);
+        return p;
+    }
+    if (!((c.in_mode == BNERV_IN_PLAIN && c.in_s == 1) || (c.in_mode == BNERV_IN_UNSHUFFLE && c.in_s == 2))) return p;
+    if (!(c.ep_mode == BNERV_EP_DGELU_SAVED || c.ep_mode == BNERV_EP_DSIN || c.ep_mode == BNERV_EP_PLAIN)) return p;
+    if (c.ep_mode != BNERV_EP_PLAIN && !(c.aux0 && c.aux1 && c.scale && c.partial)) return p;
+    if (c.ep_mode == BNERV_EP_DSIN && !c.aux2) return p;
+    if (c.transposed ? !(c.Cout == c.wCi && c.Cin == c.wCo) : !(c.Cout == c.wCo && c.Cin == c.wCi)) return p;
+    // the weight-gradient half: a deferred 3x3 weight gradient on the same image size and context
+    if (!(w.k == 3 && w.x && w.g && w.dw && w.ws && w.B == c.B && w.H == c.H && w.W == c.W && w.defer_finish && w.ctx && w.ctx == c.ctx)) return p;
+    if (!(w.in_mode == BNERV_IN_PLAIN || w.in_mode == BNERV_IN_AFFINE) || !(w.g_mode == BNERV_IN_PLAIN || w.g_mode == BNERV_IN_UNSHUFFLE)) return p;
+    if (w.in_mode == BNERV_IN_AFFINE && !(w.scale && w.shift)) return p;
+    if (!(w.g_s == 1 || (w.g_s == 2 && w.g_mode == BNERV_IN_UNSHUFFLE && w.Cout % 4 == 0))) return p;
+    if (w.Cin <= 0 || w.Cout <= 0) return p;
+    if (w.ws_bytes < bnerv_conv_wgrad_ws_bytes(w.B, w.Cin, w.Cout, w.H, w.W, w.k)) {
+        p.rc = BNERV_E_WS;                                 // (the entry point sets the message: this function touches no state)
+        return p;
+    }
+    p.cvec = conv_vec_ok(c);                               // (includes out2, which no epilogue of a pair writes: the callers leave it NULL)
+    p.wvec = wgrad_vec(w, false);
+    p.wr = wgrad_route(w, p.wvec, BNERV_WGRAD_FAM_LEAN);
+    // form 1: conv4.hip's 12-channel family next to the lean weight gradient (roles interleaved per XCD on large layers, or one shared tile)
+    if (c.in_mode == BNERV_IN_PLAIN && w.g_s == 1 && p.wr.family == BNERV_WGRAD_FAM_LEAN && bnerv_q4::q4_shape_ok(bnerv_conv_kargs(c, p.cvec)) &&
+        q4_pair_modes(c, w, [](auto, auto) { return 0; }) == 0) {
+        p.form = BNERV_PAIR_Q4_LEAN;
+        p.q4 = q4_pair_plan(c, w);
+        p.n_slabs = p.q4.n_w;
+        p.fold = p.q4.kind == Q4P_FOLD;
+        return p;
+    }
+    // form 3: the wide split conv next to the wide split weight gradient, roles interleaved (layers that fill the chip in both roles)
+    if (!no_bf16 && p.wr.family == BNERV_WGRAD_FAM_WIDE_BF16 && split_wide_mode() == (int)SP_BF16X6) {
+        p.bf = bnerv_convbf_pair_plan(c, p.cvec, w, p.wr.bw);
+        if (p.bf.take) {
+            p.form = BNERV_PAIR_BF16_WIDE;
+            p.n_slabs = 8 * p.bf.slots;
+            return p;
+        }
+    }
+    // form 2: convs.hip's low-resolution family next to a wide weight gradient
+    if (small_pair_ok(c, p.cvec, w, p.wr)) {
+        p.form = BNERV_PAIR_SMALL_WIDE;
+        p.th = BNERV_CONVS_TH;
+        p.tw = BNERV_CONVS_TW;
+        p.n_slabs = p.wr.n_slabs;
+    }
+    return p;
+}
+
+// The form, or NONE where its conv half would write other rows of c.partial than bnerv_conv_partial_rows(c) promised the caller (who sized
+// the buffer with it, for the stand-alone launch): with the shipped tables every form's conv half is the family bnerv_conv_igemm runs for c.
+PairPlan pair_plan(const bnerv_conv_desc& c, const bnerv_wgrad_desc& w, bool no_bf16 = false) {
+    PairPlan p = pair_form(c, w, no_bf16);
+    const bool sums = c.ep_mode == BNERV_EP_DGELU || c.ep_mode == BNERV_EP_DSIN || c.ep_mode == BNERV_EP_DGELU_SAVED;
+    if (p.form != BNERV_PAIR_NONE && sums && cdiv(c.H, p.th) * cdiv(c.W, p.tw) != bnerv_conv_partial_rows(&c)) {
+        p.form = BNERV_PAIR_NONE;
+        p.rc = 1;
+    }
+    return p;
+}
+
+bnerv_conv_desc pair_conv_desc(const bnerv_conv_desc& cd) {
+    bnerv_conv_desc c = cd;
+    if (c.in_mode == BNERV_IN_UNSHUFFLE && c.in_s == 1) c.in_mode = BNERV_IN_PLAIN;
+    return c;
+}
+}  // namespace
+
+extern "C" int bnerv_conv_wgrad_pair_form(const bnerv_conv_desc* cdp, const bnerv_wgrad_desc* wdp, int* conv_rows) {
+    if (conv_rows) *conv_rows = 0;
+    if (!cdp || !wdp || cdp->H <= 0 || cdp->W <= 0 || cdp->B <= 0 || cdp->Cin <= 0 || cdp->Cout <= 0) return BNERV_PAIR_NONE;
+    const bnerv_conv_desc c = pair_conv_desc(*cdp);
+    const PairPlan p = pair_plan(c, *wdp);
+    if (conv_rows && p.form != BNERV_PAIR_NONE) *conv_rows = cdiv(c.H, p.th) * cdiv(c.W, p.tw);
+    return p.form;
 }
 
 // Returns BNERV_OK when both were launched together, 1 when the pair is not one this launch takes (the caller then issues
 // bnerv_conv_wgrad and bnerv_conv_igemm separately, in that order), a negative BNERV_E_* on error.
 extern "C" int bnerv_conv_wgrad_pair(void* stream, const bnerv_conv_desc* cdp, const bnerv_wgrad_desc* wdp) {
     BNERV_REQUIRE(cdp != nullptr && wdp != nullptr, "conv_wgrad_pair: null descriptor");
-    bnerv_conv::KArgs ka;
-    ka.d = *cdp;
-    bnerv_conv_desc& c = ka.d;
-    WArgs wa;
-    wa.d = *wdp;
-    const bnerv_wgrad_desc& w = wa.d;
-    // the conv half: a 3x3 stride-1 data gradient (plain input, or the unshuffle(2) prologue of an up-conv's), epilogue PLAIN / DGELU_SAVED / DSIN
-    if (c.in_mode == BNERV_IN_UNSHUFFLE && c.in_s == 1) c.in_mode = BNERV_IN_PLAIN;
-    if (c.k == 1) {                                        // form H: the 1x1 output head (tanh-grad prologue), one streaming pass
-        int ns = 0;
-        const int rh = head_pair_try(reinterpret_cast<hipStream_t>(stream), c, w, &ns);
-        if (rh != BNERV_OK) return rh;
-        bnerv_side_push(w.ctx, reinterpret_cast<hipStream_t>(stream), w.ws, ns, w.Cout * (w.Cin + 1), w.Cin + 1, w.dw, w.db);
+    const bnerv_conv_desc c = pair_conv_desc(*cdp);
+    const bnerv_wgrad_desc& w = *wdp;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    PairPlan p = pair_plan(c, w);
+    for (;;) {
+        int rc = p.rc;
+        switch (p.form) {
+        case BNERV_PAIR_HEAD:
+            if ((rc = head_pair_launch(st, c, w, p.n_slabs)) == BNERV_OK) bnerv_side_push(w.ctx, st, w.ws, p.n_slabs, w.Cout * (w.Cin + 1), w.Cin + 1, w.dw, w.db);
+            return rc;
+        case BNERV_PAIR_STEM:
+            if ((rc = bnerv_stem_pair_launch(st, c, w)) == BNERV_OK) bnerv_side_push(c.ctx, st, c.partial, p.n_slabs, c.B * c.Cout * c.H * c.W, 0, c.out, nullptr);
+            return rc;
+        case BNERV_PAIR_NONE: return rc == BNERV_E_WS ? bnerv_set_error(rc, "conv_wgrad_pair: weight-gradient workspace too small") : rc;
+        default: break;
+        }
+        const WArgs wa = wgrad_args(w, p.wr, p.wvec);
+        if (p.form == BNERV_PAIR_Q4_LEAN) {
+            bnerv_conv::KArgs ka = bnerv_conv_kargs(c, p.cvec);
+            rc = q4_pair_modes(c, w, [&](auto ep, auto in) { return launch_pair<decltype(ep)::value, decltype(in)::value>(st, ka, wa, p.q4); });
+        } else if (p.form == BNERV_PAIR_BF16_WIDE) {
+            rc = bnerv_convbf_pair_launch(st, c, wa, p.wr.bw, p.bf);
+            if (rc == BNERV_DECLINED) {                    // no scratch for the weight fragments: the forms behind this one
+                p = pair_plan(c, w, true);
+                continue;
+            }
+        } else {
+            rc = small_pair_launch(st, c, wa, p.wr);
+        }
+        if (rc != BNERV_OK) return rc;
+        if (p.fold) bnerv_side_push(w.ctx, st, wa.slab, p.n_slabs, w.Cout * wa.ncols, wa.ncols, w.dw, w.db, w.scale, w.shift);
+        else bnerv_side_push(w.ctx, st, wa.slab, p.n_slabs, w.Cout * wa.ncols, wa.ncols, w.dw, w.db);     // the slab reduction rides on a later launch
         return BNERV_OK;
     }
-    if (!(c.k == 3 && c.out_s == 1 && c.x && c.w && c.out && c.B > 0)) return 1;
-    // form 0: the stem stage (an image of <= 256 pixels: stem.hip) -- dW / db are written directly, the data gradient's K-slice slabs
-    // (c.partial, bnerv_conv_splitk_ws_bytes) are summed by a deferred reduction on the same context
-    if (c.ep_mode == BNERV_EP_PLAIN && c.partial && w.k == 3 && w.x && w.g && w.dw && w.ctx && w.ctx == c.ctx) {
-        int ns = 0;
-        const int rs = bnerv_stem_pair_try(reinterpret_cast<hipStream_t>(stream), c, w, &ns);
-        if (rs < 0) return rs;
-        if (rs == BNERV_OK) {
-            bnerv_side_push(c.ctx, reinterpret_cast<hipStream_t>(stream), c.partial, ns, c.B * c.Cout * c.H * c.W, 0, c.out, nullptr);
-            return BNERV_OK;
-        }
-    }
-    if (!((c.in_mode == BNERV_IN_PLAIN && c.in_s == 1) || (c.in_mode == BNERV_IN_UNSHUFFLE && c.in_s == 2))) return 1;
-    if (!(c.ep_mode == BNERV_EP_DGELU_SAVED || c.ep_mode == BNERV_EP_DSIN || c.ep_mode == BNERV_EP_PLAIN)) return 1;
-    if (c.ep_mode != BNERV_EP_PLAIN && !(c.aux0 && c.aux1 && c.scale && c.partial)) return 1;
-    if (c.ep_mode == BNERV_EP_DSIN && !c.aux2) return 1;
-    if (c.transposed ? !(c.Cout == c.wCi && c.Cin == c.wCo) : !(c.Cout == c.wCo && c.Cin == c.wCi)) return 1;
-    // the weight-gradient half: a deferred 3x3 weight gradient on the same image size and context
-    if (!(w.k == 3 && w.x && w.g && w.dw && w.ws && w.B == c.B && w.H == c.H && w.W == c.W && w.defer_finish && w.ctx && w.ctx == c.ctx)) return 1;
-    if (!(w.in_mode == BNERV_IN_PLAIN || w.in_mode == BNERV_IN_AFFINE) || !(w.g_mode == BNERV_IN_PLAIN || w.g_mode == BNERV_IN_UNSHUFFLE)) return 1;
-    if (w.in_mode == BNERV_IN_AFFINE && !(w.scale && w.shift)) return 1;
-    if (!(w.g_s == 1 || (w.g_s == 2 && w.g_mode == BNERV_IN_UNSHUFFLE && w.Cout % 4 == 0))) return 1;
-    if (w.ws_bytes < bnerv_conv_wgrad_ws_bytes(w.B, w.Cin, w.Cout, w.H, w.W, w.k)) return bnerv_set_error(BNERV_E_WS, "conv_wgrad_pair: weight-gradient workspace too small");
-    const Plan p = make_plan(w.B, w.Cin, w.Cout, w.H, w.W, w.k);
-    wa.slab = reinterpret_cast<float*>(w.ws);
-    wa.tiles_x = cdiv(w.W, TW);
-    wa.tiles_y = cdiv(w.H, TH);
-    wa.n_mgroups = p.n_mgroups;
-    wa.n_ngroups = p.n_ngroups;
-    wa.ncols = w.Cin * 9 + 1;
-    wa.vec = ((w.W % 4 == 0) && aligned16(w.x, w.g)) ? 1 : 0;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    int rc = 1, n_slabs = 0;
-
-    // form 1: conv4.hip's 12-channel family next to the lean weight gradient (roles interleaved per XCD on large layers)
-    ka.tiles_x = cdiv(c.W, bnerv_conv::TW);
-    ka.tiles_y = cdiv(c.H, bnerv_conv::TH);
-    ka.vec = conv_vec_ok(c);                               // (includes out2, which no epilogue of a pair writes: the callers leave it NULL)
-    ka.ksplit = 1;
-    ka.chunks_per_split = 0;
-    ka.magic_tiles = ka.magic_tiles_x = 0;
-    if (c.in_mode == BNERV_IN_PLAIN && w.g_s == 1 && bnerv_q4::q4_shape_ok(ka) && wlean_ok(wa)) {
-#define BNERV_PAIR_CASE(E, I) if (c.ep_mode == E && w.in_mode == I) rc = launch_pair<E, I>(st, ka, wa, &n_slabs);
-        BNERV_PAIR_CASE(BNERV_EP_DGELU_SAVED, BNERV_IN_AFFINE)
-        BNERV_PAIR_CASE(BNERV_EP_DSIN, BNERV_IN_AFFINE)
-        BNERV_PAIR_CASE(BNERV_EP_PLAIN, BNERV_IN_PLAIN)
-#undef BNERV_PAIR_CASE
-    }
-    // form 3: the wide split conv next to the wide split weight gradient, roles interleaved (layers that fill the chip in both roles)
-    if (rc == 1 && !wlean_ok(wa) && bw_ok(wa) && split_wide_mode() == (int)SP_BF16X6) {
-        const BwPlan bp = bw_plan(w);
-        rc = bnerv_convbf_pair_try(st, c, ka.vec, wa, bp.mtw, bp.ngroups_n, bp.ngroups_m, bp.slots, &n_slabs);
-    }
-    // form 2: convs.hip's low-resolution family next to a wide weight gradient
-    if (rc == 1) rc = small_pair_try(st, c, wa, &n_slabs);
-    if (rc != BNERV_OK) return rc;
-    if (n_slabs < 0)                                       // the shared-tile pair's fold form: slabs of ncols + 8 columns, the affine applied by the reduction
-        bnerv_side_push(w.ctx, st, wa.slab, -n_slabs, w.Cout * wa.ncols, wa.ncols, w.dw, w.db, w.scale, w.shift);
-    else
-        bnerv_side_push(w.ctx, st, wa.slab, n_slabs, w.Cout * wa.ncols, wa.ncols, w.dw, w.db);     // the slab reduction rides on a later launch
-    return BNERV_OK;
 }

@@ -158,21 +158,18 @@ static bool w1_ok(const bnerv_wgrad_desc& d) {
 
 }  // namespace
 
-// slabs this kernel writes for a k = 1 layer (0: not its layer) -- bnerv_conv_wgrad_ws_bytes sizes the workspace with it
+// slabs this kernel writes for a k = 1 layer; 0: not its layer (the predicate of this family) -- bnerv_conv_wgrad_ws_bytes sizes the workspace with it
 int bnerv_wgrad1x1_slabs(const bnerv_wgrad_desc& d) {
     if (!w1_ok(d)) return 0;
     return w1_plan(d.B, d.Cin, d.Cout, d.H * d.W).nz;
 }
 
-// 1: not this kernel's layer; BNERV_OK: slabs written to d.ws, *n_slabs of them
-int bnerv_wgrad1x1_try(hipStream_t st, const bnerv_wgrad_desc& d, int* n_slabs) {
-    if (!w1_ok(d)) return 1;
+// writes bnerv_wgrad1x1_slabs(d) slabs to d.ws (the entry point has checked d.ws_bytes against bnerv_conv_wgrad_ws_bytes, which covers them)
+int bnerv_wgrad1x1_launch(hipStream_t st, const bnerv_wgrad_desc& d) {
     const int HW = d.H * d.W;
     const W1Plan p = w1_plan(d.B, d.Cin, d.Cout, HW);
-    if ((size_t)p.nz * d.Cout * (d.Cin + 1) * sizeof(float) > d.ws_bytes) return 1;
     W1Args a{d.x, d.g, reinterpret_cast<float*>(d.ws), d.B, d.Cin, d.Cout, HW, p.n_mg, p.n_ng, p.chunk};
     hipLaunchKernelGGL(wgrad1x1_kernel, dim3(p.n_mg * p.n_ng, p.nz), dim3(256), 0, st, a);
     BNERV_LAUNCH_CHECK("wgrad1x1");
-    *n_slabs = p.nz;
     return BNERV_OK;
 }

@@ -231,8 +231,28 @@ typedef struct {
 /* number of 8x32 spatial tiles per sample of an H x W conv-space image */
 int bnerv_conv_tiles(int H, int W);
 /* EP_DGELU / EP_DSIN: number of per-sample rows R this descriptor's kernel writes into `partial` ([R][B][2][Cout]); the
- * kernel is chosen from the shape and pointer alignment, so fill in every field except `partial` before asking. */
+ * kernel is chosen from the shape and pointer alignment, so fill in every field before asking.  For the epilogues that write rows
+ * the answer does not depend on `partial`, which may still be NULL.  (For EP_PLAIN, which writes none, the answer names the tiles of
+ * the family that the launch would run with `partial` as given: a workspace changes that family.) */
 int bnerv_conv_partial_rows(const bnerv_conv_desc* d);
+/* Kernel selection as a host query (additive to ABI 9; no device is touched, like bnerv_conv_partial_rows).  bnerv_conv_igemm decides
+ * once which kernel family takes a descriptor (csrc/route.h); these report that decision, so that it can be tested without a GPU.
+ * bnerv_conv_family: the BNERV_CONV_FAM_* id that bnerv_conv_igemm(d) runs, read from d exactly as the launch reads it (`partial`
+ * included: an EP_PLAIN workspace enables split-K and the stem kernel, and the 3x3 head's data gradient wants none), or -1 for a
+ * descriptor without positive dimensions or with k other than 1 or 3.  *rows (may be NULL) = bnerv_conv_partial_rows(d): the tiles of
+ * that family's grid -- 4x16 for SMALL / SMALL96, bnerv_conv_tiles otherwise.  For the sums epilogues the answer does not depend on
+ * `partial`.  A WIDE_BF16 route may still fall to Q4 / GENERIC at launch when the context has no scratch for the weight fragments
+ * (same 8x32 tiles; the launch checks that). */
+#define BNERV_CONV_FAM_HEAD1_FWD 0      /* 1x1 head 12 -> 3 + tanh, streaming */
+#define BNERV_CONV_FAM_HEAD1_DGRAD 1    /* its data gradient (tanh-grad prologue), streaming */
+#define BNERV_CONV_FAM_HEAD3 2          /* 3x3 head with 3 outputs: forward + tanh, or its data gradient (csrc/head3.hip) */
+#define BNERV_CONV_FAM_STEM_DGRAD 3     /* image of <= 256 pixels, long K: K-slice slabs in `partial` (csrc/stem.hip) */
+#define BNERV_CONV_FAM_SMALL 4          /* low-resolution stages, 4x16 tiles (csrc/convs.hip) */
+#define BNERV_CONV_FAM_SMALL96 5        /* the same with 33..96 staged channels */
+#define BNERV_CONV_FAM_WIDE_BF16 6      /* wide layers on split bf16 (csrc/convbf.hip) */
+#define BNERV_CONV_FAM_Q4 7             /* <= 12-channel 3x3 layers on the 4x4x1 MFMA (csrc/conv4.hip) */
+#define BNERV_CONV_FAM_GENERIC 8        /* the 16x16x4 f32 kernels of csrc/conv.hip (lean, fast, generic) */
+int bnerv_conv_family(const bnerv_conv_desc* d, int* rows);
 /* EP_PLAIN only: bytes of split-K workspace this layer wants (0 = none).  Layers with a long K loop and almost no
  * spatial parallelism (the low-resolution data gradients, e.g. Cin = 750 at 9x16) split their input-channel range over
  * work items; pass a buffer of this size in `partial` and bnerv_conv_igemm finishes with a deterministic slab reduction.
@@ -264,6 +284,15 @@ typedef struct {
 
 size_t bnerv_conv_wgrad_ws_bytes(int B, int Cin, int Cout, int H, int W, int k);
 int bnerv_conv_wgrad(void* stream, const bnerv_wgrad_desc* d);
+/* The BNERV_WGRAD_FAM_* id that bnerv_conv_wgrad(d) runs (host query, additive to ABI 9; -1 for a descriptor without positive dimensions
+ * or with k other than 1 or 3) and, in *n_slabs (may be NULL), the slabs that family writes into `ws` (0 for STEM: dw / db directly). */
+#define BNERV_WGRAD_FAM_STEM 0          /* image of <= 256 pixels, >= 64 output channels (csrc/stem.hip) */
+#define BNERV_WGRAD_FAM_GEMM1X1 1       /* k = 1 with >= 16 channels on both sides: a GEMM over the pixels (csrc/wgrad1.hip) */
+#define BNERV_WGRAD_FAM_LEAN 2          /* <= 16 output channels, <= 12 (k = 3) / 15 (k = 1) input channels */
+#define BNERV_WGRAD_FAM_WIDE_BF16 3     /* > 16 output channels on split bf16 */
+#define BNERV_WGRAD_FAM_WIDE_F32 4      /* the other stride-1 3x3 layers with aligned rows */
+#define BNERV_WGRAD_FAM_GENERIC 5
+int bnerv_conv_wgrad_family(const bnerv_wgrad_desc* d, int* n_slabs);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * 5x5 'same' convolution family of the HNeRV baseline decoder (csrc/conv5.hip; additive to ABI 9).  Replaces the F.conv2d of
@@ -440,6 +469,17 @@ int bnerv_psnr(void* stream, const float* out, const float* gt, float* psnr, voi
  * deferred -- defer_finish with a context -- and both must name the same context).  Returns BNERV_OK when the pair was launched, 1 when
  * this pair is not one the launch takes (issue the two calls separately, weight gradient first), negative BNERV_E_* on error. */
 int bnerv_conv_wgrad_pair(void* stream, const bnerv_conv_desc* conv, const bnerv_wgrad_desc* wgrad);
+/* The form bnerv_conv_wgrad_pair(conv, wgrad) launches (host query, additive to ABI 9), BNERV_PAIR_NONE where it returns 1 or an error;
+ * *conv_rows (may be NULL): the rows the conv half of that form writes into conv->partial ([R][B][2][Cout], sums epilogues), 0 for NONE.
+ * The launch refuses (returns 1) a form whose rows differ from bnerv_conv_partial_rows(conv), which sized the caller's buffer; the query
+ * reports NONE there.  A form that declines late for want of scratch (BF16_WIDE) lets the launch go on to a later form. */
+#define BNERV_PAIR_NONE (-1)
+#define BNERV_PAIR_STEM 0               /* form 0: the stem stage's weight and data gradient (csrc/stem.hip) */
+#define BNERV_PAIR_Q4_LEAN 1            /* form 1: the <= 12-channel conv next to the lean weight gradient (interleaved, shared-tile or fold) */
+#define BNERV_PAIR_SMALL_WIDE 2         /* form 2: the low-resolution conv (4x16 tiles) next to a wide weight gradient */
+#define BNERV_PAIR_BF16_WIDE 3          /* form 3: the wide split conv next to the wide split weight gradient */
+#define BNERV_PAIR_HEAD 4               /* form H: the 1x1 output head's backward as one streaming pass */
+int bnerv_conv_wgrad_pair_form(const bnerv_conv_desc* conv, const bnerv_wgrad_desc* wgrad, int* conv_rows);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Fused multi-tensor Adan step.  Replaces Adan.step -> _multi_tensor_adan (optimizer.py:125-235, :296-362), i.e. the

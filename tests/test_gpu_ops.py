@@ -352,6 +352,91 @@ def test_tat_block_backward_on_the_shared_tile_pair(ops, shape, monkeypatch):
         close(a, c, msg=f"tat d{n}: fold form vs transforming form")
 
 
+# (channels, H, W, sums epilogue, {environment}, the form bnerv_conv_wgrad_pair_form must name).  B = 1.
+# The three form-1 cases differ in the KERNEL of that form only (interleaved roles / shared tile with the fold / shared tile transforming),
+# which the form query does not tell apart: the switches select it, and the kernel trace is where it shows.  The fold form needs slabs of
+# ncols + 8 columns: 16 blocks x 12 channels x (12 * 9 + 1 + 8 = 117) x 4 bytes = 89856 bytes here, against the 209280 bytes that
+# bnerv_conv_wgrad_ws_bytes(1, 12, 12, 48, 96, 3) asks for -- so the fold is not silently downgraded for want of workspace at this size.
+_PAIR_CASES = [
+    (12, 48, 96, "dgelu_saved", {}, "q4_lean"),                                                   # form 1, roles interleaved
+    (12, 48, 96, "dgelu_saved", {"BNERV_PAIR_FUSED": "8", "BNERV_PAIR_FOLD": "1"}, "q4_lean"),    # form 1, shared tile, fold
+    (12, 48, 96, "dgelu_saved", {"BNERV_PAIR_FUSED": "8", "BNERV_PAIR_FOLD": "0"}, "q4_lean"),    # form 1, shared tile, transforming
+    (15, 9, 16, "dgelu_saved", {}, "small_wide"),                                                 # form 2, f32 wide role
+    (15, 12, 20, "dgelu_saved", {}, "small_wide"),                                                # (edge tiles in both directions)
+    (15, 12, 20, "dsin", {}, "small_wide"),
+    (30, 32, 128, "dgelu_saved", {}, "small_wide"),                                               # form 2, bf16 role: 16 8x32 tiles, the bound of that role
+    (30, 36, 132, "dgelu_saved", {}, "small_wide"),                                               # 25 tiles, edge tiles
+    (30, 36, 132, "dsin", {}, "small_wide"),
+    (30, 9, 16, "dgelu_saved", {}, "none"),                                                       # declined: the two stand-alone launches
+]
+
+
+@pytest.mark.parametrize("case", _PAIR_CASES, ids=lambda c: "-".join(map(str, c[:4])) + "".join(f"-{k[6:].lower()}{v}" for k, v in c[4].items()))
+def test_partial_buffer_sized_by_the_library_fits_the_pair_that_runs(ops, case, monkeypatch):
+    """tests/test_gpu_alignment.py test_partial_buffer_sized_by_the_library_fits_the_kernel_that_runs, for the paired launch: ONE
+    bnerv_conv_wgrad_pair call with the descriptors ops._wgrad_conv_pair builds for a TAT conv's backward (the affine weight gradient's
+    input is the epilogue's raw operand), `partial` sized by bnerv_conv_partial_rows plus one NaN guard row.  Whatever form takes the pair,
+    its conv half writes exactly the rows the query promised: every asked-for row finite, the guard row still NaN, and out, the summed
+    rows, dw and db match float64.  bnerv_conv_wgrad_pair_form names the form the case is about; a declined pair (rc 1) takes the two
+    stand-alone launches under the same assertions."""
+    import ctypes as C
+    from boosting_nerv_amd import _lib as L
+    Cc, H, W, ep, env, want_form = case
+    for k in ("BNERV_PAIR_FUSED", "BNERV_PAIR_FOLD"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    lib = L.load()
+    gen = torch.Generator().manual_seed(1000 + Cc + H)
+    rnd = lambda *sh, sc=1.0: torch.randn(*sh, generator=gen) * sc
+    g, w, raw = rnd(1, Cc, H, W), rnd(Cc, Cc, 3, 3, sc=1 / math.sqrt(9 * Cc)), rnd(1, Cc, H, W)       # incoming gradient, weights, the layer's raw input
+    a_mul, a_add, a_gate = torch.rand(1, Cc, H, W, generator=gen), rnd(1, Cc, H, W), torch.rand(1, Cc, H, W, generator=gen)
+    sc, sh = rnd(1, Cc, 1, 1, sc=0.5), rnd(1, Cc, 1, 1, sc=0.5)
+    # float64: v = d/d(input) of conv(., w); the epilogue; the channel sums (ds, dt); dw / db of conv(raw * (1 + sc) + sh, w) under cotangent g
+    v = F.conv_transpose2d(g.double(), w.double(), padding=1)
+    if ep == "dgelu_saved":                                 # aux0 = saved gelu', aux1 = saved gelu (the raw operand)
+        ref_out = v * (1 + sc.double()) * a_mul.double()
+    else:                                                   # aux0 = the raw operand, aux1 added, aux2 the gate
+        ref_out = (a_add.double() + v * (1 + sc.double())) * a_gate.double()
+    ref_sum = torch.stack([(v * raw.double()).sum((2, 3)), v.sum((2, 3))], 1)
+    w64, b64 = w.double().requires_grad_(True), torch.zeros(Cc, dtype=torch.float64, requires_grad=True)
+    ref_dw, ref_db = torch.autograd.grad(F.conv2d(raw.double() * (1 + sc.double()) + sh.double(), w64, b64, padding=1), [w64, b64], g.double())
+    gd, wd_, rawd, muld, addd, gated, scd, shd = (t.to(DEV) for t in (g, w, raw, a_mul, a_add, a_gate, sc, sh))
+    out = torch.full((1, Cc, H, W), float("nan"), device=DEV)
+    dw, db = torch.full((Cc, Cc, 3, 3), float("nan"), device=DEV), torch.full((Cc,), float("nan"), device=DEV)
+    aux = dict(aux0=muld, aux1=rawd) if ep == "dgelu_saved" else dict(aux0=rawd, aux1=addd, aux2=gated)
+    cd = ops._conv_desc(gd, wd_, None, out, B=1, Cin=Cc, Cout=Cc, H=H, W=W, k=3, in_mode=L.IN_PLAIN, transposed=1, scale=scd,
+                        ep_mode=L.EP_DGELU_SAVED if ep == "dgelu_saved" else L.EP_DSIN, **aux)
+    nbytes = lib.bnerv_conv_wgrad_ws_bytes(1, Cc, Cc, H, W, 3)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=DEV)
+    wgd = ops._wgrad_desc(rawd, gd, dw, db, ws, nbytes, B=1, Cin=Cc, Cout=Cc, H=H, W=W, k=3, in_mode=L.IN_AFFINE, g_mode=L.IN_UNSHUFFLE,
+                          scale=scd, shift=shd, defer=True)
+    rows = lib.bnerv_conv_partial_rows(C.byref(cd))
+    part = torch.full((rows + 1, 1, 2, Cc), float("nan"), device=DEV)
+    cd.partial = part.data_ptr()
+    form_rows = C.c_int(-1)
+    form = lib.bnerv_conv_wgrad_pair_form(C.byref(cd), C.byref(wgd), C.byref(form_rows))
+    assert ("none" if form < 0 else L.PAIR_FORM[form]) == want_form
+    assert form_rows.value == (0 if want_form == "none" else rows)
+    assert rows == (lib.bnerv_conv_tiles(H, W) if want_form == "q4_lean" else ((H + 3) // 4) * ((W + 15) // 16))
+    rc = lib.bnerv_conv_wgrad_pair(L.stream(), C.byref(cd), C.byref(wgd))
+    if want_form == "none":
+        assert rc == 1
+        L.check(lib.bnerv_conv_wgrad(L.stream(), C.byref(wgd)), "bnerv_conv_wgrad")
+        L.check(lib.bnerv_conv_igemm(L.stream(), C.byref(cd)), "bnerv_conv_igemm")
+    else:
+        L.check(rc, "bnerv_conv_wgrad_pair")
+    ops._flush_deferred()
+    torch.cuda.synchronize()
+    assert torch.isnan(part[rows]).all(), "the pair's conv half wrote past the rows the library asked for"
+    assert torch.isfinite(part[:rows]).all(), "a row the library asked for was never written"
+    tag = f"pair {want_form} {ep} {Cc}x{H}x{W}"
+    close(out, ref_out.float(), msg=f"{tag} out")
+    close(part[:rows].double().sum(0), ref_sum.float(), msg=f"{tag} sums")
+    close(dw, ref_dw.float(), msg=f"{tag} dw")
+    close(db, ref_db.float(), msg=f"{tag} db")
+
+
 @pytest.mark.parametrize("case", [(1, 12, 12, 16, 64, 3, 1), (2, 12, 12, 9, 33, 3, 2), (1, 30, 15, 9, 16, 3, 5), (1, 20, 33, 6, 9, 1, 2), (1, 9, 7, 5, 6, 3, 3),
                                   (1, 20, 20, 24, 36, 3, 3), (1, 40, 38, 16, 32, 3, 2)])
 def test_snerv_block(ops, case):
