@@ -12,6 +12,7 @@
 //   ms_coef         ms_ssim per (b,c) and d(loss)/d(level statistic)
 //   ssim_bwd        per level, coarse -> fine: recompute the statistics for a haloed tile, differentiate, apply the adjoint
 //                   Gaussian, add the upsampled coarser-level gradient; level 0 also adds the L1/L2 terms and writes `grad`
+//   (the three FFT kernels are wrappers here; plans, tables, butterflies and the row / column bodies live in fft_body.h)
 //   fft_rows_fwd    in-place mixed-radix DIF FFT of every row in LDS (digit-reversed output order -- irrelevant, see below)
 //   fft_cols        column DIF FFT, sum(|Re|+|Im|), S = sign(F), then the ADJOINT transform of S, all in LDS
 //   fft_rows_adj    adjoint row transform, real part, accumulated into `grad`
@@ -508,475 +509,11 @@ __global__ __launch_bounds__(256) void ssim_bwd_coarse_all_kernel(const SsimAllA
     ssim_bwd_coarse_body(a, sl, (int)(blockIdx.x + gridDim.x * blockIdx.y), (int)gridDim.x, (int)gridDim.y);
 }
 
-// =====================================================================================================================
-// mixed-radix FFT in LDS
-// =====================================================================================================================
-constexpr int MAXRAD = 16;
-struct FftPlan { int N, nrad; int rad[MAXRAD]; const float2* tw; const int* pos; };   // tw[k] = exp(-2*pi*i*k/N)
-// pos[f] = buffer position that holds frequency f after the in-place DIF forward (mixed-radix digit reversal)
-
-std::mutex g_tw_mutex;
-std::map<int, float2*> g_tw;
-
-static const float2* get_twiddles(int N) {
-    std::lock_guard<std::mutex> lk(g_tw_mutex);
-    auto it = g_tw.find(N);
-    if (it != g_tw.end()) return it->second;
-    float2* h = (float2*)malloc(sizeof(float2) * N);
-    for (int k = 0; k < N; ++k) {
-        const double ang = -2.0 * M_PI * (double)k / (double)N;
-        h[k].x = (float)cos(ang);
-        h[k].y = (float)sin(ang);
-    }
-    float2* d = nullptr;
-    if (hipMalloc(&d, sizeof(float2) * N) != hipSuccess) { free(h); return nullptr; }
-    if (hipMemcpy(d, h, sizeof(float2) * N, hipMemcpyHostToDevice) != hipSuccess) { free(h); return nullptr; }
-    free(h);
-    g_tw[N] = d;
-    return d;
-}
-
-std::map<int, int*> g_pos;
-// forward DIF with radices [R, rest] on size Ns: frequency k = q + R*k' ends up in sub-block q (size M = Ns/R) at the position
-// the rest of the plan gives k'  =>  pos(k) = (k % R) * M + pos_rest(k / R)
-static const int* get_positions(const FftPlan& pl) {
-    std::lock_guard<std::mutex> lk(g_tw_mutex);
-    auto it = g_pos.find(pl.N);
-    if (it != g_pos.end()) return it->second;
-    std::vector<int> h(pl.N);
-    for (int f = 0; f < pl.N; ++f) {
-        int k = f, Ns = pl.N, p = 0;
-        for (int st = 0; st < pl.nrad; ++st) {
-            const int R = pl.rad[st], M = Ns / R;
-            p += (k % R) * M;
-            k /= R;
-            Ns = M;
-        }
-        h[f] = p;
-    }
-    int* d = nullptr;
-    if (hipMalloc(&d, sizeof(int) * pl.N) != hipSuccess) return nullptr;
-    if (hipMemcpy(d, h.data(), sizeof(int) * pl.N, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    g_pos[pl.N] = d;
-    return d;
-}
-
-// maxr: the largest prime the caller's kernels hold register arrays for (butterfly_generic<.., MAXR>)
-static bool make_plan(int N, FftPlan* p, int maxr = BNERV_FFT_MAX_RADIX) {
-    p->N = N; p->nrad = 0;
-    int n = N;
-    auto push = [&](int r) { if (p->nrad < MAXRAD) p->rad[p->nrad++] = r; };
-    while (n % 4 == 0) { push(4); n /= 4; }
-    while (n % 2 == 0) { push(2); n /= 2; }
-    while (n % 3 == 0) { push(3); n /= 3; }
-    while (n % 5 == 0) { push(5); n /= 5; }
-    for (int r = 7; r <= maxr && n > 1; r += 2)
-        while (n % r == 0) { push(r); n /= r; }
-    if (n != 1 || p->nrad >= MAXRAD) return false;
-    if (N == 1) { p->nrad = 0; }
-    p->tw = get_twiddles(N);
-    p->pos = get_positions(*p);
-    return p->tw != nullptr && p->pos != nullptr;
-}
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return float2{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ float2 cmulc(float2 a, float2 b) { return float2{a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y}; }   // a * conj(b)
-
-// One butterfly of radix R at sub-transform size Ns (M = Ns/R) on the in-place buffer.
-//  forward (DIF):  y_q = w_Ns^{jq} * sum_m x_m w_R^{mq}             x_m = buf[base+m*M], y_q -> buf[base+q*M]
-//  adjoint      :  x_m = sum_q conj(w_R^{mq}) conj(w_Ns^{jq}) y_q   (exact conjugate transpose of the forward stage)
-// Radix 2/3/4/5 cores use the closed forms (adds, +-i swaps, two or four real constants): the kernels are instruction-bound, and
-// a table-driven core costs ~300 instructions per radix-4 butterfly against ~50 here.  SGN = -1 forward, +1 adjoint: the
-// adjoint core is the forward core with i -> -i, i.e. the exact conjugate transpose with the same constants.
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return float2{a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return float2{a.x - b.x, a.y - b.y}; }
-template <int SGN> __device__ __forceinline__ float2 mul_i(float2 a) { return SGN > 0 ? float2{-a.y, a.x} : float2{a.y, -a.x}; }   // (SGN*i) * a
-
-template <int R, int SGN>
-__device__ __forceinline__ void dft_core(const float2 (&v)[R], float2 (&o)[R]) {
-    if constexpr (R == 2) {
-        o[0] = cadd(v[0], v[1]);
-        o[1] = csub(v[0], v[1]);
-    } else if constexpr (R == 4) {
-        const float2 a = cadd(v[0], v[2]), b = csub(v[0], v[2]), c = cadd(v[1], v[3]), dd = mul_i<SGN>(csub(v[1], v[3]));
-        o[0] = cadd(a, c); o[2] = csub(a, c); o[1] = cadd(b, dd); o[3] = csub(b, dd);
-    } else if constexpr (R == 3) {
-        constexpr float C = 0.86602540378443864676f;                       // sin(2 pi / 3)
-        const float2 sum = cadd(v[1], v[2]), t = mul_i<SGN>(csub(v[1], v[2]));
-        const float2 h = float2{v[0].x - 0.5f * sum.x, v[0].y - 0.5f * sum.y};
-        o[0] = cadd(v[0], sum);
-        o[1] = float2{h.x + C * t.x, h.y + C * t.y};
-        o[2] = float2{h.x - C * t.x, h.y - C * t.y};
-    } else {                                                               // R == 5
-        constexpr float C1 = 0.30901699437494742410f, C2 = -0.80901699437494742410f;   // cos(2 pi / 5), cos(4 pi / 5)
-        constexpr float S1 = 0.95105651629515357212f, S2 = 0.58778525229247312917f;    // sin(2 pi / 5), sin(4 pi / 5)
-        const float2 s1 = cadd(v[1], v[4]), s2 = cadd(v[2], v[3]), d1 = csub(v[1], v[4]), d2 = csub(v[2], v[3]);
-        const float2 a1 = float2{v[0].x + C1 * s1.x + C2 * s2.x, v[0].y + C1 * s1.y + C2 * s2.y};
-        const float2 a2 = float2{v[0].x + C2 * s1.x + C1 * s2.x, v[0].y + C2 * s1.y + C1 * s2.y};
-        const float2 b1 = mul_i<SGN>(float2{S1 * d1.x + S2 * d2.x, S1 * d1.y + S2 * d2.y});
-        const float2 b2 = mul_i<SGN>(float2{S2 * d1.x - S1 * d2.x, S2 * d1.y - S1 * d2.y});
-        o[0] = float2{v[0].x + s1.x + s2.x, v[0].y + s1.y + s2.y};
-        o[1] = cadd(a1, b1); o[4] = csub(a1, b1); o[2] = cadd(a2, b2); o[3] = csub(a2, b2);
-    }
-}
-
-template <int R, bool ADJ>
-__device__ __forceinline__ void butterfly(float2* buf, int base, int M, int j, int tstride /* N/Ns */, const FftPlan& pl, const float2* tw) {
-    float2 v[R], o[R];
-    (void)pl;
-#pragma unroll
-    for (int m = 0; m < R; ++m) v[m] = buf[base + __mul24(m, M)];
-    const int t1 = __mul24(tstride, j);                   // j < Ns/R: t1 * q < N for q < R, no wrap
-    if (ADJ) {
-#pragma unroll
-        for (int q = 1; q < R; ++q) v[q] = cmulc(v[q], tw[t1 * q]);
-        dft_core<R, +1>(v, o);
-    } else {
-        dft_core<R, -1>(v, o);
-#pragma unroll
-        for (int q = 1; q < R; ++q) o[q] = cmul(o[q], tw[t1 * q]);
-    }
-#pragma unroll
-    for (int q = 0; q < R; ++q) buf[base + __mul24(q, M)] = o[q];
-}
-
-// generic radix (primes 7..MAXR: BNERV_FFT_MAX_RADIX, or SSIM_FFT_MAX_RADIX in the single-scale SSIM path's own instantiations): O(R^2) with the table, operands staged in registers one output at a time
-template <bool ADJ, int MAXR>
-__device__ void butterfly_generic(float2* buf, int base, int M, int j, int tstride, int R, const FftPlan& pl, const float2* tw) {
-    float2 v[MAXR], o[MAXR];
-    const int rstep = pl.N / R;
-    for (int m = 0; m < R; ++m) {
-        v[m] = buf[base + m * M];
-        if (ADJ && m) v[m] = cmulc(v[m], tw[tstride * j * m]);
-    }
-    for (int q = 0; q < R; ++q) {
-        float2 s = v[0];
-        for (int m = 1; m < R; ++m) {
-            const float2 w = tw[rstep * ((m * q) % R)];
-            const float2 t = ADJ ? cmulc(v[m], w) : cmul(v[m], w);
-            s.x += t.x; s.y += t.y;
-        }
-        if (!ADJ && q) s = cmul(s, tw[tstride * j * q]);
-        o[q] = s;
-    }
-    for (int q = 0; q < R; ++q) buf[base + q * M] = o[q];
-}
-
-// all butterflies of one stage, radix R known at compile time.  A thread's butterflies (2-3 per stage at 720 / 1280 points) are
-// independent: the loop is unrolled by UNR so that their LDS reads are in flight together instead of one round trip per butterfly.
-template <int R, bool ADJ>
-__device__ __forceinline__ void fft_stage_r(float2* buf, int nlines, int lstride, int Ns, const FftPlan& pl, const float2* tw) {
-    const int N = pl.N, M = Ns / R, per_line = N / R, tstride = N / Ns;
-    // index split by reciprocal multiplication (operands < 2^20, quotients < 2^11: the +0.5 margin dwarfs the rounding error) and
-    // 24-bit multiplies: a runtime integer division costs ~40 instructions and a 32-bit multiply issues at quarter rate, and this
-    // loop is instruction-latency bound (a few butterflies per thread per stage)
-    const float inv_pl = 1.0f / (float)per_line, inv_M = 1.0f / (float)M;
-    const int total = nlines * per_line;
-    constexpr int UNR = ADJ ? 2 : 3;                       // (measured: the forward row pass 26 us at 3 / 35 at 2, the adjoint row pass 21 at 3 / 18 at 2; columns indifferent)
-    for (int bf0 = threadIdx.x; bf0 < total; bf0 += UNR * blockDim.x) {
-        float2 v[UNR][R], o[UNR][R];
-        int base[UNR], t1[UNR];
-        bool on[UNR];
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) {
-            const int bf = bf0 + u * blockDim.x;
-            on[u] = bf < total;
-            const int bfc = on[u] ? bf : 0;
-            const int line = (int)(((float)bfc + 0.5f) * inv_pl), rem = bfc - __mul24(line, per_line);
-            const int blk = (int)(((float)rem + 0.5f) * inv_M), j = rem - __mul24(blk, M);
-            base[u] = __mul24(line, lstride) + __mul24(blk, Ns) + j;
-            t1[u] = __mul24(tstride, j);                   // j < Ns/R: t1 * q < N for q < R, no wrap
-#pragma unroll
-            for (int m = 0; m < R; ++m) v[u][m] = buf[base[u] + __mul24(m, M)];
-        }
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) {
-            if (ADJ) {
-#pragma unroll
-                for (int q = 1; q < R; ++q) v[u][q] = cmulc(v[u][q], tw[t1[u] * q]);
-                dft_core<R, +1>(v[u], o[u]);
-            } else {
-                dft_core<R, -1>(v[u], o[u]);
-#pragma unroll
-                for (int q = 1; q < R; ++q) o[u][q] = cmul(o[u][q], tw[t1[u] * q]);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) {
-            if (on[u]) {
-#pragma unroll
-                for (int q = 0; q < R; ++q) buf[base[u] + __mul24(q, M)] = o[u][q];
-            }
-        }
-    }
-    __syncthreads();
-}
-
-template <bool ADJ, int MAXR>
-__device__ void fft_stage(float2* buf, int nlines, int lstride, int Ns, int R, const FftPlan& pl, const float2* tw) {
-    switch (R) {
-        case 2: fft_stage_r<2, ADJ>(buf, nlines, lstride, Ns, pl, tw); return;
-        case 3: fft_stage_r<3, ADJ>(buf, nlines, lstride, Ns, pl, tw); return;
-        case 4: fft_stage_r<4, ADJ>(buf, nlines, lstride, Ns, pl, tw); return;
-        case 5: fft_stage_r<5, ADJ>(buf, nlines, lstride, Ns, pl, tw); return;
-        default: break;
-    }
-    const int N = pl.N, M = Ns / R, per_line = N / R, tstride = N / Ns;
-    const float inv_pl = 1.0f / (float)per_line, inv_M = 1.0f / (float)M;
-    for (int bf = threadIdx.x; bf < nlines * per_line; bf += blockDim.x) {
-        const int line = (int)(((float)bf + 0.5f) * inv_pl), rem = bf - __mul24(line, per_line);
-        const int blk = (int)(((float)rem + 0.5f) * inv_M), j = rem - __mul24(blk, M);
-        const int base = __mul24(line, lstride) + __mul24(blk, Ns) + j;
-        butterfly_generic<ADJ, MAXR>(buf, base, M, j, tstride, R, pl, tw);
-    }
-    __syncthreads();
-}
-
-// `tw`: the plan's twiddle table (and, for the row kernels, the frequency -> buffer position table) copied to LDS.  The copy is split
-// into an issue half (global loads into registers, up to TAB_U per thread) and a commit half (LDS stores), so that a kernel can put its
-// own input loads between the two: ONE memory round trip for tables and data instead of one per loop iteration (these blocks are a
-// single latency chain each -- there is about one transform line per SIMD on the chip -- so every round trip shows in the launch).
-constexpr int TAB_U = 8;
-struct TabRegs { float2 t[TAB_U]; int p[TAB_U]; };
-template <bool POS>
-__device__ __forceinline__ void tables_issue(TabRegs& r, const FftPlan& pl) {
-#pragma unroll
-    for (int u = 0; u < TAB_U; ++u) {
-        const int i = threadIdx.x + u * blockDim.x;
-        r.t[u] = i < pl.N ? pl.tw[i] : float2{0.f, 0.f};
-        if (POS) r.p[u] = i < pl.N ? pl.pos[i] : 0;
-    }
-}
-template <bool POS>
-__device__ __forceinline__ void tables_commit(const TabRegs& r, float2* tw, int* lpos, const FftPlan& pl) {
-#pragma unroll
-    for (int u = 0; u < TAB_U; ++u) {
-        const int i = threadIdx.x + u * blockDim.x;
-        if (i < pl.N) { tw[i] = r.t[u]; if (POS) lpos[i] = r.p[u]; }
-    }
-    for (int i = threadIdx.x + TAB_U * blockDim.x; i < pl.N; i += blockDim.x) { tw[i] = pl.tw[i]; if (POS) lpos[i] = pl.pos[i]; }   // (N > 2048)
-}
-template <int MAXR = BNERV_FFT_MAX_RADIX>
-__device__ void fft_forward(float2* buf, int nlines, int lstride, const FftPlan& pl, const float2* tw) {
-    int Ns = pl.N;
-    for (int s = 0; s < pl.nrad; ++s) { fft_stage<false, MAXR>(buf, nlines, lstride, Ns, pl.rad[s], pl, tw); Ns /= pl.rad[s]; }
-}
-template <int MAXR = BNERV_FFT_MAX_RADIX>
-__device__ void fft_adjoint(float2* buf, int nlines, int lstride, const FftPlan& pl, const float2* tw) {
-    int Ns = 1;
-    for (int s = pl.nrad - 1; s >= 0; --s) { Ns *= pl.rad[s]; fft_stage<true, MAXR>(buf, nlines, lstride, Ns, pl.rad[s], pl, tw); }
-}
-
-// The row transforms work on PAIRS of real rows: z = a + i b is ONE complex transform, and the two real rows' spectra are its
-// Hermitian and anti-Hermitian parts, A[f] = (Z[f] + conj Z[W - f]) / 2, B[f] = (Z[f] - conj Z[W - f]) / (2 i).  The adjoint pass is the
-// same idea backwards: a row's gradient is Re(F^H G) of its mirrored spectrum G, which only sees G's Hermitian part (the entries
-// f = 0 and f = W / 2 enter with their real parts), so F^H (G_a + i G_b) = grad_a + i grad_b.  Half the butterflies of the
-// row-by-row form (these kernels are instruction-bound) for the same HBM traffic.
-#ifndef BNERV_FFT_LINES
-#define BNERV_FFT_LINES 1
-#endif
-constexpr int LINES_PER_BLOCK = BNERV_FFT_LINES;            // complex lines (row pairs) per block
-constexpr int ROWS_PER_BLOCK = 2 * LINES_PER_BLOCK;
-static_assert(LINES_PER_BLOCK == 1 || LINES_PER_BLOCK == 2, "the staging loops of the row kernels split their index into at most two lines");
-constexpr int ROW_U = LINES_PER_BLOCK == 1 ? 5 : 4;         // input elements per thread and batch (1280 points on 256 threads: one batch)
-constexpr int COLS_PER_BLOCK = 4;
-
-struct FftArgs {
-    const float* pred; const float* target;
-    float2* T;            // [BC][H][Wh] complex workspace: the input is real, so only the Wh = W/2 + 1 non-redundant columns of the
-                          // row transform are kept (natural frequency order); the others are their conjugate mirrors
-    int Wh;
-    float* partial;       // [BC][ncolblk]
-    float* grad;          // [BC][H][W]
-    int BC, H, W;
-    float gscale;         // c_fft / (B*C*H*W*2)
-    int accumulate;       // rows_adj: grad += (1) or grad = (0)
-    FftPlan prow, pcol;
-};
-
-template <int MAXR = BNERV_FFT_MAX_RADIX>
-__device__ __forceinline__ void fft_rows_fwd_body(const FftArgs& a, const int bx) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float2* buf = reinterpret_cast<float2*>(sm);
-    const int W = a.W;
-    const size_t row0 = (size_t)bx * ROWS_PER_BLOCK;                    // global row index over BC*H
-    const size_t nrows = (size_t)a.BC * a.H;
-    const int nl = (int)min((size_t)ROWS_PER_BLOCK, nrows - row0);
-    const int nlines = (nl + 1) >> 1;                                    // complex lines: rows (2 l, 2 l + 1) -> real / imaginary part
-    float2* tw = buf + LINES_PER_BLOCK * W;
-    int* lpos = reinterpret_cast<int*>(tw + W);
-    TabRegs tr;
-    tables_issue<true>(tr, a.prow);
-    bool tabs_done = false;
-    for (int i0 = threadIdx.x; i0 < nlines * W; i0 += blockDim.x * ROW_U) {   // 4 ROW_U loads in flight per thread (+ the tables), then the LDS stores
-        float pa[ROW_U], ta[ROW_U], pb[ROW_U], tb[ROW_U];
-#pragma unroll
-        for (int u = 0; u < ROW_U; ++u) {
-            const int i = i0 + u * blockDim.x;
-            const int line = (LINES_PER_BLOCK > 1 && i >= W) ? 1 : 0, x = i - line * W;
-            const bool oka = i < nlines * W, okb = oka && 2 * line + 1 < nl;
-            const size_t o = (row0 + 2 * line) * W + x;
-            pa[u] = oka ? a.pred[o] : 0.f;     ta[u] = oka ? a.target[o] : 0.f;
-            pb[u] = okb ? a.pred[o + W] : 0.f; tb[u] = okb ? a.target[o + W] : 0.f;
-        }
-        if (!tabs_done) { tables_commit<true>(tr, tw, lpos, a.prow); tabs_done = true; }
-#pragma unroll
-        for (int u = 0; u < ROW_U; ++u) {
-            const int i = i0 + u * blockDim.x;
-            if (i < nlines * W) buf[i] = float2{pa[u] - ta[u], pb[u] - tb[u]};
-        }
-    }
-    if (!tabs_done) tables_commit<true>(tr, tw, lpos, a.prow);            // (a thread without input elements still owns table entries)
-    __syncthreads();
-    fft_forward<MAXR>(buf, nlines, W, a.prow, tw);
-    const int Wh = a.Wh;
-    for (int i = threadIdx.x; i < nl * Wh; i += blockDim.x) {
-        const int row = i / Wh, f = i - row * Wh;
-        const float2* ln = buf + (row >> 1) * W;
-        const float2 z = ln[lpos[f]], m = ln[lpos[f == 0 ? 0 : W - f]];
-        // even row: (Z[f] + conj Z[W - f]) / 2;  odd row: (Z[f] - conj Z[W - f]) / (2 i)
-        a.T[(row0 + row) * Wh + f] = (row & 1) ? float2{0.5f * (z.y + m.y), 0.5f * (m.x - z.x)} : float2{0.5f * (z.x + m.x), 0.5f * (z.y - m.y)};
-    }
-}
+#include "fft_body.h"     // the mixed-radix LDS FFT: FftPlan, make_plan, FftArgs, fft_rows_fwd_body / fft_cols_body / fft_rows_adj_body
 __global__ __launch_bounds__(256) void fft_rows_fwd_kernel(const FftArgs a) { fft_rows_fwd_body(a, blockIdx.x); }
-
-template <int MAXR = BNERV_FFT_MAX_RADIX>
-__device__ __forceinline__ void fft_cols_body(const FftArgs& a, const int bx, const int bc, const int ncolblk) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float2* buf = reinterpret_cast<float2*>(sm);                          // [COLS_PER_BLOCK][H]
-    __shared__ float red[4];
-    const int H = a.H, W = a.Wh;                                           // W: kept columns (half spectrum)
-    const int v0 = bx * COLS_PER_BLOCK;
-    const int nc = min(COLS_PER_BLOCK, W - v0);
-    float2* T = a.T + (size_t)bc * H * W;
-    float2* tw = buf + COLS_PER_BLOCK * H;
-    TabRegs tr;
-    tables_issue<false>(tr, a.pcol);
-    bool tabs_done = false;
-    for (int i0 = threadIdx.x; i0 < H * nc; i0 += blockDim.x * 8) {       // column gather: 8 loads in flight per thread (+ the twiddles)
-        float2 v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int i = i0 + u * blockDim.x;
-            const int y = i / nc, c = i - y * nc;
-            v[u] = i < H * nc ? T[(size_t)y * W + v0 + c] : float2{0.f, 0.f};
-        }
-        if (!tabs_done) { tables_commit<false>(tr, tw, nullptr, a.pcol); tabs_done = true; }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int i = i0 + u * blockDim.x;
-            const int y = i / nc, c = i - y * nc;
-            if (i < H * nc) buf[c * H + y] = v[u];
-        }
-    }
-    if (!tabs_done) tables_commit<false>(tr, tw, nullptr, a.pcol);
-    __syncthreads();
-    fft_forward<MAXR>(buf, nc, H, a.pcol, tw);
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < H * nc; i += blockDim.x) {
-        const float2 f = buf[i];           // lines are contiguous: nc*H elements
-        const int col = v0 + i / H;        // a kept column stands for itself and for its mirror W_full - col, unless it is its own mirror
-        const float wgt = (col == 0 || 2 * col == a.W) ? 1.f : 2.f;
-        acc += wgt * (fabsf(f.x) + fabsf(f.y));
-        buf[i] = float2{(f.x > 0.f) ? 1.f : ((f.x < 0.f) ? -1.f : 0.f), (f.y > 0.f) ? 1.f : ((f.y < 0.f) ? -1.f : 0.f)};
-    }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) a.partial[(size_t)bc * ncolblk + bx] = red[0] + red[1] + red[2] + red[3];
-    if (a.grad == nullptr) return;
-    fft_adjoint<MAXR>(buf, nc, H, a.pcol, tw);
-    for (int i = threadIdx.x; i < H * nc; i += blockDim.x) {
-        const int y = i / nc, c = i - y * nc;
-        T[(size_t)y * W + v0 + c] = buf[c * H + y];
-    }
-}
 __global__ __launch_bounds__(256) void fft_cols_kernel(const FftArgs a) {      // (XCD-contiguous panels: see loss_mid_kernel)
     const int lb = xcd_remap((int)(blockIdx.x + gridDim.x * blockIdx.y), (int)(gridDim.x * gridDim.y));
     fft_cols_body(a, lb % (int)gridDim.x, lb / (int)gridDim.x, gridDim.x);
-}
-
-template <int MAXR = BNERV_FFT_MAX_RADIX>
-__device__ __forceinline__ void fft_rows_adj_body(const FftArgs& a, const int bx) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float2* buf = reinterpret_cast<float2*>(sm);
-    const int W = a.W;
-    const size_t row0 = (size_t)bx * ROWS_PER_BLOCK;
-    const size_t nrows = (size_t)a.BC * a.H;
-    const int nl = (int)min((size_t)ROWS_PER_BLOCK, nrows - row0);
-    const int nlines = (nl + 1) >> 1;
-    float2* tw = buf + LINES_PER_BLOCK * W;
-    int* lpos = reinterpret_cast<int*>(tw + W);
-    const int Wh = a.Wh;
-    TabRegs tr;
-    tables_issue<true>(tr, a.prow);
-    constexpr int AU = 4;
-    // P = G_a + i G_b of the row pair, G = kept columns + their conjugate mirrors (self-mirrored columns with their real parts), into DIF order
-    for (int i0 = threadIdx.x, first = 1; first || i0 < nlines * Wh; i0 += blockDim.x * AU, first = 0) {   // (every thread runs the first batch: it holds the barrier)
-        float2 va[AU], vb[AU];
-#pragma unroll
-        for (int u = 0; u < AU; ++u) {
-            const int i = i0 + u * blockDim.x;
-            const int line = (LINES_PER_BLOCK > 1 && i >= Wh) ? 1 : 0, f = i - line * Wh;
-            const bool oka = i < nlines * Wh, okb = oka && 2 * line + 1 < nl;
-            const size_t o = (row0 + 2 * line) * Wh + f;
-            va[u] = oka ? a.T[o] : float2{0.f, 0.f};
-            vb[u] = okb ? a.T[o + Wh] : float2{0.f, 0.f};
-        }
-        if (first) { tables_commit<true>(tr, tw, lpos, a.prow); __syncthreads(); }     // (the position table is read below)
-#pragma unroll
-        for (int u = 0; u < AU; ++u) {
-            const int i = i0 + u * blockDim.x;
-            if (i < nlines * Wh) {
-                const int line = (LINES_PER_BLOCK > 1 && i >= Wh) ? 1 : 0, f = i - line * Wh;
-                float2 ga = va[u], gb = vb[u];
-                const bool self = f == 0 || 2 * f == W;
-                if (self) { ga.y = 0.f; gb.y = 0.f; }
-                buf[line * W + lpos[f]] = float2{ga.x - gb.y, ga.y + gb.x};                       // G_a[f] + i G_b[f]
-                if (!self) buf[line * W + lpos[W - f]] = float2{ga.x + gb.y, gb.x - ga.y};         // conj G_a[f] + i conj G_b[f]
-            }
-        }
-    }
-    // the gradient this launch adds to: loaded under the transform
-    float ga[2 * ROW_U], gb[2 * ROW_U];
-    const bool one_batch = nlines * W <= 2 * ROW_U * (int)blockDim.x;
-    if (one_batch) {
-#pragma unroll
-        for (int u = 0; u < 2 * ROW_U; ++u) {
-            const int i = threadIdx.x + u * blockDim.x;
-            const int line = (LINES_PER_BLOCK > 1 && i >= W) ? 1 : 0, x = i - line * W;
-            const bool oka = i < nlines * W, okb = oka && 2 * line + 1 < nl;
-            const size_t o = (row0 + 2 * line) * W + x;
-            ga[u] = (a.accumulate && oka) ? a.grad[o] : 0.f;
-            gb[u] = (a.accumulate && okb) ? a.grad[o + W] : 0.f;
-        }
-    }
-    __syncthreads();
-    fft_adjoint<MAXR>(buf, nlines, W, a.prow, tw);
-    for (int i0 = threadIdx.x; i0 < nlines * W; i0 += blockDim.x * 2 * ROW_U) {
-        if (!one_batch) {
-#pragma unroll
-            for (int u = 0; u < 2 * ROW_U; ++u) {
-                const int i = i0 + u * blockDim.x;
-                const int line = (LINES_PER_BLOCK > 1 && i >= W) ? 1 : 0, x = i - line * W;
-                const bool oka = i < nlines * W, okb = oka && 2 * line + 1 < nl;
-                const size_t o = (row0 + 2 * line) * W + x;
-                ga[u] = (a.accumulate && oka) ? a.grad[o] : 0.f;
-                gb[u] = (a.accumulate && okb) ? a.grad[o + W] : 0.f;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 2 * ROW_U; ++u) {
-            const int i = i0 + u * blockDim.x;
-            if (i < nlines * W) {
-                const int line = (LINES_PER_BLOCK > 1 && i >= W) ? 1 : 0, x = i - line * W;
-                const size_t o = (row0 + 2 * line) * W + x;
-                const float2 r = buf[i];
-                a.grad[o] = ga[u] + a.gscale * r.x;
-                if (2 * line + 1 < nl) a.grad[o + W] = gb[u] + a.gscale * r.y;
-            }
-        }
-    }
 }
 __global__ __launch_bounds__(256) void fft_rows_adj_kernel(const FftArgs a) { fft_rows_adj_body(a, blockIdx.x); }
 
@@ -1152,31 +689,35 @@ __global__ __launch_bounds__(256) void ssim_metric_kernel(const SsimFinalArgs a,
 // =====================================================================================================================
 // workspace layout
 // =====================================================================================================================
+constexpr float SSIM_C1 = 0.01f * 0.01f, SSIM_C2 = 0.03f * 0.03f;
+constexpr float MS_WEIGHTS[LV] = {0.0448f, 0.2856f, 0.3001f, 0.2363f, 0.1333f};
+
 struct WsLayout {
     size_t stats_part, pyrX[LV], pyrY[LV], dXl[LV], Gl[LV], ssim_part[LV], msval, coef, T, fft_part, total;
-    int tiles[LV];
+    int tiles_x[LV], tiles_y[LV], tiles[LV];          // statistics tiles of a level: its valid window positions in STH x STW tiles
     Pyr pyr;
-    int ncolblk;
+    int ncolblk, BC;
 };
 static size_t align64(size_t x) { return (x + 63) & ~size_t(63); }
-static WsLayout make_layout(int B, int C, int H, int W, bool use_ms, bool use_fft) {
+// levels: LV = MS-SSIM; 1 = the single-scale SSIM losses (level 0 only: three statistic-gradient maps, tile partials and the planes' values, no
+// pooled images, no coefficient array); 0 = the L1 / L2 partial sums alone (bnerv_psnr)
+static WsLayout make_layout(int B, int C, int H, int W, int levels, bool use_fft) {
     WsLayout L{};
     size_t off = 0;                                   // in floats
     auto take = [&](size_t n) { size_t o = off; off = align64(off + n); return o; };
     const size_t BC = (size_t)B * C;
+    L.BC = (int)BC;
     L.stats_part = take((size_t)B * NSB * 2);
-    L.pyr = make_pyr(H, W);
-    if (use_ms) {
-        for (int l = 0; l < LV; ++l) {
-            const size_t n = BC * L.pyr.H[l] * L.pyr.W[l];
-            if (l > 0) { L.pyrX[l] = take(n); L.pyrY[l] = take(n); L.dXl[l] = take(n); }
-            L.Gl[l] = take(3 * n);
-            L.tiles[l] = cdiv(L.pyr.H[l] - HW_, STH) * cdiv(L.pyr.W[l] - HW_, STW);
-            L.ssim_part[l] = take(BC * L.tiles[l]);
-        }
-        L.msval = take(BC);
-        L.coef = take(BC * LV);
+    if (levels) L.pyr = make_pyr(H, W);
+    for (int l = 0; l < levels; ++l) {
+        const size_t n = BC * L.pyr.H[l] * L.pyr.W[l];
+        if (l > 0) { L.pyrX[l] = take(n); L.pyrY[l] = take(n); L.dXl[l] = take(n); }
+        L.Gl[l] = take(3 * n);
+        L.tiles_x[l] = cdiv(L.pyr.W[l] - HW_, STW); L.tiles_y[l] = cdiv(L.pyr.H[l] - HW_, STH); L.tiles[l] = L.tiles_y[l] * L.tiles_x[l];
+        L.ssim_part[l] = take(BC * L.tiles[l]);
     }
+    if (levels) L.msval = take(BC);
+    if (levels == LV) L.coef = take(BC * LV);
     if (use_fft) {
         L.ncolblk = cdiv(W / 2 + 1, COLS_PER_BLOCK);
         L.T = take(BC * H * (size_t)(W / 2 + 1) * 2);
@@ -1186,35 +727,101 @@ static WsLayout make_layout(int B, int C, int H, int W, bool use_ms, bool use_ff
     return L;
 }
 
-// the single-scale SSIM losses: level 0 only -- three statistic-gradient maps, tile partials, the planes' values, the L1 / L2 and FFT scratch
-static WsLayout make_layout_ssim(int B, int C, int H, int W, bool use_fft) {
-    WsLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off = align64(off + n); return o; };
-    const size_t BC = (size_t)B * C;
-    L.stats_part = take((size_t)B * NSB * 2);
-    L.pyr.H[0] = H; L.pyr.W[0] = W;
-    L.Gl[0] = take(3 * BC * H * W);
-    L.tiles[0] = cdiv(H - HW_, STH) * cdiv(W - HW_, STW);
-    L.ssim_part[0] = take(BC * L.tiles[0]);
-    L.msval = take(BC);
-    if (use_fft) {
-        L.ncolblk = cdiv(W / 2 + 1, COLS_PER_BLOCK);
-        L.T = take(BC * H * (size_t)(W / 2 + 1) * 2);
-        L.fft_part = take(BC * L.ncolblk);
-    }
-    L.total = off;
-    return L;
-}
-// level-0 arguments of both passes; G = NULL: value only, the statistic-gradient maps are not written
-static SsimArgs fill_ssim_level0(const float* X, const float* Y, float* ws, const WsLayout& L, float* G, float* grad, float coef_k, float k_l1, float k_l2, int acc) {
+// =====================================================================================================================
+// kernel arguments: one builder per struct
+// =====================================================================================================================
+// SsimArgs of level l of (X, Y): what the layout decides, for both passes.  A site overrides only what is its own: G = NULL (value only: the
+// statistic-gradient maps are not written), coef = NULL + coef_k (single scale), k_l1 / k_l2 / acc (level 0 of a backward), and dcoarse / Hc / Wc /
+// ph / pw in the level-by-level backward ALONE -- ssim_bwd_body reads them whenever dcoarse is set; the fused forms carry the chain in CoarseChain.
+static SsimArgs level_args(const float* X, const float* Y, float* grad, float* ws, const WsLayout& L, int l) {
+    static const Win win = make_win();
     SsimArgs a{};
-    a.X = X; a.Y = Y; a.partial = ws + L.ssim_part[0]; a.G = G; a.dX = grad; a.H = L.pyr.H[0]; a.W = L.pyr.W[0];
-    a.tiles_x = cdiv(a.W - HW_, STW); a.tiles_y = cdiv(a.H - HW_, STH); a.C1 = 0.01f * 0.01f; a.C2 = 0.03f * 0.03f; a.win = make_win();
-    a.coef = nullptr; a.coef_k = coef_k; a.k_l1 = k_l1; a.k_l2 = k_l2; a.acc = acc;
+    a.X = l ? ws + L.pyrX[l] : X; a.Y = l ? ws + L.pyrY[l] : Y; a.dX = l ? ws + L.dXl[l] : grad; a.G = ws + L.Gl[l];
+    a.partial = ws + L.ssim_part[l]; a.coef = ws + L.coef + (size_t)l * L.BC;
+    a.H = L.pyr.H[l]; a.W = L.pyr.W[l]; a.tiles_x = L.tiles_x[l]; a.tiles_y = L.tiles_y[l];
+    a.C1 = SSIM_C1; a.C2 = SSIM_C2; a.win = win;
     return a;
 }
+static float inv_nvalid(const WsLayout& L, int l) { return 1.0f / ((float)(L.pyr.H[l] - HW_) * (float)(L.pyr.W[l] - HW_)); }
 
+static CoefArgs coef_args(float* ws, const WsLayout& L, float chain) {
+    CoefArgs ca{};
+    for (int l = 0; l < LV; ++l) { ca.partial[l] = ws + L.ssim_part[l]; ca.tiles[l] = L.tiles[l]; ca.inv_nvalid[l] = inv_nvalid(L, l); ca.weights[l] = MS_WEIGHTS[l]; }
+    ca.msval = ws + L.msval; ca.coef = ws + L.coef; ca.BC = L.BC; ca.chain = chain;
+    return ca;
+}
+// the pyramid and every level's statistics (one launch or one per level), of an even or an odd pyramid
+static int ms_forward_args(const float* X, const float* Y, float* ws, const WsLayout& L, bool want_g, PyrArgs& pa, SsimAllArgs& sa) {
+    pa.src[0] = X; pa.src[1] = Y; pa.planes = L.BC;
+    pa.vec2 = ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 7) == 0 ? 1 : 0;
+    int nblk = 0;
+    for (int l = 0; l < LV; ++l) {
+        pa.H[l] = L.pyr.H[l]; pa.W[l] = L.pyr.W[l];
+        if (L.pyr.H[l] <= HW_ || L.pyr.W[l] <= HW_) return bnerv_set_error(BNERV_E_ARG, "ms_ssim: level %d is %dx%d, needs > %d on both sides", l, L.pyr.H[l], L.pyr.W[l], HW_);
+        if (l > 0) { pa.dst[0][l] = ws + L.pyrX[l]; pa.dst[1][l] = ws + L.pyrY[l]; }
+        sa.lv[l] = level_args(X, Y, nullptr, ws, L, l);
+        if (!want_g) sa.lv[l].G = nullptr;
+        sa.first[l] = nblk;
+        nblk += L.tiles[l];
+    }
+    sa.first[LV] = nblk;
+    return BNERV_OK;
+}
+// the fused backward launches (the coarser levels' own terms; level 0 with the 0.25-chain over them), of an even or an odd pyramid
+static void ms_backward_args(const float* X, const float* Y, float* grad, float* ws, const WsLayout& L, float k_l1, float k_l2, int acc, SsimAllArgs& sa, CoarseChain& cc) {
+    int nblk = 0;
+    for (int l = 0; l < LV; ++l) {
+        const SsimArgs& a = sa.lv[l] = level_args(X, Y, grad, ws, L, l);
+        sa.first[l] = nblk;
+        if (l >= 1) nblk += cdiv(a.W, STW) * cdiv(a.H, STH);
+        cc.own[l] = l ? a.dX : nullptr; cc.H[l] = a.H; cc.W[l] = a.W; cc.ph[l] = a.H % 2; cc.pw[l] = a.W % 2;
+    }
+    sa.lv[0].k_l1 = k_l1; sa.lv[0].k_l2 = k_l2; sa.lv[0].acc = acc;
+    sa.first[LV] = nblk;
+    cc.n = LV - 1;
+}
+
+// a checked descriptor and what both *_fwd_bwd entry points derive from it; `who` prefixes the messages
+struct LossCall { bnerv_loss_desc d; int nps, BC; float k_l1, k_l2; };
+static int open_loss_call(const bnerv_loss_desc* dp, const char* who, LossCall& c) {
+    BNERV_REQUIRE(dp != nullptr, "%s: null descriptor", who);
+    const bnerv_loss_desc& d = c.d = *dp;
+    BNERV_REQUIRE(d.pred && d.target && d.loss_out && d.stats_out && d.ws, "%s: null tensor", who);
+    BNERV_REQUIRE((reinterpret_cast<uintptr_t>(d.ws) & 7) == 0, "%s: ws must be 8-byte aligned (the spectral term keeps its float2 spectra in it)", who);
+    BNERV_REQUIRE(d.B > 0 && d.C > 0 && d.H > 0 && d.W > 0 && d.B <= 65535, "%s: bad dims", who);
+    BNERV_REQUIRE((size_t)d.C * d.H * d.W < (size_t)1 << 31, "%s: sample too large", who);
+    c.nps = d.C * d.H * d.W; c.BC = d.B * d.C;
+    c.k_l1 = d.c_l1 / ((float)d.B * (float)c.nps); c.k_l2 = 2.0f * d.c_l2 / ((float)d.B * (float)c.nps);
+    return BNERV_OK;
+}
+// the spectral term's launch data.  maxr: the radix limit of the caller's kernel instantiations; bc_grid_y: its column launch always has B * C as grid.y
+struct FftLaunch { FftArgs a; size_t lds_row, lds_col; int nrowblk; };
+static int fft_launch_args(const LossCall& c, float* ws, const WsLayout& L, int maxr, size_t row_lds_limit, bool bc_grid_y, const char* who, FftLaunch& F) {
+    const bnerv_loss_desc& d = c.d;
+    FftArgs& a = F.a;
+    if (!make_plan(d.W, &a.prow, maxr) || !make_plan(d.H, &a.pcol, maxr))
+        return bnerv_set_error(BNERV_E_ARG, "%s: FFT size %dx%d has a prime factor > %d", who, d.H, d.W, maxr);
+    BNERV_REQUIRE(!bc_grid_y || c.BC <= 65535, "%s: B * C > 65535 with a spectral term", who);
+    a.pred = d.pred; a.target = d.target; a.T = reinterpret_cast<float2*>(ws + L.T); a.Wh = d.W / 2 + 1; a.partial = ws + L.fft_part; a.grad = d.grad;
+    a.BC = c.BC; a.H = d.H; a.W = d.W; a.gscale = d.c_fft / ((float)d.B * (float)c.nps * 2.0f); a.accumulate = 0;
+    F.lds_row = (size_t)(LINES_PER_BLOCK + 1) * d.W * sizeof(float2) + (size_t)d.W * sizeof(int); F.lds_col = (size_t)(COLS_PER_BLOCK + 1) * d.H * sizeof(float2);   // + twiddle table (+ position table)
+    BNERV_REQUIRE(F.lds_row <= row_lds_limit && F.lds_col <= 160 * 1024, "%s: frame %dx%d too large for the LDS FFT", who, d.H, d.W);
+    F.nrowblk = cdiv(c.BC * d.H, ROWS_PER_BLOCK);
+    return BNERV_OK;
+}
+// (msval, c_ms): the MS-SSIM values and coefficient, or the single-scale path's plane values and c_ss -- the same combine
+static FinalArgs final_args(const LossCall& c, float* ws, const WsLayout& L, const float* msval, float c_ms) {
+    const bnerv_loss_desc& d = c.d;
+    FinalArgs f{};
+    f.stats_part = ws + L.stats_part; f.msval = msval; f.fft_part = d.c_fft != 0.f ? ws + L.fft_part : nullptr;
+    f.loss_out = d.loss_out; f.stats_out = d.stats_out; f.B = d.B; f.C = d.C; f.n_per_sample = c.nps; f.ncolblk = L.ncolblk;
+    f.c_l1 = d.c_l1; f.c_l2 = d.c_l2; f.c_ms = c_ms; f.c_fft = d.c_fft;
+    return f;
+}
+
+// =====================================================================================================================
+// launch paths
+// =====================================================================================================================
 static bool loss_fused() {                              // BNERV_LOSS_FUSED=0: the level-by-level MS-SSIM launches (A/B switch, read per call: tests compare the forms)
     return !switch_off("BNERV_LOSS_FUSED");
 }
@@ -1227,162 +834,69 @@ static bool adj_late() {                                // BNERV_LOSS_ADJ=late: 
     const char* e = switch_str("BNERV_LOSS_ADJ");       // onto the finished SSIM gradient (A/B switch, read per call; the gradient differs in the last bit:
     return e && !strcmp(e, "late");                     // fma(k, r, d) there, d + k r here)
 }
+static bool loss_merged() {                             // BNERV_LOSS_MERGED=0: every launch of the even-pyramid form on its own (A/B switch, read per call)
+    return !switch_off("BNERV_LOSS_MERGED");
+}
 // the 2x2 means of an ODD pyramid, level by level (zero padding where a side is odd, count_include_pad)
-static int launch_pools(hipStream_t st, const float* X, const float* Y, float* ws, const WsLayout& L, int BC) {
+static int launch_pools(hipStream_t st, const float* X, const float* Y, float* ws, const WsLayout& L) {
     const float* Xl = X; const float* Yl = Y;
     for (int l = 0; l < LV - 1; ++l) {
         const int Hl = L.pyr.H[l], Wl = L.pyr.W[l], Ho = L.pyr.H[l + 1], Wo = L.pyr.W[l + 1];
-        const size_t n = (size_t)BC * Ho * Wo;
+        const size_t n = (size_t)L.BC * Ho * Wo;
         int gx = (int)((n + 255) / 256); if (gx > 4096) gx = 4096;
-        hipLaunchKernelGGL(avgpool2_kernel, dim3(gx, 1, 2), dim3(256), 0, st, Xl, Yl, ws + L.pyrX[l + 1], ws + L.pyrY[l + 1], BC, Hl, Wl, Ho, Wo, Hl % 2, Wl % 2);
+        hipLaunchKernelGGL(avgpool2_kernel, dim3(gx, 1, 2), dim3(256), 0, st, Xl, Yl, ws + L.pyrX[l + 1], ws + L.pyrY[l + 1], L.BC, Hl, Wl, Ho, Wo, Hl % 2, Wl % 2);
         BNERV_LAUNCH_CHECK("avgpool2");
         Xl = ws + L.pyrX[l + 1]; Yl = ws + L.pyrY[l + 1];
     }
     return BNERV_OK;
 }
 
-static bool loss_merged() {                             // BNERV_LOSS_MERGED=0: every launch of the even-pyramid form on its own (A/B switch, read per call)
-    return !switch_off("BNERV_LOSS_MERGED");
-}
-
-// arguments of the even-pyramid forward launches (pyramid, every level's statistics, coefficients)
-static int fill_even_forward(const float* X, const float* Y, float* ws, const WsLayout& L, int BC, float chain, bool want_g, PyrArgs& pa, SsimAllArgs& sa, CoefArgs& ca) {
-    static const float wts[LV] = {0.0448f, 0.2856f, 0.3001f, 0.2363f, 0.1333f};
-    const Win win = make_win();
-    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-    pa.src[0] = X; pa.src[1] = Y; pa.planes = BC;
-    pa.vec2 = ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 7) == 0 ? 1 : 0;
-    for (int l = 0; l < LV; ++l) {
-        pa.H[l] = L.pyr.H[l]; pa.W[l] = L.pyr.W[l];
-        if (L.pyr.H[l] <= HW_ || L.pyr.W[l] <= HW_) return bnerv_set_error(BNERV_E_ARG, "ms_ssim: level %d is %dx%d, needs > %d on both sides", l, L.pyr.H[l], L.pyr.W[l], HW_);
-        if (l > 0) { pa.dst[0][l] = ws + L.pyrX[l]; pa.dst[1][l] = ws + L.pyrY[l]; }
-    }
-    int nblk = 0;
-    for (int l = 0; l < LV; ++l) {
-        SsimArgs& a = sa.lv[l];
-        a.X = l ? ws + L.pyrX[l] : X; a.Y = l ? ws + L.pyrY[l] : Y; a.partial = ws + L.ssim_part[l]; a.H = L.pyr.H[l]; a.W = L.pyr.W[l];
-        a.G = want_g ? ws + L.Gl[l] : nullptr;
-        a.tiles_x = cdiv(a.W - HW_, STW); a.tiles_y = cdiv(a.H - HW_, STH); a.C1 = C1; a.C2 = C2; a.win = win;
-        sa.first[l] = nblk;
-        nblk += a.tiles_x * a.tiles_y;
-        ca.partial[l] = ws + L.ssim_part[l]; ca.tiles[l] = L.tiles[l];
-        ca.inv_nvalid[l] = 1.0f / ((float)(a.H - HW_) * (float)(a.W - HW_));
-        ca.weights[l] = wts[l];
-    }
-    sa.first[LV] = nblk;
-    ca.msval = ws + L.msval; ca.coef = ws + L.coef; ca.BC = BC; ca.chain = chain;
-    return BNERV_OK;
-}
-// ... and of the even-pyramid backward launches (the coarser levels' own terms; level 0 with the 0.25-chain over them)
-static void fill_even_backward(const float* X, const float* Y, float* grad, float* ws, const WsLayout& L, int BC, float k_l1, float k_l2, int acc, SsimAllArgs& sa, CoarseChain& cc) {
-    const Win win = make_win();
-    int nblk = 0;
-    for (int l = 0; l < LV; ++l) {
-        SsimArgs& a = sa.lv[l];
-        a.X = l ? ws + L.pyrX[l] : X; a.Y = l ? ws + L.pyrY[l] : Y; a.coef = ws + L.coef + (size_t)l * BC;
-        a.dX = l ? ws + L.dXl[l] : grad; a.H = L.pyr.H[l]; a.W = L.pyr.W[l]; a.C1 = 0.01f * 0.01f; a.C2 = 0.03f * 0.03f; a.win = win;
-        a.k_l1 = k_l1; a.k_l2 = k_l2; a.G = ws + L.Gl[l];
-        sa.first[l] = nblk;
-        if (l >= 1) nblk += cdiv(a.W, STW) * cdiv(a.H, STH);
-        cc.own[l] = l ? ws + L.dXl[l] : nullptr; cc.H[l] = a.H; cc.W[l] = a.W; cc.ph[l] = a.H % 2; cc.pw[l] = a.W % 2;
-    }
-    sa.lv[0].acc = acc;
-    sa.first[LV] = nblk;
-    cc.n = LV - 1;
-}
-
-static int run_ms_forward(hipStream_t st, const float* X, const float* Y, float* ws, const WsLayout& L, int B, int C, float chain, bool want_g) {
-    const int BC = B * C;
-    const Win win = make_win();
-    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+// The pyramid, the statistics, the coefficients.  Fused: 3 launches on an even pyramid, 6 on an odd one (1080 -> 540 -> 270 -> 135 -> 68: the
+// padded 2x2 means stay a launch per level) -- every level's statistics share ONE launch, the same body per tile as the level-by-level launches.
+// BNERV_LOSS_FUSED=0: a statistics launch per level, 10 launches; level l's statistics read only level l's images, so the pools may all go first.
+static int run_ms_forward(hipStream_t st, const float* X, const float* Y, float* ws, const WsLayout& L, float chain, bool want_g) {
+    PyrArgs pa{}; SsimAllArgs sa{};
+    int rc = ms_forward_args(X, Y, ws, L, want_g, pa, sa);
+    if (rc) return rc;
     if (even_pyramid(L)) {
-        // 3 launches instead of 10: the pyramid, every level's statistics, the coefficients
-        PyrArgs pa{}; SsimAllArgs sa{}; CoefArgs ca{};
-        int rc = fill_even_forward(X, Y, ws, L, BC, chain, want_g, pa, sa, ca);
-        if (rc) return rc;
-        hipLaunchKernelGGL(pyramid_kernel, dim3(cdiv(L.pyr.W[1], 16), cdiv(L.pyr.H[1], 16), 2 * BC), dim3(256), 0, st, pa);
+        hipLaunchKernelGGL(pyramid_kernel, dim3(cdiv(L.pyr.W[1], 16), cdiv(L.pyr.H[1], 16), 2 * L.BC), dim3(256), 0, st, pa);
         BNERV_LAUNCH_CHECK("pyramid");
-        hipLaunchKernelGGL(ssim_fwd_all_kernel, dim3(sa.first[LV], BC), dim3(256), 0, st, sa);
+    } else { rc = launch_pools(st, X, Y, ws, L); if (rc) return rc; }
+    if (loss_fused()) {
+        hipLaunchKernelGGL(ssim_fwd_all_kernel, dim3(sa.first[LV], L.BC), dim3(256), 0, st, sa);
         BNERV_LAUNCH_CHECK("ssim_fwd_all");
-        hipLaunchKernelGGL(ms_coef_kernel, dim3(BC), dim3(320), 0, st, ca);
-        BNERV_LAUNCH_CHECK("ms_coef");
-        return BNERV_OK;
-    }
-    {
-        // odd pyramid (1080 -> 540 -> 270 -> 135 -> 68: the 1080p configs): the padded 2x2 means level by level, then EVERY level's statistics in
-        // ONE launch (the levels only depend on the pyramid; the same body per tile as the level-by-level launches, so the same bits) and the
-        // coefficients: 6 launches instead of 10.  BNERV_LOSS_FUSED=0 keeps the level-by-level form.
-        if (loss_fused()) {
-            PyrArgs pa{}; SsimAllArgs sa{}; CoefArgs ca{};
-            int rc = fill_even_forward(X, Y, ws, L, BC, chain, want_g, pa, sa, ca);
-            if (rc) return rc;
-            rc = launch_pools(st, X, Y, ws, L, BC);
-            if (rc) return rc;
-            hipLaunchKernelGGL(ssim_fwd_all_kernel, dim3(sa.first[LV], BC), dim3(256), 0, st, sa);
-            BNERV_LAUNCH_CHECK("ssim_fwd_all");
-            hipLaunchKernelGGL(ms_coef_kernel, dim3(BC), dim3(320), 0, st, ca);
-            BNERV_LAUNCH_CHECK("ms_coef");
-            return BNERV_OK;
+    } else {
+        for (int l = 0; l < LV; ++l) {
+            const dim3 grid(sa.lv[l].tiles_x, sa.lv[l].tiles_y, L.BC);
+            if (l == LV - 1) hipLaunchKernelGGL(ssim_fwd_kernel<true>, grid, dim3(256), 0, st, sa.lv[l]);
+            else hipLaunchKernelGGL(ssim_fwd_kernel<false>, grid, dim3(256), 0, st, sa.lv[l]);
+            BNERV_LAUNCH_CHECK("ssim_fwd");
         }
     }
-    const float* Xl = X; const float* Yl = Y;
-    CoefArgs ca{};
-    static const float weights[LV] = {0.0448f, 0.2856f, 0.3001f, 0.2363f, 0.1333f};
-    for (int l = 0; l < LV; ++l) {
-        const int Hl = L.pyr.H[l], Wl = L.pyr.W[l];
-        if (Hl <= HW_ || Wl <= HW_) return bnerv_set_error(BNERV_E_ARG, "ms_ssim: level %d is %dx%d, needs > %d on both sides", l, Hl, Wl, HW_);
-        SsimArgs a{};
-        a.X = Xl; a.Y = Yl; a.partial = ws + L.ssim_part[l]; a.H = Hl; a.W = Wl; a.G = want_g ? ws + L.Gl[l] : nullptr;
-        a.tiles_x = cdiv(Wl - HW_, STW); a.tiles_y = cdiv(Hl - HW_, STH); a.C1 = C1; a.C2 = C2; a.win = win;
-        dim3 grid(a.tiles_x, a.tiles_y, BC);
-        if (l == LV - 1) hipLaunchKernelGGL(ssim_fwd_kernel<true>, grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(ssim_fwd_kernel<false>, grid, dim3(256), 0, st, a);
-        BNERV_LAUNCH_CHECK("ssim_fwd");
-        ca.partial[l] = ws + L.ssim_part[l]; ca.tiles[l] = L.tiles[l];
-        ca.inv_nvalid[l] = 1.0f / ((float)(Hl - HW_) * (float)(Wl - HW_));
-        ca.weights[l] = weights[l];
-        if (l < LV - 1) {
-            const int Ho = L.pyr.H[l + 1], Wo = L.pyr.W[l + 1];
-            const size_t n = (size_t)BC * Ho * Wo;
-            int gx = (int)((n + 255) / 256); if (gx > 4096) gx = 4096;
-            hipLaunchKernelGGL(avgpool2_kernel, dim3(gx, 1, 2), dim3(256), 0, st, Xl, Yl, ws + L.pyrX[l + 1], ws + L.pyrY[l + 1], BC, Hl, Wl, Ho, Wo, Hl % 2, Wl % 2);
-            BNERV_LAUNCH_CHECK("avgpool2");
-            Xl = ws + L.pyrX[l + 1]; Yl = ws + L.pyrY[l + 1];
-        }
-    }
-    ca.msval = ws + L.msval; ca.coef = ws + L.coef; ca.BC = BC; ca.chain = chain;
-    hipLaunchKernelGGL(ms_coef_kernel, dim3(BC), dim3(320), 0, st, ca);
+    hipLaunchKernelGGL(ms_coef_kernel, dim3(L.BC), dim3(320), 0, st, coef_args(ws, L, chain));
     BNERV_LAUNCH_CHECK("ms_coef");
     return BNERV_OK;
 }
 
 // acc: the level-0 launch adds to `grad` (the spectral gradient is already there) instead of writing it
-static int run_ms_backward(hipStream_t st, const float* X, const float* Y, float* grad, float* ws, const WsLayout& L, int B, int C, float k_l1, float k_l2, int acc) {
-    const int BC = B * C;
-    const Win win = make_win();
+static int run_ms_backward(hipStream_t st, const float* X, const float* Y, float* grad, float* ws, const WsLayout& L, float k_l1, float k_l2, int acc) {
     if (loss_fused()) {
         // 2 launches instead of 5: the coarser levels' own terms together, then level 0 with the 0.25-chain over them (odd pyramids too:
         // the chain walks the padded cells, CoarseChain::ph / pw)
         SsimAllArgs sa{};
         CoarseChain cc{};
-        fill_even_backward(X, Y, grad, ws, L, BC, k_l1, k_l2, acc, sa, cc);
-        hipLaunchKernelGGL(ssim_bwd_coarse_all_kernel, dim3(sa.first[LV], BC), dim3(256), 0, st, sa);
+        ms_backward_args(X, Y, grad, ws, L, k_l1, k_l2, acc, sa, cc);
+        hipLaunchKernelGGL(ssim_bwd_coarse_all_kernel, dim3(sa.first[LV], L.BC), dim3(256), 0, st, sa);
         BNERV_LAUNCH_CHECK("ssim_bwd_coarse_all");
-        hipLaunchKernelGGL(ssim_bwd_level0_chain_kernel, dim3(cdiv(L.pyr.W[0], STW), cdiv(L.pyr.H[0], STH), BC), dim3(256), 0, st, sa.lv[0], cc);
+        hipLaunchKernelGGL(ssim_bwd_level0_chain_kernel, dim3(cdiv(L.pyr.W[0], STW), cdiv(L.pyr.H[0], STH), L.BC), dim3(256), 0, st, sa.lv[0], cc);
         BNERV_LAUNCH_CHECK("ssim_bwd_level0");
         return BNERV_OK;
     }
     for (int l = LV - 1; l >= 0; --l) {
-        const int Hl = L.pyr.H[l], Wl = L.pyr.W[l];
-        SsimArgs a{};
-        a.X = l ? ws + L.pyrX[l] : X; a.Y = l ? ws + L.pyrY[l] : Y;
-        a.coef = ws + L.coef + (size_t)l * BC;
-        a.dX = l ? ws + L.dXl[l] : grad;
-        a.H = Hl; a.W = Wl; a.C1 = 0.01f * 0.01f; a.C2 = 0.03f * 0.03f; a.win = win;
-        if (l < LV - 1) { a.dcoarse = ws + L.dXl[l + 1]; a.Hc = L.pyr.H[l + 1]; a.Wc = L.pyr.W[l + 1]; a.ph = Hl % 2; a.pw = Wl % 2; }
-        a.k_l1 = k_l1; a.k_l2 = k_l2; a.acc = l == 0 ? acc : 0;
-        a.G = ws + L.Gl[l];
-        dim3 grid(cdiv(Wl, STW), cdiv(Hl, STH), BC);
+        SsimArgs a = level_args(X, Y, grad, ws, L, l);
+        if (l < LV - 1) { a.dcoarse = ws + L.dXl[l + 1]; a.Hc = L.pyr.H[l + 1]; a.Wc = L.pyr.W[l + 1]; a.ph = a.H % 2; a.pw = a.W % 2; }
+        if (l == 0) { a.k_l1 = k_l1; a.k_l2 = k_l2; a.acc = acc; }
+        const dim3 grid(cdiv(a.W, STW), cdiv(a.H, STH), L.BC);
         if (l == 0) hipLaunchKernelGGL((ssim_bwd_from_g_kernel<true>), grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((ssim_bwd_from_g_kernel<false>), grid, dim3(256), 0, st, a);
         BNERV_LAUNCH_CHECK("ssim_bwd");
@@ -1400,7 +914,7 @@ static int launch_stats(hipStream_t st, const float* p, const float* t, float* p
 
 extern "C" size_t bnerv_loss_ws_bytes(int B, int C, int H, int W, int use_ms, int use_fft) {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
-    return make_layout(B, C, H, W, use_ms != 0, use_fft != 0).total * sizeof(float);
+    return make_layout(B, C, H, W, use_ms ? LV : 0, use_fft != 0).total * sizeof(float);
 }
 
 // (A second stream for the spectral branch was measured and dropped: forked with an event pair the loss section of the trace shrinks
@@ -1408,36 +922,23 @@ extern "C" size_t bnerv_loss_ws_bytes(int B, int C, int H, int W, int use_ms, in
 // two-branch graph replays slower than a linear one: C1 1.789 ms forked against 1.759 ms.  Independent launches are merged as block
 // ranges of one grid instead -- loss_head / loss_mid / loss_tail above.)
 extern "C" int bnerv_loss_fwd_bwd(void* stream, const bnerv_loss_desc* dp) {
-    BNERV_REQUIRE(dp != nullptr, "loss: null descriptor");
-    const bnerv_loss_desc d = *dp;
-    BNERV_REQUIRE(d.pred && d.target && d.loss_out && d.stats_out && d.ws, "loss: null tensor");
-    BNERV_REQUIRE((reinterpret_cast<uintptr_t>(d.ws) & 7) == 0, "loss: ws must be 8-byte aligned (the spectral term keeps its float2 spectra in it)");
-    BNERV_REQUIRE(d.B > 0 && d.C > 0 && d.H > 0 && d.W > 0 && d.B <= 65535, "loss: bad dims");
-    BNERV_REQUIRE((size_t)d.C * d.H * d.W < (size_t)1 << 31, "loss: sample too large");
+    LossCall c;
+    if (const int rc_d = open_loss_call(dp, "loss", c)) return rc_d;
+    const bnerv_loss_desc& d = c.d;
     const bool use_ms = d.c_ms != 0.f, use_fft = d.c_fft != 0.f;
-    const WsLayout L = make_layout(d.B, d.C, d.H, d.W, use_ms, use_fft);
+    const WsLayout L = make_layout(d.B, d.C, d.H, d.W, use_ms ? LV : 0, use_fft);
     if (d.ws_bytes < L.total * sizeof(float)) return bnerv_set_error(BNERV_E_WS, "loss: workspace %zu < %zu", d.ws_bytes, L.total * sizeof(float));
     hipStream_t st = (hipStream_t)stream;
     float* ws = reinterpret_cast<float*>(d.ws);
-    const int nps = d.C * d.H * d.W, BC = d.B * d.C;
-    const float k_l1 = d.c_l1 / ((float)d.B * (float)nps), k_l2 = 2.0f * d.c_l2 / ((float)d.B * (float)nps);
+    const int BC = c.BC;
     if (use_ms && (d.H <= 160 || d.W <= 160)) return bnerv_set_error(BNERV_E_ARG, "loss: MS-SSIM needs min(H,W) > 160 (got %dx%d)", d.H, d.W);
-    FftArgs a{};
-    size_t lds_row = 0, lds_col = 0;
-    int nrowblk = 0;
+    FftLaunch F{};
     if (use_fft) {
-        if (!make_plan(d.W, &a.prow) || !make_plan(d.H, &a.pcol))
-            return bnerv_set_error(BNERV_E_ARG, "loss: FFT size %dx%d has a prime factor > %d", d.H, d.W, BNERV_FFT_MAX_RADIX);
-        a.pred = d.pred; a.target = d.target; a.T = reinterpret_cast<float2*>(ws + L.T); a.Wh = d.W / 2 + 1; a.partial = ws + L.fft_part; a.grad = d.grad;
-        a.BC = BC; a.H = d.H; a.W = d.W; a.gscale = d.c_fft / ((float)d.B * (float)nps * 2.0f); a.accumulate = 1;
-        lds_row = (size_t)(LINES_PER_BLOCK + 1) * d.W * sizeof(float2) + (size_t)d.W * sizeof(int); lds_col = (size_t)(COLS_PER_BLOCK + 1) * d.H * sizeof(float2);   // + twiddle table (+ position table)
-        BNERV_REQUIRE(lds_row <= 160 * 1024 && lds_col <= 160 * 1024, "loss: frame %dx%d too large for the LDS FFT", d.H, d.W);
-        nrowblk = cdiv(BC * d.H, ROWS_PER_BLOCK);
+        if (const int rc_f = fft_launch_args(c, ws, L, BNERV_FFT_MAX_RADIX, 160 * 1024, false, "loss", F)) return rc_f;
+        F.a.accumulate = 1;
     }
-    FinalArgs f{};
-    f.stats_part = ws + L.stats_part; f.msval = use_ms ? ws + L.msval : nullptr; f.fft_part = use_fft ? ws + L.fft_part : nullptr;
-    f.loss_out = d.loss_out; f.stats_out = d.stats_out; f.B = d.B; f.C = d.C; f.n_per_sample = nps; f.ncolblk = L.ncolblk;
-    f.c_l1 = d.c_l1; f.c_l2 = d.c_l2; f.c_ms = d.c_ms; f.c_fft = d.c_fft;
+    const FinalArgs f = final_args(c, ws, L, use_ms ? ws + L.msval : nullptr, d.c_ms);
+    const float chain = -d.c_ms / (float)BC;
 
     const bool late = adj_late();
     if (use_ms && use_fft && d.grad && loss_fused() && loss_merged()) {
@@ -1447,29 +948,29 @@ extern "C" int bnerv_loss_fwd_bwd(void* stream, const bnerv_loss_desc* dp) {
         const bool even = even_pyramid(L);
         LossHeadArgs ha{}; LossMidArgs ma{}; LossTailArgs ta{};
         SsimAllArgs sf{};
-        int rc = fill_even_forward(d.pred, d.target, ws, L, BC, -d.c_ms / (float)BC, true, ha.p, sf, ma.c);
+        int rc = ms_forward_args(d.pred, d.target, ws, L, true, ha.p, sf);
         if (rc) return rc;
-        ha.f = a; ha.pred = d.pred; ha.target = d.target; ha.stats_part = ws + L.stats_part; ha.nps = nps;
-        ha.n_fft = nrowblk; ha.pyr_gx = cdiv(L.pyr.W[1], 16); ha.pyr_gy = cdiv(L.pyr.H[1], 16); ha.n_pyr = even ? ha.pyr_gx * ha.pyr_gy * 2 * BC : 0;
-        if (const int rc_lds = dyn_lds<&loss_head_kernel>(lds_row, "loss_head")) return rc_lds;
-        hipLaunchKernelGGL(loss_head_kernel, dim3(ha.n_fft + ha.n_pyr + NSB * d.B), dim3(256), lds_row, st, ha);
+        ha.f = F.a; ha.pred = d.pred; ha.target = d.target; ha.stats_part = ws + L.stats_part; ha.nps = c.nps;
+        ha.n_fft = F.nrowblk; ha.pyr_gx = cdiv(L.pyr.W[1], 16); ha.pyr_gy = cdiv(L.pyr.H[1], 16); ha.n_pyr = even ? ha.pyr_gx * ha.pyr_gy * 2 * BC : 0;
+        if (const int rc_lds = dyn_lds<&loss_head_kernel>(F.lds_row, "loss_head")) return rc_lds;
+        hipLaunchKernelGGL(loss_head_kernel, dim3(ha.n_fft + ha.n_pyr + NSB * d.B), dim3(256), F.lds_row, st, ha);
         BNERV_LAUNCH_CHECK("loss_head");
-        if (!even) { rc = launch_pools(st, d.pred, d.target, ws, L, BC); if (rc) return rc; }
+        if (!even) { rc = launch_pools(st, d.pred, d.target, ws, L); if (rc) return rc; }
         hipLaunchKernelGGL(ssim_fwd_all_kernel, dim3(sf.first[LV], BC), dim3(256), 0, st, sf);
         BNERV_LAUNCH_CHECK("ssim_fwd_all");
-        ma.f = a; ma.ncolblk = L.ncolblk; ma.n_cols = L.ncolblk * BC;
-        if (const int rc_lds = dyn_lds<&loss_mid_kernel>(lds_col, "loss_mid")) return rc_lds;
-        hipLaunchKernelGGL(loss_mid_kernel, dim3(ma.n_cols + BC), dim3(256), lds_col, st, ma);
+        ma.f = F.a; ma.c = coef_args(ws, L, chain); ma.ncolblk = L.ncolblk; ma.n_cols = L.ncolblk * BC;
+        if (const int rc_lds = dyn_lds<&loss_mid_kernel>(F.lds_col, "loss_mid")) return rc_lds;
+        hipLaunchKernelGGL(loss_mid_kernel, dim3(ma.n_cols + BC), dim3(256), F.lds_col, st, ma);
         BNERV_LAUNCH_CHECK("loss_mid");
         SsimAllArgs sb{};
-        fill_even_backward(d.pred, d.target, d.grad, ws, L, BC, k_l1, k_l2, late ? 0 : 1, sb, ta.cc);
+        ms_backward_args(d.pred, d.target, d.grad, ws, L, c.k_l1, c.k_l2, late ? 0 : 1, sb, ta.cc);
         if (late) {
             hipLaunchKernelGGL(ssim_bwd_coarse_all_kernel, dim3(sb.first[LV], BC), dim3(256), 0, st, sb);
             BNERV_LAUNCH_CHECK("ssim_bwd_coarse_all");
         } else {
             LossCoarseArgs ca{};
-            ca.f = a; ca.f.accumulate = 0; ca.s = sb; ca.n_adj = nrowblk; ca.gx = sb.first[LV]; ca.BC = BC;
-            const size_t lds_c = lds_row > SSIM_BWD_LDS * sizeof(float) ? lds_row : SSIM_BWD_LDS * sizeof(float);
+            ca.f = F.a; ca.f.accumulate = 0; ca.s = sb; ca.n_adj = F.nrowblk; ca.gx = sb.first[LV]; ca.BC = BC;
+            const size_t lds_c = F.lds_row > SSIM_BWD_LDS * sizeof(float) ? F.lds_row : SSIM_BWD_LDS * sizeof(float);
             if (const int rc_lds = dyn_lds<&loss_coarse_kernel>(lds_c, "loss_coarse")) return rc_lds;
             hipLaunchKernelGGL(loss_coarse_kernel, dim3(ca.n_adj + ca.gx * BC), dim3(256), lds_c, st, ca);
             BNERV_LAUNCH_CHECK("loss_coarse");
@@ -1478,8 +979,8 @@ extern "C" int bnerv_loss_fwd_bwd(void* stream, const bnerv_loss_desc* dp) {
         hipLaunchKernelGGL(loss_tail_kernel, dim3(ta.n0 + 1), dim3(256), 0, st, ta);
         BNERV_LAUNCH_CHECK("loss_tail");
         if (late) {
-            if (const int rc_lds = dyn_lds<&fft_rows_adj_kernel>(lds_row, "fft_rows_adj")) return rc_lds;
-            hipLaunchKernelGGL(fft_rows_adj_kernel, dim3(nrowblk), dim3(256), lds_row, st, a);
+            if (const int rc_lds = dyn_lds<&fft_rows_adj_kernel>(F.lds_row, "fft_rows_adj")) return rc_lds;
+            hipLaunchKernelGGL(fft_rows_adj_kernel, dim3(F.nrowblk), dim3(256), F.lds_row, st, F.a);
             BNERV_LAUNCH_CHECK("fft_rows_adj");
         }
         return BNERV_OK;
@@ -1488,32 +989,32 @@ extern "C" int bnerv_loss_fwd_bwd(void* stream, const bnerv_loss_desc* dp) {
     // one launch per kernel.  With both an MS-SSIM and a spectral term the spectral gradient is written FIRST and the level-0 SSIM launch adds
     // to it -- the arithmetic of the merged form above, so the two forms agree bit for bit (BNERV_LOSS_ADJ=late: the other order, in both forms)
     const bool fft_first = use_ms && use_fft && d.grad && !late;
-    int rc = launch_stats(st, d.pred, d.target, ws + L.stats_part, d.B, nps);
+    int rc = launch_stats(st, d.pred, d.target, ws + L.stats_part, d.B, c.nps);
     if (rc) return rc;
     auto run_fft = [&](int accumulate) -> int {
-        FftArgs fa = a; fa.accumulate = accumulate;
-        if (const int rc_lds = dyn_lds<&fft_rows_fwd_kernel>(lds_row, "fft_rows_fwd")) return rc_lds;
-        if (const int rc_lds = dyn_lds<&fft_rows_adj_kernel>(lds_row, "fft_rows_adj")) return rc_lds;
-        if (const int rc_lds = dyn_lds<&fft_cols_kernel>(lds_col, "fft_cols")) return rc_lds;
-        hipLaunchKernelGGL(fft_rows_fwd_kernel, dim3(nrowblk), dim3(256), lds_row, st, fa);
+        FftArgs fa = F.a; fa.accumulate = accumulate;
+        if (const int rc_lds = dyn_lds<&fft_rows_fwd_kernel>(F.lds_row, "fft_rows_fwd")) return rc_lds;
+        if (const int rc_lds = dyn_lds<&fft_rows_adj_kernel>(F.lds_row, "fft_rows_adj")) return rc_lds;
+        if (const int rc_lds = dyn_lds<&fft_cols_kernel>(F.lds_col, "fft_cols")) return rc_lds;
+        hipLaunchKernelGGL(fft_rows_fwd_kernel, dim3(F.nrowblk), dim3(256), F.lds_row, st, fa);
         BNERV_LAUNCH_CHECK("fft_rows_fwd");
-        hipLaunchKernelGGL(fft_cols_kernel, dim3(L.ncolblk, BC), dim3(256), lds_col, st, fa);
+        hipLaunchKernelGGL(fft_cols_kernel, dim3(L.ncolblk, BC), dim3(256), F.lds_col, st, fa);
         BNERV_LAUNCH_CHECK("fft_cols");
         if (d.grad) {
-            hipLaunchKernelGGL(fft_rows_adj_kernel, dim3(nrowblk), dim3(256), lds_row, st, fa);
+            hipLaunchKernelGGL(fft_rows_adj_kernel, dim3(F.nrowblk), dim3(256), F.lds_row, st, fa);
             BNERV_LAUNCH_CHECK("fft_rows_adj");
         }
         return BNERV_OK;
     };
     if (use_ms) {
-        rc = run_ms_forward(st, d.pred, d.target, ws, L, d.B, d.C, -d.c_ms / (float)BC, d.grad != nullptr);
+        rc = run_ms_forward(st, d.pred, d.target, ws, L, chain, d.grad != nullptr);
         if (rc) return rc;
         if (fft_first) { rc = run_fft(0); if (rc) return rc; }
-        if (d.grad) { rc = run_ms_backward(st, d.pred, d.target, d.grad, ws, L, d.B, d.C, k_l1, k_l2, fft_first ? 1 : 0); if (rc) return rc; }
+        if (d.grad) { rc = run_ms_backward(st, d.pred, d.target, d.grad, ws, L, c.k_l1, c.k_l2, fft_first ? 1 : 0); if (rc) return rc; }
     } else if (d.grad) {
-        const size_t n = (size_t)d.B * nps;
+        const size_t n = (size_t)d.B * c.nps;
         int gx = (int)((n + 1023) / 1024); if (gx > 4096) gx = 4096;
-        hipLaunchKernelGGL(grad_l1l2_kernel, dim3(gx), dim3(256), 0, st, d.pred, d.target, d.grad, n, k_l1, k_l2);
+        hipLaunchKernelGGL(grad_l1l2_kernel, dim3(gx), dim3(256), 0, st, d.pred, d.target, d.grad, n, c.k_l1, c.k_l2);
         BNERV_LAUNCH_CHECK("grad_l1l2");
     }
     if (use_fft && !fft_first) { rc = run_fft(1); if (rc) return rc; }
@@ -1525,11 +1026,11 @@ extern "C" int bnerv_loss_fwd_bwd(void* stream, const bnerv_loss_desc* dp) {
 extern "C" int bnerv_msssim(void* stream, const float* x, const float* y, float* out, void* wsv, size_t ws_bytes, int B, int C, int H, int W) {
     BNERV_REQUIRE(x && y && out && wsv && B > 0 && C > 0, "msssim: bad args");
     if (H <= 160 || W <= 160) return bnerv_set_error(BNERV_E_ARG, "msssim: needs min(H,W) > 160 (got %dx%d)", H, W);
-    const WsLayout L = make_layout(B, C, H, W, true, false);
+    const WsLayout L = make_layout(B, C, H, W, LV, false);
     if (ws_bytes < L.total * sizeof(float)) return bnerv_set_error(BNERV_E_WS, "msssim: workspace %zu < %zu", ws_bytes, L.total * sizeof(float));
     hipStream_t st = (hipStream_t)stream;
     float* ws = reinterpret_cast<float*>(wsv);
-    int rc = run_ms_forward(st, x, y, ws, L, B, C, 0.f, false);
+    int rc = run_ms_forward(st, x, y, ws, L, 0.f, false);
     if (rc) return rc;
     hipLaunchKernelGGL(msssim_final_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, ws + L.msval, out, B, C);
     BNERV_LAUNCH_CHECK("msssim_final");
@@ -1538,70 +1039,51 @@ extern "C" int bnerv_msssim(void* stream, const float* x, const float* y, float*
 
 extern "C" size_t bnerv_loss_ssim_ws_bytes(int B, int C, int H, int W, int use_fft) {
     if (B <= 0 || C <= 0 || H <= HW_ || W <= HW_) return 0;
-    return make_layout_ssim(B, C, H, W, use_fft != 0).total * sizeof(float);
+    return make_layout(B, C, H, W, 1, use_fft != 0).total * sizeof(float);
 }
 
-// The single-scale SSIM losses: the descriptor of bnerv_loss_fwd_bwd plus c_ssim (c_ms must be 0).  2 launches (4 with a spectral term).
+// The single-scale SSIM losses: the descriptor of bnerv_loss_fwd_bwd plus c_ssim (c_ms must be 0).  2 launches (5 with a spectral term).
 extern "C" int bnerv_loss_ssim_fwd_bwd(void* stream, const bnerv_loss_desc* dp, float c_ssim) {
-    BNERV_REQUIRE(dp != nullptr, "loss_ssim: null descriptor");
-    const bnerv_loss_desc d = *dp;
-    BNERV_REQUIRE(d.pred && d.target && d.loss_out && d.stats_out && d.ws, "loss_ssim: null tensor");
-    BNERV_REQUIRE((reinterpret_cast<uintptr_t>(d.ws) & 7) == 0, "loss_ssim: ws must be 8-byte aligned (the spectral term keeps its float2 spectra in it)");
-    BNERV_REQUIRE(d.B > 0 && d.C > 0 && d.H > 0 && d.W > 0 && d.B <= 65535, "loss_ssim: bad dims");
-    BNERV_REQUIRE((size_t)d.C * d.H * d.W < (size_t)1 << 31, "loss_ssim: sample too large");
+    LossCall c;
+    if (const int rc_d = open_loss_call(dp, "loss_ssim", c)) return rc_d;
+    const bnerv_loss_desc& d = c.d;
     BNERV_REQUIRE(d.c_ms == 0.f, "loss_ssim: c_ms must be 0 (the MS-SSIM losses go through bnerv_loss_fwd_bwd)");
     BNERV_REQUIRE(c_ssim != 0.f, "loss_ssim: c_ssim is 0 (losses without an SSIM term go through bnerv_loss_fwd_bwd)");
     if (d.H <= HW_ || d.W <= HW_) return bnerv_set_error(BNERV_E_ARG, "loss_ssim: SSIM needs min(H,W) >= %d (got %dx%d)", WS_, d.H, d.W);
     const bool use_fft = d.c_fft != 0.f;
-    const WsLayout L = make_layout_ssim(d.B, d.C, d.H, d.W, use_fft);
+    const WsLayout L = make_layout(d.B, d.C, d.H, d.W, 1, use_fft);
     if (d.ws_bytes < L.total * sizeof(float)) return bnerv_set_error(BNERV_E_WS, "loss_ssim: workspace %zu < %zu", d.ws_bytes, L.total * sizeof(float));
     hipStream_t st = (hipStream_t)stream;
     float* ws = reinterpret_cast<float*>(d.ws);
-    const int nps = d.C * d.H * d.W, BC = d.B * d.C;
+    const int BC = c.BC;
     BNERV_REQUIRE((size_t)L.tiles[0] * BC + (size_t)BC * d.H + (size_t)NSB * d.B < (size_t)1 << 30, "loss_ssim: batch too large for one grid");
-    const float k_l1 = d.c_l1 / ((float)d.B * (float)nps), k_l2 = 2.0f * d.c_l2 / ((float)d.B * (float)nps);
-    const float inv_nvalid = 1.0f / ((float)(d.H - HW_) * (float)(d.W - HW_));
-    SsimHeadArgs ha{};
-    FftArgs fa{};
-    size_t lds_row = 0, lds_col = 0;
-    int n_fft = 0;
+    FftLaunch F{};
     if (use_fft) {
-        FftArgs& a = fa;
-        if (!make_plan(d.W, &a.prow, SSIM_FFT_MAX_RADIX) || !make_plan(d.H, &a.pcol, SSIM_FFT_MAX_RADIX))
-            return bnerv_set_error(BNERV_E_ARG, "loss_ssim: FFT size %dx%d has a prime factor > %d", d.H, d.W, SSIM_FFT_MAX_RADIX);
-        BNERV_REQUIRE(BC <= 65535, "loss_ssim: B * C > 65535 with a spectral term");
-        a.pred = d.pred; a.target = d.target; a.T = reinterpret_cast<float2*>(ws + L.T); a.Wh = d.W / 2 + 1; a.partial = ws + L.fft_part; a.grad = d.grad;
-        a.BC = BC; a.H = d.H; a.W = d.W; a.gscale = d.c_fft / ((float)d.B * (float)nps * 2.0f); a.accumulate = 0;
-        lds_row = (size_t)(LINES_PER_BLOCK + 1) * d.W * sizeof(float2) + (size_t)d.W * sizeof(int); lds_col = (size_t)(COLS_PER_BLOCK + 1) * d.H * sizeof(float2);
-        BNERV_REQUIRE(lds_row <= 128 * 1024 && lds_col <= 160 * 1024, "loss_ssim: frame %dx%d too large for the LDS FFT", d.H, d.W);
-        n_fft = cdiv(BC * d.H, ROWS_PER_BLOCK);
-        if (const int rc_lds = dyn_lds<&ssim_fft_rows_fwd_kernel>(lds_row, "ssim_fft_rows_fwd")) return rc_lds;
-        hipLaunchKernelGGL(ssim_fft_rows_fwd_kernel, dim3(n_fft), dim3(256), lds_row, st, fa);
+        if (const int rc_f = fft_launch_args(c, ws, L, SSIM_FFT_MAX_RADIX, 128 * 1024, true, "loss_ssim", F)) return rc_f;
+        if (const int rc_lds = dyn_lds<&ssim_fft_rows_fwd_kernel>(F.lds_row, "ssim_fft_rows_fwd")) return rc_lds;
+        hipLaunchKernelGGL(ssim_fft_rows_fwd_kernel, dim3(F.nrowblk), dim3(256), F.lds_row, st, F.a);
         BNERV_LAUNCH_CHECK("ssim_fft_rows_fwd");
     }
-    // the statistic-gradient maps are written only where a gradient is asked for
-    ha.s = fill_ssim_level0(d.pred, d.target, ws, L, d.grad ? ws + L.Gl[0] : nullptr, d.grad, (-c_ssim / (float)BC) * inv_nvalid, k_l1, k_l2, use_fft ? 1 : 0);
-    ha.pred = d.pred; ha.target = d.target; ha.stats_part = ws + L.stats_part; ha.nps = nps; ha.n_sums = NSB * d.B; ha.BC = BC;
+    SsimHeadArgs ha{};
+    ha.s = level_args(d.pred, d.target, d.grad, ws, L, 0);
+    if (!d.grad) ha.s.G = nullptr;
+    ha.s.coef = nullptr; ha.s.coef_k = (-c_ssim / (float)BC) * inv_nvalid(L, 0); ha.s.k_l1 = c.k_l1; ha.s.k_l2 = c.k_l2; ha.s.acc = use_fft ? 1 : 0;
+    ha.pred = d.pred; ha.target = d.target; ha.stats_part = ws + L.stats_part; ha.nps = c.nps; ha.n_sums = NSB * d.B; ha.BC = BC;
     hipLaunchKernelGGL(ssim_head_kernel, dim3(ha.n_sums + L.tiles[0] * BC), dim3(256), 0, st, ha);
     BNERV_LAUNCH_CHECK("ssim_head");
     if (use_fft) {
-        if (const int rc_lds = dyn_lds<&ssim_fft_cols_kernel>(lds_col, "ssim_fft_cols")) return rc_lds;
-        hipLaunchKernelGGL(ssim_fft_cols_kernel, dim3(L.ncolblk, BC), dim3(256), lds_col, st, fa);
+        if (const int rc_lds = dyn_lds<&ssim_fft_cols_kernel>(F.lds_col, "ssim_fft_cols")) return rc_lds;
+        hipLaunchKernelGGL(ssim_fft_cols_kernel, dim3(L.ncolblk, BC), dim3(256), F.lds_col, st, F.a);
         BNERV_LAUNCH_CHECK("ssim_fft_cols");
         if (d.grad) {                                                      // the spectral gradient, WRITTEN: the tail adds to it
-            if (const int rc_lds = dyn_lds<&ssim_fft_rows_adj_kernel>(lds_row, "ssim_fft_rows_adj")) return rc_lds;
-            hipLaunchKernelGGL(ssim_fft_rows_adj_kernel, dim3(n_fft), dim3(256), lds_row, st, fa);
+            if (const int rc_lds = dyn_lds<&ssim_fft_rows_adj_kernel>(F.lds_row, "ssim_fft_rows_adj")) return rc_lds;
+            hipLaunchKernelGGL(ssim_fft_rows_adj_kernel, dim3(F.nrowblk), dim3(256), F.lds_row, st, F.a);
             BNERV_LAUNCH_CHECK("ssim_fft_rows_adj");
         }
     }
     SsimTailArgs ta{};
     ta.s = ha.s;
-    SsimFinalArgs& sf = ta.fin;
-    sf.part = ws + L.ssim_part[0]; sf.val = ws + L.msval; sf.inv_nvalid = inv_nvalid; sf.tiles = L.tiles[0]; sf.BC = BC;
-    FinalArgs& f = sf.fin;
-    f.stats_part = ws + L.stats_part; f.msval = ws + L.msval; f.fft_part = use_fft ? ws + L.fft_part : nullptr;
-    f.loss_out = d.loss_out; f.stats_out = d.stats_out; f.B = d.B; f.C = d.C; f.n_per_sample = nps; f.ncolblk = L.ncolblk;
-    f.c_l1 = d.c_l1; f.c_l2 = d.c_l2; f.c_ms = c_ssim; f.c_fft = d.c_fft;
+    ta.fin = SsimFinalArgs{ws + L.ssim_part[0], ws + L.msval, inv_nvalid(L, 0), L.tiles[0], BC, final_args(c, ws, L, ws + L.msval, c_ssim)};
     if (d.grad) {
         ta.gx = cdiv(d.W, STW); ta.gy = cdiv(d.H, STH); ta.BC = BC; ta.n0 = ta.gx * ta.gy * BC;
         hipLaunchKernelGGL(ssim_tail_kernel, dim3(ta.n0 + 1), dim3(256), 0, st, ta);
@@ -1617,23 +1099,23 @@ extern "C" int bnerv_loss_ssim_fwd_bwd(void* stream, const bnerv_loss_desc* dp, 
 extern "C" int bnerv_ssim(void* stream, const float* x, const float* y, float* out, void* wsv, size_t ws_bytes, int B, int C, int H, int W) {
     BNERV_REQUIRE(x && y && out && wsv && B > 0 && C > 0, "ssim: bad args");
     if (H <= HW_ || W <= HW_) return bnerv_set_error(BNERV_E_ARG, "ssim: needs min(H,W) >= %d (got %dx%d)", WS_, H, W);
-    const WsLayout L = make_layout_ssim(B, C, H, W, false);
+    const WsLayout L = make_layout(B, C, H, W, 1, false);
     if (ws_bytes < L.total * sizeof(float)) return bnerv_set_error(BNERV_E_WS, "ssim: workspace %zu < %zu", ws_bytes, L.total * sizeof(float));
     hipStream_t st = (hipStream_t)stream;
     float* ws = reinterpret_cast<float*>(wsv);
     const int BC = B * C;
     BNERV_REQUIRE(BC <= 65535, "ssim: batch too large");
-    const SsimArgs a = fill_ssim_level0(x, y, ws, L, nullptr, nullptr, 0.f, 0.f, 0.f, 0);
+    SsimArgs a = level_args(x, y, nullptr, ws, L, 0);
+    a.G = nullptr; a.coef = nullptr;
     hipLaunchKernelGGL(ssim_fwd_kernel<true>, dim3(a.tiles_x, a.tiles_y, BC), dim3(256), 0, st, a);
     BNERV_LAUNCH_CHECK("ssim_fwd");
-    SsimFinalArgs sf{};
-    sf.part = ws + L.ssim_part[0]; sf.val = ws + L.msval; sf.inv_nvalid = 1.0f / ((float)(H - HW_) * (float)(W - HW_)); sf.tiles = L.tiles[0]; sf.BC = BC;
+    const SsimFinalArgs sf{ws + L.ssim_part[0], ws + L.msval, inv_nvalid(L, 0), L.tiles[0], BC};
     hipLaunchKernelGGL(ssim_metric_kernel, dim3(1), dim3(256), 0, st, sf, out, B, C);
     BNERV_LAUNCH_CHECK("ssim_metric");
     return BNERV_OK;
 }
 
-extern "C" size_t bnerv_psnr_ws_bytes(int B, int C, int H, int W) { (void)C; (void)H; (void)W; return B > 0 ? (size_t)B * NSB * 2 * sizeof(float) : 0; }
+extern "C" size_t bnerv_psnr_ws_bytes(int B, int C, int H, int W) { return B > 0 ? make_layout(B, C, H, W, 0, false).total * sizeof(float) : 0; }
 
 extern "C" int bnerv_psnr(void* stream, const float* o, const float* gt, float* psnr, void* ws, size_t ws_bytes, int B, int C, int H, int W) {
     BNERV_REQUIRE(o && gt && psnr && ws && B > 0 && B <= 65535 && C > 0 && H > 0 && W > 0, "psnr: bad args");

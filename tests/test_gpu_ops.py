@@ -1145,6 +1145,46 @@ def test_spectral_gradient_first_or_last_is_the_same_gradient(ops, shape, monkey
         assert (ga - gb).abs().max().item() <= 2e-7 * gb.abs().max().item(), (merged, (ga - gb).abs().max().item(), gb.abs().max().item())
 
 
+SMALLEST_MS_SHAPES = [(2, 3, 176, 208), (2, 3, 180, 270), (1, 1, 161, 161)]      # even pyramid, odd, odd at the smallest legal side
+
+
+def _small_ms_inputs(shape, salt):
+    g = torch.Generator().manual_seed(salt + sum(shape))
+    tgt = torch.rand(*shape, generator=g).to(DEV)
+    return (tgt + 0.1 * torch.randn(*shape, generator=g).to(DEV)).clamp(0, 1), tgt
+
+
+@pytest.mark.parametrize("shape", SMALLEST_MS_SHAPES)
+def test_unmerged_msssim_loss_fused_equals_level_by_level(ops, shape, monkeypatch):
+    """Fusion10 -- an MS-SSIM term without a spectral one, so the call never takes the merged launches: run_ms_forward / run_ms_backward with
+    BNERV_LOSS_FUSED = 1 against 0 (where the four pools run ahead of the per-level statistics launches).  The tolerances
+    of test_fused_msssim_launches_equal_the_level_by_level_form: values rtol 5e-7, the gradient 3e-5 of its largest entry."""
+    pred, tgt = _small_ms_inputs(shape, 13)
+    out = {}
+    for mode in ("1", "0"):
+        monkeypatch.setenv("BNERV_LOSS_FUSED", mode)
+        loss, stats, grad = ops.loss_value_grad_stats(pred, tgt, "Fusion10")
+        out[mode] = (loss.clone(), stats.clone(), grad.clone())
+    for a, b in zip(out["1"][:2], out["0"][:2]):
+        torch.testing.assert_close(a, b, rtol=5e-7, atol=0)
+    ga, gb = out["1"][2], out["0"][2]
+    print("max gradient difference / largest entry", (ga - gb).abs().max().item() / gb.abs().max().item())
+    assert (ga - gb).abs().max().item() <= 3e-5 * gb.abs().max().item()
+
+
+@pytest.mark.parametrize("loss_type", ["Fusion10_freq", "Fusion10"])
+@pytest.mark.parametrize("shape", SMALLEST_MS_SHAPES)
+def test_value_only_loss_call_equals_the_value_and_gradient_call(ops, shape, loss_type):
+    """ops.loss_with_stats on a `pred` that does not require grad (no gradient buffer: G = NULL in every level's statistics launch, no
+    backward launches, the one-launch-per-kernel form) against the value + gradient call of the same inputs: the same bodies add the same
+    numbers, so loss and statistics are equal bit for bit."""
+    pred, tgt = _small_ms_inputs(shape, 17)
+    assert not pred.requires_grad
+    loss_v, stats_v = ops.loss_with_stats(pred, tgt, loss_type)
+    loss_g, stats_g, _ = ops.loss_value_grad_stats(pred, tgt, loss_type)
+    assert torch.equal(loss_v, loss_g) and torch.equal(stats_v, stats_g), ((loss_v - loss_g).abs().item(), (stats_v - stats_g).abs().max().item())
+
+
 def test_msssim_kernel_against_independent_form(ops):
     """bnerv_msssim (the kernels behind the 0.3 * (1 - ms_ssim) term of Fusion10_freq, hnerv_utils.py:369-370, and the MS-SSIM eval
     metric, :410-412) against the independent float64 form of tests/msssim_independent.py -- direct 2-D window, written from the
