@@ -27,6 +27,7 @@
 #include <vector>
 #include <math.h>
 #include <string.h>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 
@@ -794,10 +795,39 @@ static int open_loss_call(const bnerv_loss_desc* dp, const char* who, LossCall& 
     c.k_l1 = d.c_l1 / ((float)d.B * (float)c.nps); c.k_l2 = 2.0f * d.c_l2 / ((float)d.B * (float)c.nps);
     return BNERV_OK;
 }
-// the spectral term's launch data.  maxr: the radix limit of the caller's kernel instantiations; bc_grid_y: its column launch always has B * C as grid.y
+// Static LDS of the kernels that carry an FFT body, which a block needs ON TOP of the dynamic bytes of its lines and tables: the row bodies declare
+// none, fft_cols_body its 16-byte reduction, and a merged kernel whatever its other bodies declare (loss_head: the pyramid tile and the L1 / L2 sums).
+// Read from the loaded code object, once per entry point: `row` / `col` = the largest of the kernels that may run the row / column bodies there.
+constexpr size_t FFT_LDS_PER_BLOCK = 160 * 1024;
+struct FftStaticLds { size_t row = 0, col = 0; bool known = false; };
+static bool fft_static_lds(std::initializer_list<const void*> rows, std::initializer_list<const void*> cols, FftStaticLds& out) {
+    static std::mutex m;
+    std::lock_guard<std::mutex> lk(m);
+    if (out.known) return true;
+    FftStaticLds s;
+    hipFuncAttributes at;
+    for (const void* k : rows) { if (hipFuncGetAttributes(&at, k) != hipSuccess) return false; if ((size_t)at.sharedSizeBytes > s.row) s.row = (size_t)at.sharedSizeBytes; }
+    for (const void* k : cols) { if (hipFuncGetAttributes(&at, k) != hipSuccess) return false; if ((size_t)at.sharedSizeBytes > s.col) s.col = (size_t)at.sharedSizeBytes; }
+    s.known = true;
+    out = s;
+    return true;
+}
+static const FftStaticLds* loss_fft_static_lds() {           // bnerv_loss_fwd_bwd: one launch per kernel, or the merged head / mid / coarse
+    static FftStaticLds s;
+    return fft_static_lds({(const void*)&fft_rows_fwd_kernel, (const void*)&fft_rows_adj_kernel, (const void*)&loss_head_kernel, (const void*)&loss_coarse_kernel},
+                          {(const void*)&fft_cols_kernel, (const void*)&loss_mid_kernel}, s) ? &s : nullptr;
+}
+static const FftStaticLds* ssim_fft_static_lds() {           // bnerv_loss_ssim_fwd_bwd
+    static FftStaticLds s;
+    return fft_static_lds({(const void*)&ssim_fft_rows_fwd_kernel, (const void*)&ssim_fft_rows_adj_kernel}, {(const void*)&ssim_fft_cols_kernel}, s) ? &s : nullptr;
+}
+
+// the spectral term's launch data.  maxr: the radix limit of the caller's kernel instantiations; bc_grid_y: its column launch always has B * C as grid.y;
+// sl: the static LDS of its kernels.  A frame whose lines and tables do not fit a block's LDS NEXT TO those static bytes is refused here, before any launch.
 struct FftLaunch { FftArgs a; size_t lds_row, lds_col; int nrowblk; };
-static int fft_launch_args(const LossCall& c, float* ws, const WsLayout& L, int maxr, size_t row_lds_limit, bool bc_grid_y, const char* who, FftLaunch& F) {
+static int fft_launch_args(const LossCall& c, float* ws, const WsLayout& L, int maxr, size_t row_lds_limit, const FftStaticLds* sl, bool bc_grid_y, const char* who, FftLaunch& F) {
     const bnerv_loss_desc& d = c.d;
+    if (sl == nullptr) return bnerv_set_error(BNERV_E_LAUNCH, "%s: the static LDS size of the FFT kernels could not be read", who);
     FftArgs& a = F.a;
     if (!make_plan(d.W, &a.prow, maxr) || !make_plan(d.H, &a.pcol, maxr))
         return bnerv_set_error(BNERV_E_ARG, "%s: FFT size %dx%d has a prime factor > %d", who, d.H, d.W, maxr);
@@ -805,7 +835,9 @@ static int fft_launch_args(const LossCall& c, float* ws, const WsLayout& L, int 
     a.pred = d.pred; a.target = d.target; a.T = reinterpret_cast<float2*>(ws + L.T); a.Wh = d.W / 2 + 1; a.partial = ws + L.fft_part; a.grad = d.grad;
     a.BC = c.BC; a.H = d.H; a.W = d.W; a.gscale = d.c_fft / ((float)d.B * (float)c.nps * 2.0f); a.accumulate = 0;
     F.lds_row = (size_t)(LINES_PER_BLOCK + 1) * d.W * sizeof(float2) + (size_t)d.W * sizeof(int); F.lds_col = (size_t)(COLS_PER_BLOCK + 1) * d.H * sizeof(float2);   // + twiddle table (+ position table)
-    BNERV_REQUIRE(F.lds_row <= row_lds_limit && F.lds_col <= 160 * 1024, "%s: frame %dx%d too large for the LDS FFT", who, d.H, d.W);
+    BNERV_REQUIRE(F.lds_row + sl->row <= row_lds_limit && F.lds_col + sl->col <= FFT_LDS_PER_BLOCK,
+                  "%s: frame %dx%d too large for the LDS FFT (rows %zu + %zu static bytes of %zu, columns %zu + %zu of %zu)", who, d.H, d.W,
+                  F.lds_row, sl->row, row_lds_limit, F.lds_col, sl->col, FFT_LDS_PER_BLOCK);
     F.nrowblk = cdiv(c.BC * d.H, ROWS_PER_BLOCK);
     return BNERV_OK;
 }
@@ -934,7 +966,7 @@ extern "C" int bnerv_loss_fwd_bwd(void* stream, const bnerv_loss_desc* dp) {
     if (use_ms && (d.H <= 160 || d.W <= 160)) return bnerv_set_error(BNERV_E_ARG, "loss: MS-SSIM needs min(H,W) > 160 (got %dx%d)", d.H, d.W);
     FftLaunch F{};
     if (use_fft) {
-        if (const int rc_f = fft_launch_args(c, ws, L, BNERV_FFT_MAX_RADIX, 160 * 1024, false, "loss", F)) return rc_f;
+        if (const int rc_f = fft_launch_args(c, ws, L, BNERV_FFT_MAX_RADIX, FFT_LDS_PER_BLOCK, loss_fft_static_lds(), false, "loss", F)) return rc_f;
         F.a.accumulate = 1;
     }
     const FinalArgs f = final_args(c, ws, L, use_ms ? ws + L.msval : nullptr, d.c_ms);
@@ -1059,7 +1091,7 @@ extern "C" int bnerv_loss_ssim_fwd_bwd(void* stream, const bnerv_loss_desc* dp, 
     BNERV_REQUIRE((size_t)L.tiles[0] * BC + (size_t)BC * d.H + (size_t)NSB * d.B < (size_t)1 << 30, "loss_ssim: batch too large for one grid");
     FftLaunch F{};
     if (use_fft) {
-        if (const int rc_f = fft_launch_args(c, ws, L, SSIM_FFT_MAX_RADIX, 128 * 1024, true, "loss_ssim", F)) return rc_f;
+        if (const int rc_f = fft_launch_args(c, ws, L, SSIM_FFT_MAX_RADIX, 128 * 1024, ssim_fft_static_lds(), true, "loss_ssim", F)) return rc_f;
         if (const int rc_lds = dyn_lds<&ssim_fft_rows_fwd_kernel>(F.lds_row, "ssim_fft_rows_fwd")) return rc_lds;
         hipLaunchKernelGGL(ssim_fft_rows_fwd_kernel, dim3(F.nrowblk), dim3(256), F.lds_row, st, F.a);
         BNERV_LAUNCH_CHECK("ssim_fft_rows_fwd");
@@ -1133,7 +1165,8 @@ extern "C" int bnerv_psnr(void* stream, const float* o, const float* gt, float* 
 // allocates and copies synchronously, which is illegal inside a stream capture).
 extern "C" int bnerv_fft_prepare(int H, int W) {
     FftPlan p;
-    if (!make_plan(H, &p) || !make_plan(W, &p)) return bnerv_set_error(BNERV_E_ARG, "fft_prepare: %dx%d unsupported", H, W);
+    if (!make_plan(H, &p) || !make_plan(W, &p)) return bnerv_set_error(BNERV_E_ARG, "fft_prepare: %dx%d has a prime factor > %d", H, W, BNERV_FFT_MAX_RADIX);
+    (void)loss_fft_static_lds();                          // (read here so that a captured call finds it cached; a failure is reported by that call)
     return BNERV_OK;
 }
 
@@ -1142,5 +1175,6 @@ extern "C" int bnerv_loss_ssim_prepare(int H, int W) {
     FftPlan p;
     if (!make_plan(H, &p, SSIM_FFT_MAX_RADIX) || !make_plan(W, &p, SSIM_FFT_MAX_RADIX))
         return bnerv_set_error(BNERV_E_ARG, "loss_ssim_prepare: %dx%d has a prime factor > %d", H, W, SSIM_FFT_MAX_RADIX);
+    (void)ssim_fft_static_lds();
     return BNERV_OK;
 }

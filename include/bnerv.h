@@ -409,7 +409,12 @@ int bnerv_dwconv_wgrad(void* stream, const float* x, const float* g, float* dwb,
  * MS-SSIM and SSIM follow pytorch_msssim 0.2.1 (win 11, sigma 1.5; 5 levels / one level, ssim_b = mean over channels and valid window
  * positions of lum * cs, no relu) -- third-party, PARITY UNPINNED.  MS-SSIM needs min(H, W) > 160, SSIM min(H, W) >= 11.
  * The 2-D DFT is a mixed-radix LDS FFT; H and W may have any prime factors <= BNERV_FFT_MAX_RADIX.
- * (bnerv_loss_ssim_fwd_bwd, whose frames may be as small as 11 x 11: <= 37, its own kernel instantiations).
+ * (bnerv_loss_ssim_fwd_bwd, whose frames may be as small as 11 x 11: <= 37, its own kernel instantiations).  A side may be 1 or 2.
+ * A row (20 W bytes: line, twiddle and position tables) and four columns (40 H bytes) must fit the 160 KB of LDS of a block NEXT TO the static LDS
+ * of every kernel of the entry point that may run that transform; the entry reads those sizes from the loaded code object.  As built: W <= 8117
+ * (1488 static bytes in the merged head launch) and H <= 4094 (48 in the merged column launch) for bnerv_loss_fwd_bwd, whatever its coefficients;
+ * W <= 6553 (this path keeps its rows below 128 KB) and H <= 4095 for bnerv_loss_ssim_fwd_bwd.  A larger frame with c_fft != 0 is BNERV_E_ARG, before
+ * anything is launched; bnerv_fft_prepare / bnerv_loss_ssim_prepare check the prime factors only.
  * stats_out: [B, BNERV_LOSS_STATS] = {loss_b, sum|d|, sum d^2, ms_ssim_b (bnerv_loss_ssim_fwd_bwd: ssim_b), psnr_b (hnerv_utils.py:400-403)};
  * loss_out: [1].
  * ------------------------------------------------------------------------------------------------------------------ */

@@ -1082,7 +1082,11 @@ def test_wide_split_kernels_keep_the_f32_contract():
     assert r3.returncode == 1 and "OUTSIDE" in r3.stdout, r3.stdout[-3000:] + r3.stderr[-2000:]
 
 
-@pytest.mark.parametrize("shape", [(1, 3, 720, 1280), (2, 3, 176, 208), (1, 1, 192, 352), (1, 3, 1080, 1920), (2, 3, 180, 270)])
+# odd sides of generic primes (11 * 17 x 13 * 17, 7 * 23 x 7 * 31), an odd pyramid; 161: the smallest legal MS-SSIM side
+ODD_PRIME_MS_SHAPES = [(1, 3, 187, 221), (1, 1, 161, 217)]
+
+
+@pytest.mark.parametrize("shape", [(1, 3, 720, 1280), (2, 3, 176, 208), (1, 1, 192, 352), (1, 3, 1080, 1920), (2, 3, 180, 270)] + ODD_PRIME_MS_SHAPES)
 def test_fused_msssim_launches_equal_the_level_by_level_form(ops, shape, monkeypatch):
     """(The last two shapes have ODD pyramid levels -- 1080 -> ... -> 135 -> 68, and odd from level 0: there the padded 2x2 means stay a
     launch per level; the statistics of the five levels share one launch (round 4) and, since round 5, the gradient takes the same two
@@ -1105,7 +1109,7 @@ def test_fused_msssim_launches_equal_the_level_by_level_form(ops, shape, monkeyp
     assert (ga - gb).abs().max().item() <= 3e-5 * gb.abs().max().item()      # (a0 + 2 x a1 + y a2 cancels: a different contraction shows at 1e-5 of the largest entry)
 
 
-@pytest.mark.parametrize("shape", [(1, 3, 720, 1280), (2, 3, 176, 208), (1, 3, 1080, 1920), (2, 3, 180, 270)])
+@pytest.mark.parametrize("shape", [(1, 3, 720, 1280), (2, 3, 176, 208), (1, 3, 1080, 1920), (2, 3, 180, 270)] + ODD_PRIME_MS_SHAPES)
 def test_merged_loss_launches_change_no_bit(ops, shape, monkeypatch):
     """Fusion10_freq: independent launches share one grid as block ranges (row FFTs | pyramid | L1 / L2 sums; column FFTs | MS-SSIM
     coefficients; adjoint row FFTs | coarse SSIM gradients; level-0 gradient | loss_final -- 5 launches instead of 10 on an even pyramid,
@@ -1124,7 +1128,7 @@ def test_merged_loss_launches_change_no_bit(ops, shape, monkeypatch):
         assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("shape", [(1, 3, 720, 1280), (1, 3, 1080, 1920), (2, 3, 180, 270)])
+@pytest.mark.parametrize("shape", [(1, 3, 720, 1280), (1, 3, 1080, 1920), (2, 3, 180, 270)] + ODD_PRIME_MS_SHAPES)
 def test_spectral_gradient_first_or_last_is_the_same_gradient(ops, shape, monkeypatch):
     """The adjoint row FFTs either write the spectral gradient before the level-0 SSIM launch adds to it (default: they share the coarse
     SSIM launch) or accumulate onto the finished gradient as a last launch (BNERV_LOSS_ADJ=late, round 4's order).  Same terms, one rounding
