@@ -60,18 +60,23 @@ void bnerv_side_push(bnerv_ctx* ctx, hipStream_t st, const void* src, int n_slab
     hipLaunchKernelGGL(side_flush_kernel, dim3(sp.n_slices), dim3(256), 0, st, sp);
 }
 
-void bnerv_side_take(bnerv_ctx* ctx, SidePack* sp, int max_slices) {
+void bnerv_side_take(bnerv_ctx* ctx, SidePack* sp, int max_slices, bool step_over) {
     sp->n_jobs = 0;
     sp->n_slices = 0;
     if (!ctx) return;
     std::vector<SideJob>& q = ctx->queue;
-    // queued jobs in issue order; fold jobs (sidejob.h) stay behind for the flush kernels and are stepped over -- the jobs are independent of
-    // one another (distinct outputs), the order only keeps the oldest slabs moving first
+    // queued jobs in issue order; fold jobs (sidejob.h) stay behind for the flush kernels and are stepped over, and so is, for the callers
+    // that ask for it, a job too large for what is left of this launch's cap -- the jobs are independent of one another (distinct outputs),
+    // the order only keeps the oldest slabs moving first
     int n = 0;
     size_t i = 0;
     while (i < q.size() && n < SIDE_MAX_JOBS) {
         if (q[i].fs) { ++i; continue; }
-        if (sp->n_slices + q[i].slices > max_slices) break;
+        if (sp->n_slices + q[i].slices > max_slices) {
+            if (!step_over) break;
+            ++i;
+            continue;
+        }
         sp->j[n] = q[i];
         sp->n_slices += q[i].slices;
         ++n;

@@ -57,8 +57,10 @@ void* bnerv_ctx_scratch(bnerv_ctx* ctx, size_t bytes, hipStream_t st);
 // runs the reduction at once on `st`.
 void bnerv_side_push(bnerv_ctx* ctx, hipStream_t st, const void* src, int n_slabs, int count, int ncols, float* out, float* out2,
                      const float* fold_scale = nullptr, const float* fold_shift = nullptr);
-void bnerv_side_take(bnerv_ctx* ctx, SidePack* sp, int max_slices);   // moves up to SIDE_MAX_JOBS queued jobs (while their slices fit
-                                                         // max_slices) into *sp (n_jobs = 0 if none): a small grid must not host a big reduction
+// moves up to SIDE_MAX_JOBS queued jobs (while their slices fit max_slices) into *sp (n_jobs = 0 if none): a small grid must not host a big
+// reduction.  A job that does not fit ends the walk; with step_over (the low-resolution paired launches, whose caps are a few hundred
+// slices) it is left for a larger launch or the flush and the smaller jobs behind it are still taken.
+void bnerv_side_take(bnerv_ctx* ctx, SidePack* sp, int max_slices, bool step_over = false);
 int bnerv_side_flush(bnerv_ctx* ctx, hipStream_t st);    // standalone launch(es) for everything still queued
 int bnerv_side_pending(const bnerv_ctx* ctx);
 

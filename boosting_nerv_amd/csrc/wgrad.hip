@@ -645,7 +645,7 @@ __device__ __forceinline__ void wgrad_lean_body(const WArgs& wa, const int n_gro
     if (has_work) {
         issue(it);
         if constexpr (AFF) { load_affine(it.b); aff_b = it.b; }
-        commit(it);
+        if (!((BNERV_WABL & 4) && d.B > 0)) commit(it);
     }
     WTRACE(7, 1);
     int wt = 0; (void)wt;
@@ -658,6 +658,7 @@ __device__ __forceinline__ void wgrad_lean_body(const WArgs& wa, const int n_gro
         WTRACE(wt, 1);
         const Pre pre = prep(nxt);
         WTRACE(wt, 2);
+        if (!((BNERV_WABL & 8) && d.B > 0))
 #pragma unroll
         for (int st = 0; st < 16; ++st) {
             if (has_next) {                                // the next tile's loads, spread over the K steps
@@ -677,7 +678,7 @@ __device__ __forceinline__ void wgrad_lean_body(const WArgs& wa, const int n_gro
         WTRACE(wt, 5);
         if (has_next) {
             if constexpr (AFF) { if (nxt.b != aff_b) { load_affine(nxt.b); aff_b = nxt.b; } }
-            commit(nxt);
+            if (!((BNERV_WABL & 4) && d.B > 0)) commit(nxt);
         }
         WTRACE(wt, 6);
         it = nxt;
@@ -688,6 +689,7 @@ __device__ __forceinline__ void wgrad_lean_body(const WArgs& wa, const int n_gro
     __syncthreads();
     float* s_red = smem;
     constexpr int RW = NTW * 16, RSZ = 16 * RW;
+    if (!((BNERV_WABL & 2) && d.B > 0)) {
 #pragma unroll
     for (int n = 0; n < NTW; ++n)
 #pragma unroll
@@ -699,8 +701,9 @@ __device__ __forceinline__ void wgrad_lean_body(const WArgs& wa, const int n_gro
         if (row < Cout && col < wa.ncols)
             slab[(size_t)row * wa.ncols + col] = (s_red[idx] + s_red[RSZ + idx]) + (s_red[2 * RSZ + idx] + s_red[3 * RSZ + idx]);
     }
+    }
     WTRACE(7, 3);
-    side_run_hosted(side, smem, vb, vgrid);                // queued slab reductions of EARLIER launches (sidejob.h)
+    if (!(BNERV_WABL & 1)) side_run_hosted(side, smem, vb, vgrid);   // queued slab reductions of EARLIER launches (sidejob.h)
     WTRACE(7, 4);
 }
 template <int KS, int IN, int GM2>
@@ -712,8 +715,11 @@ __global__ __launch_bounds__(256, (KS == 3 ? 3 : 4)) void wgrad_lean_kernel(cons
 // block counts and the same tile walk (large layers: n_conv < 0, see launch_pair).  Inside a TAT block's backward the pairs are
 // (dW1 | dconv1), (dW0 | dconv0), (dW_block | dconv_block): each pair reads the same incoming gradient, and neither half fills the
 // chip through its prologue and tail (at 180x320 each is one tile per block: two latency-bound launches become one).
+// Queued slab reductions ride on ONE role, chosen by the launcher (pair_hosts_on_conv): side_c is the conv role's pack, side_w the weight
+// gradient's, and one of the two is empty.
 template <int EP, int WIN>
-__global__ __launch_bounds__(256, 3) void conv_wgrad_pair_kernel(const bnerv_conv::KArgs ka, const WArgs wa, const int n_grows, const int n_conv, const SidePack side, const int pat) {
+__global__ __launch_bounds__(256, 3) void conv_wgrad_pair_kernel(const bnerv_conv::KArgs ka, const WArgs wa, const int n_grows, const int n_conv, const SidePack side_c,
+                                                                 const SidePack side_w, const int pat) {
     if (n_conv < 0) {
         // interleaved roles (n_conv = -(blocks per role)): XCD-local slots alternate conv / weight gradient, and block k of either role
         // walks the same tile list on the same XCD -- what one reads of the shared gradient (and of the conv's aux = the weight
@@ -721,20 +727,18 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_pair_kernel(const bnerv_con
         const int nr = -n_conv, xcd = (int)blockIdx.x & 7, slot = (int)blockIdx.x >> 3, vb = ((slot >> 1) << 3) + xcd;
         const int role = pat == 0 ? (slot & 1) : ((slot + (slot >> pat)) & 1);
         if (role == 0) {
-            SidePack none;
-            none.n_jobs = 0; none.n_slices = 0;
-            bnerv_q4::conv_q4_body<BNERV_IN_PLAIN, EP>(ka, none, vb, nr);
+            bnerv_q4::conv_q4_body<BNERV_IN_PLAIN, EP>(ka, side_c, vb, nr);
         } else {
-            wgrad_lean_body<3, WIN, 0>(wa, n_grows, side, vb, nr);
+            if (BNERV_WABL & 16) return;
+            wgrad_lean_body<3, WIN, 0>(wa, n_grows, side_w, vb, nr);
         }
         return;
     }
     if ((int)blockIdx.x < n_conv) {                        // block-uniform
-        SidePack none;
-        none.n_jobs = 0; none.n_slices = 0;
-        bnerv_q4::conv_q4_body<BNERV_IN_PLAIN, EP>(ka, none, (int)blockIdx.x, n_conv);
+        bnerv_q4::conv_q4_body<BNERV_IN_PLAIN, EP>(ka, side_c, (int)blockIdx.x, n_conv);
     } else {
-        wgrad_lean_body<3, WIN, 0>(wa, n_grows, side, (int)blockIdx.x - n_conv, (int)gridDim.x - n_conv);
+        if (BNERV_WABL & 16) return;
+        wgrad_lean_body<3, WIN, 0>(wa, n_grows, side_w, (int)blockIdx.x - n_conv, (int)gridDim.x - n_conv);
     }
 }
 
@@ -823,13 +827,17 @@ static int launch_wlean_modes(hipStream_t st, const WArgs& wa) {
 // (38 ch: 3x6 -> 4 groups of 96 for 343 columns; 46 ch: 3x7 -> 4 groups of 112 for 415), within the 256-VGPR budget.
 // GM2: 0 = g as is, 1 = g is the pixel-shuffled (x2) gradient (two float4 per cout PAIR), 2 = tanh-grad (g, gaux),
 //      3 = pixel-shuffled by g_s (3, 5): one dword per pixel, g_s apart
+// the cross-wave reduction's form (wgrad_bfw_body.h has the same): one LDS area per wave and one barrier for the shapes that run three
+// blocks per CU (four areas of 1 x 8 tiles are 32 KB, less than the accumulation phase holds); the larger shapes keep the one-area form
+template <int MTW, int NTW> constexpr bool wide_one_barrier() { return MTW * NTW <= 8 && !BNERV_WRED4; }
 // dynamic LDS of the body: gradient rows + input planes while it accumulates, never less than the rows the A reads and the reduction touch
 template <int MTW, int NTW>
 size_t wgrad_wide_lds_bytes(int Cout) {
     const int g_rows = Cout < MTW * 16 ? Cout : MTW * 16;
     size_t fl = (size_t)g_rows * CSG + (size_t)(wgrad_npl<3, NTW>() + 2) * Geo<3>::PLANE + 64;
     if (fl < (size_t)MTW * 16 * CSG) fl = (size_t)MTW * 16 * CSG;
-    if (fl < (size_t)MTW * 16 * NTW * 16) fl = (size_t)MTW * 16 * NTW * 16;
+    const size_t red = (size_t)(wide_one_barrier<MTW, NTW>() ? 4 : 1) * MTW * 16 * NTW * 16;
+    if (fl < red) fl = red;
     return fl * sizeof(float);
 }
 template <int IN, int GM2, int MTW, int NTW>
@@ -1062,7 +1070,7 @@ __device__ __forceinline__ void wgrad_wide_body(const WArgs& wa, const int slots
 #pragma unroll
         for (int part = 0; part < NPART; ++part) issue_part(p0, part);
         if constexpr (AFF) { load_affine(it.b); aff_b = it.b; }
-        commit(it);
+        if (!((BNERV_WABL & 4) && d.B > 0)) commit(it);
     }
     for (; itx < r1; itx += slots) {
         const bool has_next = itx + slots < r1;
@@ -1077,6 +1085,7 @@ __device__ __forceinline__ void wgrad_wide_body(const WArgs& wa, const int slots
         for (int m = 0; m < MTW; ++m) af[0][m] = s_g[abase + m * 16 * CSG];
 #pragma unroll
         for (int n = 0; n < NTW; ++n) bf[0][n] = s_in[bbase[n]];
+        if (!((BNERV_WABL & 8) && d.B > 0))
 #pragma unroll
         for (int st = 0; st < 16; ++st) {
             if (has_next) {                                // the next tile's loads, spread over the K steps
@@ -1099,15 +1108,27 @@ __device__ __forceinline__ void wgrad_wide_body(const WArgs& wa, const int slots
         lds_barrier();                                     // everyone done reading tile t
         if (has_next) {
             if constexpr (AFF) { if (nxt.b != aff_b) { load_affine(nxt.b); aff_b = nxt.b; } }
-            commit(nxt);
+            if (!((BNERV_WABL & 4) && d.B > 0)) commit(nxt);
         }
         it = nxt;
     }
 
-    // cross-wave reduction, one wave after the other into one area (fixed order), then this block's columns of the slot's slab
+    // cross-wave reduction in a fixed order, then this block's columns of the slot's slab: one area per wave, added by the store loop as
+    // ((w0 + w1) + w2) + w3 behind one barrier (wide_one_barrier), or one wave after the other into one area -- the same sum
     __syncthreads();
     float* s_red = smem;
     constexpr int RW = NTW * 16, RSZ = MTW * 16 * RW;
+    constexpr bool ONEB = wide_one_barrier<MTW, NTW>();
+    if (!((BNERV_WABL & 2) && d.B > 0)) {
+    if constexpr (ONEB) {
+#pragma unroll
+        for (int m = 0; m < MTW; ++m)
+#pragma unroll
+            for (int n = 0; n < NTW; ++n)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) s_red[wave * RSZ + (m * 16 + 4 * kq + r) * RW + n * 16 + li] = acc[m][n][r];
+        __syncthreads();
+    } else
     for (int w = 0; w < 4; ++w) {
         if (wave == w) {
 #pragma unroll
@@ -1126,9 +1147,12 @@ __device__ __forceinline__ void wgrad_wide_body(const WArgs& wa, const int slots
     for (int idx = tid; idx < RSZ; idx += 256) {
         const int row = idx / RW, colq = idx - row * RW;
         const int col = n_base + colq;
-        if (co_base + row < Cout && col < wa.ncols) slab[(size_t)(co_base + row) * wa.ncols + col] = s_red[idx];
+        float v = s_red[idx];
+        if constexpr (ONEB) v = ((v + s_red[RSZ + idx]) + s_red[2 * RSZ + idx]) + s_red[3 * RSZ + idx];
+        if (co_base + row < Cout && col < wa.ncols) slab[(size_t)(co_base + row) * wa.ncols + col] = v;
     }
-    side_run_hosted(side, smem, vb, vgrid);
+    }
+    if (!(BNERV_WABL & 1)) side_run_hosted(side, smem, vb, vgrid);
 }
 
 struct WidePlan { int mtw, ntw, ngroups, mgroups, slots; };
@@ -1461,6 +1485,11 @@ enum { Q4P_INTERLEAVED, Q4P_SHARED, Q4P_FOLD };
 struct Q4PairPlan { int kind, grid, n_conv, n_w; };     // n_w: the weight gradient's slabs
 constexpr int PAIR_MIX = 384, PAIR_PAT = 5;
 
+// Which role of a paired launch runs the queued slab reductions (sidejob.h).  With several items per block about half of the weight
+// gradient's blocks own one item less and host for nothing; with at most one item per block nothing is free, the weight gradient's chain
+// (staging, K loop, cross-wave reduction, slab store) is the launch's long pole and the conv role, which finishes first, hosts instead.
+inline bool pair_hosts_on_conv(int items, int blocks) { return items <= blocks; }
+
 Q4PairPlan q4_pair_plan(const bnerv_conv_desc& c, const bnerv_wgrad_desc& w) {
     Q4PairPlan p{};
     const int total_items = c.B * cdiv(c.W, bnerv_conv::TW) * cdiv(c.H, bnerv_conv::TH), ncols = w.Cin * 9 + 1;
@@ -1528,8 +1557,12 @@ int launch_pair(hipStream_t st, bnerv_conv::KArgs& ka, const WArgs& wa, const Q4
     const size_t lw = wlean_lds_bytes<3>(n_grows);
     if (lw > lds) lds = lw;
     if (const int rc = dyn_lds<&conv_wgrad_pair_kernel<EP, WIN>>(lds, "conv_wgrad_pair")) return rc;
-    bnerv_side_take(wa.d.ctx, &side, 2 * p.n_w);
-    hipLaunchKernelGGL((conv_wgrad_pair_kernel<EP, WIN>), dim3(p.grid), dim3(256), lds, st, ka, wa, n_grows, p.n_conv, side, PAIR_PAT);
+    // one item per block in both roles (180x320 and below): the conv role finishes first and hosts; its padding blocks take the first slices
+    SidePack none;
+    none.n_jobs = 0; none.n_slices = 0;
+    const bool on_conv = p.n_conv > 0 && pair_hosts_on_conv(ka.total_items, p.n_conv);
+    bnerv_side_take(wa.d.ctx, &side, 2 * (on_conv ? p.n_conv : p.n_w), true);
+    hipLaunchKernelGGL((conv_wgrad_pair_kernel<EP, WIN>), dim3(p.grid), dim3(256), lds, st, ka, wa, n_grows, p.n_conv, on_conv ? side : none, on_conv ? none : side, PAIR_PAT);
     BNERV_LAUNCH_CHECK("conv_wgrad_pair");
     return BNERV_OK;
 }
@@ -1552,27 +1585,36 @@ struct BfwRole {
 };
 template <class WR, int CIN, int CEP, int CNQ>
 __global__ __launch_bounds__(256, 2) void small_pair_kernel(const bnerv_convs::SArgs sa, const WArgs wa, const WideRoleArgs r, const int n_c, const int n_c8,
-                                                            const int c_tiles, const int c_groups, const SidePack side) {
+                                                            const int c_tiles, const int c_groups, const SidePack side_c, const SidePack side_w) {
+    // (side_c / side_w: the queued slab reductions, given to one role by the launcher -- pair_hosts_on_conv -- and empty for the other)
+    extern __shared__ __attribute__((aligned(16))) float smem[];
     const int b = (int)blockIdx.x;
     if (b < n_c8) {
-        if (b >= n_c) return;                              // (padding block)
-        const int q = b / c_tiles;
-        bnerv_convs::conv_small_body<CIN, CEP, CNQ>(sa, b - q * c_tiles, q % c_groups, q / c_groups);
+        if (b < n_c) {                                     // (else a padding block: it only hosts)
+            const int q = b / c_tiles;
+            bnerv_convs::conv_small_body<CIN, CEP, CNQ>(sa, b - q * c_tiles, q % c_groups, q / c_groups);
+        }
+        if (!(BNERV_WABL & 1)) side_run_hosted(side_c, smem, b, n_c8);   // (its own barrier first: the body's LDS is free)
     } else {
-        WR::run(wa, r, side, b - n_c8, (int)gridDim.x - n_c8);
+        if (BNERV_WABL & 16) return;
+        WR::run(wa, r, side_w, b - n_c8, (int)gridDim.x - n_c8);
     }
 }
 template <class WR, int CIN, int CEP, int CNQ>
-int launch_small_pair(hipStream_t st, const bnerv_convs::SArgs& sa, const WArgs& wa, const WideRoleArgs& r, int n_w) {
+int launch_small_pair(hipStream_t st, const bnerv_convs::SArgs& sa, const WArgs& wa, const WideRoleArgs& r, int n_w, int w_tiles) {
     size_t lds = bnerv_convs::convs_lds_bytes<CNQ>();
     const size_t lw = WR::lds(wa);
     if (lw > lds) lds = lw;
     if (const int rc = dyn_lds<&small_pair_kernel<WR, CIN, CEP, CNQ>>(lds, "small_pair")) return rc;
     const int c_tiles = sa.tiles_x * sa.tiles_y, c_groups = cdiv(sa.d.Cout, 16);
     const int n_c = c_tiles * c_groups * sa.d.B, n_c8 = (n_c + 7) & ~7;
-    SidePack side;
-    bnerv_side_take(wa.d.ctx, &side, 2 * n_w);
-    hipLaunchKernelGGL((small_pair_kernel<WR, CIN, CEP, CNQ>), dim3(n_c8 + n_w), dim3(256), lds, st, sa, wa, r, n_c, n_c8, c_tiles, c_groups, side);
+    // the conv role's blocks own one tile each; where no weight-gradient block owns more than one either, the conv role hosts
+    SidePack side, none;
+    none.n_jobs = 0; none.n_slices = 0;
+    const bool on_conv = pair_hosts_on_conv(w_tiles, 8 * r.slots);
+    bnerv_side_take(wa.d.ctx, &side, 2 * (on_conv ? n_c8 : n_w), true);
+    hipLaunchKernelGGL((small_pair_kernel<WR, CIN, CEP, CNQ>), dim3(n_c8 + n_w), dim3(256), lds, st, sa, wa, r, n_c, n_c8, c_tiles, c_groups, on_conv ? side : none,
+                       on_conv ? none : side);
     BNERV_LAUNCH_CHECK("small_pair");
     return BNERV_OK;
 }
@@ -1613,8 +1655,9 @@ int small_pair_launch(hipStream_t st, const bnerv_conv_desc& c, const WArgs& wa,
     const bool bf = wr.family == BNERV_WGRAD_FAM_WIDE_BF16;
     const WideRoleArgs r = bf ? WideRoleArgs{wr.bw.slots, wr.bw.ngroups_n, wr.bw.ngroups_m} : WideRoleArgs{wr.wide.slots, 0, 0};
     const int n_w = bf ? 8 * wr.bw.slots * wr.bw.ngroups_n * wr.bw.ngroups_m : 8 * wr.wide.slots * wr.wide.ngroups * wr.wide.mgroups;
+    const int w_tiles = wa.d.B * cdiv(wa.d.H, bf ? BW_TH : TH) * cdiv(wa.d.W, TW);          // the weight-gradient role's tiles (32 px wide in both families)
     return small_pair_modes(c, wa.d, wr, [&](auto role, auto in, auto ep, auto nq) {
-        return launch_small_pair<typename decltype(role)::type, decltype(in)::value, decltype(ep)::value, decltype(nq)::value>(st, sa, wa, r, n_w);
+        return launch_small_pair<typename decltype(role)::type, decltype(in)::value, decltype(ep)::value, decltype(nq)::value>(st, sa, wa, r, n_w, w_tiles);
     });
 }
 }  // namespace

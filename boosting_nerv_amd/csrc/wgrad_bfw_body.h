@@ -8,6 +8,9 @@
 #ifndef BTRACE
 #define BTRACE(it_, slot) do {} while (0)
 #endif
+#ifndef BNERV_WABL
+#define BNERV_WABL 0   // debug ablations of the weight-gradient role (never shipped; tools/ksmall.py): bit 0 no hosted jobs, 1 no cross-wave
+#endif                 // reduction + slab store, 2 no staging stores, 3 no K loop, 4 the paired launches' weight-gradient role returns at once
 
 namespace bnerv_wb {
 
@@ -29,6 +32,14 @@ __device__ __forceinline__ f32x4 bload(__amdgpu_buffer_rsrc_t r, unsigned voff, 
 }
 
 struct LTile { int b, ty, tx; };
+// the cross-wave reduction's form: one LDS area per wave, all four written at once and added by the store loop, for up to two cout tiles per
+// pass -- 64 KB, what the accumulation phase holds anyway, so two blocks per CU stay resident; MTW = 3 takes a second pass for its third tile
+// (three areas at once would be 96 KB: one block per CU).  0: one area, the waves one after the other (four barriers, each wave's
+// read-add-write chain behind the previous one's).
+#ifndef BNERV_WRED4
+#define BNERV_WRED4 0  // debug: 1 = the one-area form everywhere (the A/B of tools/ksmall.py)
+#endif
+template <int MTW> constexpr int bfw_red_chunk() { return BNERV_WRED4 ? 0 : (MTW < 2 ? MTW : 2); }
 
 // ---------------------------------------------------------------------------------------------------------------- split wide kernel
 // The weight gradient of the 3x3 stride-1 layers with more than 16 output or 12 input channels (plain gradient: the TAT convs and the
@@ -285,7 +296,7 @@ __device__ __forceinline__ void wgrad_bfw_body(const WArgs& wa, const int slots,
         if constexpr (AFF) { load_affine(it.b); aff_b = it.b; }
         lds_barrier();
         if constexpr (AFF) fetch_affine();
-        store_x(tile_interior(it));
+        if (!((BNERV_WABL & 4) && d.B > 0)) store_x(tile_interior(it));
     }
     int bt = -3;                                          // (trace: tiles 3..9 of the block)
     for (; itx < r1; itx += slots, ++bt) {
@@ -325,6 +336,7 @@ __device__ __forceinline__ void wgrad_bfw_body(const WArgs& wa, const int slots,
         BTRACE(bt, 3);
         // (reading the B fragments one column tile ahead through a second register set was measured: no gain -- the other resident
         //  block covers the LDS latency -- and it costs the MTW = 3 variants their last registers)
+        if (!((BNERV_WABL & 8) && d.B > 0))
 #pragma unroll
         for (int nt = 0; nt < BW_NTW; ++nt) {
             u32x4 bfr[NS];
@@ -346,17 +358,48 @@ __device__ __forceinline__ void wgrad_bfw_body(const WArgs& wa, const int slots,
         BTRACE(bt, 5);
         if (has_next) {
             if constexpr (AFF) { if (nxt.b != aff_b) { load_affine(nxt.b); lds_barrier(); fetch_affine(); aff_b = nxt.b; } }
-            if (tile_interior(nxt)) store_x(true);
+            if ((BNERV_WABL & 4) && d.B > 0) {}
+            else if (tile_interior(nxt)) store_x(true);
             else store_x(false);
         }
         BTRACE(bt, 6);
         it = nxt;
     }
 
-    // cross-wave reduction, one wave after the other into one area (fixed order), then this block's columns of the slot's slab
+    // cross-wave reduction in a fixed order, then this block's columns of the slot's slab.  Every wave writes its accumulators to its own LDS
+    // area and the store loop adds them as ((w0 + w1) + w2) + w3 -- the sum that four one-after-the-other phases into one area produce --
+    // MCH cout tiles per pass (bfw_red_chunk).
     __syncthreads();
     float* s_red = smem;
     constexpr int RW = BW_NTW * 16, RSZ = MTW * 16 * RW;
+    constexpr int MCH = bfw_red_chunk<MTW>();
+    float* slab = wa.slab + (size_t)(xcd * slots + slot) * Cout * wa.ncols;
+    if (!((BNERV_WABL & 2) && d.B > 0)) {
+    if constexpr (MCH > 0) {
+        constexpr int CSZ = MCH * 16 * RW;                                    // one wave's area
+#pragma unroll
+        for (int m0 = 0; m0 < MTW; m0 += MCH) {
+            const int mc = MTW - m0 < MCH ? MTW - m0 : MCH;
+            if (m0 > 0) __syncthreads();                                      // the previous pass's areas have been read
+#pragma unroll
+            for (int m = 0; m < MCH; ++m)
+                if (m < mc) {
+#pragma unroll
+                    for (int n = 0; n < BW_NTW; ++n)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            // D fragment: column (N) = li, row (M) = 4 kq + r  ->  cout 16 m + 4 kq + r, column 16 n + li
+                            s_red[wave * CSZ + (m * 16 + 4 * kq + r) * RW + n * 16 + li] = acc[m0 + m < MTW ? m0 + m : 0][n][r];
+                }
+            __syncthreads();
+            for (int idx = tid; idx < mc * 16 * RW; idx += 256) {
+                const int row = idx / RW, colq = idx - row * RW;
+                const int col = n_base + colq, co = co_base + m0 * 16 + row;
+                const float v = ((s_red[idx] + s_red[CSZ + idx]) + s_red[2 * CSZ + idx]) + s_red[3 * CSZ + idx];
+                if (co < Cout && col < wa.ncols) slab[(size_t)co * wa.ncols + col] = v;
+            }
+        }
+    } else {
     for (int w = 0; w < 4; ++w) {
         if (wave == w) {
 #pragma unroll
@@ -365,27 +408,27 @@ __device__ __forceinline__ void wgrad_bfw_body(const WArgs& wa, const int slots,
                 for (int n = 0; n < BW_NTW; ++n)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        // D fragment: column (N) = li, row (M) = 4 kq + r  ->  cout 16 m + 4 kq + r, column 16 n + li
                         float* qd = s_red + (m * 16 + 4 * kq + r) * RW + n * 16 + li;
                         *qd = (w == 0) ? acc[m][n][r] : *qd + acc[m][n][r];
                     }
         }
         __syncthreads();
     }
-    float* slab = wa.slab + (size_t)(xcd * slots + slot) * Cout * wa.ncols;
     for (int idx = tid; idx < RSZ; idx += 256) {
         const int row = idx / RW, colq = idx - row * RW;
         const int col = n_base + colq;
         if (co_base + row < Cout && col < wa.ncols) slab[(size_t)(co_base + row) * wa.ncols + col] = s_red[idx];
     }
-    side_run_hosted(side, smem, vb, vgrid);
+    }
+    }
+    if (!(BNERV_WABL & 1)) side_run_hosted(side, smem, vb, vgrid);
 }
 
 struct BwPlan { int mtw, ngroups_n, ngroups_m, slots; };
 // dynamic LDS of wgrad_bfw_body: the input pieces + affine table while it accumulates, the block's output rows while it reduces
 template <int SP, int MTW>
 constexpr size_t wgrad_bfw_lds_bytes() {
-    const size_t acc = (size_t)Split<SP>::NS * BW_PIECE + 2 * BW_NPL * sizeof(float), red = (size_t)MTW * 16 * BW_NTW * 16 * sizeof(float);
+    const size_t acc = (size_t)Split<SP>::NS * BW_PIECE + 2 * BW_NPL * sizeof(float), red = (size_t)(bfw_red_chunk<MTW>() ? 4 * bfw_red_chunk<MTW>() : MTW) * 16 * BW_NTW * 16 * sizeof(float);
     return acc > red ? acc : red;
 }
 

@@ -1,6 +1,9 @@
 """Per-launch times of the LOW-RESOLUTION conv launches of the C1 step (<= 180x320: forward up-convs and TAT convs, and their backward
 pairs), each replayed as a captured graph of its own launches (bench._time_launches).  usage: python tools/ksmall.py [reps]
-BNERV_LIB=<variant .so> selects an ablation build (csrc/convs_body.h BNERV_ABLS)."""
+BNERV_LIB=<variant .so> selects an ablation build: -DBNERV_ABLS=<bits> (csrc/convs_body.h) for the low-resolution conv body, -DBNERV_WABL=<bits>
+(csrc/wgrad_bfw_body.h) for the weight-gradient role of the pairs -- 1 no hosted jobs, 2 no cross-wave reduction + slab store, 4 no staging
+stores, 8 no K loop, 16 the role returns at once (the conv role alone; 17: alone and hosting nothing) -- and -DBNERV_WRED4=1 for the one-area
+cross-wave reduction.  Only wgrad.hip needs the flag; profiles/small_pair_wgrad_phases.md is this tool's output over those builds."""
 import os
 import sys
 
