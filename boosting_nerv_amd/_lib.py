@@ -180,6 +180,11 @@ SYMBOLS = {
     "bnerv_ssim": (_I, [_V, _V, _V, _V, _V, _Z, _I, _I, _I, _I]),
     "bnerv_tanh_grad_blocks": (_I, [_I]),
     "bnerv_tanh_grad": (_I, [_V, _V, _V, _V, _V, _I, _I, _I]),
+    "bnerv_inpaint_head": (_I, [_V, _V, _V, _V, _V, _I, _I, _I]),
+    "bnerv_inpaint_ws_bytes": (_Z, [_I, _I, _I]),
+    "bnerv_inpaint_pred": (_I, [_V, _V, _V, _V, _V, _V, _Z, _I, _I, _I]),
+    "bnerv_inpaint_psnr": (_I, [_V, _V, _Z, _V, _I, _I, _I, _I]),
+    "bnerv_inpaint_grad": (_I, [_V, _V, _V, _I, _I, _I]),
     "bnerv_psnr_ws_bytes": (_Z, [_I, _I, _I, _I]),
     "bnerv_psnr": (_I, [_V, _V, _V, _V, _V, _Z, _I, _I, _I, _I]),
     "bnerv_adan_multi_tensor": (_I, [_V, C.POINTER(AdanChunk), C.POINTER(AdanHyper)]),
@@ -187,6 +192,8 @@ SYMBOLS = {
     "bnerv_adan_table": (_I, [_V, _V, _I, _I, C.POINTER(AdanHyper)]),
     "bnerv_adam_table_blocks": (_I, [_I]),
     "bnerv_adam_table": (_I, [_V, _V, _I, _I, C.POINTER(AdanHyper)]),
+    "bnerv_grad_sqsum_table": (_I, [_V, _V, _I, _I, _V]),
+    "bnerv_grad_scale_table": (_I, [_V, _V, _I, _I, _V, _I, _F, _V]),
     "bnerv_fetch_frame": (_I, [_V, _V, _V, _V, _I, _Z, _V, _V]),
     "bnerv_bucket_gather": (_I, [_V, C.POINTER(BucketChunk), _V, _F]),
     "bnerv_bucket_scatter": (_I, [_V, C.POINTER(BucketChunk), _V, _F]),

@@ -1,4 +1,5 @@
-// optim.hip -- fused multi-tensor Adan step and the flat-bucket gather/scatter used by the data-parallel exchange.
+// optim.hip -- fused multi-tensor Adan / Adam step, the device-side global-norm gradient clip in front of it, and the flat-bucket
+// gather/scatter used by the data-parallel exchange.
 //
 // Adan semantics follow the reference's default path exactly (optimizer.py:296-362 `_multi_tensor_adan`, called from
 // Adan.step optimizer.py:125-235 with betas (0.98, 0.92, 0.99), eps 1e-8, weight_decay 0, no clipping), one pass over
@@ -130,6 +131,82 @@ __global__ __launch_bounds__(256) void adam_table_kernel(const bnerv_adan_entry*
     }
 }
 
+// Global-norm gradient clip over the same device table (torch.nn.utils.clip_grad_norm_ with its defaults; reference train_nerv_all.py:346-347):
+//   total = sqrt(sum g^2);  coef = min(1, max_norm / (total + 1e-6));  g *= coef
+// Two launches with the block partition of the optimizer kernels above, no atomics: each block leaves the sum of squares of its slice as one
+// double, then every block re-adds ALL partials in one fixed order (lane l adds l, l + 64, ..., then a wave tree, as cem.hip's chunk_total),
+// so all blocks scale by the same bits.  A gradient may start at any 4-byte boundary: 16-byte loads over the aligned body, the (at most three)
+// elements before and after it go to the first block of the tensor.
+struct GradSpan { int head, nq, tail0; };      // [0, head) | nq quads from head | [tail0, n)
+__device__ __forceinline__ GradSpan grad_span(const float* g, int n) {
+    GradSpan s;
+    s.head = min(n, (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(g) & 15u)) & 15u) >> 2);
+    s.nq = (n - s.head) >> 2;
+    s.tail0 = s.head + s.nq * 4;
+    return s;
+}
+__device__ __forceinline__ int table_tensor(const bnerv_adan_entry* __restrict__ tab, int n_tensors) {
+    int t = 0;
+    for (int hi = n_tensors; hi - t > 1;) {
+        const int mid = (t + hi) >> 1;
+        if ((int)blockIdx.x >= tab[mid].bstart) t = mid; else hi = mid;
+    }
+    return t;
+}
+
+__global__ __launch_bounds__(256) void grad_sqsum_table_kernel(const bnerv_adan_entry* __restrict__ tab, const int n_tensors, double* __restrict__ part) {
+    __shared__ double red[4];
+    const bnerv_adan_entry e = tab[table_tensor(tab, n_tensors)];
+    const int gx = min(cdiv_dev(e.n, 256 * 4), 1024), bx = (int)blockIdx.x - e.bstart;
+    const float* __restrict__ g = e.g;
+    const GradSpan s = grad_span(g, e.n);
+    const f32x4* __restrict__ g4 = reinterpret_cast<const f32x4*>(g + s.head);
+    double acc = 0.0;
+    for (int i = bx * 256 + threadIdx.x; i < s.nq; i += gx * 256) {
+        const f32x4 v = g4[i];
+        acc += ((double)v[0] * (double)v[0] + (double)v[1] * (double)v[1]) + ((double)v[2] * (double)v[2] + (double)v[3] * (double)v[3]);
+    }
+    if (bx == 0) {
+        const int k = (int)threadIdx.x, edge = s.head + (e.n - s.tail0);      // <= 6 elements
+        if (k < edge) {
+            const float v = g[k < s.head ? k : s.tail0 + (k - s.head)];
+            acc += (double)v * (double)v;
+        }
+    }
+    acc = wave_sum_d(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(256) void grad_scale_table_kernel(const bnerv_adan_entry* __restrict__ tab, const int n_tensors, const double* __restrict__ part,
+                                                               const int n_part, const float max_norm, float* __restrict__ out) {
+    __shared__ float s_coef;
+    if (threadIdx.x < 64) {
+        double t = 0.0;
+        for (int c = threadIdx.x; c < n_part; c += 64) t += part[c];
+        t = wave_sum_d(t);
+        if (threadIdx.x == 0) {
+            const float total = (float)sqrt(t);
+            const float coef = fminf(1.0f, max_norm / (total + 1e-6f));
+            s_coef = coef;
+            if (blockIdx.x == 0) { out[0] = total; out[1] = coef; }
+        }
+    }
+    __syncthreads();
+    const float coef = s_coef;
+    const bnerv_adan_entry e = tab[table_tensor(tab, n_tensors)];
+    const int gx = min(cdiv_dev(e.n, 256 * 4), 1024), bx = (int)blockIdx.x - e.bstart;
+    float* __restrict__ g = const_cast<float*>(e.g);
+    const GradSpan s = grad_span(g, e.n);
+    f32x4* __restrict__ g4 = reinterpret_cast<f32x4*>(g + s.head);
+    for (int i = bx * 256 + threadIdx.x; i < s.nq; i += gx * 256) g4[i] = g4[i] * coef;
+    if (bx == 0) {
+        const int k = (int)threadIdx.x, edge = s.head + (e.n - s.tail0);
+        if (k < edge) g[k < s.head ? k : s.tail0 + (k - s.head)] *= coef;
+    }
+}
+
 __global__ __launch_bounds__(256) void fetch_frame_kernel(const float* __restrict__ clip, const double* __restrict__ norms, const float* __restrict__ sel,
                                                           const int n_frames, const size_t frame_elems, float* __restrict__ dst, double* __restrict__ dst_norm) {
     fetch_frame_body(clip, norms, sel, n_frames, frame_elems, dst, dst_norm, (int)blockIdx.x, (int)gridDim.x);
@@ -198,6 +275,27 @@ extern "C" int bnerv_adam_table(void* stream, const bnerv_adan_entry* table_dev,
     BNERV_REQUIRE(h->beta1 >= 0.f && h->beta1 < 1.f && h->beta2 >= 0.f && h->beta2 < 1.f && h->eps >= 0.f, "adam_table: bad hyper-parameters");
     hipLaunchKernelGGL(adam_table_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, table_dev, n_tensors, *h);
     BNERV_LAUNCH_CHECK("adam_table");
+    return BNERV_OK;
+}
+
+extern "C" int bnerv_grad_sqsum_table(void* stream, const bnerv_adan_entry* table_dev, int n_tensors, int total_blocks, double* partials) {
+    BNERV_REQUIRE(table_dev && partials, "grad_sqsum_table: null args");
+    BNERV_REQUIRE(n_tensors > 0 && total_blocks > 0, "grad_sqsum_table: n_tensors=%d total_blocks=%d", n_tensors, total_blocks);
+    BNERV_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 7) == 0, "grad_sqsum_table: partials must be 8-byte aligned (doubles)");
+    hipLaunchKernelGGL(grad_sqsum_table_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, table_dev, n_tensors, partials);
+    BNERV_LAUNCH_CHECK("grad_sqsum_table");
+    return BNERV_OK;
+}
+
+extern "C" int bnerv_grad_scale_table(void* stream, const bnerv_adan_entry* table_dev, int n_tensors, int total_blocks, const double* partials,
+                                      int n_partials, float max_norm, float* out) {
+    BNERV_REQUIRE(table_dev && partials && out, "grad_scale_table: null args");
+    BNERV_REQUIRE(n_tensors > 0 && total_blocks > 0 && n_partials >= total_blocks, "grad_scale_table: n_tensors=%d total_blocks=%d n_partials=%d",
+                  n_tensors, total_blocks, n_partials);
+    BNERV_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 7) == 0, "grad_scale_table: partials must be 8-byte aligned (doubles)");
+    BNERV_REQUIRE(max_norm >= 0.f, "grad_scale_table: max_norm=%g", (double)max_norm);
+    hipLaunchKernelGGL(grad_scale_table_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, table_dev, n_tensors, partials, n_partials, max_norm, out);
+    BNERV_LAUNCH_CHECK("grad_scale_table");
     return BNERV_OK;
 }
 

@@ -1,9 +1,9 @@
-"""The train step of train_nerv_all.py:328-350 as one object: forward -> loss -> backward -> (gradient all-reduce) -> Adan,
-with per-step PSNR accumulated on the device.  After a few eager steps the fixed-shape step is captured into hipGraphs and
+"""The train step of train_nerv_all.py:328-350 as one object: (inpainting mask ->) forward -> loss -> backward -> (gradient all-reduce)
+-> (global-norm clip) -> Adan / Adam, with per-step PSNR accumulated on the device.  After a few eager steps the fixed-shape step is captured into hipGraphs and
 replayed (≈100 short kernels per step: launch latency, not arithmetic, is what a Python-driven loop would pay for).
 
-  world == 1 :  one graph   [fwd, loss, bwd, Adan]
-  world  > 1 :  one graph   [fwd, loss, bwd, bucket-gather, RCCL all-reduce of ONE flat bucket, bucket-scatter, Adan]
+  world == 1 :  one graph   [fwd, loss, bwd, (clip,) Adan]
+  world  > 1 :  one graph   [fwd, loss, bwd, bucket-gather, RCCL all-reduce of ONE flat bucket, bucket-scatter, (clip,) Adan]
                 (two graphs around an eager all-reduce when the collective cannot be captured: gloo in the CPU-transport tests)
 
 Everything that changes per step and is not data (lr, Adan bias corrections) lives in device memory written by
@@ -17,15 +17,24 @@ from .dp import GradBucket
 
 class TrainStep:
     def __init__(self, model, optimizer, loss_type, takes_image, batch_shape, device, use_graph=True, warmup_eager=3,
-                 process_group=None, world_size=1, clip_max_norm=0.0, force_bucket=False, dp_buckets=None):
+                 process_group=None, world_size=1, clip_max_norm=0.0, force_bucket=False, dp_buckets=None, mask=None):
         self.model, self.opt, self.loss_type = model, optimizer, loss_type
         self.takes_image = takes_image                       # HNeRV_Boost consumes the frame; NeRV/ENeRV the frame index
         self.dev = device
         B, C, H, W = batch_shape
         self.static_img = torch.zeros(B, C, H, W, dtype=torch.float32, device=device)
         self.static_idx = torch.zeros(B, dtype=torch.float64, device=device)
-        self.use_graph = use_graph and clip_max_norm <= 0
-        self.clip_max_norm = clip_max_norm
+        self.use_graph = use_graph
+        self.clip_max_norm = clip_max_norm                   # > 0: optimizer.launch_clip() on the (averaged) gradients, in front of the update
+        # mask [H, W] (--inpanting, hnerv_utils.TransformInput): the loss sees (out * mask, frame * mask), an image-consuming model reads
+        # clamp(frame * mask, 0, 1), and psnr_out stays the PSNR against the unmasked frame (train_nerv_all.py:331-350 of the reference)
+        self.mask = self.static_gtm = self.static_in = None
+        if mask is not None:
+            if tuple(mask.shape) != (H, W):
+                raise ValueError(f"TrainStep: mask {tuple(mask.shape)} for frames of {(H, W)}")
+            self.mask = mask.detach().to(device=device, dtype=torch.float32).contiguous()
+            self.static_gtm = torch.zeros_like(self.static_img)
+            self.static_in = torch.zeros_like(self.static_img) if takes_image else None
         self.warmup_eager = warmup_eager
         self.n_calls = 0
         self.graph_a = self.graph_b = None
@@ -82,11 +91,14 @@ class TrainStep:
         if self._fetching and not getattr(self, "_fetch_done", False):
             self._fetch()
         self.opt.zero_grad(set_to_none=True)
-        inp = self.static_img if self.takes_image else self.static_idx
+        if self.mask is not None:
+            ops.inpaint_head(self.static_img, self.mask, out_gt_m=self.static_gtm, out_inp=self.static_in)
+        inp = (self.static_img if self.mask is None else self.static_in) if self.takes_image else self.static_idx
         img_out, _, _ = self.model(inp, norm_idx=self.static_idx)
         # loss_fn(...).backward() + psnr_fn_single(...) of train_nerv_all.py:337-347 as ONE fused launch sequence: the loss
-        # gradient seeds backward directly and the per-sample PSNR comes from the same L2 sums (stats[:, 4])
-        loss, stats, grad = ops.loss_value_grad_stats(img_out, self.static_img, self.loss_type)
+        # gradient seeds backward directly and the per-sample PSNR comes from the same L2 sums (stats[:, 4]).  With a mask the gradient
+        # comes back masked and stats[:, 4] is the PSNR against the unmasked frame (ops.loss_value_grad_stats)
+        loss, stats, grad = ops.loss_value_grad_stats(img_out, self.static_img, self.loss_type, mask=self.mask, target_masked=self.static_gtm)
         if self._lazy_flush_valid():
             # (dx_ok: the model's first block hands its queued input gradient to an operator of this package, which flushes on entry -- ops._end_block)
             with ops.lazy_flush(dx_ok=getattr(self.model, "lazy_dx_ok", False)):      # slab reductions are flushed by their first reader, not per block
@@ -182,11 +194,16 @@ class TrainStep:
         self._fwd_bwd()
         if self.bucket is not None:
             self.bucket.finish()
-        if self.clip_max_norm > 0:
-            torch.nn.utils.clip_grad_norm_(self.params, self.clip_max_norm)
+        self._clip_grads()
         if not prepared:
             self.opt.prepare_step()
         self.opt.launch_step()
+
+    def _clip_grads(self):
+        """--clip_max_norm: clip_grad_norm_ of train_nerv_all.py:346-347 on the device (two launches over the optimizer's table, no host round
+        trip), after the exchange: the ranks clip the AVERAGED gradient, as DDP followed by clip_grad_norm_ does in the reference."""
+        if self.clip_max_norm > 0:
+            self.opt.launch_clip(self.clip_max_norm)
 
     def _bucket_calls(self, which):
         import ctypes as C
@@ -215,7 +232,8 @@ class TrainStep:
         else:
             L.reserve_ctx(self._cap_ctx)
         if hasattr(self.opt, "begin_capture"):
-            self.opt.begin_capture()            # this capture's own descriptor tables (optimizer.Adan.launch_step, capture contract)
+            # this capture's own descriptor tables (optimizer._FusedTableOptimizer._table, capture contract) and, with a clip, its workspace
+            self.opt.begin_capture(clip=self.clip_max_norm > 0)
         try:
             with L.use_ctx(self._cap_ctx):
                 self._capture_in_ctx(pool)
@@ -235,6 +253,7 @@ class TrainStep:
         if self.bucket is None:
             with L.graph_capture(self.graph_a, **cap):
                 self._planned_fwd_bwd()
+                self._clip_grads()
                 self.opt.launch_step()
             return
 
@@ -247,6 +266,7 @@ class TrainStep:
 
         def tail():
             self._bucket_calls("scatter")
+            self._clip_grads()
             self.opt.launch_step()
         backend = dist.get_backend(self.bucket.group) if dist.is_initialized() else ""
         if backend == "nccl" and os.environ.get("BNERV_DP_INGRAPH", "1") != "0":
@@ -254,6 +274,7 @@ class TrainStep:
                 with L.graph_capture(self.graph_a, **cap):
                     self._planned_fwd_bwd()                   # (two buckets: the hook starts the early segment's all-reduce in here)
                     self.bucket.finish()                      # gather -> all-reduce -> [join] -> scatter
+                    self._clip_grads()
                     self.opt.launch_step()
                 self.collective_in_graph = True
                 return

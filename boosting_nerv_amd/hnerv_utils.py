@@ -226,12 +226,14 @@ def adjust_lr(optimizer, cur_epoch, cur_iter, args):
 # ----------------------------------------------------------------------------------------------------------------------
 # loss and metrics                                                           reference hnerv_utils.py:335-419
 # ----------------------------------------------------------------------------------------------------------------------
-def loss_fn(pred, target, loss_type="L2", batch_average=True):
+def loss_fn(pred, target, loss_type="L2", batch_average=True, mask=None):
     """Value + gradient come from one fused HIP call.  Every variant of the reference is built: L1, L2, L1_freq, Fusion7/8 and the
     MS-SSIM mixes Fusion10/11/12, Fusion10_freq (bnerv_loss_fwd_bwd; MS-SSIM needs min(H, W) > 160), and the single-scale SSIM mixes
     SSIM, Fusion1-6, Fusion9, L1_ssim_freq (bnerv_loss_ssim_fwd_bwd; min(H, W) >= 11 -- a smaller frame raises NotImplementedError,
-    where the reference skips the filter along the short side)."""
-    loss, stats = ops.loss_with_stats(pred, target, loss_type)
+    where the reference skips the filter along the short side).
+    mask ([H, W], inpainting): loss_fn(pred * mask, target * mask, ...) of train_nerv_all.py:343, bit for bit, without the two full-frame
+    products in the autograd graph."""
+    loss, stats = ops.loss_with_stats(pred, target, loss_type, mask=mask)
     if batch_average:
         return loss
     # per-sample values (no gradient path): stats[:,0]

@@ -13,6 +13,7 @@ ATen):
   sft_affine               SFTLayer.forward (affine part)        model_blocks.py:101-105
   head_tanh                head_layer + OutImg('tanh')           model_nerv.py:56-57, model_blocks.py:57-63
   loss / psnr / msssim     loss_fn, psnr_fn_single, ms_ssim      hnerv_utils.py:335-403, :410-412
+  inpaint_head, mask=      TransformInput, loss_fn(out * mask, ..) hnerv_utils.py:59-84, train_nerv_all.py:343
 """
 import ctypes as C
 import os
@@ -1122,17 +1123,67 @@ def _loss_launch(pred, target, coeffs, need_grad):
     return loss, stats, grad
 
 
-def loss_value_grad_stats(pred, target, loss_type="Fusion10_freq"):
+def _mask_hw(mask, like):
+    """The [H, W] inpainting mask as the kernels read it: contiguous fp32 on the device of `like` ([B, C, H, W])."""
+    mask = L.f32c(L.require_device(mask.detach(), "mask"))
+    if tuple(mask.shape) != tuple(like.shape[-2:]) or like.dim() != 4:
+        raise ValueError(f"mask {tuple(mask.shape)} does not match the [H, W] of a frame batch {tuple(like.shape)}")
+    return mask
+
+
+def inpaint_head(img, mask, want_inp=False, out_gt_m=None, out_inp=None):
+    """(gt_m, inp) = (img * mask, clamp(img * mask, 0, 1) | None) in ONE pass: both sides' target of the masked loss and the masked frame
+    an image-consuming model reads (TransformInput.forward, hnerv_utils.py:59-84).  out_*: buffers to write into (a captured step's)."""
+    img = L.f32c(L.require_device(img.detach(), "img"))
+    mask = _mask_hw(mask, img)
+    B, Cc, H, W = img.shape
+    gt_m = torch.empty_like(img) if out_gt_m is None else out_gt_m
+    inp = out_inp if out_inp is not None else (torch.empty_like(img) if want_inp else None)
+    L.check(L.load().bnerv_inpaint_head(L.stream(), L.ptr(img), L.ptr(mask), L.ptr(inp), L.ptr(gt_m), B, Cc, H * W), "bnerv_inpaint_head")
+    return gt_m, inp
+
+
+def _masked_loss_launch(pred, target, mask, coeffs, need_grad, target_masked=None):
+    """_loss_launch(pred * mask, target * mask) with the products, the gradient's mask and the UNMASKED per-sample PSNR (stats[:, 4]) from
+    this package's streaming kernels: [head,] pred, the unchanged loss launches, PSNR finalize, [grad]."""
+    pred = L.f32c(L.require_device(pred, "pred")); target = L.f32c(L.require_device(target.detach(), "target"))
+    mask = _mask_hw(mask, pred)
+    B, Cc, H, W = pred.shape
+    lib = L.load()
+    if target_masked is None:
+        target_masked, _ = inpaint_head(target, mask)
+    pred_m = torch.empty_like(pred)
+    nbytes = lib.bnerv_inpaint_ws_bytes(B, Cc, H * W)
+    ws = _ws(nbytes, pred.device)
+    L.check(lib.bnerv_inpaint_pred(L.stream(), L.ptr(pred), L.ptr(target), L.ptr(mask), L.ptr(pred_m), L.ptr(ws), nbytes, B, Cc, H * W), "bnerv_inpaint_pred")
+    loss, stats, grad = _loss_launch(pred_m, target_masked, coeffs, need_grad)
+    # after the loss call: its own column 4 is the PSNR of the masked pair, not the number the reference logs (train_nerv_all.py:350)
+    L.check(lib.bnerv_inpaint_psnr(L.stream(), L.ptr(ws), nbytes, stats.data_ptr() + 4 * 4, L.LOSS_STATS, B, Cc, H * W), "bnerv_inpaint_psnr")
+    if grad is not None:
+        L.check(lib.bnerv_inpaint_grad(L.stream(), L.ptr(grad), L.ptr(mask), B, Cc, H * W), "bnerv_inpaint_grad")
+    return loss, stats, grad
+
+
+def loss_value_grad_stats(pred, target, loss_type="Fusion10_freq", mask=None, target_masked=None):
     """(loss [scalar], stats [B,5], d loss/d pred) without an autograd node: the train step seeds pred.backward(grad) with
-    the gradient directly (no ones-fill, no grad * 1 pass over the frame) and reads the per-sample PSNR from stats[:, 4]."""
-    loss, stats, grad = _loss_launch(pred.detach(), target, _loss_plan(pred, loss_type), True)
+    the gradient directly (no ones-fill, no grad * 1 pass over the frame) and reads the per-sample PSNR from stats[:, 4].
+    mask ([H, W], inpainting): the loss of (pred * mask, target * mask), bit for bit; grad is already multiplied by the mask and
+    stats[:, 4] is the PSNR of pred against the UNMASKED target.  target_masked: target * mask where the caller has it (inpaint_head)."""
+    coeffs = _loss_plan(pred, loss_type)
+    if mask is None:
+        loss, stats, grad = _loss_launch(pred.detach(), target, coeffs, True)
+    else:
+        loss, stats, grad = _masked_loss_launch(pred.detach(), target, mask, coeffs, True, target_masked)
     return loss.reshape(()), stats, grad
 
 
 class _Loss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pred, target, coeffs):
-        loss, stats, grad = _loss_launch(pred, target, coeffs, ctx.needs_input_grad[0])
+    def forward(ctx, pred, target, coeffs, mask):
+        if mask is None:
+            loss, stats, grad = _loss_launch(pred, target, coeffs, ctx.needs_input_grad[0])
+        else:
+            loss, stats, grad = _masked_loss_launch(pred, target, mask, coeffs, ctx.needs_input_grad[0])
         ctx.grad = grad
         ctx.mark_non_differentiable(stats)
         return loss.reshape(()), stats
@@ -1142,13 +1193,14 @@ class _Loss(torch.autograd.Function):
         _enter_backward()
         g = ctx.grad
         ctx.grad = None
-        return (g * gl if g is not None else None), None, None
+        return (g * gl if g is not None else None), None, None, None
 
 
-def loss_with_stats(pred, target, loss_type="Fusion10_freq"):
+def loss_with_stats(pred, target, loss_type="Fusion10_freq", mask=None):
     """Returns (batch-mean loss [scalar tensor], stats [B,5] = {loss_b, sum|d|, sum d^2, ms_ssim_b, psnr_b}); column 3 carries ssim_b for
-    the single-scale SSIM losses (SSIM_LOSS_COEFFS)."""
-    return _Loss.apply(pred, target, _loss_plan(pred, loss_type))
+    the single-scale SSIM losses (SSIM_LOSS_COEFFS).  mask ([H, W]): the value and gradient of loss_with_stats(pred * mask, target * mask)
+    with psnr_b taken against the unmasked target (loss_value_grad_stats)."""
+    return _Loss.apply(pred, target, _loss_plan(pred, loss_type), mask)
 
 
 def psnr(output, gt):

@@ -27,6 +27,8 @@ class _FusedTableOptimizer(Optimizer):
         self._cap_open = None     # begin_capture() .. finish_capture(): group index -> (pinned host, device) descriptor table of THIS capture
         self._chunk_cache = {}    # group index -> (key, device descriptor table, n, blocks, tensors the table points into, pending host table)
         self.state_epoch = 0      # bumped whenever state tensors are replaced: a captured step (engine.TrainStep) re-captures
+        self._clip_ws = None      # launch_clip(): one double per block of every group's table (device)
+        self.clip_out = None      # launch_clip(): device [2] = (total gradient norm, clip coefficient) of the last clip
 
     def _invalidate(self):
         """The descriptors of launch_step() hold raw device pointers into the state tensors; whoever replaces those tensors
@@ -40,6 +42,10 @@ class _FusedTableOptimizer(Optimizer):
 
     def _clip_coef(self):
         return 1.0
+
+    def _clip_fresh(self, group):
+        """launch_clip(): the parameters of `group` whose state the table is about to create from the UNCLIPPED gradient."""
+        return []
 
     @torch.no_grad()
     def prepare_step(self, aux=None):
@@ -72,69 +78,117 @@ class _FusedTableOptimizer(Optimizer):
                 events[slot] = torch.cuda.Event()
             events[slot].record()
 
-    @torch.no_grad()
-    def launch_step(self, clip=1.0):
-        """Device side of a step: ONE fused launch over a device-resident descriptor table (any number of tensors).  No sync; the
-        only host<->device traffic is the table upload when a tensor address changed (never in a replayed step).
+    def _table(self, lib, gi, group, clip, what):
+        """The device-resident descriptor table of group gi for the gradients that exist now -- built, or refreshed when a tensor address
+        changed, and uploaded (outside a capture).  -> (device table, tensors, blocks), None for a group without gradients.  launch_clip()
+        and launch_step() of one step share it: the second call finds the first one's table.
 
         Capture contract: a captured launch records only the ADDRESS of its descriptor table; the content is uploaded by
         finish_capture().  Inside a stream capture this method therefore raises unless a begin_capture() .. finish_capture() bracket
         is open (engine.TrainStep._capture opens one); every bracket gets a table of its own, which the caller keeps alive with its
         graph (finish_capture() returns it), so a second capture never rewrites the table an earlier graph still replays with."""
+        ps = [p for p in group["params"] if p.grad is not None]
+        if not ps:
+            return None
+        # the key covers every pointer a descriptor holds (parameter, gradient and the four state tensors), and the cache
+        # entry keeps the state tensors alive, so a descriptor can never point at freed memory
+        sts = [self._ensure_state(p, group.get("step", 1), clip) for p in ps]
+        ents = [self._entry_state(st) for st in sts]          # (exp_avg, exp_avg_sq, exp_avg_diff | None, neg_pre_grad | None)
+        key = tuple((p.data_ptr(), p.grad.data_ptr()) + tuple(0 if t is None else t.data_ptr() for t in en) for p, en in zip(ps, ents))
+        capturing = torch.cuda.is_current_stream_capturing()
+        ck = (gi, capturing)        # a captured launch owns its table: an eager step in between must not rewrite the addresses it replays with
+        if capturing and self._cap_open is None:
+            raise L.BnervError(f"{type(self).__name__}.{what}() inside a stream capture needs an open begin_capture() .. finish_capture() bracket "
+                               "(the captured launch reads a descriptor table that finish_capture() uploads)")
+        cached = self._chunk_cache.get(ck)
+        if capturing and cached is not None and cached[1] is not self._cap_open[gi][1]:
+            cached = None               # a table of an earlier capture: that graph keeps it; this capture writes its own
+        if cached is None or cached[0] != key:
+            # (not p.grad: it is alive whenever the step launches, and pinning it would move the next eager gradient elsewhere)
+            keep = [(p,) + tuple(en) for p, en in zip(ps, ents)]
+            tab = (L.AdanEntry * len(ps))()
+            blocks = 0
+            for j, (p, en) in enumerate(zip(ps, ents)):
+                if not (p.is_contiguous() and p.grad.is_contiguous() and p.dtype == torch.float32 and p.grad.dtype == torch.float32):
+                    raise L.BnervError(f"fused {type(self).__name__} needs contiguous fp32 parameters and gradients")
+                e = tab[j]
+                e.p, e.g = p.data_ptr(), p.grad.data_ptr()
+                e.exp_avg, e.exp_avg_sq = en[0].data_ptr(), en[1].data_ptr()
+                e.exp_avg_diff = None if en[2] is None else en[2].data_ptr()
+                e.neg_pre_grad = None if en[3] is None else en[3].data_ptr()
+                e.n, e.bstart = p.numel(), blocks
+                blocks += lib.bnerv_adan_table_blocks(p.numel())
+            raw = bytes(tab)
+            if capturing:
+                # nothing may allocate pinned or device memory inside a capture: begin_capture() set both aside
+                host, dev_tab = self._cap_open[gi]
+                if host.numel() < len(raw):
+                    raise L.BnervError("fused optimizer: the capture-time descriptor table is larger than the one begin_capture() reserved")
+                C.memmove(host.data_ptr(), raw, len(raw))
+            else:
+                host = torch.frombuffer(bytearray(raw), dtype=torch.uint8).pin_memory()
+                # ONE device table per group, reused while the tensor count does not change
+                dev_tab = cached[1] if (cached is not None and cached[1].numel() == host.numel()) else torch.empty(host.numel(), dtype=torch.uint8, device=ps[0].device)
+            cached = [key, dev_tab, len(ps), blocks, keep, host]
+            self._chunk_cache[ck] = cached
+        if cached[5] is not None and not capturing:
+            cached[1].copy_(cached[5], non_blocking=True)      # stream-ordered before the launch that follows
+            cached[5] = None                                   # (inside a capture the upload waits for finish_capture(): a copy node would replay every step)
+        return cached[1], cached[2], cached[3]
+
+    @torch.no_grad()
+    def launch_step(self, clip=1.0):
+        """Device side of a step: ONE fused launch over a device-resident descriptor table (any number of tensors).  No sync; the
+        only host<->device traffic is the table upload when a tensor address changed (never in a replayed step).  Inside a stream
+        capture: see the capture contract of _table()."""
         lib = L.load()
         for gi, group in enumerate(self.param_groups):
-            ps = [p for p in group["params"] if p.grad is not None]
-            if not ps:
-                continue
-            # the key covers every pointer a descriptor holds (parameter, gradient and the four state tensors), and the cache
-            # entry keeps the state tensors alive, so a descriptor can never point at freed memory
-            sts = [self._ensure_state(p, group.get("step", 1), clip) for p in ps]
-            ents = [self._entry_state(st) for st in sts]          # (exp_avg, exp_avg_sq, exp_avg_diff | None, neg_pre_grad | None)
-            key = tuple((p.data_ptr(), p.grad.data_ptr()) + tuple(0 if t is None else t.data_ptr() for t in en) for p, en in zip(ps, ents))
-            capturing = torch.cuda.is_current_stream_capturing()
-            ck = (gi, capturing)        # a captured launch owns its table: an eager step in between must not rewrite the addresses it replays with
-            if capturing and self._cap_open is None:
-                raise L.BnervError(f"{type(self).__name__}.launch_step() inside a stream capture needs an open begin_capture() .. finish_capture() bracket "
-                                   "(the captured launch reads a descriptor table that finish_capture() uploads)")
-            cached = self._chunk_cache.get(ck)
-            if capturing and cached is not None and cached[1] is not self._cap_open[gi][1]:
-                cached = None               # a table of an earlier capture: that graph keeps it; this capture writes its own
-            if cached is None or cached[0] != key:
-                # (not p.grad: it is alive whenever the step launches, and pinning it would move the next eager gradient elsewhere)
-                keep = [(p,) + tuple(en) for p, en in zip(ps, ents)]
-                tab = (L.AdanEntry * len(ps))()
-                blocks = 0
-                for j, (p, en) in enumerate(zip(ps, ents)):
-                    if not (p.is_contiguous() and p.grad.is_contiguous() and p.dtype == torch.float32 and p.grad.dtype == torch.float32):
-                        raise L.BnervError(f"fused {type(self).__name__} needs contiguous fp32 parameters and gradients")
-                    e = tab[j]
-                    e.p, e.g = p.data_ptr(), p.grad.data_ptr()
-                    e.exp_avg, e.exp_avg_sq = en[0].data_ptr(), en[1].data_ptr()
-                    e.exp_avg_diff = None if en[2] is None else en[2].data_ptr()
-                    e.neg_pre_grad = None if en[3] is None else en[3].data_ptr()
-                    e.n, e.bstart = p.numel(), blocks
-                    blocks += lib.bnerv_adan_table_blocks(p.numel())
-                raw = bytes(tab)
-                if capturing:
-                    # nothing may allocate pinned or device memory inside a capture: begin_capture() set both aside
-                    host, dev_tab = self._cap_open[gi]
-                    if host.numel() < len(raw):
-                        raise L.BnervError("fused optimizer: the capture-time descriptor table is larger than the one begin_capture() reserved")
-                    C.memmove(host.data_ptr(), raw, len(raw))
-                else:
-                    host = torch.frombuffer(bytearray(raw), dtype=torch.uint8).pin_memory()
-                    # ONE device table per group, reused while the tensor count does not change
-                    dev_tab = cached[1] if (cached is not None and cached[1].numel() == host.numel()) else torch.empty(host.numel(), dtype=torch.uint8, device=ps[0].device)
-                cached = [key, dev_tab, len(ps), blocks, keep, host]
-                self._chunk_cache[ck] = cached
-            if cached[5] is not None and not capturing:
-                cached[1].copy_(cached[5], non_blocking=True)      # stream-ordered before the launch below
-                cached[5] = None                                   # (inside a capture the upload waits for finish_capture(): a copy node would replay every step)
-            self._launch(lib, group, clip, self._sched[gi][1].data_ptr(), cached[1].data_ptr(), cached[2], cached[3])
+            tab = self._table(lib, gi, group, clip, "launch_step")
+            if tab is not None:
+                self._launch(lib, group, clip, self._sched[gi][1].data_ptr(), tab[0].data_ptr(), tab[1], tab[2])
 
-    def begin_capture(self):
+    def _clip_buffers(self):
+        """The clip's workspace (one double per block the tables of ALL parameters can have) and its 2-float result, made once: on the first
+        eager launch_clip(), or by begin_capture(clip=True) when a capture comes first."""
+        lib = L.load()
+        need = sum(lib.bnerv_adan_table_blocks(p.numel()) for group in self.param_groups for p in group["params"])
+        if self._clip_ws is None or self._clip_ws.numel() < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise L.BnervError("fused optimizer: launch_clip() inside a stream capture needs the workspace begin_capture(clip=True) reserves")
+            dev = self.param_groups[0]["params"][0].device
+            self._clip_ws = torch.zeros(max(need, 1), dtype=torch.float64, device=dev)
+            if self.clip_out is None:
+                self.clip_out = torch.zeros(2, dtype=torch.float32, device=dev)
+        return self._clip_ws, self.clip_out
+
+    @torch.no_grad()
+    def launch_clip(self, max_norm):
+        """torch.nn.utils.clip_grad_norm_(parameters, max_norm) on the device, in front of launch_step(): two launches per parameter group
+        over launch_step()'s own descriptor table (bnerv_grad_sqsum_table, bnerv_grad_scale_table), no host round trip -- capturable under
+        launch_step()'s capture contract.  The norm is global: every group's partial sums go into one workspace and every group is scaled
+        by the sum of all of them.  `clip_out` (device, [2]) then holds (total norm, coefficient)."""
+        lib = L.load()
+        ws, out = self._clip_buffers()
+        tabs, late, base = [], [], 0
+        for gi, group in enumerate(self.param_groups):
+            fresh = self._clip_fresh(group)
+            tab = self._table(lib, gi, group, 1.0, "launch_clip")
+            if tab is None:
+                continue
+            late += fresh
+            tabs.append((tab, base))
+            L.check(lib.bnerv_grad_sqsum_table(L.stream(), tab[0].data_ptr(), tab[1], tab[2], ws.data_ptr() + 8 * base), "bnerv_grad_sqsum_table")
+            base += tab[2]
+        for tab, _ in tabs:
+            L.check(lib.bnerv_grad_scale_table(L.stream(), tab[0].data_ptr(), tab[1], tab[2], ws.data_ptr(), base, float(max_norm), out.data_ptr()),
+                    "bnerv_grad_scale_table")
+        for p in late:                      # (their state was made from the gradient as it was BEFORE the clip)
+            self.state[p]["neg_pre_grad"].copy_(p.grad).neg_()
+
+    def begin_capture(self, clip=False):
         """Before a hipGraph capture that will contain launch_step(): reserve THIS capture's descriptor tables (pinned host + device,
-        one pair per parameter group, sized for every parameter) -- nothing may allocate inside the capture."""
+        one pair per parameter group, sized for every parameter) -- nothing may allocate inside the capture.  clip: the capture will
+        contain launch_clip() as well, whose workspace and result are made here unless an eager launch_clip() already made them."""
         tabs = {}
         for gi, group in enumerate(self.param_groups):
             nb = max(len(group["params"]), 1) * C.sizeof(L.AdanEntry)
@@ -142,6 +196,8 @@ class _FusedTableOptimizer(Optimizer):
             host = torch.empty(nb, dtype=torch.uint8)
             tabs[gi] = (host.pin_memory() if dev.type == "cuda" else host, torch.empty(nb, dtype=torch.uint8, device=dev))
         self._cap_open = tabs
+        if clip:
+            self._clip_buffers()
 
     def finish_capture(self):
         """After a hipGraph capture that contained launch_step(): upload the descriptor tables that capture referenced (the captured
@@ -190,6 +246,8 @@ class Adan(_FusedTableOptimizer):
             group.setdefault("no_prox", False)
         self.__dict__.setdefault("_sched", {})
         self.__dict__["_cap_open"] = None
+        self.__dict__.setdefault("_clip_ws", None)
+        self.__dict__.setdefault("clip_out", None)
         self._invalidate()
 
     @torch.no_grad()
@@ -217,6 +275,12 @@ class Adan(_FusedTableOptimizer):
                     total.add_(p.grad.pow(2).sum())
         total = torch.sqrt(total)
         return torch.clamp(self.defaults["max_grad_norm"] / (total + self.param_groups[-1]["eps"]), max=1.0).item()
+
+    def _clip_fresh(self, group):
+        # a parameter whose first gradient appears after step 1 starts from neg_pre_grad = -(its gradient) (_ensure_state): after the clip
+        if group.get("step", 1) <= 1:
+            return []
+        return [p for p in group["params"] if p.grad is not None and "neg_pre_grad" not in self.state[p]]
 
     def _sched_record(self, group):
         beta1, beta2, beta3 = group["betas"]
@@ -269,6 +333,8 @@ class Adam(_FusedTableOptimizer):
         super().__setstate__(state)
         self.__dict__.setdefault("_sched", {})
         self.__dict__["_cap_open"] = None
+        self.__dict__.setdefault("_clip_ws", None)
+        self.__dict__.setdefault("clip_out", None)
         self._invalidate()
 
     def load_state_dict(self, state_dict):

@@ -238,6 +238,14 @@ def _make_optimizer(model, args):
     raise ValueError(f"--optim_type {args.optim_type!r}: pass Adan or Adam (the reference's default 'adan' matches neither of its branches)")
 
 
+def step_mode(optimizer, args):
+    """Which train step a run takes: "captured" -- engine.TrainStep, one replayed hipGraph per step (eager under --no_graph) -- for the
+    fused optimizers of this package (they have launch_step()), whatever --inpanting mask or --clip_max_norm the recipe sets: the step
+    takes the mask and clips on the device.  "generic" -- _generic_step, eager, op by op -- for a stock torch optimizer
+    (--optim_type Adam on a boost model).  Needs no GPU."""
+    return "captured" if hasattr(optimizer, "launch_step") else "generic"
+
+
 def train(local_rank, args):
     for seed_fn in (torch.manual_seed, np.random.seed, random.seed):
         seed_fn(args.manualSeed)
@@ -294,10 +302,14 @@ def train(local_rank, args):
 
     h, w = (int(x) for x in args.crop_list.split('_')[:2])
     takes_image = 'pe' not in args.embed or "HNeRV_Boost" in args.model
-    fused = hasattr(optimizer, "launch_step") and args.transform_func.identity        # Adan, and Adam for the HNeRV baseline
+    mode = step_mode(optimizer, args)                                                 # "captured": Adan, and Adam for the HNeRV baseline
+    # the reference's masks depend on the frame size only: built once, on a dummy frame of the crop size (None without --inpanting)
+    mask = None if args.transform_func.identity else args.transform_func(torch.zeros(1, 3, h, w, device=device), None)[2]
     step = TrainStep(model, optimizer, args.loss, takes_image, (args.batchSize, 3, h, w), device, use_graph=not args.no_graph,
-                     world_size=world, clip_max_norm=args.clip_max_norm) if fused else None
-    # the generic path (Adam, inpainting masks) averages its gradients over the ranks with the same flat bucket the fused step uses
+                     world_size=world, clip_max_norm=args.clip_max_norm, mask=mask) if mode == "captured" else None
+    log.line(f'Train step: {mode}' + (' (eager: --no_graph)' if mode == "captured" and args.no_graph else '')
+             + f', inpainting mask: {args.inpanting if mask is not None else "none"}, clip_max_norm: {args.clip_max_norm}', echo=False)
+    # the generic path (stock Adam) averages its gradients over the ranks with the same flat bucket the fused step uses
     bucket = GradBucket(model.parameters()) if (step is None and world > 1) else None
 
     t_start = time.time()
@@ -366,8 +378,8 @@ def train(local_rank, args):
 
 
 def _generic_step(model, optimizer, bucket, args, frames, img_idx, norm_idx, takes_image):
-    """One eager step for the configurations the captured step does not cover (--optim_type Adam, --inpanting masks): the same
-    kernels, driven op by op.  With several ranks the gradients are averaged through the flat bucket before clipping / the step
+    """One eager step for the configuration the captured step does not cover (--optim_type Adam on a boost model: torch.optim.Adam), with
+    or without an --inpanting mask: the same kernels, driven op by op.  With several ranks the gradients are averaged through the flat bucket before clipping / the step
     (the reference gets this from its DistributedDataParallel wrap)."""
     img_in, img_gt, mask = args.transform_func(frames, img_idx)
     out, _, _ = model(img_in if takes_image else norm_idx, norm_idx=norm_idx)

@@ -461,6 +461,25 @@ int bnerv_ssim(void* stream, const float* x, const float* y, float* out, void* w
 int bnerv_tanh_grad_blocks(int HW);
 int bnerv_tanh_grad(void* stream, const float* g, const float* img, float* gt, float* part, int B, int C, int HW);
 
+/* Inpainting (additive to ABI 9; csrc/eltwise.hip): the reference masks both sides of the loss with an [H, W] mask that depends on the frame
+ * size only (hnerv_utils.py:59-84 TransformInput; train_nerv_all.py:343 loss_fn(out * mask, gt * mask)).  Streaming passes over [B, C, HW]
+ * fp32 with the mask [HW] broadcast over B and C; every product is ONE fp32 multiply, so a loss entry point called on (pred_m, gt_m) sees
+ * the bits torch's `x * mask` would hand it.
+ *   bnerv_inpaint_head:  gt_m = img * mask;  inp (may be NULL) = clamp(img * mask, 0, 1), the frame an image-consuming model reads
+ *   bnerv_inpaint_pred:  pred_m = pred * mask, and per-block sums of (pred - gt)^2 against the UNMASKED gt as doubles in ws
+ *                        (bnerv_inpaint_ws_bytes(B, C, HW) bytes)
+ *   bnerv_inpaint_psnr:  psnr[b * stride] = -10 log10(mean_{CHW}(pred - gt)^2 + 1e-9) from that ws, partials added in one fixed order --
+ *                        the PSNR the reference logs (train_nerv_all.py:350).  A launch of its own so that it can follow the loss call and
+ *                        land in column 4 of its stats (stride = BNERV_LOSS_STATS), which the loss computes on masked data
+ *   bnerv_inpaint_grad:  g *= mask in place (the backward of pred * mask)
+ * Alignment: any 4-byte boundary and any HW; the 16-byte form runs when HW % 4 == 0 and every tensor is 16-byte aligned, the scalar form
+ * otherwise (same bits; no refusal).  ws must be 8-byte aligned. */
+int bnerv_inpaint_head(void* stream, const float* img, const float* mask, float* inp, float* gt_m, int B, int C, int HW);
+size_t bnerv_inpaint_ws_bytes(int B, int C, int HW);
+int bnerv_inpaint_pred(void* stream, const float* pred, const float* gt, const float* mask, float* pred_m, void* ws, size_t ws_bytes, int B, int C, int HW);
+int bnerv_inpaint_psnr(void* stream, const void* ws, size_t ws_bytes, float* psnr, int stride, int B, int C, int HW);
+int bnerv_inpaint_grad(void* stream, float* g, const float* mask, int B, int C, int HW);
+
 /* psnr[b] = -10 log10(mean_{CHW}(out-gt)^2 + 1e-9)  (hnerv_utils.py:400-403); ws: bnerv_psnr_ws_bytes() */
 size_t bnerv_psnr_ws_bytes(int B, int C, int H, int W);
 int bnerv_psnr(void* stream, const float* out, const float* gt, float* psnr, void* ws, size_t ws_bytes, int B, int C, int H, int W);
@@ -540,6 +559,20 @@ int bnerv_adan_table(void* stream, const bnerv_adan_entry* table_dev, int n_tens
  *   m += (1 - b1)(g - m);  v = b2 v + (1 - b2) g^2;  p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps) */
 int bnerv_adam_table_blocks(int n);
 int bnerv_adam_table(void* stream, const bnerv_adan_entry* table_dev, int n_tensors, int total_blocks, const bnerv_adan_hyper* h);
+
+/* Global-norm gradient clip on the device (additive to ABI 9): torch.nn.utils.clip_grad_norm_(params, max_norm) with its defaults
+ * (train_nerv_all.py:346-347 of the reference) over the gradients of the same device table, with no host round trip, so a captured step can hold it:
+ *   total = sqrt(sum g^2);  coef = min(1, max_norm / (total + 1e-6));  g *= coef  (also when coef == 1)
+ * Of an entry only g, n and bstart are read; the grid is the optimizer launch's (bnerv_adan_table_blocks).  bnerv_grad_sqsum_table leaves one
+ * double per block in partials[0 .. total_blocks); bnerv_grad_scale_table has every block add partials[0 .. n_partials) in one fixed order
+ * (n_partials >= total_blocks: several tables -- parameter groups -- may have written consecutive ranges of one workspace and are then clipped
+ * by their common norm), forms coef in fp32, scales its slice in place, and block 0 writes out[0] = total, out[1] = coef.  No atomics: the same
+ * build and launch sequence gives the same bits.  max_norm travels by value (fixed for a run).
+ * Alignment: a gradient may start at any 4-byte boundary and n need not be a multiple of 4 (16-byte accesses over the aligned body only);
+ * partials must be 8-byte aligned. */
+int bnerv_grad_sqsum_table(void* stream, const bnerv_adan_entry* table_dev, int n_tensors, int total_blocks, double* partials);
+int bnerv_grad_scale_table(void* stream, const bnerv_adan_entry* table_dev, int n_tensors, int total_blocks, const double* partials,
+                           int n_partials, float max_norm, float* out);
 
 /* Frame fetch of a step whose clip is resident in device memory (train_nerv_all.py:329 moves one frame host -> device per step; with
  * the clip in HBM the step only needs to know WHICH frame): copies frame k = (int)sel_dev[0] of clip [N][frame_elems] to dst_img
