@@ -12,6 +12,7 @@
 //   ms_coef         ms_ssim per (b,c) and d(loss)/d(level statistic)
 //   ssim_bwd        per level, coarse -> fine: recompute the statistics for a haloed tile, differentiate, apply the adjoint
 //                   Gaussian, add the upsampled coarser-level gradient; level 0 also adds the L1/L2 terms and writes `grad`
+//   (ssim_fwd / ssim_bwd are wrappers here too: the two tile bodies -- 16-byte window loads, 4-output strips -- live in ssim_body.h)
 //   (the three FFT kernels are wrappers here; plans, tables, butterflies and the row / column bodies live in fft_body.h)
 //   fft_rows_fwd    in-place mixed-radix DIF FFT of every row in LDS (digit-reversed output order -- irrelevant, see below)
 //   fft_cols        column DIF FFT, sum(|Re|+|Im|), S = sign(F), then the ADJOINT transform of S, all in LDS
@@ -221,99 +222,14 @@ struct SsimArgs {
     Win win;
 };
 
-// ---- forward: per-tile sum of cs (LAST=false) or ssim (LAST=true) over the valid region ----
-// The filter passes run on PACKED pairs of maps (v_pk_fma_f32: two fused multiply-adds per issued instruction; these kernels are bound
-// by instruction issue): (x, y) live interleaved in LDS, so a tap is one 8-byte read and pk_fma(g, (x, y)), pk_fma(g, (x x, y y)),
-// fma(g, x y) -- five instructions for the eight of the scalar form; the second pass reads (v0, v1), (v2, v3), v4 likewise.  Every
-// lane of a packed operation is the same IEEE fma in the same tap order as before: the numbers keep their bits.
+// level-0 backward: the coarser levels' OWN terms (n of them), combined there; ph / pw[k]: the zero padding level k was pooled into level k + 1 with
+// (0 on an even pyramid; 1080 -> 540 -> 270 -> 135 -> 68 pads 135), so pixel (y, x) of level k lies in cell ((y + ph) / 2, (x + pw) / 2)
+struct CoarseChain { const float* own[LV]; int H[LV], W[LV], ph[LV], pw[LV]; int n; };
+
 typedef float pk2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ pk2 pk_fma(pk2 a, pk2 b, pk2 c) { return __builtin_elementwise_fma(a, b, c); }
+#include "ssim_body.h"    // ssim_fwd_body (statistics of a tile), ssim_bwd_body (adjoint filter + chain), SSIM_BWD_LDS
 
-__device__ __forceinline__ void ssim_fwd_body(const SsimArgs& a, const bool LAST, const int bx, const int by, const int bc, const int nbc) {
-#pragma clang fp contract(off)                           // the SSIM algebra as written (products rounded, then added -- as the reference's tensor ops do), identical in every instantiation; the filter taps are explicit fmas
-    constexpr int WH = STH + HW_, WW = STW + HW_;        // 26 x 42 input window
-    __shared__ pk2 sXY[WH][WW];
-    __shared__ pk2 sV01[STH][WW], sV23[STH][WW];
-    __shared__ float sV4[STH][WW];
-    __shared__ float red[4];
-    const int tid = threadIdx.x;
-    const int oy0 = by * STH, ox0 = bx * STW;
-    const float* X = a.X + (size_t)bc * a.H * a.W;
-    const float* Y = a.Y + (size_t)bc * a.H * a.W;
-    {   // the whole window in flight (10 loads per thread), then the LDS stores: one memory round trip per block instead of five
-        constexpr int NLD = (WH * WW + 255) / 256;
-        pk2 ld[NLD];
-#pragma unroll
-        for (int u = 0; u < NLD; ++u) {
-            const int i = tid + u * 256;
-            const int r = i / WW, c = i - r * WW;
-            const int y = oy0 + r, x = ox0 + c;
-            const bool in = i < WH * WW && y < a.H && x < a.W;
-            ld[u] = pk2{in ? X[(size_t)y * a.W + x] : 0.f, in ? Y[(size_t)y * a.W + x] : 0.f};
-        }
-#pragma unroll
-        for (int u = 0; u < NLD; ++u) {
-            const int i = tid + u * 256;
-            if (i < WH * WW) (&sXY[0][0])[i] = ld[u];
-        }
-    }
-    __syncthreads();
-    // vertical (along H) first, as the reference filters dim 2 then dim 3
-    for (int i = tid; i < STH * WW; i += 256) {
-        const int r = i / WW, c = i - r * WW;
-        pk2 v01 = {0.f, 0.f}, v23 = {0.f, 0.f};
-        float v4 = 0.f;
-#pragma unroll
-        for (int k = 0; k < WS_; ++k) {
-            const float g = a.win.g[k];
-            const pk2 gg = {g, g}, xy = sXY[r + k][c];
-            v01 = pk_fma(gg, xy, v01); v23 = pk_fma(gg, xy * xy, v23); v4 = fmaf(g, xy.x * xy.y, v4);
-        }
-        sV01[r][c] = v01; sV23[r][c] = v23; sV4[r][c] = v4;
-    }
-    __syncthreads();
-    float acc = 0.f;
-    const int Hv = a.H - HW_, Wv = a.W - HW_;
-    for (int i = tid; i < STH * STW; i += 256) {
-        const int r = i / STW, c = i - r * STW;
-        pk2 m = {0.f, 0.f}, e = {0.f, 0.f};
-        float exy = 0.f;
-#pragma unroll
-        for (int k = 0; k < WS_; ++k) {
-            const float g = a.win.g[k];
-            const pk2 gg = {g, g};
-            m = pk_fma(gg, sV01[r][c + k], m); e = pk_fma(gg, sV23[r][c + k], e); exy = fmaf(g, sV4[r][c + k], exy);
-        }
-        const float m1 = m.x, m2 = m.y, exx = e.x, eyy = e.y;
-        if (oy0 + r < Hv && ox0 + c < Wv) {
-            const float m11 = m1 * m1, m22 = m2 * m2, m12 = m1 * m2;
-            const float s1 = exx - m11, s2 = eyy - m22, s12 = exy - m12;
-            const float B2 = s1 + s2 + a.C2;
-            const float cs = (2.f * s12 + a.C2) / B2;
-            float lum = 1.f;
-            if (LAST) { lum = (2.f * m12 + a.C1) / (m11 + m22 + a.C1); acc += lum * cs; }
-            else acc += cs;
-            if (a.G) {
-                // the statistic gradients take 1 / B2 (and 1 / B1) through v_rcp_f32 (1 ulp) -- three IEEE divisions were a quarter of this
-                // pass's instructions; the VALUE path (cs, lum) keeps the exact quotient
-                const float dxy0 = 2.f * __builtin_amdgcn_rcpf(B2);
-                float dm = dxy0 * (m1 * cs - m2), dxx = -0.5f * cs * dxy0, dxy = dxy0;
-                if (LAST) {
-                    const float B1 = m11 + m22 + a.C1;
-                    dm = (2.f * __builtin_amdgcn_rcpf(B1)) * (m2 - m1 * lum) * cs + lum * dm;
-                    dxx *= lum; dxy *= lum;
-                }
-                const size_t plane = (size_t)a.H * a.W, o = (size_t)bc * plane + (size_t)(oy0 + r) * a.W + (ox0 + c);
-                const size_t mstride = (size_t)nbc * plane;
-                a.G[o] = dm; a.G[mstride + o] = dxx; a.G[2 * mstride + o] = dxy;
-            }
-        }
-    }
-    acc = wave_sum(acc);
-    if ((tid & 63) == 0) red[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0) a.partial[(size_t)bc * (a.tiles_x * a.tiles_y) + by * a.tiles_x + bx] = red[0] + red[1] + red[2] + red[3];
-}
 // XCD-contiguous tile order of a (tiles_x, tiles_y, planes) grid: the dispatcher deals linear block ids round-robin over the 8 XCDs;
 // with this remap each XCD works on a contiguous run of tiles, whose shared window rows / columns it finds in its own L2
 struct Tile3 { int x, y, z; };
@@ -385,106 +301,6 @@ __device__ __forceinline__ void ms_coef_body(const CoefArgs& a, const int bc) {
 }
 __global__ __launch_bounds__(320) void ms_coef_kernel(const CoefArgs a) { ms_coef_body(a, blockIdx.x); }
 
-// ---- backward from the stored statistic gradients: adjoint of the separable "valid" filter over the 3 maps, then
-//      dX = coef * (A0 + 2 x A1 + y A2) [+ 0.25 * d(coarser level)] [+ L1/L2 terms at level 0].  ~6x less arithmetic than
-//      recomputing the statistics on a 36x52 window per tile.
-// level-0 form: the coarser levels' OWN terms (n of them), combined here; ph / pw[k]: the zero padding level k was pooled into level k + 1 with
-// (0 on an even pyramid; 1080 -> 540 -> 270 -> 135 -> 68 pads 135), so pixel (y, x) of level k lies in cell ((y + ph) / 2, (x + pw) / 2)
-struct CoarseChain { const float* own[LV]; int H[LV], W[LV], ph[LV], pw[LV]; int n; };
-constexpr int SSIM_BWD_LDS = 3 * (2 * STH + HW_) * (STW + HW_);     // floats: a packed pair and a single map, each (26 + 16) x 42
-// `lds`: SSIM_BWD_LDS floats of the caller's LDS (8-byte aligned) -- a pointer so that a kernel whose blocks run EITHER this body or an FFT
-// body (loss_coarse_kernel) can give both the same allocation: two static arrays would add up and halve the blocks per CU
-template <bool LEVEL0>
-__device__ __forceinline__ void ssim_bwd_body(const SsimArgs& a, const CoarseChain* cc, float* lds, const int bx, const int by, const int bc, const int nbc) {
-    constexpr int GH = STH + HW_, GW = STW + HW_;        // 26 x 42 statistic-gradient region
-    pk2 (*sG01)[GW] = reinterpret_cast<pk2 (*)[GW]>(lds);                                   // packed pairs of maps, as in the forward pass
-    pk2 (*sA01)[GW] = reinterpret_cast<pk2 (*)[GW]>(lds + 2 * GH * GW);
-    float (*sG2)[GW] = reinterpret_cast<float (*)[GW]>(lds + 2 * GH * GW + 2 * STH * GW);
-    float (*sA2)[GW] = reinterpret_cast<float (*)[GW]>(lds + 3 * GH * GW + 2 * STH * GW);
-    const int tid = threadIdx.x;
-    const int py0 = by * STH, px0 = bx * STW;
-    const int wy0 = py0 - HW_, wx0 = px0 - HW_;
-    const int Hv = a.H - HW_, Wv = a.W - HW_;
-    const size_t plane = (size_t)a.H * a.W, mstride = (size_t)nbc * plane;
-    const float* Gp = a.G + (size_t)bc * plane;
-    {   // the whole 26 x 42 region of the three maps in flight (15 loads per thread), then the LDS stores
-        constexpr int NLD = (GH * GW + 255) / 256;
-        float l0[NLD], l1[NLD], l2[NLD];
-#pragma unroll
-        for (int u = 0; u < NLD; ++u) {
-            const int i = tid + u * 256;
-            const int r = i / GW, c = i - r * GW;
-            const int oy = wy0 + r, ox = wx0 + c;
-            l0[u] = 0.f; l1[u] = 0.f; l2[u] = 0.f;
-            if (i < GH * GW && oy >= 0 && oy < Hv && ox >= 0 && ox < Wv) {
-                const size_t o = (size_t)oy * a.W + ox;
-                l0[u] = Gp[o]; l1[u] = Gp[mstride + o]; l2[u] = Gp[2 * mstride + o];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < NLD; ++u) {
-            const int i = tid + u * 256;
-            if (i < GH * GW) { (&sG01[0][0])[i] = pk2{l0[u], l1[u]}; (&sG2[0][0])[i] = l2[u]; }
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < STH * GW; i += 256) {
-        const int r = i / GW, c = i - r * GW;
-        pk2 a01 = {0.f, 0.f};
-        float a2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < WS_; ++k) {
-            const float g = a.win.g[k];
-            a01 = pk_fma(pk2{g, g}, sG01[r + HW_ - k][c], a01);
-            a2 = fmaf(g, sG2[r + HW_ - k][c], a2);
-        }
-        sA01[r][c] = a01; sA2[r][c] = a2;
-    }
-    __syncthreads();
-    const float coef = a.coef ? a.coef[bc] : a.coef_k;
-    const float* X = a.X + (size_t)bc * plane;
-    const float* Y = a.Y + (size_t)bc * plane;
-    for (int i = tid; i < STH * STW; i += 256) {
-        const int r = i / STW, c = i - r * STW;
-        const int y = py0 + r, x = px0 + c;
-        if (y >= a.H || x >= a.W) continue;
-        pk2 a01 = {0.f, 0.f};
-        float a2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < WS_; ++k) {
-            const float g = a.win.g[k];
-            a01 = pk_fma(pk2{g, g}, sA01[r][c + HW_ - k], a01);
-            a2 = fmaf(g, sA2[r][c + HW_ - k], a2);
-        }
-        const float a0 = a01.x, a1 = a01.y;
-        const float xv = X[(size_t)y * a.W + x], yv = Y[(size_t)y * a.W + x];
-        float d = coef * (a0 + 2.f * xv * a1 + yv * a2);
-        if (a.dcoarse) d += 0.25f * a.dcoarse[((size_t)bc * a.Hc + (y + a.ph) / 2) * a.Wc + (x + a.pw) / 2];
-        if (LEVEL0 && cc != nullptr && cc->n > 0) {
-            // even pyramid: the coarser levels stored only their OWN terms; d_k = own_k + 0.25 d_{k+1} is evaluated here, innermost first,
-            // exactly as the level-by-level launches did (0.25 * is exact), so the gradient keeps its bits
-            float dc = 0.f;
-            int yk[LV], xk[LV];
-            yk[0] = y; xk[0] = x;
-#pragma unroll
-            for (int k = 1; k < LV; ++k) { yk[k] = (yk[k - 1] + cc->ph[k - 1]) >> 1; xk[k] = (xk[k - 1] + cc->pw[k - 1]) >> 1; }
-#pragma unroll
-            for (int k = LV - 1; k >= 1; --k) {
-                if (k > cc->n) continue;
-                const float o = cc->own[k][((size_t)bc * cc->H[k] + yk[k]) * cc->W[k] + xk[k]];
-                dc = (k == cc->n) ? o : o + 0.25f * dc;
-            }
-            d += 0.25f * dc;
-        }
-        if (LEVEL0) {
-            const float df = xv - yv;
-            const float sg = (df > 0.f) ? 1.f : ((df < 0.f) ? -1.f : 0.f);
-            d += a.k_l1 * sg + a.k_l2 * df;
-        }
-        float* dst = a.dX + ((size_t)bc * a.H + y) * a.W + x;
-        *dst = (LEVEL0 && a.acc) ? d + *dst : d;
-    }
-}
 template <bool LEVEL0>
 __global__ __launch_bounds__(256) void ssim_bwd_from_g_kernel(const SsimArgs a) {
     __shared__ __attribute__((aligned(16))) float sl[SSIM_BWD_LDS];
