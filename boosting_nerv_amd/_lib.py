@@ -107,6 +107,17 @@ class CemChunkBwd(C.Structure):
     _fields_ = [("it", CemItemBwd * CEM_MAX_TENSORS), ("n_items", C.c_int), ("training", C.c_int), ("first", C.c_int), ("_pad", C.c_int)]
 
 
+DEQUANT_CHUNK = 8192      # BNERV_DEQUANT_CHUNK
+
+
+class DequantItem(C.Structure):
+    _fields_ = [("q", _fp), ("out", _fp), ("scale", _fp), ("beta", _fp), ("n", C.c_int), ("_pad", C.c_int)]
+
+
+class DequantChunk(C.Structure):
+    _fields_ = [("it", DequantItem * CEM_MAX_TENSORS), ("n_items", C.c_int), ("_pad", C.c_int)]
+
+
 # every symbol include/bnerv.h declares: name -> (restype, argtypes)
 _I, _Z, _V, _F = C.c_int, C.c_size_t, C.c_void_p, C.c_float
 SYMBOLS = {
@@ -154,6 +165,8 @@ SYMBOLS = {
     "bnerv_cem_ws_bytes": (_Z, [_I, _I]),
     "bnerv_cem_scale_fwd": (_I, [_V, C.POINTER(CemChunk), _V, _V, _Z]),
     "bnerv_cem_scale_bwd": (_I, [_V, C.POINTER(CemChunkBwd), _V, _V, _V, _V, _Z]),
+    "bnerv_dequant_table": (_I, [_V, C.POINTER(DequantChunk)]),
+    "bnerv_frame_to_u8": (_I, [_V, _V, _V, _I, _I, _I]),
     "bnerv_dense_gemm_fwd": (_I, [_V, _V, _V, _V, _V, _V, _I, _I, _I, _I]),
     "bnerv_dense_gemm_bwd_ws_bytes": (_Z, [_I, _I, _I]),
     "bnerv_dense_gemm_bwd": (_I, [_V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _Z, _I, _I, _I, _I]),

@@ -1,0 +1,352 @@
+"""Encoder and decoder of the compression bitstream (bitstream.py).
+
+encode() writes what train_nerv_compression.evaluate() scores: the same integer symbols under the same Gaussians through the same
+range-ANS coder, so the coded words of the file are the bits evaluate() reports as `real`.  Decoder rebuilds the model from the file's
+header without quantisers, ANS-decodes every record on the host, de-quantises the symbols straight into the parameter tensors (and
+HNeRV_Boost's frame embeddings) with one table-driven launch per 48 tensors (ops.dequant_table), and replays the forward plus the
+uint8 packing kernel as a captured graph -- the frames evaluate() scored, bit for bit.
+
+    python -m boosting_nerv_amd.codec decode FILE --out DIR [--format png|npy]
+    python -m boosting_nerv_amd.codec info FILE"""
+import argparse
+import json
+import os
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+from . import bitstream
+from .bitstream import Record
+
+# the settings the model constructors read (model_nerv.py, model_hnerv.py, model_enerv.py, model_blocks.py), resolved: fc_dim after the size
+# solver, enc_dim after its rewrite -- the architecture rows of args.yaml
+SETTINGS_KEYS = ("model", "embed", "lfreq", "fc_hw", "fc_dim", "ch_t", "ks", "enc_blks", "enc_strds", "enc_dim", "dec_strds", "dec_blks", "reduce",
+                 "lower_width", "conv_type", "norm", "act", "sft_block", "out_bias", "block_dim")
+MODELS = ("NeRV_Boost", "ENeRV_Boost", "HNeRV_Boost")
+
+
+def _plain(v):
+    if isinstance(v, (bool, str)) or v is None:
+        return v
+    if isinstance(v, (int, np.integer)):
+        return int(v)
+    if isinstance(v, (float, np.floating)):
+        return float(v)
+    if isinstance(v, (list, tuple)):
+        return [_plain(x) for x in v]
+    raise TypeError(f"codec: setting of type {type(v).__name__} cannot be stored in the header")
+
+
+def _settings(args, n_frames, frame_hw):
+    s = {k: _plain(getattr(args, k)) for k in SETTINGS_KEYS if hasattr(args, k)}
+    missing = [k for k in SETTINGS_KEYS if k not in s]
+    if missing:
+        raise ValueError(f"codec.encode: args lacks the model settings {missing}")
+    s.update(full_data_length=int(n_frames), final_size=int(frame_hw[0] * frame_hw[1]), crop_list=f"{int(frame_hw[0])}_{int(frame_hw[1])}")
+    return s
+
+
+def _check_supported(model, entropy_model, args):
+    from .lib.transform_ops import Scale_T, ScaleBeta_T
+    name = getattr(args, "model", type(model).__name__)
+    if name not in MODELS or type(model).__name__ not in MODELS:
+        raise NotImplementedError(f"codec.encode: --model {name} has no bitstream (the CEM compression path is built for {', '.join(MODELS)}; "
+                                  "the HNeRV baseline has no quantised form here)")
+    if entropy_model is None or getattr(entropy_model, "distribution", None) != "gaussian":
+        raise NotImplementedError("codec.encode: only the Gaussian rate model is coded")
+    mods = model._quant_modules()
+    if not mods or not getattr(mods[0], "quant", False):
+        raise NotImplementedError("codec.encode: the model was built without --quant: there are no symbols to code")
+    for m in mods:
+        for kind in ("weight", "bias"):
+            if getattr(m, kind) is None:
+                continue
+            q = getattr(m, f"{kind}_quantizer")
+            if type(q) is not Scale_T:
+                raise NotImplementedError(f"codec.encode: {kind} quantiser {type(q).__name__} is not coded (the recipes' --quantizer_w / _b scale is)")
+            if q.per_channel:
+                raise NotImplementedError(f"codec.encode: per-channel {kind} scales are not coded (one scale per tensor is)")
+    if name == "HNeRV_Boost":
+        q = model.embed_quantizer
+        if type(q) is not ScaleBeta_T:
+            raise NotImplementedError(f"codec.encode: embedding quantiser {type(q).__name__} is not coded (the recipes' --quantizer_e scalebeta is)")
+        if q.per_channel:
+            raise NotImplementedError("codec.encode: per-channel embedding scales are not coded")
+
+
+def _code_symbols(symbols, mean, std, scale, beta=None):
+    """One record from what DiffEntropyModel.cal_bitrate is given at evaluation time -- the steps of
+    lib.entropy_model.compress_matrix_flatten_gaussian_global, keeping the message."""
+    from .lib.entropy_model import ans_encode_gaussian
+    mean = float(mean)
+    std = float(torch.as_tensor(std).clamp(1e-5, 1e10))
+    sym = symbols.detach().int().flatten().cpu().numpy()
+    lo, hi = int(sym.min()), int(sym.max())
+    if lo == hi:
+        hi = lo + 1
+    words = ans_encode_gaussian(sym, lo, hi, mean, std)
+    return Record(int(sym.size), np.float32(float(scale)), np.float32(mean), np.float32(std), lo, hi, words, None if beta is None else np.float32(float(beta)))
+
+
+def _tensor_records(model, entropy_model):
+    """Every weight / bias tensor as evaluate() accounts for it: the fused evaluation pass where it applies (it hands out the messages it
+    measures), the tensor-by-tensor loop otherwise.  Fills the modules' dequant_* and rate dictionaries as evaluate() does."""
+    got = []
+    fused = (os.environ.get("BNERV_CEM_EVAL_FUSED", "1") != "0" and getattr(model, "cem_fused", True)
+             and model.cal_params_eval_fused(entropy_model, records=got))
+    if fused:
+        return [Record(*r) for r in got]
+    records = []
+    for m in model._quant_modules():
+        for kind in ("weight", "bias"):
+            tensor = getattr(m, kind)
+            if tensor is None:
+                continue
+            quantizer = getattr(m, f"{kind}_quantizer")
+            code, symbols, dequant = quantizer(tensor)
+            setattr(m, "dequant_w" if kind == "weight" else "dequant_b", dequant)
+            rate = entropy_model.cal_bitrate(code, symbols, False)
+            getattr(m, "bitrate_w_dict" if kind == "weight" else "bitrate_b_dict").update(rate)
+            rec = _code_symbols(symbols, rate["mean"], rate["std"], quantizer.scale)
+            assert 32 * rec.words.size == rate["real_bitrate"]
+            records.append(rec)
+    return records
+
+
+def _raw_keys(model, is_hnerv):
+    """state_dict keys of the raw fp32 section, in state_dict order: everything that is neither the weight / bias of a quantised module nor a
+    quantiser's own parameter nor (HNeRV_Boost) part of the content encoder.  The same list on the encoder's model and on the decoder's."""
+    quantised = set(model._quant_modules())
+    covered = set()
+    for name, m in model.named_modules():
+        if m in quantised:
+            covered.update((f"{name}.weight", f"{name}.bias"))
+    return [k for k in model.state_dict().keys() if k not in covered and "quantizer." not in k and not (is_hnerv and k.startswith("encoder."))]
+
+
+def _frames_in_order(frames_or_loader, args, device):
+    """-> (n_frames, iterator of (index, [1, 3, H, W] device frame)) from a [N, 3, H, W] tensor or a loader of the training scripts (whose
+    samples carry 'idx' and either 'img' or nothing but the index of a clip resident on the device, args._frames_dev)."""
+    if frames_or_loader is None:
+        return int(args.full_data_length), iter(())
+    if torch.is_tensor(frames_or_loader):
+        n = frames_or_loader.shape[0]
+        return n, ((i, frames_or_loader[i:i + 1].to(device)) for i in range(n))
+    resident = getattr(args, "_frames_dev", None)
+    n = len(frames_or_loader.dataset)
+
+    def walk():
+        for sample in frames_or_loader:
+            idx = [int(i) for i in sample["idx"]]
+            batch = resident[torch.as_tensor(idx, device=resident.device)] if resident is not None else sample["img"].to(device)
+            for col, i in enumerate(idx):
+                yield i, batch[col:col + 1]
+    return n, walk()
+
+
+@torch.no_grad()
+def encode(model, entropy_model, args, frames_or_loader, path):
+    """Write the model (and, for HNeRV_Boost, every frame's embedding) as a bitstream to `path` (a file name or a binary file object);
+    returns bitstream.info of what was written.
+
+    frames_or_loader: the clip as a [N, 3, H, W] tensor or the full-clip loader of the training scripts; the models that decode from the
+    frame index alone (NeRV_Boost, ENeRV_Boost) read only its length (None: args.full_data_length).  Symbols, means and stds are those of evaluate()'s accounting:
+    the coded words of the file are get_bitrate_sum("real_bitrate") plus, with one frame per evaluation batch, the embedding bits."""
+    _check_supported(model, entropy_model, args)
+    device = next(model.parameters()).device
+    n_frames, frames = _frames_in_order(frames_or_loader, args, device)
+    is_hnerv = args.model == "HNeRV_Boost"
+    was_training = model.training
+    model.eval()
+    try:
+        tensors = _tensor_records(model, entropy_model)
+        embeds, embed_shape, frame_hw = {}, None, None
+        if is_hnerv:
+            transform = getattr(args, "transform_func", None)
+            scale, beta = model.embed_quantizer.scale, model.embed_quantizer.beta
+            for i, frame in frames:
+                img_in = frame if transform is None else transform(frame, torch.as_tensor([i], device=device))[0]
+                code, symbols, _ = model.forward_embed_quant(model.forward_encoder(img_in))
+                embeds[i] = _code_symbols(symbols, torch.mean(code), torch.std(code), scale, beta)
+                embed_shape, frame_hw = tuple(code.shape[1:]), tuple(frame.shape[-2:])
+            if sorted(embeds) != list(range(n_frames)):
+                raise ValueError(f"codec.encode: the loader delivered frames {sorted(embeds)[:4]}... of a {n_frames}-frame clip (a sharded loader?)")
+    finally:
+        model.train(was_training)
+    if frame_hw is None:
+        if hasattr(args, "crop_list"):
+            frame_hw = tuple(int(v) for v in args.crop_list.split("_")[:2])
+        elif torch.is_tensor(frames_or_loader):
+            frame_hw = tuple(frames_or_loader.shape[-2:])
+        else:
+            raise ValueError("codec.encode: the frame size is unknown (no args.crop_list and no frame tensor)")
+    sd = model.state_dict()
+    raw = [sd[k].detach().float().reshape(-1).cpu().numpy() for k in _raw_keys(model, is_hnerv)]
+    bitstream.write(path, _settings(args, n_frames, frame_hw), tensors, [embeds[i] for i in range(n_frames)] if is_hnerv else [], embed_shape, raw)
+    if hasattr(path, "getvalue"):
+        return bitstream.info(path.getvalue())
+    return bitstream.info(path) if not hasattr(path, "write") else None
+
+
+def describe(budget):
+    """One line of a bitstream.info budget (the log of train_nerv_compression --bitstream, `codec info`)."""
+    return (f"{budget['bytes']} bytes = {budget['total']} bits: coded words {budget['tensor_words']} ({budget['n_tensors']} tensors) + per-tensor side "
+            f"{budget['tensor_side']} + embeddings {budget['embed_words'] + budget['embed_side']} ({budget['n_embeds']} frames, {budget['embed_words']} coded) "
+            f"+ raw fp32 {budget['raw']} ({budget['n_raw']} entries) + header {budget['header']}")
+
+
+class Decoder:
+    """A bitstream, ready to decode frames on `device`.
+
+        dec = Decoder("clip.bnrv")
+        len(dec)                 frames of the clip
+        dec.decode_f32(i)        [1, 3, H, W] fp32 device tensor: the frame evaluate() scored
+        dec.decode_u8(i)         [H, W, 3] uint8 numpy array, (x.clamp(0, 1) * 255 + 0.5) as the image dump writes it
+        for frame in dec: ...    every frame as uint8, decoded ahead of the host: the device-to-host copy of frame i runs into one of two
+                                 pinned buffers while frame i + 1 decodes; the host waits on an event per frame, never on the device
+
+    use_graph=False decodes with eager launches instead of the captured graph (same kernels, same bits)."""
+
+    def __init__(self, path, device="cuda", use_graph=True):
+        from . import ops
+        from .engine import FrameDecodeGraph
+        from .lib.entropy_model import ans_decode_gaussian
+        from .train_nerv_all import build_model
+        bs = bitstream.read(path)
+        s = dict(bs.settings)
+        if s.get("model") not in MODELS:
+            raise ValueError(f"bitstream: header names the model {s.get('model')!r}; this build decodes {', '.join(MODELS)}")
+        self.settings = s
+        self.device = torch.device(device)
+        self.n_frames = int(s["full_data_length"])
+        self.frame_hw = tuple(int(v) for v in s["crop_list"].split("_")[:2])
+        self.is_hnerv = s["model"] == "HNeRV_Boost"
+        margs = SimpleNamespace(**s)
+        margs.__dict__.update(quant=False, outf="")
+        model = build_model(margs)
+        if self.is_hnerv:
+            model.encoder = torch.nn.Identity()            # the embeddings replace it: never written, never needed
+        model = model.to(self.device).eval().requires_grad_(False)
+        self.model = model
+
+        # host: ANS-decode every record into ONE pinned int32 array (segments start on 16-byte boundaries), upload it once
+        targets = []
+        for m in model._quant_modules():
+            targets.append(m.weight.data)
+            if m.bias is not None:
+                targets.append(m.bias.data)
+        if len(targets) != len(bs.tensors) or any(t.numel() != r.count for t, r in zip(targets, bs.tensors)):
+            raise ValueError("bitstream: the tensor records do not match the model the header describes")
+        if self.is_hnerv:
+            if len(bs.embeds) != self.n_frames or any(r.count != int(np.prod(bs.embed_shape)) for r in bs.embeds):
+                raise ValueError("bitstream: the embedding records do not match the header's frame count and embedding shape")
+            self.embeds = torch.empty(self.n_frames, *bs.embed_shape, dtype=torch.float32, device=self.device)
+            targets += [self.embeds[i] for i in range(self.n_frames)]
+        else:
+            if bs.embeds:
+                raise ValueError(f"bitstream: embedding records in a {s['model']} stream")
+            self.embeds = None
+        records = list(bs.tensors) + list(bs.embeds)
+        offs, total = [], 0
+        for r in records:
+            offs.append(total)
+            total += (r.count + 3) // 4 * 4
+        pin = self.device.type == "cuda"
+        sym_h = torch.zeros(total, dtype=torch.int32, pin_memory=pin)
+        sym_np = sym_h.numpy()
+        for r, o in zip(records, offs):
+            sym_np[o:o + r.count] = ans_decode_gaussian(r.words, r.count, r.lo, r.hi, float(r.mean), float(r.std))
+        coef_h = torch.tensor([float(r.scale) for r in records] + [float(r.beta) for r in bs.embeds], dtype=torch.float32)
+        sym_d = sym_h.to(self.device, non_blocking=True)
+        coef_d = coef_h.to(self.device)
+        n_rec = len(records)
+        ops.dequant_table([sym_d[o:o + r.count] for r, o in zip(records, offs)], [t.reshape(-1) for t in targets],
+                          [coef_d[i:i + 1] for i in range(n_rec)],
+                          [None] * len(bs.tensors) + [coef_d[n_rec + i:n_rec + i + 1] for i in range(len(bs.embeds))])
+
+        # raw fp32 section: the decoder's state_dict entries no record covers, in state_dict order
+        torch.cuda.current_stream().synchronize()          # (the pinned symbols may go now)
+        sd = model.state_dict()
+        rest = [sd[k] for k in _raw_keys(model, self.is_hnerv)]
+        if len(rest) != len(bs.raw) or any(v.numel() != a.size for v, a in zip(rest, bs.raw)):
+            raise ValueError("bitstream: the raw section does not match the model the header describes")
+        for v, a in zip(rest, bs.raw):
+            v.copy_(torch.from_numpy(a).reshape(v.shape))
+
+        self.norms = torch.tensor([float(i + 1) / self.n_frames for i in range(self.n_frames)], dtype=torch.float64, device=self.device)
+        first_embed = self.embeds[0:1] if self.is_hnerv else None
+        self._loop = FrameDecodeGraph(model, self.norms[0:1], first_embed, self.norms[0:1], self.frame_hw, use_graph=use_graph)
+        H, W = self.frame_hw
+        self._pinned = [torch.empty(H, W, 3, dtype=torch.uint8, pin_memory=pin) for _ in range(2)]
+        self._events = [torch.cuda.Event() for _ in range(2)] if pin else None
+
+    def __len__(self):
+        return self.n_frames
+
+    def _launch(self, i):
+        if not 0 <= i < self.n_frames:
+            raise IndexError(f"frame {i} of a {self.n_frames}-frame clip")
+        norm = self.norms[i:i + 1]
+        return self._loop.launch(norm, self.embeds[i:i + 1] if self.is_hnerv else None, norm)
+
+    def decode_f32(self, i):
+        return self._launch(i)[0].clone()
+
+    def _to_host(self, u8, slot):
+        self._pinned[slot].copy_(u8[0], non_blocking=True)
+        self._events[slot].record()
+
+    def decode_u8(self, i):
+        self._to_host(self._launch(i)[1], 0)
+        self._events[0].synchronize()
+        return self._pinned[0].numpy().copy()
+
+    def frames_u8(self, copy=True):
+        """Every frame in order as [H, W, 3] uint8.  copy=False yields views of the two pinned buffers: a view is valid until the
+        generator is resumed."""
+        take = (lambda a: a.numpy().copy()) if copy else (lambda a: a.numpy())
+        for i in range(self.n_frames):
+            self._to_host(self._launch(i)[1], i % 2)
+            if i:
+                self._events[(i - 1) % 2].synchronize()
+                yield take(self._pinned[(i - 1) % 2])
+        self._events[(self.n_frames - 1) % 2].synchronize()
+        yield take(self._pinned[(self.n_frames - 1) % 2])
+
+    def __iter__(self):
+        return self.frames_u8()
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(prog="python -m boosting_nerv_amd.codec", description="decode or inspect a compression bitstream")
+    sub = p.add_subparsers(dest="cmd", required=True)
+    d = sub.add_parser("decode", help="decode every frame of FILE into --out")
+    d.add_argument("file")
+    d.add_argument("--out", required=True, help="directory for frame_NNNN.png / .npy")
+    d.add_argument("--format", choices=("png", "npy"), default="png")
+    d.add_argument("--no_graph", action="store_true", help="eager launches instead of the captured graph")
+    i = sub.add_parser("info", help="print the bit budget of FILE")
+    i.add_argument("file")
+    a = p.parse_args(argv)
+    if a.cmd == "info":
+        budget = bitstream.info(a.file)
+        print(describe(budget))
+        print(json.dumps(budget))
+        return budget
+    if not torch.cuda.is_available():
+        raise RuntimeError("codec decode: no ROCm GPU visible -- the decoder path has no CPU fallback")
+    os.makedirs(a.out, exist_ok=True)
+    dec = Decoder(a.file, "cuda", use_graph=not a.no_graph)
+    for k, frame in enumerate(dec.frames_u8(copy=False)):
+        if a.format == "png":
+            from PIL import Image
+            Image.fromarray(frame).save(os.path.join(a.out, f"frame_{k:04d}.png"))
+        else:
+            np.save(os.path.join(a.out, f"frame_{k:04d}.npy"), frame)
+    print(f"decoded {len(dec)} frames of {dec.frame_hw[0]}x{dec.frame_hw[1]} into {a.out}")
+    return len(dec)
+
+
+if __name__ == "__main__":
+    main()

@@ -453,3 +453,57 @@ class DecodeGraph:
         self.graph.replay()
         torch.cuda.synchronize()
         return self.out, self._time.time() - t0
+
+
+class _ForwardAndPack:
+    """What FrameDecodeGraph captures: the model's forward followed by the packing kernel into a static uint8 frame."""
+    time_decode = False
+
+    def __init__(self, model, u8):
+        self.model, self.u8 = model, u8
+
+    def __call__(self, cur_input, embed, norm_idx=None):
+        from . import ops
+        out = self.model(cur_input, embed, norm_idx=norm_idx)[0]
+        ops.frame_to_u8(out, out=self.u8)
+        return (out,)
+
+
+class FrameDecodeGraph:
+    """The frame loop of a bitstream decoder (codec.Decoder): DecodeGraph's capture -- same warm-up, same weight-fragment plan -- of the
+    forward PLUS ops.frame_to_u8, replayed WITHOUT a host synchronisation.  `launch(cur_input, embed, norm_idx)` refreshes the static inputs
+    with device-side copies and replays on the current stream; `out` ([B, 3, H, W] fp32) and `u8` ([B, H, W, 3] uint8) are the static results,
+    valid in stream order until the next launch.  use_graph=False runs the same two steps eagerly into the same buffers."""
+
+    def __init__(self, model, cur_input, embed, norm_idx, frame_hw, use_graph=True):
+        self.use_graph = use_graph
+        self.u8 = torch.empty(norm_idx.shape[0], frame_hw[0], frame_hw[1], 3, dtype=torch.uint8, device=norm_idx.device)
+        self._body = _ForwardAndPack(model, self.u8)
+        td = getattr(model, "time_decode", False)
+        model.time_decode = False
+        try:
+            if use_graph:
+                self._dg = DecodeGraph(self._body, cur_input, embed, norm_idx)
+                self.inp, self.embed, self.norm, self.out = self._dg.inp, self._dg.embed, self._dg.norm, self._dg.out
+                torch.cuda.current_stream().synchronize()
+            else:
+                self._dg = None
+                self.inp, self.embed, self.norm = cur_input.clone(), None if embed is None else embed.clone(), norm_idx.clone()
+                with torch.no_grad():
+                    self.out = self._body(self.inp, self.embed, norm_idx=self.norm)[0]
+        finally:
+            model.time_decode = td
+        if tuple(self.out.shape[-2:]) != tuple(frame_hw):
+            raise ValueError(f"FrameDecodeGraph: the model decodes {tuple(self.out.shape[-2:])} frames, the caller announced {tuple(frame_hw)}")
+
+    def launch(self, cur_input, embed, norm_idx):
+        self.inp.copy_(cur_input, non_blocking=True)
+        self.norm.copy_(norm_idx, non_blocking=True)
+        if self.embed is not None:
+            self.embed.copy_(embed, non_blocking=True)
+        if self._dg is not None:
+            self._dg.graph.replay()
+        else:
+            with torch.no_grad():
+                self.out = self._body(self.inp, self.embed, norm_idx=self.norm)[0]
+        return self.out, self.u8

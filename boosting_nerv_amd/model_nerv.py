@@ -57,13 +57,15 @@ class _CEMHooks:
                 m.bitrate_w_dict.update(d)
         return True
 
-    def cal_params_eval_fused(self, entropy_model):
+    def cal_params_eval_fused(self, entropy_model, records=None):
         """Evaluation-time bit accounting of every weight / bias tensor (reference train_nerv_compression.py:466-489: quantise, keep the
         de-quantised tensor, estimate the rounded symbols' bits, code them) without the per-tensor loop: ONE fused quantise + rate pass
         (ops.cem_scale_rate, rounded symbols), ONE device -> host copy of the flat weights, scales and statistics, and the host
         rANS coder (csrc/ans.cpp) over the symbols rebuilt there -- np.rint(w / s) in float32 is the device's round(w / s) bit for
         bit (IEEE division, ties to even).  Fills the modules' dequant_w / dequant_b and rate dictionaries exactly as the loop does;
-        returns False when the model is outside the fused kernel's scope (per-channel scales, other quantisers, CPU tensors)."""
+        returns False when the model is outside the fused kernel's scope (per-channel scales, other quantisers, CPU tensors).
+        records: a list that receives, per tensor, what the coder was given and what it produced -- (numel, scale, mean, std, lo, hi,
+        words) -- for whoever keeps the message instead of its length (codec.encode)."""
         import numpy as np
         from . import ops
         from .lib.entropy_model import ans_encode_gaussian
@@ -91,7 +93,11 @@ class _CEMHooks:
             off += t.numel()
             lo, hi = int(sym.min()), int(sym.max())
             std = float(np.clip(stats_h[i, 2], 1e-5, 1e10))                     # (compress_matrix_flatten_gaussian_global's clamp)
-            real = int(ans_encode_gaussian(sym, lo, hi if hi > lo else lo + 1, float(stats_h[i, 1]), std).size) * 32
+            hi = hi if hi > lo else lo + 1
+            words = ans_encode_gaussian(sym, lo, hi, float(stats_h[i, 1]), std)
+            real = int(words.size) * 32
+            if records is not None:
+                records.append((int(sym.size), np.float32(scales_h[i]), np.float32(stats_h[i, 1]), np.float32(std), lo, hi, words))
             d = {"bitrate": bits[i], "mean": stats[i, 1], "std": stats[i, 2], "real_bitrate": real}
             if is_bias:
                 m.dequant_b = deqs[i].reshape(t.shape)

@@ -909,6 +909,54 @@ def cem_scale_rate(ws, scales, noises, training):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# bitstream decoder (codec.py): symbols -> parameters, decoded frame -> interleaved bytes (csrc/codec.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+def dequant_table(symbols, outs, scales, betas=None):
+    """outs[i][...] = symbols[i].float() * scales[i]  (+ betas[i] where given), written IN PLACE with the bits of torch's `quant * scale`
+    (`+ beta`): Scale_T / ScaleBeta_T de-quantisation of int32 symbol tensors, <= CEM_MAX_TENSORS tensors per launch.  symbols / outs:
+    contiguous int32 / fp32 device tensors of equal numel (views at any 4-byte offset are fine); scales / betas: 1-element fp32 device
+    tensors (betas: None, or a list with None entries)."""
+    n = len(symbols)
+    betas = [None] * n if betas is None else betas
+    if not (len(outs) == len(scales) == len(betas) == n):
+        raise ValueError("dequant_table: symbols, outs, scales and betas must have one entry per tensor")
+    for i in range(n):
+        q, o = L.require_device(symbols[i], "symbols"), L.require_device(outs[i], "out")
+        if q.dtype != torch.int32 or o.dtype != torch.float32 or not q.is_contiguous() or not o.is_contiguous() or q.numel() != o.numel() or q.numel() == 0:
+            raise ValueError(f"dequant_table: item {i}: need non-empty contiguous int32 symbols and an fp32 output of the same numel "
+                             f"(got {q.dtype} {tuple(q.shape)}, {o.dtype} {tuple(o.shape)})")
+        for t, what in ((scales[i], "scale"), (betas[i], "beta")):
+            if t is not None and (t.dtype != torch.float32 or t.numel() != 1 or not t.is_cuda):
+                raise ValueError(f"dequant_table: item {i}: {what} must be a 1-element fp32 device tensor (per-tensor quantisers only)")
+    lib = L.load()
+    for i0 in range(0, n, L.CEM_MAX_TENSORS):
+        ck = L.DequantChunk()
+        m = min(L.CEM_MAX_TENSORS, n - i0)
+        for j in range(m):
+            i = i0 + j
+            ck.it[j].q, ck.it[j].out, ck.it[j].scale, ck.it[j].n = symbols[i].data_ptr(), outs[i].data_ptr(), scales[i].data_ptr(), symbols[i].numel()
+            ck.it[j].beta = betas[i].data_ptr() if betas[i] is not None else None
+        ck.n_items = m
+        L.check(lib.bnerv_dequant_table(L.stream(), C.byref(ck)), "bnerv_dequant_table")
+    return outs
+
+
+def frame_to_u8(x, out=None):
+    """[B, 3, H, W] fp32 -> [B, H, W, 3] uint8 = (x.clamp(0, 1) * 255 + 0.5).to(uint8).permute(0, 2, 3, 1) in one pass (the image
+    convention of train_nerv_all._save_images).  out: a contiguous uint8 buffer to write into (a captured decode's)."""
+    x = L.require_device(x.detach(), "x")
+    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError(f"frame_to_u8: need a non-empty contiguous fp32 [B, 3, H, W] tensor, got {x.dtype} {tuple(x.shape)}")
+    B, _, H, W = x.shape
+    if out is None:
+        out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=x.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, H, W, 3) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"frame_to_u8: out must be a contiguous uint8 [{B}, {H}, {W}, 3] tensor on {x.device}")
+    L.check(L.load().bnerv_frame_to_u8(L.stream(), L.ptr(x), L.ptr(out), B, H, W), "bnerv_frame_to_u8")
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # depthwise conv of the ConvNeXt encoder block (first kernels of row N3)
 # ----------------------------------------------------------------------------------------------------------------------
 class _DWConv(torch.autograd.Function):

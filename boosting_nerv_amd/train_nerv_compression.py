@@ -44,6 +44,7 @@ def build_parser():
     add('--embed_entropy', action='store_true', default=False, help='use entropy model for embedding')
     add('--target_bit', type=float, default=5)
     add('--lambda_rate', type=float, default=0.2)
+    add('--bitstream', type=str, default=None, help='write the final evaluation\'s coded model (and embeddings) to this file (codec.py decodes it)')
     return p
 
 
@@ -159,7 +160,7 @@ def train(local_rank, args):
     if args.eval_only:
         # (no init_data() here: the quantiser scales come from the checkpoint -- re-initialising them from the weight range would
         #  report the rate / quality of a different model; the reference initialises them on the training path only)
-        values, hw = evaluate(model, full_loader, local_rank, args, args.dump_vis, coding=True, entropy_model=entropy_model)
+        values, hw = evaluate(model, full_loader, local_rank, args, args.dump_vis, coding=True, entropy_model=entropy_model, write_bitstream=True)
         top = rt.BestTracker(args.metric_names).update(values)
         text = f'PSNR for output {hw} for quant {args.quant_str}: ' + ''.join(
             f'best_{n}: {rt.fmt(v, 4)} | ' for n, v in zip(args.metric_names, top))      # 4 decimals for every metric (train_nerv_compression.py:317)
@@ -212,7 +213,8 @@ def train(local_rank, args):
         epoch_secs.append(now - t_epoch)
         last = epoch == args.epochs - 1
         if (epoch + 1) % args.eval_freq == 0 or (args.epochs - epoch) in (1, 3, 5):
-            values, hw = evaluate(model, full_loader, local_rank, args, args.dump_vis and last, coding=True, entropy_model=entropy_model)
+            values, hw = evaluate(model, full_loader, local_rank, args, args.dump_vis and last, coding=True, entropy_model=entropy_model,
+                                  write_bitstream=last)
             best.update(values)
             psnr_trace.append(values[args.metric_names.index('quant_seen_psnr')].max())
             if is_main:
@@ -231,11 +233,12 @@ def train(local_rank, args):
 
 
 @torch.no_grad()
-def evaluate(model, full_dataloader, local_rank, args, dump_vis=False, coding=False, entropy_model=None):
+def evaluate(model, full_dataloader, local_rank, args, dump_vis=False, coding=False, entropy_model=None, write_bitstream=False):
     """Quality of the model run with its DE-QUANTISED weights and embeddings (filed under the quant_* metric slots, as the
     reference does, train_nerv_compression.py:457-585) and the bit accounting: bits the rate model estimates for the rounded
     symbols, and the bytes an ANS coder actually produces for them (lib/entropy_model.py -> csrc/ans.cpp), plus 32 bits for every
-    transmitted quantiser / entropy-model parameter."""
+    transmitted quantiser / entropy-model parameter.  write_bitstream (the final evaluation) with --bitstream PATH: the coded words are kept --
+    codec.encode writes the file codec.Decoder turns back into the frames scored here -- and its size and bit budget are logged."""
     book = rt.MetricBook(args.val_ind_list, args.metric_names)
     log = rt.RunLog(args.outf, local_rank in (0, None))
     model.eval()
@@ -303,6 +306,10 @@ def evaluate(model, full_dataloader, local_rank, args, dump_vis=False, coding=Fa
         args.estimate_bpp = (est_bits + side_bits) / pixels
         log.line(f'Gaussian Entropy Model real bpp: {round(args.total_bpp, 6)}, estimated bpp:{round(args.estimate_bpp, 6)}, '
                  f'target_bpp:{round(args.target_bpp, 6)} \n', every_rank=False)
+        if write_bitstream and getattr(args, 'bitstream', None) and local_rank in (0, None):
+            from . import codec
+            args.bitstream_budget = codec.encode(model, entropy_model, args, full_dataloader, args.bitstream)
+            log.line(f'Bitstream {args.bitstream}: {codec.describe(args.bitstream_budget)} \n', every_rank=False)
     return values, hw
 
 

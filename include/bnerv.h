@@ -341,6 +341,22 @@ int bnerv_cem_scale_bwd(void* stream, const bnerv_cem_chunk_bwd* chunk, const fl
                         void* ws, size_t ws_bytes);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Bitstream decoder (additive to ABI 9; csrc/codec.hip, boosting_nerv_amd/codec.py).
+ *   bnerv_dequant_table:  for every item  out[i] = float(q[i]) * scale[0]  (+ beta[0] when beta != NULL), i < n: the de-quantisation of
+ *       Scale_T / ScaleBeta_T (lib/transform_ops.py) from int32 symbols, every product and sum ONE IEEE fp32 operation (no fused
+ *       multiply-add), i.e. the bits of torch's `quant * scale` and `quant * scale + beta`.  <= BNERV_CEM_MAX_TENSORS items per launch (the
+ *       table travels by value), every item cut into chunks of BNERV_DEQUANT_CHUNK elements, one block each.  16-byte loads / stores where q
+ *       and out are 16-byte aligned and n % 4 == 0, element by element otherwise (4-byte alignment is all that is required).
+ *   bnerv_frame_to_u8:  x [B, 3, H, W] fp32 planar -> out [B, H, W, 3] uint8 interleaved, u = (uint8)(clamp(x, 0, 1) * 255.0f + 0.5f) with the
+ *       multiply and the add rounded separately (train_nerv_all._save_images).  Four pixels per thread (three 16-byte loads, three dword
+ *       stores) where H * W % 4 == 0, x is 16-byte and out 4-byte aligned; pixel by pixel otherwise.  NaN inputs are not defined. */
+#define BNERV_DEQUANT_CHUNK 8192
+typedef struct { const int* q; float* out; const float* scale; const float* beta; int n; int _pad; } bnerv_dequant_item;
+typedef struct { bnerv_dequant_item it[BNERV_CEM_MAX_TENSORS]; int n_items; int _pad; } bnerv_dequant_chunk;
+int bnerv_dequant_table(void* stream, const bnerv_dequant_chunk* chunk);
+int bnerv_frame_to_u8(void* stream, const float* x, unsigned char* out, int B, int H, int W);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * GEMM-shaped dense work on v_mfma_f32_16x16x4_f32 (csrc/gemm.hip).
  *
  * Dense layers applied to many rows (B >= 16: the token MLPs of E-NeRV's transformer stem, NeRV_MLP at larger batches;

@@ -1,43 +1,232 @@
-"""Decode (forward-only) rate of the C1 decoder on the HIP path: frames/s for single-frame decodes under torch.no_grad(),
-eager and as a captured hipGraph (N4 row: the figure the reference logs as "FPS" in evaluate())."""
-import os, sys, time, torch
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import bench
-dev = torch.device("cuda:0")
-args, model = bench.build(sys.argv[1] if len(sys.argv) > 1 else "c1")
-model = model.to(dev).eval()
-N = 132
-idx = torch.tensor([[37 / N]], dtype=torch.float64, device=dev).reshape(1)
-with torch.no_grad():
-    for _ in range(5):
-        out = model(idx, norm_idx=idx)[0]
-    torch.cuda.synchronize()
-    t0 = time.time()
-    for _ in range(100):
-        out = model(idx, norm_idx=idx)[0]
-    torch.cuda.synchronize()
-    print(f"eager decode : {100 / (time.time() - t0):8.1f} frames/s")
-    g = torch.cuda.CUDAGraph(); s = torch.cuda.Stream()
+"""Decode rates on the HIP path.
+
+    python tools/kdecode.py [c1|c3|c4]            forward-only frames/s of a bench.py decoder: eager, captured, engine.DecodeGraph
+    python tools/kdecode.py --bitstream [...]     the bitstream decoder (codec.py), below
+
+--bitstream times, in ONE process:
+  (1) bitstream -> model-ready: codec.Decoder(file) -- header, host rANS decode of every record, one upload of the symbols, the
+      de-quantisation launches, the raw section, the warm-up forwards and (with the graph) the capture -- host clock, ends in a device
+      synchronisation; the first construction of the process (code objects, lazily built tables) is reported apart;
+  (2) frames per second of the frame loop, replay -> pinned host uint8 (Decoder.frames_u8(copy=False): forward + packing kernel, the
+      device-to-host copy into one of two pinned buffers, one event wait per frame), captured graph and eager launches alternated;
+  (3) bnerv_frame_to_u8 against the torch expression it replaces, (x.clamp(0, 1) * 255 + 0.5).to(uint8).permute(0, 2, 3, 1).contiguous(),
+      at 720p and 1080p: both captured `reps` times into a graph and replayed (HIP events; a Python-driven launch costs more host time
+      than either takes on the GPU), alternated over the rounds; outputs compared first.
+Cases: "c1q" -- the C1 model (NeRV_Boost 1.5M, 720x1280) built with the compression recipe's quantiser flags; "c5" -- BASELINE configs[4]
+(HNeRV_Boost 3M, 1080x1920, quantised embeddings).  Weights are the seeded initialisation with init_data() scales: the timing does not
+depend on what the weights say.
+usage: python tools/kdecode.py --bitstream [--frames 16] [--rounds 3] [--only c1q|c5|pack]   (needs the GPU)"""
+import argparse
+import io
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+QUANT_FLAGS = ("--embed_entropy --quant --quant_model_bit 8 --quant_bias_bit 8 --quant_embed_bit 8 --quantizer_w scale --quantizer_b scale "
+               "--quantizer_e scalebeta")
+
+
+def build(case):
+    import torch
+    import bench
+    from boosting_nerv_amd import train_nerv_all as T
+    from boosting_nerv_amd import train_nerv_compression as T5
+    if case == "c5":
+        return bench.build("c5")
+    r = bench.RECIPES["c1"]
+    args = T5.build_parser().parse_args(r["flags"].split() + QUANT_FLAGS.split() + ["--data_path", f"synthetic:{r['n']}x{r['h']}x{r['w']}", "--vid", "bench"])
+    args.final_size, args.full_data_length, args.outf = r["h"] * r["w"], r["n"], "bench"
+    args.fc_dim, _ = T.solve_fc_dim(args, args.final_size, args.full_data_length)
+    torch.manual_seed(args.manualSeed)
+    return args, T.build_model(args)
+
+
+def time_graph(fns, reps=50, rounds=5):
+    """us per call of every fn in fns on the GPU: `reps` calls of each captured into a graph of its own; the graphs replayed in turn,
+    `rounds` times; -> [(best, worst)] per fn."""
+    import torch
     from boosting_nerv_amd import _lib as L
-    with torch.cuda.stream(s):
-        L.ctx()                                  # the capture stream's library context (and its scratch) must exist before the capture
-        with torch.cuda.graph(g, stream=s):
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    graphs, out = [], [[] for _ in fns]
+    with torch.cuda.stream(side):
+        for fn in fns:
+            for _ in range(3):
+                fn()
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with L.graph_capture(g, stream=side):
+                for _ in range(reps):
+                    fn()
+            graphs.append(g)
+        torch.cuda.synchronize()
+        for g in graphs:
+            g.replay()
+        torch.cuda.synchronize()
+        for _ in range(rounds):
+            for k, g in enumerate(graphs):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                g.replay()
+                e1.record()
+                torch.cuda.synchronize()
+                out[k].append(e0.elapsed_time(e1) * 1e3 / reps)
+    torch.cuda.current_stream().wait_stream(side)
+    return [(min(v), max(v)) for v in out]
+
+
+def run_pack(rounds):
+    import torch
+    from boosting_nerv_amd import ops
+    dev = torch.device("cuda:0")
+    slower = False
+    for name, (h, w) in (("720p", (720, 1280)), ("1080p", (1080, 1920))):
+        x = (torch.rand(1, 3, h, w, generator=torch.Generator().manual_seed(1)) * 1.2 - 0.1).to(dev)
+        buf = torch.empty(1, h, w, 3, dtype=torch.uint8, device=dev)
+        chain = lambda: (x.clamp(0, 1) * 255 + 0.5).to(torch.uint8).permute(0, 2, 3, 1).contiguous()      # noqa: E731
+        assert torch.equal(ops.frame_to_u8(x, out=buf), chain())
+        (k_lo, k_hi), (t_lo, t_hi) = time_graph([lambda: ops.frame_to_u8(x, out=buf), chain], rounds=max(rounds, 3))
+        nbytes = 15 * h * w
+        print(f"pack {name}: bnerv_frame_to_u8 {k_lo:.1f} us (worst {k_hi:.1f}; {nbytes / k_lo / 1e3:.0f} GB/s of its 15 B/pixel) | torch chain {t_lo:.1f} us "
+              f"(worst {t_hi:.1f}) | torch / kernel = {t_lo / k_lo:.2f}" + ("   ** the kernel is SLOWER **" if k_lo > t_lo else ""), flush=True)
+        slower = slower or k_lo > t_lo
+    return slower
+
+
+def run_case(case, n_frames, rounds):
+    import torch
+    from boosting_nerv_amd import bitstream, codec
+    from boosting_nerv_amd.lib.entropy_model import DiffEntropyModel
+    from boosting_nerv_amd.synth import SyntheticVideo
+    dev = torch.device("cuda:0")
+    args, model = build(case)
+    model = model.to(dev)
+    model.init_data()
+    h, w = (int(v) for v in args.crop_list.split("_")[:2])
+    is_hnerv = args.model == "HNeRV_Boost"
+    frames = None
+    if is_hnerv:
+        vid = SyntheticVideo(n_frames, h, w)
+        frames = torch.stack([vid.frame(i, device=dev) for i in range(n_frames)])
+        with torch.no_grad():
+            model.embed_quantizer.init_data(model.forward_encoder(frames[0:1]))
+    args.full_data_length = n_frames
+    buf = io.BytesIO()
+    torch.cuda.synchronize()
+    t0 = time.time()
+    budget = codec.encode(model, DiffEntropyModel("gaussian"), args, frames, buf)
+    torch.cuda.synchronize()
+    blob = buf.getvalue()
+    n_par = sum(m.weight.numel() + (m.bias.numel() if m.bias is not None else 0) for m in model._quant_modules())
+    print(f"{case}: {args.model} {h}x{w}, {n_par} quantised parameters, {n_frames} frames; encode {time.time() - t0:.2f} s; file {codec.describe(budget)}", flush=True)
+    del model
+
+    # (1) bitstream -> model-ready
+    ready = {}
+    for label, use_graph in (("first construction of the process (eager)", False), ("eager", False), ("graph", True), ("eager", False), ("graph", True)):
+        t0 = time.time()
+        bitstream.read(blob)
+        t_read = time.time() - t0
+        dec = None                                             # (the previous decoder is released outside the timed window)
+        torch.cuda.synchronize()
+        t0 = time.time()
+        dec = codec.Decoder(blob, dev, use_graph=use_graph)
+        torch.cuda.synchronize()
+        ready.setdefault(label, []).append(time.time() - t0)
+        print(f"{case} model-ready, {label}: {ready[label][-1] * 1e3:.1f} ms (container parse + CRC alone: {t_read * 1e3:.1f} ms)", flush=True)
+    dec_g = dec
+    dec_e = codec.Decoder(blob, dev, use_graph=False)
+
+    # (2) frame loop: replay -> pinned host u8
+    fps = {"graph": [], "eager": []}
+    loops = max(1, 64 // n_frames)
+    for d in (dec_g, dec_e):                                   # warm-up of both
+        for _ in d.frames_u8(copy=False):
+            pass
+    for r in range(rounds):
+        for label, d in (("graph", dec_g), ("eager", dec_e)):
+            torch.cuda.synchronize()
+            t0 = time.time()
+            for _ in range(loops):
+                for _ in d.frames_u8(copy=False):
+                    pass
+            torch.cuda.synchronize()
+            fps[label].append(loops * n_frames / (time.time() - t0))
+            print(f"{case} round {r} frame loop, {label}: {fps[label][-1]:.1f} frames/s ({1e3 / fps[label][-1]:.3f} ms/frame)", flush=True)
+    for label, v in fps.items():
+        print(f"{case} frame loop, {label}: {sum(v) / len(v):.1f} frames/s (min {min(v):.1f}, max {max(v):.1f} over {rounds} rounds of {loops * n_frames} frames)")
+    for label, v in ready.items():
+        print(f"{case} model-ready, {label}: {min(v) * 1e3:.1f} ms best of {len(v)}")
+
+
+def forward_rates(cfg):
+    """Decode (forward-only) rate of a bench.py decoder (c1 | c3 | c4) on the HIP path: frames/s for single-frame decodes under
+    torch.no_grad(), eager and as a captured hipGraph (N4 row: the figure the reference logs as "FPS" in evaluate())."""
+    import torch
+    import bench
+    dev = torch.device("cuda:0")
+    args, model = bench.build(cfg)
+    model = model.to(dev).eval()
+    N = 132
+    idx = torch.tensor([[37 / N]], dtype=torch.float64, device=dev).reshape(1)
+    with torch.no_grad():
+        for _ in range(5):
             out = model(idx, norm_idx=idx)[0]
-    g.replay(); torch.cuda.synchronize()
-    t0 = time.time()
-    for _ in range(300):
-        g.replay()
-    torch.cuda.synchronize()
-    print(f"graph decode : {300 / (time.time() - t0):8.1f} frames/s   ({(time.time() - t0) / 300 * 1e3:.3f} ms/frame)")
-    # engine.DecodeGraph: the same captured forward with the decoder's weight fragments prepared once (context plan, ABI 4)
-    from boosting_nerv_amd.engine import DecodeGraph
-    embed = model(idx, norm_idx=idx)[1][0]
-    dg = DecodeGraph(model, idx, embed, idx)
-    ref = model(idx, embed, norm_idx=idx)[0]
-    assert torch.equal(dg(idx, embed, idx)[0], ref)
-    torch.cuda.synchronize()
-    t0 = time.time()
-    for _ in range(300):
-        dg.graph.replay()
-    torch.cuda.synchronize()
-    print(f"DecodeGraph  : {300 / (time.time() - t0):8.1f} frames/s   ({(time.time() - t0) / 300 * 1e3:.3f} ms/frame), {dg.wplan_entries} planned weight tensors")
+        torch.cuda.synchronize()
+        t0 = time.time()
+        for _ in range(100):
+            out = model(idx, norm_idx=idx)[0]
+        torch.cuda.synchronize()
+        print(f"eager decode : {100 / (time.time() - t0):8.1f} frames/s")
+        g = torch.cuda.CUDAGraph(); s = torch.cuda.Stream()
+        from boosting_nerv_amd import _lib as L
+        with torch.cuda.stream(s):
+            L.ctx()                                  # the capture stream's library context (and its scratch) must exist before the capture
+            with torch.cuda.graph(g, stream=s):
+                out = model(idx, norm_idx=idx)[0]
+        g.replay(); torch.cuda.synchronize()
+        t0 = time.time()
+        for _ in range(300):
+            g.replay()
+        torch.cuda.synchronize()
+        print(f"graph decode : {300 / (time.time() - t0):8.1f} frames/s   ({(time.time() - t0) / 300 * 1e3:.3f} ms/frame)")
+        # engine.DecodeGraph: the same captured forward with the decoder's weight fragments prepared once (context plan, ABI 4)
+        from boosting_nerv_amd.engine import DecodeGraph
+        embed = model(idx, norm_idx=idx)[1][0]
+        dg = DecodeGraph(model, idx, embed, idx)
+        ref = model(idx, embed, norm_idx=idx)[0]
+        assert torch.equal(dg(idx, embed, idx)[0], ref)
+        torch.cuda.synchronize()
+        t0 = time.time()
+        for _ in range(300):
+            dg.graph.replay()
+        torch.cuda.synchronize()
+        print(f"DecodeGraph  : {300 / (time.time() - t0):8.1f} frames/s   ({(time.time() - t0) / 300 * 1e3:.3f} ms/frame), {dg.wplan_entries} planned weight tensors")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("cfg", nargs="?", default="c1", help="without --bitstream: the bench.py recipe whose forward-only rate is measured")
+    ap.add_argument("--bitstream", action="store_true", help="time the bitstream decoder instead")
+    ap.add_argument("--frames", type=int, default=16)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--only", choices=["c1q", "c5", "pack"], default=None)
+    a = ap.parse_args()
+    import torch
+    assert torch.cuda.is_available(), "kdecode needs the GPU"
+    if not a.bitstream:
+        forward_rates(a.cfg)
+        return 0
+    for case in ([a.only] if a.only else ["c1q", "c5", "pack"]):
+        if case == "pack":
+            run_pack(a.rounds)
+        else:
+            run_case(case, a.frames, a.rounds)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
