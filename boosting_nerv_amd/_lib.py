@@ -118,6 +118,10 @@ class DequantChunk(C.Structure):
     _fields_ = [("it", DequantItem * CEM_MAX_TENSORS), ("n_items", C.c_int), ("_pad", C.c_int)]
 
 
+class YuvCoeffs(C.Structure):      # bnerv_yuv_coeffs: what yuvio.coefficients() computed in float64, rounded to fp32
+    _fields_ = [("m", C.c_float * 9), ("off", C.c_float * 3), ("scale", C.c_float * 3), ("maxcode", C.c_float)]
+
+
 # every symbol include/bnerv.h declares: name -> (restype, argtypes)
 _I, _Z, _V, _F = C.c_int, C.c_size_t, C.c_void_p, C.c_float
 SYMBOLS = {
@@ -167,6 +171,8 @@ SYMBOLS = {
     "bnerv_cem_scale_bwd": (_I, [_V, C.POINTER(CemChunkBwd), _V, _V, _V, _V, _Z]),
     "bnerv_dequant_table": (_I, [_V, C.POINTER(DequantChunk)]),
     "bnerv_frame_to_u8": (_I, [_V, _V, _V, _I, _I, _I]),
+    "bnerv_yuv420_to_rgb": (_I, [_V, _V, _I, _I, _Z, _I, _I, _I, _I, _V, _I, _I, C.POINTER(YuvCoeffs)]),
+    "bnerv_rgb_to_yuv420": (_I, [_V, _V, _I, _I, _I, _V, _I, _Z, C.POINTER(YuvCoeffs)]),
     "bnerv_dense_gemm_fwd": (_I, [_V, _V, _V, _V, _V, _V, _I, _I, _I, _I]),
     "bnerv_dense_gemm_bwd_ws_bytes": (_Z, [_I, _I, _I]),
     "bnerv_dense_gemm_bwd": (_I, [_V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _Z, _I, _I, _I, _I]),

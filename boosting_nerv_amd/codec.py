@@ -7,8 +7,11 @@ HNeRV_Boost's frame embeddings) with one table-driven launch per 48 tensors (ops
 uint8 packing kernel as a captured graph -- the frames evaluate() scored, bit for bit.
 
     python -m boosting_nerv_amd.codec decode FILE --out DIR [--format png|npy]
+    python -m boosting_nerv_amd.codec decode FILE --out clip.yuv --format yuv [--pix_fmt yuv420p|yuv420p10le] [--matrix bt709|bt601] [--range limited|full]
+    python -m boosting_nerv_amd.codec psnr FILE --ref source.yuv [--size WxH] [--pix_fmt ...] [--matrix ...] [--range ...]
     python -m boosting_nerv_amd.codec info FILE"""
 import argparse
+import builtins
 import json
 import os
 from types import SimpleNamespace
@@ -206,9 +209,15 @@ class Decoder:
         for frame in dec: ...    every frame as uint8, decoded ahead of the host: the device-to-host copy of frame i runs into one of two
                                  pinned buffers while frame i + 1 decodes; the host waits on an event per frame, never on the device
 
-    use_graph=False decodes with eager launches instead of the captured graph (same kernels, same bits)."""
+    use_graph=False decodes with eager launches instead of the captured graph (same kernels, same bits).
 
-    def __init__(self, path, device="cuda", use_graph=True):
+    pack="yuv420p" | "yuv420p10le" (with matrix="bt709" | "bt601", range="limited" | "full") puts the raw-video packing
+    kernel behind the forward instead of the uint8 one -- colour settings are decode-time choices, the file knows nothing of them:
+        dec.decode_yuv(i)        frame i in file layout: a 1-D array of 1.5 H W samples (uint8, or little-endian uint16), planes Y, U, V
+        dec.frames_yuv()         every frame in order, pipelined like frames_u8
+    decode_u8 / frames_u8 need the default pack="rgb8"."""
+
+    def __init__(self, path, device="cuda", use_graph=True, pack="rgb8", matrix="bt709", range="limited"):
         from . import ops
         from .engine import FrameDecodeGraph
         from .lib.entropy_model import ans_decode_gaussian
@@ -242,7 +251,7 @@ class Decoder:
             if len(bs.embeds) != self.n_frames or any(r.count != int(np.prod(bs.embed_shape)) for r in bs.embeds):
                 raise ValueError("bitstream: the embedding records do not match the header's frame count and embedding shape")
             self.embeds = torch.empty(self.n_frames, *bs.embed_shape, dtype=torch.float32, device=self.device)
-            targets += [self.embeds[i] for i in range(self.n_frames)]
+            targets += [self.embeds[i] for i in builtins.range(self.n_frames)]
         else:
             if bs.embeds:
                 raise ValueError(f"bitstream: embedding records in a {s['model']} stream")
@@ -262,8 +271,8 @@ class Decoder:
         coef_d = coef_h.to(self.device)
         n_rec = len(records)
         ops.dequant_table([sym_d[o:o + r.count] for r, o in zip(records, offs)], [t.reshape(-1) for t in targets],
-                          [coef_d[i:i + 1] for i in range(n_rec)],
-                          [None] * len(bs.tensors) + [coef_d[n_rec + i:n_rec + i + 1] for i in range(len(bs.embeds))])
+                          [coef_d[i:i + 1] for i in builtins.range(n_rec)],
+                          [None] * len(bs.tensors) + [coef_d[n_rec + i:n_rec + i + 1] for i in builtins.range(len(bs.embeds))])
 
         # raw fp32 section: the decoder's state_dict entries no record covers, in state_dict order
         torch.cuda.current_stream().synchronize()          # (the pinned symbols may go now)
@@ -274,12 +283,13 @@ class Decoder:
         for v, a in zip(rest, bs.raw):
             v.copy_(torch.from_numpy(a).reshape(v.shape))
 
-        self.norms = torch.tensor([float(i + 1) / self.n_frames for i in range(self.n_frames)], dtype=torch.float64, device=self.device)
+        self.norms = torch.tensor([float(i + 1) / self.n_frames for i in builtins.range(self.n_frames)], dtype=torch.float64, device=self.device)
         first_embed = self.embeds[0:1] if self.is_hnerv else None
-        self._loop = FrameDecodeGraph(model, self.norms[0:1], first_embed, self.norms[0:1], self.frame_hw, use_graph=use_graph)
-        H, W = self.frame_hw
-        self._pinned = [torch.empty(H, W, 3, dtype=torch.uint8, pin_memory=pin) for _ in range(2)]
-        self._events = [torch.cuda.Event() for _ in range(2)] if pin else None
+        self._loop = FrameDecodeGraph(model, self.norms[0:1], first_embed, self.norms[0:1], self.frame_hw, use_graph=use_graph,
+                                      pack=pack, matrix=matrix, range=range)
+        self.pack, self.coeffs = pack, self._loop.coeffs
+        self._pinned = [torch.empty(self._loop.u8.shape[1:], dtype=torch.uint8, pin_memory=pin) for _ in (0, 1)]
+        self._events = [torch.cuda.Event() for _ in builtins.range(2)] if pin else None
 
     def __len__(self):
         return self.n_frames
@@ -297,38 +307,114 @@ class Decoder:
         self._pinned[slot].copy_(u8[0], non_blocking=True)
         self._events[slot].record()
 
+    def _need_pack(self, yuv, what):
+        if (self.coeffs is not None) != yuv:
+            raise RuntimeError(f"Decoder.{what}: this decoder packs {self.pack} (pass pack={'a yuv420 format' if yuv else 'rgb8'!r} to Decoder)")
+
+    def _host_view(self, slot):
+        a = self._pinned[slot].numpy()
+        return a if self.coeffs is None else a.view(self.coeffs.dtype)
+
     def decode_u8(self, i):
+        self._need_pack(False, "decode_u8")
         self._to_host(self._launch(i)[1], 0)
         self._events[0].synchronize()
         return self._pinned[0].numpy().copy()
 
+    def decode_yuv(self, i):
+        self._need_pack(True, "decode_yuv")
+        self._to_host(self._launch(i)[1], 0)
+        self._events[0].synchronize()
+        return self._host_view(0).copy()
+
+    def split_planes(self, frame):
+        """A frame of decode_yuv / frames_yuv as its (y, u, v) planes (views)."""
+        H, W = self.frame_hw
+        hw, q = H * W, (H // 2) * (W // 2)
+        return frame[:hw].reshape(H, W), frame[hw:hw + q].reshape(H // 2, W // 2), frame[hw + q:].reshape(H // 2, W // 2)
+
     def frames_u8(self, copy=True):
         """Every frame in order as [H, W, 3] uint8.  copy=False yields views of the two pinned buffers: a view is valid until the
         generator is resumed."""
-        take = (lambda a: a.numpy().copy()) if copy else (lambda a: a.numpy())
+        self._need_pack(False, "frames_u8")
+        return self._frames(copy)
+
+    def frames_yuv(self, copy=True):
+        """Every frame in order in file layout (decode_yuv), two pinned buffers and one event per frame like frames_u8."""
+        self._need_pack(True, "frames_yuv")
+        return self._frames(copy)
+
+    def _frames(self, copy):
+        take = (lambda s: self._host_view(s).copy()) if copy else self._host_view
         for i in range(self.n_frames):
             self._to_host(self._launch(i)[1], i % 2)
             if i:
                 self._events[(i - 1) % 2].synchronize()
-                yield take(self._pinned[(i - 1) % 2])
+                yield take((i - 1) % 2)
         self._events[(self.n_frames - 1) % 2].synchronize()
-        yield take(self._pinned[(self.n_frames - 1) % 2])
+        yield take((self.n_frames - 1) % 2)
 
     def __iter__(self):
-        return self.frames_u8()
+        return self.frames_u8() if self.coeffs is None else self.frames_yuv()
 
 
-def main(argv=None):
+def _colour_flags(p, default_fmt):
+    p.add_argument("--pix_fmt", choices=("yuv420p", "yuv420p10le"), default=default_fmt,
+                   help="raw pixel format" + ("" if default_fmt else " of --ref (default: from its file name)"))
+    p.add_argument("--matrix", choices=("bt709", "bt601"), default="bt709")
+    p.add_argument("--range", choices=("limited", "full"), default="limited")
+
+
+def _psnr(a):
+    """`codec psnr`: every decoded frame, packed to the source's pixel format on the device, against the source's planes (cropped at even
+    offsets where the clip is smaller than the source).  The averages are means of per-frame dB, like evaluate()."""
+    from . import yuvio
+    w, h = yuvio.parse_size(a.size) if a.size else (None, None)
+    ref = yuvio.YuvFile(a.ref, w, h, a.pix_fmt)
+    dec = Decoder(a.file, "cuda", use_graph=not a.no_graph, pack=ref.pix_fmt, matrix=a.matrix, range=a.range)
+    H, W = dec.frame_hw
+    if len(ref) < len(dec):
+        raise ValueError(f"codec psnr: {a.ref} has {len(ref)} frames, the bitstream {len(dec)}")
+    top, left = (v & ~1 for v in yuvio.crop_offsets(ref.height, ref.width, H, W))
+    names = ("psnr_y", "psnr_u", "psnr_v", "psnr_yuv")
+    sums, sse = dict.fromkeys(names, 0.0), dict.fromkeys(("sse_y", "sse_u", "sse_v"), 0)
+    for i, frame in enumerate(dec.frames_yuv(copy=False)):
+        y, u, v = ref.planes(i)
+        src = (y[top:top + H, left:left + W], u[top // 2:(top + H) // 2, left // 2:(left + W) // 2], v[top // 2:(top + H) // 2, left // 2:(left + W) // 2])
+        one = yuvio.psnr_planes(dec.split_planes(frame), src, ref.depth)
+        for k in names:
+            sums[k] += one[k]
+        for k in sse:
+            sse[k] += one[k]
+    result = {k: sums[k] / len(dec) for k in names}
+    result.update(sse, frames=len(dec), pix_fmt=ref.pix_fmt, matrix=a.matrix, range=a.range)
+    print(" | ".join(f"{k.upper().replace('_', '-')} {result[k]:.4f} dB" for k in names) + f" | {len(dec)} frames of {H}x{W}, {ref.pix_fmt}")
+    print(json.dumps(result))
+    return result
+
+
+def build_parser():
     p = argparse.ArgumentParser(prog="python -m boosting_nerv_amd.codec", description="decode or inspect a compression bitstream")
     sub = p.add_subparsers(dest="cmd", required=True)
     d = sub.add_parser("decode", help="decode every frame of FILE into --out")
     d.add_argument("file")
-    d.add_argument("--out", required=True, help="directory for frame_NNNN.png / .npy")
-    d.add_argument("--format", choices=("png", "npy"), default="png")
+    d.add_argument("--out", required=True, help="directory for frame_NNNN.png / .npy; with --format yuv the raw file to write")
+    d.add_argument("--format", choices=("png", "npy", "yuv"), default="png")
     d.add_argument("--no_graph", action="store_true", help="eager launches instead of the captured graph")
+    _colour_flags(d, "yuv420p")
+    q = sub.add_parser("psnr", help="decode FILE and score it against the raw 4:2:0 source --ref: PSNR-Y, -U, -V and the 6:1:1 PSNR-YUV")
+    q.add_argument("file")
+    q.add_argument("--ref", required=True, help="the source clip, raw planar YUV 4:2:0")
+    q.add_argument("--size", default=None, help="WxH of --ref (default: from a UVG-style file name)")
+    q.add_argument("--no_graph", action="store_true", help="eager launches instead of the captured graph")
+    _colour_flags(q, None)
     i = sub.add_parser("info", help="print the bit budget of FILE")
     i.add_argument("file")
-    a = p.parse_args(argv)
+    return p
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
     if a.cmd == "info":
         budget = bitstream.info(a.file)
         print(describe(budget))
@@ -336,6 +422,15 @@ def main(argv=None):
         return budget
     if not torch.cuda.is_available():
         raise RuntimeError("codec decode: no ROCm GPU visible -- the decoder path has no CPU fallback")
+    if a.cmd == "psnr":
+        return _psnr(a)
+    if a.format == "yuv":
+        from . import yuvio
+        dec = Decoder(a.file, "cuda", use_graph=not a.no_graph, pack=a.pix_fmt, matrix=a.matrix, range=a.range)
+        yuvio.write(a.out, dec.frames_yuv(copy=False), a.pix_fmt)
+        print(f"decoded {len(dec)} frames of {dec.frame_hw[0]}x{dec.frame_hw[1]} into {a.out} ({a.pix_fmt}, {a.matrix}, {a.range} range, "
+              f"{os.path.getsize(a.out)} bytes)")
+        return len(dec)
     os.makedirs(a.out, exist_ok=True)
     dec = Decoder(a.file, "cuda", use_graph=not a.no_graph)
     for k, frame in enumerate(dec.frames_u8(copy=False)):

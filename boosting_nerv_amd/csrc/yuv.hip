@@ -1,0 +1,256 @@
+// yuv.hip -- raw planar YUV 4:2:0 <-> planar fp32 RGB (boosting_nerv_amd/yuvio.py is the host side and the float64 restatement).
+//
+// bnerv_yuv420_to_rgb: B frames of a raw clip as they lie in the file (plane Y [H, W], U [H/2, W/2], V [H/2, W/2]; 1 or 2 bytes per sample) ->
+// [B, 3, ch, cw] fp32 in [0, 1], the centre crop fused in.  Chroma is up-sampled for MPEG-2 "left" siting on the INTEGER sample values (weights
+// 3/4, 1/4 down the rows, 1/2, 1/2 along them: exact in fp32 for codes up to 1023), in source coordinates, so an odd crop offset changes nothing.
+// bnerv_rgb_to_yuv420: the inverse for even H and W -- [1 2 1] / 4 along the rows at even x, the mean of the two rows, floor(offset + scale * v + 0.5).
+//
+// Both are pure streams without LDS.  A thread owns 4 consecutive pixels of a luma row PAIR.  The fp32 side carries 12 of the 13.5 .. 15 bytes a
+// pixel moves, so the strip is sized for it: one 16-byte access per row and channel, lane-contiguous (a wave moves 1 KiB per instruction).  The
+// sample side of such a strip is 4 or 8 bytes of luma and 2 or 4 bytes of each chroma row, moved as one access each; a 16-sample strip would make
+// the luma access 16 bytes and put the fp32 accesses of neighbouring lanes 64 bytes apart.  Of the load's row pair: luma rows 2p + 1 and 2p + 2
+// interpolate between the SAME chroma rows p and p + 1 (weights 3/4, 1/4 and 1/4, 3/4), so a thread reads each chroma sample once for two output
+// rows.  Every access checks its own address: a pointer, width, stride or crop offset that breaks the alignment of an access sends that access
+// (not the launch) to the element-by-element form.
+//
+// The kernels know nothing of standards: matrix, offsets and scales arrive as one struct of fp32 values computed by the host in float64.
+#include "common.h"
+#include <stdint.h>
+
+namespace {
+
+constexpr int STRIP = 4, THREADS = 256;
+
+template <typename T> struct Pack;                                   // the unsigned word that holds 2 / 4 samples
+template <> struct Pack<unsigned char> { typedef uint16_t two; typedef uint32_t four; };
+template <> struct Pack<unsigned short> { typedef uint32_t two; typedef uint2 four; };
+
+__device__ __forceinline__ void unpack4(uint32_t w, float* v) {
+    v[0] = (float)(w & 0xffu); v[1] = (float)((w >> 8) & 0xffu); v[2] = (float)((w >> 16) & 0xffu); v[3] = (float)(w >> 24);
+}
+__device__ __forceinline__ void unpack4(uint2 w, float* v) {
+    v[0] = (float)(w.x & 0xffffu); v[1] = (float)(w.x >> 16); v[2] = (float)(w.y & 0xffffu); v[3] = (float)(w.y >> 16);
+}
+__device__ __forceinline__ void unpack2(uint16_t w, float* v) { v[0] = (float)(w & 0xffu); v[1] = (float)(w >> 8); }
+__device__ __forceinline__ void unpack2(uint32_t w, float* v) { v[0] = (float)(w & 0xffffu); v[1] = (float)(w >> 16); }
+
+// n <= 4 samples row[i0 .. i0 + n): one access when the strip is whole and its address allows, sample by sample otherwise (the rest: 0)
+template <typename T>
+__device__ __forceinline__ void load_luma(const T* __restrict__ row, const int i0, const int n, float* v) {
+    typedef typename Pack<T>::four W4;
+    const T* p = row + i0;
+    if (n == STRIP && (reinterpret_cast<uintptr_t>(p) & (sizeof(W4) - 1)) == 0) {
+        unpack4(*reinterpret_cast<const W4*>(p), v);
+    } else {
+#pragma unroll
+        for (int k = 0; k < STRIP; ++k) v[k] = k < n ? (float)p[k] : 0.0f;
+    }
+}
+
+// chroma samples row[min(c0 + i, last)], i = 0, 1, 2
+template <typename T>
+__device__ __forceinline__ void load_chroma3(const T* __restrict__ row, const int c0, const int last, float* v) {
+    typedef typename Pack<T>::two W2;
+    const T* p = row + c0;
+    if (c0 + 1 <= last && (reinterpret_cast<uintptr_t>(p) & (sizeof(W2) - 1)) == 0) {
+        unpack2(*reinterpret_cast<const W2*>(p), v);
+    } else {
+        v[0] = (float)p[0];
+        v[1] = (float)row[min(c0 + 1, last)];
+    }
+    v[2] = (float)row[min(c0 + 2, last)];
+}
+
+__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }      // (NaN -> 0)
+
+// grid = (blocks over row pairs x strips, B).  PAR: the parity of every strip's first SOURCE column (left & 1; strips start at multiples of 4)
+template <typename T, int PAR>
+__global__ __launch_bounds__(THREADS) void yuv420_to_rgb_kernel(const unsigned char* __restrict__ src, const size_t frame_stride, const int H, const int W,
+                                                                const int top, const int left, float* __restrict__ out, const int ch, const int cw,
+                                                                const int p0, const int npairs, const int nstrips, const bnerv_yuv_coeffs k) {
+    const int t = (int)blockIdx.x * THREADS + (int)threadIdx.x;
+    if (t >= npairs * nstrips) return;
+    const int pr = t / nstrips, st = t - pr * nstrips;
+    const int p = p0 + pr;                                             // luma rows 2p + 1 and 2p + 2, chroma rows p and p + 1 (clamped)
+    const int ox0 = st * STRIP, x0 = left + ox0, n = min(STRIP, cw - ox0);
+    const int H2 = H >> 1, W2 = W >> 1;
+    const T* Y = reinterpret_cast<const T*>(src + (size_t)blockIdx.y * frame_stride);
+    const T* U = Y + (size_t)H * W;
+    const T* V = U + (size_t)H2 * W2;
+    const int ca = max(p, 0), cb = min(p + 1, H2 - 1), c0 = x0 >> 1;
+    float ua[3], ub[3], va[3], vb[3];
+    load_chroma3(U + (size_t)ca * W2, c0, W2 - 1, ua);
+    load_chroma3(U + (size_t)cb * W2, c0, W2 - 1, ub);
+    load_chroma3(V + (size_t)ca * W2, c0, W2 - 1, va);
+    load_chroma3(V + (size_t)cb * W2, c0, W2 - 1, vb);
+    float* const frame = out + (size_t)blockIdx.y * 3 * ch * cw;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int y = 2 * p + 1 + r;
+        if (y < top || y >= top + ch) continue;
+        const float wa = r == 0 ? 0.75f : 0.25f, wb = 1.0f - wa;
+        float cu[3], cv[3], ys[STRIP];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { cu[i] = wa * ua[i] + wb * ub[i]; cv[i] = wa * va[i] + wb * vb[i]; }
+        load_luma(Y + (size_t)y * W, x0, n, ys);
+        float rgb[3][STRIP];
+#pragma unroll
+        for (int q = 0; q < STRIP; ++q) {
+            const int i = (PAR + q) >> 1;
+            const bool odd = (PAR + q) & 1;
+            const float u = odd ? 0.5f * (cu[i] + cu[i + 1 > 2 ? 2 : i + 1]) : cu[i];
+            const float v = odd ? 0.5f * (cv[i] + cv[i + 1 > 2 ? 2 : i + 1]) : cv[i];
+            const float yn = (ys[q] - k.off[0]) * k.scale[0], cbn = (u - k.off[1]) * k.scale[1], crn = (v - k.off[2]) * k.scale[2];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) rgb[c][q] = clamp01(k.m[3 * c] * yn + k.m[3 * c + 1] * cbn + k.m[3 * c + 2] * crn);
+        }
+        const size_t o = (size_t)(y - top) * cw + ox0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float* d = frame + (size_t)c * ch * cw + o;
+            if (n == STRIP && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
+                *reinterpret_cast<f32x4*>(d) = f32x4{rgb[c][0], rgb[c][1], rgb[c][2], rgb[c][3]};
+            } else {
+#pragma unroll
+                for (int q = 0; q < STRIP; ++q)
+                    if (q < n) d[q] = rgb[c][q];
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ unsigned to_code(float v, float off, float scale, float top) {
+    const float c = floorf(off + scale * v + 0.5f);
+    return (unsigned)(int)fminf(fmaxf(c, 0.0f), top);
+}
+
+template <typename T>
+__device__ __forceinline__ void store_samples(T* __restrict__ d, const unsigned* c, const int n, const int whole);
+template <>
+__device__ __forceinline__ void store_samples<unsigned char>(unsigned char* __restrict__ d, const unsigned* c, const int n, const int whole) {
+    if (n == whole && whole == 4 && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
+        *reinterpret_cast<uint32_t*>(d) = c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24);
+    } else if (n == whole && whole == 2 && (reinterpret_cast<uintptr_t>(d) & 1) == 0) {
+        *reinterpret_cast<uint16_t*>(d) = (uint16_t)(c[0] | (c[1] << 8));
+    } else {
+        for (int q = 0; q < n; ++q) d[q] = (unsigned char)c[q];
+    }
+}
+template <>
+__device__ __forceinline__ void store_samples<unsigned short>(unsigned short* __restrict__ d, const unsigned* c, const int n, const int whole) {
+    if (n == whole && whole == 4 && (reinterpret_cast<uintptr_t>(d) & 7) == 0) {
+        *reinterpret_cast<uint2*>(d) = make_uint2(c[0] | (c[1] << 16), c[2] | (c[3] << 16));
+    } else if (n == whole && whole == 2 && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
+        *reinterpret_cast<uint32_t*>(d) = c[0] | (c[1] << 16);
+    } else {
+        for (int q = 0; q < n; ++q) d[q] = (unsigned short)c[q];
+    }
+}
+
+// grid = (blocks over row pairs x strips, B).  A thread: luma rows 2j, 2j + 1, columns x0 .. x0 + n (n = 4, or 2 at the end of a row whose width
+// is not a multiple of 4) plus the column left of the strip (clamped), which the [1 2 1] filter of the strip's first chroma sample reads.
+template <typename T>
+__global__ __launch_bounds__(THREADS) void rgb_to_yuv420_kernel(const float* __restrict__ x, const int H, const int W, unsigned char* __restrict__ out,
+                                                                const size_t frame_stride, const int nstrips, const bnerv_yuv_coeffs k) {
+    const int H2 = H >> 1, W2 = W >> 1;
+    const int t = (int)blockIdx.x * THREADS + (int)threadIdx.x;
+    if (t >= H2 * nstrips) return;
+    const int j = t / nstrips, st = t - j * nstrips;
+    const int x0 = st * STRIP, n = min(STRIP, W - x0), xl = max(x0 - 1, 0);
+    const size_t HW = (size_t)H * W;
+    const float* const frame = x + (size_t)blockIdx.y * 3 * HW;
+    T* const Yp = reinterpret_cast<T*>(out + (size_t)blockIdx.y * frame_stride);
+    T* const Up = Yp + HW;
+    T* const Vp = Up + (size_t)H2 * W2;
+    float cbs[2] = {0.0f, 0.0f}, crs[2] = {0.0f, 0.0f};
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const size_t o = (size_t)(2 * j + r) * W;
+        float c[3][STRIP + 1];                                         // [channel][0: the column left of the strip, 1 + q: column x0 + q]
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float* s = frame + (size_t)a * HW + o;
+            c[a][0] = clamp01(s[xl]);
+            if (n == STRIP && (reinterpret_cast<uintptr_t>(s + x0) & 15) == 0) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(s + x0);
+#pragma unroll
+                for (int q = 0; q < STRIP; ++q) c[a][1 + q] = clamp01(v[q]);
+            } else {
+#pragma unroll
+                for (int q = 0; q < STRIP; ++q) c[a][1 + q] = q < n ? clamp01(s[x0 + q]) : 0.0f;
+            }
+        }
+        float cbp[STRIP + 1], crp[STRIP + 1];
+        unsigned yc[STRIP];
+#pragma unroll
+        for (int q = 0; q <= STRIP; ++q) {
+            const float R = c[0][q], G = c[1][q], B = c[2][q];
+            cbp[q] = k.m[3] * R + k.m[4] * G + k.m[5] * B;
+            crp[q] = k.m[6] * R + k.m[7] * G + k.m[8] * B;
+            if (q > 0) yc[q - 1] = to_code(k.m[0] * R + k.m[1] * G + k.m[2] * B, k.off[0], k.scale[0], k.maxcode);
+        }
+        cbs[0] += 0.25f * (cbp[0] + 2.0f * cbp[1] + cbp[2]); cbs[1] += 0.25f * (cbp[2] + 2.0f * cbp[3] + cbp[4]);
+        crs[0] += 0.25f * (crp[0] + 2.0f * crp[1] + crp[2]); crs[1] += 0.25f * (crp[2] + 2.0f * crp[3] + crp[4]);
+        store_samples<T>(Yp + o + x0, yc, n, STRIP);
+    }
+    const unsigned uc[2] = {to_code(0.5f * cbs[0], k.off[1], k.scale[1], k.maxcode), to_code(0.5f * cbs[1], k.off[1], k.scale[1], k.maxcode)};
+    const unsigned vc[2] = {to_code(0.5f * crs[0], k.off[2], k.scale[2], k.maxcode), to_code(0.5f * crs[1], k.off[2], k.scale[2], k.maxcode)};
+    const size_t oc = (size_t)j * W2 + (x0 >> 1);
+    store_samples<T>(Up + oc, uc, n >> 1, STRIP / 2);
+    store_samples<T>(Vp + oc, vc, n >> 1, STRIP / 2);
+}
+
+// what both entry points ask of the raw side
+int check_raw(const char* what, const void* raw, int bytes_per_sample, int B, size_t frame_stride_bytes, int H, int W) {
+    BNERV_REQUIRE(bytes_per_sample == 1 || bytes_per_sample == 2, "%s: bytes_per_sample=%d (1: yuv420p, 2: yuv420p10le)", what, bytes_per_sample);
+    BNERV_REQUIRE(B > 0 && B <= 65535, "%s: B=%d", what, B);
+    BNERV_REQUIRE(H > 0 && W > 0 && (size_t)H * W <= 0x7fffffffu / 4, "%s: H=%d W=%d", what, H, W);
+    BNERV_REQUIRE(H % 2 == 0 && W % 2 == 0, "%s: 4:2:0 needs even dimensions, got %dx%d", what, W, H);
+    const size_t frame = (size_t)H * W * 3 / 2 * bytes_per_sample;
+    BNERV_REQUIRE(frame_stride_bytes >= frame, "%s: frame_stride_bytes=%zu is smaller than a frame (%zu bytes)", what, frame_stride_bytes, frame);
+    BNERV_REQUIRE(bytes_per_sample == 1 || ((reinterpret_cast<uintptr_t>(raw) | frame_stride_bytes) & 1) == 0,
+                  "%s: 16-bit samples at an odd address or frame stride", what);
+    return BNERV_OK;
+}
+
+}  // namespace
+
+extern "C" int bnerv_yuv420_to_rgb(void* stream, const void* src, int bytes_per_sample, int B, size_t frame_stride_bytes, int src_h, int src_w, int top,
+                                   int left, float* out, int ch, int cw, const bnerv_yuv_coeffs* coeffs) {
+    BNERV_REQUIRE(src && out && coeffs, "yuv420_to_rgb: null args");
+    if (const int rc = check_raw("yuv420_to_rgb", src, bytes_per_sample, B, frame_stride_bytes, src_h, src_w)) return rc;
+    BNERV_REQUIRE(ch > 0 && cw > 0 && top >= 0 && left >= 0 && top <= src_h - ch && left <= src_w - cw,
+                  "yuv420_to_rgb: the %dx%d crop at (top %d, left %d) leaves the %dx%d frame", cw, ch, top, left, src_w, src_h);
+    BNERV_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "yuv420_to_rgb: out is not 4-byte aligned");
+    const int p0 = ((top + 1) >> 1) - 1, npairs = ((top + ch) >> 1) - 1 - p0 + 1, nstrips = cdiv(cw, STRIP);
+    const dim3 grid(cdiv(npairs * nstrips, THREADS), B), block(THREADS);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const unsigned char* raw = static_cast<const unsigned char*>(src);
+#define BNERV_YUV_LOAD(T, PAR) \
+    hipLaunchKernelGGL((yuv420_to_rgb_kernel<T, PAR>), grid, block, 0, s, raw, frame_stride_bytes, src_h, src_w, top, left, out, ch, cw, p0, npairs, nstrips, *coeffs)
+    if (bytes_per_sample == 1) {
+        if (left & 1) BNERV_YUV_LOAD(unsigned char, 1); else BNERV_YUV_LOAD(unsigned char, 0);
+    } else {
+        if (left & 1) BNERV_YUV_LOAD(unsigned short, 1); else BNERV_YUV_LOAD(unsigned short, 0);
+    }
+#undef BNERV_YUV_LOAD
+    BNERV_LAUNCH_CHECK("yuv420_to_rgb");
+    return BNERV_OK;
+}
+
+extern "C" int bnerv_rgb_to_yuv420(void* stream, const float* x, int B, int H, int W, void* out, int bytes_per_sample, size_t frame_stride_bytes,
+                                   const bnerv_yuv_coeffs* coeffs) {
+    BNERV_REQUIRE(x && out && coeffs, "rgb_to_yuv420: null args");
+    if (const int rc = check_raw("rgb_to_yuv420", out, bytes_per_sample, B, frame_stride_bytes, H, W)) return rc;
+    BNERV_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0, "rgb_to_yuv420: x is not 4-byte aligned");
+    const int nstrips = cdiv(W, STRIP);
+    const dim3 grid(cdiv((H / 2) * nstrips, THREADS), B), block(THREADS);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    unsigned char* raw = static_cast<unsigned char*>(out);
+    if (bytes_per_sample == 1)
+        hipLaunchKernelGGL(rgb_to_yuv420_kernel<unsigned char>, grid, block, 0, s, x, H, W, raw, frame_stride_bytes, nstrips, *coeffs);
+    else
+        hipLaunchKernelGGL(rgb_to_yuv420_kernel<unsigned short>, grid, block, 0, s, x, H, W, raw, frame_stride_bytes, nstrips, *coeffs);
+    BNERV_LAUNCH_CHECK("rgb_to_yuv420");
+    return BNERV_OK;
+}

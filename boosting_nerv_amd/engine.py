@@ -456,16 +456,20 @@ class DecodeGraph:
 
 
 class _ForwardAndPack:
-    """What FrameDecodeGraph captures: the model's forward followed by the packing kernel into a static uint8 frame."""
+    """What FrameDecodeGraph captures: the model's forward followed by the packing kernel into a static frame buffer -- uint8 RGB
+    (coeffs None) or raw YUV 4:2:0 in file layout (coeffs: yuvio.coefficients of the pixel format)."""
     time_decode = False
 
-    def __init__(self, model, u8):
-        self.model, self.u8 = model, u8
+    def __init__(self, model, packed, coeffs=None):
+        self.model, self.packed, self.coeffs = model, packed, coeffs
 
     def __call__(self, cur_input, embed, norm_idx=None):
         from . import ops
         out = self.model(cur_input, embed, norm_idx=norm_idx)[0]
-        ops.frame_to_u8(out, out=self.u8)
+        if self.coeffs is None:
+            ops.frame_to_u8(out, out=self.packed)
+        else:
+            ops.rgb_to_yuv420(out, self.coeffs, out=self.packed)
         return (out,)
 
 
@@ -473,12 +477,25 @@ class FrameDecodeGraph:
     """The frame loop of a bitstream decoder (codec.Decoder): DecodeGraph's capture -- same warm-up, same weight-fragment plan -- of the
     forward PLUS ops.frame_to_u8, replayed WITHOUT a host synchronisation.  `launch(cur_input, embed, norm_idx)` refreshes the static inputs
     with device-side copies and replays on the current stream; `out` ([B, 3, H, W] fp32) and `u8` ([B, H, W, 3] uint8) are the static results,
-    valid in stream order until the next launch.  use_graph=False runs the same two steps eagerly into the same buffers."""
+    valid in stream order until the next launch.  use_graph=False runs the same two steps eagerly into the same buffers.
+    pack selects the packing node behind the forward: "rgb8" (ops.frame_to_u8), or "yuv420p" / "yuv420p10le" (ops.rgb_to_yuv420 with the
+    given matrix and range; `u8` is then [B, frame bytes] uint8, every frame in file layout: planes Y, U, V)."""
 
-    def __init__(self, model, cur_input, embed, norm_idx, frame_hw, use_graph=True):
-        self.use_graph = use_graph
-        self.u8 = torch.empty(norm_idx.shape[0], frame_hw[0], frame_hw[1], 3, dtype=torch.uint8, device=norm_idx.device)
-        self._body = _ForwardAndPack(model, self.u8)
+    def __init__(self, model, cur_input, embed, norm_idx, frame_hw, use_graph=True, pack="rgb8", matrix="bt709", range="limited"):
+        self.use_graph, self.pack = use_graph, pack
+        B, (H, W) = norm_idx.shape[0], frame_hw
+        if pack == "rgb8":
+            self.coeffs = None
+            self.u8 = torch.empty(B, H, W, 3, dtype=torch.uint8, device=norm_idx.device)
+        else:
+            from . import yuvio
+            if pack not in yuvio.PIX_FMTS:
+                raise ValueError(f"FrameDecodeGraph: pack={pack!r} (rgb8, {', '.join(yuvio.PIX_FMTS)})")
+            if H % 2 or W % 2:
+                raise ValueError(f"FrameDecodeGraph: 4:2:0 needs even dimensions, the frames are {H}x{W}")
+            self.coeffs = yuvio.coefficients(matrix, range, yuvio.PIX_FMTS[pack])
+            self.u8 = torch.empty(B, yuvio.frame_samples(H, W) * self.coeffs.bytes_per_sample, dtype=torch.uint8, device=norm_idx.device)
+        self._body = _ForwardAndPack(model, self.u8, self.coeffs)
         td = getattr(model, "time_decode", False)
         model.time_decode = False
         try:

@@ -32,12 +32,22 @@ def _center_crop(img, ch, cw):
 class VideoDataSet(Dataset):
     """Sorted directory of frames (PNG/JPG), centre-cropped to --crop_list, ToTensor, norm_idx = (idx+1)/N  (:19-47).
     ``--data_path synthetic:bunny | synthetic:uvg | synthetic:NxHxW`` selects the in-repo deterministic generator instead
-    (no dataset ships with the reference)."""
+    (no dataset ships with the reference).  A ``--data_path`` ending in ``.yuv`` is a raw planar YUV 4:2:0 clip (yuvio.YuvFile; --yuv_size,
+    --yuv_fmt, --yuv_matrix, --yuv_range): same samples, same crop, decoded by the float64 restatement here and by the conversion kernel
+    when the clip is made resident (to_device)."""
 
     def __init__(self, args):
         self.crop_h, self.crop_w = [int(x) for x in args.crop_list.split("_")[:2]]
         self.synthetic = None
-        if str(args.data_path).startswith("synthetic:"):
+        self.yuv = None
+        if str(args.data_path).lower().endswith(".yuv"):
+            from . import yuvio
+            w, h = yuvio.parse_size(args.yuv_size) if getattr(args, "yuv_size", None) else (None, None)
+            self.yuv = yuvio.YuvFile(args.data_path, w, h, getattr(args, "yuv_fmt", None))
+            self.yuv_matrix, self.yuv_range = getattr(args, "yuv_matrix", "bt709"), getattr(args, "yuv_range", "limited")
+            self.yuv.crop_window((self.crop_h, self.crop_w))              # (raises for a clip smaller than --crop_list)
+            self.samples = list(range(len(self.yuv)))
+        elif str(args.data_path).startswith("synthetic:"):
             n, h, w = synth.parse_spec(args.data_path)
             if (h, w) != (self.crop_h, self.crop_w):
                 h, w = self.crop_h, self.crop_w
@@ -51,7 +61,7 @@ class VideoDataSet(Dataset):
         self.crop = True
         self.final_size = self.crop_h * self.crop_w
         self.embed_inter = getattr(args, "embed_inter", False) and getattr(args, "interpolation", False)
-        if self.synthetic is None:
+        if self.synthetic is None and self.yuv is None:
             from PIL import Image
             first = Image.open(self.samples[0]).convert("RGB")
             if not (first.height >= self.crop_h and first.width >= self.crop_w):
@@ -65,8 +75,17 @@ class VideoDataSet(Dataset):
             if idx not in self._cache:
                 self._cache[idx] = self.synthetic.frame(idx)
             return self._cache[idx]
+        if self.yuv is not None:
+            return torch.from_numpy(self.yuv.frame_rgb(self.samples[idx], (self.crop_h, self.crop_w), self.yuv_matrix, self.yuv_range))
         from PIL import Image
         return _to_tensor(_center_crop(Image.open(self.samples[idx]).convert("RGB"), self.crop_h, self.crop_w))
+
+    def to_device(self, device):
+        """The clip as a resident [N, 3, H, W] fp32 device tensor: a raw YUV clip goes up as it lies in the file and is converted there
+        (YuvFile.to_device, no host fp32 frames); every other source is stacked on the host and uploaded."""
+        if self.yuv is not None:
+            return self.yuv.to_device(device, crop=(self.crop_h, self.crop_w), matrix=self.yuv_matrix, range=self.yuv_range, count=len(self.samples))
+        return torch.stack([self[i]['img'] for i in range(len(self))]).to(device)
 
     def __getitem__(self, idx):
         img = self._load(idx)

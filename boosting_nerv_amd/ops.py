@@ -956,6 +956,54 @@ def frame_to_u8(x, out=None):
     return out
 
 
+def _raw_bytes(t, name):
+    """A contiguous device tensor of raw samples (uint8, or any dtype of file bytes) as its byte count."""
+    t = L.require_device(t, name)
+    if not t.is_contiguous() or t.numel() == 0:
+        raise ValueError(f"{name}: need a non-empty contiguous device tensor of raw samples")
+    return t.numel() * t.element_size()
+
+
+def yuv420_to_rgb(src, coeffs, B, src_h, src_w, crop=None, frame_stride_bytes=None, out=None):
+    """B raw 4:2:0 frames as they lie in a file (src: contiguous device bytes; frame b at byte b * frame_stride_bytes, default: packed) ->
+    [B, 3, ch, cw] fp32 RGB in [0, 1] in one launch (DESIGN section 25).  coeffs: yuvio.coefficients(matrix, range, depth);
+    crop = (top, left, ch, cw) in source coordinates, any parity (None: the whole frame)."""
+    nbytes = _raw_bytes(src, "yuv420_to_rgb: src")
+    bps = coeffs.bytes_per_sample
+    frame = src_h * src_w * 3 // 2 * bps
+    stride = frame if frame_stride_bytes is None else int(frame_stride_bytes)
+    top, left, ch, cw = (0, 0, src_h, src_w) if crop is None else (int(v) for v in crop)
+    if B < 1 or stride < frame or (B - 1) * stride + frame > nbytes:
+        raise ValueError(f"yuv420_to_rgb: {B} frames of {frame} bytes at stride {stride} do not fit the {nbytes} bytes of src")
+    if out is None:
+        out = torch.empty(B, 3, max(ch, 0), max(cw, 0), dtype=torch.float32, device=src.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, 3, ch, cw) or not out.is_contiguous() or out.device != src.device:
+        raise ValueError(f"yuv420_to_rgb: out must be a contiguous fp32 [{B}, 3, {ch}, {cw}] tensor on {src.device}")
+    c = coeffs.load_struct()
+    L.check(L.load().bnerv_yuv420_to_rgb(L.stream(), L.ptr(src), bps, B, stride, src_h, src_w, top, left, L.ptr(out), ch, cw, C.byref(c)),
+            "bnerv_yuv420_to_rgb")
+    return out
+
+
+def rgb_to_yuv420(x, coeffs, out=None, frame_stride_bytes=None):
+    """[B, 3, H, W] fp32 (H, W even; values clamped to [0, 1]) -> B raw 4:2:0 frames in file layout, a uint8 [B, frame_stride_bytes] tensor
+    (default stride: one frame, 1.5 H W samples of coeffs.bytes_per_sample bytes) in one launch.  coeffs: yuvio.coefficients(...)."""
+    x = L.require_device(x.detach(), "x")
+    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError(f"rgb_to_yuv420: need a non-empty contiguous fp32 [B, 3, H, W] tensor, got {x.dtype} {tuple(x.shape)}")
+    B, _, H, W = x.shape
+    bps = coeffs.bytes_per_sample
+    frame = H * W * 3 // 2 * bps
+    stride = frame if frame_stride_bytes is None else int(frame_stride_bytes)
+    if out is None:
+        out = torch.empty(B, max(stride, frame), dtype=torch.uint8, device=x.device)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.device != x.device or out.numel() < (B - 1) * stride + frame:
+        raise ValueError(f"rgb_to_yuv420: out must be a contiguous uint8 tensor of at least {(B - 1) * stride + frame} bytes on {x.device}")
+    c = coeffs.store_struct()
+    L.check(L.load().bnerv_rgb_to_yuv420(L.stream(), L.ptr(x), B, H, W, L.ptr(out), bps, stride, C.byref(c)), "bnerv_rgb_to_yuv420")
+    return out
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # depthwise conv of the ConvNeXt encoder block (first kernels of row N3)
 # ----------------------------------------------------------------------------------------------------------------------

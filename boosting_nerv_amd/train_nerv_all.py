@@ -110,6 +110,11 @@ def build_parser():
     # MI355X-side switches (not in the reference)
     parser.add_argument('--no_graph', action='store_true', help='disable hipGraph replay of the train step')
     parser.add_argument('--host_frames', action='store_true', help='stream frames through the DataLoader instead of keeping them in HBM')
+    # a --data_path ending in .yuv is a raw planar YUV 4:2:0 clip (yuvio.py)
+    parser.add_argument('--yuv_size', type=str, default=None, help='WxH of a raw .yuv clip (default: the _WxH_ of a UVG-style file name)')
+    parser.add_argument('--yuv_fmt', type=str, default=None, choices=['yuv420p', 'yuv420p10le'], help='pixel format of a raw .yuv clip (default: 8bit / 10bit in its name)')
+    parser.add_argument('--yuv_matrix', type=str, default='bt709', choices=['bt709', 'bt601'], help='colour matrix of a raw .yuv clip')
+    parser.add_argument('--yuv_range', type=str, default='limited', choices=['limited', 'full'], help='sample range of a raw .yuv clip')
     return parser
 
 
@@ -285,7 +290,7 @@ def train(local_rank, args):
     if args.start_epoch < 0:
         args.start_epoch = max(ckpt['epoch'] if ckpt is not None else 0, 0)
 
-    args._frames_dev = torch.stack([full_dataset[i]['img'] for i in range(len(full_dataset))]).to(device) if resident else None
+    args._frames_dev = full_dataset.to_device(device) if resident else None
 
     if args.eval_only:
         values, hw = evaluate(model, full_loader, local_rank, args, args.dump_vis, huffman_coding=True)

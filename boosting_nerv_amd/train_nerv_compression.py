@@ -154,7 +154,7 @@ def train(local_rank, args):
     if args.start_epoch < 0:
         args.start_epoch = max(ckpt['epoch'] if (ckpt is not None and not args.not_resume) else 0, 0)
 
-    args._frames_dev = torch.stack([full_dataset[i]['img'] for i in range(len(full_dataset))]).to(device) if resident else None
+    args._frames_dev = full_dataset.to_device(device) if resident else None
     takes_image = 'pe' not in args.embed or "HNeRV_Boost" in args.model
 
     if args.eval_only:

@@ -357,6 +357,25 @@ int bnerv_dequant_table(void* stream, const bnerv_dequant_chunk* chunk);
 int bnerv_frame_to_u8(void* stream, const float* x, unsigned char* out, int B, int H, int W);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Raw planar YUV 4:2:0 video in and out (additive to ABI 9; csrc/yuv.hip, boosting_nerv_amd/yuvio.py; definitions: DESIGN section 25).
+ * A raw frame is plane Y [H, W], then U [H/2, W/2], then V [H/2, W/2], bytes_per_sample 1 (yuv420p) or 2 (yuv420p10le, little endian);
+ * frame b starts frame_stride_bytes * b bytes behind the pointer.  The kernels know no standard: bnerv_yuv_coeffs carries what the host
+ * computed in float64 --
+ *   load:   n_p = (sample_p - off[p]) * scale[p] for p = Y, U, V;  rgb[c] = clamp(m[3c] n_Y + m[3c+1] n_U + m[3c+2] n_V, 0, 1)
+ *   store:  v_p = m[3p] R + m[3p+1] G + m[3p+2] B from RGB clamped to [0, 1];  code_p = clamp(floor(off[p] + scale[p] * v_p + 0.5), 0, maxcode)
+ *           (chroma v_p filtered [1 2 1] / 4 along the row at even x with the left edge clamped, then averaged over the row pair)
+ *   bnerv_yuv420_to_rgb:  src -> out [B, 3, ch, cw] fp32, the crop window at (top, left) of the src_h x src_w frame (any parity); chroma
+ *       up-sampled for MPEG-2 "left" siting on the sample values, in source coordinates.
+ *   bnerv_rgb_to_yuv420:  x [B, 3, H, W] fp32 -> out in file layout.
+ * Both validate before any launch (null pointers, odd dimensions, bytes_per_sample, a crop that leaves the frame, a stride smaller than a
+ * frame); fp32 operands need 4-byte, 16-bit samples 2-byte alignment, every wider access is chosen per address. */
+typedef struct { float m[9]; float off[3]; float scale[3]; float maxcode; } bnerv_yuv_coeffs;
+int bnerv_yuv420_to_rgb(void* stream, const void* src, int bytes_per_sample, int B, size_t frame_stride_bytes, int src_h, int src_w, int top,
+                        int left, float* out, int ch, int cw, const bnerv_yuv_coeffs* coeffs);
+int bnerv_rgb_to_yuv420(void* stream, const float* x, int B, int H, int W, void* out, int bytes_per_sample, size_t frame_stride_bytes,
+                        const bnerv_yuv_coeffs* coeffs);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * GEMM-shaped dense work on v_mfma_f32_16x16x4_f32 (csrc/gemm.hip).
  *
  * Dense layers applied to many rows (B >= 16: the token MLPs of E-NeRV's transformer stem, NeRV_MLP at larger batches;
