@@ -118,6 +118,18 @@ class DequantChunk(C.Structure):
     _fields_ = [("it", DequantItem * CEM_MAX_TENSORS), ("n_items", C.c_int), ("_pad", C.c_int)]
 
 
+HUFF_RUN, HUFF_LEAVES, HUFF_LUT_BITS = 256, 257, 12      # BNERV_HUFF_RUN, BNERV_HUFF_LEAVES, BNERV_HUFF_LUT_BITS
+HUFF_F32, HUFF_F16 = 0, 1
+
+
+class HuffRun(C.Structure):        # bnerv_huff_run
+    _fields_ = [("start_bit", C.c_uint64), ("item", C.c_uint32), ("first", C.c_uint32)]
+
+
+class HuffItem(C.Structure):       # bnerv_huff_item
+    _fields_ = [("out", _fp), ("min", _fp), ("scale", _fp), ("dtype", C.c_int), ("n", C.c_uint32), ("red", C.c_uint32), ("inner", C.c_uint32)]
+
+
 class YuvCoeffs(C.Structure):      # bnerv_yuv_coeffs: what yuvio.coefficients() computed in float64, rounded to fp32
     _fields_ = [("m", C.c_float * 9), ("off", C.c_float * 3), ("scale", C.c_float * 3), ("maxcode", C.c_float)]
 
@@ -183,6 +195,9 @@ SYMBOLS = {
     "bnerv_ans_decode_gaussian": (_I, [_V, _Z, _Z, _I, _I, C.c_double, C.c_double, _V]),
     "bnerv_ans_encode_categorical": (C.c_long, [_V, _Z, _V, _I, _V, _Z]),
     "bnerv_ans_decode_categorical": (_I, [_V, _Z, _Z, _V, _I, _V]),
+    "bnerv_huff_encode": (C.c_long, [_V, _V, _I, _V, _I, _V, _Z, _V, _Z]),
+    "bnerv_huff_decode": (_I, [_V, _Z, _V, _Z, _V, _I, _V, _I, _V]),
+    "bnerv_huff_dequant": (_I, [_V, _V, _Z, _V, _Z, _V, _I, _V, _I, _V]),
     "bnerv_dwconv_fwd": (_I, [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I]),
     "bnerv_dwconv_wgrad_ws_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "bnerv_dwconv_wgrad": (_I, [_V, _V, _V, _V, _V, _Z, _I, _I, _I, _I, _I, _V]),

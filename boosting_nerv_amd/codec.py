@@ -9,7 +9,12 @@ uint8 packing kernel as a captured graph -- the frames evaluate() scored, bit fo
     python -m boosting_nerv_amd.codec decode FILE --out DIR [--format png|npy]
     python -m boosting_nerv_amd.codec decode FILE --out clip.yuv --format yuv [--pix_fmt yuv420p|yuv420p10le] [--matrix bt709|bt601] [--range limited|full]
     python -m boosting_nerv_amd.codec psnr FILE --ref source.yuv [--size WxH] [--pix_fmt ...] [--matrix ...] [--range ...]
-    python -m boosting_nerv_amd.codec info FILE"""
+    python -m boosting_nerv_amd.codec info FILE
+
+The regression path (train_nerv_all.py --bitstream) has a file of its own kind (qstream.py): encode_posthoc() writes the
+8-bit codes of evaluate()'s post-hoc quantised twin under the one Huffman code the log reports, and Decoder -- which tells the two kinds
+apart by their magic number -- uploads the coded bytes as they lie in the file and lets ONE kernel (ops.huff_dequant) Huffman-decode and
+de-quantise them straight into the parameter tensors.  Every command above works on both kinds."""
 import argparse
 import builtins
 import json
@@ -19,7 +24,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import bitstream
+from . import bitstream, qstream
 from .bitstream import Record
 
 # the settings the model constructors read (model_nerv.py, model_hnerv.py, model_enerv.py, model_blocks.py), resolved: fc_dim after the size
@@ -27,6 +32,7 @@ from .bitstream import Record
 SETTINGS_KEYS = ("model", "embed", "lfreq", "fc_hw", "fc_dim", "ch_t", "ks", "enc_blks", "enc_strds", "enc_dim", "dec_strds", "dec_blks", "reduce",
                  "lower_width", "conv_type", "norm", "act", "sft_block", "out_bias", "block_dim")
 MODELS = ("NeRV_Boost", "ENeRV_Boost", "HNeRV_Boost")
+POSTHOC_MODELS = MODELS + ("HNeRV",)      # what a qstream file (post-hoc quantisation, no quantisers in the model) can hold
 
 
 def _plain(v):
@@ -199,6 +205,101 @@ def describe(budget):
             f"+ raw fp32 {budget['raw']} ({budget['n_raw']} entries) + header {budget['header']}")
 
 
+def _grid_geometry(rec):
+    """(outer, red, inner, dtype flag) of a hnerv_utils.quant_tensor record: which elements share a (min, scale) pair."""
+    q, lo, step = rec["quant"], rec["min"], rec["scale"]
+    if lo.dtype != step.dtype or lo.dtype not in (torch.float32, torch.float16) or lo.numel() != step.numel():
+        raise NotImplementedError(f"codec.encode_posthoc: a (min, scale) grid of dtypes {lo.dtype}, {step.dtype} is not coded")
+    flag = qstream.F16 if lo.dtype == torch.float16 else qstream.F32
+    n = q.numel()
+    if lo.numel() == 1:
+        return 1, n, 1, flag
+    axes = [a for a in builtins.range(q.dim()) if lo.shape[a] != q.shape[a]] if lo.dim() == q.dim() else []
+    if len(axes) != 1 or lo.shape[axes[0]] != 1:
+        raise NotImplementedError(f"codec.encode_posthoc: a grid of shape {tuple(lo.shape)} on a tensor of shape {tuple(q.shape)} is not one reduced axis")
+    a = axes[0]
+    return int(np.prod(q.shape[:a], dtype=np.int64)), int(q.shape[a]), int(np.prod(q.shape[a + 1:], dtype=np.int64)), flag
+
+
+def huffman_lengths(hist):
+    """The 257 code lengths of a qstream file from the 256-bin histogram of all symbols: the leaf depths of the very construction
+    train_nerv_all._huffman_total_bits sums over (used symbols in increasing order, then the EOF leaf of count 1)."""
+    from .train_nerv_all import _huffman_depths
+    hist = np.asarray(hist, dtype=np.int64)
+    used = np.flatnonzero(hist)
+    depths = _huffman_depths(hist[used].tolist())
+    lengths = np.zeros(qstream.LEAVES, dtype=np.int64)
+    lengths[used] = depths[:-1]
+    lengths[qstream.LEAVES - 1] = depths[-1]
+    if lengths.max() > 32:
+        raise NotImplementedError(f"codec.encode_posthoc: the Huffman code has a {int(lengths.max())}-bit code word; the format carries 32 "
+                                  "(the code is not length-limited: that would change the bits the log reports)")
+    return lengths.astype(np.uint8)
+
+
+def check_posthoc_flags(args):
+    """The refusals of encode_posthoc that depend on the run's flags alone -- train_nerv_all calls this right after argument parsing, so a
+    run that cannot write its --bitstream stops before it trains."""
+    name = getattr(args, "model", None)
+    if name not in POSTHOC_MODELS:
+        raise NotImplementedError(f"codec.encode_posthoc: --model {name} has no bitstream (built for {', '.join(POSTHOC_MODELS)})")
+    if getattr(args, "quant_model_bit", 8) == -1:
+        raise NotImplementedError("codec.encode_posthoc: --quant_model_bit -1 builds no quantised twin: there are no symbols to code")
+    if "HNeRV" in name and getattr(args, "interpolation", False) and getattr(args, "embed_inter", False):
+        raise NotImplementedError("codec.encode_posthoc: --interpolation --embed_inter scores the held-out frames from fp32 encoder outputs of "
+                                  "their neighbours, which no file holds")
+
+
+@torch.no_grad()
+def encode_posthoc(model, args, records, quant_embed, path):
+    """Write what train_nerv_all.evaluate() scored under `quant_*` -- `records` of its quant_model() call and, for the HNeRV models, the
+    `quant_embed` record of its frame embeddings -- as a qstream file to `path` (a file name or a binary file object); returns
+    qstream.info of what was written.  Nothing is re-quantised: the symbols, the grids and the Huffman code are those of that evaluation,
+    so info["symbol_bits"] is _huffman_total_bits of its histogram, args.bits_per_param * numel."""
+    from .lib.entropy_model import huff_encode
+    check_posthoc_flags(args)
+    if records is None:
+        raise NotImplementedError("codec.encode_posthoc: --quant_model_bit -1 builds no quantised twin: there are no symbols to code")
+    name = args.model
+    is_hnerv = "HNeRV" in name
+    if is_hnerv and quant_embed is None:
+        raise ValueError(f"codec.encode_posthoc: --model {name} needs the quantised frame embeddings of the evaluation")
+    recs = ([quant_embed] if is_hnerv else []) + list(records.values())
+    for r in recs:
+        if r["quant"].dtype != torch.uint8 or r["quant"].numel() == 0:
+            raise NotImplementedError(f"codec.encode_posthoc: symbols of dtype {r['quant'].dtype} are not coded (8 bits at most)")
+    symbols = np.concatenate([r["quant"].detach().reshape(-1).cpu().numpy() for r in recs])
+    counts = [int(r["quant"].numel()) for r in recs]
+    lengths = huffman_lengths(np.bincount(symbols, minlength=256))
+    words, run_bits = huff_encode(symbols, counts, lengths, qstream.RUN)
+    out, at = [], 0
+    for r, n in zip(recs, counts):
+        outer, red, inner, flag = _grid_geometry(r)
+        k = qstream.n_runs(n)
+        out.append(qstream.QRecord(n, outer, red, inner, flag, r["min"].detach().reshape(-1).cpu().numpy(), r["scale"].detach().reshape(-1).cpu().numpy(),
+                                   run_bits[at:at + k]))
+        at += k
+    frame_hw = tuple(int(v) for v in args.crop_list.split("_")[:2])
+    s = _settings(args, args.full_data_length, frame_hw)
+    s.update(final_size=int(args.final_size), quant_model_bit=int(args.quant_model_bit), quant_embed_bit=int(args.quant_embed_bit), huff_run=qstream.RUN)
+    if is_hnerv:
+        s["embed_shape"] = [int(v) for v in quant_embed["quant"].shape]
+    blob = qstream.to_bytes(s, lengths, out, words)
+    if hasattr(path, "write"):
+        path.write(blob)
+    else:
+        with open(path, "wb") as f:
+            f.write(blob)
+    return qstream.info(blob)
+
+
+def describe_posthoc(budget):
+    """One line of a qstream.info budget (the log of train_nerv_all --bitstream, `codec info`)."""
+    return (f"{budget['bytes']} bytes = {budget['total']} bits: Huffman codes {budget['symbol_bits']} ({budget['n_symbols']} symbols in {budget['n_records']} "
+            f"tensors) + run index {budget['run_index']} ({budget['n_runs']} runs) + grids {budget['grid_side']} + code table {budget['code_table']} "
+            f"+ header {budget['header']} + padding {budget['padding']}")
+
+
 class Decoder:
     """A bitstream, ready to decode frames on `device`.
 
@@ -219,9 +320,12 @@ class Decoder:
 
     def __init__(self, path, device="cuda", use_graph=True, pack="rgb8", matrix="bt709", range="limited"):
         from . import ops
-        from .engine import FrameDecodeGraph
         from .lib.entropy_model import ans_decode_gaussian
         from .train_nerv_all import build_model
+        self.kind = "posthoc" if qstream.magic_of(path) == qstream.MAGIC else "cem"
+        if self.kind == "posthoc":
+            self._load_posthoc(path, device)
+            return self._frame_loop(use_graph, pack, matrix, range)
         bs = bitstream.read(path)
         s = dict(bs.settings)
         if s.get("model") not in MODELS:
@@ -283,6 +387,64 @@ class Decoder:
         for v, a in zip(rest, bs.raw):
             v.copy_(torch.from_numpy(a).reshape(v.shape))
 
+        self._frame_loop(use_graph, pack, matrix, range)
+
+    def _load_posthoc(self, path, device):
+        """A qstream file: the model without quantisers (and, for the HNeRV models, without its encoder), the bit
+        string uploaded once as it lies in the file, ONE launch that Huffman-decodes and de-quantises it into the state_dict tensors and the
+        [N, C, h, w] embedding tensor."""
+        from . import ops
+        from .train_nerv_all import build_model
+        qs = qstream.read(path)
+        s = dict(qs.settings)
+        if s.get("model") not in POSTHOC_MODELS:
+            raise ValueError(f"qstream: header names the model {s.get('model')!r}; this build decodes {', '.join(POSTHOC_MODELS)}")
+        self.settings = s
+        self.device = torch.device(device)
+        self.n_frames = int(s["full_data_length"])
+        self.frame_hw = tuple(int(v) for v in s["crop_list"].split("_")[:2])
+        self.is_hnerv = "HNeRV" in s["model"]
+        margs = SimpleNamespace(**s)
+        margs.__dict__.update(quant=False, outf="")
+        model = build_model(margs)
+        if self.is_hnerv:
+            model.encoder = torch.nn.Identity()            # the embeddings replace it: never written, never needed
+        model = model.to(self.device).eval().requires_grad_(False)
+        self.model = model
+        targets = []
+        if self.is_hnerv:
+            shape = tuple(int(v) for v in s.get("embed_shape", ()))
+            if len(shape) != 4 or shape[0] != self.n_frames:
+                raise ValueError(f"qstream: the header's embedding shape {shape} does not match its {self.n_frames} frames")
+            self.embeds = torch.empty(shape, dtype=torch.float32, device=self.device)
+            targets.append(self.embeds)
+        else:
+            self.embeds = None
+        targets += [v for k, v in model.state_dict().items() if "encoder" not in k]
+        if len(targets) != len(qs.records) or any(t.numel() != r.count for t, r in zip(targets, qs.records)):
+            raise ValueError("qstream: the records do not match the model the header describes")
+        if any(t.dtype != torch.float32 or not t.is_contiguous() for t in targets):
+            raise ValueError("qstream: the model the header describes has a state_dict entry that is not a dense fp32 tensor")
+        # every grid in ONE upload: min and scale of each record as they lie in the file, each array on a 4-byte boundary
+        blobs, spans, at = [], [], 0
+        for r in qs.records:
+            for a in (r.min, r.scale):
+                raw = a.tobytes()
+                raw += b"\0" * (-len(raw) % 4)
+                spans.append((at, a.nbytes))
+                blobs.append(raw)
+                at += len(raw)
+        grids = torch.frombuffer(bytearray(b"".join(blobs)), dtype=torch.uint8).to(self.device)
+        items = []
+        for k, (t, r) in enumerate(zip(targets, qs.records)):
+            tdt = torch.float16 if r.dtype == qstream.F16 else torch.float32
+            lo, step = (grids[o:o + n].view(tdt) for o, n in spans[2 * k:2 * k + 2])
+            items.append((t, lo, step, r.red, r.inner, r.run_bits))
+        ops.huff_dequant(qs.words, qs.lengths, items, int(s["huff_run"]))
+
+    def _frame_loop(self, use_graph, pack, matrix, range):
+        from .engine import FrameDecodeGraph
+        model, pin = self.model, self.device.type == "cuda"
         self.norms = torch.tensor([float(i + 1) / self.n_frames for i in builtins.range(self.n_frames)], dtype=torch.float64, device=self.device)
         first_embed = self.embeds[0:1] if self.is_hnerv else None
         self._loop = FrameDecodeGraph(model, self.norms[0:1], first_embed, self.norms[0:1], self.frame_hw, use_graph=use_graph,
@@ -416,8 +578,9 @@ def build_parser():
 def main(argv=None):
     a = build_parser().parse_args(argv)
     if a.cmd == "info":
-        budget = bitstream.info(a.file)
-        print(describe(budget))
+        posthoc = qstream.magic_of(a.file) == qstream.MAGIC
+        budget = qstream.info(a.file) if posthoc else bitstream.info(a.file)
+        print(describe_posthoc(budget) if posthoc else describe(budget))
         print(json.dumps(budget))
         return budget
     if not torch.cuda.is_available():

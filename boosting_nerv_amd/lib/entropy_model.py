@@ -89,6 +89,42 @@ def ans_decode_categorical(words, n, probs):
     return out[:n]
 
 
+def huff_encode(symbols, counts, lengths, run=L.HUFF_RUN):
+    """uint8 symbols of the items back to back (counts[k] each) under the canonical code of the 257 `lengths` ->
+    (uint32 words of the bit string, uint16 bit length of every run of `run` symbols); csrc/huff.cpp, DESIGN section 26."""
+    lib = L.load()
+    sym = np.ascontiguousarray(symbols, dtype=np.uint8)
+    cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+    ln = np.ascontiguousarray(lengths, dtype=np.uint8)
+    if ln.size != L.HUFF_LEAVES or int(cnt.sum()) != sym.size or run < 1:
+        raise ValueError(f"huff_encode: need {L.HUFF_LEAVES} code lengths, counts that add up to the symbols and a positive run length")
+    n_runs = int(sum((int(c) + run - 1) // run for c in cnt))
+    run_bits = np.zeros(max(n_runs, 1), dtype=np.uint16)
+    args = (sym.ctypes.data, cnt.ctypes.data, cnt.size, ln.ctypes.data, int(run))
+    need = lib.bnerv_huff_encode(*args, None, 0, run_bits.ctypes.data, run_bits.size)
+    if need < 0:
+        L.check(-1, "bnerv_huff_encode")
+    out = np.zeros(max(need, 1), dtype=np.uint32)
+    got = lib.bnerv_huff_encode(*args, out.ctypes.data, out.size, run_bits.ctypes.data, run_bits.size)
+    assert got == need
+    return out[:need], run_bits[:n_runs]
+
+
+def huff_decode(words, run_bits, counts, lengths, run=L.HUFF_RUN):
+    """The inverse of huff_encode -> uint8 symbols; raises BnervError when a run does not end on its recorded bit."""
+    lib = L.load()
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    rb = np.ascontiguousarray(run_bits, dtype=np.uint16)
+    cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+    ln = np.ascontiguousarray(lengths, dtype=np.uint8)
+    if ln.size != L.HUFF_LEAVES:
+        raise ValueError(f"huff_decode: need {L.HUFF_LEAVES} code lengths")
+    out = np.zeros(max(int(cnt.sum()), 1), dtype=np.uint8)
+    L.check(lib.bnerv_huff_decode(w.ctypes.data, w.size, rb.ctypes.data, rb.size, cnt.ctypes.data, cnt.size, ln.ctypes.data, int(run), out.ctypes.data),
+            "bnerv_huff_decode")
+    return out[:int(cnt.sum())]
+
+
 def compress_matrix_flatten_gaussian_global(matrix, mean, std):
     """Bits of the rANS message of the integer tensor `matrix` under QuantizedGaussian(min, max, mean, std) -- the reference's
     function of the same name (lib/entropy_model.py:46-62), which returns 8 * bytes of constriction's compressed buffer."""

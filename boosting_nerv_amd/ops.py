@@ -941,6 +941,88 @@ def dequant_table(symbols, outs, scales, betas=None):
     return outs
 
 
+class HuffDequant:
+    """The device side of one qstream payload, ready to launch: the bit string (padded by two zero words), one
+    descriptor per run (64-bit start bit, item, first element; built here from the u16 run lengths) and the item table.
+
+        words      uint32 numpy array: the bit string as it lies in the file
+        lengths    the 257 code lengths
+        items      one (out, min, scale, red, inner, run_bits) per tensor: out a contiguous fp32 device tensor, min / scale contiguous fp32
+                   or fp16 device tensors of out.numel() / red entries, run_bits its uint16 run lengths
+    launch() decodes and de-quantises everything in one kernel; check() reads the device error word (a host sync) and raises ValueError
+    when a run did not end on its recorded bit."""
+
+    def __init__(self, words, lengths, items, run=L.HUFF_RUN):
+        import numpy as np
+        if not items:
+            raise ValueError("huff_dequant: no items")
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        self.lengths = np.ascontiguousarray(lengths, dtype=np.uint8)
+        if self.lengths.size != L.HUFF_LEAVES:
+            raise ValueError(f"huff_dequant: need {L.HUFF_LEAVES} code lengths")
+        if run != L.HUFF_RUN:
+            raise ValueError(f"huff_dequant: the kernel is built for runs of {L.HUFF_RUN} symbols, not {run}")
+        self.run = int(run)
+        table = np.zeros(len(items), dtype=np.dtype([("out", "<u8"), ("min", "<u8"), ("scale", "<u8"), ("dtype", "<i4"), ("n", "<u4"), ("red", "<u4"), ("inner", "<u4")]))
+        assert table.dtype.itemsize == C.sizeof(L.HuffItem)
+        starts, item_of, first_of, bit = [], [], [], 0
+        device = items[0][0].device
+        for k, (out, lo, step, red, inner, run_bits) in enumerate(items):
+            L.require_device(out, "out"), L.require_device(lo, "min"), L.require_device(step, "scale")
+            n, red, inner = out.numel(), int(red), int(inner)
+            if out.dtype != torch.float32 or not out.is_contiguous() or n == 0 or n >= 2 ** 31 or out.data_ptr() % 4 or out.device != device:
+                raise ValueError(f"huff_dequant: item {k}: out must be a non-empty contiguous 4-byte aligned fp32 tensor on {device} (below 2^31 elements)")
+            if red < 1 or inner < 1 or n % (red * inner):
+                raise ValueError(f"huff_dequant: item {k}: {n} elements do not split into slices of red={red}, inner={inner}")
+            slices = n // red
+            if lo.dtype != step.dtype or lo.dtype not in (torch.float32, torch.float16) or lo.numel() != slices or step.numel() != slices \
+                    or not lo.is_contiguous() or not step.is_contiguous() or (lo.data_ptr() | step.data_ptr()) % lo.element_size():
+                raise ValueError(f"huff_dequant: item {k}: min and scale must be contiguous fp32 or fp16 tensors of {slices} entries each")
+            rb = np.ascontiguousarray(run_bits, dtype=np.uint16)
+            n_runs = (n + run - 1) // run
+            if rb.size != n_runs:
+                raise ValueError(f"huff_dequant: item {k}: {rb.size} run lengths for {n_runs} runs")
+            table[k] = (out.data_ptr(), lo.data_ptr(), step.data_ptr(), L.HUFF_F16 if lo.dtype == torch.float16 else L.HUFF_F32, n, red, inner)
+            ends = bit + np.cumsum(rb, dtype=np.uint64)
+            starts.append(np.concatenate([np.array([bit], dtype=np.uint64), ends[:-1]]))
+            item_of.append(np.full(n_runs, k, dtype=np.uint32))
+            first_of.append(np.arange(n_runs, dtype=np.uint32) * np.uint32(run))
+            bit = int(ends[-1])
+        if (bit + 31) // 32 != words.size:
+            raise ValueError(f"huff_dequant: the run lengths add up to {bit} bits, the bit string has {words.size} words")
+        self.n_runs = int(sum(a.size for a in starts))
+        runs = np.zeros(self.n_runs + 1, dtype=np.dtype([("start_bit", "<u8"), ("item", "<u4"), ("first", "<u4")]))
+        assert runs.dtype.itemsize == C.sizeof(L.HuffRun)
+        runs["start_bit"][:-1], runs["item"][:-1], runs["first"][:-1] = np.concatenate(starts), np.concatenate(item_of), np.concatenate(first_of)
+        runs["start_bit"][-1] = bit                              # the sentinel: where the last run ends
+        padded = np.zeros(words.size + 2, dtype=np.uint32)       # the kernel clamps every read to these words
+        padded[:words.size] = words
+        up = lambda a: torch.from_numpy(a.view(np.uint8).copy()).to(device)      # noqa: E731
+        self.words, self.runs, self.items = up(padded), up(runs), up(table)
+        self.n_words, self.n_items = padded.size, len(items)
+        self.err = torch.zeros(1, dtype=torch.int32, device=device)
+        self._keep = [(o, a, b) for o, a, b, *_ in items]
+
+    def launch(self):
+        L.check(L.load().bnerv_huff_dequant(L.stream(), L.ptr(self.words), self.n_words, L.ptr(self.runs), self.n_runs, L.ptr(self.items), self.n_items,
+                                            self.lengths.ctypes.data, self.run, L.ptr(self.err)), "bnerv_huff_dequant")
+        return self
+
+    def check(self):
+        if int(self.err.item()) != 0:
+            raise ValueError("huff_dequant: a run of the bit string did not end on its recorded bit (the payload does not match its run index)")
+        return self
+
+
+def huff_dequant(words, lengths, items, run=L.HUFF_RUN):
+    """Huffman-decode a qstream bit string and de-quantise it into the items' `out` tensors IN PLACE, one launch:
+    out[i] = float(min[s]) + float(scale[s]) * float(q[i]), s = (i // (red * inner)) * inner + i % inner, product and sum one fp32
+    operation each -- the `rebuilt` of hnerv_utils.quant_tensor, bit for bit.  Arguments: HuffDequant.  Raises ValueError when the device
+    reports a run that did not end on its recorded bit."""
+    HuffDequant(words, lengths, items, run).launch().check()
+    return [it[0] for it in items]
+
+
 def frame_to_u8(x, out=None):
     """[B, 3, H, W] fp32 -> [B, H, W, 3] uint8 = (x.clamp(0, 1) * 255 + 0.5).to(uint8).permute(0, 2, 3, 1) in one pass (the image
     convention of train_nerv_all._save_images).  out: a contiguous uint8 buffer to write into (a captured decode's)."""

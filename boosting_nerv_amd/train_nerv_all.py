@@ -92,6 +92,8 @@ def build_parser():
     parser.add_argument('--quant_embed_bit', type=int, default=6, help='bit length for embedding quantization')
     parser.add_argument('--quant_axis', type=int, default=0, help='quantization axis (-1 means per tensor)')
     parser.add_argument('--dump_images', action='store_true', default=False, help='dump the prediction images')
+    parser.add_argument('--bitstream', type=str, default=None,
+                        help='write the post-hoc quantised model of the final evaluation (and of --eval_only) to this file (codec.py decodes it)')
     parser.add_argument('--dump_videos', action='store_true', default=False, help='concat the prediction images into video')
     parser.add_argument('--eval_fps', action='store_true', default=False, help='fwd multiple times to test the fps')
     parser.add_argument('--encoder_file', default='', type=str, help='specify the embedding file')
@@ -163,6 +165,9 @@ def build_model(args):
 def main(argv=None):
     args = build_parser().parse_args(argv)
     torch.set_printoptions(precision=2)
+    if args.bitstream:                                     # what no file can hold is refused before the run, not after its last epoch
+        from .codec import check_posthoc_flags
+        check_posthoc_flags(args)
     if args.debug:
         args.eval_freq, args.outf = 1, 'output/debug'
     else:
@@ -399,10 +404,10 @@ def _generic_step(model, optimizer, bucket, args, frames, img_idx, norm_idx, tak
     return psnr_fn_device(out.detach(), img_gt)
 
 
-def _huffman_total_bits(counts):
-    """sum_i count_i * code_length_i of a Huffman code built over the data symbols plus one EOF symbol of count 1 -- what
-    the reference obtains from dahuffman's HuffmanCodec.from_data + get_code_table (train_nerv_all.py:593-605).  Every optimal
-    code has the same total over all leaves; which tie the EOF leaf wins can move the data-only total by a bit or two."""
+def _huffman_depths(counts):
+    """Code length of every leaf of a Huffman code built over the data symbols (counts, in order) plus one EOF symbol of count 1, the
+    last entry of the returned list -- the construction behind _huffman_total_bits, whose depths are the code lengths a qstream file
+    stores."""
     n = len(counts)
     heap = [(int(c), i, [i]) for i, c in enumerate(list(counts) + [1])]      # last leaf = EOF
     depth = [0] * (n + 1)
@@ -415,7 +420,14 @@ def _huffman_total_bits(counts):
             depth[leaf] += 1
         heapq.heappush(heap, (a[0] + b[0], uid, a[2] + b[2]))
         uid += 1
-    return sum(int(c) * d for c, d in zip(counts, depth[:n]))
+    return depth
+
+
+def _huffman_total_bits(counts):
+    """sum_i count_i * code_length_i of a Huffman code built over the data symbols plus one EOF symbol of count 1 -- what
+    the reference obtains from dahuffman's HuffmanCodec.from_data + get_code_table (train_nerv_all.py:593-605).  Every optimal
+    code has the same total over all leaves; which tie the EOF leaf wins can move the data-only total by a bit or two."""
+    return sum(int(c) * d for c, d in zip(counts, _huffman_depths(counts)[:len(counts)]))
 
 
 def quant_model(model, args):
@@ -509,6 +521,10 @@ def evaluate(model, full_dataloader, local_rank, args, dump_vis=False, huffman_c
     values = book.means(device=next(model.parameters()).device)
     if local_rank in (0, None) and records is not None and huffman_coding:
         _huffman_report(args, records, quant_embed if is_hnerv else None, log)
+    if local_rank in (0, None) and huffman_coding and getattr(args, 'bitstream', None):
+        from . import codec
+        args.bitstream_budget = codec.encode_posthoc(model, args, records, quant_embed if is_hnerv else None, args.bitstream)
+        log.line(f'Bitstream {args.bitstream}: {codec.describe_posthoc(args.bitstream_budget)}')
     return values, hw
 
 

@@ -419,6 +419,42 @@ long bnerv_ans_encode_categorical(const int32_t* symbols, size_t n, const double
 int bnerv_ans_decode_categorical(const uint32_t* words, size_t n_words, size_t n, const double* probs, int K, int32_t* symbols_out);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Huffman coder of the post-hoc quantised model (additive to ABI 9; csrc/huff.cpp on the host, csrc/huff.hip on the device;
+ * boosting_nerv_amd/qstream.py).
+ *
+ * The code is given by BNERV_HUFF_LEAVES code lengths, one byte each: symbols 0..255, then the EOF leaf (never written); length 0 = unused,
+ * at most 32, Kraft equality over the used leaves.  Codes are canonical: leaves ordered by (length, leaf index), the first code of the
+ * shortest length is 0, code(next leaf) = (code + 1) << (its length - the previous length).  A code's bits go into the bit string most
+ * significant first; bit p of the string is bit 31 - (p % 32) of 32-bit word p / 32.
+ * The symbols of item k (counts[k] of them, items back to back in `symbols`) are cut into runs of R = BNERV_HUFF_RUN symbols (the last run
+ * of an item may be shorter; a run never spans two items); the bit string is continuous over runs and items, padded with zero bits to
+ * the final word only.  run_bits[r] is the bit length of run r (<= 32 R, so it fits 16 bits).
+ *   bnerv_huff_encode   (host)  -> the number of 32-bit words of the bit string, also when words_out == NULL or cap_words is too small
+ *                       (nothing is written then); -1 on a bad argument (a symbol without a code, bad lengths, cap_runs too small).
+ *   bnerv_huff_decode   (host)  the inverse, run by run from the recorded lengths.  An error -- never a read past `words` -- when a run
+ *                       does not end on its recorded bit, a bit pattern has no code or decodes to EOF, or the lengths do not add up to n_words.
+ *   bnerv_huff_dequant  (device) ONE launch: one lane decodes one run sequentially into LDS (first-level lookup table of 2^BNERV_HUFF_LUT_BITS
+ *                       entries, canonical search of <= 32 steps for longer codes), a wave then writes
+ *                           out[i] = float(min[s]) + float(scale[s]) * float(q[i]),   s = (i / (red * inner)) * inner + i % inner
+ *                       for its 64 runs with coalesced stores; the product and the sum are each ONE IEEE fp32 operation.  `words`: n_words
+ *                       device words of which the last two are zero padding (every payload read is clamped to them); `runs`: n_runs + 1
+ *                       device descriptors, the last one a sentinel holding the total bit count; `items`: n_items device entries.  A lane
+ *                       whose run does not end on the next descriptor's start bit (or that meets EOF) sets bit 0 of *err (device int). */
+#define BNERV_HUFF_RUN 256
+#define BNERV_HUFF_LEAVES 257
+#define BNERV_HUFF_LUT_BITS 12
+#define BNERV_HUFF_F32 0
+#define BNERV_HUFF_F16 1
+typedef struct { unsigned long long start_bit; unsigned item; unsigned first; } bnerv_huff_run;      /* first: index of the run's first element in its item */
+typedef struct { float* out; const void* min; const void* scale; int dtype; unsigned n; unsigned red; unsigned inner; } bnerv_huff_item;
+long bnerv_huff_encode(const unsigned char* symbols, const unsigned* counts, int n_items, const unsigned char* lengths, int R,
+                       uint32_t* words_out, size_t cap_words, unsigned short* run_bits_out, size_t cap_runs);
+int bnerv_huff_decode(const uint32_t* words, size_t n_words, const unsigned short* run_bits, size_t n_runs, const unsigned* counts, int n_items,
+                      const unsigned char* lengths, int R, unsigned char* symbols_out);
+int bnerv_huff_dequant(void* stream, const uint32_t* words, size_t n_words, const bnerv_huff_run* runs, size_t n_runs,
+                       const bnerv_huff_item* items, int n_items, const unsigned char* lengths_host, int R, int* err);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Depthwise KxK convolution (K odd <= 7, stride 1, padding K/2) of the ConvNeXt encoder block of HNeRV_Boost
  * (model_blocks.py:223-247: nn.Conv2d(dim, dim, 7, padding=3, groups=dim)); first kernels of SURVEY 8(f) row N3.
  *   bnerv_dwconv_fwd(flip=0): y = conv(x, w) + bias;   flip=1: the data gradient (taps flipped, bias ignored: pass g as x)

@@ -15,7 +15,10 @@
 Cases: "c1q" -- the C1 model (NeRV_Boost 1.5M, 720x1280) built with the compression recipe's quantiser flags; "c5" -- BASELINE configs[4]
 (HNeRV_Boost 3M, 1080x1920, quantised embeddings).  Weights are the seeded initialisation with init_data() scales: the timing does not
 depend on what the weights say.
-usage: python tools/kdecode.py --bitstream [--frames 16] [--rounds 3] [--only c1q|c5|pack]   (needs the GPU)"""
+--bitstream --posthoc times the file of the regression path instead (qstream.py) on the C1 model as train_nerv_all builds
+it: quant_model -> codec.encode_posthoc, then (1) as above -- here the coded bytes go up as they lie in the file and ONE kernel decodes and
+de-quantises them -- and the decode kernel alone under HIP events (ops.HuffDequant.launch, tables already on the device; 20 launches replayed from a graph).
+usage: python tools/kdecode.py --bitstream [--posthoc] [--frames 16] [--rounds 3] [--only c1q|c5|pack]   (needs the GPU)"""
 import argparse
 import io
 import os
@@ -162,6 +165,53 @@ def run_case(case, n_frames, rounds):
         print(f"{case} model-ready, {label}: {min(v) * 1e3:.1f} ms best of {len(v)}")
 
 
+def run_posthoc(n_frames, rounds):
+    import torch
+    import bench
+    from boosting_nerv_amd import codec, ops, qstream
+    from boosting_nerv_amd import train_nerv_all as T
+    dev = torch.device("cuda:0")
+    args, model = bench.build("c1")
+    model = model.to(dev)
+    h, w = (int(v) for v in args.crop_list.split("_")[:2])
+    args.full_data_length, args.final_size = n_frames, h * w
+    t0 = time.time()
+    _, records = T.quant_model(model, args)
+    buf = io.BytesIO()
+    budget = codec.encode_posthoc(model, args, records, None, buf)
+    blob = buf.getvalue()
+    print(f"c1 post hoc: {args.model} {h}x{w}, {budget['n_symbols']} symbols in {budget['n_records']} tensors; quantise + encode {time.time() - t0:.2f} s; "
+          f"file {codec.describe_posthoc(budget)}", flush=True)
+    del model
+    ready = {}
+    for label, use_graph in (("first construction of the process (eager)", False), ("eager", False), ("graph", True), ("eager", False), ("graph", True)):
+        t0 = time.time()
+        qs = qstream.read(blob)
+        t_read = time.time() - t0
+        dec = None
+        torch.cuda.synchronize()
+        t0 = time.time()
+        dec = codec.Decoder(blob, dev, use_graph=use_graph)
+        torch.cuda.synchronize()
+        ready.setdefault(label, []).append(time.time() - t0)
+        print(f"c1 post hoc model-ready, {label}: {ready[label][-1] * 1e3:.1f} ms (container parse + CRC alone: {t_read * 1e3:.1f} ms)", flush=True)
+    for label, v in ready.items():
+        print(f"c1 post hoc model-ready, {label}: {min(v) * 1e3:.1f} ms best of {len(v)}")
+    # the kernel alone: the same tables, outputs of its own
+    items = []
+    for r in qs.records:
+        tdt = torch.float16 if r.dtype == qstream.F16 else torch.float32
+        items.append((torch.empty(r.count, device=dev), torch.from_numpy(r.min).to(dev).to(tdt), torch.from_numpy(r.scale).to(dev).to(tdt), r.red, r.inner, r.run_bits))
+    plan = ops.HuffDequant(qs.words, qs.lengths, items)
+    plan.launch().check()
+    plan.check()
+    (best, worst), = time_graph([plan.launch], reps=20, rounds=max(rounds, 3))      # replayed from a graph: a Python-driven launch costs more host time
+    plan.check()
+    coded = budget["symbol_bits"] / 8
+    print(f"c1 post hoc decode kernel: {best:.1f} us best, {worst:.1f} worst per launch ({plan.n_runs} runs, {budget['n_symbols'] / best:.0f} symbols/us, "
+          f"{coded / best / 1e3:.2f} GB/s of coded bytes in, {4 * budget['n_symbols'] / best / 1e3:.1f} GB/s of fp32 out)")
+
+
 def forward_rates(cfg):
     """Decode (forward-only) rate of a bench.py decoder (c1 | c3 | c4) on the HIP path: frames/s for single-frame decodes under
     torch.no_grad(), eager and as a captured hipGraph (N4 row: the figure the reference logs as "FPS" in evaluate())."""
@@ -211,6 +261,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("cfg", nargs="?", default="c1", help="without --bitstream: the bench.py recipe whose forward-only rate is measured")
     ap.add_argument("--bitstream", action="store_true", help="time the bitstream decoder instead")
+    ap.add_argument("--posthoc", action="store_true", help="with --bitstream: the post-hoc quantised file of the regression path (C1 model)")
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--only", choices=["c1q", "c5", "pack"], default=None)
@@ -219,6 +270,9 @@ def main():
     assert torch.cuda.is_available(), "kdecode needs the GPU"
     if not a.bitstream:
         forward_rates(a.cfg)
+        return 0
+    if a.posthoc:
+        run_posthoc(a.frames, a.rounds)
         return 0
     for case in ([a.only] if a.only else ["c1q", "c5", "pack"]):
         if case == "pack":
