@@ -130,6 +130,18 @@ class HuffItem(C.Structure):       # bnerv_huff_item
     _fields_ = [("out", _fp), ("min", _fp), ("scale", _fp), ("dtype", C.c_int), ("n", C.c_uint32), ("red", C.c_uint32), ("inner", C.c_uint32)]
 
 
+RANS_MAX_ALPHABET, RANS_MIN_RUN, RANS_MAX_RUN = 4096, 64, 4096      # BNERV_RANS_MAX_ALPHABET, BNERV_RANS_MIN_RUN, BNERV_RANS_MAX_RUN
+
+
+class RansBlock(C.Structure):      # bnerv_rans_block
+    _fields_ = [("item", C.c_uint32), ("run", C.c_uint32), ("first", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class RansItem(C.Structure):       # bnerv_rans_item
+    _fields_ = [("out", _fp), ("scale", C.c_float), ("beta", C.c_float), ("lo", C.c_int), ("n", C.c_uint32), ("table", C.c_uint32), ("alphabet", C.c_uint32),
+                ("has_beta", C.c_int), ("_pad", C.c_int)]
+
+
 class YuvCoeffs(C.Structure):      # bnerv_yuv_coeffs: what yuvio.coefficients() computed in float64, rounded to fp32
     _fields_ = [("m", C.c_float * 9), ("off", C.c_float * 3), ("scale", C.c_float * 3), ("maxcode", C.c_float)]
 
@@ -195,6 +207,10 @@ SYMBOLS = {
     "bnerv_ans_decode_gaussian": (_I, [_V, _Z, _Z, _I, _I, C.c_double, C.c_double, _V]),
     "bnerv_ans_encode_categorical": (C.c_long, [_V, _Z, _V, _I, _V, _Z]),
     "bnerv_ans_decode_categorical": (_I, [_V, _Z, _Z, _V, _I, _V]),
+    "bnerv_ans_gaussian_cdf": (C.c_long, [_I, _I, C.c_double, C.c_double, _V, _Z]),
+    "bnerv_ans_encode_gaussian_runs": (C.c_long, [_V, _Z, _I, _I, C.c_double, C.c_double, _I, _V, _Z, _V]),
+    "bnerv_ans_decode_gaussian_runs": (_I, [_V, _Z, _V, _Z, _Z, _I, _I, C.c_double, C.c_double, _I, _V]),
+    "bnerv_rans_dequant": (_I, [_V, _V, _Z, _V, _Z, _V, _Z, _V, _I, _V, _Z, _I, _V]),
     "bnerv_huff_encode": (C.c_long, [_V, _V, _I, _V, _I, _V, _Z, _V, _Z]),
     "bnerv_huff_decode": (_I, [_V, _Z, _V, _Z, _V, _I, _V, _I, _V]),
     "bnerv_huff_dequant": (_I, [_V, _V, _Z, _V, _Z, _V, _I, _V, _I, _V]),

@@ -14,7 +14,13 @@ uint8 packing kernel as a captured graph -- the frames evaluate() scored, bit fo
 The regression path (train_nerv_all.py --bitstream) has a file of its own kind (qstream.py): encode_posthoc() writes the
 8-bit codes of evaluate()'s post-hoc quantised twin under the one Huffman code the log reports, and Decoder -- which tells the two kinds
 apart by their magic number -- uploads the coded bytes as they lie in the file and lets ONE kernel (ops.huff_dequant) Huffman-decode and
-de-quantise them straight into the parameter tensors.  Every command above works on both kinds."""
+de-quantise them straight into the parameter tensors.
+
+A CEM file also comes in a chunked kind (rstream.py) whose records are cut into runs that are range-ANS coded
+independently: encode(..., run=N) or repack() writes it, and Decoder uploads its words as they lie in the file and lets ONE kernel
+(ops.ans_dequant) entropy-decode and de-quantise them -- no entropy decode on the host.  Every command above works on all three kinds.
+
+    python -m boosting_nerv_amd.codec repack in.bnrv out.bnrc [--run N]"""
 import argparse
 import builtins
 import json
@@ -24,7 +30,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import bitstream, qstream
+from . import bitstream, qstream, rstream
 from .bitstream import Record
 
 # the settings the model constructors read (model_nerv.py, model_hnerv.py, model_enerv.py, model_blocks.py), resolved: fc_dim after the size
@@ -155,13 +161,22 @@ def _frames_in_order(frames_or_loader, args, device):
 
 
 @torch.no_grad()
-def encode(model, entropy_model, args, frames_or_loader, path):
+def encode(model, entropy_model, args, frames_or_loader, path, run=0):
     """Write the model (and, for HNeRV_Boost, every frame's embedding) as a bitstream to `path` (a file name or a binary file object);
     returns bitstream.info of what was written.
 
     frames_or_loader: the clip as a [N, 3, H, W] tensor or the full-clip loader of the training scripts; the models that decode from the
     frame index alone (NeRV_Boost, ENeRV_Boost) read only its length (None: args.full_data_length).  Symbols, means and stds are those of evaluate()'s accounting:
-    the coded words of the file are get_bitrate_sum("real_bitrate") plus, with one frame per evaluation batch, the embedding bits."""
+    the coded words of the file are get_bitrate_sum("real_bitrate") plus, with one frame per evaluation batch, the embedding bits.
+
+    run > 0 writes the chunked kind instead (rstream.py: runs of `run` symbols, decoded on the device): the version-1 file is encoded into a
+    buffer and repacked, so its symbols and side information are the same by construction; returns rstream.info then."""
+    if run:
+        import io
+        rstream.check_run(run)
+        buf = io.BytesIO()
+        encode(model, entropy_model, args, frames_or_loader, buf)
+        return repack(buf.getvalue(), path, run)
     _check_supported(model, entropy_model, args)
     device = next(model.parameters()).device
     n_frames, frames = _frames_in_order(frames_or_loader, args, device)
@@ -196,6 +211,57 @@ def encode(model, entropy_model, args, frames_or_loader, path):
     if hasattr(path, "getvalue"):
         return bitstream.info(path.getvalue())
     return bitstream.info(path) if not hasattr(path, "write") else None
+
+
+def repack(src, dst, run=1024):
+    """A version-1 CEM file `src` (a file name, a binary file object or bytes) as the chunked kind `dst` (a file name or a binary file
+    object): every record rANS-decoded on the host and re-encoded in independent runs of `run` symbols under the same Gaussian.  Header
+    settings (plus "ans_run"), record order, side values and the raw section are copied.  Host only: no GPU, no retraining.  Returns
+    rstream.info of what was written."""
+    from .lib.entropy_model import ans_decode_gaussian, ans_encode_gaussian_runs
+    run = rstream.check_run(run)
+    bs = bitstream.read(src)
+    settings = dict(bs.settings)
+    settings["ans_run"] = run
+    words = []
+
+    def chunk(r):
+        if r.hi - r.lo + 1 > rstream.MAX_ALPHABET:
+            raise NotImplementedError(f"codec.repack: a record's symbols span [{r.lo}, {r.hi}]: {r.hi - r.lo + 1} values; the chunked kind carries "
+                                      f"{rstream.MAX_ALPHABET} (the device decoder holds a record's table in LDS)")
+        sym = ans_decode_gaussian(r.words, r.count, r.lo, r.hi, float(r.mean), float(r.std))
+        w, run_words = ans_encode_gaussian_runs(sym, r.lo, r.hi, float(r.mean), float(r.std), run)
+        words.append(w)
+        return rstream.RRecord(r.count, r.scale, r.mean, r.std, r.lo, r.hi, run_words, r.beta)
+
+    tensors = [chunk(r) for r in bs.tensors]
+    embeds = [chunk(r) for r in bs.embeds]
+    blob = rstream.to_bytes(settings, tensors, embeds, bs.embed_shape, bs.raw, np.concatenate(words) if words else np.zeros(0, dtype=np.uint32))
+    if hasattr(dst, "write"):
+        dst.write(blob)
+    else:
+        with open(dst, "wb") as f:
+            f.write(blob)
+    return rstream.info(blob)
+
+
+def describe_chunked(budget):
+    """One line of an rstream.info budget (the log of train_nerv_compression --bitstream --bitstream_run, `codec info`)."""
+    return (f"{budget['bytes']} bytes = {budget['total']} bits: ANS words {budget['ans_words']} ({budget['n_symbols']} symbols in {budget['n_runs']} runs of "
+            f"{budget['ans_run']}) + run index {budget['run_index']} + per-tensor side {budget['tensor_side']} ({budget['n_tensors']} tensors) + embedding side "
+            f"{budget['embed_side']} ({budget['n_embeds']} frames) + raw fp32 {budget['raw']} ({budget['n_raw']} entries) + header {budget['header']} "
+            f"+ padding {budget['padding']}")
+
+
+def describe_any(budget):
+    """describe, describe_posthoc or describe_chunked, by the budget's items."""
+    return describe_chunked(budget) if "ans_words" in budget else describe_posthoc(budget) if "symbol_bits" in budget else describe(budget)
+
+
+def info(path_or_buffer):
+    """The bit budget of a file of any of the three kinds (bitstream.info, qstream.info or rstream.info, by the magic number)."""
+    magic = qstream.magic_of(path_or_buffer)
+    return (qstream.info if magic == qstream.MAGIC else rstream.info if magic == rstream.MAGIC else bitstream.info)(path_or_buffer)
 
 
 def describe(budget):
@@ -322,20 +388,22 @@ class Decoder:
         from . import ops
         from .lib.entropy_model import ans_decode_gaussian
         from .train_nerv_all import build_model
-        self.kind = "posthoc" if qstream.magic_of(path) == qstream.MAGIC else "cem"
+        magic = qstream.magic_of(path)
+        self.kind = "posthoc" if magic == qstream.MAGIC else "chunked" if magic == rstream.MAGIC else "cem"
         if self.kind == "posthoc":
             self._load_posthoc(path, device)
             return self._frame_loop(use_graph, pack, matrix, range)
-        bs = bitstream.read(path)
+        bs = rstream.read(path) if self.kind == "chunked" else bitstream.read(path)
+        what = "rstream" if self.kind == "chunked" else "bitstream"
         s = dict(bs.settings)
         if s.get("model") not in MODELS:
-            raise ValueError(f"bitstream: header names the model {s.get('model')!r}; this build decodes {', '.join(MODELS)}")
+            raise ValueError(f"{what}: header names the model {s.get('model')!r}; this build decodes {', '.join(MODELS)}")
         self.settings = s
         self.device = torch.device(device)
         self.n_frames = int(s["full_data_length"])
         self.frame_hw = tuple(int(v) for v in s["crop_list"].split("_")[:2])
         self.is_hnerv = s["model"] == "HNeRV_Boost"
-        margs = SimpleNamespace(**s)
+        margs = SimpleNamespace(**{k: v for k, v in s.items() if k != "ans_run"})
         margs.__dict__.update(quant=False, outf="")
         model = build_model(margs)
         if self.is_hnerv:
@@ -343,47 +411,58 @@ class Decoder:
         model = model.to(self.device).eval().requires_grad_(False)
         self.model = model
 
-        # host: ANS-decode every record into ONE pinned int32 array (segments start on 16-byte boundaries), upload it once
         targets = []
         for m in model._quant_modules():
             targets.append(m.weight.data)
             if m.bias is not None:
                 targets.append(m.bias.data)
         if len(targets) != len(bs.tensors) or any(t.numel() != r.count for t, r in zip(targets, bs.tensors)):
-            raise ValueError("bitstream: the tensor records do not match the model the header describes")
+            raise ValueError(f"{what}: the tensor records do not match the model the header describes")
         if self.is_hnerv:
             if len(bs.embeds) != self.n_frames or any(r.count != int(np.prod(bs.embed_shape)) for r in bs.embeds):
-                raise ValueError("bitstream: the embedding records do not match the header's frame count and embedding shape")
+                raise ValueError(f"{what}: the embedding records do not match the header's frame count and embedding shape")
             self.embeds = torch.empty(self.n_frames, *bs.embed_shape, dtype=torch.float32, device=self.device)
             targets += [self.embeds[i] for i in builtins.range(self.n_frames)]
         else:
             if bs.embeds:
-                raise ValueError(f"bitstream: embedding records in a {s['model']} stream")
+                raise ValueError(f"{what}: embedding records in a {s['model']} stream")
             self.embeds = None
         records = list(bs.tensors) + list(bs.embeds)
-        offs, total = [], 0
-        for r in records:
-            offs.append(total)
-            total += (r.count + 3) // 4 * 4
-        pin = self.device.type == "cuda"
-        sym_h = torch.zeros(total, dtype=torch.int32, pin_memory=pin)
-        sym_np = sym_h.numpy()
-        for r, o in zip(records, offs):
-            sym_np[o:o + r.count] = ans_decode_gaussian(r.words, r.count, r.lo, r.hi, float(r.mean), float(r.std))
-        coef_h = torch.tensor([float(r.scale) for r in records] + [float(r.beta) for r in bs.embeds], dtype=torch.float32)
-        sym_d = sym_h.to(self.device, non_blocking=True)
-        coef_d = coef_h.to(self.device)
-        n_rec = len(records)
-        ops.dequant_table([sym_d[o:o + r.count] for r, o in zip(records, offs)], [t.reshape(-1) for t in targets],
-                          [coef_d[i:i + 1] for i in builtins.range(n_rec)],
-                          [None] * len(bs.tensors) + [coef_d[n_rec + i:n_rec + i + 1] for i in builtins.range(len(bs.embeds))])
+        if self.kind == "chunked":
+            # the words as they lie in the file, every record's table and the run descriptors: one upload each, ONE launch that
+            # entropy-decodes and de-quantises; its error word is read at the synchronisation below
+            if any(not t.is_contiguous() for t in targets):
+                raise ValueError("rstream: the model the header describes has a quantised tensor that is not dense")
+            job = ops.AnsDequant(bs.words, [(t.reshape(-1), float(r.scale), r.lo, r.hi, float(r.mean), float(r.std), r.run_words,
+                                             None if r.beta is None else float(r.beta)) for t, r in zip(targets, records)], int(s["ans_run"])).launch()
+        else:
+            # host: ANS-decode every record into ONE pinned int32 array (segments start on 16-byte boundaries), upload it once
+            job = None
+            offs, total = [], 0
+            for r in records:
+                offs.append(total)
+                total += (r.count + 3) // 4 * 4
+            pin = self.device.type == "cuda"
+            sym_h = torch.zeros(total, dtype=torch.int32, pin_memory=pin)
+            sym_np = sym_h.numpy()
+            for r, o in zip(records, offs):
+                sym_np[o:o + r.count] = ans_decode_gaussian(r.words, r.count, r.lo, r.hi, float(r.mean), float(r.std))
+            coef_h = torch.tensor([float(r.scale) for r in records] + [float(r.beta) for r in bs.embeds], dtype=torch.float32)
+            sym_d = sym_h.to(self.device, non_blocking=True)
+            coef_d = coef_h.to(self.device)
+            n_rec = len(records)
+            ops.dequant_table([sym_d[o:o + r.count] for r, o in zip(records, offs)], [t.reshape(-1) for t in targets],
+                              [coef_d[i:i + 1] for i in builtins.range(n_rec)],
+                              [None] * len(bs.tensors) + [coef_d[n_rec + i:n_rec + i + 1] for i in builtins.range(len(bs.embeds))])
 
         # raw fp32 section: the decoder's state_dict entries no record covers, in state_dict order
         torch.cuda.current_stream().synchronize()          # (the pinned symbols may go now)
+        if job is not None:
+            job.check()
         sd = model.state_dict()
         rest = [sd[k] for k in _raw_keys(model, self.is_hnerv)]
         if len(rest) != len(bs.raw) or any(v.numel() != a.size for v, a in zip(rest, bs.raw)):
-            raise ValueError("bitstream: the raw section does not match the model the header describes")
+            raise ValueError(f"{what}: the raw section does not match the model the header describes")
         for v, a in zip(rest, bs.raw):
             v.copy_(torch.from_numpy(a).reshape(v.shape))
 
@@ -572,15 +651,23 @@ def build_parser():
     _colour_flags(q, None)
     i = sub.add_parser("info", help="print the bit budget of FILE")
     i.add_argument("file")
+    r = sub.add_parser("repack", help="rewrite the version-1 CEM file SRC as the chunked kind DST, whose symbols decode on the device (host only)")
+    r.add_argument("src")
+    r.add_argument("dst")
+    r.add_argument("--run", type=int, default=1024, help="symbols per independently coded run: a multiple of 64 in 64..4096")
     return p
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
     if a.cmd == "info":
-        posthoc = qstream.magic_of(a.file) == qstream.MAGIC
-        budget = qstream.info(a.file) if posthoc else bitstream.info(a.file)
-        print(describe_posthoc(budget) if posthoc else describe(budget))
+        budget = info(a.file)
+        print(describe_any(budget))
+        print(json.dumps(budget))
+        return budget
+    if a.cmd == "repack":
+        budget = repack(a.src, a.dst, a.run)
+        print(describe_chunked(budget))
         print(json.dumps(budget))
         return budget
     if not torch.cuda.is_available():

@@ -71,7 +71,8 @@ bool categorical_table(const double* p, int K, Table& t) {
 }
 
 // symbols are table indices 0 .. n-1
-long encode(const Table& t, const int32_t* sym, size_t count, uint32_t* out, size_t cap) {
+// two_state_words: the final state always takes two words (low, high), zero ones included -- the runs of the chunked layout
+long encode(const Table& t, const int32_t* sym, size_t count, uint32_t* out, size_t cap, bool two_state_words = false) {
     std::vector<uint32_t> rev;                                  // words in emission order; the message is this order REVERSED + state
     rev.reserve(count / 3 + 8);
     uint64_t state = 0;
@@ -83,7 +84,7 @@ long encode(const Table& t, const int32_t* sym, size_t count, uint32_t* out, siz
         if ((state >> (64 - PREC)) >= prob) { rev.push_back((uint32_t)state); state >>= 32; }
         state = ((state / prob) << PREC) | (state % prob + left);
     }
-    size_t state_words = state == 0 ? 0 : (state >> 32 ? 2 : 1);
+    const size_t state_words = two_state_words ? 2 : state == 0 ? 0 : (state >> 32 ? 2 : 1);
     const size_t total = rev.size() + state_words;
     if (out == nullptr || cap < total) return (long)total;
     // layout: [bulk words in REVERSE emission order (= the order the decoder refills in), low state word, high state word]
@@ -123,7 +124,82 @@ int decode(const Table& t, const uint32_t* words, size_t n_words, size_t count, 
     return bnerv_set_error(BNERV_E_ARG, "ans_decode: the words do not decode to %zu symbols under this model", count);
 }
 
+// One run of the chunked layout: `n_words` words = bulk words + the final state as exactly two words, so the state's
+// place is known and the run is decoded once.  The refill rule is decode()'s.  Reads words[0 .. n_words) only.
+bool decode_run(const Table& t, const uint32_t* words, size_t n_words, size_t count, int32_t* sym) {
+    if (n_words < 2) return false;
+    const size_t bulk = n_words - 2;
+    uint64_t state = (uint64_t)words[bulk] | ((uint64_t)words[bulk + 1] << 32);
+    size_t next = 0;
+    for (size_t i = 0; i < count; ++i) {
+        const uint32_t q = (uint32_t)(state & (TOTAL - 1));
+        const size_t s = (size_t)(std::upper_bound(t.cdf.begin(), t.cdf.end(), q) - t.cdf.begin()) - 1;
+        const uint32_t left = t.cdf[s], prob = t.cdf[s + 1] - left;
+        sym[i] = (int32_t)s;
+        state = (state >> PREC) * prob + (q - left);
+        if ((state >> 32) == 0 && next < bulk) state = (state << 32) | words[next++];
+    }
+    return next == bulk && state == 0;
+}
+
+constexpr size_t MAX_RUN_WORDS = 65535;
+
 }  // namespace
+
+extern "C" long bnerv_ans_gaussian_cdf(int32_t min_sym, int32_t max_sym, double mean, double std_, uint32_t* out_cdf, size_t cap) {
+    Table t;
+    if (!gaussian_table(min_sym, max_sym, mean, std_, t)) { bnerv_set_error(BNERV_E_ARG, "ans_gaussian_cdf: bad model (min %d max %d mean %g std %g)", min_sym, max_sym, mean, std_); return -1; }
+    if (out_cdf && cap >= t.cdf.size()) std::copy(t.cdf.begin(), t.cdf.end(), out_cdf);
+    return (long)t.cdf.size();
+}
+
+extern "C" long bnerv_ans_encode_gaussian_runs(const int32_t* symbols, size_t n, int32_t min_sym, int32_t max_sym, double mean, double std_, int run,
+                                               uint32_t* out_words, size_t cap_words, unsigned short* out_run_words) {
+    Table t;
+    if (!symbols && n) { bnerv_set_error(BNERV_E_ARG, "ans_encode_gaussian_runs: null symbols"); return -1; }
+    if (run < 1 || (size_t)run * PREC / 32 + 3 > MAX_RUN_WORDS) { bnerv_set_error(BNERV_E_ARG, "ans_encode_gaussian_runs: run = %d (a run's words must fit 16 bits)", run); return -1; }
+    if (!gaussian_table(min_sym, max_sym, mean, std_, t)) { bnerv_set_error(BNERV_E_ARG, "ans_encode_gaussian_runs: bad model (min %d max %d mean %g std %g)", min_sym, max_sym, mean, std_); return -1; }
+    std::vector<int32_t> idx(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (symbols[i] < min_sym || symbols[i] > max_sym) { bnerv_set_error(BNERV_E_ARG, "ans_encode_gaussian_runs: symbol %d outside [%d, %d]", symbols[i], min_sym, max_sym); return -1; }
+        idx[i] = symbols[i] - min_sym;
+    }
+    // every run through encode() from an empty state, its final state written as two words whatever its size
+    std::vector<uint32_t> msg((size_t)run * PREC / 32 + 3);
+    std::vector<uint32_t> all;
+    all.reserve(n / 3 + 8);
+    size_t k = 0;
+    for (size_t at = 0; at < n; at += (size_t)run, ++k) {
+        const size_t count = n - at < (size_t)run ? n - at : (size_t)run;
+        const long got = encode(t, idx.data() + at, count, msg.data(), msg.size(), true);
+        if (got < 2 || (size_t)got > msg.size()) { bnerv_set_error(BNERV_E_ARG, "ans_encode_gaussian_runs: run %zu takes %ld words (%zu at most)", k, got, msg.size()); return -1; }
+        all.insert(all.end(), msg.begin(), msg.begin() + got);
+        if (out_run_words) out_run_words[k] = (unsigned short)got;
+    }
+    if (out_words && cap_words >= all.size()) std::copy(all.begin(), all.end(), out_words);
+    return (long)all.size();
+}
+
+extern "C" int bnerv_ans_decode_gaussian_runs(const uint32_t* words, size_t n_words, const unsigned short* run_words, size_t n_runs, size_t n,
+                                              int32_t min_sym, int32_t max_sym, double mean, double std_, int run, int32_t* symbols_out) {
+    Table t;
+    BNERV_REQUIRE((words || !n_words) && (symbols_out || !n) && (run_words || !n_runs), "ans_decode_gaussian_runs: null buffer");
+    BNERV_REQUIRE(run >= 1 && n_runs == (n + (size_t)run - 1) / (size_t)run, "ans_decode_gaussian_runs: %zu run lengths for %zu symbols in runs of %d", n_runs, n, run);
+    BNERV_REQUIRE(gaussian_table(min_sym, max_sym, mean, std_, t), "ans_decode_gaussian_runs: bad model");
+    size_t total = 0;
+    for (size_t k = 0; k < n_runs; ++k) total += run_words[k];
+    BNERV_REQUIRE(total == n_words, "ans_decode_gaussian_runs: the run lengths add up to %zu words, the message has %zu", total, n_words);
+    size_t at = 0;
+    for (size_t k = 0; k < n_runs; ++k) {
+        const size_t first = k * (size_t)run, count = n - first < (size_t)run ? n - first : (size_t)run;
+        if (!decode_run(t, words + at, run_words[k], count, symbols_out + first))
+            return bnerv_set_error(BNERV_E_ARG, "ans_decode_gaussian_runs: run %zu (%u words at word %zu) does not decode to %zu symbols under this model",
+                                   k, (unsigned)run_words[k], at, count);
+        for (size_t i = 0; i < count; ++i) symbols_out[first + i] += min_sym;
+        at += run_words[k];
+    }
+    return BNERV_OK;
+}
 
 extern "C" long bnerv_ans_encode_gaussian(const int32_t* symbols, size_t n, int32_t min_sym, int32_t max_sym, double mean, double std_, uint32_t* out, size_t cap_words) {
     Table t;

@@ -67,6 +67,46 @@ def ans_decode_gaussian(words, n, lo, hi, mean, std):
     return out[:n]
 
 
+def ans_gaussian_cdf(lo, hi, mean, std):
+    """The hi - lo + 2 cumulative 24-bit slot counts of the quantised Gaussian on [lo, hi] (uint32 numpy): the one table of the encoders,
+    the host decoders and the device kernel (csrc/rans.hip)."""
+    lib = L.load()
+    need = lib.bnerv_ans_gaussian_cdf(int(lo), int(hi), float(mean), float(std), None, 0)
+    if need < 0:
+        L.check(-1, "bnerv_ans_gaussian_cdf")
+    out = np.empty(need, dtype=np.uint32)
+    assert lib.bnerv_ans_gaussian_cdf(int(lo), int(hi), float(mean), float(std), out.ctypes.data, out.size) == need
+    return out
+
+
+def ans_encode_gaussian_runs(symbols, lo, hi, mean, std, run):
+    """int32 symbols in [lo, hi], cut into runs of `run` that are coded independently ->
+    (uint32 words of all runs back to back, uint16 word count of every run: bulk words + two state words)."""
+    lib = L.load()
+    sym = _i32(symbols)
+    run_words = np.zeros(max((sym.size + int(run) - 1) // max(int(run), 1), 1), dtype=np.uint16)
+    args = (sym.ctypes.data, sym.size, int(lo), int(hi), float(mean), float(std), int(run))
+    need = lib.bnerv_ans_encode_gaussian_runs(*args, None, 0, run_words.ctypes.data)
+    if need < 0:
+        L.check(-1, "bnerv_ans_encode_gaussian_runs")
+    out = np.empty(max(need, 1), dtype=np.uint32)
+    got = lib.bnerv_ans_encode_gaussian_runs(*args, out.ctypes.data, out.size, run_words.ctypes.data)
+    assert got == need
+    return out[:need], run_words[:(sym.size + int(run) - 1) // int(run)]
+
+
+def ans_decode_gaussian_runs(words, run_words, n, lo, hi, mean, std, run):
+    """The inverse of ans_encode_gaussian_runs -> int32 symbols; raises BnervError naming the first run that does not consume exactly its
+    words and end with state 0."""
+    lib = L.load()
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    rw = np.ascontiguousarray(run_words, dtype=np.uint16)
+    out = np.empty(max(int(n), 1), dtype=np.int32)
+    L.check(lib.bnerv_ans_decode_gaussian_runs(w.ctypes.data, w.size, rw.ctypes.data, rw.size, int(n), int(lo), int(hi), float(mean), float(std), int(run),
+                                               out.ctypes.data), "bnerv_ans_decode_gaussian_runs")
+    return out[:n]
+
+
 def ans_encode_categorical(symbols, probs):
     """symbols 0 .. K-1 under probs[K] -> uint32 words."""
     lib = L.load()

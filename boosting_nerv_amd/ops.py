@@ -1023,6 +1023,94 @@ def huff_dequant(words, lengths, items, run=L.HUFF_RUN):
     return [it[0] for it in items]
 
 
+class AnsDequant:
+    """The device side of one chunked CEM payload (rstream.py), ready to launch: the words of all runs (padded by two
+    zero words), the first word of every run, one cumulative table per record (built on the host by bnerv_ans_gaussian_cdf, all uploaded as
+    one array), the item table and the block table -- a block serves up to 64 consecutive runs of one record.
+
+        words      uint32 numpy array: the runs of all items back to back, as they lie in the file
+        items      one (out, scale, lo, hi, mean, std, run_words, beta) per record: out a contiguous fp32 device tensor (any 4-byte alignment),
+                   scale / mean / std floats, [lo, hi] the symbol range (at most 4096 symbols), run_words the uint16 word count of every run,
+                   beta a float or None
+        run        symbols per run: a multiple of 64 in 64..4096
+    Every run's span is validated against the words here, before anything is uploaded.  launch() decodes and de-quantises everything in one
+    kernel; check() reads the device error word (a host sync) and raises ValueError when a run did not consume exactly its words or did not
+    end with an empty state."""
+
+    def __init__(self, words, items, run):
+        import numpy as np
+        from .lib.entropy_model import ans_gaussian_cdf
+        if not items:
+            raise ValueError("ans_dequant: no items")
+        run = int(run)
+        if not L.RANS_MIN_RUN <= run <= L.RANS_MAX_RUN or run % 64:
+            raise ValueError(f"ans_dequant: run = {run} (a multiple of 64 in {L.RANS_MIN_RUN}..{L.RANS_MAX_RUN})")
+        self.run = run
+        words = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        table = np.zeros(len(items), dtype=np.dtype([("out", "<u8"), ("scale", "<f4"), ("beta", "<f4"), ("lo", "<i4"), ("n", "<u4"), ("table", "<u4"),
+                                                     ("alphabet", "<u4"), ("has_beta", "<i4"), ("_pad", "<i4")]))
+        assert table.dtype.itemsize == C.sizeof(L.RansItem)
+        device = items[0][0].device
+        cdfs, lengths, blocks, at_table, at_run = [], [], [], 0, 0
+        for k, (out, scale, lo, hi, mean, std, run_words, beta) in enumerate(items):
+            L.require_device(out, "out")
+            n, lo, hi = out.numel(), int(lo), int(hi)
+            if out.dtype != torch.float32 or not out.is_contiguous() or n == 0 or n >= 2 ** 31 or out.data_ptr() % 4 or out.device != device:
+                raise ValueError(f"ans_dequant: item {k}: out must be a non-empty contiguous 4-byte aligned fp32 tensor on {device} (below 2^31 elements)")
+            if not 2 <= hi - lo + 1 <= L.RANS_MAX_ALPHABET:
+                raise ValueError(f"ans_dequant: item {k}: the symbol range [{lo}, {hi}] has {hi - lo + 1} symbols (2..{L.RANS_MAX_ALPHABET})")
+            rw = np.ascontiguousarray(run_words, dtype=np.uint16).reshape(-1)
+            n_runs = (n + run - 1) // run
+            if rw.size != n_runs:
+                raise ValueError(f"ans_dequant: item {k}: {rw.size} run lengths for {n_runs} runs")
+            if int(rw.min()) < 2:
+                raise ValueError(f"ans_dequant: item {k}: run {int(rw.argmin())} has {int(rw.min())} words, fewer than its two state words")
+            cdf = ans_gaussian_cdf(lo, hi, mean, std)
+            table[k] = (out.data_ptr(), np.float32(scale), np.float32(0.0 if beta is None else beta), lo, n, at_table, cdf.size - 1, int(beta is not None), 0)
+            cdfs.append(cdf)
+            at_table += cdf.size
+            lengths.append(rw)
+            first = np.arange(0, n_runs, 64, dtype=np.uint32)
+            blk = np.zeros((first.size, 4), dtype=np.uint32)
+            blk[:, 0], blk[:, 1], blk[:, 2] = k, at_run + first, first
+            blocks.append(blk)
+            at_run += n_runs
+        lengths = np.concatenate(lengths)
+        starts = np.zeros(lengths.size + 1, dtype=np.uint64)
+        np.cumsum(lengths, dtype=np.uint64, out=starts[1:])
+        if int(starts[-1]) != words.size or words.size + 2 >= 2 ** 32:
+            raise ValueError(f"ans_dequant: the run lengths add up to {int(starts[-1])} words, the payload has {words.size}")
+        padded = np.zeros(words.size + 2, dtype=np.uint32)       # (every run's span ends at or before words.size: validated just above)
+        padded[:words.size] = words
+        blocks = np.concatenate(blocks)
+        assert blocks.dtype.itemsize * 4 == C.sizeof(L.RansBlock)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(device)      # noqa: E731
+        self.words, self.starts, self.blocks, self.items, self.tables = up(padded), up(starts.astype(np.uint32)), up(blocks), up(table), up(np.concatenate(cdfs))
+        self.n_words, self.n_runs, self.n_blocks, self.n_items, self.n_table_words = padded.size, int(lengths.size), int(blocks.shape[0]), len(items), at_table
+        self.err = torch.zeros(1, dtype=torch.int32, device=device)
+        self._keep = [it[0] for it in items]
+
+    def launch(self):
+        L.check(L.load().bnerv_rans_dequant(L.stream(), L.ptr(self.words), self.n_words, L.ptr(self.starts), self.n_runs, L.ptr(self.blocks), self.n_blocks,
+                                            L.ptr(self.items), self.n_items, L.ptr(self.tables), self.n_table_words, self.run, L.ptr(self.err)), "bnerv_rans_dequant")
+        return self
+
+    def check(self):
+        e = int(self.err.item())
+        if e != 0:
+            raise ValueError("ans_dequant: " + ("a descriptor points outside the uploaded arrays" if e & 2 else
+                                                "a run did not consume exactly its words and end with an empty state (the payload does not match its run index)"))
+        return self
+
+
+def ans_dequant(words, items, run):
+    """Range-ANS-decode the runs of a chunked CEM payload and de-quantise them into the items' `out` tensors IN PLACE, one launch:
+    out[i] = float(symbol) * scale (+ beta), product and sum one fp32 operation each -- Scale_T's and ScaleBeta_T's expressions, bit for bit.
+    Arguments: AnsDequant.  Raises ValueError when the device reports a run that did not decode."""
+    AnsDequant(words, items, run).launch().check()
+    return [it[0] for it in items]
+
+
 def frame_to_u8(x, out=None):
     """[B, 3, H, W] fp32 -> [B, H, W, 3] uint8 = (x.clamp(0, 1) * 255 + 0.5).to(uint8).permute(0, 2, 3, 1) in one pass (the image
     convention of train_nerv_all._save_images).  out: a contiguous uint8 buffer to write into (a captured decode's)."""

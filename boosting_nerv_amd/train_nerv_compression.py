@@ -45,6 +45,8 @@ def build_parser():
     add('--target_bit', type=float, default=5)
     add('--lambda_rate', type=float, default=0.2)
     add('--bitstream', type=str, default=None, help='write the final evaluation\'s coded model (and embeddings) to this file (codec.py decodes it)')
+    add('--bitstream_run', type=int, default=0, help='0: --bitstream writes the version-1 file; N > 0 (a multiple of 64 in 64..4096): the chunked kind, '
+                                                      'coded in independent runs of N symbols that the decoder entropy-decodes on the GPU')
     return p
 
 
@@ -308,8 +310,8 @@ def evaluate(model, full_dataloader, local_rank, args, dump_vis=False, coding=Fa
                  f'target_bpp:{round(args.target_bpp, 6)} \n', every_rank=False)
         if write_bitstream and getattr(args, 'bitstream', None) and local_rank in (0, None):
             from . import codec
-            args.bitstream_budget = codec.encode(model, entropy_model, args, full_dataloader, args.bitstream)
-            log.line(f'Bitstream {args.bitstream}: {codec.describe(args.bitstream_budget)} \n', every_rank=False)
+            args.bitstream_budget = codec.encode(model, entropy_model, args, full_dataloader, args.bitstream, run=getattr(args, 'bitstream_run', 0))
+            log.line(f'Bitstream {args.bitstream}: {codec.describe_any(args.bitstream_budget)} \n', every_rank=False)
     return values, hw
 
 

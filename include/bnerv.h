@@ -419,6 +419,44 @@ long bnerv_ans_encode_categorical(const int32_t* symbols, size_t n, const double
 int bnerv_ans_decode_categorical(const uint32_t* words, size_t n_words, size_t n, const double* probs, int K, int32_t* symbols_out);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * The same coder in independent runs (additive to ABI 9; csrc/ans.cpp on the host, csrc/rans.hip on the device;
+ * boosting_nerv_amd/rstream.py).
+ *
+ * The n symbols of a record are cut into runs of `run` symbols (the last may be shorter).  Every run is a message of its own, coded from
+ * an empty state under the record's one table: its bulk words in refill order, then its final state as EXACTLY two words (low, high; the
+ * high word may be zero), so a decoder knows where the state lies without trying.  The messages of the runs lie back to back;
+ * run_words[k] is the word count of run k (>= 2; <= 65535, which bounds `run`: 24 bits per symbol at most).
+ *   bnerv_ans_gaussian_cdf          the max_sym - min_sym + 2 cumulative 24-bit slot counts of the quantised Gaussian (symbol i owns
+ *                                   [cdf[i], cdf[i + 1])): the one table of the encoders, the host decoders and the device kernel.  Returns
+ *                                   the entry count (also when out_cdf == NULL or cap is too small: nothing is written then), -1 on a bad model.
+ *   bnerv_ans_encode_gaussian_runs  -> the total word count (also when out_words == NULL or cap_words is too small: no word is written
+ *                                   then); out_run_words (may be NULL) takes ceil(n / run) counts either way; -1 on a bad argument.
+ *   bnerv_ans_decode_gaussian_runs  the inverse, run by run, each from its own span of `words`: a run is valid when it consumes exactly its
+ *                                   bulk words and ends with state 0; otherwise an error that names the run.  Never reads outside a run's span.
+ *   bnerv_rans_dequant  (device)    ONE launch.  A block is one wave and serves up to 64 consecutive runs of ONE record: it stages that
+ *                                   record's table (with a first-level table on the top 8 bits of a slot) and its runs' words in LDS, lane k decodes run blocks[b].run + k sequentially, and the
+ *                                   wave writes  out[i] = float(lo + index) * scale (+ beta, when the item has one)  -- product and sum one
+ *                                   fp32 operation each -- with consecutive lanes on consecutive elements.  `words`: the device copy of all
+ *                                   runs back to back followed by two zero words (n_words counts them); `run_start`: n_runs + 1 device
+ *                                   entries, the first word of every run and the end of the last; `blocks`, `items`, `tables` (all tables
+ *                                   back to back, items[k].table = offset of its first entry): device arrays.  A run that does not consume
+ *                                   exactly its words or does not end with state 0 sets bit 0 of *err (device int); a descriptor that
+ *                                   points outside `words` or `tables` sets bit 1 and nothing of its block is decoded. */
+#define BNERV_RANS_MAX_ALPHABET 4096
+#define BNERV_RANS_MIN_RUN 64
+#define BNERV_RANS_MAX_RUN 4096
+typedef struct { unsigned item; unsigned run; unsigned first; unsigned _pad; } bnerv_rans_block;   /* run: global index of the block's first run; first: that run's index within its item */
+typedef struct { float* out; float scale; float beta; int lo; unsigned n; unsigned table; unsigned alphabet; int has_beta; int _pad; } bnerv_rans_item;
+long bnerv_ans_gaussian_cdf(int32_t min_sym, int32_t max_sym, double mean, double std, uint32_t* out_cdf, size_t cap);
+long bnerv_ans_encode_gaussian_runs(const int32_t* symbols, size_t n, int32_t min_sym, int32_t max_sym, double mean, double std, int run,
+                                    uint32_t* out_words, size_t cap_words, unsigned short* out_run_words);
+int bnerv_ans_decode_gaussian_runs(const uint32_t* words, size_t n_words, const unsigned short* run_words, size_t n_runs, size_t n,
+                                   int32_t min_sym, int32_t max_sym, double mean, double std, int run, int32_t* symbols_out);
+int bnerv_rans_dequant(void* stream, const uint32_t* words, size_t n_words, const uint32_t* run_start, size_t n_runs,
+                       const bnerv_rans_block* blocks, size_t n_blocks, const bnerv_rans_item* items, int n_items,
+                       const uint32_t* tables, size_t n_table_words, int run, int* err);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Huffman coder of the post-hoc quantised model (additive to ABI 9; csrc/huff.cpp on the host, csrc/huff.hip on the device;
  * boosting_nerv_amd/qstream.py).
  *

@@ -18,7 +18,11 @@ depend on what the weights say.
 --bitstream --posthoc times the file of the regression path instead (qstream.py) on the C1 model as train_nerv_all builds
 it: quant_model -> codec.encode_posthoc, then (1) as above -- here the coded bytes go up as they lie in the file and ONE kernel decodes and
 de-quantises them -- and the decode kernel alone under HIP events (ops.HuffDequant.launch, tables already on the device; 20 launches replayed from a graph).
-usage: python tools/kdecode.py --bitstream [--posthoc] [--frames 16] [--rounds 3] [--only c1q|c5|pack]   (needs the GPU)"""
+--bitstream --chunked compares the two kinds of CEM file of ONE model (c1q, c5): the version-1 file, whose records the host
+rANS-decodes, against the chunked file (rstream.py) repacked from it at runs of 256 and 1024, whose words ONE kernel decodes.  (1) as above
+for every file, the kinds alternated in one process, eager and graph; the decode launch alone under HIP events (ops.AnsDequant.launch, tables
+already on the device; 50 launches replayed from a graph); every file's size and the chunked overhead in bits per symbol.
+usage: python tools/kdecode.py --bitstream [--posthoc|--chunked] [--frames 16] [--rounds 3] [--only c1q|c5|pack]   (needs the GPU)"""
 import argparse
 import io
 import os
@@ -212,6 +216,89 @@ def run_posthoc(n_frames, rounds):
           f"{coded / best / 1e3:.2f} GB/s of coded bytes in, {4 * budget['n_symbols'] / best / 1e3:.1f} GB/s of fp32 out)")
 
 
+def run_chunked(case, n_frames, rounds):
+    import torch
+    from boosting_nerv_amd import bitstream, codec, ops, rstream
+    from boosting_nerv_amd.lib.entropy_model import DiffEntropyModel
+    from boosting_nerv_amd.synth import SyntheticVideo
+    dev = torch.device("cuda:0")
+    args, model = build(case)
+    model = model.to(dev)
+    model.init_data()
+    h, w = (int(v) for v in args.crop_list.split("_")[:2])
+    frames = None
+    if args.model == "HNeRV_Boost":
+        vid = SyntheticVideo(n_frames, h, w)
+        frames = torch.stack([vid.frame(i, device=dev) for i in range(n_frames)])
+        with torch.no_grad():
+            model.embed_quantizer.init_data(model.forward_encoder(frames[0:1]))
+    args.full_data_length = n_frames
+    buf = io.BytesIO()
+    v1 = codec.encode(model, DiffEntropyModel("gaussian"), args, frames, buf)
+    del model
+    files = {"version 1": buf.getvalue()}
+    print(f"{case}: {args.model} {h}x{w}, {n_frames} frames; version-1 file {codec.describe(v1)}", flush=True)
+    for run in (256, 1024):
+        out = io.BytesIO()
+        t0 = time.time()
+        b = codec.repack(files["version 1"], out, run)
+        files[f"chunked {run}"] = out.getvalue()
+        extra = b["ans_words"] + b["run_index"] + b["padding"] - v1["coded_words"] - 32 * (b["n_tensors"] + b["n_embeds"])      # (a version-1 record carries its word count)
+        print(f"{case} chunked, run {run}: repack {time.time() - t0:.2f} s on the host; file {codec.describe_chunked(b)}; {b['bytes'] - v1['bytes']:+d} bytes "
+              f"against version 1 ({100.0 * (b['bytes'] - v1['bytes']) / v1['bytes']:+.2f} %), {extra / b['n_symbols']:.4f} bits per symbol for cutting "
+              f"({(b['ans_words'] - v1['coded_words']) / b['n_symbols']:.4f} in the words, {b['run_index'] / b['n_symbols']:.4f} in the run index)", flush=True)
+
+    # (1) model-ready, the kinds alternated
+    first = {}
+    for label, blob in files.items():                          # (code objects, lazily built tables: the first construction of each kind apart)
+        torch.cuda.synchronize()
+        t0 = time.time()
+        dec = codec.Decoder(blob, dev, use_graph=False)
+        torch.cuda.synchronize()
+        first[label] = time.time() - t0
+        print(f"{case} model-ready, first construction, {label}: {first[label] * 1e3:.1f} ms", flush=True)
+    ready = {}
+    for r in range(max(rounds, 3)):
+        for use_graph in (False, True):
+            for label, blob in files.items():
+                t0 = time.time()
+                (bitstream if label == "version 1" else rstream).read(blob)
+                t_read = time.time() - t0
+                dec = None                                     # (the previous decoder is released outside the timed window)
+                torch.cuda.synchronize()
+                t0 = time.time()
+                dec = codec.Decoder(blob, dev, use_graph=use_graph)
+                torch.cuda.synchronize()
+                key = (label, "graph" if use_graph else "eager")
+                ready.setdefault(key, []).append((time.time() - t0, t_read))
+                print(f"{case} round {r} model-ready, {key[1]}, {label}: {ready[key][-1][0] * 1e3:.1f} ms (container parse + CRC alone: {t_read * 1e3:.1f} ms)", flush=True)
+    ref = codec.Decoder(files["version 1"], dev, use_graph=False)
+    for label, blob in files.items():
+        d = codec.Decoder(blob, dev, use_graph=False)
+        assert all(torch.equal(d.decode_f32(i), ref.decode_f32(i)) for i in (0, n_frames - 1)), label
+    for mode in ("eager", "graph"):
+        base = min(t for t, _ in ready[("version 1", mode)])
+        for label in files:
+            v = [t for t, _ in ready[(label, mode)]]
+            print(f"{case} model-ready, {mode}, {label}: {min(v) * 1e3:.1f} ms best, {max(v) * 1e3:.1f} worst of {len(v)} (version 1 / this = {base / min(v):.2f})")
+
+    # the decode launch alone: the same tables, outputs of its own
+    for run in (256, 1024):
+        rs = rstream.read(files[f"chunked {run}"])
+        items = [(torch.empty(r.count, device=dev), float(r.scale), r.lo, r.hi, float(r.mean), float(r.std), r.run_words, None if r.beta is None else float(r.beta))
+                 for r in rs.tensors + rs.embeds]
+        t0 = time.time()
+        plan = ops.AnsDequant(rs.words, items, run)
+        t_plan = time.time() - t0
+        plan.launch().check()
+        (best, worst), = time_graph([plan.launch], reps=50, rounds=max(rounds, 3))
+        plan.check()
+        n_sym = sum(r.count for r in rs.tensors + rs.embeds)
+        print(f"{case} decode launch, run {run}: {best:.1f} us best, {worst:.1f} worst per launch ({plan.n_runs} runs in {plan.n_blocks} blocks, "
+              f"{n_sym / best:.0f} symbols/us, {4 * rs.words.size / best / 1e3:.2f} GB/s of words in, {4 * n_sym / best / 1e3:.1f} GB/s of fp32 out); "
+              f"tables, descriptors and uploads on the host: {t_plan * 1e3:.1f} ms")
+
+
 def forward_rates(cfg):
     """Decode (forward-only) rate of a bench.py decoder (c1 | c3 | c4) on the HIP path: frames/s for single-frame decodes under
     torch.no_grad(), eager and as a captured hipGraph (N4 row: the figure the reference logs as "FPS" in evaluate())."""
@@ -262,6 +349,7 @@ def main():
     ap.add_argument("cfg", nargs="?", default="c1", help="without --bitstream: the bench.py recipe whose forward-only rate is measured")
     ap.add_argument("--bitstream", action="store_true", help="time the bitstream decoder instead")
     ap.add_argument("--posthoc", action="store_true", help="with --bitstream: the post-hoc quantised file of the regression path (C1 model)")
+    ap.add_argument("--chunked", action="store_true", help="with --bitstream: the version-1 CEM file against the chunked file of the same model (c1q, c5)")
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--only", choices=["c1q", "c5", "pack"], default=None)
@@ -273,6 +361,10 @@ def main():
         return 0
     if a.posthoc:
         run_posthoc(a.frames, a.rounds)
+        return 0
+    if a.chunked:
+        for case in ([a.only] if a.only else ["c1q", "c5"]):
+            run_chunked(case, a.frames, a.rounds)
         return 0
     for case in ([a.only] if a.only else ["c1q", "c5", "pack"]):
         if case == "pack":
