@@ -142,6 +142,21 @@ class RansItem(C.Structure):       # bnerv_rans_item
                 ("has_beta", C.c_int), ("_pad", C.c_int)]
 
 
+HIST_SLICE = 16384      # BNERV_HIST_SLICE
+
+
+class HistItem(C.Structure):       # bnerv_hist_item
+    _fields_ = [("sym", _fp), ("n", C.c_uint32), ("lo", C.c_int), ("alphabet", C.c_uint32), ("out", C.c_uint32)]
+
+
+class RencItem(C.Structure):       # bnerv_renc_item
+    _fields_ = [("sym", _fp), ("n", C.c_uint32), ("lo", C.c_int), ("alphabet", C.c_uint32), ("table", C.c_uint32)]
+
+
+class RansCopy(C.Structure):       # bnerv_rans_copy
+    _fields_ = [("slot", C.c_uint32), ("dst", C.c_uint32), ("count", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class YuvCoeffs(C.Structure):      # bnerv_yuv_coeffs: what yuvio.coefficients() computed in float64, rounded to fp32
     _fields_ = [("m", C.c_float * 9), ("off", C.c_float * 3), ("scale", C.c_float * 3), ("maxcode", C.c_float)]
 
@@ -211,6 +226,12 @@ SYMBOLS = {
     "bnerv_ans_encode_gaussian_runs": (C.c_long, [_V, _Z, _I, _I, C.c_double, C.c_double, _I, _V, _Z, _V]),
     "bnerv_ans_decode_gaussian_runs": (_I, [_V, _Z, _V, _Z, _Z, _I, _I, C.c_double, C.c_double, _I, _V]),
     "bnerv_rans_dequant": (_I, [_V, _V, _Z, _V, _Z, _V, _Z, _V, _I, _V, _Z, _I, _V]),
+    "bnerv_ans_counts_cdf": (C.c_long, [_V, _I, _V, _Z]),
+    "bnerv_ans_encode_table_runs": (C.c_long, [_V, _Z, _I, _V, _I, _I, _V, _Z, _V]),
+    "bnerv_ans_decode_table_runs": (_I, [_V, _Z, _V, _Z, _Z, _I, _V, _I, _I, _V]),
+    "bnerv_sym_hist": (_I, [_V, _V, _I, _V, _Z, _V, _Z, _V]),
+    "bnerv_rans_encode": (_I, [_V, _V, _Z, _V, _I, _V, _Z, _I, _V, _Z, _V, _V]),
+    "bnerv_rans_compact": (_I, [_V, _V, _Z, _I, _V, _Z, _V, _Z, _V]),
     "bnerv_huff_encode": (C.c_long, [_V, _V, _I, _V, _I, _V, _Z, _V, _Z]),
     "bnerv_huff_decode": (_I, [_V, _Z, _V, _Z, _V, _I, _V, _I, _V]),
     "bnerv_huff_dequant": (_I, [_V, _V, _Z, _V, _Z, _V, _I, _V, _I, _V]),

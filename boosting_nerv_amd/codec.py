@@ -20,7 +20,14 @@ A CEM file also comes in a chunked kind (rstream.py) whose re
 independently: encode(..., run=N) or repack() writes it, and Decoder uploads its words as they lie in the file and lets ONE kernel
 (ops.ans_dequant) entropy-decode and de-quantise them -- no entropy decode on the host.  Every command above works on all three kinds.
 
-    python -m boosting_nerv_amd.codec repack in.bnrv out.bnrc [--run N]"""
+    python -m boosting_nerv_amd.codec repack in.bnrv out.bnrc [--run N]
+
+The chunked kind has a second form (estream.py) in which every record is coded under the Gaussian or under a table of its own
+symbol frequencies, whichever makes the file smaller: encode(..., run=N, tables="empirical") codes it on the device -- one histogram
+launch, one encode launch over both tables of every record, one compaction -- and repack(..., tables="empirical") makes the same bytes on
+the host.  Decoder launches the same decode kernel on it, with the tables the file carries.
+
+    python -m boosting_nerv_amd.codec repack in.bnrv out.bnre [--run N] --tables empirical"""
 import argparse
 import builtins
 import json
@@ -30,8 +37,10 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import bitstream, qstream, rstream
+from . import bitstream, estream, qstream, rstream
 from .bitstream import Record
+
+TABLES = ("gaussian", "empirical")
 
 # the settings the model constructors read (model_nerv.py, model_hnerv.py, model_enerv.py, model_blocks.py), resolved: fc_dim after the size
 # solver, enc_dim after its rewrite -- the architecture rows of args.yaml
@@ -161,7 +170,7 @@ def _frames_in_order(frames_or_loader, args, device):
 
 
 @torch.no_grad()
-def encode(model, entropy_model, args, frames_or_loader, path, run=0):
+def encode(model, entropy_model, args, frames_or_loader, path, run=0, tables="gaussian"):
     """Write the model (and, for HNeRV_Boost, every frame's embedding) as a bitstream to `path` (a file name or a binary file object);
     returns bitstream.info of what was written.
 
@@ -170,7 +179,16 @@ def encode(model, entropy_model, args, frames_or_loader, path, run=0):
     the coded words of the file are get_bitrate_sum("real_bitrate") plus, with one frame per evaluation batch, the embedding bits.
 
     run > 0 writes the chunked kind instead (rstream.py: runs of `run` symbols, decoded on the device): the version-1 file is encoded into a
-    buffer and repacked, so its symbols and side information are the same by construction; returns rstream.info then."""
+    buffer and repacked, so its symbols and side information are the same by construction; returns rstream.info then.
+
+    tables="empirical" (with run > 0) writes the chunked kind with per-record tables (estream.py) and codes it on the device: the symbols
+    never leave it, no version-1 message is built; returns estream.info then."""
+    if tables not in TABLES:
+        raise ValueError(f"codec.encode: tables = {tables!r} ({' | '.join(TABLES)})")
+    if tables == "empirical":
+        if not run:
+            raise ValueError("codec.encode: tables='empirical' needs run > 0 (only the chunked kind carries tables)")
+        return _encode_empirical(model, entropy_model, args, frames_or_loader, path, rstream.check_run(run))
     if run:
         import io
         rstream.check_run(run)
@@ -198,13 +216,7 @@ def encode(model, entropy_model, args, frames_or_loader, path, run=0):
                 raise ValueError(f"codec.encode: the loader delivered frames {sorted(embeds)[:4]}... of a {n_frames}-frame clip (a sharded loader?)")
     finally:
         model.train(was_training)
-    if frame_hw is None:
-        if hasattr(args, "crop_list"):
-            frame_hw = tuple(int(v) for v in args.crop_list.split("_")[:2])
-        elif torch.is_tensor(frames_or_loader):
-            frame_hw = tuple(frames_or_loader.shape[-2:])
-        else:
-            raise ValueError("codec.encode: the frame size is unknown (no args.crop_list and no frame tensor)")
+    frame_hw = _frame_hw(args, frames_or_loader, frame_hw)
     sd = model.state_dict()
     raw = [sd[k].detach().float().reshape(-1).cpu().numpy() for k in _raw_keys(model, is_hnerv)]
     bitstream.write(path, _settings(args, n_frames, frame_hw), tensors, [embeds[i] for i in range(n_frames)] if is_hnerv else [], embed_shape, raw)
@@ -213,13 +225,166 @@ def encode(model, entropy_model, args, frames_or_loader, path, run=0):
     return bitstream.info(path) if not hasattr(path, "write") else None
 
 
-def repack(src, dst, run=1024):
+def _frame_hw(args, frames_or_loader, seen):
+    if seen is not None:
+        return seen
+    if hasattr(args, "crop_list"):
+        return tuple(int(v) for v in args.crop_list.split("_")[:2])
+    if torch.is_tensor(frames_or_loader):
+        return tuple(frames_or_loader.shape[-2:])
+    raise ValueError("codec.encode: the frame size is unknown (no args.crop_list and no frame tensor)")
+
+
+def _write_blob(dst, blob):
+    if hasattr(dst, "write"):
+        dst.write(blob)
+    else:
+        with open(dst, "wb") as f:
+            f.write(blob)
+
+
+def _too_wide(who, lo, hi):
+    if hi - lo + 1 > rstream.MAX_ALPHABET:
+        raise NotImplementedError(f"{who}: a record's symbols span [{lo}, {hi}]: {hi - lo + 1} values; the chunked kind carries "
+                                  f"{rstream.MAX_ALPHABET} (the device decoder holds a record's table in LDS)")
+
+
+def _empirical_record(side, cdf, n_words, run_words):
+    """The choice rule of the file with per-record tables, one place for the host and the device path: the record
+    under the model with fewer bits, its words plus its own side bytes (mean and std, or the LEB128 table); a tie goes to the Gaussian.
+    side: (count, scale, mean, std, lo, hi, beta); cdf: the cumulative table of the record's histogram (ans_counts_cdf); n_words /
+    run_words: (Gaussian, table) totals and per-run word counts.  -> (ERecord, 0 | 1: which of the two was taken)."""
+    count, scale, mean, std, lo, hi, beta = side
+    freq = np.diff(cdf.astype(np.int64)).astype(np.uint32)
+    take = int(32 * n_words[1] + 8 * len(estream.table_bytes(freq)) < 32 * n_words[0] + 64)
+    if take:
+        return estream.ERecord(count, scale, lo, hi, estream.TABLE, None, None, freq, run_words[1], beta), 1
+    return estream.ERecord(count, scale, lo, hi, estream.GAUSSIAN, mean, std, None, run_words[0], beta), 0
+
+
+@torch.no_grad()
+def _encode_empirical(model, entropy_model, args, frames_or_loader, path, run):
+    """encode(..., run, tables="empirical"): the symbols stay on the device.  Every quantiser called once for its symbols, the moments of the
+    evaluation pass evaluate() accounts with (fused or tensor by tensor), the embeddings frame by frame as encode() makes them, ONE host copy of every record's (mean, std, scale,
+    beta) and symbol range, then: histogram launch -> counts to the host -> both tables per record -> ONE encode launch over both -> the
+    choice per record -> compaction -> one copy of the words."""
+    from . import ops
+    from .lib.entropy_model import ans_counts_cdf, ans_gaussian_cdf
+    _check_supported(model, entropy_model, args)
+    device = next(model.parameters()).device
+    n_frames, frames = _frames_in_order(frames_or_loader, args, device)
+    is_hnerv = args.model == "HNeRV_Boost"
+    was_training = model.training
+    model.eval()
+    try:
+        tensors, scales, codes, symbols = [], [], [], []
+        for m in model._quant_modules():
+            for kind in ("weight", "bias"):
+                if getattr(m, kind) is not None:
+                    quantizer = getattr(m, f"{kind}_quantizer")
+                    code, quant, _ = quantizer(getattr(m, kind).detach())
+                    tensors.append(getattr(m, kind).detach())
+                    scales.append(quantizer.scale.detach())
+                    codes.append(code)
+                    symbols.append(quant.detach().to(torch.int32).reshape(-1))
+        # the moments evaluate() accounts with, by the switch _tensor_records honours: the fused pass's, or cal_global_bitrate's
+        if os.environ.get("BNERV_CEM_EVAL_FUSED", "1") != "0" and getattr(model, "cem_fused", True):
+            _, stats, _ = ops.cem_scale_rate(tensors, scales, [None] * len(tensors), False)
+            means, stds = list(stats[:, 1]), list(stats[:, 2])
+        else:
+            means, stds = [torch.mean(c) for c in codes], [torch.std(c) for c in codes]
+        del codes
+        scales = [s.reshape(()) for s in scales]
+        n_tensors, embeds, embed_shape, frame_hw = len(tensors), {}, None, None
+        if is_hnerv:
+            transform = getattr(args, "transform_func", None)
+            for i, frame in frames:
+                img_in = frame if transform is None else transform(frame, torch.as_tensor([i], device=device))[0]
+                code, sym, _ = model.forward_embed_quant(model.forward_encoder(img_in))
+                embeds[i] = (sym.detach().to(torch.int32).reshape(-1), torch.mean(code), torch.std(code))
+                embed_shape, frame_hw = tuple(code.shape[1:]), tuple(frame.shape[-2:])
+            if sorted(embeds) != list(range(n_frames)):
+                raise ValueError(f"codec.encode: the loader delivered frames {sorted(embeds)[:4]}... of a {n_frames}-frame clip (a sharded loader?)")
+            for i in range(n_frames):
+                symbols.append(embeds[i][0])
+                means.append(embeds[i][1])
+                stds.append(embeds[i][2])
+                scales.append(model.embed_quantizer.scale.detach().reshape(()))
+    finally:
+        model.train(was_training)
+    n_rec = len(symbols)
+    beta = model.embed_quantizer.beta.detach().reshape(()).float() if is_hnerv else torch.zeros((), device=device)
+    side_h = torch.stack([v.float() for v in means + stds + scales] + [beta]).cpu().numpy()
+    range_h = torch.stack([s.min() for s in symbols] + [s.max() for s in symbols]).cpu().numpy()
+    sides = []
+    for k in range(n_rec):
+        lo, hi = int(range_h[k]), int(range_h[n_rec + k])
+        hi = hi if hi > lo else lo + 1
+        _too_wide("codec.encode", lo, hi)
+        std = np.float32(np.clip(side_h[n_rec + k], np.float32(1e-5), np.float32(1e10)))      # (compress_matrix_flatten_gaussian_global's clamp)
+        sides.append((int(symbols[k].numel()), np.float32(side_h[2 * n_rec + k]), np.float32(side_h[k]), std, lo, hi,
+                      np.float32(side_h[-1]) if k >= n_tensors else None))
+    counts = ops.SymHist([(s, r[4], r[5] - r[4] + 1) for s, r in zip(symbols, sides)]).launch().check().host()
+    items = []
+    for s, r, c in zip(symbols, sides, counts):
+        items += [(s, r[4], ans_gaussian_cdf(r[4], r[5], float(r[2]), float(r[3]))), (s, r[4], ans_counts_cdf(c))]
+    enc = ops.AnsEncodeRuns(items, run).launch().check()
+    run_words = enc.run_words()
+    records, chosen = [], []
+    for k, r in enumerate(sides):
+        rw = (run_words[2 * k], run_words[2 * k + 1])
+        rec, take = _empirical_record(r, items[2 * k + 1][2], [int(w.sum(dtype=np.uint64)) for w in rw], rw)
+        records.append(rec)
+        chosen.append(2 * k + take)
+    words = enc.compact(chosen, run_words).launch().check().host()
+    frame_hw = _frame_hw(args, frames_or_loader, frame_hw)
+    sd = model.state_dict()
+    raw = [sd[k].detach().float().reshape(-1).cpu().numpy() for k in _raw_keys(model, is_hnerv)]
+    settings = dict(_settings(args, n_frames, frame_hw), ans_run=run, ans_tables="empirical")
+    blob = estream.to_bytes(settings, records[:n_tensors], records[n_tensors:], embed_shape, raw, words)
+    _write_blob(path, blob)
+    return estream.info(blob)
+
+
+def _repack_empirical(src, dst, run):
+    """repack(..., tables="empirical"): the host oracle of _encode_empirical -- the same tables, the same coder arithmetic (csrc/ans.cpp), the
+    same choice rule, from the symbols of a version-1 or a chunked file."""
+    from .lib.entropy_model import ans_counts_cdf, ans_decode_gaussian, ans_encode_table_runs, ans_gaussian_cdf
+    chunked = qstream.magic_of(src) == rstream.MAGIC
+    bs = rstream.read(src) if chunked else bitstream.read(src)
+    settings = dict(bs.settings, ans_run=run, ans_tables="empirical")
+    words = []
+
+    def chunk(k, r):
+        _too_wide("codec.repack", r.lo, r.hi)
+        sym = rstream.decode_record(bs, k) if chunked else ans_decode_gaussian(r.words, r.count, r.lo, r.hi, float(r.mean), float(r.std))
+        cdfs = (ans_gaussian_cdf(r.lo, r.hi, float(r.mean), float(r.std)), ans_counts_cdf(np.bincount(sym - r.lo, minlength=r.hi - r.lo + 1)))
+        coded = [ans_encode_table_runs(sym, r.lo, cdf, run) for cdf in cdfs]
+        rec, take = _empirical_record((r.count, r.scale, r.mean, r.std, r.lo, r.hi, r.beta), cdfs[1], [w.size for w, _ in coded], [rw for _, rw in coded])
+        words.append(coded[take][0])
+        return rec
+
+    tensors = [chunk(k, r) for k, r in enumerate(bs.tensors)]
+    embeds = [chunk(len(tensors) + k, r) for k, r in enumerate(bs.embeds)]
+    blob = estream.to_bytes(settings, tensors, embeds, bs.embed_shape, bs.raw, np.concatenate(words) if words else np.zeros(0, dtype=np.uint32))
+    _write_blob(dst, blob)
+    return estream.info(blob)
+
+
+def repack(src, dst, run=1024, tables="gaussian"):
     """A version-1 CEM file `src` (a file name, a binary file object or bytes) as the chunked kind `dst` (a file name or a binary file
     object): every record rANS-decoded on the host and re-encoded in independent runs of `run` symbols under the same Gaussian.  Header
     settings (plus "ans_run"), record order, side values and the raw section are copied.  Host only: no GPU, no retraining.  Returns
-    rstream.info of what was written."""
+    rstream.info of what was written.
+
+    tables="empirical": the chunked kind with per-record tables instead (estream.py) -- every record under its Gaussian or under the table
+    of its own histogram, whichever is smaller; `src` may then be a chunked file as well.  Returns estream.info."""
     from .lib.entropy_model import ans_decode_gaussian, ans_encode_gaussian_runs
     run = rstream.check_run(run)
+    if tables not in TABLES:
+        raise ValueError(f"codec.repack: tables = {tables!r} ({' | '.join(TABLES)})")
+    if tables == "empirical":
+        return _repack_empirical(src, dst, run)
     bs = bitstream.read(src)
     settings = dict(bs.settings)
     settings["ans_run"] = run
@@ -237,11 +402,7 @@ def repack(src, dst, run=1024):
     tensors = [chunk(r) for r in bs.tensors]
     embeds = [chunk(r) for r in bs.embeds]
     blob = rstream.to_bytes(settings, tensors, embeds, bs.embed_shape, bs.raw, np.concatenate(words) if words else np.zeros(0, dtype=np.uint32))
-    if hasattr(dst, "write"):
-        dst.write(blob)
-    else:
-        with open(dst, "wb") as f:
-            f.write(blob)
+    _write_blob(dst, blob)
     return rstream.info(blob)
 
 
@@ -253,15 +414,26 @@ def describe_chunked(budget):
             f"+ padding {budget['padding']}")
 
 
+def describe_empirical(budget):
+    """One line of an estream.info budget (the log of train_nerv_compression --bitstream_tables empirical, `codec info`)."""
+    return (f"{budget['bytes']} bytes = {budget['total']} bits: ANS words {budget['ans_words']} ({budget['n_symbols']} symbols in {budget['n_runs']} runs of "
+            f"{budget['ans_run']}) + run index {budget['run_index']} + tables {budget['tables']} ({budget['n_table_records']} records under their own table, "
+            f"{budget['n_gaussian_records']} under a Gaussian) + per-tensor side {budget['tensor_side']} ({budget['n_tensors']} tensors) + embedding side "
+            f"{budget['embed_side']} ({budget['n_embeds']} frames) + raw fp32 {budget['raw']} ({budget['n_raw']} entries) + header {budget['header']} "
+            f"+ padding {budget['padding']}")
+
+
 def describe_any(budget):
-    """describe, describe_posthoc or describe_chunked, by the budget's items."""
+    """describe, describe_posthoc, describe_chunked or describe_empirical, by the budget's items."""
+    if "tables" in budget:
+        return describe_empirical(budget)
     return describe_chunked(budget) if "ans_words" in budget else describe_posthoc(budget) if "symbol_bits" in budget else describe(budget)
 
 
 def info(path_or_buffer):
-    """The bit budget of a file of any of the three kinds (bitstream.info, qstream.info or rstream.info, by the magic number)."""
+    """The bit budget of a file of any kind (bitstream.info, qstream.info, rstream.info or estream.info, by the magic number)."""
     magic = qstream.magic_of(path_or_buffer)
-    return (qstream.info if magic == qstream.MAGIC else rstream.info if magic == rstream.MAGIC else bitstream.info)(path_or_buffer)
+    return {qstream.MAGIC: qstream.info, rstream.MAGIC: rstream.info, estream.MAGIC: estream.info}.get(magic, bitstream.info)(path_or_buffer)
 
 
 def describe(budget):
@@ -389,12 +561,12 @@ class Decoder:
         from .lib.entropy_model import ans_decode_gaussian
         from .train_nerv_all import build_model
         magic = qstream.magic_of(path)
-        self.kind = "posthoc" if magic == qstream.MAGIC else "chunked" if magic == rstream.MAGIC else "cem"
+        self.kind = {qstream.MAGIC: "posthoc", rstream.MAGIC: "chunked", estream.MAGIC: "empirical"}.get(magic, "cem")
         if self.kind == "posthoc":
             self._load_posthoc(path, device)
             return self._frame_loop(use_graph, pack, matrix, range)
-        bs = rstream.read(path) if self.kind == "chunked" else bitstream.read(path)
-        what = "rstream" if self.kind == "chunked" else "bitstream"
+        bs = {"chunked": rstream.read, "empirical": estream.read}.get(self.kind, bitstream.read)(path)
+        what = {"chunked": "rstream", "empirical": "estream"}.get(self.kind, "bitstream")
         s = dict(bs.settings)
         if s.get("model") not in MODELS:
             raise ValueError(f"{what}: header names the model {s.get('model')!r}; this build decodes {', '.join(MODELS)}")
@@ -403,7 +575,7 @@ class Decoder:
         self.n_frames = int(s["full_data_length"])
         self.frame_hw = tuple(int(v) for v in s["crop_list"].split("_")[:2])
         self.is_hnerv = s["model"] == "HNeRV_Boost"
-        margs = SimpleNamespace(**{k: v for k, v in s.items() if k != "ans_run"})
+        margs = SimpleNamespace(**{k: v for k, v in s.items() if k not in ("ans_run", "ans_tables")})
         margs.__dict__.update(quant=False, outf="")
         model = build_model(margs)
         if self.is_hnerv:
@@ -428,13 +600,17 @@ class Decoder:
                 raise ValueError(f"{what}: embedding records in a {s['model']} stream")
             self.embeds = None
         records = list(bs.tensors) + list(bs.embeds)
-        if self.kind == "chunked":
+        if self.kind in ("chunked", "empirical"):
             # the words as they lie in the file, every record's table and the run descriptors: one upload each, ONE launch that
             # entropy-decodes and de-quantises; its error word is read at the synchronisation below
             if any(not t.is_contiguous() for t in targets):
-                raise ValueError("rstream: the model the header describes has a quantised tensor that is not dense")
-            job = ops.AnsDequant(bs.words, [(t.reshape(-1), float(r.scale), r.lo, r.hi, float(r.mean), float(r.std), r.run_words,
-                                             None if r.beta is None else float(r.beta)) for t, r in zip(targets, records)], int(s["ans_run"])).launch()
+                raise ValueError(f"{what}: the model the header describes has a quantised tensor that is not dense")
+            if self.kind == "chunked":
+                job = ops.AnsDequant(bs.words, [(t.reshape(-1), float(r.scale), r.lo, r.hi, float(r.mean), float(r.std), r.run_words,
+                                                 None if r.beta is None else float(r.beta)) for t, r in zip(targets, records)], int(s["ans_run"])).launch()
+            else:                                          # the same kernel under the table each record names or carries
+                job = ops.AnsDequantTables(bs.words, [(t.reshape(-1), float(r.scale), r.lo, estream.record_cdf(r), r.run_words,
+                                                       None if r.beta is None else float(r.beta)) for t, r in zip(targets, records)], int(s["ans_run"])).launch()
         else:
             # host: ANS-decode every record into ONE pinned int32 array (segments start on 16-byte boundaries), upload it once
             job = None
@@ -655,6 +831,8 @@ def build_parser():
     r.add_argument("src")
     r.add_argument("dst")
     r.add_argument("--run", type=int, default=1024, help="symbols per independently coded run: a multiple of 64 in 64..4096")
+    r.add_argument("--tables", choices=TABLES, default="gaussian", help="empirical: every record under its Gaussian or under the table of its own symbol "
+                                                                        "histogram, whichever is smaller (SRC may then be a chunked file too)")
     return p
 
 
@@ -666,8 +844,8 @@ def main(argv=None):
         print(json.dumps(budget))
         return budget
     if a.cmd == "repack":
-        budget = repack(a.src, a.dst, a.run)
-        print(describe_chunked(budget))
+        budget = repack(a.src, a.dst, a.run, a.tables)
+        print(describe_any(budget))
         print(json.dumps(budget))
         return budget
     if not torch.cuda.is_available():

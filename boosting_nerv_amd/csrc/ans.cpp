@@ -144,24 +144,13 @@ bool decode_run(const Table& t, const uint32_t* words, size_t n_words, size_t co
 
 constexpr size_t MAX_RUN_WORDS = 65535;
 
-}  // namespace
-
-extern "C" long bnerv_ans_gaussian_cdf(int32_t min_sym, int32_t max_sym, double mean, double std_, uint32_t* out_cdf, size_t cap) {
-    Table t;
-    if (!gaussian_table(min_sym, max_sym, mean, std_, t)) { bnerv_set_error(BNERV_E_ARG, "ans_gaussian_cdf: bad model (min %d max %d mean %g std %g)", min_sym, max_sym, mean, std_); return -1; }
-    if (out_cdf && cap >= t.cdf.size()) std::copy(t.cdf.begin(), t.cdf.end(), out_cdf);
-    return (long)t.cdf.size();
-}
-
-extern "C" long bnerv_ans_encode_gaussian_runs(const int32_t* symbols, size_t n, int32_t min_sym, int32_t max_sym, double mean, double std_, int run,
-                                               uint32_t* out_words, size_t cap_words, unsigned short* out_run_words) {
-    Table t;
-    if (!symbols && n) { bnerv_set_error(BNERV_E_ARG, "ans_encode_gaussian_runs: null symbols"); return -1; }
-    if (run < 1 || (size_t)run * PREC / 32 + 3 > MAX_RUN_WORDS) { bnerv_set_error(BNERV_E_ARG, "ans_encode_gaussian_runs: run = %d (a run's words must fit 16 bits)", run); return -1; }
-    if (!gaussian_table(min_sym, max_sym, mean, std_, t)) { bnerv_set_error(BNERV_E_ARG, "ans_encode_gaussian_runs: bad model (min %d max %d mean %g std %g)", min_sym, max_sym, mean, std_); return -1; }
+// The two run entry points of either model share these: `what` names the caller in the messages.
+long encode_runs(const Table& t, const char* what, const int32_t* symbols, size_t n, int32_t min_sym, int run, uint32_t* out_words, size_t cap_words,
+                 unsigned short* out_run_words) {
+    const int32_t max_sym = min_sym + t.n() - 1;
     std::vector<int32_t> idx(n);
     for (size_t i = 0; i < n; ++i) {
-        if (symbols[i] < min_sym || symbols[i] > max_sym) { bnerv_set_error(BNERV_E_ARG, "ans_encode_gaussian_runs: symbol %d outside [%d, %d]", symbols[i], min_sym, max_sym); return -1; }
+        if (symbols[i] < min_sym || symbols[i] > max_sym) { bnerv_set_error(BNERV_E_ARG, "%s: symbol %d outside [%d, %d]", what, symbols[i], min_sym, max_sym); return -1; }
         idx[i] = symbols[i] - min_sym;
     }
     // every run through encode() from an empty state, its final state written as two words whatever its size
@@ -172,12 +161,85 @@ extern "C" long bnerv_ans_encode_gaussian_runs(const int32_t* symbols, size_t n,
     for (size_t at = 0; at < n; at += (size_t)run, ++k) {
         const size_t count = n - at < (size_t)run ? n - at : (size_t)run;
         const long got = encode(t, idx.data() + at, count, msg.data(), msg.size(), true);
-        if (got < 2 || (size_t)got > msg.size()) { bnerv_set_error(BNERV_E_ARG, "ans_encode_gaussian_runs: run %zu takes %ld words (%zu at most)", k, got, msg.size()); return -1; }
+        if (got < 2 || (size_t)got > msg.size()) { bnerv_set_error(BNERV_E_ARG, "%s: run %zu takes %ld words (%zu at most)", what, k, got, msg.size()); return -1; }
         all.insert(all.end(), msg.begin(), msg.begin() + got);
         if (out_run_words) out_run_words[k] = (unsigned short)got;
     }
     if (out_words && cap_words >= all.size()) std::copy(all.begin(), all.end(), out_words);
     return (long)all.size();
+}
+
+int decode_runs(const Table& t, const char* what, const uint32_t* words, size_t n_words, const unsigned short* run_words, size_t n_runs, size_t n,
+                int32_t min_sym, int run, int32_t* symbols_out) {
+    size_t total = 0;
+    for (size_t k = 0; k < n_runs; ++k) total += run_words[k];
+    BNERV_REQUIRE(total == n_words, "%s: the run lengths add up to %zu words, the message has %zu", what, total, n_words);
+    size_t at = 0;
+    for (size_t k = 0; k < n_runs; ++k) {
+        const size_t first = k * (size_t)run, count = n - first < (size_t)run ? n - first : (size_t)run;
+        if (!decode_run(t, words + at, run_words[k], count, symbols_out + first))
+            return bnerv_set_error(BNERV_E_ARG, "%s: run %zu (%u words at word %zu) does not decode to %zu symbols under this model",
+                                   what, k, (unsigned)run_words[k], at, count);
+        for (size_t i = 0; i < count; ++i) symbols_out[first + i] += min_sym;
+        at += run_words[k];
+    }
+    return BNERV_OK;
+}
+
+// The ONE place that turns a histogram into a table, integer arithmetic only: one slot per symbol, the other
+// 2^24 - A split by floor((2^24 - A) * count / n), the slots lost to truncation (fewer than A) one each to the symbols in order of
+// decreasing count, index order on ties.
+bool counts_table(const uint32_t* counts, int A, Table& t) {
+    if (!counts || A < 2 || A > (int)(TOTAL / 2)) return false;
+    uint64_t n = 0;
+    for (int k = 0; k < A; ++k) n += counts[k];
+    if (n == 0) return false;
+    const uint64_t free_slots = TOTAL - (uint32_t)A;
+    std::vector<uint32_t> f((size_t)A);
+    uint64_t used = 0;
+    for (int k = 0; k < A; ++k) { f[(size_t)k] = 1u + (uint32_t)(free_slots * counts[k] / n); used += f[(size_t)k]; }
+    std::vector<int> order((size_t)A);
+    for (int k = 0; k < A; ++k) order[(size_t)k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return counts[a] > counts[b]; });
+    for (size_t j = 0; used < TOTAL; j = (j + 1) % (size_t)A) { ++f[(size_t)order[j]]; ++used; }
+    t.cdf.resize((size_t)A + 1);
+    t.cdf[0] = 0;
+    for (int k = 0; k < A; ++k) t.cdf[(size_t)k + 1] = t.cdf[(size_t)k] + f[(size_t)k];
+    return t.cdf[(size_t)A] == TOTAL;
+}
+
+// a caller's cumulative table: A + 1 entries from 0 to 2^24, strictly increasing
+bool given_table(const uint32_t* cdf, int A, Table& t) {
+    if (!cdf || A < 2 || A > (int)(TOTAL / 2) || cdf[0] != 0 || cdf[A] != TOTAL) return false;
+    for (int k = 0; k < A; ++k)
+        if (cdf[k + 1] <= cdf[k]) return false;
+    t.cdf.assign(cdf, cdf + A + 1);
+    return true;
+}
+
+}  // namespace
+
+extern "C" long bnerv_ans_gaussian_cdf(int32_t min_sym, int32_t max_sym, double mean, double std_, uint32_t* out_cdf, size_t cap) {
+    Table t;
+    if (!gaussian_table(min_sym, max_sym, mean, std_, t)) { bnerv_set_error(BNERV_E_ARG, "ans_gaussian_cdf: bad model (min %d max %d mean %g std %g)", min_sym, max_sym, mean, std_); return -1; }
+    if (out_cdf && cap >= t.cdf.size()) std::copy(t.cdf.begin(), t.cdf.end(), out_cdf);
+    return (long)t.cdf.size();
+}
+
+extern "C" long bnerv_ans_counts_cdf(const uint32_t* counts, int A, uint32_t* out_cdf, size_t cap) {
+    Table t;
+    if (!counts_table(counts, A, t)) { bnerv_set_error(BNERV_E_ARG, "ans_counts_cdf: bad histogram (%d symbols, 2..%u, at least one counted)", A, TOTAL / 2); return -1; }
+    if (out_cdf && cap >= t.cdf.size()) std::copy(t.cdf.begin(), t.cdf.end(), out_cdf);
+    return (long)t.cdf.size();
+}
+
+extern "C" long bnerv_ans_encode_gaussian_runs(const int32_t* symbols, size_t n, int32_t min_sym, int32_t max_sym, double mean, double std_, int run,
+                                               uint32_t* out_words, size_t cap_words, unsigned short* out_run_words) {
+    Table t;
+    if (!symbols && n) { bnerv_set_error(BNERV_E_ARG, "ans_encode_gaussian_runs: null symbols"); return -1; }
+    if (run < 1 || (size_t)run * PREC / 32 + 3 > MAX_RUN_WORDS) { bnerv_set_error(BNERV_E_ARG, "ans_encode_gaussian_runs: run = %d (a run's words must fit 16 bits)", run); return -1; }
+    if (!gaussian_table(min_sym, max_sym, mean, std_, t)) { bnerv_set_error(BNERV_E_ARG, "ans_encode_gaussian_runs: bad model (min %d max %d mean %g std %g)", min_sym, max_sym, mean, std_); return -1; }
+    return encode_runs(t, "ans_encode_gaussian_runs", symbols, n, min_sym, run, out_words, cap_words, out_run_words);
 }
 
 extern "C" int bnerv_ans_decode_gaussian_runs(const uint32_t* words, size_t n_words, const unsigned short* run_words, size_t n_runs, size_t n,
@@ -186,19 +248,25 @@ extern "C" int bnerv_ans_decode_gaussian_runs(const uint32_t* words, size_t n_wo
     BNERV_REQUIRE((words || !n_words) && (symbols_out || !n) && (run_words || !n_runs), "ans_decode_gaussian_runs: null buffer");
     BNERV_REQUIRE(run >= 1 && n_runs == (n + (size_t)run - 1) / (size_t)run, "ans_decode_gaussian_runs: %zu run lengths for %zu symbols in runs of %d", n_runs, n, run);
     BNERV_REQUIRE(gaussian_table(min_sym, max_sym, mean, std_, t), "ans_decode_gaussian_runs: bad model");
-    size_t total = 0;
-    for (size_t k = 0; k < n_runs; ++k) total += run_words[k];
-    BNERV_REQUIRE(total == n_words, "ans_decode_gaussian_runs: the run lengths add up to %zu words, the message has %zu", total, n_words);
-    size_t at = 0;
-    for (size_t k = 0; k < n_runs; ++k) {
-        const size_t first = k * (size_t)run, count = n - first < (size_t)run ? n - first : (size_t)run;
-        if (!decode_run(t, words + at, run_words[k], count, symbols_out + first))
-            return bnerv_set_error(BNERV_E_ARG, "ans_decode_gaussian_runs: run %zu (%u words at word %zu) does not decode to %zu symbols under this model",
-                                   k, (unsigned)run_words[k], at, count);
-        for (size_t i = 0; i < count; ++i) symbols_out[first + i] += min_sym;
-        at += run_words[k];
-    }
-    return BNERV_OK;
+    return decode_runs(t, "ans_decode_gaussian_runs", words, n_words, run_words, n_runs, n, min_sym, run, symbols_out);
+}
+
+extern "C" long bnerv_ans_encode_table_runs(const int32_t* symbols, size_t n, int32_t min_sym, const uint32_t* cdf, int A, int run,
+                                            uint32_t* out_words, size_t cap_words, unsigned short* out_run_words) {
+    Table t;
+    if (!symbols && n) { bnerv_set_error(BNERV_E_ARG, "ans_encode_table_runs: null symbols"); return -1; }
+    if (run < 1 || (size_t)run * PREC / 32 + 3 > MAX_RUN_WORDS) { bnerv_set_error(BNERV_E_ARG, "ans_encode_table_runs: run = %d (a run's words must fit 16 bits)", run); return -1; }
+    if (!given_table(cdf, A, t)) { bnerv_set_error(BNERV_E_ARG, "ans_encode_table_runs: bad table (%d symbols; strictly increasing from 0 to 2^24)", A); return -1; }
+    return encode_runs(t, "ans_encode_table_runs", symbols, n, min_sym, run, out_words, cap_words, out_run_words);
+}
+
+extern "C" int bnerv_ans_decode_table_runs(const uint32_t* words, size_t n_words, const unsigned short* run_words, size_t n_runs, size_t n,
+                                           int32_t min_sym, const uint32_t* cdf, int A, int run, int32_t* symbols_out) {
+    Table t;
+    BNERV_REQUIRE((words || !n_words) && (symbols_out || !n) && (run_words || !n_runs), "ans_decode_table_runs: null buffer");
+    BNERV_REQUIRE(run >= 1 && n_runs == (n + (size_t)run - 1) / (size_t)run, "ans_decode_table_runs: %zu run lengths for %zu symbols in runs of %d", n_runs, n, run);
+    BNERV_REQUIRE(given_table(cdf, A, t), "ans_decode_table_runs: bad table (%d symbols; strictly increasing from 0 to 2^24)", A);
+    return decode_runs(t, "ans_decode_table_runs", words, n_words, run_words, n_runs, n, min_sym, run, symbols_out);
 }
 
 extern "C" long bnerv_ans_encode_gaussian(const int32_t* symbols, size_t n, int32_t min_sym, int32_t max_sym, double mean, double std_, uint32_t* out, size_t cap_words) {

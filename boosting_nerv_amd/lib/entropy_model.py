@@ -107,6 +107,44 @@ def ans_decode_gaussian_runs(words, run_words, n, lo, hi, mean, std, run):
     return out[:n]
 
 
+def ans_counts_cdf(counts):
+    """The len(counts) + 1 cumulative 24-bit slot counts of a histogram (uint32 numpy): every symbol at least one slot,
+    integer arithmetic only -- the one place a histogram becomes a table."""
+    lib = L.load()
+    c = np.ascontiguousarray(counts, dtype=np.uint32)
+    out = np.empty(c.size + 1, dtype=np.uint32)
+    if lib.bnerv_ans_counts_cdf(c.ctypes.data, c.size, out.ctypes.data, out.size) != out.size:
+        L.check(-1, "bnerv_ans_counts_cdf")
+    return out
+
+
+def ans_encode_table_runs(symbols, lo, cdf, run):
+    """ans_encode_gaussian_runs under an explicit cumulative table: symbol lo + i owns [cdf[i], cdf[i + 1])."""
+    lib = L.load()
+    sym, t = _i32(symbols), np.ascontiguousarray(cdf, dtype=np.uint32)
+    run_words = np.zeros(max((sym.size + int(run) - 1) // max(int(run), 1), 1), dtype=np.uint16)
+    args = (sym.ctypes.data, sym.size, int(lo), t.ctypes.data, t.size - 1, int(run))
+    need = lib.bnerv_ans_encode_table_runs(*args, None, 0, run_words.ctypes.data)
+    if need < 0:
+        L.check(-1, "bnerv_ans_encode_table_runs")
+    out = np.empty(max(need, 1), dtype=np.uint32)
+    got = lib.bnerv_ans_encode_table_runs(*args, out.ctypes.data, out.size, run_words.ctypes.data)
+    assert got == need
+    return out[:need], run_words[:(sym.size + int(run) - 1) // int(run)]
+
+
+def ans_decode_table_runs(words, run_words, n, lo, cdf, run):
+    """The inverse of ans_encode_table_runs -> int32 symbols; raises BnervError naming the first run that does not decode."""
+    lib = L.load()
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    rw = np.ascontiguousarray(run_words, dtype=np.uint16)
+    t = np.ascontiguousarray(cdf, dtype=np.uint32)
+    out = np.empty(max(int(n), 1), dtype=np.int32)
+    L.check(lib.bnerv_ans_decode_table_runs(w.ctypes.data, w.size, rw.ctypes.data, rw.size, int(n), int(lo), t.ctypes.data, t.size - 1, int(run),
+                                            out.ctypes.data), "bnerv_ans_decode_table_runs")
+    return out[:n]
+
+
 def ans_encode_categorical(symbols, probs):
     """symbols 0 .. K-1 under probs[K] -> uint32 words."""
     lib = L.load()

@@ -1111,6 +1111,268 @@ def ans_dequant(words, items, run):
     return [it[0] for it in items]
 
 
+class AnsDequantTables(AnsDequant):
+    """AnsDequant for a chunked CEM payload whose records bring their tables (estream.py): the same uploads, the same
+    kernel (bnerv_rans_dequant), launch() and check(), with every record's cumulative table given by the caller instead of built from
+    (mean, std).
+
+        items      one (out, scale, lo, cdf, run_words, beta) per record: cdf the record's cumulative table (uint32 numpy, A + 1 entries rising
+                   strictly from 0 to 2^24, 2 <= A <= 4096: symbol lo + i owns [cdf[i], cdf[i + 1])); the rest as in AnsDequant"""
+
+    def __init__(self, words, items, run):
+        import numpy as np
+        if not items:
+            raise ValueError("ans_dequant_tables: no items")
+        run = int(run)
+        if not L.RANS_MIN_RUN <= run <= L.RANS_MAX_RUN or run % 64:
+            raise ValueError(f"ans_dequant_tables: run = {run} (a multiple of 64 in {L.RANS_MIN_RUN}..{L.RANS_MAX_RUN})")
+        self.run = run
+        words = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        table = np.zeros(len(items), dtype=np.dtype([("out", "<u8"), ("scale", "<f4"), ("beta", "<f4"), ("lo", "<i4"), ("n", "<u4"), ("table", "<u4"),
+                                                     ("alphabet", "<u4"), ("has_beta", "<i4"), ("_pad", "<i4")]))
+        assert table.dtype.itemsize == C.sizeof(L.RansItem)
+        device = items[0][0].device
+        cdfs, lengths, blocks, at_table, at_run = [], [], [], 0, 0
+        for k, (out, scale, lo, cdf, run_words, beta) in enumerate(items):
+            L.require_device(out, "out")
+            n = out.numel()
+            if out.dtype != torch.float32 or not out.is_contiguous() or n == 0 or n >= 2 ** 31 or out.data_ptr() % 4 or out.device != device:
+                raise ValueError(f"ans_dequant_tables: item {k}: out must be a non-empty contiguous 4-byte aligned fp32 tensor on {device} (below 2^31 elements)")
+            cdf = np.ascontiguousarray(cdf, dtype=np.uint32).reshape(-1)
+            if not 2 <= cdf.size - 1 <= L.RANS_MAX_ALPHABET:
+                raise ValueError(f"ans_dequant_tables: item {k}: a table of {cdf.size - 1} symbols (2..{L.RANS_MAX_ALPHABET})")
+            if cdf[0] != 0 or cdf[-1] != 1 << 24 or (np.diff(cdf.astype(np.int64)) <= 0).any():
+                raise ValueError(f"ans_dequant_tables: item {k}: the cumulative table does not rise strictly from 0 to 2^24")
+            rw = np.ascontiguousarray(run_words, dtype=np.uint16).reshape(-1)
+            n_runs = (n + run - 1) // run
+            if rw.size != n_runs:
+                raise ValueError(f"ans_dequant_tables: item {k}: {rw.size} run lengths for {n_runs} runs")
+            if int(rw.min()) < 2:
+                raise ValueError(f"ans_dequant_tables: item {k}: run {int(rw.argmin())} has {int(rw.min())} words, fewer than its two state words")
+            table[k] = (out.data_ptr(), np.float32(scale), np.float32(0.0 if beta is None else beta), int(lo), n, at_table, cdf.size - 1, int(beta is not None), 0)
+            cdfs.append(cdf)
+            at_table += cdf.size
+            lengths.append(rw)
+            first = np.arange(0, n_runs, 64, dtype=np.uint32)
+            blk = np.zeros((first.size, 4), dtype=np.uint32)
+            blk[:, 0], blk[:, 1], blk[:, 2] = k, at_run + first, first
+            blocks.append(blk)
+            at_run += n_runs
+        lengths = np.concatenate(lengths)
+        starts = np.zeros(lengths.size + 1, dtype=np.uint64)
+        np.cumsum(lengths, dtype=np.uint64, out=starts[1:])
+        if int(starts[-1]) != words.size or words.size + 2 >= 2 ** 32:
+            raise ValueError(f"ans_dequant_tables: the run lengths add up to {int(starts[-1])} words, the payload has {words.size}")
+        padded = np.zeros(words.size + 2, dtype=np.uint32)       # (every run's span ends at or before words.size: validated just above)
+        padded[:words.size] = words
+        blocks = np.concatenate(blocks)
+        self.words, self.starts, self.blocks, self.items, self.tables = (_upload(a, device) for a in (padded, starts.astype(np.uint32), blocks, table, np.concatenate(cdfs)))
+        self.n_words, self.n_runs, self.n_blocks, self.n_items, self.n_table_words = padded.size, int(lengths.size), int(blocks.shape[0]), len(items), at_table
+        self.err = torch.zeros(1, dtype=torch.int32, device=device)
+        self._keep = [it[0] for it in items]
+
+
+def ans_dequant_tables(words, items, run):
+    """ans_dequant with an explicit cumulative table per record.  Arguments: AnsDequantTables."""
+    AnsDequantTables(words, items, run).launch().check()
+    return [it[0] for it in items]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# device encoder of the chunked CEM file with per-record tables (codec.encode(..., tables="empirical"); csrc/ransenc.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+def _symbol_items(items, what):
+    """Validates (symbols, lo, ...) items: non-empty contiguous int32 device tensors below 2^31 elements, all on one device."""
+    device = items[0][0].device
+    for k, it in enumerate(items):
+        sym = L.require_device(it[0], "symbols")
+        if sym.dtype != torch.int32 or not sym.is_contiguous() or sym.numel() == 0 or sym.numel() >= 2 ** 31 or sym.data_ptr() % 4 or sym.device != device:
+            raise ValueError(f"{what}: item {k}: symbols must be a non-empty contiguous int32 tensor on {device} (below 2^31 elements)")
+    return device
+
+
+def _upload(a, device):
+    import numpy as np
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(device)
+
+
+class SymHist:
+    """The histograms of int32 symbol tensors, ONE launch (bnerv_sym_hist).
+
+        items      one (symbols, lo, alphabet) per record: symbols a contiguous int32 device tensor (any 4-byte alignment), counted on
+                   [lo, lo + alphabet), alphabet in 1..4096
+    launch() zeroes and fills `counts` (int32 device tensor, the records' histograms back to back; record k at offsets[k]); check() reads
+    the device error word (a host sync) and raises ValueError when a symbol lay outside its record's range; host() is the list of the
+    records' uint32 numpy histograms (one copy, after check())."""
+
+    def __init__(self, items):
+        import numpy as np
+        if not items:
+            raise ValueError("sym_hist: no items")
+        device = _symbol_items(items, "sym_hist")
+        table = np.zeros(len(items), dtype=np.dtype([("sym", "<u8"), ("n", "<u4"), ("lo", "<i4"), ("alphabet", "<u4"), ("out", "<u4")]))
+        assert table.dtype.itemsize == C.sizeof(L.HistItem)
+        blocks, self.offsets, at = [], [], 0
+        for k, (sym, lo, alphabet) in enumerate(items):
+            alphabet = int(alphabet)
+            if not 1 <= alphabet <= L.RANS_MAX_ALPHABET:
+                raise ValueError(f"sym_hist: item {k}: an alphabet of {alphabet} symbols (1..{L.RANS_MAX_ALPHABET})")
+            table[k] = (sym.data_ptr(), sym.numel(), int(lo), alphabet, at)
+            first = np.arange(0, sym.numel(), L.HIST_SLICE, dtype=np.uint32)
+            blocks.append(np.stack([np.full(first.size, k, dtype=np.uint32), first], axis=1))
+            self.offsets.append(at)
+            at += alphabet
+        blocks = np.concatenate(blocks)
+        self.alphabets = [int(it[2]) for it in items]
+        self.items, self.blocks = _upload(table, device), _upload(blocks, device)
+        self.n_items, self.n_blocks, self.n_counts = len(items), int(blocks.shape[0]), at
+        self.counts = torch.zeros(at, dtype=torch.int32, device=device)
+        self.err = torch.zeros(1, dtype=torch.int32, device=device)
+        self._keep = [it[0] for it in items]
+
+    def launch(self, zero=True):
+        """zero=False adds to the counts that are there (a caller that has just zeroed them; the kernel alone under a timer)."""
+        if zero:
+            self.counts.zero_()
+        L.check(L.load().bnerv_sym_hist(L.stream(), L.ptr(self.items), self.n_items, L.ptr(self.blocks), self.n_blocks, L.ptr(self.counts), self.n_counts,
+                                        L.ptr(self.err)), "bnerv_sym_hist")
+        return self
+
+    def check(self):
+        e = int(self.err.item())
+        if e != 0:
+            raise ValueError("sym_hist: " + ("a descriptor points outside the uploaded arrays" if e & 2 else "a symbol lies outside its record's range"))
+        return self
+
+    def host(self):
+        import numpy as np
+        flat = self.counts.cpu().numpy().view(np.uint32)
+        return [flat[o:o + a].copy() for o, a in zip(self.offsets, self.alphabets)]
+
+
+def sym_hist(items):
+    """The uint32 numpy histogram of every item, one launch.  Arguments: SymHist.  Raises ValueError for a symbol outside its range."""
+    return SymHist(items).launch().check().host()
+
+
+class AnsEncodeRuns:
+    """The device encoder of range-ANS runs (bnerv_rans_encode, bnerv_rans_compact), the inverse of AnsDequantTables.
+
+        items      one (symbols, lo, cdf) per message: symbols a contiguous int32 device tensor (any 4-byte alignment; items may share one),
+                   cdf its cumulative table (uint32 numpy, A + 1 entries rising strictly from 0 to 2^24, 2 <= A <= 4096)
+        run        symbols per run: a multiple of 64 in 64..4096
+    launch() encodes every run of every item in ONE kernel, each into a slot of its own (run * 24 / 32 + 3 words, the host coder's bound);
+    check() reads the device error word (a host sync) and raises ValueError when a symbol lay outside its table.  run_words() is the
+    uint16 word count of every run per item (one copy); result(chosen) -- the items to keep, in output order; default all -- compacts their
+    runs in ONE more launch and returns (uint32 numpy words back to back, [run_words of each chosen item]): bit for bit what
+    lib.entropy_model.ans_encode_table_runs returns item by item."""
+
+    def __init__(self, items, run):
+        import numpy as np
+        if not items:
+            raise ValueError("ans_encode_runs: no items")
+        run = int(run)
+        if not L.RANS_MIN_RUN <= run <= L.RANS_MAX_RUN or run % 64:
+            raise ValueError(f"ans_encode_runs: run = {run} (a multiple of 64 in {L.RANS_MIN_RUN}..{L.RANS_MAX_RUN})")
+        self.run, self.slot_words = run, run * 24 // 32 + 3
+        self.device = device = _symbol_items(items, "ans_encode_runs")
+        table = np.zeros(len(items), dtype=np.dtype([("sym", "<u8"), ("n", "<u4"), ("lo", "<i4"), ("alphabet", "<u4"), ("table", "<u4")]))
+        assert table.dtype.itemsize == C.sizeof(L.RencItem)
+        cdfs, blocks, self.first_run, at_table, at_run = [], [], [], 0, 0
+        for k, (sym, lo, cdf) in enumerate(items):
+            cdf = np.ascontiguousarray(cdf, dtype=np.uint32).reshape(-1)
+            if not 2 <= cdf.size - 1 <= L.RANS_MAX_ALPHABET:
+                raise ValueError(f"ans_encode_runs: item {k}: a table of {cdf.size - 1} symbols (2..{L.RANS_MAX_ALPHABET})")
+            if cdf[0] != 0 or cdf[-1] != 1 << 24 or (np.diff(cdf.astype(np.int64)) <= 0).any():
+                raise ValueError(f"ans_encode_runs: item {k}: the cumulative table does not rise strictly from 0 to 2^24")
+            n_runs = (sym.numel() + run - 1) // run
+            table[k] = (sym.data_ptr(), sym.numel(), int(lo), cdf.size - 1, at_table)
+            cdfs.append(cdf)
+            at_table += cdf.size
+            first = np.arange(0, n_runs, 64, dtype=np.uint32)
+            blk = np.zeros((first.size, 4), dtype=np.uint32)
+            blk[:, 0], blk[:, 1], blk[:, 2] = k, at_run + first, first
+            blocks.append(blk)
+            self.first_run.append(at_run)
+            at_run += n_runs
+        self.first_run.append(at_run)
+        blocks = np.concatenate(blocks)
+        if at_run * self.slot_words >= 2 ** 32:
+            raise ValueError(f"ans_encode_runs: {at_run} runs of {run} symbols need more than 2^32 scratch words")
+        self.items, self.blocks, self.tables = _upload(table, device), _upload(blocks, device), _upload(np.concatenate(cdfs), device)
+        self.n_items, self.n_blocks, self.n_table_words, self.n_slots = len(items), int(blocks.shape[0]), at_table, at_run
+        self.slots = torch.empty(at_run * self.slot_words, dtype=torch.int32, device=device)
+        self.counts = torch.zeros(at_run, dtype=torch.int16, device=device)
+        self.err = torch.zeros(1, dtype=torch.int32, device=device)
+        self._keep = [it[0] for it in items]
+
+    def launch(self):
+        L.check(L.load().bnerv_rans_encode(L.stream(), L.ptr(self.blocks), self.n_blocks, L.ptr(self.items), self.n_items, L.ptr(self.tables), self.n_table_words,
+                                           self.run, L.ptr(self.slots), self.n_slots, L.ptr(self.counts), L.ptr(self.err)), "bnerv_rans_encode")
+        return self
+
+    def check(self):
+        e = int(self.err.item())
+        if e != 0:
+            raise ValueError("ans_encode_runs: " + ("a descriptor points outside the uploaded arrays" if e & 2 else
+                                                    "a symbol lies outside its table (or a run outgrew its slot)"))
+        return self
+
+    def run_words(self):
+        import numpy as np
+        flat = self.counts.cpu().numpy().view(np.uint16)
+        return [flat[a:b].copy() for a, b in zip(self.first_run[:-1], self.first_run[1:])]
+
+    def compact(self, chosen, run_words):
+        """An AnsCompact that gathers the runs of the items `chosen`, in that order; run_words: what run_words() returned."""
+        return AnsCompact(self, chosen, run_words)
+
+    def result(self, chosen=None):
+        self.check()
+        chosen = list(range(self.n_items)) if chosen is None else list(chosen)
+        rw = self.run_words()
+        job = self.compact(chosen, rw).launch().check()
+        return job.host(), [rw[k] for k in chosen]
+
+
+class AnsCompact:
+    """The runs of the chosen items of an AnsEncodeRuns, copied from their slots to one array back to back (bnerv_rans_compact): the
+    destination of every run is the exclusive sum of the word counts before it.  launch(), check() as elsewhere; `words`: the int32 device
+    tensor; host(): its uint32 numpy copy."""
+
+    def __init__(self, enc, chosen, run_words):
+        import numpy as np
+        if not chosen:
+            raise ValueError("ans_compact: no items")
+        counts = np.concatenate([run_words[k] for k in chosen]).astype(np.uint32)
+        slot = np.concatenate([np.arange(enc.first_run[k], enc.first_run[k + 1], dtype=np.uint32) for k in chosen])
+        ends = np.cumsum(counts, dtype=np.uint64)
+        if int(counts.min()) < 2 or int(counts.max()) > enc.slot_words or int(ends[-1]) >= 2 ** 32:
+            raise ValueError(f"ans_compact: run word counts in {int(counts.min())}..{int(counts.max())} (2..{enc.slot_words}; was the encoder checked?)")
+        copies = np.zeros((counts.size, 4), dtype=np.uint32)
+        copies[:, 0], copies[:, 1], copies[:, 2] = slot, (ends - counts).astype(np.uint32), counts
+        assert copies.dtype.itemsize * 4 == C.sizeof(L.RansCopy)
+        self.enc, self.n_copies, self.n_out = enc, int(counts.size), int(ends[-1])
+        self.copies = _upload(copies, enc.device)
+        self.words = torch.empty(self.n_out, dtype=torch.int32, device=enc.device)
+        self.err = torch.zeros(1, dtype=torch.int32, device=enc.device)
+
+    def launch(self):
+        e = self.enc
+        L.check(L.load().bnerv_rans_compact(L.stream(), L.ptr(e.slots), e.n_slots, e.slot_words, L.ptr(self.copies), self.n_copies, L.ptr(self.words), self.n_out,
+                                            L.ptr(self.err)), "bnerv_rans_compact")
+        return self
+
+    def check(self):
+        if int(self.err.item()) != 0:
+            raise ValueError("ans_compact: a copy points outside the slots or the output")
+        return self
+
+    def host(self):
+        import numpy as np
+        return self.words.cpu().numpy().view(np.uint32)
+
+
 def frame_to_u8(x, out=None):
     """[B, 3, H, W] fp32 -> [B, H, W, 3] uint8 = (x.clamp(0, 1) * 255 + 0.5).to(uint8).permute(0, 2, 3, 1) in one pass (the image
     convention of train_nerv_all._save_images).  out: a contiguous uint8 buffer to write into (a captured decode's)."""

@@ -47,6 +47,9 @@ def build_parser():
     add('--bitstream', type=str, default=None, help='write the final evaluation\'s coded model (and embeddings) to this file (codec.py decodes it)')
     add('--bitstream_run', type=int, default=0, help='0: --bitstream writes the version-1 file; N > 0 (a multiple of 64 in 64..4096): the chunked kind, '
                                                       'coded in independent runs of N symbols that the decoder entropy-decodes on the GPU')
+    add('--bitstream_tables', choices=('gaussian', 'empirical'), default='gaussian',
+        help='empirical (needs --bitstream_run N > 0): every record under its Gaussian or under a table of its own symbol frequencies that the file '
+             'carries, whichever is smaller; coded on the GPU')
     return p
 
 
@@ -55,7 +58,10 @@ def data_to_gpu(x, device):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.bitstream_tables == 'empirical' and not args.bitstream_run:
+        parser.error('--bitstream_tables empirical needs --bitstream_run N > 0 (only the chunked kind carries tables)')
     torch.set_printoptions(precision=2)
     if args.debug:
         args.eval_freq, args.outf = 1, 'output/debug'
@@ -310,7 +316,8 @@ def evaluate(model, full_dataloader, local_rank, args, dump_vis=False, coding=Fa
                  f'target_bpp:{round(args.target_bpp, 6)} \n', every_rank=False)
         if write_bitstream and getattr(args, 'bitstream', None) and local_rank in (0, None):
             from . import codec
-            args.bitstream_budget = codec.encode(model, entropy_model, args, full_dataloader, args.bitstream, run=getattr(args, 'bitstream_run', 0))
+            args.bitstream_budget = codec.encode(model, entropy_model, args, full_dataloader, args.bitstream, run=getattr(args, 'bitstream_run', 0),
+                                                 tables=getattr(args, 'bitstream_tables', 'gaussian'))
             log.line(f'Bitstream {args.bitstream}: {codec.describe_any(args.bitstream_budget)} \n', every_rank=False)
     return values, hw
 

@@ -457,6 +457,45 @@ int bnerv_rans_dequant(void* stream, const uint32_t* words, size_t n_words, cons
                        const uint32_t* tables, size_t n_table_words, int run, int* err);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Runs under a table the file carries, and the device encoder (additive to ABI 9; csrc/ans.cpp on the host, csrc/ransenc.hip on the
+ * device; boosting_nerv_amd/estream.py).
+ *
+ *   bnerv_ans_counts_cdf          the A + 1 cumulative 24-bit slot counts of a histogram of A symbols, integer arithmetic only:
+ *                                 f[k] = 1 + floor((2^24 - A) * counts[k] / n), the slots lost to truncation one each to the symbols in
+ *                                 order of decreasing count (index order on ties).  A pure function of the counts; strictly increasing,
+ *                                 ends at 2^24.  Returns A + 1 (also when out_cdf == NULL or cap is too small), -1 on a bad histogram.
+ *   bnerv_ans_encode_table_runs / bnerv_ans_decode_table_runs
+ *                                 bnerv_ans_encode_gaussian_runs / _decode_gaussian_runs with an explicit cumulative table (A + 1 entries,
+ *                                 strictly increasing from 0 to 2^24; symbol min_sym + i owns [cdf[i], cdf[i + 1])) in place of (mean, std).
+ *   bnerv_sym_hist  (device)      ONE launch over `items`: counts[items[k].out + s - lo] = how often symbol s occurs in items[k].sym.
+ *                                 `blocks`: n_blocks device pairs (item, first element); a block counts BNERV_HIST_SLICE elements from there
+ *                                 in a private LDS histogram and adds it to `counts` (n_counts device dwords, zeroed by the caller).  A
+ *                                 symbol outside [lo, lo + alphabet) sets bit 0 of *err and is not counted; a descriptor that points
+ *                                 outside the arrays sets bit 1.
+ *   bnerv_rans_encode  (device)   ONE launch.  Blocks as bnerv_rans_dequant's: one wave, up to 64 consecutive runs of ONE item, that item's
+ *                                 table in LDS; lane k encodes run blocks[b].run + k from its last symbol to its first with the host
+ *                                 coder's arithmetic.  Run g owns slot g of `slots`: slot_words = run * 24 / 32 + 3 dwords.  The run's
+ *                                 message -- bulk words in refill order, state low, state high -- ends at the END of its slot, and
+ *                                 run_words[g] is its length.  A symbol outside the table, or a word that would leave the slot, sets bit 0
+ *                                 of *err, and the lane writes nothing more (run_words[g] = 0); a bad descriptor sets bit 1.
+ *   bnerv_rans_compact (device)   copies[j] = (slot, destination word, word count): the last `count` words of slot `slot` go to
+ *                                 out[dst .. dst + count).  A copy that points outside `slots` or `out` sets bit 1 of *err and is skipped. */
+#define BNERV_HIST_SLICE 16384
+typedef struct { const int* sym; unsigned n; int lo; unsigned alphabet; unsigned out; } bnerv_hist_item;      /* out: first entry in `counts` */
+typedef struct { const int* sym; unsigned n; int lo; unsigned alphabet; unsigned table; } bnerv_renc_item;     /* table: first entry in `tables` */
+typedef struct { unsigned slot; unsigned dst; unsigned count; unsigned _pad; } bnerv_rans_copy;
+long bnerv_ans_counts_cdf(const uint32_t* counts, int A, uint32_t* out_cdf, size_t cap);
+long bnerv_ans_encode_table_runs(const int32_t* symbols, size_t n, int32_t min_sym, const uint32_t* cdf, int A, int run,
+                                 uint32_t* out_words, size_t cap_words, unsigned short* out_run_words);
+int bnerv_ans_decode_table_runs(const uint32_t* words, size_t n_words, const unsigned short* run_words, size_t n_runs, size_t n,
+                                int32_t min_sym, const uint32_t* cdf, int A, int run, int32_t* symbols_out);
+int bnerv_sym_hist(void* stream, const bnerv_hist_item* items, int n_items, const uint32_t* blocks, size_t n_blocks, uint32_t* counts, size_t n_counts, int* err);
+int bnerv_rans_encode(void* stream, const bnerv_rans_block* blocks, size_t n_blocks, const bnerv_renc_item* items, int n_items,
+                      const uint32_t* tables, size_t n_table_words, int run, uint32_t* slots, size_t n_slots, unsigned short* run_words, int* err);
+int bnerv_rans_compact(void* stream, const uint32_t* slots, size_t n_slots, int slot_words, const bnerv_rans_copy* copies, size_t n_copies,
+                       uint32_t* out, size_t n_out, int* err);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Huffman coder of the post-hoc quantised model (additive to ABI 9; csrc/huff.cpp on the host, csrc/huff.hip on the device;
  * boosting_nerv_amd/qstream.py).
  *

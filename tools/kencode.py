@@ -1,0 +1,201 @@
+"""File sizes and encode times of the chunked CEM file with per-record tables (estream.py) on the HIP path.
+
+    python tools/kencode.py [--only c1q|c5] [--frames 16] [--rounds 3]     seeded weights (the cases of tools/kdecode.py)
+    python tools/kencode.py --trained tiny|c1 [--epochs E]                 a trained model: sizes only
+
+Seeded cases, in ONE process:
+  sizes   the version-1 file (BNRV), the chunked file (BNRC) and the file with per-record tables (BNRE) at runs 256 and 1024; how many
+          records took a table; the BNRE file of the device path against the host repack of the version-1 file, byte for byte;
+  time    codec.encode(run=N) -- the host chain: version-1 messages, decoded again, re-encoded in runs -- against
+          codec.encode(run=N, tables="empirical") -- histogram, encode and compaction launches on the device -- alternated, host clock,
+          every call ending in a device synchronisation; then the three launches alone (ops.SymHist, ops.AnsEncodeRuns, ops.AnsCompact
+          with everything uploaded), each captured `reps` times into a graph of its own and the graphs replayed in turn under HIP events.
+--trained tiny: the README's tiny compression recipe (HNeRV_Boost, 4 frames of 180x320) through train_nerv_compression.main with --bitstream.
+--trained c1:   the C1 model (NeRV_Boost 1.5M, 132 synthetic 720x1280 frames): train_nerv_all.main for --epochs epochs (regression), then
+                train_nerv_compression.main from that checkpoint (--weight) for --epochs // 2 rate-distortion epochs with the compression
+                recipe's quantiser and rate flags (without --embed_entropy: the model has no embedding to code) and --bitstream.
+Both write the version-1 file; the other kinds are made from it on the host (codec.repack: the bytes of the device path, tests/test_gpu_estream.py).
+(needs the GPU)"""
+import argparse
+import glob
+import io
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+RUNS = (256, 1024)
+TINY = ("--outf kenc --data_path synthetic:4x180x320 --vid tiny --model HNeRV_Boost --sft_block res_sft --ch_t 32 --optim_type Adan "
+        "--conv_type convnext pshuffel_3x3 --act sin --norm none --crop_list 180_320 --resize_list -1 --loss Fusion10_freq --embed pe_1.25_80 "
+        "--enc_strds 5 2 2 --enc_dim 16_4 --dec_strds 5 2 2 --ks 0_1_5 --reduce 1.2 --dec_blks 1 1 2 --modelsize 0.05 --lower_width 6 -b 1 "
+        "-e 2 --eval_freq 2 --lr 0.002 --lr_type cosine_0_1_0.1 --not_resume --embed_entropy --quant --quant_model_bit 8 --quant_bias_bit 8 "
+        "--quant_embed_bit 8 --quantizer_w scale --quantizer_b scale --quantizer_e scalebeta --lambda_rate 0.5 --target_bit 2")
+
+# the compression flags of the recipes on a model that decodes from the frame index (no embedding to code: no --embed_entropy)
+C1_CEM = ("--quant --quant_model_bit 8 --quant_bias_bit 8 --quant_embed_bit 8 --quantizer_w scale --quantizer_b scale --quantizer_e scalebeta "
+          "--lr 0.0005 --lr_type cosine_0_1_0.1 --lambda_rate 0.05 --target_bit 4")
+
+
+def sizes_from_v1(label, v1):
+    """BNRC and BNRE of a version-1 file at every run, on the host; one line each."""
+    from boosting_nerv_amd import bitstream, codec
+    b1 = bitstream.info(v1)
+    print(f"{label}: BNRV {len(v1)} bytes ({b1['n_tensors']} tensors, {b1['n_embeds']} embeddings, coded words {b1['coded_words']} bits)", flush=True)
+    bs = bitstream.read(v1)
+    wide = [(r.count, r.lo, r.hi, float(r.scale)) for r in bs.tensors + bs.embeds if r.hi - r.lo + 1 > 4096]
+    if wide:                                                   # (the chunked kinds carry at most 4096 symbol values per record: section 27)
+        print(f"{label}: no chunked file of either kind: {len(wide)} of {len(bs.tensors + bs.embeds)} records span more than 4096 symbol values "
+              f"(symbols, lo, hi, scale): {wide[:6]}", flush=True)
+        return b1
+    for run in RUNS:
+        c, e = io.BytesIO(), io.BytesIO()
+        bc = codec.repack(v1, c, run)
+        be = codec.repack(v1, e, run, tables="empirical")
+        report(label, run, len(v1), bc, be)
+    return b1
+
+
+def report(label, run, n_v1, bc, be):
+    n_rec = be["n_tensors"] + be["n_embeds"]
+    part = lambda b: b["ans_words"] + b.get("tables", 0) + b["tensor_side"] + b["embed_side"]      # noqa: E731
+    assert part(be) <= part(bc) + 8 * n_rec
+    print(f"{label} run {run}: BNRC {bc['bytes']} bytes ({100.0 * (bc['bytes'] - n_v1) / n_v1:+.2f} % against BNRV) | BNRE {be['bytes']} bytes "
+          f"({100.0 * (be['bytes'] - n_v1) / n_v1:+.2f} % against BNRV, {100.0 * (be['bytes'] - bc['bytes']) / bc['bytes']:+.2f} % against BNRC); "
+          f"{be['n_table_records']} of {n_rec} records took a table ({be['tables']} bits of tables); words + tables + side: BNRE {part(be)} bits, BNRC {part(bc)} bits",
+          flush=True)
+
+
+def run_seeded(case, n_frames, rounds, reps):
+    import numpy as np
+    import torch
+    from kdecode import build, time_graph
+    from boosting_nerv_amd import codec, estream, ops
+    from boosting_nerv_amd.lib.entropy_model import DiffEntropyModel, ans_counts_cdf, ans_gaussian_cdf
+    from boosting_nerv_amd.synth import SyntheticVideo
+    dev = torch.device("cuda:0")
+    args, model = build(case)
+    model = model.to(dev)
+    model.init_data()
+    h, w = (int(v) for v in args.crop_list.split("_")[:2])
+    frames = None
+    if args.model == "HNeRV_Boost":
+        vid = SyntheticVideo(n_frames, h, w)
+        frames = torch.stack([vid.frame(i, device=dev) for i in range(n_frames)])
+        with torch.no_grad():
+            model.embed_quantizer.init_data(model.forward_encoder(frames[0:1]))
+    args.full_data_length = n_frames
+    em = DiffEntropyModel("gaussian")
+    buf = io.BytesIO()
+    codec.encode(model, em, args, frames, buf)
+    v1 = buf.getvalue()
+    print(f"{case}: {args.model} {h}x{w}, {n_frames} frames, seeded weights", flush=True)
+    sizes_from_v1(case, v1)
+
+    def encode(run, tables):
+        out = io.BytesIO()
+        torch.cuda.synchronize()
+        t0 = time.time()
+        codec.encode(model, em, args, frames, out, run=run, tables=tables)
+        torch.cuda.synchronize()
+        return time.time() - t0, out.getvalue()
+
+    for run in RUNS:                                            # first calls apart (code objects, lazily built tables); the bytes compared
+        t_h, chunked = encode(run, "gaussian")
+        t_d, emp = encode(run, "empirical")
+        host = io.BytesIO()
+        codec.repack(v1, host, run, tables="empirical")
+        assert emp == host.getvalue(), (case, run)
+        print(f"{case} run {run}: first calls: host chain {t_h * 1e3:.0f} ms, device path {t_d * 1e3:.0f} ms; the device path's file is the host repack's, "
+              f"byte for byte", flush=True)
+    times = {}
+    for r in range(rounds):
+        for run in RUNS:
+            for tables in ("gaussian", "empirical"):
+                times.setdefault((run, tables), []).append(encode(run, tables)[0])
+    for run in RUNS:
+        g, e = times[(run, "gaussian")], times[(run, "empirical")]
+        print(f"{case} encode, run {run}: host chain codec.encode(run=N) {min(g) * 1e3:.0f} ms best, {max(g) * 1e3:.0f} worst of {len(g)} | device path "
+              f"tables='empirical' {min(e) * 1e3:.0f} ms best, {max(e) * 1e3:.0f} worst | host chain / device path = {min(g) / min(e):.2f}", flush=True)
+
+    # the three launches alone: the symbols of the file, both tables per record, everything uploaded
+    for run in RUNS:
+        es = estream.read(encode(run, "empirical")[1])
+        recs = es.tensors + es.embeds
+        syms = [torch.from_numpy(estream.decode_record(es, k)).to(dev) for k in range(len(recs))]
+        hist = ops.SymHist([(s, r.lo, r.hi - r.lo + 1) for s, r in zip(syms, recs)]).launch().check()
+        counts = hist.host()
+        items = []
+        for s, r, c in zip(syms, recs, counts):
+            assert np.array_equal(c, np.bincount(s.cpu().numpy() - r.lo, minlength=r.hi - r.lo + 1))
+            # two items per record, as the encoder launches: its Gaussian and its own table.  A record that took its table carries no
+            # (mean, std): the Gaussian of its symbols' moments stands in for the one of its codes' (same alphabet, nearly the same words)
+            sf = s.float()
+            g = estream.record_cdf(r) if r.model == estream.GAUSSIAN else ans_gaussian_cdf(r.lo, r.hi, float(sf.mean()), max(float(sf.std()), 1e-5))
+            items += [(s, r.lo, g), (s, r.lo, ans_counts_cdf(c))]
+        enc = ops.AnsEncodeRuns(items, run).launch().check()
+        rw = enc.run_words()
+        comp = enc.compact(list(range(0, len(items), 2)), rw).launch().check()
+        (h_lo, h_hi), (k_lo, k_hi), (e_lo, e_hi), (c_lo, c_hi) = time_graph([hist.launch, lambda: hist.launch(zero=False), enc.launch, comp.launch], reps=reps,
+                                                                            rounds=max(rounds, 3))
+        n_sym = sum(r.count for r in recs)
+        print(f"{case} launches, run {run}: histogram {h_lo:.1f} us with the memset of its counts (worst {h_hi:.1f}), {k_lo:.1f} us the kernel alone (worst {k_hi:.1f}; "
+              f"{hist.n_blocks} blocks, {n_sym / k_lo:.0f} symbols/us) | encode under both "
+              f"tables {e_lo:.1f} us (worst {e_hi:.1f}; {enc.n_slots} runs in {enc.n_blocks} blocks, {2 * n_sym / e_lo:.0f} symbols/us) | compaction {c_lo:.1f} us "
+              f"(worst {c_hi:.1f}; {comp.n_out} words)", flush=True)
+        hist.check(), enc.check(), comp.check()
+
+
+def run_trained(which, epochs, cem_epochs=None):
+    import torch
+    import bench
+    from boosting_nerv_amd import train_nerv_all as T
+    from boosting_nerv_amd import train_nerv_compression as C
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as tmp:
+        os.chdir(tmp)
+        try:
+            path = os.path.join(tmp, "trained.bnrv")
+            if which == "tiny":
+                C.main(TINY.split() + ["--bitstream", path])
+                label = "tiny recipe, trained (2 epochs)"
+            else:
+                r = bench.RECIPES["c1"]
+                flags = r["flags"].split() + ["--data_path", f"synthetic:{r['n']}x{r['h']}x{r['w']}", "--vid", "c1", "--not_resume"]
+                T.main(flags + ["--outf", "kenc_reg", "-e", str(epochs), "--eval_freq", str(epochs)])
+                ckpt = glob.glob(os.path.join(tmp, "output", "kenc_reg", "**", "model_latest.pth"), recursive=True)
+                assert len(ckpt) == 1, ckpt
+                cem = max(epochs // 2, 1) if cem_epochs is None else cem_epochs
+                C.main(flags + C1_CEM.split() + ["--outf", "kenc_cem", "-e", str(cem), "--eval_freq", str(cem), "--weight", ckpt[0], "--bitstream", path])
+                label = f"C1, {epochs} regression + {cem} compression epochs on {r['n']} frames"
+            torch.cuda.synchronize()
+            sizes_from_v1(label, open(path, "rb").read())
+        finally:
+            os.chdir(cwd)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--only", choices=["c1q", "c5"], default=None)
+    ap.add_argument("--trained", choices=["tiny", "c1"], default=None)
+    ap.add_argument("--epochs", type=int, default=30)
+    ap.add_argument("--cem_epochs", type=int, default=None, help="--trained c1: rate-distortion epochs (default: --epochs // 2)")
+    ap.add_argument("--frames", type=int, default=16)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=10)
+    a = ap.parse_args()
+    import torch
+    assert torch.cuda.is_available(), "kencode needs the GPU"
+    if a.trained:
+        run_trained(a.trained, a.epochs, a.cem_epochs)
+        return 0
+    for case in ([a.only] if a.only else ["c1q", "c5"]):
+        run_seeded(case, a.frames, a.rounds, a.reps)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
