@@ -217,6 +217,7 @@ SYMBOLS = {
     "bnerv_dense_gemm_bwd": (_I, [_V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _Z, _I, _I, _I, _I]),
     "bnerv_cnx_mlp_fwd": (_I, [_V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _I, _I, _I]),
     "bnerv_cnx_mlp_bwd": (_I, [_V, _V, _V, _V, _V, _V, _V, _V, _V, _I, _I, _I]),
+    "bnerv_cnx_mlp_plan": (_I, [_I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "bnerv_cnx_param_grads": (_I, [_V, _V, _V, _V, _V, _V, _V, _V, _V, _I]),
     "bnerv_ans_encode_gaussian": (C.c_long, [_V, _Z, _I, _I, C.c_double, C.c_double, _V, _Z]),
     "bnerv_ans_decode_gaussian": (_I, [_V, _Z, _Z, _I, _I, C.c_double, C.c_double, _V]),
@@ -238,6 +239,7 @@ SYMBOLS = {
     "bnerv_dwconv_fwd": (_I, [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I]),
     "bnerv_dwconv_wgrad_ws_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "bnerv_dwconv_wgrad": (_I, [_V, _V, _V, _V, _V, _Z, _I, _I, _I, _I, _I, _V]),
+    "bnerv_dwconv_wgrad_plan": (_I, [_I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
     "bnerv_lncf_fwd": (_I, [_V, _V, _V, _V, _V, _I, _I, _I, _F]),
     "bnerv_lncf_bwd_ws_bytes": (_Z, [_I, _I, _I]),
     "bnerv_lncf_bwd": (_I, [_V, _V, _V, _V, _V, _V, _V, _Z, _I, _I, _I, _F]),

@@ -140,6 +140,9 @@ static int dw_groups(int B, int C, int H, int W) {
     return cdiv(ty, rows);
 }
 
+// tile rows per group (the last group may hold fewer)
+static int dw_rows_per_group(int H, int groups) { return cdiv(cdiv(H, DTH), groups); }
+
 }  // namespace
 
 extern "C" int bnerv_dwconv_fwd(void* stream, const float* x, const float* w, const float* bias, float* y, int B, int C, int H, int W, int K, int flip) {
@@ -159,6 +162,15 @@ extern "C" size_t bnerv_dwconv_wgrad_ws_bytes(int B, int C, int H, int W, int K)
     return (size_t)B * cdiv(W, DTW) * cdiv(H, DTH) * C * (K * K + 1) * sizeof(float);
 }
 
+// host-only: the grid rows of bnerv_dwconv_wgrad's launch (groups of 16-row tile rows per tile column) and the tile rows of a group
+extern "C" int bnerv_dwconv_wgrad_plan(int B, int C, int H, int W, int* groups, int* rows_per_group) {
+    BNERV_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "dwconv_wgrad_plan: bad args");
+    const int gr = dw_groups(B, C, H, W);
+    if (groups) *groups = gr;
+    if (rows_per_group) *rows_per_group = dw_rows_per_group(H, gr);
+    return BNERV_OK;
+}
+
 // dwb: [C][K*K + 1] (weight gradient rows with the bias gradient as the last column); `defer`: queue the slab reduction
 extern "C" int bnerv_dwconv_wgrad(void* stream, const float* x, const float* g, float* dwb, void* ws, size_t ws_bytes, int B, int C, int H, int W, int K, bnerv_ctx* defer_ctx) {
     BNERV_REQUIRE(x && g && dwb && ws && B > 0 && C > 0 && H > 0 && W > 0, "dwconv_wgrad: bad args");
@@ -166,7 +178,7 @@ extern "C" int bnerv_dwconv_wgrad(void* stream, const float* x, const float* g, 
     BNERV_REQUIRE((size_t)B * C <= 65535, "dwconv_wgrad: B*C too large");
     if (ws_bytes < bnerv_dwconv_wgrad_ws_bytes(B, C, H, W, K)) return bnerv_set_error(BNERV_E_WS, "dwconv_wgrad: workspace too small");
     const int tiles_x = cdiv(W, DTW), tiles_y = cdiv(H, DTH);
-    const int groups = dw_groups(B, C, H, W), rows = cdiv(tiles_y, groups);
+    const int groups = dw_groups(B, C, H, W), rows = dw_rows_per_group(H, groups);
     const int n_slabs = B * tiles_x * groups;                   // (<= B * tiles: bnerv_dwconv_wgrad_ws_bytes covers it)
     dim3 grid(tiles_x, groups, B * C);
     hipLaunchKernelGGL(dwconv_wgrad_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, g, (float*)ws, C, H, W, K, tiles_y, rows);

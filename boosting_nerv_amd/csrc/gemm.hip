@@ -380,36 +380,53 @@ __global__ __launch_bounds__(256) void cnx_mlp_bwd_kernel(const MlpArgs a) {
     }
 }
 
+// What a cnx_mlp launch of [B, C, HW] looks like: pixel tiles per wave, LDS bytes, blocks, wave items (a block's four waves take items
+// blockIdx.x * 4 + wave, + gridDim.x * 4, ...).  The launchers below and bnerv_cnx_mlp_plan both read it from here.
+struct MlpPlan { int nt; size_t lds; int grid; int items; };
+
+inline MlpPlan mlp_plan(int B, int C, int HW) {
+    // one 16-pixel tile per wave while that still leaves every wave at most one item (1024 wave slots at one block per CU)
+    constexpr long NT1_MAX_PX = 16384;
+    MlpPlan p;
+    p.nt = (long)B * HW <= NT1_MAX_PX ? 1 : 2;
+    p.lds = (size_t)2 * 4 * C * C * sizeof(float);
+    p.items = B * cdiv(HW, 16 * p.nt);
+    p.grid = cdiv(p.items, 4);
+    const int cap = 256 * (p.lds > 80 * 1024 ? 1 : 2);
+    if (p.grid > cap) p.grid = cap;
+    return p;
+}
+
 template <int C, int NT>
-int launch_mlp_nt(hipStream_t st, const MlpArgs& a, bool bwd) {
-    const size_t lds = (size_t)2 * 4 * C * C * sizeof(float);
-    const int total = a.B * cdiv(a.HW, 16 * NT);
-    int grid = cdiv(total, 4);
-    const int cap = 256 * (lds > 80 * 1024 ? 1 : 2);
-    if (grid > cap) grid = cap;
-    if (const int rc = bwd ? dyn_lds<&cnx_mlp_bwd_kernel<C, NT>>(lds, "cnx_mlp_bwd") : dyn_lds<&cnx_mlp_fwd_kernel<C, NT>>(lds, "cnx_mlp_fwd")) return rc;
-    if (bwd) hipLaunchKernelGGL((cnx_mlp_bwd_kernel<C, NT>), dim3(grid), dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((cnx_mlp_fwd_kernel<C, NT>), dim3(grid), dim3(256), lds, st, a);
+int launch_mlp_nt(hipStream_t st, const MlpArgs& a, bool bwd, const MlpPlan& p) {
+    if (const int rc = bwd ? dyn_lds<&cnx_mlp_bwd_kernel<C, NT>>(p.lds, "cnx_mlp_bwd") : dyn_lds<&cnx_mlp_fwd_kernel<C, NT>>(p.lds, "cnx_mlp_fwd")) return rc;
+    if (bwd) hipLaunchKernelGGL((cnx_mlp_bwd_kernel<C, NT>), dim3(p.grid), dim3(256), p.lds, st, a);
+    else hipLaunchKernelGGL((cnx_mlp_fwd_kernel<C, NT>), dim3(p.grid), dim3(256), p.lds, st, a);
     BNERV_LAUNCH_CHECK(bwd ? "cnx_mlp_bwd" : "cnx_mlp_fwd");
     return BNERV_OK;
 }
 
 template <int C>
 int launch_mlp(hipStream_t st, const MlpArgs& a, bool bwd) {
-    // one 16-pixel tile per wave while that still leaves every wave at most one item (1024 wave slots at one block per CU)
-    constexpr long NT1_MAX_PX = 16384;
-    if ((long)a.B * a.HW <= NT1_MAX_PX) return launch_mlp_nt<C, 1>(st, a, bwd);
-    return launch_mlp_nt<C, 2>(st, a, bwd);
+    const MlpPlan p = mlp_plan(a.B, C, a.HW);
+    if (p.nt == 1) return launch_mlp_nt<C, 1>(st, a, bwd, p);
+    return launch_mlp_nt<C, 2>(st, a, bwd, p);
+}
+
+// the widths the kernels are built for (launch_mlp_c and bnerv_cnx_mlp_plan refuse any other with the same words)
+int mlp_check_c(int C) {
+    if (C == 16 || C == 32 || C == 48 || C == 64) return BNERV_OK;
+    return bnerv_set_error(BNERV_E_ARG, "cnx_mlp: C must be 16, 32, 48 or 64 (got %d)", C);
 }
 
 int launch_mlp_c(hipStream_t st, const MlpArgs& a, bool bwd) {
+    if (const int rc = mlp_check_c(a.C)) return rc;
     switch (a.C) {
         case 16: return launch_mlp<16>(st, a, bwd);
         case 32: return launch_mlp<32>(st, a, bwd);
         case 48: return launch_mlp<48>(st, a, bwd);
-        case 64: return launch_mlp<64>(st, a, bwd);
     }
-    return bnerv_set_error(BNERV_E_ARG, "cnx_mlp: C must be 16, 32, 48 or 64 (got %d)", a.C);
+    return launch_mlp<64>(st, a, bwd);
 }
 
 // dw2 = gamma S, db2 = gamma t, dgamma = rowsum(w2 * S) + b2 * t for one ConvNeXt block ([C x 4C] bookkeeping after the two k = 1
@@ -517,6 +534,17 @@ extern "C" int bnerv_cnx_mlp_bwd(void* stream, const float* h1, const float* dou
     a.hin = h1; a.dout = dout; a.w1 = w1; a.w2 = w2; a.gamma = gamma; a.dx = dx; a.gbuf = gbuf; a.dhbuf = dhbuf;
     a.B = B; a.C = C; a.HW = HW;
     return launch_mlp_c(reinterpret_cast<hipStream_t>(stream), a, true);
+}
+
+// host-only: the launch bnerv_cnx_mlp_fwd / _bwd would make for [B, C, HW] (mlp_plan, as the launchers read it); launches nothing
+extern "C" int bnerv_cnx_mlp_plan(int B, int C, int HW, int* nt, int* grid_blocks, int* items) {
+    BNERV_REQUIRE(B > 0 && HW > 0, "cnx_mlp_plan: bad args");
+    if (const int rc = mlp_check_c(C)) return rc;
+    const MlpPlan p = mlp_plan(B, C, HW);
+    if (nt) *nt = p.nt;
+    if (grid_blocks) *grid_blocks = p.grid;
+    if (items) *items = p.items;
+    return BNERV_OK;
 }
 
 // S [C, 4C], t [C]: what bnerv_conv_wgrad (k = 1) returns for (gelu(h1), dout); outputs dw2 [C, 4C], db2 [C], dgamma [C]

@@ -399,6 +399,10 @@ int bnerv_cnx_mlp_fwd(void* stream, const float* x, const float* inp, const floa
                       const float* gamma, float* out, float* hsave, int B, int C, int HW);
 int bnerv_cnx_mlp_bwd(void* stream, const float* h1, const float* dout, const float* w1, const float* w2, const float* gamma,
                       float* dx, float* gbuf, float* dhbuf, int B, int C, int HW);
+/* Host-only (no launch, no device): the launch the two calls above make for [B, C, HW] -- nt: 16-pixel tiles per wave item (1 or 2),
+ * grid_blocks: blocks of four waves, items: wave items; wave w of block k takes items 4 k + w, + 4 grid_blocks, ...  (outputs may be
+ * NULL).  BNERV_E_ARG for a C the kernels are not built for. */
+int bnerv_cnx_mlp_plan(int B, int C, int HW, int* nt, int* grid_blocks, int* items);
 /* the [C x 4C] bookkeeping of that backward in one launch: dw2 = gamma S, db2 = gamma t, dgamma = rowsum(w2 * S) + b2 * t */
 int bnerv_cnx_param_grads(void* stream, const float* S, const float* t, const float* w2, const float* b2, const float* gamma,
                           float* dw2, float* db2, float* dgamma, int C);
@@ -541,6 +545,9 @@ int bnerv_huff_dequant(void* stream, const uint32_t* words, size_t n_words, cons
 int bnerv_dwconv_fwd(void* stream, const float* x, const float* w, const float* bias, float* y, int B, int C, int H, int W, int K, int flip);
 size_t bnerv_dwconv_wgrad_ws_bytes(int B, int C, int H, int W, int K);
 int bnerv_dwconv_wgrad(void* stream, const float* x, const float* g, float* dwb, void* ws, size_t ws_bytes, int B, int C, int H, int W, int K, bnerv_ctx* defer_ctx);
+/* Host-only (no launch, no device): how bnerv_dwconv_wgrad splits the rows of 16 x 64 tiles of a plane -- `groups` blocks per tile column,
+ * each summing rows_per_group tile rows in registers (the last group may hold fewer).  Outputs may be NULL. */
+int bnerv_dwconv_wgrad_plan(int B, int C, int H, int W, int* groups, int* rows_per_group);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Loss and metrics.  Replaces loss_fn (hnerv_utils.py:335-397; every variant) including its autograd backward, and

@@ -7,7 +7,7 @@ import math
 import pytest
 import torch
 
-QUERIES = ("_ws_bytes", "bnerv_conv_partial_rows", "bnerv_tanh_grad_blocks")      # answered on the host: no launch
+QUERIES = ("_ws_bytes", "bnerv_conv_partial_rows", "bnerv_tanh_grad_blocks", "bnerv_cnx_mlp_plan", "bnerv_dwconv_wgrad_plan")      # answered on the host: no launch
 PAIR, FLUSH = "bnerv_conv_wgrad_pair", "bnerv_flush_deferred"
 
 

@@ -21,7 +21,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "tests", "conv_route_pins.json")
 CONFIGS = ("c1", "c3", "c4", "hnerv")
 # answered by the real library: they size buffers or grids and touch no device
-HOST_QUERIES = ("bnerv_conv_partial_rows", "bnerv_conv_tiles", "bnerv_tanh_grad_blocks", "bnerv_adan_table_blocks", "bnerv_adam_table_blocks")
+HOST_QUERIES = ("bnerv_conv_partial_rows", "bnerv_conv_tiles", "bnerv_tanh_grad_blocks", "bnerv_adan_table_blocks", "bnerv_adam_table_blocks",
+                "bnerv_cnx_mlp_plan", "bnerv_dwconv_wgrad_plan")
 
 
 def int_fields(d):
