@@ -157,6 +157,18 @@ class RansCopy(C.Structure):       # bnerv_rans_copy
     _fields_ = [("slot", C.c_uint32), ("dst", C.c_uint32), ("count", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+RANSW_MAX_SHIFT = 16    # BNERV_RANSW_MAX_SHIFT
+
+
+class WsymItem(C.Structure):       # bnerv_wsym_item
+    _fields_ = [("sym", _fp), ("n", C.c_uint32), ("lo", C.c_int), ("alphabet", C.c_uint32), ("at", C.c_uint32), ("shift", C.c_uint32), ("span_m1", C.c_uint32)]
+
+
+class RanswItem(C.Structure):      # bnerv_ransw_item
+    _fields_ = [("out", _fp), ("scale", C.c_float), ("beta", C.c_float), ("lo", C.c_int), ("n", C.c_uint32), ("table", C.c_uint32), ("alphabet", C.c_uint32),
+                ("has_beta", C.c_int), ("shift", C.c_uint32), ("span_m1", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class YuvCoeffs(C.Structure):      # bnerv_yuv_coeffs: what yuvio.coefficients() computed in float64, rounded to fp32
     _fields_ = [("m", C.c_float * 9), ("off", C.c_float * 3), ("scale", C.c_float * 3), ("maxcode", C.c_float)]
 
@@ -233,6 +245,12 @@ SYMBOLS = {
     "bnerv_sym_hist": (_I, [_V, _V, _I, _V, _Z, _V, _Z, _V]),
     "bnerv_rans_encode": (_I, [_V, _V, _Z, _V, _I, _V, _Z, _I, _V, _Z, _V, _V]),
     "bnerv_rans_compact": (_I, [_V, _V, _Z, _I, _V, _Z, _V, _Z, _V]),
+    "bnerv_ans_gaussian_bucket_cdf": (C.c_long, [_I, _I, _I, C.c_double, C.c_double, _V, _Z]),
+    "bnerv_ans_encode_wide_runs": (C.c_long, [_V, _Z, _I, _I, _V, _I, _I, _I, _V, _Z, _V]),
+    "bnerv_ans_decode_wide_runs": (_I, [_V, _Z, _V, _Z, _Z, _I, _I, _V, _I, _I, _I, _V]),
+    "bnerv_sym_hist_wide": (_I, [_V, _V, _I, _V, _Z, _V, _Z, _V]),
+    "bnerv_rans_encode_wide": (_I, [_V, _V, _Z, _V, _I, _V, _Z, _I, _V, _Z, _I, _V, _V]),
+    "bnerv_rans_dequant_wide": (_I, [_V, _V, _Z, _V, _Z, _V, _Z, _V, _I, _V, _Z, _I, _V]),
     "bnerv_huff_encode": (C.c_long, [_V, _V, _I, _V, _I, _V, _Z, _V, _Z]),
     "bnerv_huff_decode": (_I, [_V, _Z, _V, _Z, _V, _I, _V, _I, _V]),
     "bnerv_huff_dequant": (_I, [_V, _V, _Z, _V, _Z, _V, _I, _V, _I, _V]),

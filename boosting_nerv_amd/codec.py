@@ -27,7 +27,13 @@ symbol frequencies, whichever makes the file smaller: encode(..., run=N, tables=
 launch, one encode launch over both tables of every record, one compaction -- and repack(..., tables="empirical") makes the same bytes on
 the host.  Decoder launches the same decode kernel on it, with the tables the file carries.
 
-    python -m boosting_nerv_amd.codec repack in.bnrv out.bnre [--run N] --tables empirical"""
+    python -m boosting_nerv_amd.codec repack in.bnrv out.bnre [--run N] --tables empirical
+
+Both chunked kinds hold a record's table in LDS and so refuse a record whose symbols span more than 4096 values.  The wide kind (wstream.py,
+DESIGN section 29) codes such a record as a bucket under a table of at most 4096 entries plus raw low bits in the same rANS state:
+encode(..., run=N, tables=..., wide=True) on the device, repack(..., wide=True) the same bytes on the host:
+
+    python -m boosting_nerv_amd.codec repack in.bnrv out.bnrw [--run N] [--tables empirical] --wide"""
 import argparse
 import builtins
 import json
@@ -37,7 +43,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import bitstream, estream, qstream, rstream
+from . import bitstream, estream, qstream, rstream, wstream
 from .bitstream import Record
 
 TABLES = ("gaussian", "empirical")
@@ -170,7 +176,7 @@ def _frames_in_order(frames_or_loader, args, device):
 
 
 @torch.no_grad()
-def encode(model, entropy_model, args, frames_or_loader, path, run=0, tables="gaussian"):
+def encode(model, entropy_model, args, frames_or_loader, path, run=0, tables="gaussian", wide=False):
     """Write the model (and, for HNeRV_Boost, every frame's embedding) as a bitstream to `path` (a file name or a binary file object);
     returns bitstream.info of what was written.
 
@@ -182,9 +188,16 @@ def encode(model, entropy_model, args, frames_or_loader, path, run=0, tables="ga
     buffer and repacked, so its symbols and side information are the same by construction; returns rstream.info then.
 
     tables="empirical" (with run > 0) writes the chunked kind with per-record tables (estream.py) and codes it on the device: the symbols
-    never leave it, no version-1 message is built; returns estream.info then."""
+    never leave it, no version-1 message is built; returns estream.info then.
+
+    wide=True (with run > 0) writes the wide kind (wstream.py): the device path of tables="empirical" with a shift per record, so a record
+    may span any number of symbol values; with tables="gaussian" every record stays under its Gaussian.  Returns wstream.info then."""
     if tables not in TABLES:
         raise ValueError(f"codec.encode: tables = {tables!r} ({' | '.join(TABLES)})")
+    if wide:
+        if not run:
+            raise ValueError("codec.encode: wide=True needs run > 0 (only a chunked kind is decoded by the wide kernel)")
+        return _encode_empirical(model, entropy_model, args, frames_or_loader, path, rstream.check_run(run), wide=tables)
     if tables == "empirical":
         if not run:
             raise ValueError("codec.encode: tables='empirical' needs run > 0 (only the chunked kind carries tables)")
@@ -246,7 +259,14 @@ def _write_blob(dst, blob):
 def _too_wide(who, lo, hi):
     if hi - lo + 1 > rstream.MAX_ALPHABET:
         raise NotImplementedError(f"{who}: a record's symbols span [{lo}, {hi}]: {hi - lo + 1} values; the chunked kind carries "
-                                  f"{rstream.MAX_ALPHABET} (the device decoder holds a record's table in LDS)")
+                                  f"{rstream.MAX_ALPHABET} (the device decoder holds a record's table in LDS); the wide kind (wide=True, "
+                                  f"--wide, --bitstream_wide) takes it")
+
+
+def _table_pays(freq, n_words):
+    """The choice rule: the table is taken when its words plus its LEB128 bytes are fewer bits than the Gaussian's words
+    plus mean and std; a tie goes to the Gaussian.  n_words: (Gaussian, table)."""
+    return 32 * n_words[1] + 8 * len(estream.table_bytes(freq)) < 32 * n_words[0] + 64
 
 
 def _empirical_record(side, cdf, n_words, run_words):
@@ -256,18 +276,31 @@ def _empirical_record(side, cdf, n_words, run_words):
     run_words: (Gaussian, table) totals and per-run word counts.  -> (ERecord, 0 | 1: which of the two was taken)."""
     count, scale, mean, std, lo, hi, beta = side
     freq = np.diff(cdf.astype(np.int64)).astype(np.uint32)
-    take = int(32 * n_words[1] + 8 * len(estream.table_bytes(freq)) < 32 * n_words[0] + 64)
+    take = int(_table_pays(freq, n_words))
     if take:
         return estream.ERecord(count, scale, lo, hi, estream.TABLE, None, None, freq, run_words[1], beta), 1
     return estream.ERecord(count, scale, lo, hi, estream.GAUSSIAN, mean, std, None, run_words[0], beta), 0
 
 
 @torch.no_grad()
-def _encode_empirical(model, entropy_model, args, frames_or_loader, path, run):
+def _wide_record(side, shift, table_cdf, n_words, run_words):
+    """_empirical_record for the wide kind: the same choice rule over the bucket tables; table_cdf None (tables="gaussian"): the Gaussian."""
+    count, scale, mean, std, lo, hi, beta = side
+    if table_cdf is not None:
+        freq = np.diff(table_cdf.astype(np.int64)).astype(np.uint32)
+        if _table_pays(freq, n_words):
+            return wstream.WRecord(count, scale, lo, hi, estream.TABLE, shift, None, None, freq, run_words[1], beta), 1
+    return wstream.WRecord(count, scale, lo, hi, estream.GAUSSIAN, shift, mean, std, None, run_words[0], beta), 0
+
+
+def _encode_empirical(model, entropy_model, args, frames_or_loader, path, run, wide=None):
     """encode(..., run, tables="empirical"): the symbols stay on the device.  Every quantiser called once for its symbols, the moments of the
     evaluation pass evaluate() accounts with (fused or tensor by tensor), the embeddings frame by frame as encode() makes them, ONE host copy of every record's (mean, std, scale,
     beta) and symbol range, then: histogram launch -> counts to the host -> both tables per record -> ONE encode launch over both -> the
-    choice per record -> compaction -> one copy of the words."""
+    choice per record -> compaction -> one copy of the words.
+
+    wide: None, or the `tables` of the wide kind (wstream.py) -- the same walk with a shift per record, bucket histograms and bucket tables, the
+    wide kernels; under "gaussian" one message per record and no histogram."""
     from . import ops
     from .lib.entropy_model import ans_counts_cdf, ans_gaussian_cdf
     _check_supported(model, entropy_model, args)
@@ -320,10 +353,35 @@ def _encode_empirical(model, entropy_model, args, frames_or_loader, path, run):
     for k in range(n_rec):
         lo, hi = int(range_h[k]), int(range_h[n_rec + k])
         hi = hi if hi > lo else lo + 1
-        _too_wide("codec.encode", lo, hi)
+        if wide is None:
+            _too_wide("codec.encode", lo, hi)
         std = np.float32(np.clip(side_h[n_rec + k], np.float32(1e-5), np.float32(1e10)))      # (compress_matrix_flatten_gaussian_global's clamp)
         sides.append((int(symbols[k].numel()), np.float32(side_h[2 * n_rec + k]), np.float32(side_h[k]), std, lo, hi,
                       np.float32(side_h[-1]) if k >= n_tensors else None))
+    frame_hw = _frame_hw(args, frames_or_loader, frame_hw)
+    sd = model.state_dict()
+    raw = [sd[k].detach().float().reshape(-1).cpu().numpy() for k in _raw_keys(model, is_hnerv)]
+    if wide is not None:
+        from .lib.entropy_model import ans_gaussian_bucket_cdf
+        shifts = [wstream.min_shift(r[4], r[5]) for r in sides]
+        per = 2 if wide == "empirical" else 1                 # messages per record
+        items = [(s, r[4], r[5], ans_gaussian_bucket_cdf(r[4], r[5], k, float(r[2]), float(r[3])), k) for s, r, k in zip(symbols, sides, shifts)]
+        if per == 2:
+            counts = ops.SymHistWide([(s, r[4], r[5], k) for s, r, k in zip(symbols, sides, shifts)]).launch().check().host()
+            items = [it for g, c in zip(items, counts) for it in (g, (g[0], g[1], g[2], ans_counts_cdf(c), g[4]))]
+        enc = ops.AnsEncodeRunsWide(items, run).launch().check()
+        run_words = enc.run_words()
+        records, chosen = [], []
+        for k, r in enumerate(sides):
+            rw = run_words[per * k:per * k + per]
+            rec, take = _wide_record(r, shifts[k], items[2 * k + 1][3] if per == 2 else None, [int(w.sum(dtype=np.uint64)) for w in rw], rw)
+            records.append(rec)
+            chosen.append(per * k + take)
+        words = enc.compact(chosen, run_words).launch().check().host()
+        settings = dict(_settings(args, n_frames, frame_hw), ans_run=run, ans_tables=wide, ans_wide=True)
+        blob = wstream.to_bytes(settings, records[:n_tensors], records[n_tensors:], embed_shape, raw, words)
+        _write_blob(path, blob)
+        return wstream.info(blob)
     counts = ops.SymHist([(s, r[4], r[5] - r[4] + 1) for s, r in zip(symbols, sides)]).launch().check().host()
     items = []
     for s, r, c in zip(symbols, sides, counts):
@@ -337,9 +395,6 @@ def _encode_empirical(model, entropy_model, args, frames_or_loader, path, run):
         records.append(rec)
         chosen.append(2 * k + take)
     words = enc.compact(chosen, run_words).launch().check().host()
-    frame_hw = _frame_hw(args, frames_or_loader, frame_hw)
-    sd = model.state_dict()
-    raw = [sd[k].detach().float().reshape(-1).cpu().numpy() for k in _raw_keys(model, is_hnerv)]
     settings = dict(_settings(args, n_frames, frame_hw), ans_run=run, ans_tables="empirical")
     blob = estream.to_bytes(settings, records[:n_tensors], records[n_tensors:], embed_shape, raw, words)
     _write_blob(path, blob)
@@ -371,18 +426,51 @@ def _repack_empirical(src, dst, run):
     return estream.info(blob)
 
 
-def repack(src, dst, run=1024, tables="gaussian"):
+def _repack_wide(src, dst, run, tables):
+    """repack(..., wide=True): the host oracle of encode(..., wide=True) -- the same shifts, tables, coder arithmetic (csrc/ans.cpp) and choice
+    rule, from the symbols of a version-1 or a chunked (BNRC) file."""
+    from .lib.entropy_model import ans_counts_cdf, ans_decode_gaussian, ans_encode_wide_runs, ans_gaussian_bucket_cdf
+    chunked = qstream.magic_of(src) == rstream.MAGIC
+    bs = rstream.read(src) if chunked else bitstream.read(src)
+    settings = dict(bs.settings, ans_run=run, ans_tables=tables, ans_wide=True)
+    words = []
+
+    def chunk(k, r):
+        shift = wstream.min_shift(r.lo, r.hi)
+        sym = rstream.decode_record(bs, k) if chunked else ans_decode_gaussian(r.words, r.count, r.lo, r.hi, float(r.mean), float(r.std))
+        cdfs = [ans_gaussian_bucket_cdf(r.lo, r.hi, shift, float(r.mean), float(r.std))]
+        if tables == "empirical":
+            cdfs.append(ans_counts_cdf(np.bincount((sym - r.lo) >> shift, minlength=wstream.n_buckets(r.lo, r.hi, shift))))
+        coded = [ans_encode_wide_runs(sym, r.lo, r.hi, cdf, shift, run) for cdf in cdfs]
+        rec, take = _wide_record((r.count, r.scale, r.mean, r.std, r.lo, r.hi, r.beta), shift, cdfs[1] if len(cdfs) == 2 else None,
+                                 [w.size for w, _ in coded], [rw for _, rw in coded])
+        words.append(coded[take][0])
+        return rec
+
+    tensors = [chunk(k, r) for k, r in enumerate(bs.tensors)]
+    embeds = [chunk(len(tensors) + k, r) for k, r in enumerate(bs.embeds)]
+    blob = wstream.to_bytes(settings, tensors, embeds, bs.embed_shape, bs.raw, np.concatenate(words) if words else np.zeros(0, dtype=np.uint32))
+    _write_blob(dst, blob)
+    return wstream.info(blob)
+
+
+def repack(src, dst, run=1024, tables="gaussian", wide=False):
     """A version-1 CEM file `src` (a file name, a binary file object or bytes) as the chunked kind `dst` (a file name or a binary file
     object): every record rANS-decoded on the host and re-encoded in independent runs of `run` symbols under the same Gaussian.  Header
     settings (plus "ans_run"), record order, side values and the raw section are copied.  Host only: no GPU, no retraining.  Returns
     rstream.info of what was written.
 
     tables="empirical": the chunked kind with per-record tables instead (estream.py) -- every record under its Gaussian or under the table
-    of its own histogram, whichever is smaller; `src` may then be a chunked file as well.  Returns estream.info."""
+    of its own histogram, whichever is smaller; `src` may then be a chunked file as well.  Returns estream.info.
+
+    wide=True: the wide kind (wstream.py) under either `tables`, for records of any span; `src` a version-1 or a chunked (BNRC) file.
+    Returns wstream.info."""
     from .lib.entropy_model import ans_decode_gaussian, ans_encode_gaussian_runs
     run = rstream.check_run(run)
     if tables not in TABLES:
         raise ValueError(f"codec.repack: tables = {tables!r} ({' | '.join(TABLES)})")
+    if wide:
+        return _repack_wide(src, dst, run, tables)
     if tables == "empirical":
         return _repack_empirical(src, dst, run)
     bs = bitstream.read(src)
@@ -393,7 +481,7 @@ def repack(src, dst, run=1024, tables="gaussian"):
     def chunk(r):
         if r.hi - r.lo + 1 > rstream.MAX_ALPHABET:
             raise NotImplementedError(f"codec.repack: a record's symbols span [{r.lo}, {r.hi}]: {r.hi - r.lo + 1} values; the chunked kind carries "
-                                      f"{rstream.MAX_ALPHABET} (the device decoder holds a record's table in LDS)")
+                                      f"{rstream.MAX_ALPHABET} (the device decoder holds a record's table in LDS); --wide takes it")
         sym = ans_decode_gaussian(r.words, r.count, r.lo, r.hi, float(r.mean), float(r.std))
         w, run_words = ans_encode_gaussian_runs(sym, r.lo, r.hi, float(r.mean), float(r.std), run)
         words.append(w)
@@ -423,17 +511,26 @@ def describe_empirical(budget):
             f"+ padding {budget['padding']}")
 
 
+def describe_wide(budget):
+    """One line of a wstream.info budget (the log of train_nerv_compression --bitstream_wide, `codec info`)."""
+    return (f"{describe_empirical(budget)}; wide: {budget['n_wide_records']} records with raw low bits, largest shift {budget['max_shift']}, "
+            f"tables {budget['ans_tables']}")
+
+
 def describe_any(budget):
-    """describe, describe_posthoc, describe_chunked or describe_empirical, by the budget's items."""
+    """describe, describe_posthoc, describe_chunked, describe_empirical or describe_wide, by the budget's items."""
+    if "max_shift" in budget:
+        return describe_wide(budget)
     if "tables" in budget:
         return describe_empirical(budget)
     return describe_chunked(budget) if "ans_words" in budget else describe_posthoc(budget) if "symbol_bits" in budget else describe(budget)
 
 
 def info(path_or_buffer):
-    """The bit budget of a file of any kind (bitstream.info, qstream.info, rstream.info or estream.info, by the magic number)."""
+    """The bit budget of a file of any kind (bitstream.info, qstream.info, rstream.info, estream.info or wstream.info, by the magic number)."""
     magic = qstream.magic_of(path_or_buffer)
-    return {qstream.MAGIC: qstream.info, rstream.MAGIC: rstream.info, estream.MAGIC: estream.info}.get(magic, bitstream.info)(path_or_buffer)
+    return {qstream.MAGIC: qstream.info, rstream.MAGIC: rstream.info, estream.MAGIC: estream.info,
+            wstream.MAGIC: wstream.info}.get(magic, bitstream.info)(path_or_buffer)
 
 
 def describe(budget):
@@ -561,12 +658,12 @@ class Decoder:
         from .lib.entropy_model import ans_decode_gaussian
         from .train_nerv_all import build_model
         magic = qstream.magic_of(path)
-        self.kind = {qstream.MAGIC: "posthoc", rstream.MAGIC: "chunked", estream.MAGIC: "empirical"}.get(magic, "cem")
+        self.kind = {qstream.MAGIC: "posthoc", rstream.MAGIC: "chunked", estream.MAGIC: "empirical", wstream.MAGIC: "wide"}.get(magic, "cem")
         if self.kind == "posthoc":
             self._load_posthoc(path, device)
             return self._frame_loop(use_graph, pack, matrix, range)
-        bs = {"chunked": rstream.read, "empirical": estream.read}.get(self.kind, bitstream.read)(path)
-        what = {"chunked": "rstream", "empirical": "estream"}.get(self.kind, "bitstream")
+        bs = {"chunked": rstream.read, "empirical": estream.read, "wide": wstream.read}.get(self.kind, bitstream.read)(path)
+        what = {"chunked": "rstream", "empirical": "estream", "wide": "wstream"}.get(self.kind, "bitstream")
         s = dict(bs.settings)
         if s.get("model") not in MODELS:
             raise ValueError(f"{what}: header names the model {s.get('model')!r}; this build decodes {', '.join(MODELS)}")
@@ -575,7 +672,7 @@ class Decoder:
         self.n_frames = int(s["full_data_length"])
         self.frame_hw = tuple(int(v) for v in s["crop_list"].split("_")[:2])
         self.is_hnerv = s["model"] == "HNeRV_Boost"
-        margs = SimpleNamespace(**{k: v for k, v in s.items() if k not in ("ans_run", "ans_tables")})
+        margs = SimpleNamespace(**{k: v for k, v in s.items() if k not in ("ans_run", "ans_tables", "ans_wide")})
         margs.__dict__.update(quant=False, outf="")
         model = build_model(margs)
         if self.is_hnerv:
@@ -600,7 +697,7 @@ class Decoder:
                 raise ValueError(f"{what}: embedding records in a {s['model']} stream")
             self.embeds = None
         records = list(bs.tensors) + list(bs.embeds)
-        if self.kind in ("chunked", "empirical"):
+        if self.kind in ("chunked", "empirical", "wide"):
             # the words as they lie in the file, every record's table and the run descriptors: one upload each, ONE launch that
             # entropy-decodes and de-quantises; its error word is read at the synchronisation below
             if any(not t.is_contiguous() for t in targets):
@@ -608,6 +705,9 @@ class Decoder:
             if self.kind == "chunked":
                 job = ops.AnsDequant(bs.words, [(t.reshape(-1), float(r.scale), r.lo, r.hi, float(r.mean), float(r.std), r.run_words,
                                                  None if r.beta is None else float(r.beta)) for t, r in zip(targets, records)], int(s["ans_run"])).launch()
+            elif self.kind == "wide":                      # the kernel that pops a record's raw low bits after every bucket
+                job = ops.AnsDequantWide(bs.words, [(t.reshape(-1), float(r.scale), r.lo, r.hi, wstream.record_cdf(r), r.shift, r.run_words,
+                                                     None if r.beta is None else float(r.beta)) for t, r in zip(targets, records)], int(s["ans_run"])).launch()
             else:                                          # the same kernel under the table each record names or carries
                 job = ops.AnsDequantTables(bs.words, [(t.reshape(-1), float(r.scale), r.lo, estream.record_cdf(r), r.run_words,
                                                        None if r.beta is None else float(r.beta)) for t, r in zip(targets, records)], int(s["ans_run"])).launch()
@@ -833,6 +933,8 @@ def build_parser():
     r.add_argument("--run", type=int, default=1024, help="symbols per independently coded run: a multiple of 64 in 64..4096")
     r.add_argument("--tables", choices=TABLES, default="gaussian", help="empirical: every record under its Gaussian or under the table of its own symbol "
                                                                         "histogram, whichever is smaller (SRC may then be a chunked file too)")
+    r.add_argument("--wide", action="store_true", help="write the wide kind (BNRW): a record may span more than 4096 symbol values -- a bucket under the "
+                                                       "table plus raw low bits (SRC: a version-1 or a BNRC file)")
     return p
 
 
@@ -844,7 +946,7 @@ def main(argv=None):
         print(json.dumps(budget))
         return budget
     if a.cmd == "repack":
-        budget = repack(a.src, a.dst, a.run, a.tables)
+        budget = repack(a.src, a.dst, a.run, a.tables, wide=a.wide)
         print(describe_any(budget))
         print(json.dumps(budget))
         return budget

@@ -30,9 +30,10 @@ struct Table {                       // cumulative slot counts: symbol i owns [c
 
 inline double phi(double x) { return 0.5 * erfc(-x * 0.70710678118654752440); }
 
-bool gaussian_table(int32_t lo, int32_t hi, double mean, double std, Table& t) {
-    if (hi < lo || !(std > 0.0) || !isfinite(mean) || !isfinite(std)) return false;
-    const int64_t n = (int64_t)hi - lo + 1;
+// shift > 0 (the wide runs): entry k is the bucket of the 2^shift integers from lo + (k << shift); the last may be partial
+bool gaussian_table(int32_t lo, int32_t hi, double mean, double std, Table& t, int shift = 0) {
+    if (hi < lo || shift < 0 || shift > 30 || !(std > 0.0) || !isfinite(mean) || !isfinite(std)) return false;
+    const int64_t n = ((int64_t)hi - lo + ((int64_t)1 << shift)) >> shift;
     if (n > (int64_t)TOTAL / 2) return false;
     const double free_slots = (double)(TOTAL - (uint32_t)n);
     const double c0 = phi((lo - 0.5 - mean) / std), c1 = phi((hi + 0.5 - mean) / std);
@@ -40,7 +41,7 @@ bool gaussian_table(int32_t lo, int32_t hi, double mean, double std, Table& t) {
     t.cdf.resize((size_t)n + 1);
     t.cdf[0] = 0;
     for (int64_t k = 1; k < n; ++k) {
-        double f = z > 0.0 ? (phi((lo + k - 0.5 - mean) / std) - c0) / z : (double)k / (double)n;
+        double f = z > 0.0 ? (phi((lo + (k << shift) - 0.5 - mean) / std) - c0) / z : (double)k / (double)n;
         f = f < 0.0 ? 0.0 : (f > 1.0 ? 1.0 : f);
         t.cdf[(size_t)k] = (uint32_t)(free_slots * f) + (uint32_t)k;             // leak: one slot per symbol below k
     }
@@ -72,17 +73,23 @@ bool categorical_table(const double* p, int K, Table& t) {
 
 // symbols are table indices 0 .. n-1
 // two_state_words: the final state always takes two words (low, high), zero ones included -- the runs of the chunked layout
-long encode(const Table& t, const int32_t* sym, size_t count, uint32_t* out, size_t cap, bool two_state_words = false) {
+// shift > 0: sym[i] = (table index << shift) | low; per symbol the low bits go in first, as `shift` raw bits under the implicit uniform
+// table (left = low << (24 - shift), prob = 1 << (24 - shift)), then the table index -- so the decoder pops the index first
+long encode(const Table& t, const int32_t* sym, size_t count, uint32_t* out, size_t cap, bool two_state_words = false, int shift = 0) {
     std::vector<uint32_t> rev;                                  // words in emission order; the message is this order REVERSED + state
     rev.reserve(count / 3 + 8);
     uint64_t state = 0;
     const int n = t.n();
-    for (size_t i = count; i-- > 0;) {
-        const int32_t s = sym[i];
-        if (s < 0 || s >= n) return -1;
-        const uint32_t left = t.cdf[(size_t)s], prob = t.cdf[(size_t)s + 1] - left;
+    auto push = [&](uint32_t left, uint32_t prob) {
         if ((state >> (64 - PREC)) >= prob) { rev.push_back((uint32_t)state); state >>= 32; }
         state = ((state / prob) << PREC) | (state % prob + left);
+    };
+    for (size_t i = count; i-- > 0;) {
+        if (sym[i] < 0) return -1;
+        const int32_t s = sym[i] >> shift;
+        if (s >= n) return -1;
+        if (shift) push(((uint32_t)sym[i] & ((1u << shift) - 1u)) << (PREC - shift), 1u << (PREC - shift));
+        push(t.cdf[(size_t)s], t.cdf[(size_t)s + 1] - t.cdf[(size_t)s]);
     }
     const size_t state_words = two_state_words ? 2 : state == 0 ? 0 : (state >> 32 ? 2 : 1);
     const size_t total = rev.size() + state_words;
@@ -126,7 +133,8 @@ int decode(const Table& t, const uint32_t* words, size_t n_words, size_t count, 
 
 // One run of the chunked layout: `n_words` words = bulk words + the final state as exactly two words, so the state's
 // place is known and the run is decoded once.  The refill rule is decode()'s.  Reads words[0 .. n_words) only.
-bool decode_run(const Table& t, const uint32_t* words, size_t n_words, size_t count, int32_t* sym) {
+// shift > 0: after the table index, `shift` raw bits (encode()); a value above max_off -- past the range in a partial last bucket -- fails the run
+bool decode_run(const Table& t, const uint32_t* words, size_t n_words, size_t count, int32_t* sym, int shift = 0, uint32_t max_off = 0xffffffffu) {
     if (n_words < 2) return false;
     const size_t bulk = n_words - 2;
     uint64_t state = (uint64_t)words[bulk] | ((uint64_t)words[bulk + 1] << 32);
@@ -135,9 +143,17 @@ bool decode_run(const Table& t, const uint32_t* words, size_t n_words, size_t co
         const uint32_t q = (uint32_t)(state & (TOTAL - 1));
         const size_t s = (size_t)(std::upper_bound(t.cdf.begin(), t.cdf.end(), q) - t.cdf.begin()) - 1;
         const uint32_t left = t.cdf[s], prob = t.cdf[s + 1] - left;
-        sym[i] = (int32_t)s;
+        uint32_t off = (uint32_t)s;
         state = (state >> PREC) * prob + (q - left);
         if ((state >> 32) == 0 && next < bulk) state = (state << 32) | words[next++];
+        if (shift) {
+            const uint32_t r = (uint32_t)(state & (TOTAL - 1));
+            off = (off << shift) | (r >> (PREC - shift));
+            state = ((state >> PREC) << (PREC - shift)) | (r & ((1u << (PREC - shift)) - 1u));
+            if ((state >> 32) == 0 && next < bulk) state = (state << 32) | words[next++];
+        }
+        if (off > max_off) return false;
+        sym[i] = (int32_t)off;
     }
     return next == bulk && state == 0;
 }
@@ -146,21 +162,21 @@ constexpr size_t MAX_RUN_WORDS = 65535;
 
 // The two run entry points of either model share these: `what` names the caller in the messages.
 long encode_runs(const Table& t, const char* what, const int32_t* symbols, size_t n, int32_t min_sym, int run, uint32_t* out_words, size_t cap_words,
-                 unsigned short* out_run_words) {
-    const int32_t max_sym = min_sym + t.n() - 1;
+                 unsigned short* out_run_words, int shift = 0, const int32_t* wide_max = nullptr) {
+    const int32_t max_sym = wide_max ? *wide_max : min_sym + t.n() - 1;
     std::vector<int32_t> idx(n);
     for (size_t i = 0; i < n; ++i) {
         if (symbols[i] < min_sym || symbols[i] > max_sym) { bnerv_set_error(BNERV_E_ARG, "%s: symbol %d outside [%d, %d]", what, symbols[i], min_sym, max_sym); return -1; }
         idx[i] = symbols[i] - min_sym;
     }
     // every run through encode() from an empty state, its final state written as two words whatever its size
-    std::vector<uint32_t> msg((size_t)run * PREC / 32 + 3);
+    std::vector<uint32_t> msg((size_t)run * (size_t)(PREC + shift) / 32 + 3);
     std::vector<uint32_t> all;
     all.reserve(n / 3 + 8);
     size_t k = 0;
     for (size_t at = 0; at < n; at += (size_t)run, ++k) {
         const size_t count = n - at < (size_t)run ? n - at : (size_t)run;
-        const long got = encode(t, idx.data() + at, count, msg.data(), msg.size(), true);
+        const long got = encode(t, idx.data() + at, count, msg.data(), msg.size(), true, shift);
         if (got < 2 || (size_t)got > msg.size()) { bnerv_set_error(BNERV_E_ARG, "%s: run %zu takes %ld words (%zu at most)", what, k, got, msg.size()); return -1; }
         all.insert(all.end(), msg.begin(), msg.begin() + got);
         if (out_run_words) out_run_words[k] = (unsigned short)got;
@@ -170,14 +186,14 @@ long encode_runs(const Table& t, const char* what, const int32_t* symbols, size_
 }
 
 int decode_runs(const Table& t, const char* what, const uint32_t* words, size_t n_words, const unsigned short* run_words, size_t n_runs, size_t n,
-                int32_t min_sym, int run, int32_t* symbols_out) {
+                int32_t min_sym, int run, int32_t* symbols_out, int shift = 0, uint32_t max_off = 0xffffffffu) {
     size_t total = 0;
     for (size_t k = 0; k < n_runs; ++k) total += run_words[k];
     BNERV_REQUIRE(total == n_words, "%s: the run lengths add up to %zu words, the message has %zu", what, total, n_words);
     size_t at = 0;
     for (size_t k = 0; k < n_runs; ++k) {
         const size_t first = k * (size_t)run, count = n - first < (size_t)run ? n - first : (size_t)run;
-        if (!decode_run(t, words + at, run_words[k], count, symbols_out + first))
+        if (!decode_run(t, words + at, run_words[k], count, symbols_out + first, shift, max_off))
             return bnerv_set_error(BNERV_E_ARG, "%s: run %zu (%u words at word %zu) does not decode to %zu symbols under this model",
                                    what, k, (unsigned)run_words[k], at, count);
         for (size_t i = 0; i < count; ++i) symbols_out[first + i] += min_sym;
@@ -267,6 +283,50 @@ extern "C" int bnerv_ans_decode_table_runs(const uint32_t* words, size_t n_words
     BNERV_REQUIRE(run >= 1 && n_runs == (n + (size_t)run - 1) / (size_t)run, "ans_decode_table_runs: %zu run lengths for %zu symbols in runs of %d", n_runs, n, run);
     BNERV_REQUIRE(given_table(cdf, A, t), "ans_decode_table_runs: bad table (%d symbols; strictly increasing from 0 to 2^24)", A);
     return decode_runs(t, "ans_decode_table_runs", words, n_words, run_words, n_runs, n, min_sym, run, symbols_out);
+}
+
+// ---- wide runs: a table over the B buckets of 2^shift values, the low bits raw in the same state
+namespace {
+// B for [min_sym, max_sym] at `shift`, or 0 where the three do not go together
+int wide_buckets(int32_t min_sym, int32_t max_sym, int shift) {
+    if (max_sym < min_sym || shift < 0 || shift > BNERV_RANSW_MAX_SHIFT) return 0;
+    const int64_t B = ((int64_t)max_sym - min_sym + ((int64_t)1 << shift)) >> shift;
+    return B >= 2 && B <= (int64_t)(TOTAL / 2) && (int64_t)max_sym - min_sym < ((int64_t)1 << 28) ? (int)B : 0;
+}
+}  // namespace
+
+extern "C" long bnerv_ans_gaussian_bucket_cdf(int32_t min_sym, int32_t max_sym, int shift, double mean, double std_, uint32_t* out_cdf, size_t cap) {
+    Table t;
+    if (shift < 0 || shift > BNERV_RANSW_MAX_SHIFT || !gaussian_table(min_sym, max_sym, mean, std_, t, shift)) {
+        bnerv_set_error(BNERV_E_ARG, "ans_gaussian_bucket_cdf: bad model (min %d max %d shift %d mean %g std %g)", min_sym, max_sym, shift, mean, std_);
+        return -1;
+    }
+    if (out_cdf && cap >= t.cdf.size()) std::copy(t.cdf.begin(), t.cdf.end(), out_cdf);
+    return (long)t.cdf.size();
+}
+
+extern "C" long bnerv_ans_encode_wide_runs(const int32_t* symbols, size_t n, int32_t min_sym, int32_t max_sym, const uint32_t* cdf, int B, int shift, int run,
+                                           uint32_t* out_words, size_t cap_words, unsigned short* out_run_words) {
+    Table t;
+    if (!symbols && n) { bnerv_set_error(BNERV_E_ARG, "ans_encode_wide_runs: null symbols"); return -1; }
+    if (B < 2 || wide_buckets(min_sym, max_sym, shift) != B) {
+        bnerv_set_error(BNERV_E_ARG, "ans_encode_wide_runs: %d buckets for [%d, %d] at shift %d (0..%d)", B, min_sym, max_sym, shift, BNERV_RANSW_MAX_SHIFT);
+        return -1;
+    }
+    if (run < 1 || (size_t)run * (size_t)(PREC + shift) / 32 + 3 > MAX_RUN_WORDS) { bnerv_set_error(BNERV_E_ARG, "ans_encode_wide_runs: run = %d (a run's words must fit 16 bits)", run); return -1; }
+    if (!given_table(cdf, B, t)) { bnerv_set_error(BNERV_E_ARG, "ans_encode_wide_runs: bad table (%d buckets; strictly increasing from 0 to 2^24)", B); return -1; }
+    return encode_runs(t, "ans_encode_wide_runs", symbols, n, min_sym, run, out_words, cap_words, out_run_words, shift, &max_sym);
+}
+
+extern "C" int bnerv_ans_decode_wide_runs(const uint32_t* words, size_t n_words, const unsigned short* run_words, size_t n_runs, size_t n,
+                                          int32_t min_sym, int32_t max_sym, const uint32_t* cdf, int B, int shift, int run, int32_t* symbols_out) {
+    Table t;
+    BNERV_REQUIRE((words || !n_words) && (symbols_out || !n) && (run_words || !n_runs), "ans_decode_wide_runs: null buffer");
+    BNERV_REQUIRE(run >= 1 && n_runs == (n + (size_t)run - 1) / (size_t)run, "ans_decode_wide_runs: %zu run lengths for %zu symbols in runs of %d", n_runs, n, run);
+    BNERV_REQUIRE(B >= 2 && wide_buckets(min_sym, max_sym, shift) == B, "ans_decode_wide_runs: %d buckets for [%d, %d] at shift %d (0..%d)", B, min_sym, max_sym, shift,
+                  BNERV_RANSW_MAX_SHIFT);
+    BNERV_REQUIRE(given_table(cdf, B, t), "ans_decode_wide_runs: bad table (%d buckets; strictly increasing from 0 to 2^24)", B);
+    return decode_runs(t, "ans_decode_wide_runs", words, n_words, run_words, n_runs, n, min_sym, run, symbols_out, shift, (uint32_t)((int64_t)max_sym - min_sym));
 }
 
 extern "C" long bnerv_ans_encode_gaussian(const int32_t* symbols, size_t n, int32_t min_sym, int32_t max_sym, double mean, double std_, uint32_t* out, size_t cap_words) {

@@ -1,0 +1,317 @@
+// ransw.hip -- the kernels of the chunked CEM file for records that span more than 4096 symbol values (boosting_nerv_amd/wstream.py,
+// codec.encode(..., wide=True)).  A record has a shift k: a symbol is  v - lo = (bucket << k) | low,  the bucket coded
+// under the record's table of B <= 4096 entries exactly as csrc/rans.hip and csrc/ransenc.hip code a symbol, `low` as k raw bits in the
+// same 64-bit state under the implicit uniform table (left = low << (24 - k), prob = 1 << (24 - k)).  With k = 0 nothing is added.
+//
+// sym_hist_wide     sym_hist of csrc/ransenc.hip over (sym - lo) >> k.
+// rans_encode_wide  rans_encode's block shape: one wave, up to 64 consecutive runs of ONE item, its table in LDS; lane k walks run k from
+//                   its last symbol to its first and pushes low, then the bucket, with encode()'s arithmetic of csrc/ans.cpp.  The offsets
+//                   need up to 28 bits, so they are staged as dwords, 64 per run and round, runs 65 dwords apart (65 mod 32 = 1: the lanes'
+//                   reads hit 32 banks).  Slots are `slot_words` apart; a lane may fill the last run * (24 + k) / 32 + 3 words of its own.
+// rans_dequant_wide rans_dequant's block shape and every clamp of it; per symbol the raw-bits step after the bucket:
+//                   q = state & (2^24 - 1), low = q >> (24 - k), state = ((state >> 24) << (24 - k)) | (q & (2^(24-k) - 1)), refill by the same
+//                   rule.  Decoded offsets are staged as full dwords, CH = 32 per lane and round with a lane stride of 33 dwords (rans.hip
+//                   stages 64 sixteen-bit symbols in the same 33 dwords), so static LDS stays 58 KB per block and two decode waves fit a CU.
+//                   An offset above hi - lo sets bit 0 of the error word and is clamped; it is a value, never an address.
+// Every index that comes from a descriptor is checked against the array it points into before it is used.
+#include "common.h"
+
+namespace {
+
+constexpr int WAVE = 64, MAX_A = BNERV_RANS_MAX_ALPHABET, PREC = 24, HIST_THREADS = 256, MAX_SHIFT = BNERV_RANSW_MAX_SHIFT;
+constexpr int ENC_CH = 64, ENC_STRIDE = ENC_CH + 1;
+constexpr int DEC_CH = 32, DEC_STRIDE = DEC_CH + 1, SPAN_WORDS = 8192, LUT_BITS = 8;
+constexpr unsigned MASK = (1u << PREC) - 1u;
+constexpr unsigned BAD = 0xffffffffu;                // a staged offset outside the range (offsets stay below 2^28)
+
+// the range and the table of an item go together: B buckets of 2^shift values cover [0, span_m1], the last one not empty
+__device__ __forceinline__ bool shape_ok(unsigned A, unsigned shift, unsigned span_m1) {
+    return shift <= (unsigned)MAX_SHIFT && A >= 2u && A <= (unsigned)MAX_A && span_m1 < (1u << 28) && (span_m1 >> shift) + 1u == A;
+}
+
+__global__ __launch_bounds__(HIST_THREADS) void sym_hist_wide_kernel(const bnerv_wsym_item* __restrict__ items, const unsigned n_items,
+                                                                     const unsigned* __restrict__ blocks, unsigned* __restrict__ counts,
+                                                                     const unsigned n_counts, int* __restrict__ err) {
+    __shared__ unsigned hist[MAX_A];
+    const unsigned item = blocks[2 * blockIdx.x], first = blocks[2 * blockIdx.x + 1];
+    bool ok = item < n_items;
+    bnerv_wsym_item it = {};
+    if (ok) it = items[item];
+    const unsigned A = it.alphabet;
+    ok = ok && it.sym != nullptr && shape_ok(A, it.shift, it.span_m1) && it.at <= n_counts && A <= n_counts - it.at && first < it.n;
+    if (!ok) {
+        if (threadIdx.x == 0) atomicOr(err, 2);
+        return;
+    }
+    for (unsigned i = threadIdx.x; i < A; i += HIST_THREADS) hist[i] = 0;
+    __syncthreads();
+    const unsigned end = it.n - first < (unsigned)BNERV_HIST_SLICE ? it.n : first + (unsigned)BNERV_HIST_SLICE;
+    bool bad = false;
+    for (unsigned i = first + threadIdx.x; i < end; i += HIST_THREADS) {
+        const unsigned s = (unsigned)it.sym[i] - (unsigned)it.lo;    // (wraps for a symbol below lo: then s > span_m1 as well)
+        if (s <= it.span_m1) atomicAdd(&hist[s >> it.shift], 1u);    // (s >> shift <= span_m1 >> shift = A - 1)
+        else bad = true;
+    }
+    if (bad) atomicOr(err, 1);
+    __syncthreads();
+    for (unsigned i = threadIdx.x; i < A; i += HIST_THREADS)
+        if (hist[i]) atomicAdd(&counts[it.at + i], hist[i]);
+}
+
+__global__ __launch_bounds__(WAVE) void rans_encode_wide_kernel(const bnerv_rans_block* __restrict__ blocks, const bnerv_wsym_item* __restrict__ items,
+                                                                const unsigned n_items, const unsigned* __restrict__ tables, const unsigned n_table_words,
+                                                                const unsigned run, unsigned* __restrict__ slots, const unsigned n_slots, const unsigned S,
+                                                                unsigned short* __restrict__ run_words, int* __restrict__ err) {
+    __shared__ unsigned cdf[MAX_A + 1];
+    __shared__ unsigned stage[WAVE * ENC_STRIDE];       // run rr's offsets at rr * ENC_STRIDE
+    const unsigned lane = threadIdx.x;
+    // ---- the block's descriptors, all uniform; anything that points outside the uploaded arrays ends the block before a dependent access
+    const bnerv_rans_block b = blocks[blockIdx.x];
+    bool ok = b.item < n_items;
+    bnerv_wsym_item it = {};
+    if (ok) it = items[b.item];
+    const unsigned A = it.alphabet, k = it.shift;
+    const unsigned item_runs = ok && it.n ? (it.n - 1u) / run + 1u : 0u;
+    ok = ok && it.sym != nullptr && shape_ok(A, k, it.span_m1) && it.at <= n_table_words && A + 1u <= n_table_words - it.at && b.first < item_runs;
+    const unsigned limit = ok ? run * ((unsigned)PREC + k) / 32u + 3u : 3u;      // the host's bound on a run's words at this shift
+    ok = ok && limit <= S;
+    const unsigned live = ok ? (item_runs - b.first < (unsigned)WAVE ? item_runs - b.first : (unsigned)WAVE) : 0u;
+    ok = ok && b.run <= n_slots && live <= n_slots - b.run;
+    if (!ok) {
+        if (lane == 0) atomicOr(err, 2);
+        return;
+    }
+    for (unsigned i = lane; i <= A; i += WAVE) cdf[i] = tables[it.at + i];
+
+    // ---- lane j: run b.first + j of the item, slot b.run + j
+    const bool active = lane < live;
+    const unsigned first_elem = (b.first + lane) * run;                   // (< it.n < 2^31 for an active lane)
+    const unsigned cnt = active ? (it.n - first_elem < run ? it.n - first_elem : run) : 0u;
+    unsigned* const slot = slots + (size_t)(b.run + (active ? lane : 0u)) * S;
+    const unsigned floor_p = S - limit;                                   // the slot's usable part is slot[floor_p .. S)
+    unsigned p = S - 2;                                                   // the next word goes to slot[--p]; slot[S - 2], slot[S - 1]: the state
+    bool dead = false;
+    unsigned long long state = 0;
+    // the first half of encode()'s step: a word leaves when the state has no room for `prob`; false when it would leave the usable part of the slot
+    auto make_room = [&](unsigned prob) -> bool {
+        if ((state >> (64 - PREC)) >= prob) {
+            if (p <= floor_p) return false;
+            slot[--p] = (unsigned)state;
+            state >>= 32;
+        }
+        return true;
+    };
+    const unsigned low_mask = (1u << k) - 1u, low_bits = (unsigned)PREC - k;
+    const unsigned long long keep = (1ull << low_bits) - 1ull;
+    const unsigned block_cnt = it.n - b.first * run < run ? it.n - b.first * run : run;      // lane 0's count: no lane has more
+    for (unsigned r = (block_cnt + ENC_CH - 1) / ENC_CH; r-- > 0;) {
+        __syncthreads();                                                  // (the table on the first pass, the last round's reads after)
+        const unsigned e = r * ENC_CH + lane;
+        for (unsigned rr = 0; rr < live; ++rr) {
+            const unsigned f = (b.first + rr) * run, c = it.n - f < run ? it.n - f : run;
+            if (e < c) {
+                const unsigned s = (unsigned)it.sym[(size_t)f + e] - (unsigned)it.lo;
+                stage[rr * ENC_STRIDE + lane] = s <= it.span_m1 ? s : BAD;
+            }
+        }
+        __syncthreads();
+        const unsigned have = cnt > r * ENC_CH ? (cnt - r * ENC_CH < (unsigned)ENC_CH ? cnt - r * ENC_CH : (unsigned)ENC_CH) : 0u;
+        for (unsigned j = have; j-- > 0;) {
+            const unsigned s = stage[lane * ENC_STRIDE + j];
+            if (dead) continue;
+            if (s == BAD) { dead = true; continue; }
+            if (k) {                                                      // the raw bits: prob = 2^low_bits, so the division is a shift
+                if (!make_room(1u << low_bits)) { dead = true; continue; }
+                state = ((state >> low_bits) << PREC) | ((state & keep) + ((unsigned long long)(s & low_mask) << low_bits));
+            }
+            const unsigned bucket = s >> k;                               // (<= span_m1 >> k = A - 1)
+            const unsigned left = cdf[bucket], prob = cdf[bucket + 1] - left;
+            if (!make_room(prob)) { dead = true; continue; }
+            state = ((state / prob) << PREC) | (state % prob + left);
+        }
+    }
+    if (active) {
+        if (dead) {
+            atomicOr(err, 1);
+            run_words[b.run + lane] = 0;
+        } else {
+            slot[S - 2] = (unsigned)state;
+            slot[S - 1] = (unsigned)(state >> 32);
+            run_words[b.run + lane] = (unsigned short)(S - p);            // (<= limit <= 4096 * 40 / 32 + 3 = 5123)
+        }
+    }
+}
+
+// the product and the sum as two IEEE fp32 operations (see codec.hip on the pragma): Scale_T's `quant * scale`, ScaleBeta_T's `+ beta`
+__device__ __forceinline__ float dequant1(int q, float s, float b, bool has_beta) {
+#pragma clang fp contract(off)
+    const float v = (float)q * s;
+    return has_beta ? v + b : v;
+}
+
+__global__ __launch_bounds__(WAVE) void rans_dequant_wide_kernel(const unsigned* __restrict__ words, const unsigned n_words, const unsigned* __restrict__ run_start,
+                                                                 const unsigned n_runs, const bnerv_rans_block* __restrict__ blocks,
+                                                                 const bnerv_ransw_item* __restrict__ items, const unsigned n_items,
+                                                                 const unsigned* __restrict__ tables, const unsigned n_table_words, const unsigned run,
+                                                                 int* __restrict__ err) {
+    __shared__ unsigned cdf[MAX_A + 1];
+    __shared__ unsigned span[SPAN_WORDS];
+    __shared__ unsigned stage[WAVE * DEC_STRIDE];
+    __shared__ unsigned lut[1 << LUT_BITS];
+    const unsigned lane = threadIdx.x;
+    // ---- the block's descriptors, all uniform; anything that points outside the uploaded arrays ends the block before a dependent load
+    const bnerv_rans_block b = blocks[blockIdx.x];
+    bool ok = b.item < n_items && b.run < n_runs;
+    bnerv_ransw_item it = {};
+    if (ok) it = items[b.item];
+    const unsigned A = it.alphabet, k = it.shift;
+    const unsigned item_runs = ok && it.n ? (it.n - 1u) / run + 1u : 0u;
+    ok = ok && it.out != nullptr && shape_ok(A, k, it.span_m1) && it.table <= n_table_words && A + 1u <= n_table_words - it.table && b.first < item_runs;
+    const unsigned live = ok ? (item_runs - b.first < (unsigned)WAVE ? item_runs - b.first : (unsigned)WAVE) : 0u;
+    ok = ok && live <= n_runs - b.run;
+    unsigned w0 = 0, w1 = 0;
+    if (ok) {
+        w0 = run_start[b.run];
+        w1 = run_start[b.run + live];
+        ok = w0 <= w1 && w1 <= n_words;
+    }
+    if (!ok) {
+        if (lane == 0) atomicOr(err, 2);
+        return;
+    }
+    for (unsigned i = lane; i <= A; i += WAVE) cdf[i] = tables[it.table + i];
+    // the words of the block's runs go to LDS in one coalesced sweep, so a refill is an LDS read; a part that does not fit is read from memory
+    const unsigned nw = w1 - w0;
+    const bool staged = nw <= (unsigned)SPAN_WORDS;
+    if (staged)
+        for (unsigned i = lane; i < nw; i += WAVE) span[i] = words[w0 + i];
+    __syncthreads();
+    auto fetch = [&](unsigned i) -> unsigned { return staged ? span[i - w0] : words[i]; };      // callers keep w0 <= i < w1
+    // the largest sym in [from, from + 2 * bit) with cdf[sym] <= q, by bit descent.  cdf[A] = 2^24 > q, so a candidate at or past A is never taken
+    auto search = [&](unsigned from, unsigned bit, unsigned q) -> unsigned {
+        unsigned sym = from;
+        for (; bit; bit >>= 1) {
+            const unsigned c = sym + bit;
+            sym = cdf[c < A ? c : A] <= q ? c : sym;
+        }
+        return sym;
+    };
+    const unsigned top = 1u << (31 - __clz((int)(A - 1u)));              // the highest power of two <= A - 1: the first step of a search of the whole table
+    // first level (csrc/rans.hip): entry e answers every q whose top LUT_BITS bits are e
+    for (unsigned e = lane; e < (1u << LUT_BITS); e += WAVE) {
+        const unsigned a = search(0, top, e << (PREC - LUT_BITS)), z = search(0, top, ((e + 1u) << (PREC - LUT_BITS)) - 1u);
+        lut[e] = a | ((z > a ? 1u << (31 - __clz((int)(z - a))) : 0u) << 16);
+    }
+    __syncthreads();
+
+    // ---- lane j: run b.run + j, words [s, e) inside [w0, w1), the last two of them the state
+    const bool active = lane < live;
+    const unsigned first_elem = (b.first + lane) * run;                   // (< it.n < 2^31 for an active lane)
+    const unsigned cnt = active ? (it.n - first_elem < run ? it.n - first_elem : run) : 0u;
+    unsigned next = w0, bulk_end = w0, bad = 0;
+    unsigned long long state = 0;
+    if (active) {
+        unsigned s = run_start[b.run + lane], e = run_start[b.run + lane + 1];
+        s = s < w0 ? w0 : (s > w1 ? w1 : s);
+        e = e < s ? s : (e > w1 ? w1 : e);
+        if (e - s < 2u) {
+            bad = 1;                                                      // no state words: decodes zeros from an empty state, refills nothing
+            next = bulk_end = s;
+        } else {
+            next = s;
+            bulk_end = e - 2u;
+            state = (unsigned long long)fetch(e - 2u) | ((unsigned long long)fetch(e - 1u) << 32);
+        }
+    }
+    const unsigned low_bits = (unsigned)PREC - k, keep = (1u << low_bits) - 1u;
+    const unsigned block_cnt = it.n - b.first * run < run ? it.n - b.first * run : run;      // lane 0's count: no lane has more
+    const unsigned rounds = (block_cnt + DEC_CH - 1) / DEC_CH;
+    const bool has_beta = it.has_beta != 0;
+    for (unsigned r = 0; r < rounds; ++r) {
+        for (unsigned j = 0; j < (unsigned)DEC_CH; ++j) {
+            unsigned off = 0;
+            if (r * DEC_CH + j < cnt) {
+                const unsigned q = (unsigned)state & MASK;
+                const unsigned ent = lut[q >> (PREC - LUT_BITS)];
+                const unsigned sym = search(ent & 0xffffu, ent >> 16, q);
+                const unsigned left = cdf[sym], prob = cdf[sym + 1] - left;
+                state = (state >> PREC) * prob + (q - left);
+                if ((state >> 32) == 0 && next < bulk_end) state = (state << 32) | fetch(next++);
+                off = sym << k;                                           // (sym < A <= 4096, k <= 16: below 2^28)
+                if (k) {
+                    const unsigned q2 = (unsigned)state & MASK;
+                    off |= q2 >> low_bits;
+                    state = ((state >> PREC) << low_bits) | (q2 & keep);
+                    if ((state >> 32) == 0 && next < bulk_end) state = (state << 32) | fetch(next++);
+                }
+                if (off > it.span_m1) { bad = 1; off = it.span_m1; }      // past hi in the last bucket: flagged, clamped
+            }
+            stage[lane * DEC_STRIDE + j] = off;
+        }
+        __syncthreads();
+        // store: run rr of the block, elements r * DEC_CH + (lane & 31) of runs rr and rr + 1 (the two halves of the wave)
+        const unsigned e = r * DEC_CH + (lane & (DEC_CH - 1u));
+        for (unsigned rr = lane >> 5; rr < live; rr += 2) {
+            const unsigned f = (b.first + rr) * run, c = it.n - f < run ? it.n - f : run;
+            if (e < c) {
+                const unsigned off = stage[rr * DEC_STRIDE + (lane & (DEC_CH - 1u))];
+                it.out[(size_t)f + e] = dequant1((int)((unsigned)it.lo + off), it.scale, it.beta, has_beta);
+            }
+        }
+        __syncthreads();
+    }
+    if (active && (bad || next != bulk_end || state != 0)) atomicOr(err, 1);
+}
+
+bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+}  // namespace
+
+extern "C" int bnerv_sym_hist_wide(void* stream, const bnerv_wsym_item* items, int n_items, const uint32_t* blocks, size_t n_blocks, uint32_t* counts,
+                                   size_t n_counts, int* err) {
+    BNERV_REQUIRE(items && blocks && counts && err, "sym_hist_wide: null args");
+    BNERV_REQUIRE(n_items > 0 && n_blocks > 0 && n_blocks <= 0x7fffffffu && n_counts > 0 && n_counts <= 0xffffffffu, "sym_hist_wide: n_items=%d n_blocks=%zu n_counts=%zu",
+                  n_items, n_blocks, n_counts);
+    BNERV_REQUIRE(aligned(items, 8) && aligned(blocks, 4) && aligned(counts, 4) && aligned(err, 4), "sym_hist_wide: items (8 bytes) / blocks / counts / err (4) are not aligned");
+    hipLaunchKernelGGL(sym_hist_wide_kernel, dim3((unsigned)n_blocks), dim3(HIST_THREADS), 0, reinterpret_cast<hipStream_t>(stream), items, (unsigned)n_items,
+                       reinterpret_cast<const unsigned*>(blocks), reinterpret_cast<unsigned*>(counts), (unsigned)n_counts, err);
+    BNERV_LAUNCH_CHECK("sym_hist_wide");
+    return BNERV_OK;
+}
+
+extern "C" int bnerv_rans_encode_wide(void* stream, const bnerv_rans_block* blocks, size_t n_blocks, const bnerv_wsym_item* items, int n_items,
+                                      const uint32_t* tables, size_t n_table_words, int run, uint32_t* slots, size_t n_slots, int slot_words,
+                                      unsigned short* run_words, int* err) {
+    BNERV_REQUIRE(blocks && items && tables && slots && run_words && err, "rans_encode_wide: null args");
+    BNERV_REQUIRE(run >= BNERV_RANS_MIN_RUN && run <= BNERV_RANS_MAX_RUN && run % WAVE == 0, "rans_encode_wide: run = %d (a multiple of %d in %d..%d)", run, WAVE,
+                  BNERV_RANS_MIN_RUN, BNERV_RANS_MAX_RUN);
+    BNERV_REQUIRE(slot_words >= run * PREC / 32 + 3 && slot_words <= run * (PREC + MAX_SHIFT) / 32 + 3, "rans_encode_wide: slot_words = %d (%d..%d at run %d)", slot_words,
+                  run * PREC / 32 + 3, run * (PREC + MAX_SHIFT) / 32 + 3, run);
+    BNERV_REQUIRE(n_slots > 0 && n_slots < 0x7fffffffu && n_blocks > 0 && n_blocks <= 0x7fffffffu && n_items > 0 && n_table_words >= 3 && n_table_words <= 0xffffffffu,
+                  "rans_encode_wide: n_slots=%zu n_blocks=%zu n_items=%d n_table_words=%zu", n_slots, n_blocks, n_items, n_table_words);
+    BNERV_REQUIRE(aligned(blocks, 16) && aligned(items, 8) && aligned(tables, 4) && aligned(slots, 4) && aligned(run_words, 2) && aligned(err, 4),
+                  "rans_encode_wide: blocks (16 bytes) / items (8) / tables / slots / err (4) / run_words (2) are not aligned");
+    hipLaunchKernelGGL(rans_encode_wide_kernel, dim3((unsigned)n_blocks), dim3(WAVE), 0, reinterpret_cast<hipStream_t>(stream), blocks, items, (unsigned)n_items,
+                       reinterpret_cast<const unsigned*>(tables), (unsigned)n_table_words, (unsigned)run, reinterpret_cast<unsigned*>(slots), (unsigned)n_slots,
+                       (unsigned)slot_words, run_words, err);
+    BNERV_LAUNCH_CHECK("rans_encode_wide");
+    return BNERV_OK;
+}
+
+extern "C" int bnerv_rans_dequant_wide(void* stream, const uint32_t* words, size_t n_words, const uint32_t* run_start, size_t n_runs,
+                                       const bnerv_rans_block* blocks, size_t n_blocks, const bnerv_ransw_item* items, int n_items,
+                                       const uint32_t* tables, size_t n_table_words, int run, int* err) {
+    BNERV_REQUIRE(words && run_start && blocks && items && tables && err, "rans_dequant_wide: null args");
+    BNERV_REQUIRE(run >= BNERV_RANS_MIN_RUN && run <= BNERV_RANS_MAX_RUN && run % WAVE == 0, "rans_dequant_wide: run = %d (a multiple of %d in %d..%d)", run, WAVE,
+                  BNERV_RANS_MIN_RUN, BNERV_RANS_MAX_RUN);
+    BNERV_REQUIRE(n_words >= 2 && n_words <= 0xffffffffu && n_runs > 0 && n_runs < 0x7fffffffu && n_blocks > 0 && n_blocks <= 0x7fffffffu && n_items > 0
+                  && n_table_words >= 3 && n_table_words <= 0xffffffffu, "rans_dequant_wide: n_words=%zu (two of them padding) n_runs=%zu n_blocks=%zu n_items=%d n_table_words=%zu",
+                  n_words, n_runs, n_blocks, n_items, n_table_words);
+    BNERV_REQUIRE(aligned(words, 4) && aligned(run_start, 4) && aligned(tables, 4) && aligned(err, 4), "rans_dequant_wide: words / run_start / tables / err are not 4-byte aligned");
+    BNERV_REQUIRE(aligned(blocks, 16) && aligned(items, 8), "rans_dequant_wide: the descriptor tables are not aligned (blocks 16, items 8 bytes)");
+    hipLaunchKernelGGL(rans_dequant_wide_kernel, dim3((unsigned)n_blocks), dim3(WAVE), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const unsigned*>(words),
+                       (unsigned)n_words, reinterpret_cast<const unsigned*>(run_start), (unsigned)n_runs, blocks, items, (unsigned)n_items,
+                       reinterpret_cast<const unsigned*>(tables), (unsigned)n_table_words, (unsigned)run, err);
+    BNERV_LAUNCH_CHECK("rans_dequant_wide");
+    return BNERV_OK;
+}

@@ -145,6 +145,47 @@ def ans_decode_table_runs(words, run_words, n, lo, cdf, run):
     return out[:n]
 
 
+def ans_gaussian_bucket_cdf(lo, hi, shift, mean, std):
+    """ans_gaussian_cdf over the ceil((hi - lo + 1) / 2^shift) buckets of 2^shift values from lo: bucket j starts at
+    lo + j * 2^shift - 0.5, the last ends at hi + 0.5.  With shift 0 it is ans_gaussian_cdf entry for entry."""
+    lib = L.load()
+    need = lib.bnerv_ans_gaussian_bucket_cdf(int(lo), int(hi), int(shift), float(mean), float(std), None, 0)
+    if need < 0:
+        L.check(-1, "bnerv_ans_gaussian_bucket_cdf")
+    out = np.empty(need, dtype=np.uint32)
+    assert lib.bnerv_ans_gaussian_bucket_cdf(int(lo), int(hi), int(shift), float(mean), float(std), out.ctypes.data, out.size) == need
+    return out
+
+
+def ans_encode_wide_runs(symbols, lo, hi, cdf, shift, run):
+    """ans_encode_table_runs for a range of any width: symbol - lo = (bucket << shift) | low, the bucket under `cdf` (one
+    entry per bucket), low as `shift` raw bits in the same state.  A run takes at most run * (24 + shift) / 32 + 3 words."""
+    lib = L.load()
+    sym, t = _i32(symbols), np.ascontiguousarray(cdf, dtype=np.uint32)
+    run_words = np.zeros(max((sym.size + int(run) - 1) // max(int(run), 1), 1), dtype=np.uint16)
+    args = (sym.ctypes.data, sym.size, int(lo), int(hi), t.ctypes.data, t.size - 1, int(shift), int(run))
+    need = lib.bnerv_ans_encode_wide_runs(*args, None, 0, run_words.ctypes.data)
+    if need < 0:
+        L.check(-1, "bnerv_ans_encode_wide_runs")
+    out = np.empty(max(need, 1), dtype=np.uint32)
+    got = lib.bnerv_ans_encode_wide_runs(*args, out.ctypes.data, out.size, run_words.ctypes.data)
+    assert got == need
+    return out[:need], run_words[:(sym.size + int(run) - 1) // int(run)]
+
+
+def ans_decode_wide_runs(words, run_words, n, lo, hi, cdf, shift, run):
+    """The inverse of ans_encode_wide_runs -> int32 symbols; raises BnervError naming the first run that does not decode, a value above
+    `hi` in the last bucket included."""
+    lib = L.load()
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    rw = np.ascontiguousarray(run_words, dtype=np.uint16)
+    t = np.ascontiguousarray(cdf, dtype=np.uint32)
+    out = np.empty(max(int(n), 1), dtype=np.int32)
+    L.check(lib.bnerv_ans_decode_wide_runs(w.ctypes.data, w.size, rw.ctypes.data, rw.size, int(n), int(lo), int(hi), t.ctypes.data, t.size - 1, int(shift),
+                                           int(run), out.ctypes.data), "bnerv_ans_decode_wide_runs")
+    return out[:n]
+
+
 def ans_encode_categorical(symbols, probs):
     """symbols 0 .. K-1 under probs[K] -> uint32 words."""
     lib = L.load()

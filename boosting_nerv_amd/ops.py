@@ -1373,6 +1373,213 @@ class AnsCompact:
         return self.words.cpu().numpy().view(np.uint32)
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# records that span more than 4096 symbol values (wstream.py, codec.encode(..., wide=True); csrc/ransw.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+def _wide_shape(what, k, lo, hi, shift, cdf=None):
+    """Validates the (range, shift, table) of a wide item -> (lo, hi, shift, B, cdf): B = ceil((hi - lo + 1) / 2^shift) buckets, 2..4096,
+    and, where a table is given, its B + 1 entries rising strictly from 0 to 2^24."""
+    import numpy as np
+    lo, hi, shift = int(lo), int(hi), int(shift)
+    if not 0 <= shift <= L.RANSW_MAX_SHIFT:
+        raise ValueError(f"{what}: item {k}: shift = {shift} (0..{L.RANSW_MAX_SHIFT})")
+    B = (hi - lo + (1 << shift)) >> shift
+    if hi < lo or hi - lo >= 1 << 28 or not 2 <= B <= L.RANS_MAX_ALPHABET:
+        raise ValueError(f"{what}: item {k}: the range [{lo}, {hi}] at shift {shift} has {B} buckets (2..{L.RANS_MAX_ALPHABET})")
+    if cdf is not None:
+        cdf = np.ascontiguousarray(cdf, dtype=np.uint32).reshape(-1)
+        if cdf.size - 1 != B:
+            raise ValueError(f"{what}: item {k}: a table of {cdf.size - 1} buckets for the {B} of [{lo}, {hi}] at shift {shift}")
+        if cdf[0] != 0 or cdf[-1] != 1 << 24 or (np.diff(cdf.astype(np.int64)) <= 0).any():
+            raise ValueError(f"{what}: item {k}: the cumulative table does not rise strictly from 0 to 2^24")
+    return lo, hi, shift, B, cdf
+
+
+_WSYM_DTYPE = [("sym", "<u8"), ("n", "<u4"), ("lo", "<i4"), ("alphabet", "<u4"), ("at", "<u4"), ("shift", "<u4"), ("span_m1", "<u4")]
+
+
+class SymHistWide(SymHist):
+    """SymHist over buckets, ONE launch (bnerv_sym_hist_wide): counts of (symbol - lo) >> shift.
+
+        items      one (symbols, lo, hi, shift) per record: symbols a contiguous int32 device tensor (any 4-byte alignment), counted on
+                   [lo, hi] in ceil((hi - lo + 1) / 2^shift) buckets (2..4096), shift in 0..16
+    launch(), check(), host() as SymHist's."""
+
+    def __init__(self, items):
+        import numpy as np
+        if not items:
+            raise ValueError("sym_hist_wide: no items")
+        device = _symbol_items(items, "sym_hist_wide")
+        table = np.zeros(len(items), dtype=np.dtype(_WSYM_DTYPE))
+        assert table.dtype.itemsize == C.sizeof(L.WsymItem)
+        blocks, self.offsets, self.alphabets, at = [], [], [], 0
+        for k, (sym, lo, hi, shift) in enumerate(items):
+            lo, hi, shift, B, _ = _wide_shape("sym_hist_wide", k, lo, hi, shift)
+            table[k] = (sym.data_ptr(), sym.numel(), lo, B, at, shift, hi - lo)
+            first = np.arange(0, sym.numel(), L.HIST_SLICE, dtype=np.uint32)
+            blocks.append(np.stack([np.full(first.size, k, dtype=np.uint32), first], axis=1))
+            self.offsets.append(at)
+            self.alphabets.append(B)
+            at += B
+        blocks = np.concatenate(blocks)
+        self.items, self.blocks = _upload(table, device), _upload(blocks, device)
+        self.n_items, self.n_blocks, self.n_counts = len(items), int(blocks.shape[0]), at
+        self.counts = torch.zeros(at, dtype=torch.int32, device=device)
+        self.err = torch.zeros(1, dtype=torch.int32, device=device)
+        self._keep = [it[0] for it in items]
+
+    def launch(self, zero=True):
+        if zero:
+            self.counts.zero_()
+        L.check(L.load().bnerv_sym_hist_wide(L.stream(), L.ptr(self.items), self.n_items, L.ptr(self.blocks), self.n_blocks, L.ptr(self.counts), self.n_counts,
+                                             L.ptr(self.err)), "bnerv_sym_hist_wide")
+        return self
+
+
+def sym_hist_wide(items):
+    """The uint32 numpy bucket histogram of every item, one launch.  Arguments: SymHistWide.  Raises ValueError for a symbol outside its range."""
+    return SymHistWide(items).launch().check().host()
+
+
+class AnsEncodeRunsWide(AnsEncodeRuns):
+    """AnsEncodeRuns for ranges of any width (bnerv_rans_encode_wide, bnerv_rans_compact), the inverse of AnsDequantWide.
+
+        items      one (symbols, lo, hi, cdf, shift) per message: symbols a contiguous int32 device tensor in [lo, hi] (any 4-byte alignment; items
+                   may share one), cdf the cumulative table of its B = ceil((hi - lo + 1) / 2^shift) buckets (uint32 numpy, B + 1 entries
+                   rising strictly from 0 to 2^24, 2 <= B <= 4096), shift in 0..16
+        run        symbols per run: a multiple of 64 in 64..4096
+    A run of an item may take run * (24 + shift) / 32 + 3 words, the host coder's bound; the slots of one launch are as far apart as the
+    largest shift needs.  launch(), check(), run_words(), compact(), result() as AnsEncodeRuns's: bit for bit what
+    lib.entropy_model.ans_encode_wide_runs returns item by item."""
+
+    def __init__(self, items, run):
+        import numpy as np
+        if not items:
+            raise ValueError("ans_encode_runs_wide: no items")
+        run = int(run)
+        if not L.RANS_MIN_RUN <= run <= L.RANS_MAX_RUN or run % 64:
+            raise ValueError(f"ans_encode_runs_wide: run = {run} (a multiple of 64 in {L.RANS_MIN_RUN}..{L.RANS_MAX_RUN})")
+        self.run = run
+        self.device = device = _symbol_items(items, "ans_encode_runs_wide")
+        table = np.zeros(len(items), dtype=np.dtype(_WSYM_DTYPE))
+        assert table.dtype.itemsize == C.sizeof(L.WsymItem)
+        cdfs, blocks, self.first_run, at_table, at_run, top = [], [], [], 0, 0, 0
+        for k, (sym, lo, hi, cdf, shift) in enumerate(items):
+            lo, hi, shift, B, cdf = _wide_shape("ans_encode_runs_wide", k, lo, hi, shift, cdf)
+            n_runs = (sym.numel() + run - 1) // run
+            table[k] = (sym.data_ptr(), sym.numel(), lo, B, at_table, shift, hi - lo)
+            cdfs.append(cdf)
+            at_table += cdf.size
+            top = max(top, shift)
+            first = np.arange(0, n_runs, 64, dtype=np.uint32)
+            blk = np.zeros((first.size, 4), dtype=np.uint32)
+            blk[:, 0], blk[:, 1], blk[:, 2] = k, at_run + first, first
+            blocks.append(blk)
+            self.first_run.append(at_run)
+            at_run += n_runs
+        self.first_run.append(at_run)
+        self.slot_words = run * (24 + top) // 32 + 3
+        blocks = np.concatenate(blocks)
+        if at_run * self.slot_words >= 2 ** 32:
+            raise ValueError(f"ans_encode_runs_wide: {at_run} runs of {run} symbols need more than 2^32 scratch words")
+        self.items, self.blocks, self.tables = _upload(table, device), _upload(blocks, device), _upload(np.concatenate(cdfs), device)
+        self.n_items, self.n_blocks, self.n_table_words, self.n_slots = len(items), int(blocks.shape[0]), at_table, at_run
+        self.slots = torch.empty(at_run * self.slot_words, dtype=torch.int32, device=device)
+        self.counts = torch.zeros(at_run, dtype=torch.int16, device=device)
+        self.err = torch.zeros(1, dtype=torch.int32, device=device)
+        self._keep = [it[0] for it in items]
+
+    def launch(self):
+        L.check(L.load().bnerv_rans_encode_wide(L.stream(), L.ptr(self.blocks), self.n_blocks, L.ptr(self.items), self.n_items, L.ptr(self.tables),
+                                                self.n_table_words, self.run, L.ptr(self.slots), self.n_slots, self.slot_words, L.ptr(self.counts),
+                                                L.ptr(self.err)), "bnerv_rans_encode_wide")
+        return self
+
+    def check(self):
+        e = int(self.err.item())
+        if e != 0:
+            raise ValueError("ans_encode_runs_wide: " + ("a descriptor points outside the uploaded arrays" if e & 2 else
+                                                         "a symbol lies outside its range (or a run outgrew its slot)"))
+        return self
+
+
+class AnsDequantWide(AnsDequant):
+    """AnsDequantTables for records of any width (wstream.py): the same uploads, launch() and check(), with the kernel
+    that pops `shift` raw bits after every bucket (bnerv_rans_dequant_wide).
+
+        items      one (out, scale, lo, hi, cdf, shift, run_words, beta) per record: [lo, hi] the symbol range, cdf the cumulative table of its
+                   B = ceil((hi - lo + 1) / 2^shift) buckets (uint32 numpy, B + 1 entries rising strictly from 0 to 2^24, 2 <= B <= 4096),
+                   shift in 0..16; the rest as in AnsDequant"""
+
+    def __init__(self, words, items, run):
+        import numpy as np
+        if not items:
+            raise ValueError("ans_dequant_wide: no items")
+        run = int(run)
+        if not L.RANS_MIN_RUN <= run <= L.RANS_MAX_RUN or run % 64:
+            raise ValueError(f"ans_dequant_wide: run = {run} (a multiple of 64 in {L.RANS_MIN_RUN}..{L.RANS_MAX_RUN})")
+        self.run = run
+        words = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        table = np.zeros(len(items), dtype=np.dtype([("out", "<u8"), ("scale", "<f4"), ("beta", "<f4"), ("lo", "<i4"), ("n", "<u4"), ("table", "<u4"),
+                                                     ("alphabet", "<u4"), ("has_beta", "<i4"), ("shift", "<u4"), ("span_m1", "<u4"), ("_pad", "<u4")]))
+        assert table.dtype.itemsize == C.sizeof(L.RanswItem)
+        device = items[0][0].device
+        cdfs, lengths, blocks, at_table, at_run = [], [], [], 0, 0
+        for k, (out, scale, lo, hi, cdf, shift, run_words, beta) in enumerate(items):
+            L.require_device(out, "out")
+            n = out.numel()
+            if out.dtype != torch.float32 or not out.is_contiguous() or n == 0 or n >= 2 ** 31 or out.data_ptr() % 4 or out.device != device:
+                raise ValueError(f"ans_dequant_wide: item {k}: out must be a non-empty contiguous 4-byte aligned fp32 tensor on {device} (below 2^31 elements)")
+            lo, hi, shift, B, cdf = _wide_shape("ans_dequant_wide", k, lo, hi, shift, cdf)
+            rw = np.ascontiguousarray(run_words, dtype=np.uint16).reshape(-1)
+            n_runs = (n + run - 1) // run
+            if rw.size != n_runs:
+                raise ValueError(f"ans_dequant_wide: item {k}: {rw.size} run lengths for {n_runs} runs")
+            if int(rw.min()) < 2:
+                raise ValueError(f"ans_dequant_wide: item {k}: run {int(rw.argmin())} has {int(rw.min())} words, fewer than its two state words")
+            table[k] = (out.data_ptr(), np.float32(scale), np.float32(0.0 if beta is None else beta), lo, n, at_table, B, int(beta is not None), shift, hi - lo, 0)
+            cdfs.append(cdf)
+            at_table += cdf.size
+            lengths.append(rw)
+            first = np.arange(0, n_runs, 64, dtype=np.uint32)
+            blk = np.zeros((first.size, 4), dtype=np.uint32)
+            blk[:, 0], blk[:, 1], blk[:, 2] = k, at_run + first, first
+            blocks.append(blk)
+            at_run += n_runs
+        lengths = np.concatenate(lengths)
+        starts = np.zeros(lengths.size + 1, dtype=np.uint64)
+        np.cumsum(lengths, dtype=np.uint64, out=starts[1:])
+        if int(starts[-1]) != words.size or words.size + 2 >= 2 ** 32:
+            raise ValueError(f"ans_dequant_wide: the run lengths add up to {int(starts[-1])} words, the payload has {words.size}")
+        padded = np.zeros(words.size + 2, dtype=np.uint32)       # (every run's span ends at or before words.size: validated just above)
+        padded[:words.size] = words
+        blocks = np.concatenate(blocks)
+        self.words, self.starts, self.blocks, self.items, self.tables = (_upload(a, device) for a in (padded, starts.astype(np.uint32), blocks, table, np.concatenate(cdfs)))
+        self.n_words, self.n_runs, self.n_blocks, self.n_items, self.n_table_words = padded.size, int(lengths.size), int(blocks.shape[0]), len(items), at_table
+        self.err = torch.zeros(1, dtype=torch.int32, device=device)
+        self._keep = [it[0] for it in items]
+
+    def launch(self):
+        L.check(L.load().bnerv_rans_dequant_wide(L.stream(), L.ptr(self.words), self.n_words, L.ptr(self.starts), self.n_runs, L.ptr(self.blocks), self.n_blocks,
+                                                 L.ptr(self.items), self.n_items, L.ptr(self.tables), self.n_table_words, self.run, L.ptr(self.err)),
+                "bnerv_rans_dequant_wide")
+        return self
+
+    def check(self):
+        e = int(self.err.item())
+        if e != 0:
+            raise ValueError("ans_dequant_wide: " + ("a descriptor points outside the uploaded arrays" if e & 2 else
+                                                     "a run did not consume exactly its words and end with an empty state, or decoded a value past its range "
+                                                     "(the payload does not match its run index)"))
+        return self
+
+
+def ans_dequant_wide(words, items, run):
+    """ans_dequant_tables for records of any width.  Arguments: AnsDequantWide."""
+    AnsDequantWide(words, items, run).launch().check()
+    return [it[0] for it in items]
+
+
 def frame_to_u8(x, out=None):
     """[B, 3, H, W] fp32 -> [B, H, W, 3] uint8 = (x.clamp(0, 1) * 255 + 0.5).to(uint8).permute(0, 2, 3, 1) in one pass (the image
     convention of train_nerv_all._save_images).  out: a contiguous uint8 buffer to write into (a captured decode's)."""

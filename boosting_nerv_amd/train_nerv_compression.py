@@ -50,6 +50,9 @@ def build_parser():
     add('--bitstream_tables', choices=('gaussian', 'empirical'), default='gaussian',
         help='empirical (needs --bitstream_run N > 0): every record under its Gaussian or under a table of its own symbol frequencies that the file '
              'carries, whichever is smaller; coded on the GPU')
+    add('--bitstream_wide', action='store_true',
+        help='(needs --bitstream_run N > 0) write the wide kind: a record whose symbols span more than 4096 values is coded as a bucket under its table '
+             'plus raw low bits; coded on the GPU under either --bitstream_tables')
     return p
 
 
@@ -60,6 +63,8 @@ def data_to_gpu(x, device):
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.bitstream_wide and not args.bitstream_run:
+        parser.error('--bitstream_wide needs --bitstream_run N > 0 (only a chunked kind is decoded by the wide kernel)')
     if args.bitstream_tables == 'empirical' and not args.bitstream_run:
         parser.error('--bitstream_tables empirical needs --bitstream_run N > 0 (only the chunked kind carries tables)')
     torch.set_printoptions(precision=2)
@@ -317,7 +322,8 @@ def evaluate(model, full_dataloader, local_rank, args, dump_vis=False, coding=Fa
         if write_bitstream and getattr(args, 'bitstream', None) and local_rank in (0, None):
             from . import codec
             args.bitstream_budget = codec.encode(model, entropy_model, args, full_dataloader, args.bitstream, run=getattr(args, 'bitstream_run', 0),
-                                                 tables=getattr(args, 'bitstream_tables', 'gaussian'))
+                                                 tables=getattr(args, 'bitstream_tables', 'gaussian'),
+                                                 **({'wide': True} if getattr(args, 'bitstream_wide', False) else {}))
             log.line(f'Bitstream {args.bitstream}: {codec.describe_any(args.bitstream_budget)} \n', every_rank=False)
     return values, hw
 

@@ -500,6 +500,43 @@ int bnerv_rans_compact(void* stream, const uint32_t* slots, size_t n_slots, int 
                        uint32_t* out, size_t n_out, int* err);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Wide runs: records whose symbols span more than 4096 values (additive to ABI 9; csrc/ans.cpp on the host, csrc/ransw.hip on the
+ * device; boosting_nerv_amd/wstream.py).
+ *
+ * A record on [min_sym, max_sym] has a `shift` k in 0..16 and B = ceil((max_sym - min_sym + 1) / 2^k) buckets.  A symbol v is coded as
+ * v - min_sym = (bucket << k) | low: the bucket under a cumulative table of B entries, `low` as k raw bits in the same state under the
+ * implicit uniform table (left = low << (24 - k), prob = 1 << (24 - k)).  The encoder pushes low, then the bucket; the decoder pops the
+ * bucket, refills, pops low ( q = state & (2^24 - 1); low = q >> (24 - k); state = ((state >> 24) << (24 - k)) | (q & (2^(24-k) - 1)) ),
+ * refills.  A run takes at most run * (24 + k) / 32 + 3 words.  With k = 0 the words are those of bnerv_ans_encode_table_runs.
+ *   bnerv_ans_gaussian_bucket_cdf   bnerv_ans_gaussian_cdf over the buckets: B + 1 entries, bucket j from min_sym + j * 2^shift - 0.5 (the last
+ *                                   one ends at max_sym + 0.5).  With shift 0 it is bnerv_ans_gaussian_cdf entry for entry.
+ *   bnerv_ans_encode_wide_runs / bnerv_ans_decode_wide_runs
+ *                                   bnerv_ans_encode_table_runs / _decode_table_runs with the range, the table over its B buckets and the
+ *                                   shift.  Decode also fails a run in which a value of the last bucket lies above max_sym.
+ *   bnerv_sym_hist_wide  (device)   bnerv_sym_hist over buckets: counts[items[k].at + ((s - lo) >> shift)].  A symbol outside [lo, lo + span_m1]
+ *                                   sets bit 0 of *err and is not counted.
+ *   bnerv_rans_encode_wide (device) bnerv_rans_encode with the extra push per symbol.  Every run owns `slot_words` dwords of `slots` (one
+ *                                   stride for the launch: at least run * (24 + shift) / 32 + 3 of every item) and may fill the last
+ *                                   run * (24 + shift) / 32 + 3 of them; a symbol outside the range, or a word past that, sets bit 0 of *err and
+ *                                   ends the lane's stores (run_words[g] = 0).  bnerv_rans_compact gathers the slots as it does the narrow ones.
+ *   bnerv_rans_dequant_wide (device) bnerv_rans_dequant with the raw-bits step per symbol:  out[i] = float(lo + offset) * scale (+ beta).  An offset
+ *                                   above span_m1 sets bit 0 of *err and is clamped to span_m1. */
+#define BNERV_RANSW_MAX_SHIFT 16
+typedef struct { const int* sym; unsigned n; int lo; unsigned alphabet; unsigned at; unsigned shift; unsigned span_m1; } bnerv_wsym_item;   /* alphabet: B; at: first entry in `counts` / `tables`; span_m1: max_sym - min_sym */
+typedef struct { float* out; float scale; float beta; int lo; unsigned n; unsigned table; unsigned alphabet; int has_beta; unsigned shift; unsigned span_m1; unsigned _pad; } bnerv_ransw_item;
+long bnerv_ans_gaussian_bucket_cdf(int32_t min_sym, int32_t max_sym, int shift, double mean, double std, uint32_t* out_cdf, size_t cap);
+long bnerv_ans_encode_wide_runs(const int32_t* symbols, size_t n, int32_t min_sym, int32_t max_sym, const uint32_t* cdf, int B, int shift, int run,
+                                uint32_t* out_words, size_t cap_words, unsigned short* out_run_words);
+int bnerv_ans_decode_wide_runs(const uint32_t* words, size_t n_words, const unsigned short* run_words, size_t n_runs, size_t n,
+                               int32_t min_sym, int32_t max_sym, const uint32_t* cdf, int B, int shift, int run, int32_t* symbols_out);
+int bnerv_sym_hist_wide(void* stream, const bnerv_wsym_item* items, int n_items, const uint32_t* blocks, size_t n_blocks, uint32_t* counts, size_t n_counts, int* err);
+int bnerv_rans_encode_wide(void* stream, const bnerv_rans_block* blocks, size_t n_blocks, const bnerv_wsym_item* items, int n_items,
+                           const uint32_t* tables, size_t n_table_words, int run, uint32_t* slots, size_t n_slots, int slot_words, unsigned short* run_words, int* err);
+int bnerv_rans_dequant_wide(void* stream, const uint32_t* words, size_t n_words, const uint32_t* run_start, size_t n_runs,
+                            const bnerv_rans_block* blocks, size_t n_blocks, const bnerv_ransw_item* items, int n_items,
+                            const uint32_t* tables, size_t n_table_words, int run, int* err);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Huffman coder of the post-hoc quantised model (additive to ABI 9; csrc/huff.cpp on the host, csrc/huff.hip on the device;
  * boosting_nerv_amd/qstream.py).
  *

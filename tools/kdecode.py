@@ -22,7 +22,12 @@ de-quantises them -- and the decode kernel alone under HIP events (ops.HuffDequa
 rANS-decodes, against the chunked file (rstream.py) repacked from it at runs of 256 and 1024, whose words ONE kernel decodes.  (1) as above
 for every file, the kinds alternated in one process, eager and graph; the decode launch alone under HIP events (ops.AnsDequant.launch, tables
 already on the device; 50 launches replayed from a graph); every file's size and the chunked overhead in bits per symbol.
-usage: python tools/kdecode.py --bitstream [--posthoc|--chunked] [--frames 16] [--rounds 3] [--only c1q|c5|pack]   (needs the GPU)"""
+--bitstream --wide times the decode kernel of the wide kind (wstream.py) on the seeded c1q model in ONE process: the narrow
+model's BNRE file under ops.AnsDequantTables and, the same records with shift 0, under ops.AnsDequantWide; then the model with the scale of
+its first (stem) weight quantiser cut so that the record spans about 25 000 values -- which only the wide kind holds -- under
+ops.AnsDequantWide; the size of that record against its version-1 message.  Times are per launch and per symbol of a run (a lane decodes
+its run's symbols one after the other).
+usage: python tools/kdecode.py --bitstream [--posthoc|--chunked|--wide] [--frames 16] [--rounds 3] [--only c1q|c5|pack]   (needs the GPU)"""
 import argparse
 import io
 import os
@@ -299,6 +304,75 @@ def run_chunked(case, n_frames, rounds):
               f"tables, descriptors and uploads on the host: {t_plan * 1e3:.1f} ms")
 
 
+WIDE_SPAN = 25000
+
+
+def build_wide(wide):
+    """The seeded c1q model on the device with init_data() scales; wide: the scale of its first (stem) weight quantiser cut so that the
+    record spans about WIDE_SPAN values.  -> (args, model, entropy model)."""
+    import torch
+    from boosting_nerv_amd.lib.entropy_model import DiffEntropyModel
+    args, model = build("c1q")
+    model = model.to("cuda:0")
+    model.init_data()
+    if wide:
+        with torch.no_grad():
+            model._quant_modules()[0].weight_quantizer.scale.mul_(255.0 / WIDE_SPAN)
+    return args, model, DiffEntropyModel("gaussian")
+
+
+def run_wide(n_frames, rounds):
+    import torch
+    from boosting_nerv_amd import bitstream, codec, estream, ops, wstream
+    dev = torch.device("cuda:0")
+    for wide in (False, True):
+        args, model, em = build_wide(wide)
+        args.full_data_length = n_frames
+        buf = io.BytesIO()
+        codec.encode(model, em, args, None, buf)
+        v1 = buf.getvalue()
+        label = f"c1q, stem weight on about {WIDE_SPAN} values" if wide else "c1q"
+        for run in (256, 1024):
+            out = io.BytesIO()
+            b = codec.repack(v1, out, run, tables="empirical", wide=True)
+            ws = wstream.read(out.getvalue())
+            recs = ws.tensors + ws.embeds
+            print(f"{label}, run {run}: BNRV {len(v1)} bytes, BNRW {b['bytes']} bytes ({100.0 * (b['bytes'] - len(v1)) / len(v1):+.2f} %); "
+                  f"{b['n_wide_records']} wide records, largest shift {b['max_shift']}, {b['n_table_records']} of {len(recs)} under a table", flush=True)
+            plans = []
+            if wide:
+                r0, m0 = recs[0], bitstream.read(v1).tensors[0]
+                spans = wstream.record_words(ws)
+                side = 8 * (18 + (8 if r0.model == estream.GAUSSIAN else len(estream.table_bytes(r0.freq))) + 2 * r0.run_words.size)
+                print(f"{label}, run {run}: the wide record: {r0.count} symbols on {r0.hi - r0.lo + 1} values, shift {r0.shift}, model {r0.model}: "
+                      f"{32 * spans[0][1]} bits of words + {side} bits of side, table and run index = {(32 * spans[0][1] + side) / r0.count:.3f} bits per symbol | "
+                      f"its version-1 message: {32 * m0.words.size} bits of words + {8 * 28} of side = {(32 * m0.words.size + 224) / r0.count:.3f} bits per symbol",
+                      flush=True)
+            else:
+                es_blob = io.BytesIO()
+                codec.repack(v1, es_blob, run, tables="empirical")
+                es = estream.read(es_blob.getvalue())
+                assert all(r.shift == 0 for r in recs) and (es.words == ws.words).all()
+                plans.append(("ops.AnsDequantTables", ops.AnsDequantTables(es.words, [(torch.empty(r.count, device=dev), float(r.scale), r.lo, estream.record_cdf(r), r.run_words,
+                                                                                     None if r.beta is None else float(r.beta)) for r in es.tensors + es.embeds], run)))
+            plans.append(("ops.AnsDequantWide", ops.AnsDequantWide(ws.words, [(torch.empty(r.count, device=dev), float(r.scale), r.lo, r.hi, wstream.record_cdf(r), r.shift,
+                                                                               r.run_words, None if r.beta is None else float(r.beta)) for r in recs], run)))
+            for _, p in plans:
+                p.launch().check()
+            times = time_graph([p.launch for _, p in plans], reps=50, rounds=max(rounds, 3))
+            n_sym = sum(r.count for r in recs)
+            for (name, p), (best, worst) in zip(plans, times):
+                p.check()
+                print(f"{label} decode launch, run {run}, {name}: {best:.1f} us best, {worst:.1f} worst per launch = {best / run:.3f} us per symbol of a run "
+                      f"({p.n_runs} runs in {p.n_blocks} blocks, {n_sym / best:.0f} symbols/us)", flush=True)
+        if wide:                                               # the file decodes to the model of its version-1 file
+            a, b = codec.Decoder(out.getvalue(), dev, use_graph=False), codec.Decoder(v1, dev, use_graph=False)
+            assert a.kind == "wide" and all(torch.equal(x, y) for x, y in zip(a.model.state_dict().values(), b.model.state_dict().values()))
+            assert torch.equal(a.decode_f32(0), b.decode_f32(0))
+            print(f"{label}: the BNRW file decodes to the parameters and the first frame of its version-1 file", flush=True)
+        del model
+
+
 def forward_rates(cfg):
     """Decode (forward-only) rate of a bench.py decoder (c1 | c3 | c4) on the HIP path: frames/s for single-frame decodes under
     torch.no_grad(), eager and as a captured hipGraph (N4 row: the figure the reference logs as "FPS" in evaluate())."""
@@ -350,6 +424,7 @@ def main():
     ap.add_argument("--bitstream", action="store_true", help="time the bitstream decoder instead")
     ap.add_argument("--posthoc", action="store_true", help="with --bitstream: the post-hoc quantised file of the regression path (C1 model)")
     ap.add_argument("--chunked", action="store_true", help="with --bitstream: the version-1 CEM file against the chunked file of the same model (c1q, c5)")
+    ap.add_argument("--wide", action="store_true", help="with --bitstream: the decode kernel of the wide kind against the narrow one (c1q)")
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--only", choices=["c1q", "c5", "pack"], default=None)
@@ -361,6 +436,9 @@ def main():
         return 0
     if a.posthoc:
         run_posthoc(a.frames, a.rounds)
+        return 0
+    if a.wide:
+        run_wide(a.frames, a.rounds)
         return 0
     if a.chunked:
         for case in ([a.only] if a.only else ["c1q", "c5"]):

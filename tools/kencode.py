@@ -2,6 +2,7 @@
 
     python tools/kencode.py [--only c1q|c5] [--frames 16] [--rounds 3]     seeded weights (the cases of tools/kdecode.py)
     python tools/kencode.py --trained tiny|c1 [--epochs E]                 a trained model: sizes only
+    python tools/kencode.py --wide [--rounds 3]                            the wide kind (BNRW) on c1q: kernels against the narrow ones
 
 Seeded cases, in ONE process:
   sizes   the version-1 file (BNRV), the chunked file (BNRC) and the file with per-record tables (BNRE) at runs 256 and 1024; how many
@@ -14,7 +15,11 @@ Seeded cases, in ONE process:
 --trained c1:   the C1 model (NeRV_Boost 1.5M, 132 synthetic 720x1280 frames): train_nerv_all.main for --epochs epochs (regression), then
                 train_nerv_compression.main from that checkpoint (--weight) for --epochs // 2 rate-distortion epochs with the compression
                 recipe's quantiser and rate flags (without --embed_entropy: the model has no embedding to code) and --bitstream.
-Both write the version-1 file; the other kinds are made from it on the host (codec.repack: the bytes of the device path, tests/test_gpu_estream.py).
+--wide: the encode kernel of the wide kind (wstream.py) on the seeded c1q model in ONE process: the narrow model's records
+under ops.AnsEncodeRuns and, with shift 0, under ops.AnsEncodeRunsWide (both tables per record, as the file is coded); then the model of
+tools/kdecode.py --wide, whose stem weight record spans about 25 000 values, under ops.AnsEncodeRunsWide with ops.SymHistWide; the file of
+codec.encode(..., wide=True) against the host repack, byte for byte.
+Both --trained cases write the version-1 file; the other kinds are made from it on the host (codec.repack: the bytes of the device path, tests/test_gpu_estream.py).
 (needs the GPU)"""
 import argparse
 import glob
@@ -149,6 +154,58 @@ def run_seeded(case, n_frames, rounds, reps):
         hist.check(), enc.check(), comp.check()
 
 
+def run_wide(n_frames, rounds, reps):
+    import numpy as np
+    import torch
+    from kdecode import build_wide, time_graph
+    from boosting_nerv_amd import codec, ops, wstream
+    from boosting_nerv_amd.lib.entropy_model import ans_counts_cdf
+    dev = torch.device("cuda:0")
+    for wide in (False, True):
+        args, model, em = build_wide(wide)
+        args.full_data_length = n_frames
+        buf = io.BytesIO()
+        codec.encode(model, em, args, None, buf)
+        v1 = buf.getvalue()
+        label = "c1q, stem weight on about 25000 values" if wide else "c1q"
+        for run in RUNS:
+            out, host = io.BytesIO(), io.BytesIO()
+            torch.cuda.synchronize()
+            t0 = time.time()
+            b = codec.encode(model, em, args, None, out, run=run, tables="empirical", wide=True)
+            torch.cuda.synchronize()
+            t_d = time.time() - t0
+            assert codec.repack(v1, host, run, tables="empirical", wide=True) == b and host.getvalue() == out.getvalue()
+            print(f"{label}, run {run}: codec.encode(wide=True) {t_d * 1e3:.0f} ms (a first call); BNRV {len(v1)} bytes, BNRW {b['bytes']} bytes "
+                  f"({100.0 * (b['bytes'] - len(v1)) / len(v1):+.2f} %), {b['n_wide_records']} wide records, largest shift {b['max_shift']}; the device path's file "
+                  f"is the host repack's, byte for byte", flush=True)
+            ws = wstream.read(out.getvalue())
+            recs = ws.tensors + ws.embeds
+            syms = [torch.from_numpy(wstream.decode_record(ws, k)).to(dev) for k in range(len(recs))]
+            hist = ops.SymHistWide([(s, r.lo, r.hi, r.shift) for s, r in zip(syms, recs)]).launch().check()
+            counts = hist.host()
+            items, narrow = [], []
+            for s, r, c in zip(syms, recs, counts):
+                assert np.array_equal(c, np.bincount((s.cpu().numpy() - r.lo) >> r.shift, minlength=c.size))
+                sf = s.float()                                 # (a record that took its table carries no moments: those of its symbols stand in)
+                g = wstream.record_cdf(r) if r.mean is not None else wstream.record_cdf(r._replace(model=0, mean=float(sf.mean()), std=max(float(sf.std()), 1e-5)))
+                items += [(s, r.lo, r.hi, g, r.shift), (s, r.lo, r.hi, ans_counts_cdf(c), r.shift)]
+                narrow += [(s, r.lo, g), (s, r.lo, items[-1][3])]
+            plans = [("ops.AnsEncodeRunsWide", ops.AnsEncodeRunsWide(items, run).launch().check())]
+            if not wide:
+                plans.insert(0, ("ops.AnsEncodeRuns", ops.AnsEncodeRuns(narrow, run).launch().check()))
+                a, b2 = plans[0][1].result(), plans[1][1].result()
+                assert np.array_equal(a[0], b2[0])             # shift 0: the narrow encoder's words
+            times = time_graph([lambda: hist.launch(zero=False)] + [p.launch for _, p in plans], reps=reps, rounds=max(rounds, 3))
+            n_sym = sum(r.count for r in recs)
+            print(f"{label} launches, run {run}: ops.SymHistWide {times[0][0]:.1f} us the kernel alone (worst {times[0][1]:.1f}; {n_sym / times[0][0]:.0f} symbols/us)", flush=True)
+            for (name, p), (best, worst) in zip(plans, times[1:]):
+                p.check()
+                print(f"{label} encode launch under both tables, run {run}, {name}: {best:.1f} us best, {worst:.1f} worst = {best / run:.3f} us per symbol of a run "
+                      f"({p.n_slots} runs in {p.n_blocks} blocks, slots of {p.slot_words} words, {2 * n_sym / best:.0f} symbols/us)", flush=True)
+        del model
+
+
 def run_trained(which, epochs, cem_epochs=None):
     import torch
     import bench
@@ -183,12 +240,16 @@ def main():
     ap.add_argument("--trained", choices=["tiny", "c1"], default=None)
     ap.add_argument("--epochs", type=int, default=30)
     ap.add_argument("--cem_epochs", type=int, default=None, help="--trained c1: rate-distortion epochs (default: --epochs // 2)")
+    ap.add_argument("--wide", action="store_true", help="the encode kernels of the wide kind against the narrow ones (c1q)")
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--reps", type=int, default=10)
     a = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "kencode needs the GPU"
+    if a.wide:
+        run_wide(a.frames, a.rounds, a.reps)
+        return 0
     if a.trained:
         run_trained(a.trained, a.epochs, a.cem_epochs)
         return 0
