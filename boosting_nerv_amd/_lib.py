@@ -169,6 +169,13 @@ class RanswItem(C.Structure):      # bnerv_ransw_item
                 ("has_beta", C.c_int), ("shift", C.c_uint32), ("span_m1", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+PRUNE_SLICE = 16384     # BNERV_PRUNE_SLICE
+
+
+class PruneItem(C.Structure):      # bnerv_prune_item
+    _fields_ = [("x", _fp), ("mask", _fp), ("n", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class YuvCoeffs(C.Structure):      # bnerv_yuv_coeffs: what yuvio.coefficients() computed in float64, rounded to fp32
     _fields_ = [("m", C.c_float * 9), ("off", C.c_float * 3), ("scale", C.c_float * 3), ("maxcode", C.c_float)]
 
@@ -288,6 +295,10 @@ SYMBOLS = {
     "bnerv_fetch_frame": (_I, [_V, _V, _V, _V, _I, _Z, _V, _V]),
     "bnerv_bucket_gather": (_I, [_V, C.POINTER(BucketChunk), _V, _F]),
     "bnerv_bucket_scatter": (_I, [_V, C.POINTER(BucketChunk), _V, _F]),
+    "bnerv_kth_abs": (_I, [_V, _V, _V, _I, _V, _Z, C.c_ulonglong, _V]),
+    "bnerv_prune_masks": (_I, [_V, _V, _I, _V, _Z, _V]),
+    "bnerv_mask_mul": (_I, [_V, _V, _I, _V, _Z]),
+    "bnerv_grad_mask_table": (_I, [_V, _V, _I, _I, _V]),
 }
 
 _lib = None

@@ -1,5 +1,5 @@
 """The train step of train_nerv_all.py:328-350 as one object: (inpainting mask ->) forward -> loss -> backward -> (gradient all-reduce)
--> (global-norm clip) -> Adan / Adam, with per-step PSNR accumulated on the device.  After a few eager steps the fixed-shape step is captured into hipGraphs and
+-> (pruning: gradient mask) -> (global-norm clip) -> Adan / Adam, with per-step PSNR accumulated on the device.  After a few eager steps the fixed-shape step is captured into hipGraphs and
 replayed (≈100 short kernels per step: launch latency, not arithmetic, is what a Python-driven loop would pay for).
 
   world == 1 :  one graph   [fwd, loss, bwd, (clip,) Adan]
@@ -17,8 +17,17 @@ from .dp import GradBucket
 
 class TrainStep:
     def __init__(self, model, optimizer, loss_type, takes_image, batch_shape, device, use_graph=True, warmup_eager=3,
-                 process_group=None, world_size=1, clip_max_norm=0.0, force_bucket=False, dp_buckets=None, mask=None):
+                 process_group=None, world_size=1, clip_max_norm=0.0, force_bucket=False, dp_buckets=None, mask=None, prune=None):
         self.model, self.opt, self.loss_type = model, optimizer, loss_type
+        # prune (prune.Pruner of this model and optimizer): the gradients of the prunable tensors are multiplied by their masks in one
+        # launch after the exchange, in front of the clip and the update (_clip_grads).  The masks keep their addresses, so an event
+        # between two replays (Pruner.prune_to) changes weights, masks and optimizer state in place and needs no re-capture.
+        if prune is not None:
+            if type(self) is not TrainStep:
+                raise NotImplementedError(f"{type(self).__name__}: pruning is built for the plain train step only")
+            if prune.optimizer is not optimizer or not hasattr(optimizer, "launch_grad_mask"):
+                raise ValueError("TrainStep: prune must be a prune.Pruner of this model and of this step's fused optimizer")
+        self.prune = prune
         self.takes_image = takes_image                       # HNeRV_Boost consumes the frame; NeRV/ENeRV the frame index
         self.dev = device
         B, C, H, W = batch_shape
@@ -201,7 +210,10 @@ class TrainStep:
 
     def _clip_grads(self):
         """--clip_max_norm: clip_grad_norm_ of train_nerv_all.py:346-347 on the device (two launches over the optimizer's table, no host round
-        trip), after the exchange: the ranks clip the AVERAGED gradient, as DDP followed by clip_grad_norm_ does in the reference."""
+        trip), after the exchange: the ranks clip the AVERAGED gradient, as DDP followed by clip_grad_norm_ does in the reference.
+        With a Pruner the gradient mask comes first (one launch over the same table): the clip sees the norm of the masked gradient."""
+        if self.prune is not None:
+            self.opt.launch_grad_mask()
         if self.clip_max_norm > 0:
             self.opt.launch_clip(self.clip_max_norm)
 
@@ -345,7 +357,9 @@ class CompressionStep(TrainStep):
     `bpp_out` holds bits per pixel (x N)."""
 
     def __init__(self, model, optimizer, entropy_model, args, batch_shape, device, use_graph=True, warmup_eager=3, world_size=1,
-                 process_group=None, force_bucket=False):
+                 process_group=None, force_bucket=False, prune=None):
+        if prune is not None:
+            raise NotImplementedError("CompressionStep: pruning is built for the plain train step only (engine.TrainStep)")
         super().__init__(model, optimizer, args.loss, "HNeRV_Boost" in args.model or 'pe' not in args.embed, batch_shape, device,
                          use_graph=use_graph, warmup_eager=warmup_eager, clip_max_norm=getattr(args, "clip_max_norm", 0.0),
                          world_size=world_size, process_group=process_group, force_bucket=force_bucket)

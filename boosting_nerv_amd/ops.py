@@ -1974,3 +1974,99 @@ def ssim(x, y):
     out = torch.empty(B, dtype=torch.float32, device=x.device)
     L.check(lib.bnerv_ssim(L.stream(), L.ptr(x), L.ptr(y), L.ptr(out), L.ptr(ws), nbytes, B, Cc, H, W), "bnerv_ssim")
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# global magnitude pruning (csrc/prune.hip; boosting_nerv_amd/prune.py drives it)
+# ----------------------------------------------------------------------------------------------------------------------
+class PruneTable:
+    """The device descriptor table of bnerv_kth_abs / bnerv_prune_masks / bnerv_mask_mul over fp32 tensors (and their uint8 masks): one
+    (tensor, mask, n) item per tensor and one (item, first element) pair per slice of PRUNE_SLICE elements, uploaded once.  The tensors are
+    used IN PLACE: contiguous fp32 device tensors at any 4-byte boundary, masks contiguous uint8 of the same element count at any byte.
+    `key` names every address the table holds: whoever caches a table compares it."""
+
+    def __init__(self, tensors, masks=None, what="prune table"):
+        import numpy as np
+        tensors = list(tensors)
+        if not tensors:
+            raise ValueError(f"{what}: no tensors")
+        if masks is not None and len(masks) != len(tensors):
+            raise ValueError(f"{what}: {len(tensors)} tensors and {len(masks)} masks")
+        for t in tensors + list(masks or []):
+            L.require_device(t, what)
+        device = tensors[0].device
+        table = np.zeros(len(tensors), dtype=np.dtype([("x", "<u8"), ("mask", "<u8"), ("n", "<u4"), ("_pad", "<u4")]))
+        assert table.dtype.itemsize == C.sizeof(L.PruneItem)
+        blocks, total = [], 0
+        for k, t in enumerate(tensors):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() == 0 or t.numel() >= 2 ** 31 or t.device != device:
+                raise ValueError(f"{what}: tensor {k} must be a non-empty contiguous fp32 tensor on {device} (below 2^31 elements)")
+            m = None if masks is None else masks[k]
+            if m is not None and (m.dtype != torch.uint8 or not m.is_contiguous() or m.numel() != t.numel() or m.device != device):
+                raise ValueError(f"{what}: mask {k} must be a contiguous uint8 tensor of {t.numel()} elements on {device}")
+            table[k] = (t.data_ptr(), 0 if m is None else m.data_ptr(), t.numel(), 0)
+            first = np.arange(0, t.numel(), L.PRUNE_SLICE, dtype=np.uint32)
+            blocks.append(np.stack([np.full(first.size, k, dtype=np.uint32), first], axis=1))
+            total += t.numel()
+        if total >= 2 ** 32:
+            raise ValueError(f"{what}: {total} elements (a table holds fewer than 2^32)")
+        blocks = np.concatenate(blocks)
+        self.key = tuple((int(r["x"]), int(r["mask"]), int(r["n"])) for r in table)
+        self.items, self.blocks = _upload(table, device), _upload(blocks, device)
+        self.n_items, self.n_blocks, self.total, self.device = len(tensors), int(blocks.shape[0]), total, device
+        self.has_masks = masks is not None
+        self._keep = (tensors, masks)
+
+    def _args(self):
+        return L.ptr(self.items), self.n_items, L.ptr(self.blocks), self.n_blocks
+
+    def kth_abs(self, k, out=None):
+        """Launches the select; -> out, int32 [4] on the device: (bits of tau, flags, pruned count low, high).  See kth_abs()."""
+        k = int(k)
+        if not 1 <= k <= self.total:
+            raise ValueError(f"kth_abs: k = {k} outside 1..{self.total}")
+        if out is None:
+            out = torch.zeros(4, dtype=torch.int32, device=self.device)
+        L.check(L.load().bnerv_kth_abs(L.ctx().handle, L.stream(), *self._args(), k, L.ptr(out)), "bnerv_kth_abs")
+        return out
+
+    def prune_masks(self, tau):
+        if not self.has_masks:
+            raise ValueError("prune_masks: the table was built without masks")
+        if tau.dtype not in (torch.float32, torch.int32) or tau.numel() < 1 or tau.device != self.device:
+            raise ValueError(f"prune_masks: tau must be a float32 (or int32 bit pattern) tensor on {self.device}")
+        L.check(L.load().bnerv_prune_masks(L.stream(), *self._args(), L.ptr(tau)), "bnerv_prune_masks")
+
+    def mask_mul(self):
+        if not self.has_masks:
+            raise ValueError("mask_mul: the table was built without masks")
+        L.check(L.load().bnerv_mask_mul(L.stream(), *self._args()), "bnerv_mask_mul")
+
+
+KTH_FLAG_NAN, KTH_FLAG_RANK, KTH_FLAG_DESC = 1, 2, 4      # flag word of bnerv_kth_abs
+
+
+def kth_abs(tensors, k, return_flags=False):
+    """(tau, n_pruned) as device tensors, no host sync: tau (float32 [1]) is the k-th smallest |w| over ALL tensors (1-based, exact: a radix
+    select on the bit patterns, the same bits on every device and in every run) and n_pruned (int64 [1]) counts the elements with
+    |w| <= tau.  return_flags: a third int32 [1] tensor, KTH_FLAG_NAN set when a tensor holds a NaN."""
+    tensors = list(tensors)
+    for t in tensors:
+        L.require_device(t, "kth_abs: tensor")
+    out = PruneTable(tensors, None, "kth_abs").kth_abs(k)
+    res = (out[0:1].view(torch.float32), out[2:4].view(torch.int64))
+    return res + (out[1:2],) if return_flags else res
+
+
+def prune_masks(tensors, masks, tau):
+    """masks[j][i] = |tensors[j][i]| > tau (uint8 1 / 0), tensors[j] *= masks[j]: one launch, in place; tau a device tensor (kth_abs)."""
+    for t in list(tensors) + list(masks):
+        L.require_device(t, "prune_masks: tensor")
+    PruneTable(tensors, list(masks), "prune_masks").prune_masks(tau)
+
+
+def mask_mul(tensors, masks):
+    """tensors[j] *= masks[j] (fp32 by uint8) for the whole list in ONE launch, in place."""
+    for t in list(tensors) + list(masks):
+        L.require_device(t, "mask_mul: tensor")
+    PruneTable(tensors, list(masks), "mask_mul").mask_mul()

@@ -29,6 +29,8 @@ class _FusedTableOptimizer(Optimizer):
         self.state_epoch = 0      # bumped whenever state tensors are replaced: a captured step (engine.TrainStep) re-captures
         self._clip_ws = None      # launch_clip(): one double per block of every group's table (device)
         self.clip_out = None      # launch_clip(): device [2] = (total gradient norm, clip coefficient) of the last clip
+        self._grad_masks = None   # set_grad_masks(): parameter -> uint8 mask (prune.Pruner); the tables then carry a mask pointer per entry
+        self._mask_late = []      # launch_grad_mask() -> launch_clip(): parameters whose state was made from the unclipped gradient
 
     def _invalidate(self):
         """The descriptors of launch_step() hold raw device pointers into the state tensors; whoever replaces those tensors
@@ -42,6 +44,13 @@ class _FusedTableOptimizer(Optimizer):
 
     def _clip_coef(self):
         return 1.0
+
+    def set_grad_masks(self, masks):
+        """masks: {parameter: uint8 tensor of its shape} (None: no masks).  From now on every descriptor table is followed, in the same
+        buffer, by one mask pointer per entry (NULL for a parameter without a mask) -- what launch_grad_mask() reads.  The masks keep
+        their addresses for the life of the optimizer's tables (prune.Pruner allocates them once)."""
+        self._grad_masks = None if not masks else {id(p): m for p, m in masks.items()}
+        self._chunk_cache = {}
 
     def _clip_fresh(self, group):
         """launch_clip(): the parameters of `group` whose state the table is about to create from the UNCLIPPED gradient."""
@@ -95,6 +104,10 @@ class _FusedTableOptimizer(Optimizer):
         sts = [self._ensure_state(p, group.get("step", 1), clip) for p in ps]
         ents = [self._entry_state(st) for st in sts]          # (exp_avg, exp_avg_sq, exp_avg_diff | None, neg_pre_grad | None)
         key = tuple((p.data_ptr(), p.grad.data_ptr()) + tuple(0 if t is None else t.data_ptr() for t in en) for p, en in zip(ps, ents))
+        gm = getattr(self, "_grad_masks", None)
+        if gm is not None:
+            mptr = [gm[id(p)].data_ptr() if id(p) in gm else 0 for p in ps]
+            key += (tuple(mptr),)
         capturing = torch.cuda.is_current_stream_capturing()
         ck = (gi, capturing)        # a captured launch owns its table: an eager step in between must not rewrite the addresses it replays with
         if capturing and self._cap_open is None:
@@ -105,7 +118,7 @@ class _FusedTableOptimizer(Optimizer):
             cached = None               # a table of an earlier capture: that graph keeps it; this capture writes its own
         if cached is None or cached[0] != key:
             # (not p.grad: it is alive whenever the step launches, and pinning it would move the next eager gradient elsewhere)
-            keep = [(p,) + tuple(en) for p, en in zip(ps, ents)]
+            keep = [(p,) + tuple(en) for p, en in zip(ps, ents)] + ([] if gm is None else [gm[id(p)] for p in ps if id(p) in gm])
             tab = (L.AdanEntry * len(ps))()
             blocks = 0
             for j, (p, en) in enumerate(zip(ps, ents)):
@@ -119,6 +132,8 @@ class _FusedTableOptimizer(Optimizer):
                 e.n, e.bstart = p.numel(), blocks
                 blocks += lib.bnerv_adan_table_blocks(p.numel())
             raw = bytes(tab)
+            if gm is not None:              # the mask pointers of the entries, behind the table (launch_grad_mask)
+                raw += bytes((C.c_uint64 * len(ps))(*mptr))
             if capturing:
                 # nothing may allocate pinned or device memory inside a capture: begin_capture() set both aside
                 host, dev_tab = self._cap_open[gi]
@@ -179,11 +194,32 @@ class _FusedTableOptimizer(Optimizer):
             tabs.append((tab, base))
             L.check(lib.bnerv_grad_sqsum_table(L.stream(), tab[0].data_ptr(), tab[1], tab[2], ws.data_ptr() + 8 * base), "bnerv_grad_sqsum_table")
             base += tab[2]
+        late += self._mask_late             # (launch_grad_mask() of this step met them first: their state exists by now)
+        self._mask_late = []
         for tab, _ in tabs:
             L.check(lib.bnerv_grad_scale_table(L.stream(), tab[0].data_ptr(), tab[1], tab[2], ws.data_ptr(), base, float(max_norm), out.data_ptr()),
                     "bnerv_grad_scale_table")
         for p in late:                      # (their state was made from the gradient as it was BEFORE the clip)
             self.state[p]["neg_pre_grad"].copy_(p.grad).neg_()
+
+    @torch.no_grad()
+    def launch_grad_mask(self):
+        """p.grad *= mask for every parameter that has one (set_grad_masks), ONE launch per parameter group over launch_step()'s own
+        descriptor table (bnerv_grad_mask_table) -- capturable under launch_step()'s capture contract.  In front of launch_clip() and
+        launch_step(): the clip then sees the masked norm and the update a zero gradient wherever a weight is pruned."""
+        if getattr(self, "_grad_masks", None) is None:
+            raise L.BnervError("fused optimizer: launch_grad_mask() without set_grad_masks()")
+        lib = L.load()
+        for gi, group in enumerate(self.param_groups):
+            fresh = self._clip_fresh(group)
+            tab = self._table(lib, gi, group, 1.0, "launch_grad_mask")
+            if tab is None:
+                continue
+            L.check(lib.bnerv_grad_mask_table(L.stream(), tab[0].data_ptr(), tab[1], tab[2], tab[0].data_ptr() + tab[1] * C.sizeof(L.AdanEntry)),
+                    "bnerv_grad_mask_table")
+            for p in fresh:                 # (their state was made from the gradient as it was BEFORE the mask; a clip that follows redoes this)
+                self.state[p]["neg_pre_grad"].copy_(p.grad).neg_()
+            self._mask_late += fresh
 
     def begin_capture(self, clip=False):
         """Before a hipGraph capture that will contain launch_step(): reserve THIS capture's descriptor tables (pinned host + device,
@@ -191,7 +227,7 @@ class _FusedTableOptimizer(Optimizer):
         contain launch_clip() as well, whose workspace and result are made here unless an eager launch_clip() already made them."""
         tabs = {}
         for gi, group in enumerate(self.param_groups):
-            nb = max(len(group["params"]), 1) * C.sizeof(L.AdanEntry)
+            nb = max(len(group["params"]), 1) * (C.sizeof(L.AdanEntry) + (8 if getattr(self, "_grad_masks", None) is not None else 0))
             dev = group["params"][0].device
             host = torch.empty(nb, dtype=torch.uint8)
             tabs[gi] = (host.pin_memory() if dev.type == "cuda" else host, torch.empty(nb, dtype=torch.uint8, device=dev))
@@ -248,6 +284,8 @@ class Adan(_FusedTableOptimizer):
         self.__dict__["_cap_open"] = None
         self.__dict__.setdefault("_clip_ws", None)
         self.__dict__.setdefault("clip_out", None)
+        self.__dict__["_grad_masks"] = None         # (keyed by parameter identity: a copy has none until a Pruner is attached to it)
+        self.__dict__["_mask_late"] = []
         self._invalidate()
 
     @torch.no_grad()
@@ -335,6 +373,8 @@ class Adam(_FusedTableOptimizer):
         self.__dict__["_cap_open"] = None
         self.__dict__.setdefault("_clip_ws", None)
         self.__dict__.setdefault("clip_out", None)
+        self.__dict__["_grad_masks"] = None         # (keyed by parameter identity: a copy has none until a Pruner is attached to it)
+        self.__dict__["_mask_late"] = []
         self._invalidate()
 
     def load_state_dict(self, state_dict):

@@ -84,6 +84,10 @@ def build_parser():
     parser.add_argument('--interpolation', action='store_true', default=False, help='do interpolation')
     parser.add_argument('--embed_inter', action='store_true', default=False, help='do interpolation')
     parser.add_argument('--cabac', action='store_true', default=False)
+    # global magnitude pruning with masked fine-tuning (prune.py); off by default
+    parser.add_argument('--prune_sparsity', type=float, default=0., help='final total sparsity of the decoder weights, in [0, 1); 0 = no pruning')
+    parser.add_argument('--prune_steps', type=int, nargs='+', default=[0],
+                        help='epochs at whose start a prune event runs; event j of m prunes to 1 - (1 - S) ** ((j + 1) / m)')
     # evaluation
     parser.add_argument('--quant', action='store_true', default=False, help='enable quantization')
     parser.add_argument('--eval_only', action='store_true', default=False, help='do evaluation only')
@@ -118,6 +122,18 @@ def build_parser():
     parser.add_argument('--yuv_matrix', type=str, default='bt709', choices=['bt709', 'bt601'], help='colour matrix of a raw .yuv clip')
     parser.add_argument('--yuv_range', type=str, default='limited', choices=['limited', 'full'], help='sample range of a raw .yuv clip')
     return parser
+
+
+def parse_args(argv=None):
+    """The parsed command line, with the flag combinations no run can honour refused here (ValueError) instead of after the data is loaded."""
+    args = build_parser().parse_args(argv)
+    if not 0.0 <= args.prune_sparsity < 1.0:
+        raise ValueError(f"--prune_sparsity {args.prune_sparsity}: a total sparsity in [0, 1)")
+    steps = list(args.prune_steps)
+    if not steps or len(set(steps)) != len(steps) or min(steps) < 0 or max(steps) >= max(args.epochs, 1):
+        raise ValueError(f"--prune_steps {steps}: distinct epochs in [0, {args.epochs})")
+    args.prune_steps = sorted(steps)
+    return args
 
 
 def solve_fc_dim(args, final_size, full_data_length):
@@ -163,7 +179,7 @@ def build_model(args):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     torch.set_printoptions(precision=2)
     if args.bitstream:                                     # what no file can hold is refused before the run, not after its last epoch
         from .codec import check_posthoc_flags
@@ -297,6 +313,18 @@ def train(local_rank, args):
 
     args._frames_dev = full_dataset.to_device(device) if resident else None
 
+    # pruning (off by default): the masks live in a Pruner; a checkpoint that carries them restores them (resume, --weight, --eval_only)
+    pruner = None
+    if args.prune_sparsity > 0 or (ckpt is not None and 'prune' in ckpt):
+        if not args.eval_only and step_mode(optimizer, args) != "captured":
+            raise NotImplementedError("pruning (--prune_sparsity, or a checkpoint with masks) needs the captured train step (Adan, or Adam on the HNeRV baseline): the generic eager step "
+                                      "of a stock torch optimizer does not mask its gradients")
+        from .prune import Pruner
+        pruner = Pruner(model, optimizer)
+        if ckpt is not None and 'prune' in ckpt:
+            pruner.load_state_dict(ckpt['prune'])
+    args._pruner = pruner
+
     if args.eval_only:
         values, hw = evaluate(model, full_loader, local_rank, args, args.dump_vis, huffman_coding=True)
         top = best.update(values)
@@ -316,7 +344,10 @@ def train(local_rank, args):
     # the reference's masks depend on the frame size only: built once, on a dummy frame of the crop size (None without --inpanting)
     mask = None if args.transform_func.identity else args.transform_func(torch.zeros(1, 3, h, w, device=device), None)[2]
     step = TrainStep(model, optimizer, args.loss, takes_image, (args.batchSize, 3, h, w), device, use_graph=not args.no_graph,
-                     world_size=world, clip_max_norm=args.clip_max_norm, mask=mask) if mode == "captured" else None
+                     world_size=world, clip_max_norm=args.clip_max_norm, mask=mask, prune=pruner) if mode == "captured" else None
+    # events of this run: those of epochs already trained (resume) are in the checkpoint's masks
+    from .prune import schedule as prune_schedule
+    prune_events = {e: (j, s) for j, (e, s) in enumerate(prune_schedule(args.prune_sparsity, args.prune_steps))} if args.prune_sparsity > 0 else {}
     log.line(f'Train step: {mode}' + (' (eager: --no_graph)' if mode == "captured" and args.no_graph else '')
              + f', inpainting mask: {args.inpanting if mask is not None else "none"}, clip_max_norm: {args.clip_max_norm}', echo=False)
     # the generic path (stock Adam) averages its gradients over the ranks with the same flat bucket the fused step uses
@@ -328,6 +359,12 @@ def train(local_rank, args):
     lr = args.lr
     for epoch in range(args.start_epoch, args.epochs):
         model.train()
+        if epoch in prune_events:
+            j, target = prune_events[epoch]
+            ev = pruner.prune_to(target)
+            pruner.step_index = j
+            log.line(f"Prune: epoch {epoch}, target {target:.4f}, pruned {ev['pruned']} of {ev['n']} ({ev['pruned'] / ev['n']:.4f}), threshold {ev['tau']:.6e}",
+                     every_rank=False)
         t_epoch = time.time()
         psnr_sum = torch.zeros((), dtype=torch.float32, device=device)     # accumulated on the device: no per-step host sync
         seen = 0
@@ -373,6 +410,8 @@ def train(local_rank, args):
 
         if is_main:
             state = {'epoch': epoch + 1, 'state_dict': model.state_dict(), 'optimizer': optimizer.state_dict()}
+            if pruner is not None:
+                state['prune'] = pruner.state_dict()
             torch.save(state, os.path.join(args.outf, 'model_latest.pth'))
             if last:
                 args.cur_epoch, args.train_time = epoch + 1, rt.hms(time.time() - t_start)
@@ -521,6 +560,9 @@ def evaluate(model, full_dataloader, local_rank, args, dump_vis=False, huffman_c
     values = book.means(device=next(model.parameters()).device)
     if local_rank in (0, None) and records is not None and huffman_coding:
         _huffman_report(args, records, quant_embed if is_hnerv else None, log)
+        pruner = getattr(args, '_pruner', None)
+        if pruner is not None:
+            log.line(f'Sparsity: {pruner.pruned()} of {pruner.n} prunable weights are zero ({pruner.sparsity():.4f})')
     if local_rank in (0, None) and huffman_coding and getattr(args, 'bitstream', None):
         from . import codec
         args.bitstream_budget = codec.encode_posthoc(model, args, records, quant_embed if is_hnerv else None, args.bitstream)

@@ -785,6 +785,36 @@ typedef struct {
 int bnerv_bucket_gather(void* stream, const bnerv_bucket_chunk* c, float* bucket, float scale);
 int bnerv_bucket_scatter(void* stream, const bnerv_bucket_chunk* c, const float* bucket, float scale);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Global magnitude pruning (additive to ABI 9; csrc/prune.hip, boosting_nerv_amd/prune.py).
+ * A table of fp32 tensors (`items`, device memory) is walked by blocks of 256 threads; `blocks` holds n_blocks device pairs
+ * (item, first element) and a block owns BNERV_PRUNE_SLICE elements of its item from there -- the layout of bnerv_sym_hist.  A tensor may
+ * start at any 4-byte boundary, a mask at any byte (16-byte accesses over the aligned body of x only); an item has fewer than 2^31 elements,
+ * a table fewer than 2^32.
+ *
+ *   bnerv_kth_abs      tau = the k-th smallest |x| over ALL items (1-based, 1 <= k <= total, exact): a most-significant-digit radix select on
+ *                      key = bits(x) & 0x7fffffff, BNERV_KTH_PASSES digits of 8 bits.  A fixed launch sequence -- one memset, then per digit
+ *                      one histogram launch over `blocks` and one single-block launch that finds the bin holding the remaining rank and
+ *                      narrows the prefix -- with the select state in the context's scratch: no host round trip, no launch that depends on
+ *                      the data, integer arithmetic only (the same table and k give the same bits on every device and in every run).
+ *                      out (device, 4 dwords, 8-byte aligned): out[0] = bits of tau, out[1] = flags (bit 0: a NaN was seen -- it ranks
+ *                      above +inf; bit 1: k exceeds the element count; bit 2: a descriptor points outside the uploaded arrays),
+ *                      out[2..3] = 64-bit count of elements with |x| <= tau.  The mask pointers of the items are not read.
+ *                      Needs a context (BNERV_E_ARG without one, or when its scratch would have to grow inside a stream capture).
+ *   bnerv_prune_masks  mask[i] = |x[i]| > tau (1 / 0, key compare: a NaN is kept), x[i] *= mask[i]; tau_dev = out of bnerv_kth_abs.
+ *   bnerv_mask_mul     x[i] *= mask[i] over the table.
+ *   bnerv_grad_mask_table  g *= mask over the GRADIENTS of the optimizer's device table (of an entry g, n and bstart are read; the grid is
+ *                      the optimizer launch's): masks_dev[t] is the mask of entry t, NULL for a tensor that is not pruned.  The per-step
+ *                      launch of a masked train step, in front of the clip and the update. */
+#define BNERV_PRUNE_SLICE 16384
+#define BNERV_KTH_PASSES 4
+typedef struct { float* x; unsigned char* mask; unsigned n; unsigned _pad; } bnerv_prune_item;
+int bnerv_kth_abs(bnerv_ctx* ctx, void* stream, const bnerv_prune_item* items, int n_items, const uint32_t* blocks, size_t n_blocks,
+                  unsigned long long k, uint32_t* out);
+int bnerv_prune_masks(void* stream, const bnerv_prune_item* items, int n_items, const uint32_t* blocks, size_t n_blocks, const uint32_t* tau_dev);
+int bnerv_mask_mul(void* stream, const bnerv_prune_item* items, int n_items, const uint32_t* blocks, size_t n_blocks);
+int bnerv_grad_mask_table(void* stream, const bnerv_adan_entry* table_dev, int n_tensors, int total_blocks, const unsigned char* const* masks_dev);
+
 #ifdef __cplusplus
 }
 #endif
