@@ -120,6 +120,8 @@ class DequantChunk(C.Structure):
 
 HUFF_RUN, HUFF_LEAVES, HUFF_LUT_BITS = 256, 257, 12      # BNERV_HUFF_RUN, BNERV_HUFF_LEAVES, BNERV_HUFF_LUT_BITS
 HUFF_F32, HUFF_F16 = 0, 1
+HUFFZ_LEAVES, HUFFZ_ZERO, HUFFZ_ZERO_LEAVES = 266, 256, 9      # BNERV_HUFFZ_LEAVES, BNERV_HUFFZ_ZERO, BNERV_HUFFZ_ZERO_LEAVES
+HUFFZ_SINGLE, HUFFZ_RUNS = 0, 1                                # BNERV_HUFFZ_SINGLE, BNERV_HUFFZ_RUNS
 
 
 class HuffRun(C.Structure):        # bnerv_huff_run
@@ -261,6 +263,9 @@ SYMBOLS = {
     "bnerv_huff_encode": (C.c_long, [_V, _V, _I, _V, _I, _V, _Z, _V, _Z]),
     "bnerv_huff_decode": (_I, [_V, _Z, _V, _Z, _V, _I, _V, _I, _V]),
     "bnerv_huff_dequant": (_I, [_V, _V, _Z, _V, _Z, _V, _I, _V, _I, _V]),
+    "bnerv_huffz_encode": (C.c_long, [_V, _V, _V, _I, _V, _I, _I, _V, _Z, _V, _Z]),
+    "bnerv_huffz_decode": (_I, [_V, _Z, _V, _Z, _V, _I, _V, _I, _V, _V]),
+    "bnerv_huffz_dequant": (_I, [_V, _V, _Z, _V, _Z, _V, _I, _V, _I, _V]),
     "bnerv_dwconv_fwd": (_I, [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I]),
     "bnerv_dwconv_wgrad_ws_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "bnerv_dwconv_wgrad": (_I, [_V, _V, _V, _V, _V, _Z, _I, _I, _I, _I, _I, _V]),

@@ -33,7 +33,12 @@ Both chunked kinds hold a record's table in LDS and so refuse a record whose sym
 DESIGN section 29) codes such a record as a bucket under a table of at most 4096 entries plus raw low bits in the same rANS state:
 encode(..., run=N, tables=..., wide=True) on the device, repack(..., wide=True) the same bytes on the host:
 
-    python -m boosting_nerv_amd.codec repack in.bnrv out.bnrw [--run N] [--tables empirical] --wide"""
+    python -m boosting_nerv_amd.codec repack in.bnrv out.bnrw [--run N] [--tables empirical] --wide
+
+The post-hoc file has a sparse kind (zstream.py) for pruned models: train_nerv_all.py --bitstream FILE --bitstream_sparse
+quantises every prunable tensor with hnerv_utils.quant_tensor_sparse -- a zero weight stays exactly zero -- and encode_posthoc() writes the
+twin under a Huffman alphabet with leaves for runs of zeros; Decoder lets ONE kernel (ops.huffz_dequant) decode it.  decode, psnr and info
+work on it; there is no repack into it (a .bnrq twin has already lost its zeros)."""
 import argparse
 import builtins
 import json
@@ -43,7 +48,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import bitstream, estream, qstream, rstream, wstream
+from . import bitstream, estream, qstream, rstream, wstream, zstream
 from .bitstream import Record
 
 TABLES = ("gaussian", "empirical")
@@ -466,6 +471,10 @@ def repack(src, dst, run=1024, tables="gaussian", wide=False):
     wide=True: the wide kind (wstream.py) under either `tables`, for records of any span; `src` a version-1 or a chunked (BNRC) file.
     Returns wstream.info."""
     from .lib.entropy_model import ans_decode_gaussian, ans_encode_gaussian_runs
+    if qstream.magic_of(src) in (qstream.MAGIC, zstream.MAGIC):
+        raise NotImplementedError("codec.repack: a post-hoc file is not repacked.  A .bnrq twin was quantised with its zeros on the grid, so the pruned "
+                                  "weights are no longer zero in it and no sparse (.bnrz) file can be made from it; write one from the checkpoint: "
+                                  "train_nerv_all.py --eval_only --weight ... --bitstream FILE --bitstream_sparse")
     run = rstream.check_run(run)
     if tables not in TABLES:
         raise ValueError(f"codec.repack: tables = {tables!r} ({' | '.join(TABLES)})")
@@ -518,7 +527,9 @@ def describe_wide(budget):
 
 
 def describe_any(budget):
-    """describe, describe_posthoc, describe_chunked, describe_empirical or describe_wide, by the budget's items."""
+    """describe, describe_posthoc, describe_sparse, describe_chunked, describe_empirical or describe_wide, by the budget's items."""
+    if "zero_parse" in budget:
+        return describe_sparse(budget)
     if "max_shift" in budget:
         return describe_wide(budget)
     if "tables" in budget:
@@ -527,9 +538,10 @@ def describe_any(budget):
 
 
 def info(path_or_buffer):
-    """The bit budget of a file of any kind (bitstream.info, qstream.info, rstream.info, estream.info or wstream.info, by the magic number)."""
+    """The bit budget of a file of any kind (bitstream.info, qstream.info, zstream.info, rstream.info, estream.info or wstream.info, by the
+    magic number)."""
     magic = qstream.magic_of(path_or_buffer)
-    return {qstream.MAGIC: qstream.info, rstream.MAGIC: rstream.info, estream.MAGIC: estream.info,
+    return {qstream.MAGIC: qstream.info, zstream.MAGIC: zstream.info, rstream.MAGIC: rstream.info, estream.MAGIC: estream.info,
             wstream.MAGIC: wstream.info}.get(magic, bitstream.info)(path_or_buffer)
 
 
@@ -572,6 +584,34 @@ def huffman_lengths(hist):
     return lengths.astype(np.uint8)
 
 
+def sparse_code(symbols, keep, counts):
+    """The code of a zstream file: the histogram and the Huffman code (huffman_lengths' construction over the 265 data leaves and EOF) of
+    both parses of the zeros; the parse with fewer symbol bits wins, "single" on a tie.  -> (parse, 266 lengths, symbol bits, histogram)."""
+    from .train_nerv_all import _huffman_depths
+    best = None
+    for parse in zstream.PARSES:
+        hist = zstream.parse_histogram(symbols, keep, counts, parse)
+        used = np.flatnonzero(hist)
+        depths = _huffman_depths(hist[used].tolist())
+        lengths = np.zeros(zstream.LEAVES, dtype=np.int64)
+        lengths[used] = depths[:-1]
+        lengths[zstream.LEAVES - 1] = depths[-1]
+        bits = int((hist * lengths[:-1]).sum())
+        if best is None or bits < best[2]:
+            best = (parse, lengths, bits, hist)
+    if best[1].max() > 32:
+        raise NotImplementedError(f"codec.encode_posthoc: the Huffman code has a {int(best[1].max())}-bit code word; the format carries 32 "
+                                  "(the code is not length-limited: that would change the bits the log reports)")
+    return best[0], best[1].astype(np.uint8), best[2], best[3]
+
+
+def posthoc_symbols(recs):
+    """(uint8 symbols, bool keep, counts) of quant_tensor / quant_tensor_sparse records back to back; a record without `keep` keeps everything."""
+    symbols = np.concatenate([r["quant"].detach().reshape(-1).cpu().numpy() for r in recs])
+    keep = np.concatenate([r["keep"].detach().reshape(-1).cpu().numpy().astype(bool) if "keep" in r else np.ones(r["quant"].numel(), dtype=bool) for r in recs])
+    return symbols, keep, [int(r["quant"].numel()) for r in recs]
+
+
 def check_posthoc_flags(args):
     """The refusals of encode_posthoc that depend on the run's flags alone -- train_nerv_all calls this right after argument parsing, so a
     run that cannot write its --bitstream stops before it trains."""
@@ -590,8 +630,9 @@ def encode_posthoc(model, args, records, quant_embed, path):
     """Write what train_nerv_all.evaluate() scored under `quant_*` -- `records` of its quant_model() call and, for the HNeRV models, the
     `quant_embed` record of its frame embeddings -- as a qstream file to `path` (a file name or a binary file object); returns
     qstream.info of what was written.  Nothing is re-quantised: the symbols, the grids and the Huffman code are those of that evaluation,
-    so info["symbol_bits"] is _huffman_total_bits of its histogram, args.bits_per_param * numel."""
-    from .lib.entropy_model import huff_encode
+    so info["symbol_bits"] is _huffman_total_bits of its histogram, args.bits_per_param * numel.
+    Records that carry `keep` (quant_tensor_sparse, --bitstream_sparse) make a zstream file instead; returns zstream.info."""
+    from .lib.entropy_model import huff_encode, huffz_encode
     check_posthoc_flags(args)
     if records is None:
         raise NotImplementedError("codec.encode_posthoc: --quant_model_bit -1 builds no quantised twin: there are no symbols to code")
@@ -603,29 +644,32 @@ def encode_posthoc(model, args, records, quant_embed, path):
     for r in recs:
         if r["quant"].dtype != torch.uint8 or r["quant"].numel() == 0:
             raise NotImplementedError(f"codec.encode_posthoc: symbols of dtype {r['quant'].dtype} are not coded (8 bits at most)")
-    symbols = np.concatenate([r["quant"].detach().reshape(-1).cpu().numpy() for r in recs])
-    counts = [int(r["quant"].numel()) for r in recs]
-    lengths = huffman_lengths(np.bincount(symbols, minlength=256))
-    words, run_bits = huff_encode(symbols, counts, lengths, qstream.RUN)
-    out, at = [], 0
+    sparse = any("keep" in r for r in recs)
+    symbols, keep, counts = posthoc_symbols(recs)
+    if sparse:
+        parse, lengths, _, hist = sparse_code(symbols, keep, counts)
+        words, run_bits = huffz_encode(symbols, keep, counts, lengths, parse, zstream.RUN)
+    else:
+        lengths = huffman_lengths(np.bincount(symbols, minlength=256))
+        words, run_bits = huff_encode(symbols, counts, lengths, qstream.RUN)
+    out, at, el = [], 0, 0
     for r, n in zip(recs, counts):
         outer, red, inner, flag = _grid_geometry(r)
         k = qstream.n_runs(n)
-        out.append(qstream.QRecord(n, outer, red, inner, flag, r["min"].detach().reshape(-1).cpu().numpy(), r["scale"].detach().reshape(-1).cpu().numpy(),
-                                   run_bits[at:at + k]))
+        grid = (r["min"].detach().reshape(-1).cpu().numpy(), r["scale"].detach().reshape(-1).cpu().numpy(), run_bits[at:at + k])
+        out.append(zstream.ZRecord(n, outer, red, inner, flag, int(keep[el:el + n].sum()), *grid) if sparse else qstream.QRecord(n, outer, red, inner, flag, *grid))
         at += k
+        el += n
     frame_hw = tuple(int(v) for v in args.crop_list.split("_")[:2])
     s = _settings(args, args.full_data_length, frame_hw)
     s.update(final_size=int(args.final_size), quant_model_bit=int(args.quant_model_bit), quant_embed_bit=int(args.quant_embed_bit), huff_run=qstream.RUN)
     if is_hnerv:
         s["embed_shape"] = [int(v) for v in quant_embed["quant"].shape]
-    blob = qstream.to_bytes(s, lengths, out, words)
-    if hasattr(path, "write"):
-        path.write(blob)
-    else:
-        with open(path, "wb") as f:
-            f.write(blob)
-    return qstream.info(blob)
+    if sparse:
+        s.update(zero_parse=parse, n_zero_leaves=int(hist[zstream.ZERO:].sum()))
+    blob = (zstream if sparse else qstream).to_bytes(s, lengths, out, words)
+    _write_blob(path, blob)
+    return (zstream if sparse else qstream).info(blob)
 
 
 def describe_posthoc(budget):
@@ -633,6 +677,12 @@ def describe_posthoc(budget):
     return (f"{budget['bytes']} bytes = {budget['total']} bits: Huffman codes {budget['symbol_bits']} ({budget['n_symbols']} symbols in {budget['n_records']} "
             f"tensors) + run index {budget['run_index']} ({budget['n_runs']} runs) + grids {budget['grid_side']} + code table {budget['code_table']} "
             f"+ header {budget['header']} + padding {budget['padding']}")
+
+
+def describe_sparse(budget):
+    """One line of a zstream.info budget (the log of train_nerv_all --bitstream --bitstream_sparse, `codec info`)."""
+    return (f"{describe_posthoc(budget)}; sparse: {budget['n_zero_elements']} zero elements in {budget['n_zero_leaves']} zero-run leaves, "
+            f"parse {budget['zero_parse']}")
 
 
 class Decoder:
@@ -658,9 +708,9 @@ class Decoder:
         from .lib.entropy_model import ans_decode_gaussian
         from .train_nerv_all import build_model
         magic = qstream.magic_of(path)
-        self.kind = {qstream.MAGIC: "posthoc", rstream.MAGIC: "chunked", estream.MAGIC: "empirical", wstream.MAGIC: "wide"}.get(magic, "cem")
-        if self.kind == "posthoc":
-            self._load_posthoc(path, device)
+        self.kind = {qstream.MAGIC: "posthoc", zstream.MAGIC: "sparse", rstream.MAGIC: "chunked", estream.MAGIC: "empirical", wstream.MAGIC: "wide"}.get(magic, "cem")
+        if self.kind in ("posthoc", "sparse"):
+            (self._load_sparse if self.kind == "sparse" else self._load_posthoc)(path, device)
             return self._frame_loop(use_graph, pack, matrix, range)
         bs = {"chunked": rstream.read, "empirical": estream.read, "wide": wstream.read}.get(self.kind, bitstream.read)(path)
         what = {"chunked": "rstream", "empirical": "estream", "wide": "wstream"}.get(self.kind, "bitstream")
@@ -744,16 +794,22 @@ class Decoder:
 
         self._frame_loop(use_graph, pack, matrix, range)
 
-    def _load_posthoc(self, path, device):
+    def _load_sparse(self, path, device):
+        """A zstream file: _load_posthoc with the 266-leaf code and the kernel that writes pruned weights as +0.0."""
+        from . import ops
+        self._load_posthoc(path, device, zstream, ops.huffz_dequant)
+
+    def _load_posthoc(self, path, device, fmt=qstream, dequant=None):
         """A qstream file: the model without quantisers (and, for the HNeRV models, without its encoder), the bit
         string uploaded once as it lies in the file, ONE launch that Huffman-decodes and de-quantises it into the state_dict tensors and the
         [N, C, h, w] embedding tensor."""
         from . import ops
         from .train_nerv_all import build_model
-        qs = qstream.read(path)
+        qs = fmt.read(path)
+        what = "zstream" if fmt is zstream else "qstream"
         s = dict(qs.settings)
         if s.get("model") not in POSTHOC_MODELS:
-            raise ValueError(f"qstream: header names the model {s.get('model')!r}; this build decodes {', '.join(POSTHOC_MODELS)}")
+            raise ValueError(f"{what}: header names the model {s.get('model')!r}; this build decodes {', '.join(POSTHOC_MODELS)}")
         self.settings = s
         self.device = torch.device(device)
         self.n_frames = int(s["full_data_length"])
@@ -770,16 +826,16 @@ class Decoder:
         if self.is_hnerv:
             shape = tuple(int(v) for v in s.get("embed_shape", ()))
             if len(shape) != 4 or shape[0] != self.n_frames:
-                raise ValueError(f"qstream: the header's embedding shape {shape} does not match its {self.n_frames} frames")
+                raise ValueError(f"{what}: the header's embedding shape {shape} does not match its {self.n_frames} frames")
             self.embeds = torch.empty(shape, dtype=torch.float32, device=self.device)
             targets.append(self.embeds)
         else:
             self.embeds = None
         targets += [v for k, v in model.state_dict().items() if "encoder" not in k]
         if len(targets) != len(qs.records) or any(t.numel() != r.count for t, r in zip(targets, qs.records)):
-            raise ValueError("qstream: the records do not match the model the header describes")
+            raise ValueError(f"{what}: the records do not match the model the header describes")
         if any(t.dtype != torch.float32 or not t.is_contiguous() for t in targets):
-            raise ValueError("qstream: the model the header describes has a state_dict entry that is not a dense fp32 tensor")
+            raise ValueError(f"{what}: the model the header describes has a state_dict entry that is not a dense fp32 tensor")
         # every grid in ONE upload: min and scale of each record as they lie in the file, each array on a 4-byte boundary
         blobs, spans, at = [], [], 0
         for r in qs.records:
@@ -795,7 +851,7 @@ class Decoder:
             tdt = torch.float16 if r.dtype == qstream.F16 else torch.float32
             lo, step = (grids[o:o + n].view(tdt) for o, n in spans[2 * k:2 * k + 2])
             items.append((t, lo, step, r.red, r.inner, r.run_bits))
-        ops.huff_dequant(qs.words, qs.lengths, items, int(s["huff_run"]))
+        (dequant or ops.huff_dequant)(qs.words, qs.lengths, items, int(s["huff_run"]))
 
     def _frame_loop(self, use_graph, pack, matrix, range):
         from .engine import FrameDecodeGraph

@@ -7,7 +7,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result"
 mkdir -p _obj
 pids=()
-UNITS="abi conv conv4 conv5 convs convbf wgrad wgrad1 eltwise head3 stem gemm dense optim loss dwconv cem lnorm codec yuv huff rans ransenc ransw prune"
+UNITS="abi conv conv4 conv5 convs convbf wgrad wgrad1 eltwise head3 stem gemm dense optim loss dwconv cem lnorm codec yuv huff rans ransenc ransw prune huffz"
 for f in $UNITS; do
   stale=0
   for h in *.h ../../include/bnerv.h; do [ $h -nt _obj/$f.o ] && stale=1; done
@@ -24,6 +24,10 @@ if [ ! -f _obj/huffh.o ] || [ huff.cpp -nt _obj/huffh.o ] || [ common.h -nt _obj
   $HIPCC -x hip $FLAGS -c huff.cpp -o _obj/huffh.o &
   pids+=($!)
 fi
+if [ ! -f _obj/huffzh.o ] || [ huffz.cpp -nt _obj/huffzh.o ] || [ huff_code.h -nt _obj/huffzh.o ] || [ ../../include/bnerv.h -nt _obj/huffzh.o ]; then
+  $HIPCC -x hip $FLAGS -c huffz.cpp -o _obj/huffzh.o &
+  pids+=($!)
+fi
 for p in "${pids[@]:-}"; do [ -n "$p" ] && wait $p; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT $(printf '_obj/%s.o ' $UNITS) _obj/ans.o _obj/huffh.o
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT $(printf '_obj/%s.o ' $UNITS) _obj/ans.o _obj/huffh.o _obj/huffzh.o
 echo "built $(realpath $OUT)"

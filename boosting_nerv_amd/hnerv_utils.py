@@ -170,6 +170,43 @@ def quant_tensor(t, bits=8):
     return {"quant": codes.to(torch.uint8), "min": lo, "scale": step}, rebuilt
 
 
+def quant_tensor_sparse(t, bits=8):
+    """quant_tensor for a pruned tensor: an element that is zero stays exactly +0.0 and takes no part in fitting the
+    grids.  The candidate grids are quant_tensor's; `lo` and `hi` of a slice are taken over its kept (non-zero) elements only, a slice
+    without one takes lo = 0, step = 0, and where step == 0 the codes are 0 and the rebuilt value is lo (nothing is divided by zero).
+    The grid with the smallest sum of |t - rebuilt| over the kept elements wins (first one on ties).  Returns
+    ({'quant', 'min', 'scale', 'keep'}, rebuilt) with keep = t != 0; on a tensor without zeros and without a constant slice every field
+    equals quant_tensor's."""
+    top = 2 ** bits - 1
+    keep = t != 0
+    big = torch.full_like(t, float("inf"))
+
+    def fit(axis):
+        lo = torch.where(keep, t, big).min() if axis is None else torch.where(keep, t, big).amin(axis, keepdim=True)
+        hi = torch.where(keep, t, -big).max() if axis is None else torch.where(keep, t, -big).amax(axis, keepdim=True)
+        empty = lo > hi                                    # no kept element in the slice: (+inf, -inf)
+        lo, hi = torch.where(empty, torch.zeros_like(lo), lo), torch.where(empty, torch.zeros_like(hi), hi)
+        return lo, (hi - lo) / top
+
+    grids = [fit(None)]
+    for axis in range(t.dim()):
+        lo, step = fit(axis)
+        if lo.nelement() / t.nelement() < 0.02:
+            grids.append((lo.to(torch.float16), step.to(torch.float16)))
+    best = None
+    for lo, step in grids:
+        lo_e, step_e = lo.expand_as(t), step.expand_as(t)
+        flat = step_e == 0
+        codes = ((t - lo_e) / torch.where(flat, torch.ones_like(step_e), step_e)).round().clamp(0, top)
+        codes = torch.where(flat | ~keep, torch.zeros_like(codes), codes)
+        rebuilt = torch.where(keep, lo_e + step_e * codes, torch.zeros_like(codes))
+        err = ((t - rebuilt).abs() * keep).sum()
+        if best is None or err < best[0]:
+            best = (err, codes, rebuilt, lo, step)
+    _, codes, rebuilt, lo, step = best
+    return {"quant": codes.to(torch.uint8), "min": lo, "scale": step, "keep": keep}, rebuilt
+
+
 def dequant_tensor(quant_t):
     q, tmin, scale = quant_t["quant"], quant_t["min"], quant_t["scale"]
     return tmin.expand_as(q) + scale.expand_as(q) * q

@@ -244,6 +244,47 @@ def huff_decode(words, run_bits, counts, lengths, run=L.HUFF_RUN):
     return out[:int(cnt.sum())]
 
 
+def huffz_encode(symbols, keep, counts, lengths, parse, run=L.HUFF_RUN):
+    """The sparse form of huff_encode (csrc/huffz.cpp): uint8 symbols and keep bytes of the items back to back under the
+    canonical code of the 266 `lengths`, zeros written as zero-run leaves under parse "single" | "runs" (or BNERV_HUFFZ_SINGLE | _RUNS) ->
+    (uint32 words of the bit string, uint16 bit length of every run of `run` ELEMENTS)."""
+    lib = L.load()
+    sym = np.ascontiguousarray(symbols, dtype=np.uint8)
+    kp = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+    cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+    ln = np.ascontiguousarray(lengths, dtype=np.uint8)
+    parse = {"single": L.HUFFZ_SINGLE, "runs": L.HUFFZ_RUNS}.get(parse, parse)
+    if ln.size != L.HUFFZ_LEAVES or int(cnt.sum()) != sym.size or kp.size != sym.size or run < 1:
+        raise ValueError(f"huffz_encode: need {L.HUFFZ_LEAVES} code lengths, counts that add up to the symbols, one keep byte per symbol and a positive run length")
+    n_runs = int(sum((int(c) + run - 1) // run for c in cnt))
+    run_bits = np.zeros(max(n_runs, 1), dtype=np.uint16)
+    args = (sym.ctypes.data, kp.ctypes.data, cnt.ctypes.data, cnt.size, ln.ctypes.data, int(parse), int(run))
+    need = lib.bnerv_huffz_encode(*args, None, 0, run_bits.ctypes.data, run_bits.size)
+    if need < 0:
+        L.check(-1, "bnerv_huffz_encode")
+    out = np.zeros(max(need, 1), dtype=np.uint32)
+    got = lib.bnerv_huffz_encode(*args, out.ctypes.data, out.size, run_bits.ctypes.data, run_bits.size)
+    assert got == need
+    return out[:need], run_bits[:n_runs]
+
+
+def huffz_decode(words, run_bits, counts, lengths, run=L.HUFF_RUN):
+    """The inverse of huffz_encode -> (uint8 symbols, bool keep); a zero element has symbol 0.  Raises BnervError when a run does not end on
+    its recorded bit, decodes the EOF leaf, or holds a zero-run leaf that passes its element count."""
+    lib = L.load()
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    rb = np.ascontiguousarray(run_bits, dtype=np.uint16)
+    cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+    ln = np.ascontiguousarray(lengths, dtype=np.uint8)
+    if ln.size != L.HUFFZ_LEAVES:
+        raise ValueError(f"huffz_decode: need {L.HUFFZ_LEAVES} code lengths")
+    n = int(cnt.sum())
+    out, kp = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint8)
+    L.check(lib.bnerv_huffz_decode(w.ctypes.data, w.size, rb.ctypes.data, rb.size, cnt.ctypes.data, cnt.size, ln.ctypes.data, int(run), out.ctypes.data,
+                                   kp.ctypes.data), "bnerv_huffz_decode")
+    return out[:n], kp[:n].astype(bool)
+
+
 def compress_matrix_flatten_gaussian_global(matrix, mean, std):
     """Bits of the rANS message of the integer tensor `matrix` under QuantizedGaussian(min, max, mean, std) -- the reference's
     function of the same name (lib/entropy_model.py:46-62), which returns 8 * bytes of constriction's compressed buffer."""

@@ -951,17 +951,18 @@ class HuffDequant:
                    or fp16 device tensors of out.numel() / red entries, run_bits its uint16 run lengths
     launch() decodes and de-quantises everything in one kernel; check() reads the device error word (a host sync) and raises ValueError
     when a run did not end on its recorded bit."""
+    _name, _entry, _leaves = "huff_dequant", "bnerv_huff_dequant", L.HUFF_LEAVES
 
     def __init__(self, words, lengths, items, run=L.HUFF_RUN):
         import numpy as np
         if not items:
-            raise ValueError("huff_dequant: no items")
+            raise ValueError(f"{self._name}: no items")
         words = np.ascontiguousarray(words, dtype=np.uint32)
         self.lengths = np.ascontiguousarray(lengths, dtype=np.uint8)
-        if self.lengths.size != L.HUFF_LEAVES:
-            raise ValueError(f"huff_dequant: need {L.HUFF_LEAVES} code lengths")
+        if self.lengths.size != self._leaves:
+            raise ValueError(f"{self._name}: need {self._leaves} code lengths")
         if run != L.HUFF_RUN:
-            raise ValueError(f"huff_dequant: the kernel is built for runs of {L.HUFF_RUN} symbols, not {run}")
+            raise ValueError(f"{self._name}: the kernel is built for runs of {L.HUFF_RUN} symbols, not {run}")
         self.run = int(run)
         table = np.zeros(len(items), dtype=np.dtype([("out", "<u8"), ("min", "<u8"), ("scale", "<u8"), ("dtype", "<i4"), ("n", "<u4"), ("red", "<u4"), ("inner", "<u4")]))
         assert table.dtype.itemsize == C.sizeof(L.HuffItem)
@@ -971,17 +972,17 @@ class HuffDequant:
             L.require_device(out, "out"), L.require_device(lo, "min"), L.require_device(step, "scale")
             n, red, inner = out.numel(), int(red), int(inner)
             if out.dtype != torch.float32 or not out.is_contiguous() or n == 0 or n >= 2 ** 31 or out.data_ptr() % 4 or out.device != device:
-                raise ValueError(f"huff_dequant: item {k}: out must be a non-empty contiguous 4-byte aligned fp32 tensor on {device} (below 2^31 elements)")
+                raise ValueError(f"{self._name}: item {k}: out must be a non-empty contiguous 4-byte aligned fp32 tensor on {device} (below 2^31 elements)")
             if red < 1 or inner < 1 or n % (red * inner):
-                raise ValueError(f"huff_dequant: item {k}: {n} elements do not split into slices of red={red}, inner={inner}")
+                raise ValueError(f"{self._name}: item {k}: {n} elements do not split into slices of red={red}, inner={inner}")
             slices = n // red
             if lo.dtype != step.dtype or lo.dtype not in (torch.float32, torch.float16) or lo.numel() != slices or step.numel() != slices \
                     or not lo.is_contiguous() or not step.is_contiguous() or (lo.data_ptr() | step.data_ptr()) % lo.element_size():
-                raise ValueError(f"huff_dequant: item {k}: min and scale must be contiguous fp32 or fp16 tensors of {slices} entries each")
+                raise ValueError(f"{self._name}: item {k}: min and scale must be contiguous fp32 or fp16 tensors of {slices} entries each")
             rb = np.ascontiguousarray(run_bits, dtype=np.uint16)
             n_runs = (n + run - 1) // run
             if rb.size != n_runs:
-                raise ValueError(f"huff_dequant: item {k}: {rb.size} run lengths for {n_runs} runs")
+                raise ValueError(f"{self._name}: item {k}: {rb.size} run lengths for {n_runs} runs")
             table[k] = (out.data_ptr(), lo.data_ptr(), step.data_ptr(), L.HUFF_F16 if lo.dtype == torch.float16 else L.HUFF_F32, n, red, inner)
             ends = bit + np.cumsum(rb, dtype=np.uint64)
             starts.append(np.concatenate([np.array([bit], dtype=np.uint64), ends[:-1]]))
@@ -989,7 +990,7 @@ class HuffDequant:
             first_of.append(np.arange(n_runs, dtype=np.uint32) * np.uint32(run))
             bit = int(ends[-1])
         if (bit + 31) // 32 != words.size:
-            raise ValueError(f"huff_dequant: the run lengths add up to {bit} bits, the bit string has {words.size} words")
+            raise ValueError(f"{self._name}: the run lengths add up to {bit} bits, the bit string has {words.size} words")
         self.n_runs = int(sum(a.size for a in starts))
         runs = np.zeros(self.n_runs + 1, dtype=np.dtype([("start_bit", "<u8"), ("item", "<u4"), ("first", "<u4")]))
         assert runs.dtype.itemsize == C.sizeof(L.HuffRun)
@@ -1004,13 +1005,13 @@ class HuffDequant:
         self._keep = [(o, a, b) for o, a, b, *_ in items]
 
     def launch(self):
-        L.check(L.load().bnerv_huff_dequant(L.stream(), L.ptr(self.words), self.n_words, L.ptr(self.runs), self.n_runs, L.ptr(self.items), self.n_items,
-                                            self.lengths.ctypes.data, self.run, L.ptr(self.err)), "bnerv_huff_dequant")
+        L.check(getattr(L.load(), self._entry)(L.stream(), L.ptr(self.words), self.n_words, L.ptr(self.runs), self.n_runs, L.ptr(self.items), self.n_items,
+                                               self.lengths.ctypes.data, self.run, L.ptr(self.err)), self._entry)
         return self
 
     def check(self):
         if int(self.err.item()) != 0:
-            raise ValueError("huff_dequant: a run of the bit string did not end on its recorded bit (the payload does not match its run index)")
+            raise ValueError(f"{self._name}: a run of the bit string did not end on its recorded bit (the payload does not match its run index)")
         return self
 
 
@@ -1020,6 +1021,22 @@ def huff_dequant(words, lengths, items, run=L.HUFF_RUN):
     operation each -- the `rebuilt` of hnerv_utils.quant_tensor, bit for bit.  Arguments: HuffDequant.  Raises ValueError when the device
     reports a run that did not end on its recorded bit."""
     HuffDequant(words, lengths, items, run).launch().check()
+    return [it[0] for it in items]
+
+
+class HuffzDequant(HuffDequant):
+    """The device side of one zstream payload: HuffDequant under the 266-leaf code, launched as bnerv_huffz_dequant.
+    A run is 256 ELEMENTS; zero elements are written as +0.0.  check() raises ValueError when a run did not end on its recorded bit, met
+    the EOF leaf, or held a zero-run leaf that passed its element count."""
+    _name, _entry, _leaves = "huffz_dequant", "bnerv_huffz_dequant", L.HUFFZ_LEAVES
+
+
+def huffz_dequant(words, lengths, items, run=L.HUFF_RUN):
+    """Huffman-decode a zstream bit string and de-quantise it into the items' `out` tensors IN PLACE, one launch:
+    out[i] = keep[i] ? float(min[s]) + float(scale[s]) * float(q[i]) : +0.0 -- the `rebuilt` of hnerv_utils.quant_tensor_sparse, bit for
+    bit.  Arguments: HuffDequant, with 266 code lengths.  Raises ValueError when the device reports a run that did not decode to its
+    element count on its recorded bit."""
+    HuffzDequant(words, lengths, items, run).launch().check()
     return [it[0] for it in items]
 
 

@@ -28,7 +28,7 @@ from . import ops
 from . import runtime as rt
 from .dp import GradBucket
 from .engine import TrainStep
-from .hnerv_utils import TransformInput, VideoDataSet, adjust_lr, data_split, loss_fn, psnr_fn_device, quant_tensor, worker_init_fn
+from .hnerv_utils import TransformInput, VideoDataSet, adjust_lr, data_split, loss_fn, psnr_fn_device, quant_tensor, quant_tensor_sparse, worker_init_fn
 from .model_enerv import ENeRV_Boost
 from .model_hnerv import HNeRV, HNeRV_Boost
 from .model_nerv import NeRV_Boost
@@ -98,6 +98,9 @@ def build_parser():
     parser.add_argument('--dump_images', action='store_true', default=False, help='dump the prediction images')
     parser.add_argument('--bitstream', type=str, default=None,
                         help='write the post-hoc quantised model of the final evaluation (and of --eval_only) to this file (codec.py decodes it)')
+    parser.add_argument('--bitstream_sparse', action='store_true', default=False,
+                        help='with --bitstream: quantise the prunable tensors so that a zero weight stays exactly zero and write the sparse file '
+                             'kind, whose Huffman alphabet has leaves for runs of zeros (DESIGN section 31)')
     parser.add_argument('--dump_videos', action='store_true', default=False, help='concat the prediction images into video')
     parser.add_argument('--eval_fps', action='store_true', default=False, help='fwd multiple times to test the fps')
     parser.add_argument('--encoder_file', default='', type=str, help='specify the embedding file')
@@ -133,6 +136,8 @@ def parse_args(argv=None):
     if not steps or len(set(steps)) != len(steps) or min(steps) < 0 or max(steps) >= max(args.epochs, 1):
         raise ValueError(f"--prune_steps {steps}: distinct epochs in [0, {args.epochs})")
     args.prune_steps = sorted(steps)
+    if args.bitstream_sparse and not args.bitstream:
+        raise ValueError("--bitstream_sparse: the sparse twin is what --bitstream FILE writes; give the file")
     return args
 
 
@@ -472,7 +477,9 @@ def _huffman_total_bits(counts):
 def quant_model(model, args):
     """[fp32 copy, post-hoc quantised twin], {key: quantised tensor record} -- the two models evaluate() reports on
     (reference train_nerv_all.py:622-642).  Every decoder tensor goes through hnerv_utils.quant_tensor at --quant_model_bit bits;
-    the encoder is left alone (it is not part of the transmitted model).  --quant_model_bit -1 disables the twin."""
+    the encoder is left alone (it is not part of the transmitted model).  --quant_model_bit -1 disables the twin.
+    --bitstream_sparse: the entries pruning acts on (prune.prunable: dim() > 1) go through quant_tensor_sparse instead, which keeps every
+    zero of the tensor -- whoever put it there -- exactly zero; their records carry `keep`."""
     plain = copy.deepcopy(model)
     if args.quant_model_bit == -1:
         return [plain], None
@@ -482,7 +489,8 @@ def quant_model(model, args):
         if 'encoder' in key:
             dequantised[key] = tensor
         else:
-            records[key], dequantised[key] = quant_tensor(tensor, args.quant_model_bit)
+            sparse = getattr(args, 'bitstream_sparse', False) and tensor.dim() > 1
+            records[key], dequantised[key] = (quant_tensor_sparse if sparse else quant_tensor)(tensor, args.quant_model_bit)
     twin.load_state_dict(dequantised)
     return [plain, twin], records
 
@@ -566,7 +574,7 @@ def evaluate(model, full_dataloader, local_rank, args, dump_vis=False, huffman_c
     if local_rank in (0, None) and huffman_coding and getattr(args, 'bitstream', None):
         from . import codec
         args.bitstream_budget = codec.encode_posthoc(model, args, records, quant_embed if is_hnerv else None, args.bitstream)
-        log.line(f'Bitstream {args.bitstream}: {codec.describe_posthoc(args.bitstream_budget)}')
+        log.line(f'Bitstream {args.bitstream}: {codec.describe_any(args.bitstream_budget)}')
     return values, hw
 
 
@@ -574,12 +582,17 @@ def _huffman_report(args, records, quant_embed, log):
     """Bits per parameter / per pixel of the post-hoc quantised tensors under one Huffman code over all symbols, plus 16 bits for
     every stored (min, scale) entry (reference train_nerv_all.py:577-612)."""
     symbols, side_entries = [], 0
-    for rec in ([quant_embed] if quant_embed is not None else []) + list(records.values()):
+    recs = ([quant_embed] if quant_embed is not None else []) + list(records.values())
+    for rec in recs:
         symbols.append(rec['quant'].flatten().cpu())
         side_entries += rec['min'].nelement() + rec['scale'].nelement()
     flat = torch.cat(symbols).to(torch.int64)
-    hist = torch.bincount(flat, minlength=1)
-    bits = _huffman_total_bits(hist[hist > 0].tolist())
+    if any('keep' in rec for rec in recs):                 # --bitstream_sparse: the bits of the parsed leaves, zero runs among them
+        from . import codec
+        bits = codec.sparse_code(*codec.posthoc_symbols(recs))[2]
+    else:
+        hist = torch.bincount(flat, minlength=1)
+        bits = _huffman_total_bits(hist[hist > 0].tolist())
     args.bits_per_param = bits / flat.numel()
     bits += side_entries * 16
     args.full_bits_per_param = bits / flat.numel()

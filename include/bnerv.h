@@ -573,6 +573,37 @@ int bnerv_huff_dequant(void* stream, const uint32_t* words, size_t n_words, cons
                        const bnerv_huff_item* items, int n_items, const unsigned char* lengths_host, int R, int* err);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Huffman coder of the SPARSE post-hoc quantised model (additive to ABI 9; csrc/huffz.cpp on the host, csrc/huffz.hip on the device;
+ * boosting_nerv_amd/zstream.py).  Bit order, canonical codes, descriptors and item table are those of the coder above.
+ *
+ * The alphabet has BNERV_HUFFZ_LEAVES leaves: 0..255 the 8-bit code of a kept element, BNERV_HUFFZ_ZERO + k (k = 0..8) 2^k consecutive
+ * zero elements, then the EOF leaf (never written).  An element is a zero when its `keep` byte is 0; its symbol byte is ignored by the
+ * encoder and written as 0 by the decoder.  The ELEMENTS of item k are cut into runs of R <= BNERV_HUFF_RUN (the last run of an item may be
+ * shorter); a stretch of zeros is clipped at the ends of its run.  A stretch of z zeros is written as z leaves BNERV_HUFFZ_ZERO under
+ * parse BNERV_HUFFZ_SINGLE and as the leaves BNERV_HUFFZ_ZERO + k of the set bits of z, highest first, under BNERV_HUFFZ_RUNS; a decoder
+ * needs no case for the parse.  A run holds at most R leaves, so run_bits[r] fits 16 bits.
+ *   bnerv_huffz_encode  (host)  as bnerv_huff_encode: the word count also when words_out == NULL or cap_words is too small; -1 on a bad argument.
+ *   bnerv_huffz_decode  (host)  -> symbols_out and keep_out (one byte each per element).  An error -- never a read past `words` -- when a
+ *                       run does not end on its recorded bit, a bit pattern has no code or decodes to EOF, a zero-run leaf would carry the
+ *                       run past its element count, or the lengths do not add up to n_words.
+ *   bnerv_huffz_dequant (device) ONE launch, arguments as bnerv_huff_dequant (R = BNERV_HUFF_RUN):
+ *                           out[i] = keep[i] ? float(min[s]) + float(scale[s]) * float(q[i]) : +0.0f
+ *                       A lane decodes until it has produced the element count of its run (from the descriptors); every leaf produces
+ *                       at least one element.  A leaf that would overrun the run, an EOF, or a run that does not end on the next
+ *                       descriptor's start bit sets bit 0 of *err. */
+#define BNERV_HUFFZ_LEAVES 266
+#define BNERV_HUFFZ_ZERO 256
+#define BNERV_HUFFZ_ZERO_LEAVES 9
+#define BNERV_HUFFZ_SINGLE 0
+#define BNERV_HUFFZ_RUNS 1
+long bnerv_huffz_encode(const unsigned char* symbols, const unsigned char* keep, const unsigned* counts, int n_items, const unsigned char* lengths,
+                        int parse, int R, uint32_t* words_out, size_t cap_words, unsigned short* run_bits_out, size_t cap_runs);
+int bnerv_huffz_decode(const uint32_t* words, size_t n_words, const unsigned short* run_bits, size_t n_runs, const unsigned* counts, int n_items,
+                       const unsigned char* lengths, int R, unsigned char* symbols_out, unsigned char* keep_out);
+int bnerv_huffz_dequant(void* stream, const uint32_t* words, size_t n_words, const bnerv_huff_run* runs, size_t n_runs,
+                        const bnerv_huff_item* items, int n_items, const unsigned char* lengths_host, int R, int* err);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Depthwise KxK convolution (K odd <= 7, stride 1, padding K/2) of the ConvNeXt encoder block of HNeRV_Boost
  * (model_blocks.py:223-247: nn.Conv2d(dim, dim, 7, padding=3, groups=dim)); first kernels of SURVEY 8(f) row N3.
  *   bnerv_dwconv_fwd(flip=0): y = conv(x, w) + bias;   flip=1: the data gradient (taps flipped, bias ignored: pass g as x)

@@ -27,7 +27,11 @@ model's BNRE file under ops.AnsDequantTables and, the same records with shift 0,
 its first (stem) weight quantiser cut so that the record spans about 25 000 values -- which only the wide kind holds -- under
 ops.AnsDequantWide; the size of that record against its version-1 message.  Times are per launch and per symbol of a run (a lane decodes
 its run's symbols one after the other).
-usage: python tools/kdecode.py --bitstream [--posthoc|--chunked|--wide] [--frames 16] [--rounds 3] [--only c1q|c5|pack]   (needs the GPU)"""
+--bitstream --posthoc --sparse times the sparse post-hoc file (zstream.py) against the dense file of the SAME pruned model in
+ONE process: the seeded C1 model pruned by global magnitude to --sparsity (default 0.4), quantised once with quant_tensor (the .bnrq file)
+and once with quant_tensor_sparse (the .bnrz file); model-ready of both files alternated, eager and graph; then the two decode launches
+alone under HIP events (ops.HuffDequant.launch / ops.HuffzDequant.launch, 20 launches replayed from a graph each, alternated over the rounds).
+usage: python tools/kdecode.py --bitstream [--posthoc [--sparse [--sparsity S]]|--chunked|--wide] [--frames 16] [--rounds 3] [--only c1q|c5|pack]   (needs the GPU)"""
 import argparse
 import io
 import os
@@ -219,6 +223,64 @@ def run_posthoc(n_frames, rounds):
     coded = budget["symbol_bits"] / 8
     print(f"c1 post hoc decode kernel: {best:.1f} us best, {worst:.1f} worst per launch ({plan.n_runs} runs, {budget['n_symbols'] / best:.0f} symbols/us, "
           f"{coded / best / 1e3:.2f} GB/s of coded bytes in, {4 * budget['n_symbols'] / best / 1e3:.1f} GB/s of fp32 out)")
+
+
+def run_posthoc_sparse(n_frames, rounds, sparsity):
+    import torch
+    import bench
+    from boosting_nerv_amd import codec, ops, prune, qstream, zstream
+    from boosting_nerv_amd import train_nerv_all as T
+    dev = torch.device("cuda:0")
+    args, model = bench.build("c1")
+    model = model.to(dev)
+    h, w = (int(v) for v in args.crop_list.split("_")[:2])
+    args.full_data_length, args.final_size = n_frames, h * w
+    with torch.no_grad():                                      # global magnitude pruning, as prune.Pruner selects (ties aside)
+        params = [p for _, p in prune.prunable(model)]
+        mags = torch.cat([p.abs().flatten() for p in params])
+        tau = mags.kthvalue(max(int(sparsity * mags.numel()), 1)).values
+        for p in params:
+            p.mul_(p.abs() > tau)
+    files = {}
+    for kind, flag in (("dense", False), ("sparse", True)):
+        args.bitstream_sparse = flag
+        _, records = T.quant_model(model, args)
+        buf = io.BytesIO()
+        budget = codec.encode_posthoc(model, args, records, None, buf)
+        files[kind] = (buf.getvalue(), budget)
+        print(f"c1 pruned to {sparsity}, {kind} file: {codec.describe_any(budget)}; {budget['symbol_bits'] / budget['n_symbols']:.3f} symbol bits per parameter", flush=True)
+    del model
+    print(f"c1 pruned to {sparsity}: .bnrz / .bnrq = {files['sparse'][1]['bytes'] / files['dense'][1]['bytes']:.4f}")
+    ready = {}
+    for r in range(rounds + 1):                                # round 0: the first constructions of the process, reported apart
+        for use_graph in (False, True):
+            for kind in ("dense", "sparse"):
+                torch.cuda.synchronize()
+                t0 = time.time()
+                dec = codec.Decoder(files[kind][0], dev, use_graph=use_graph)
+                torch.cuda.synchronize()
+                label = f"{kind}, {'graph' if use_graph else 'eager'}" + (" (first of the process)" if r == 0 else "")
+                ready.setdefault(label, []).append(time.time() - t0)
+                del dec
+    for label, v in ready.items():
+        print(f"c1 pruned model-ready, {label}: {min(v) * 1e3:.1f} ms best, {max(v) * 1e3:.1f} worst of {len(v)}")
+    plans = {}
+    for kind, fmt, cls in (("dense", qstream, ops.HuffDequant), ("sparse", zstream, ops.HuffzDequant)):
+        fs = fmt.read(files[kind][0])
+        items = []
+        for r in fs.records:
+            tdt = torch.float16 if r.dtype == qstream.F16 else torch.float32
+            items.append((torch.empty(r.count, device=dev), torch.from_numpy(r.min).to(dev).to(tdt), torch.from_numpy(r.scale).to(dev).to(tdt), r.red, r.inner, r.run_bits))
+        plans[kind] = cls(fs.words, fs.lengths, items)
+        plans[kind].launch().check()
+    times = time_graph([plans["dense"].launch, plans["sparse"].launch], reps=20, rounds=max(rounds, 5))
+    for (kind, plan), (best, worst) in zip(plans.items(), times):
+        plan.check()
+        n = files[kind][1]["n_symbols"]
+        print(f"c1 pruned decode kernel, {kind}: {best:.1f} us best, {worst:.1f} worst per launch ({plan.n_runs} runs, {n / best:.0f} elements/us, "
+              f"{files[kind][1]['symbol_bits'] / 8 / best / 1e3:.2f} GB/s of coded bytes in)")
+    (db, dw), (sb, sw) = times
+    print(f"c1 pruned decode kernel: sparse - dense = {sb - db:+.1f} us best against best; the dense kernel's own worst - best spread is {dw - db:.1f} us")
 
 
 def run_chunked(case, n_frames, rounds):
@@ -425,6 +487,8 @@ def main():
     ap.add_argument("--posthoc", action="store_true", help="with --bitstream: the post-hoc quantised file of the regression path (C1 model)")
     ap.add_argument("--chunked", action="store_true", help="with --bitstream: the version-1 CEM file against the chunked file of the same model (c1q, c5)")
     ap.add_argument("--wide", action="store_true", help="with --bitstream: the decode kernel of the wide kind against the narrow one (c1q)")
+    ap.add_argument("--sparse", action="store_true", help="with --bitstream --posthoc: the sparse file against the dense file of the same pruned C1 model")
+    ap.add_argument("--sparsity", type=float, default=0.4, help="with --sparse: the global magnitude sparsity the model is pruned to")
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--only", choices=["c1q", "c5", "pack"], default=None)
@@ -433,6 +497,9 @@ def main():
     assert torch.cuda.is_available(), "kdecode needs the GPU"
     if not a.bitstream:
         forward_rates(a.cfg)
+        return 0
+    if a.posthoc and a.sparse:
+        run_posthoc_sparse(a.frames, a.rounds, a.sparsity)
         return 0
     if a.posthoc:
         run_posthoc(a.frames, a.rounds)

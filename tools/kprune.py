@@ -7,7 +7,9 @@
            synchronisation; the mask launch alone from a replayed graph of 50 launches;
   train    a short C1 schedule (synthetic clip, `--frames` frames, `--epochs` epochs) at final sparsity 0 / 0.2 / 0.4, events at 1/4 and 1/2
            of the run: end PSNR (fp32 and 8-bit twin), bits per parameter of the Huffman report, size of the .bnrq file.
-usage: python tools/kprune.py [--only select|step|train] [--steps 100] [--repeats 3] [--frames 8] [--epochs 40]   (needs the GPU)"""
+  sparse   (only on request) the schedule of `train` at 0 / 0.2 / 0.4 / 0.8 with --bitstream_sparse: the .bnrz file of the sparse twin from the
+           training run and the .bnrq file of the dense twin from --eval_only on the same checkpoint; sizes, bits per parameter, PSNR of both.
+usage: python tools/kprune.py [--only select|step|train|sparse] [--steps 100] [--repeats 3] [--frames 8] [--epochs 40]   (needs the GPU)"""
 import argparse
 import os
 import re
@@ -159,9 +161,52 @@ def train(frames, epochs):
             os.chdir(cwd)
 
 
+def train_sparse(frames, epochs):
+    """The schedule of train() at final sparsity 0 / 0.2 / 0.4 / 0.8 with --bitstream_sparse: the training run writes the
+    .bnrz file of the sparse twin, then --eval_only on its checkpoint without the flag writes the .bnrq file of the dense twin."""
+    import torch
+    import bench
+    from boosting_nerv_amd import codec
+    from boosting_nerv_amd import train_nerv_all as T
+    flags = bench.RECIPES["c1"]["flags"].split()
+    for drop in ("-e", "--eval_freq"):
+        if drop in flags:
+            i = flags.index(drop)
+            del flags[i:i + 2]
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as tmp:
+        os.chdir(tmp)
+        try:
+            for S in (0.0, 0.2, 0.4, 0.8):
+                tag = f"z{int(S * 100)}"
+                common = ["--data_path", f"synthetic:{frames}x{H}x{W}", "--vid", "kprune", "--outf", tag, "-e", str(epochs), "--eval_freq", str(epochs), "-p", "1000"]
+                extra = ["--not_resume", "--bitstream", f"{tag}.bnrz", "--bitstream_sparse"]
+                if S > 0:
+                    extra += ["--prune_sparsity", str(S), "--prune_steps", str(epochs // 4), str(epochs // 2)]
+                t0 = time.time()
+                T.main(flags + common + extra)
+                T.main(flags + common + ["--eval_only", "--bitstream", f"{tag}.bnrq"])
+                torch.cuda.synchronize()
+                out = os.path.join("output", tag, "kprune")
+                log = open(os.path.join(out, os.listdir(out)[0], "rank0.txt")).read().splitlines()
+                evals = [x for x in log if x.startswith("Eval at epoch")]
+                print(f"c1 sparse S={S}: {time.time() - t0:.1f} s;  sparse twin: {evals[-1]}")
+                for x in log:
+                    if x.startswith(("Sparsity:", "Bitstream ", " bits per parameter")):
+                        print(f"c1 sparse S={S}: {x}")
+                for x in open(os.path.join(out, os.listdir(out)[0], "eval.txt")).read().splitlines():
+                    if x.strip():
+                        print(f"c1 sparse S={S}: dense twin (--eval_only): {x}")
+                z, q = codec.info(f"{tag}.bnrz"), codec.info(f"{tag}.bnrq")
+                print(f"c1 sparse S={S}: {tag}.bnrz {z['bytes']} bytes ({z['symbol_bits'] / z['n_symbols']:.3f} symbol bits per parameter, parse {z['zero_parse']}, "
+                      f"{z['n_zero_elements']} zeros), {tag}.bnrq {q['bytes']} bytes ({q['symbol_bits'] / q['n_symbols']:.3f}); ratio {z['bytes'] / q['bytes']:.4f}", flush=True)
+        finally:
+            os.chdir(cwd)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=["select", "step", "train"], default=None)
+    ap.add_argument("--only", choices=["select", "step", "train", "sparse"], default=None)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--frames", type=int, default=8)
@@ -176,6 +221,8 @@ def main():
         step(a.steps, a.repeats)
     if a.only in (None, "train"):
         train(a.frames, a.epochs)
+    if a.only == "sparse":
+        train_sparse(a.frames, a.epochs)
     return 0
 
 
