@@ -9,6 +9,7 @@ uint8 packing kernel as a captured graph -- the frames evaluate() scored, bit fo
     python -m boosting_nerv_amd.codec decode FILE --out DIR [--format png|npy]
     python -m boosting_nerv_amd.codec decode FILE --out clip.yuv --format yuv [--pix_fmt yuv420p|yuv420p10le] [--matrix bt709|bt601] [--range limited|full]
     python -m boosting_nerv_amd.codec psnr FILE --ref source.yuv [--size WxH] [--pix_fmt ...] [--matrix ...] [--range ...]
+    python -m boosting_nerv_amd.codec score FILE --ref source.yuv [--size WxH] [--pix_fmt ...] [--matrix ...] [--range ...] [--rgb] [--no_msssim] [--per_frame OUT.csv]
     python -m boosting_nerv_amd.codec info FILE
 
 The regression path (train_nerv_all.py --bitstream) has a file of its own kind (qstream.py): encode_posthoc() writes the
@@ -927,6 +928,74 @@ class Decoder:
         self._events[(self.n_frames - 1) % 2].synchronize()
         yield take((self.n_frames - 1) % 2)
 
+    def score(self, ref, msssim=True, rgb=False, chunk=32):
+        """Every frame against the raw source `ref` (a yuvio.YuvFile of this decoder's pack format with at least len(self) frames), on the
+        device.  The source goes up as it lies on disk, `chunk` frames at a time through two pinned buffers (the staging
+        of YuvFile.to_device); behind every frame's launch the packed result is scored against the staged source frame -- ops.yuv420_sse,
+        with `msssim` ops.yuv_luma_f32 of both and ops.msssim, with `rgb` ops.yuv420_to_rgb of the source frame and ops.psnr / ops.msssim
+        against the fp32 frame -- into a per-clip device table, read once at the end.  The plane metrics use `codec psnr`'s window (the
+        centre crop's offsets rounded down to even), the RGB metrics the loader's own.
+
+        -> {"sse": [N, 3] int64, "psnr_y" | "psnr_u" | "psnr_v" | "psnr_yuv": [N] float64 (yuvio.psnr_from_sse of the exact integers),
+            "msssim_y": [N] float32, with rgb "psnr_rgb" and "msssim_rgb": [N] float32, "mean": {name: the mean of the per-frame values}}.
+        MS-SSIM needs min(H, W) > 160: below that (or with msssim=False) the MS-SSIM entries are None."""
+        from . import ops, yuvio
+        self._need_pack(True, "score")
+        if ref.pix_fmt != self.pack:
+            raise RuntimeError(f"Decoder.score: this decoder packs {self.pack}, the source is {ref.pix_fmt} (pass pack={ref.pix_fmt!r} to Decoder)")
+        n, (H, W) = self.n_frames, self.frame_hw
+        if len(ref) < n:
+            raise ValueError(f"Decoder.score: {ref.path} has {len(ref)} frames, the bitstream {n}")
+        top, left = (v & ~1 for v in yuvio.crop_offsets(ref.height, ref.width, H, W))
+        bps, src_hw, dev = ref.bytes_per_sample, (ref.height, ref.width), self.device
+        ms = bool(msssim) and min(H, W) > 160
+        names = (["msssim_y"] if ms else []) + (["psnr_rgb"] if rgb else []) + (["msssim_rgb"] if rgb and ms else [])
+        sse = torch.empty(n, 3, dtype=torch.int64, device=dev)
+        table = torch.zeros(len(names) + 1, n, dtype=torch.float32, device=dev)       # (one spare row: never empty)
+        rows = {k: table[r] for r, k in enumerate(names)}
+        luma = [torch.empty(1, 1, H, W, dtype=torch.float32, device=dev) for _ in (0, 1)] if ms else None
+        src_rgb = torch.empty(1, 3, H, W, dtype=torch.float32, device=dev) if rgb else None
+        rgb_window = ref.crop_window((H, W))
+        chunk = max(1, min(int(chunk), n))
+        pinned = [torch.empty(chunk * ref.frame_bytes, dtype=torch.uint8, pin_memory=True) for _ in (0, 1)]
+        staged = [torch.empty(chunk * ref.frame_bytes, dtype=torch.uint8, device=dev) for _ in (0, 1)]
+        events = [torch.cuda.Event() for _ in (0, 1)]
+        with torch.cuda.device(dev):
+            for k, i0 in enumerate(builtins.range(0, n, chunk)):
+                i1, slot = min(i0 + chunk, n), k % 2
+                nbytes = (i1 - i0) * ref.frame_bytes
+                if k >= 2:
+                    events[slot].synchronize()                       # the copy that last read this pinned buffer is done
+                pinned[slot].numpy()[:nbytes] = ref.raw(i0, i1)
+                staged[slot][:nbytes].copy_(pinned[slot][:nbytes], non_blocking=True)
+                events[slot].record()
+                for i in builtins.range(i0, i1):
+                    src = staged[slot][(i - i0) * ref.frame_bytes:(i - i0 + 1) * ref.frame_bytes]
+                    out, packed = self._launch(i)
+                    ops.yuv420_sse(packed, src, 1, H, W, bps, src_hw=src_hw, window=(top, left), out=sse[i:i + 1])
+                    if ms:
+                        ops.yuv_luma_f32(packed, bps, 1, H, W, out=luma[0])
+                        ops.yuv_luma_f32(src, bps, 1, *src_hw, window=(top, left, H, W), out=luma[1])
+                        rows["msssim_y"][i:i + 1].copy_(ops.msssim(luma[0], luma[1]))
+                    if rgb:
+                        ops.yuv420_to_rgb(src, self.coeffs, 1, *src_hw, crop=rgb_window, out=src_rgb)
+                        rows["psnr_rgb"][i:i + 1].copy_(ops.psnr(out, src_rgb))
+                        if ms:
+                            rows["msssim_rgb"][i:i + 1].copy_(ops.msssim(out, src_rgb))
+            means = table.sum(dim=1) / float(n)                      # (runtime.MetricBook.means: an fp32 sum on the device over the frame count)
+            sse_h, table_h, means_h = sse.cpu().numpy(), table.cpu().numpy(), means.cpu().numpy()      # the one read
+        per = [yuvio.psnr_from_sse(row, H * W, ref.depth) for row in sse_h.tolist()]
+        result = {"sse": sse_h, "mean": {}}
+        for key in ("psnr_y", "psnr_u", "psnr_v", "psnr_yuv"):
+            result[key] = np.array([p[key] for p in per], dtype=np.float64)
+            result["mean"][key] = sum((p[key] for p in per), 0.0) / n            # (`codec psnr`'s sum, in its order)
+        for key in ("msssim_y", "psnr_rgb", "msssim_rgb"):
+            if key in rows:
+                result[key], result["mean"][key] = table_h[names.index(key)], float(means_h[names.index(key)])
+            elif key == "msssim_y" or rgb:
+                result[key], result["mean"][key] = None, None
+        return result
+
     def __iter__(self):
         return self.frames_u8() if self.coeffs is None else self.frames_yuv()
 
@@ -966,6 +1035,32 @@ def _psnr(a):
     return result
 
 
+def _score(a):
+    """`codec score`: `codec psnr`'s numbers plus MS-SSIM-Y (and, with --rgb, the RGB PSNR / MS-SSIM evaluate() logs), computed on the device
+    by Decoder.score: the source is uploaded as it lies on disk, nothing but the table of results comes back."""
+    from . import yuvio
+    w, h = yuvio.parse_size(a.size) if a.size else (None, None)
+    ref = yuvio.YuvFile(a.ref, w, h, a.pix_fmt)
+    dec = Decoder(a.file, "cuda", use_graph=not a.no_graph, pack=ref.pix_fmt, matrix=a.matrix, range=a.range)
+    H, W = dec.frame_hw
+    if len(ref) < len(dec):
+        raise ValueError(f"codec score: {a.ref} has {len(ref)} frames, the bitstream {len(dec)}")
+    got = dec.score(ref, msssim=not a.no_msssim, rgb=a.rgb)
+    names = [k for k in ("psnr_y", "psnr_u", "psnr_v", "psnr_yuv", "msssim_y", "psnr_rgb", "msssim_rgb") if got.get(k) is not None]
+    result = {k: got["mean"][k] for k in names}
+    result.update({f"sse_{p}": int(got["sse"][:, c].sum()) for c, p in enumerate("yuv")})
+    result.update(frames=len(dec), pix_fmt=ref.pix_fmt, matrix=a.matrix, range=a.range)
+    if a.per_frame:
+        with open(a.per_frame, "w") as f:
+            f.write(",".join(["frame", "sse_y", "sse_u", "sse_v"] + names) + "\n")
+            for i in builtins.range(len(dec)):
+                f.write(",".join([str(i)] + [str(int(v)) for v in got["sse"][i]] + [repr(float(got[k][i])) for k in names]) + "\n")
+    print(" | ".join(f"{k.upper().replace('_', '-')} {result[k]:.4f}" + (" dB" if k.startswith("psnr") else "") for k in names)
+          + f" | {len(dec)} frames of {H}x{W}, {ref.pix_fmt}")
+    print(json.dumps(result))
+    return result
+
+
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m boosting_nerv_amd.codec", description="decode or inspect a compression bitstream")
     sub = p.add_subparsers(dest="cmd", required=True)
@@ -981,6 +1076,16 @@ def build_parser():
     q.add_argument("--size", default=None, help="WxH of --ref (default: from a UVG-style file name)")
     q.add_argument("--no_graph", action="store_true", help="eager launches instead of the captured graph")
     _colour_flags(q, None)
+    c = sub.add_parser("score", help="decode FILE and score it against the raw 4:2:0 source --ref on the device: the numbers of psnr plus MS-SSIM-Y "
+                                     "(--rgb: the RGB PSNR / MS-SSIM of the training log)")
+    c.add_argument("file")
+    c.add_argument("--ref", required=True, help="the source clip, raw planar YUV 4:2:0")
+    c.add_argument("--size", default=None, help="WxH of --ref (default: from a UVG-style file name)")
+    c.add_argument("--rgb", action="store_true", help="also PSNR / MS-SSIM of the fp32 RGB frames against the source as the loader converts it")
+    c.add_argument("--no_msssim", action="store_true", help="PSNR only")
+    c.add_argument("--per_frame", default=None, metavar="OUT.csv", help="write one CSV row per frame")
+    c.add_argument("--no_graph", action="store_true", help="eager launches instead of the captured graph")
+    _colour_flags(c, None)
     i = sub.add_parser("info", help="print the bit budget of FILE")
     i.add_argument("file")
     r = sub.add_parser("repack", help="rewrite the version-1 CEM file SRC as the chunked kind DST, whose symbols decode on the device (host only)")
@@ -1010,6 +1115,8 @@ def main(argv=None):
         raise RuntimeError("codec decode: no ROCm GPU visible -- the decoder path has no CPU fallback")
     if a.cmd == "psnr":
         return _psnr(a)
+    if a.cmd == "score":
+        return _score(a)
     if a.format == "yuv":
         from . import yuvio
         dec = Decoder(a.file, "cuda", use_graph=not a.no_graph, pack=a.pix_fmt, matrix=a.matrix, range=a.range)

@@ -14,6 +14,9 @@
 // (not the launch) to the element-by-element form.
 //
 // The kernels know nothing of standards: matrix, offsets and scales arrive as one struct of fp32 values computed by the host in float64.
+//
+// bnerv_yuv420_sse and bnerv_yuv_luma_f32 score packed frames against a window of raw source frames: exact 64-bit sums of
+// squared code differences per frame and plane, and the luma plane as fp32 for MS-SSIM.  The same access policy; their shape is described below.
 #include "common.h"
 #include <stdint.h>
 
@@ -200,7 +203,92 @@ __global__ __launch_bounds__(THREADS) void rgb_to_yuv420_kernel(const float* __r
     store_samples<T>(Vp + oc, vc, n >> 1, STRIP / 2);
 }
 
-// what both entry points ask of the raw side
+// ---- scoring: the exact sum of squared code differences per frame and plane, and the luma plane as fp32 ----
+//
+// yuv420_sse_kernel: grid = (blocks over strips, 3 planes, B).  A strip is 16 bytes of one plane row (16 or 8 samples); a lane takes
+// SSE_ITEMS strips, THREADS apart, so a wave's loads are contiguous within a row.  `a` is a packed frame (row pitch = plane width), `b` a
+// window of a larger source frame; each side picks the 16-byte load or the element loop by its own address.  Widths: a squared difference is
+// below 2^20, a strip's 16 below 2^24, a lane's SSE_ITEMS = 4 strips below 2^26: 32 bits; from the wave sum upward 64 bits.  A wave reduces
+// over its lanes with shuffles (no LDS) and lane 0 issues ONE 64-bit atomic add: THREADS / 64 atomics per block and plane.  Integer sums:
+// the order of the additions changes no bit.
+constexpr int SSE_ITEMS = 4;
+
+__device__ __forceinline__ unsigned sq_diff(unsigned a, unsigned b) { const int d = (int)a - (int)b; return (unsigned)(d * d); }
+
+__device__ __forceinline__ unsigned sse_words(uint32_t wa, uint32_t wb, unsigned char) {
+    return sq_diff(wa & 0xffu, wb & 0xffu) + sq_diff((wa >> 8) & 0xffu, (wb >> 8) & 0xffu) + sq_diff((wa >> 16) & 0xffu, (wb >> 16) & 0xffu) +
+           sq_diff(wa >> 24, wb >> 24);
+}
+__device__ __forceinline__ unsigned sse_words(uint32_t wa, uint32_t wb, unsigned short) {
+    return sq_diff(wa & 0xffffu, wb & 0xffffu) + sq_diff(wa >> 16, wb >> 16);
+}
+
+// n <= 16 / sizeof(T) samples at p as four 32-bit words (samples in memory order, the rest 0): one 16-byte load when the strip is whole and p allows
+template <typename T>
+__device__ __forceinline__ uint4 load_strip(const T* __restrict__ p, const int n) {
+    constexpr int S = 16 / (int)sizeof(T), PER = 4 / (int)sizeof(T);
+    if (n == S && (reinterpret_cast<uintptr_t>(p) & 15) == 0) return *reinterpret_cast<const uint4*>(p);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < S; ++k)
+        if (k < n) w[k / PER] |= (uint32_t)p[k] << (8 * (int)sizeof(T) * (k % PER));
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+template <typename T>
+__global__ __launch_bounds__(THREADS) void yuv420_sse_kernel(const unsigned char* __restrict__ a, const size_t a_stride, const unsigned char* __restrict__ b,
+                                                             const size_t b_stride, const int H, const int W, const int src_h, const int src_w,
+                                                             const int top, const int left, unsigned long long* __restrict__ out) {
+    constexpr int S = 16 / (int)sizeof(T);
+    const int plane = (int)blockIdx.y, sh = plane ? 1 : 0;
+    const int ph = H >> sh, pw = W >> sh, spw = src_w >> sh, ptop = top >> sh, pleft = left >> sh;
+    const int nstrips = (pw + S - 1) / S, items = ph * nstrips;
+    if ((int)blockIdx.x * (THREADS * SSE_ITEMS) >= items) return;        // (the chroma planes fill a quarter of the luma's blocks)
+    const size_t a_off = plane == 0 ? 0 : (size_t)H * W + (plane == 2 ? (size_t)ph * pw : 0);
+    const size_t b_off = plane == 0 ? 0 : (size_t)src_h * src_w + (plane == 2 ? (size_t)(src_h >> 1) * spw : 0);
+    const T* pa = reinterpret_cast<const T*>(a + (size_t)blockIdx.z * a_stride) + a_off;
+    const T* pb = reinterpret_cast<const T*>(b + (size_t)blockIdx.z * b_stride) + b_off + (size_t)ptop * spw + pleft;
+    unsigned acc = 0;
+#pragma unroll
+    for (int k = 0; k < SSE_ITEMS; ++k) {
+        const int item = ((int)blockIdx.x * SSE_ITEMS + k) * THREADS + (int)threadIdx.x;
+        if (item < items) {
+            const int row = item / nstrips, x0 = (item - row * nstrips) * S, n = min(S, pw - x0);
+            const uint4 va = load_strip(pa + (size_t)row * pw + x0, n);
+            const uint4 vb = load_strip(pb + (size_t)row * spw + x0, n);
+            acc += sse_words(va.x, vb.x, T()) + sse_words(va.y, vb.y, T()) + sse_words(va.z, vb.z, T()) + sse_words(va.w, vb.w, T());
+        }
+    }
+    unsigned long long sum = acc;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+    if (((int)threadIdx.x & 63) == 0 && sum != 0) atomicAdd(out + (size_t)blockIdx.z * 3 + plane, sum);
+}
+
+// grid = (blocks over rows x strips of 4 pixels, B): out[b, 0, y, x] = float(code) / maxcode, the IEEE division
+template <typename T>
+__global__ __launch_bounds__(THREADS) void yuv_luma_f32_kernel(const unsigned char* __restrict__ src, const size_t frame_stride, const int src_w, const int top,
+                                                               const int left, float* __restrict__ out, const int H, const int W, const int nstrips,
+                                                               const float maxcode) {
+    const int t = (int)blockIdx.x * THREADS + (int)threadIdx.x;
+    if (t >= H * nstrips) return;
+    const int y = t / nstrips, x0 = (t - y * nstrips) * STRIP, n = min(STRIP, W - x0);
+    const T* Y = reinterpret_cast<const T*>(src + (size_t)blockIdx.y * frame_stride);
+    float v[STRIP];
+    load_luma(Y + (size_t)(top + y) * src_w, left + x0, n, v);
+#pragma unroll
+    for (int q = 0; q < STRIP; ++q) v[q] = __fdiv_rn(v[q], maxcode);
+    float* d = out + ((size_t)blockIdx.y * H + y) * W + x0;
+    if (n == STRIP && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
+        *reinterpret_cast<f32x4*>(d) = f32x4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+        for (int q = 0; q < STRIP; ++q)
+            if (q < n) d[q] = v[q];
+    }
+}
+
+// what every entry point asks of the raw side
 int check_raw(const char* what, const void* raw, int bytes_per_sample, int B, size_t frame_stride_bytes, int H, int W) {
     BNERV_REQUIRE(bytes_per_sample == 1 || bytes_per_sample == 2, "%s: bytes_per_sample=%d (1: yuv420p, 2: yuv420p10le)", what, bytes_per_sample);
     BNERV_REQUIRE(B > 0 && B <= 65535, "%s: B=%d", what, B);
@@ -252,5 +340,50 @@ extern "C" int bnerv_rgb_to_yuv420(void* stream, const float* x, int B, int H, i
     else
         hipLaunchKernelGGL(rgb_to_yuv420_kernel<unsigned short>, grid, block, 0, s, x, H, W, raw, frame_stride_bytes, nstrips, *coeffs);
     BNERV_LAUNCH_CHECK("rgb_to_yuv420");
+    return BNERV_OK;
+}
+
+extern "C" int bnerv_yuv420_sse(void* stream, const void* a, size_t a_stride_bytes, const void* b, size_t b_stride_bytes, int bytes_per_sample, int B,
+                                int H, int W, int src_h, int src_w, int top, int left, unsigned long long* out) {
+    BNERV_REQUIRE(a && b && out, "yuv420_sse: null args");
+    if (const int rc = check_raw("yuv420_sse: a", a, bytes_per_sample, B, a_stride_bytes, H, W)) return rc;
+    if (const int rc = check_raw("yuv420_sse: b", b, bytes_per_sample, B, b_stride_bytes, src_h, src_w)) return rc;
+    BNERV_REQUIRE(top >= 0 && left >= 0 && top % 2 == 0 && left % 2 == 0, "yuv420_sse: the window offset (top %d, left %d) must be even and not negative",
+                  top, left);
+    BNERV_REQUIRE(top <= src_h - H && left <= src_w - W, "yuv420_sse: the %dx%d window at (top %d, left %d) leaves the %dx%d frame", W, H, top, left,
+                  src_w, src_h);
+    BNERV_REQUIRE((reinterpret_cast<uintptr_t>(out) & 7) == 0, "yuv420_sse: out is not 8-byte aligned");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const hipError_t e = hipMemsetAsync(out, 0, (size_t)B * 3 * sizeof(unsigned long long), s);      // (a memset node under capture)
+    if (e != hipSuccess) return bnerv_set_error(BNERV_E_LAUNCH, "yuv420_sse: memset: %s", hipGetErrorString(e));
+    const int strip = 16 / bytes_per_sample;
+    const dim3 grid(cdiv(H * cdiv(W, strip), THREADS * SSE_ITEMS), 3, B), block(THREADS);
+    const unsigned char* ra = static_cast<const unsigned char*>(a);
+    const unsigned char* rb = static_cast<const unsigned char*>(b);
+    if (bytes_per_sample == 1)
+        hipLaunchKernelGGL(yuv420_sse_kernel<unsigned char>, grid, block, 0, s, ra, a_stride_bytes, rb, b_stride_bytes, H, W, src_h, src_w, top, left, out);
+    else
+        hipLaunchKernelGGL(yuv420_sse_kernel<unsigned short>, grid, block, 0, s, ra, a_stride_bytes, rb, b_stride_bytes, H, W, src_h, src_w, top, left, out);
+    BNERV_LAUNCH_CHECK("yuv420_sse");
+    return BNERV_OK;
+}
+
+extern "C" int bnerv_yuv_luma_f32(void* stream, const void* src, int bytes_per_sample, int B, size_t frame_stride_bytes, int src_h, int src_w, int top,
+                                  int left, float* out, int H, int W, float maxcode) {
+    BNERV_REQUIRE(src && out, "yuv_luma_f32: null args");
+    if (const int rc = check_raw("yuv_luma_f32", src, bytes_per_sample, B, frame_stride_bytes, src_h, src_w)) return rc;
+    BNERV_REQUIRE(H > 0 && W > 0 && top >= 0 && left >= 0 && top <= src_h - H && left <= src_w - W,
+                  "yuv_luma_f32: the %dx%d window at (top %d, left %d) leaves the %dx%d frame", W, H, top, left, src_w, src_h);
+    BNERV_REQUIRE(maxcode >= 1.0f, "yuv_luma_f32: maxcode=%g", (double)maxcode);
+    BNERV_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "yuv_luma_f32: out is not 4-byte aligned");
+    const int nstrips = cdiv(W, STRIP);
+    const dim3 grid(cdiv(H * nstrips, THREADS), B), block(THREADS);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const unsigned char* raw = static_cast<const unsigned char*>(src);
+    if (bytes_per_sample == 1)
+        hipLaunchKernelGGL(yuv_luma_f32_kernel<unsigned char>, grid, block, 0, s, raw, frame_stride_bytes, src_w, top, left, out, H, W, nstrips, maxcode);
+    else
+        hipLaunchKernelGGL(yuv_luma_f32_kernel<unsigned short>, grid, block, 0, s, raw, frame_stride_bytes, src_w, top, left, out, H, W, nstrips, maxcode);
+    BNERV_LAUNCH_CHECK("yuv_luma_f32");
     return BNERV_OK;
 }

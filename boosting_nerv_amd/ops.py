@@ -1660,6 +1660,56 @@ def rgb_to_yuv420(x, coeffs, out=None, frame_stride_bytes=None):
     return out
 
 
+def _raw_frames(t, name, B, h, w, bps, stride):
+    """The frame stride of B raw h x w frames in `t` (contiguous device bytes), checked against its size."""
+    nbytes = _raw_bytes(t, name)
+    frame = h * w * 3 // 2 * bps
+    stride = frame if stride is None else int(stride)
+    if B < 1 or stride < frame or (B - 1) * stride + frame > nbytes:
+        raise ValueError(f"{name}: {B} frames of {frame} bytes at stride {stride} do not fit its {nbytes} bytes")
+    return stride
+
+
+def yuv420_sse(a, b, B, H, W, bytes_per_sample, src_hw=None, window=(0, 0), a_stride=None, b_stride=None, out=None):
+    """The exact sums of squared code differences per frame and plane, [B, 3] int64 (Y, U, V), of B packed H x W frames `a` in file layout
+    (what rgb_to_yuv420 writes) against the H x W window at `window` = (top, left), both even, of B raw frames `b` of src_hw = (src_h,
+    src_w) (default: H x W) -- one memset and one launch.  a, b: contiguous device bytes, frame k at byte k * stride
+    (default: packed).  out: a contiguous int64 [B, 3] device tensor to write into."""
+    bps = int(bytes_per_sample)
+    if bps not in (1, 2):
+        raise ValueError(f"yuv420_sse: bytes_per_sample={bytes_per_sample} (1: yuv420p, 2: yuv420p10le)")
+    src_h, src_w = (H, W) if src_hw is None else (int(v) for v in src_hw)
+    sa = _raw_frames(a, "yuv420_sse: a", B, H, W, bps, a_stride)
+    sb = _raw_frames(b, "yuv420_sse: b", B, src_h, src_w, bps, b_stride)
+    if b.device != a.device:
+        raise ValueError(f"yuv420_sse: a is on {a.device}, b on {b.device}")
+    top, left = (int(v) for v in window)
+    if out is None:
+        out = torch.empty(B, 3, dtype=torch.int64, device=a.device)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (B, 3) or not out.is_contiguous() or out.device != a.device:
+        raise ValueError(f"yuv420_sse: out must be a contiguous int64 [{B}, 3] tensor on {a.device}")
+    L.check(L.load().bnerv_yuv420_sse(L.stream(), L.ptr(a), sa, L.ptr(b), sb, bps, B, H, W, src_h, src_w, top, left, L.ptr(out)), "bnerv_yuv420_sse")
+    return out
+
+
+def yuv_luma_f32(src, bytes_per_sample, B, src_h, src_w, window=None, frame_stride_bytes=None, out=None):
+    """The luma window of B raw 4:2:0 frames (src: contiguous device bytes in file layout) as [B, 1, H, W] fp32 = code / maxcode with the
+    correctly rounded fp32 division (maxcode 255 at 1 byte per sample, 1023 at 2): the plane MS-SSIM-Y is taken on.
+    window = (top, left, H, W) in source coordinates, any parity (None: the whole frame)."""
+    bps = int(bytes_per_sample)
+    if bps not in (1, 2):
+        raise ValueError(f"yuv_luma_f32: bytes_per_sample={bytes_per_sample} (1: yuv420p, 2: yuv420p10le)")
+    stride = _raw_frames(src, "yuv_luma_f32: src", B, src_h, src_w, bps, frame_stride_bytes)
+    top, left, H, W = (0, 0, src_h, src_w) if window is None else (int(v) for v in window)
+    if out is None:
+        out = torch.empty(B, 1, max(H, 0), max(W, 0), dtype=torch.float32, device=src.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, 1, H, W) or not out.is_contiguous() or out.device != src.device:
+        raise ValueError(f"yuv_luma_f32: out must be a contiguous fp32 [{B}, 1, {H}, {W}] tensor on {src.device}")
+    L.check(L.load().bnerv_yuv_luma_f32(L.stream(), L.ptr(src), bps, B, stride, src_h, src_w, top, left, L.ptr(out), H, W, 255.0 if bps == 1 else 1023.0),
+            "bnerv_yuv_luma_f32")
+    return out
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # depthwise conv of the ConvNeXt encoder block (first kernels of row N3)
 # ----------------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """Raw planar YUV 4:2:0 video in and out: the file reader, the float64 restatement of the colour conversion (the
 CPU / --host_frames path of the loader and the oracle of the GPU tests), the writer and the per-plane PSNR codecs are scored with.
-The device path is csrc/yuv.hip behind ops.yuv420_to_rgb / ops.rgb_to_yuv420.
+The device path is csrc/yuv.hip behind ops.yuv420_to_rgb / ops.rgb_to_yuv420; ops.yuv420_sse / ops.yuv_luma_f32 behind codec.Decoder.score
+ are the device form of psnr_planes' sums.
 
 A frame is plane Y [H, W], then U [H/2, W/2], then V [H/2, W/2]; frames follow each other without a header.  yuv420p: one byte per
 sample; yuv420p10le: two bytes, little endian, values 0..1023."""
@@ -263,18 +264,35 @@ def write(path, frames, pix_fmt="yuv420p", append=False):
     return n
 
 
+def psnr_from_sse(sse_yuv, n_luma, depth):
+    """The formula part of psnr_planes: (SSE-Y, SSE-U, SSE-V) of one 4:2:0 frame of n_luma luma samples (each chroma plane has n_luma / 4;
+    a triple gives the three sample counts themselves) -> {"psnr_y", "psnr_u", "psnr_v", "psnr_yuv"}: 10 log10(peak^2 n / SSE) with
+    peak = 2^depth - 1 (inf at SSE 0) and (6 Y + U + V) / 8.  The sums are taken as exact Python integers, so a sum from the device
+    (ops.yuv420_sse) gives the floats psnr_planes gives."""
+    peak = 2 ** int(depth) - 1
+    sizes = tuple(int(n) for n in n_luma) if isinstance(n_luma, (tuple, list)) else (int(n_luma), int(n_luma) // 4, int(n_luma) // 4)
+    out = {}
+    for name, sse, n in zip("yuv", sse_yuv, sizes):
+        sse = int(sse)
+        out[f"psnr_{name}"] = float("inf") if sse == 0 else 10.0 * float(np.log10(peak * peak * n / sse))
+    out["psnr_yuv"] = (6.0 * out["psnr_y"] + out["psnr_u"] + out["psnr_v"]) / 8.0
+    return out
+
+
 def psnr_planes(a, b, depth):
     """Per-plane distortion of two frames given as (y, u, v) triples of integer codes: the sums of squared errors as exact Python integers,
     PSNR-Y / -U / -V = 10 log10(peak^2 n / SSE) with peak = 2^depth - 1 (inf at SSE 0), and PSNR-YUV = (6 Y + U + V) / 8."""
-    peak = 2 ** int(depth) - 1
-    out = {}
+    sse, sizes = [], []
     for name, pa, pb in zip("yuv", a, b):
         pa, pb = np.asarray(pa), np.asarray(pb)
         if pa.shape != pb.shape:
             raise ValueError(f"psnr_planes: plane {name}: {pa.shape} against {pb.shape}")
         d = pa.astype(np.int64) - pb.astype(np.int64)
-        sse = int((d * d).sum())
-        out[f"sse_{name}"] = sse
-        out[f"psnr_{name}"] = float("inf") if sse == 0 else 10.0 * float(np.log10(peak * peak * pa.size / sse))
-    out["psnr_yuv"] = (6.0 * out["psnr_y"] + out["psnr_u"] + out["psnr_v"]) / 8.0
+        sse.append(int((d * d).sum()))
+        sizes.append(pa.size)
+    psnr = psnr_from_sse(sse, sizes, depth)
+    out = {}
+    for name, s in zip("yuv", sse):
+        out[f"sse_{name}"], out[f"psnr_{name}"] = s, psnr[f"psnr_{name}"]
+    out["psnr_yuv"] = psnr["psnr_yuv"]
     return out

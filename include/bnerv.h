@@ -375,6 +375,20 @@ int bnerv_yuv420_to_rgb(void* stream, const void* src, int bytes_per_sample, int
 int bnerv_rgb_to_yuv420(void* stream, const float* x, int B, int H, int W, void* out, int bytes_per_sample, size_t frame_stride_bytes,
                         const bnerv_yuv_coeffs* coeffs);
 
+/* Scoring a decoded clip against its raw source (additive to ABI 9; csrc/yuv.hip; definitions: DESIGN section 32).
+ *   bnerv_yuv420_sse:  a = B packed H x W frames in file layout (what bnerv_rgb_to_yuv420 writes), b = B raw src_h x src_w frames of the same
+ *       bytes_per_sample; the window of b starts at (top, left), both even, its chroma at (top/2, left/2).  out[B][3] (8-byte aligned) receives the
+ *       exact sums of squared differences of the integer codes per frame and plane Y, U, V.  The call zeroes out itself (a memset in front of the
+ *       launch, on `stream`: capturable) and accumulates with 64-bit integer atomics: the result does not depend on the order of the additions.
+ *   bnerv_yuv_luma_f32:  the H x W luma window at (top, left), any parity, of B raw src_h x src_w frames -> out [B, 1, H, W] fp32 =
+ *       float(code) / maxcode, the correctly rounded fp32 division (maxcode: 255 or 1023 as a float).
+ * Both validate like the two entry points above (plus: a window that leaves the frame, an odd window offset for the SSE); every access wider than a
+ * sample is chosen per address. */
+int bnerv_yuv420_sse(void* stream, const void* a, size_t a_stride_bytes, const void* b, size_t b_stride_bytes, int bytes_per_sample, int B, int H, int W,
+                     int src_h, int src_w, int top, int left, unsigned long long* out);
+int bnerv_yuv_luma_f32(void* stream, const void* src, int bytes_per_sample, int B, size_t frame_stride_bytes, int src_h, int src_w, int top, int left,
+                       float* out, int H, int W, float maxcode);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * GEMM-shaped dense work on v_mfma_f32_16x16x4_f32 (csrc/gemm.hip).
  *
