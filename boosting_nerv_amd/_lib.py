@@ -235,6 +235,9 @@ SYMBOLS = {
     "bnerv_rgb_to_yuv420": (_I, [_V, _V, _I, _I, _I, _V, _I, _Z, C.POINTER(YuvCoeffs)]),
     "bnerv_yuv420_sse": (_I, [_V, _V, _Z, _V, _Z, _I, _I, _I, _I, _I, _I, _I, _I, _V]),
     "bnerv_yuv_luma_f32": (_I, [_V, _V, _I, _I, _Z, _I, _I, _I, _I, _V, _I, _I, _F]),
+    "bnerv_yuv420_loss_ws_bytes": (_Z, [_I, _I, _I]),
+    "bnerv_yuv420_loss": (_I, [_V, _V, _I, _I, _I, _V, _I, _Z, _I, _I, _I, _I, _I, _V, C.POINTER(YuvCoeffs), C.POINTER(C.c_float), _F, _V, _I, _V,
+                               _V, _V, _Z]),
     "bnerv_dense_gemm_fwd": (_I, [_V, _V, _V, _V, _V, _V, _I, _I, _I, _I]),
     "bnerv_dense_gemm_bwd_ws_bytes": (_Z, [_I, _I, _I]),
     "bnerv_dense_gemm_bwd": (_I, [_V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _Z, _I, _I, _I, _I]),

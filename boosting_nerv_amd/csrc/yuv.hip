@@ -17,6 +17,9 @@
 //
 // bnerv_yuv420_sse and bnerv_yuv_luma_f32 score packed frames against a window of raw source frames: exact 64-bit sums of
 // squared code differences per frame and plane, and the luma plane as fp32 for MS-SSIM.  The same access policy; their shape is described below.
+//
+// bnerv_yuv420_loss is the training side of that score: the store arithmetic before rounding, minus the source codes, squared
+// and averaged per plane, with its exact gradient -- one stream launch of rgb_to_yuv420's shape plus a fixed-order finalize; described below.
 #include "common.h"
 #include <stdint.h>
 
@@ -288,6 +291,180 @@ __global__ __launch_bounds__(THREADS) void yuv_luma_f32_kernel(const unsigned ch
     }
 }
 
+// ---- the plane loss: rgb_to_yuv420's arithmetic before rounding, minus the source codes, squared; and its exact adjoint ----
+//
+// yuv420_loss_kernel has rgb_to_yuv420_kernel's shape: grid = (blocks over row pairs x strips, B), a thread owns luma rows 2j, 2j + 1 of columns
+// x0 .. x0 + n (n = 4, or 2 at the end of a row), one 16-byte access per channel and row for the prediction and again for the gradient, one access
+// per sample row.  The column left of the strip feeds the [1 2 1] filter of the strip's first chroma sample.  The gradient of the strip's last odd
+// pixel x0 + 3 also needs the chroma error of sample (x0 + 4) / 2, which belongs to the next thread: it is RECOMPUTED here from the two columns
+// right of the strip (they and the next sample's codes are that thread's own loads: L2 hits) instead of exchanged, so one launch gives the sums
+// and the gradient and the kernel needs no LDS and no barrier.  No clamp anywhere: the loss is a plain quadratic of the prediction.
+//   sums:      every wave writes its three sums of squared errors to ws[b][block * 4 + wave][plane] (wave_sum: shuffles); the finalize adds
+//              them lane-strided in fp64 in a fixed order.  No atomics on floats: the same operands give the same bits.
+//   gradient:  g = kg[0][c] e_0(y, x) + kg[1][c] t_u(x) + kg[2][c] t_v(x) with t_p(x) = sum_i k(x, i) e_p(j, i) (the taps of section 33) and
+//              kg[p][c] = 2 w_p d_p M[p, c] / (B m n_p) (times 1/2 for the row pair on the chroma planes), computed by the host in float64 WITHOUT
+//              lambda; written as lambda * g, or added as fma(lambda, g, grad): the accumulating call rounds once more than the writing one.
+struct yuvloss_consts {
+    float m[9], off[3], d[3], inv_m;       // the store struct's matrix, offsets and denominators; 1 / maxcode
+    float kg[9];                           // [plane][channel] gradient constants (above)
+    float lambda;
+};
+
+template <typename T>
+__global__ __launch_bounds__(THREADS) void yuv420_loss_kernel(const float* __restrict__ pred, const int H, const int W, const unsigned char* __restrict__ src,
+                                                              const size_t frame_stride, const int n_frames, const int src_h, const int src_w,
+                                                              const int top, const int left, const float* __restrict__ frame_sel, const int nstrips,
+                                                              float* __restrict__ grad, const int accumulate, float* __restrict__ part,
+                                                              const yuvloss_consts k) {
+    const int t = (int)blockIdx.x * THREADS + (int)threadIdx.x;
+    float sq[3] = {0.0f, 0.0f, 0.0f};
+    if (t < (H >> 1) * nstrips) {                                      // (no early return: every lane takes part in the wave sums below)
+        const int b = (int)blockIdx.y;
+        int f = b;
+        if (frame_sel) f = min(max((int)frame_sel[b], 0), n_frames - 1);
+        const int j = t / nstrips, st = t - j * nstrips;
+        const int x0 = st * STRIP, n = min(STRIP, W - x0), xl = max(x0 - 1, 0);
+        const bool right = x0 + STRIP < W;                             // the next strip exists: W is even, so columns x0 + 4 and x0 + 5 do
+        const size_t HW = (size_t)H * W;
+        const float* const frame = pred + (size_t)b * 3 * HW;
+        const int sw2 = src_w >> 1;
+        const T* Y = reinterpret_cast<const T*>(src + (size_t)f * frame_stride);
+        const T* U = Y + (size_t)src_h * src_w;
+        const T* V = U + (size_t)(src_h >> 1) * sw2;
+        const size_t crow = (size_t)((top >> 1) + j) * sw2;
+        const int c0 = (left >> 1) + (x0 >> 1), clast = (left >> 1) + (W >> 1) - 1;
+        float su[3], sv[3];                                            // codes of chroma samples x0 / 2 + {0, 1, 2} (clamped to the window's last)
+        load_chroma3(U + crow, c0, clast, su);
+        load_chroma3(V + crow, c0, clast, sv);
+        float e0[2][STRIP], cu[3] = {0.0f, 0.0f, 0.0f}, cv[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const size_t o = (size_t)(2 * j + r) * W;
+            float c[3][STRIP + 3];                                     // [channel][0: column x0 - 1 (clamped), 1 + q: column x0 + q, q = 0 .. 5]
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const float* s = frame + (size_t)a * HW + o;
+                c[a][0] = s[xl];
+                if (n == STRIP && (reinterpret_cast<uintptr_t>(s + x0) & 15) == 0) {
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(s + x0);
+#pragma unroll
+                    for (int q = 0; q < STRIP; ++q) c[a][1 + q] = v[q];
+                } else {
+#pragma unroll
+                    for (int q = 0; q < STRIP; ++q) c[a][1 + q] = q < n ? s[x0 + q] : 0.0f;
+                }
+                if (right) {
+                    const float* h = s + x0 + STRIP;
+                    if ((reinterpret_cast<uintptr_t>(h) & 7) == 0) {
+                        const f32x2 v = *reinterpret_cast<const f32x2*>(h);
+                        c[a][5] = v.x; c[a][6] = v.y;
+                    } else {
+                        c[a][5] = h[0]; c[a][6] = h[1];
+                    }
+                } else {
+                    c[a][5] = c[a][6] = 0.0f;
+                }
+            }
+            float ys[STRIP], u[STRIP + 3], v[STRIP + 3];
+            load_luma(Y + (size_t)(top + 2 * j + r) * src_w, left + x0, n, ys);
+#pragma unroll
+            for (int q = 0; q < STRIP + 3; ++q) {
+                const float R = c[0][q], G = c[1][q], B = c[2][q];
+                u[q] = k.m[3] * R + k.m[4] * G + k.m[5] * B;
+                v[q] = k.m[6] * R + k.m[7] * G + k.m[8] * B;
+                if (q >= 1 && q <= STRIP) {
+                    const float e = q - 1 < n ? fmaf(k.d[0], k.m[0] * R + k.m[1] * G + k.m[2] * B, k.off[0] - ys[q - 1]) * k.inv_m : 0.0f;
+                    e0[r][q - 1] = e;
+                    sq[0] = fmaf(e, e, sq[0]);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {                              // 4 h_p(2j + r, x0 / 2 + i), summed over the row pair
+                cu[i] += u[2 * i] + 2.0f * u[2 * i + 1] + u[2 * i + 2];
+                cv[i] += v[2 * i] + 2.0f * v[2 * i + 1] + v[2 * i + 2];
+            }
+        }
+        float eu[3], ev[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const bool have = i == 0 || (i == 1 && n == STRIP) || (i == 2 && right);
+            eu[i] = have ? fmaf(k.d[1], 0.125f * cu[i], k.off[1] - su[i]) * k.inv_m : 0.0f;
+            ev[i] = have ? fmaf(k.d[2], 0.125f * cv[i], k.off[2] - sv[i]) * k.inv_m : 0.0f;
+        }
+        sq[1] = eu[0] * eu[0] + eu[1] * eu[1];                         // (sample 2 is the next thread's)
+        sq[2] = ev[0] * ev[0] + ev[1] * ev[1];
+        if (grad) {
+            const float k0 = x0 == 0 ? 0.75f : 0.5f;                   // column 0 is also its own left neighbour
+            const float tu[STRIP] = {k0 * eu[0], 0.25f * (eu[0] + eu[1]), 0.5f * eu[1], 0.25f * (eu[1] + eu[2])};
+            const float tv[STRIP] = {k0 * ev[0], 0.25f * (ev[0] + ev[1]), 0.5f * ev[1], 0.25f * (ev[1] + ev[2])};
+            float* const gframe = grad + (size_t)b * 3 * HW;
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    float g[STRIP];
+#pragma unroll
+                    for (int q = 0; q < STRIP; ++q) g[q] = k.kg[a] * e0[r][q] + k.kg[3 + a] * tu[q] + k.kg[6 + a] * tv[q];
+                    float* d = gframe + (size_t)a * HW + (size_t)(2 * j + r) * W + x0;
+                    if (n == STRIP && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
+                        f32x4 w = {0.0f, 0.0f, 0.0f, 0.0f};
+                        if (accumulate) w = *reinterpret_cast<const f32x4*>(d);
+#pragma unroll
+                        for (int q = 0; q < STRIP; ++q) w[q] = accumulate ? fmaf(k.lambda, g[q], w[q]) : k.lambda * g[q];
+                        *reinterpret_cast<f32x4*>(d) = w;
+                    } else {
+#pragma unroll
+                        for (int q = 0; q < STRIP; ++q)
+                            if (q < n) d[q] = accumulate ? fmaf(k.lambda, g[q], d[q]) : k.lambda * g[q];
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < 3; ++p) sq[p] = wave_sum(sq[p]);
+    if (((int)threadIdx.x & 63) == 0) {
+        float* o = part + (((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (THREADS / 64) + ((int)threadIdx.x >> 6)) * 3;
+        o[0] = sq[0]; o[1] = sq[1]; o[2] = sq[2];
+    }
+}
+
+// one block: per sample the nparts wave partials of each plane, lane-strided in fp64, then across the four waves; stats, then the batch mean
+__global__ __launch_bounds__(THREADS) void yuv420_loss_final_kernel(const float* __restrict__ part, const int B, const int nparts, const double inv_hw,
+                                                                    const double w0, const double w1, const double w2, const float lambda,
+                                                                    const int accumulate, float* __restrict__ loss, float* __restrict__ stats) {
+    __shared__ double red[3][THREADS / 64];
+    double total = 0.0;
+    for (int b = 0; b < B; ++b) {
+        double s[3] = {0.0, 0.0, 0.0};
+        for (int i = (int)threadIdx.x; i < nparts; i += THREADS) {
+            const float* p = part + ((size_t)b * nparts + i) * 3;
+            s[0] += (double)p[0]; s[1] += (double)p[1]; s[2] += (double)p[2];
+        }
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            s[p] = wave_sum_d(s[p]);
+            if (((int)threadIdx.x & 63) == 0) red[p][(int)threadIdx.x >> 6] = s[p];
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double mse[3];
+#pragma unroll
+            for (int p = 0; p < 3; ++p) mse[p] = (red[p][0] + red[p][1] + red[p][2] + red[p][3]) * inv_hw * (p ? 4.0 : 1.0);
+            const double Lb = w0 * mse[0] + w1 * mse[1] + w2 * mse[2];
+            stats[4 * b] = (float)Lb; stats[4 * b + 1] = (float)mse[0]; stats[4 * b + 2] = (float)mse[1]; stats[4 * b + 3] = (float)mse[2];
+            total += Lb;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float L = (float)(total / (double)B);
+        loss[0] = accumulate ? fmaf(lambda, L, loss[0]) : lambda * L;
+    }
+}
+
+int yuv420_loss_blocks(int H, int W) { return cdiv((H / 2) * cdiv(W, STRIP), THREADS); }
+
 // what every entry point asks of the raw side
 int check_raw(const char* what, const void* raw, int bytes_per_sample, int B, size_t frame_stride_bytes, int H, int W) {
     BNERV_REQUIRE(bytes_per_sample == 1 || bytes_per_sample == 2, "%s: bytes_per_sample=%d (1: yuv420p, 2: yuv420p10le)", what, bytes_per_sample);
@@ -385,5 +562,63 @@ extern "C" int bnerv_yuv_luma_f32(void* stream, const void* src, int bytes_per_s
     else
         hipLaunchKernelGGL(yuv_luma_f32_kernel<unsigned short>, grid, block, 0, s, raw, frame_stride_bytes, src_w, top, left, out, H, W, nstrips, maxcode);
     BNERV_LAUNCH_CHECK("yuv_luma_f32");
+    return BNERV_OK;
+}
+
+extern "C" size_t bnerv_yuv420_loss_ws_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || (size_t)H * W > 0x7fffffffu / 4) return 0;
+    return (size_t)B * yuv420_loss_blocks(H, W) * (THREADS / 64) * 3 * sizeof(float);
+}
+
+extern "C" int bnerv_yuv420_loss(void* stream, const float* pred, int B, int H, int W, const void* src, int bytes_per_sample, size_t frame_stride_bytes,
+                                 int n_frames, int src_h, int src_w, int top, int left, const float* frame_sel, const bnerv_yuv_coeffs* coeffs,
+                                 const float* weights, float lambda, float* grad, int accumulate, float* loss, float* stats, void* ws, size_t ws_bytes) {
+    BNERV_REQUIRE(pred && src && coeffs && weights && loss && stats && ws, "yuv420_loss: null args");
+    BNERV_REQUIRE(n_frames > 0, "yuv420_loss: n_frames=%d", n_frames);
+    if (const int rc = check_raw("yuv420_loss", src, bytes_per_sample, 1, frame_stride_bytes, src_h, src_w)) return rc;
+    BNERV_REQUIRE(B > 0 && B <= 65535 && (frame_sel || B <= n_frames), "yuv420_loss: B=%d samples against %d frames%s", B, n_frames,
+                  frame_sel ? "" : " without frame_sel");
+    BNERV_REQUIRE(H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, "yuv420_loss: 4:2:0 needs even dimensions, got %dx%d", W, H);
+    BNERV_REQUIRE(top >= 0 && left >= 0 && top % 2 == 0 && left % 2 == 0, "yuv420_loss: the window offset (top %d, left %d) must be even and not negative",
+                  top, left);
+    BNERV_REQUIRE(top <= src_h - H && left <= src_w - W, "yuv420_loss: the %dx%d window at (top %d, left %d) leaves the %dx%d frame", W, H, top, left,
+                  src_w, src_h);
+    const double wsum = (double)weights[0] + (double)weights[1] + (double)weights[2];
+    BNERV_REQUIRE(weights[0] >= 0.0f && weights[1] >= 0.0f && weights[2] >= 0.0f && wsum > 0.0 && wsum < 1e30,
+                  "yuv420_loss: weights (%g, %g, %g) must not be negative and must have a positive finite sum", (double)weights[0], (double)weights[1],
+                  (double)weights[2]);
+    BNERV_REQUIRE(coeffs->maxcode >= 1.0f, "yuv420_loss: maxcode=%g", (double)coeffs->maxcode);
+    BNERV_REQUIRE(((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(loss) |
+                    reinterpret_cast<uintptr_t>(stats) | reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(frame_sel)) & 3) == 0,
+                  "yuv420_loss: pred, grad, loss, stats, ws and frame_sel must be 4-byte aligned");
+    if (ws_bytes < bnerv_yuv420_loss_ws_bytes(B, H, W)) return bnerv_set_error(BNERV_E_WS, "yuv420_loss: workspace too small");
+    const int nblocks = yuv420_loss_blocks(H, W), nstrips = cdiv(W, STRIP);
+    const double hw = (double)H * W, m = (double)coeffs->maxcode;
+    const double w[3] = {weights[0] / wsum, weights[1] / wsum, weights[2] / wsum};
+    yuvloss_consts k;
+    for (int i = 0; i < 9; ++i) k.m[i] = coeffs->m[i];
+    for (int p = 0; p < 3; ++p) {
+        k.off[p] = coeffs->off[p];
+        k.d[p] = coeffs->scale[p];
+        // d L / d a_p per sample: 2 w_p e_p / (B m n_p), n_p = HW or HW / 4; a chroma sample spreads 1/2 to each row of its pair
+        const double g = 2.0 * w[p] * (double)coeffs->scale[p] / ((double)B * m * (p ? hw / 4.0 : hw)) * (p ? 0.5 : 1.0);
+        for (int c = 0; c < 3; ++c) k.kg[3 * p + c] = (float)(g * (double)coeffs->m[3 * p + c]);
+    }
+    k.inv_m = (float)(1.0 / m);
+    k.lambda = lambda;
+    const dim3 grid(nblocks, B), block(THREADS);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const unsigned char* raw = static_cast<const unsigned char*>(src);
+    float* part = static_cast<float*>(ws);
+    if (bytes_per_sample == 1)
+        hipLaunchKernelGGL(yuv420_loss_kernel<unsigned char>, grid, block, 0, s, pred, H, W, raw, frame_stride_bytes, n_frames, src_h, src_w, top, left,
+                           frame_sel, nstrips, grad, accumulate, part, k);
+    else
+        hipLaunchKernelGGL(yuv420_loss_kernel<unsigned short>, grid, block, 0, s, pred, H, W, raw, frame_stride_bytes, n_frames, src_h, src_w, top, left,
+                           frame_sel, nstrips, grad, accumulate, part, k);
+    BNERV_LAUNCH_CHECK("yuv420_loss");
+    hipLaunchKernelGGL(yuv420_loss_final_kernel, dim3(1), dim3(THREADS), 0, s, (const float*)part, B, nblocks * (THREADS / 64), 1.0 / hw, w[0], w[1], w[2],
+                       lambda, accumulate, loss, stats);
+    BNERV_LAUNCH_CHECK("yuv420_loss_final");
     return BNERV_OK;
 }

@@ -15,9 +15,37 @@ from . import ops
 from .dp import GradBucket
 
 
+class YuvTerm:
+    """What a step needs to add the plane loss of DESIGN section 33 (ops.yuv420_loss) to its loss: `raw`, the resident raw 4:2:0 clip in
+    file layout (YuvFile.raw_to_device: a uint8 device tensor, frame k at byte k * frame_stride_bytes); coeffs = yuvio.coefficients(...);
+    src_hw = (src_h, src_w) of a raw frame; window = (top, left) of the training crop in it, both even; the plane weights; lam, the factor
+    of the term in the total loss; pure: the term is the whole loss (--loss YUV420), the RGB loss is not launched."""
+
+    def __init__(self, raw, coeffs, src_hw, window, weights=(6, 1, 1), lam=1.0, pure=False, frame_stride_bytes=None):
+        from . import yuvio
+        self.raw, self.coeffs = raw, coeffs
+        self.src_hw = tuple(int(v) for v in src_hw)
+        self.window = tuple(int(v) for v in window)
+        self.weights = yuvio.parse_weights(weights)
+        self.lam, self.pure, self.frame_stride_bytes = float(lam), bool(pure), frame_stride_bytes
+        if self.window[0] % 2 or self.window[1] % 2 or min(self.window) < 0:
+            raise ValueError(f"YuvTerm: the crop offset (top {self.window[0]}, left {self.window[1]}) must be even: a 4:2:0 chroma sample covers a 2x2 block of the source")
+        if not self.lam > 0:
+            raise ValueError(f"YuvTerm: lam={lam} (a positive factor; leave the term out to switch it off)")
+
+    def check_frame(self, H, W):
+        if H % 2 or W % 2:
+            raise ValueError(f"YuvTerm: 4:2:0 needs an even crop, the frames are {H}x{W}")
+        if self.window[0] + H > self.src_hw[0] or self.window[1] + W > self.src_hw[1]:
+            raise ValueError(f"YuvTerm: the {H}x{W} crop at {self.window} leaves the {self.src_hw[0]}x{self.src_hw[1]} source frame")
+
+    def kwargs(self):
+        return dict(weights=self.weights, frame_stride_bytes=self.frame_stride_bytes)
+
+
 class TrainStep:
     def __init__(self, model, optimizer, loss_type, takes_image, batch_shape, device, use_graph=True, warmup_eager=3,
-                 process_group=None, world_size=1, clip_max_norm=0.0, force_bucket=False, dp_buckets=None, mask=None, prune=None):
+                 process_group=None, world_size=1, clip_max_norm=0.0, force_bucket=False, dp_buckets=None, mask=None, prune=None, yuv=None):
         self.model, self.opt, self.loss_type = model, optimizer, loss_type
         # prune (prune.Pruner of this model and optimizer): the gradients of the prunable tensors are multiplied by their masks in one
         # launch after the exchange, in front of the clip and the update (_clip_grads).  The masks keep their addresses, so an event
@@ -44,6 +72,15 @@ class TrainStep:
             self.mask = mask.detach().to(device=device, dtype=torch.float32).contiguous()
             self.static_gtm = torch.zeros_like(self.static_img)
             self.static_in = torch.zeros_like(self.static_img) if takes_image else None
+        # yuv (YuvTerm): the plane loss against the raw source is added to the loss -- value and gradient -- by one more launch behind the
+        # RGB loss (or replaces it: yuv.pure).  The frame number(s) it compares against are device words: the schedule record's on a bound
+        # clip, yuv_sel (refreshed by a device copy in __call__) otherwise.  yuv_stats_out: its [B, 4] stats {L[b], mse_y, mse_u, mse_v}
+        self.yuv, self.yuv_sel, self.yuv_stats_out = yuv, None, None
+        if yuv is not None:
+            if mask is not None:
+                raise ValueError("TrainStep: the plane loss has no masked (inpainting) form: give a mask or yuv, not both")
+            yuv.check_frame(H, W)
+            self.yuv_sel = torch.zeros(B, dtype=torch.float32, device=device)
         self.warmup_eager = warmup_eager
         self.n_calls = 0
         self.graph_a = self.graph_b = None
@@ -107,7 +144,11 @@ class TrainStep:
         # loss_fn(...).backward() + psnr_fn_single(...) of train_nerv_all.py:337-347 as ONE fused launch sequence: the loss
         # gradient seeds backward directly and the per-sample PSNR comes from the same L2 sums (stats[:, 4]).  With a mask the gradient
         # comes back masked and stats[:, 4] is the PSNR against the unmasked frame (ops.loss_value_grad_stats)
-        loss, stats, grad = ops.loss_value_grad_stats(img_out, self.static_img, self.loss_type, mask=self.mask, target_masked=self.static_gtm)
+        if self.yuv is None:
+            loss, stats, grad = ops.loss_value_grad_stats(img_out, self.static_img, self.loss_type, mask=self.mask, target_masked=self.static_gtm)
+            psnr = stats[:, 4]
+        else:
+            loss, psnr, grad = self._yuv_loss(img_out)
         if self._lazy_flush_valid():
             # (dx_ok: the model's first block hands its queued input gradient to an operator of this package, which flushes on entry -- ops._end_block)
             with ops.lazy_flush(dx_ok=getattr(self.model, "lazy_dx_ok", False)):      # slab reductions are flushed by their first reader, not per block
@@ -115,7 +156,24 @@ class TrainStep:
         else:
             img_out.backward(grad)
         self.loss_out = loss
-        self.psnr_out = stats[:, 4]
+        self.psnr_out = psnr
+
+    def _yuv_sel(self):
+        """The device word(s) the plane loss reads its frame number(s) from: on a bound clip the one the frame fetch reads."""
+        return self.opt._sched[0][1][5:6] if self._fetching else self.yuv_sel
+
+    def _yuv_loss(self, img_out):
+        """(loss, psnr [B], grad) with the plane loss: added by its own launch into the RGB loss call's loss and gradient (no further pass
+        over the frame), or alone (yuv.pure; the PSNR then comes from ops.psnr)."""
+        y = self.yuv
+        if y.pure:
+            loss, self.yuv_stats_out, grad = ops.yuv420_loss_value_grad_stats(img_out, y.raw, y.coeffs, y.src_hw, y.window, self._yuv_sel(), lam=y.lam,
+                                                                              **y.kwargs())
+            return loss, ops.psnr(img_out.detach(), self.static_img), grad
+        loss, stats, grad = ops.loss_value_grad_stats(img_out, self.static_img, self.loss_type)
+        _, self.yuv_stats_out, _ = ops.yuv420_loss_value_grad_stats(img_out, y.raw, y.coeffs, y.src_hw, y.window, self._yuv_sel(), lam=y.lam,
+                                                                    grad=grad, loss=loss, **y.kwargs())
+        return loss, stats[:, 4], grad
 
     def _lazy_flush_valid(self):
         """Lazy flushing (ops.lazy_flush) lets backward RETURN weight / bias gradients and TAT channel sums whose slab reductions are
@@ -306,14 +364,18 @@ class TrainStep:
             tail()
 
     # ---- one step ------------------------------------------------------------------------------------------------------
-    def __call__(self, img, norm_idx):
+    def __call__(self, img, norm_idx, frame_idx=None):
         """img [B,3,H,W] fp32 and norm_idx [B] fp64, already on the device.  Returns (loss, psnr[B]) device tensors that are
-        overwritten by the next call."""
+        overwritten by the next call.  frame_idx [B] (any number type, on the device): with a YuvTerm, the raw frames img was made of."""
         if self._fetching:
             self._fetching = False
             self.graph_a = self.graph_b = None      # the captured step started with a frame fetch: capture the plain form
         self.static_img.copy_(img, non_blocking=True)
         self.static_idx.copy_(norm_idx, non_blocking=True)
+        if self.yuv is not None:
+            if frame_idx is None:
+                raise ValueError("TrainStep: a step with the plane loss needs frame_idx, the numbers of the raw frames to compare against")
+            self.yuv_sel.copy_(frame_idx.reshape(-1), non_blocking=True)
         return self._run(None)
 
     def step_frame(self, i):
@@ -357,12 +419,12 @@ class CompressionStep(TrainStep):
     `bpp_out` holds bits per pixel (x N)."""
 
     def __init__(self, model, optimizer, entropy_model, args, batch_shape, device, use_graph=True, warmup_eager=3, world_size=1,
-                 process_group=None, force_bucket=False, prune=None):
+                 process_group=None, force_bucket=False, prune=None, yuv=None):
         if prune is not None:
             raise NotImplementedError("CompressionStep: pruning is built for the plain train step only (engine.TrainStep)")
         super().__init__(model, optimizer, args.loss, "HNeRV_Boost" in args.model or 'pe' not in args.embed, batch_shape, device,
                          use_graph=use_graph, warmup_eager=warmup_eager, clip_max_norm=getattr(args, "clip_max_norm", 0.0),
-                         world_size=world_size, process_group=process_group, force_bucket=force_bucket)
+                         world_size=world_size, process_group=process_group, force_bucket=force_bucket, yuv=yuv)
         self.entropy_model, self.cargs = entropy_model, args
         self.bpp_out = None
 
@@ -379,7 +441,12 @@ class CompressionStep(TrainStep):
         else:
             img_out, _, _ = m(inp, norm_idx=self.static_idx)
             bpp = m.get_bitrate_sum(name="bitrate") / a.final_size
-        out_loss = hu.loss_fn(img_out, self.static_img, self.loss_type)
+        if self.yuv is None:
+            out_loss = hu.loss_fn(img_out, self.static_img, self.loss_type)
+        else:                                   # the plane loss through its autograd form, added to (or, pure, in place of) the RGB loss
+            y = self.yuv
+            term, self.yuv_stats_out = ops.yuv420_loss(img_out, y.raw, y.coeffs, y.src_hw, y.window, self._yuv_sel(), **y.kwargs())
+            out_loss = y.lam * term if y.pure else hu.loss_fn(img_out, self.static_img, self.loss_type) + y.lam * term
         gate = (bpp.detach() / a.full_data_length > a.target_bpp).to(out_loss.dtype)     # `if bpp / N > target_bpp` (:363) on the device
         final_loss = out_loss + gate * a.lambda_rate * bpp
         final_loss.backward()

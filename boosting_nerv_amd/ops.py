@@ -1710,6 +1710,87 @@ def yuv_luma_f32(src, bytes_per_sample, B, src_h, src_w, window=None, frame_stri
     return out
 
 
+YUV_LOSS_STATS = 4         # stats [B, 4] of the plane loss: {L[b], mse_y, mse_u, mse_v}
+
+
+def _yuv420_loss_launch(pred, src, coeffs, src_hw, window, frame_sel, weights, lam, grad, loss, frame_stride_bytes, accumulate):
+    pred = L.require_device(pred, "pred")
+    if pred.dim() != 4 or pred.shape[1] != 3 or pred.dtype != torch.float32 or not pred.is_contiguous() or pred.numel() == 0:
+        raise ValueError(f"yuv420_loss: need a non-empty contiguous fp32 [B, 3, H, W] prediction, got {pred.dtype} {tuple(pred.shape)}")
+    B, _, H, W = pred.shape
+    bps = coeffs.bytes_per_sample
+    src_h, src_w = (int(v) for v in src_hw)
+    top, left = (int(v) for v in window)
+    nbytes = _raw_bytes(src, "yuv420_loss: src")
+    if src.device != pred.device:
+        raise ValueError(f"yuv420_loss: pred is on {pred.device}, src on {src.device}")
+    frame = src_h * src_w * 3 // 2 * bps
+    stride = frame if frame_stride_bytes is None else int(frame_stride_bytes)
+    if frame <= 0 or stride < frame or nbytes < frame:
+        raise ValueError(f"yuv420_loss: frames of {frame} bytes at stride {stride} do not fit the {nbytes} bytes of src")
+    n_frames = (nbytes - frame) // stride + 1
+    if frame_sel is not None:
+        frame_sel = L.require_device(frame_sel, "frame_sel")
+        if frame_sel.dtype != torch.float32 or frame_sel.numel() < B or not frame_sel.is_contiguous() or frame_sel.device != pred.device:
+            raise ValueError(f"yuv420_loss: frame_sel must hold {B} contiguous fp32 frame numbers on {pred.device}")
+    for name, t, shape in (("grad", grad, tuple(pred.shape)), ("loss", loss, None)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != pred.device or
+                              (t.numel() != 1 if shape is None else tuple(t.shape) != shape)):
+            raise ValueError(f"yuv420_loss: {name} must be a contiguous fp32 {'scalar' if shape is None else list(shape)} tensor on {pred.device}")
+    if loss is None:
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+    stats = torch.empty(B, YUV_LOSS_STATS, dtype=torch.float32, device=pred.device)
+    lib = L.load()
+    ws_bytes = lib.bnerv_yuv420_loss_ws_bytes(B, H, W)
+    ws = _ws(max(ws_bytes, 4), pred.device)
+    c = coeffs.store_struct()
+    w = (C.c_float * 3)(*(float(v) for v in weights))
+    L.check(lib.bnerv_yuv420_loss(L.stream(), L.ptr(pred), B, H, W, L.ptr(src), bps, stride, n_frames, src_h, src_w, top, left, L.ptr(frame_sel),
+                                  C.byref(c), w, float(lam), L.ptr(grad), int(accumulate), L.ptr(loss), L.ptr(stats), L.ptr(ws), ws_bytes),
+            "bnerv_yuv420_loss")
+    return loss, stats, grad
+
+
+def yuv420_loss_value_grad_stats(pred, src, coeffs, src_hw, window, frame_sel=None, weights=(6, 1, 1), lam=1.0, grad=None, loss=None,
+                                 frame_stride_bytes=None, need_grad=True):
+    """The plane loss of DESIGN section 33 without an autograd node (the captured step's form): pred [B, 3, H, W] fp32, not clamped, against
+    the H x W window at window = (top, left), both even, of raw 4:2:0 frames `src` (contiguous device bytes in file layout, src_hw = (src_h,
+    src_w), frame k at byte k * frame_stride_bytes) under coeffs = yuvio.coefficients(...).  Sample b is compared against frame b, or against
+    frame int(frame_sel[b]) (fp32 device tensor; clamped to the frames src holds).  Returns (lam * L, stats [B, 4] = {L[b], mse_y, mse_u,
+    mse_v}, lam * dL/dpred).  grad and loss handed in: the term is ADDED to them in the same launch (no extra pass over the frame) and they
+    are returned; loss handed in alone, or need_grad=False: value and stats only, grad is None."""
+    accumulate = loss is not None
+    if grad is not None and loss is None:
+        raise ValueError("yuv420_loss: a grad to accumulate into needs the loss to accumulate into as well")
+    pred = L.f32c(pred.detach())
+    if grad is None and need_grad and not accumulate:
+        grad = torch.empty_like(pred)
+    return _yuv420_loss_launch(pred, src, coeffs, src_hw, window, frame_sel, weights, lam, grad, loss, frame_stride_bytes, accumulate)
+
+
+class _Yuv420Loss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, src, coeffs, src_hw, window, frame_sel, weights, frame_stride_bytes):
+        p = L.f32c(pred.detach())
+        grad = torch.empty_like(p) if ctx.needs_input_grad[0] else None
+        loss, stats, grad = _yuv420_loss_launch(p, src, coeffs, src_hw, window, frame_sel, weights, 1.0, grad, None, frame_stride_bytes, False)
+        ctx.grad = grad
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, gl, _gs):
+        _enter_backward()
+        g = ctx.grad
+        ctx.grad = None
+        return (g * gl if g is not None else None), None, None, None, None, None, None, None
+
+
+def yuv420_loss(pred, src, coeffs, src_hw, window, frame_sel=None, weights=(6, 1, 1), frame_stride_bytes=None):
+    """The plane loss as an autograd function (the eager steps): returns (L [scalar], stats [B, 4]); see yuv420_loss_value_grad_stats."""
+    return _Yuv420Loss.apply(pred, src, coeffs, src_hw, window, frame_sel, tuple(float(v) for v in weights), frame_stride_bytes)
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # depthwise conv of the ConvNeXt encoder block (first kernels of row N3)
 # ----------------------------------------------------------------------------------------------------------------------

@@ -26,6 +26,7 @@ from torch.utils.data import Subset
 
 from . import ops
 from . import runtime as rt
+from . import yuvloss
 from .dp import GradBucket
 from .engine import TrainStep
 from .hnerv_utils import TransformInput, VideoDataSet, adjust_lr, data_split, loss_fn, psnr_fn_device, quant_tensor, quant_tensor_sparse, worker_init_fn
@@ -124,6 +125,8 @@ def build_parser():
     parser.add_argument('--yuv_fmt', type=str, default=None, choices=['yuv420p', 'yuv420p10le'], help='pixel format of a raw .yuv clip (default: 8bit / 10bit in its name)')
     parser.add_argument('--yuv_matrix', type=str, default='bt709', choices=['bt709', 'bt601'], help='colour matrix of a raw .yuv clip')
     parser.add_argument('--yuv_range', type=str, default='limited', choices=['limited', 'full'], help='sample range of a raw .yuv clip')
+    # the plane loss against the raw source (yuvloss.py); off by default.  --loss YUV420 is its pure form
+    yuvloss.add_flags(parser)
     return parser
 
 
@@ -138,7 +141,7 @@ def parse_args(argv=None):
     args.prune_steps = sorted(steps)
     if args.bitstream_sparse and not args.bitstream:
         raise ValueError("--bitstream_sparse: the sparse twin is what --bitstream FILE writes; give the file")
-    return args
+    return yuvloss.check_flags(args)
 
 
 def solve_fc_dim(args, final_size, full_data_length):
@@ -317,6 +320,7 @@ def train(local_rank, args):
         args.start_epoch = max(ckpt['epoch'] if ckpt is not None else 0, 0)
 
     args._frames_dev = full_dataset.to_device(device) if resident else None
+    yuv_term = None if args.eval_only else yuvloss.make_term(args, full_dataset, device, resident)
 
     # pruning (off by default): the masks live in a Pruner; a checkpoint that carries them restores them (resume, --weight, --eval_only)
     pruner = None
@@ -349,12 +353,14 @@ def train(local_rank, args):
     # the reference's masks depend on the frame size only: built once, on a dummy frame of the crop size (None without --inpanting)
     mask = None if args.transform_func.identity else args.transform_func(torch.zeros(1, 3, h, w, device=device), None)[2]
     step = TrainStep(model, optimizer, args.loss, takes_image, (args.batchSize, 3, h, w), device, use_graph=not args.no_graph,
-                     world_size=world, clip_max_norm=args.clip_max_norm, mask=mask, prune=pruner) if mode == "captured" else None
+                     world_size=world, clip_max_norm=args.clip_max_norm, mask=mask, prune=pruner, yuv=yuv_term) if mode == "captured" else None
     # events of this run: those of epochs already trained (resume) are in the checkpoint's masks
     from .prune import schedule as prune_schedule
     prune_events = {e: (j, s) for j, (e, s) in enumerate(prune_schedule(args.prune_sparsity, args.prune_steps))} if args.prune_sparsity > 0 else {}
     log.line(f'Train step: {mode}' + (' (eager: --no_graph)' if mode == "captured" and args.no_graph else '')
              + f', inpainting mask: {args.inpanting if mask is not None else "none"}, clip_max_norm: {args.clip_max_norm}', echo=False)
+    if yuv_term is not None:
+        log.line(yuvloss.describe(yuv_term), echo=False)
     # the generic path (stock Adam) averages its gradients over the ranks with the same flat bucket the fused step uses
     bucket = GradBucket(model.parameters()) if (step is None and world > 1) else None
 
@@ -381,14 +387,17 @@ def train(local_rank, args):
             frames = args._frames_dev[img_idx] if resident else data_to_gpu(sample['img'], device)
             lr = adjust_lr(optimizer, (epoch + float(i) / n_iter) / args.epochs, i, args)
             if step is not None:
-                _, psnr_b = step(frames, norm_idx)
+                _, psnr_b = step(frames, norm_idx) if yuv_term is None else step(frames, norm_idx, frame_idx=img_idx)
+                yuv_stats = step.yuv_stats_out
             else:
-                psnr_b = _generic_step(model, optimizer, bucket, args, frames, img_idx, norm_idx, takes_image)
+                psnr_b = _generic_step(model, optimizer, bucket, args, frames, img_idx, norm_idx, takes_image, yuv_term)
+                yuv_stats = getattr(args, '_yuv_stats_out', None)
             psnr_sum += psnr_b.sum()
             seen += psnr_b.numel()
             if i % args.print_freq == 0 or i == n_iter - 1:                 # the only host sync of the loop
                 log.line('[{}] Rank:{}, Epoch[{}/{}], Step [{}/{}], lr:{:.2e} pred_PSNR: {}'.format(
-                    log.stamp(), local_rank, epoch + 1, args.epochs, i + 1, n_iter, lr, rt.fmt((psnr_sum / seen).cpu(), 4)))
+                    log.stamp(), local_rank, epoch + 1, args.epochs, i + 1, n_iter, lr, rt.fmt((psnr_sum / seen).cpu(), 4))
+                    + ('' if yuv_term is None else f', yuv_psnr: {yuvloss.psnr_text(yuv_stats)}'))
         train_psnr = psnr_sum / max(seen, 1)
         if world > 1:
             dist.all_reduce(train_psnr)
@@ -431,13 +440,21 @@ def train(local_rank, args):
         dist.destroy_process_group()
 
 
-def _generic_step(model, optimizer, bucket, args, frames, img_idx, norm_idx, takes_image):
+def _generic_step(model, optimizer, bucket, args, frames, img_idx, norm_idx, takes_image, yuv_term=None):
     """One eager step for the configuration the captured step does not cover (--optim_type Adam on a boost model: torch.optim.Adam), with
     or without an --inpanting mask: the same kernels, driven op by op.  With several ranks the gradients are averaged through the flat bucket before clipping / the step
-    (the reference gets this from its DistributedDataParallel wrap)."""
+    (the reference gets this from its DistributedDataParallel wrap).  yuv_term (engine.YuvTerm): lam times the plane loss is added through
+    its autograd form (or is the whole loss: --loss YUV420) and its [B, 4] stats are left in args._yuv_stats_out."""
     img_in, img_gt, mask = args.transform_func(frames, img_idx)
     out, _, _ = model(img_in if takes_image else norm_idx, norm_idx=norm_idx)
-    loss = loss_fn(out, img_gt, args.loss) if mask is None else loss_fn(out * mask, img_gt * mask, args.loss)
+    yuv_stats = None
+    if yuv_term is not None and yuv_term.pure:
+        loss, yuv_stats = yuvloss.eager_term(yuv_term, out, img_idx)
+    else:
+        loss = loss_fn(out, img_gt, args.loss) if mask is None else loss_fn(out * mask, img_gt * mask, args.loss)
+        if yuv_term is not None:
+            term, yuv_stats = yuvloss.eager_term(yuv_term, out, img_idx)
+            loss = loss + term
     optimizer.zero_grad()
     loss.backward()
     if bucket is not None:
@@ -445,6 +462,8 @@ def _generic_step(model, optimizer, bucket, args, frames, img_idx, norm_idx, tak
     if args.clip_max_norm > 0:
         torch.nn.utils.clip_grad_norm_(model.parameters(), args.clip_max_norm)
     optimizer.step()
+    if yuv_term is not None:
+        args._yuv_stats_out = yuv_stats
     return psnr_fn_device(out.detach(), img_gt)
 
 

@@ -21,6 +21,7 @@ import torch.multiprocessing as mp
 from . import ops
 from . import runtime as rt
 from . import train_nerv_all as T
+from . import yuvloss
 from .dp import GradBucket
 from .hnerv_utils import TransformInput, adjust_lr, loss_fn
 from .lib.entropy_model import DiffEntropyModel
@@ -60,9 +61,14 @@ def data_to_gpu(x, device):
     return x.to(device, non_blocking=True)
 
 
+def parse_args(argv=None, parser=None):
+    """The parsed command line with the plane-loss flags checked (yuvloss.check_flags: ValueError for what no run can honour)."""
+    return yuvloss.check_flags((parser or build_parser()).parse_args(argv))
+
+
 def main(argv=None):
     parser = build_parser()
-    args = parser.parse_args(argv)
+    args = parse_args(argv, parser)
     if args.bitstream_wide and not args.bitstream_run:
         parser.error('--bitstream_wide needs --bitstream_run N > 0 (only a chunked kind is decoded by the wide kernel)')
     if args.bitstream_tables == 'empirical' and not args.bitstream_run:
@@ -118,7 +124,14 @@ def _eager_rd_step(model, optimizer, entropy_model, bucket, args, frames, img_id
     img_in, img_gt, mask = args.transform_func(frames, img_idx)
     model.cal_params(entropy_model)
     out, bpp = _rate_terms(model, entropy_model, args, img_in if takes_image else norm_idx, norm_idx)
-    dist_loss = loss_fn(out, img_gt, args.loss) if mask is None else loss_fn(out * mask, img_gt * mask, args.loss)
+    yuv_term = getattr(args, '_yuv_term', None)                        # the plane loss (yuvloss.py): added to, or (--loss YUV420) in place of, the RGB loss
+    if yuv_term is not None and yuv_term.pure:
+        dist_loss, args._yuv_stats_out = yuvloss.eager_term(yuv_term, out, img_idx)
+    else:
+        dist_loss = loss_fn(out, img_gt, args.loss) if mask is None else loss_fn(out * mask, img_gt * mask, args.loss)
+        if yuv_term is not None:
+            term, args._yuv_stats_out = yuvloss.eager_term(yuv_term, out, img_idx)
+            dist_loss = dist_loss + term
     over_budget = (bpp.detach() / args.full_data_length > args.target_bpp).to(dist_loss.dtype)
     loss = dist_loss + over_budget * args.lambda_rate * bpp
     optimizer.zero_grad()
@@ -169,6 +182,7 @@ def train(local_rank, args):
 
     args._frames_dev = full_dataset.to_device(device) if resident else None
     takes_image = 'pe' not in args.embed or "HNeRV_Boost" in args.model
+    args._yuv_term = yuv_term = None if args.eval_only else yuvloss.make_term(args, full_dataset, device, resident)
 
     if args.eval_only:
         # (no init_data() here: the quantiser scales come from the checkpoint -- re-initialising them from the weight range would
@@ -192,7 +206,9 @@ def train(local_rank, args):
     cstep = None
     if fused:
         from .engine import CompressionStep
-        cstep = CompressionStep(model, optimizer, entropy_model, args, (args.batchSize, 3, h_, w_), device, world_size=world)
+        cstep = CompressionStep(model, optimizer, entropy_model, args, (args.batchSize, 3, h_, w_), device, world_size=world, yuv=yuv_term)
+    if yuv_term is not None:
+        log.line(yuvloss.describe(yuv_term), echo=False)
     bucket = GradBucket(model.parameters()) if (cstep is None and world > 1) else None
 
     t_start = time.time()
@@ -210,7 +226,7 @@ def train(local_rank, args):
             frames = args._frames_dev[img_idx] if resident else data_to_gpu(sample['img'], device)
             lr = adjust_lr(optimizer, (epoch + float(i) / n_iter) / args.epochs, i, args)
             if cstep is not None:          # the whole step as one captured graph (engine.CompressionStep)
-                loss, psnr_b = cstep(frames, norm_idx)
+                loss, psnr_b = cstep(frames, norm_idx) if yuv_term is None else cstep(frames, norm_idx, frame_idx=img_idx)
                 bpp = cstep.bpp_out
             else:
                 loss, psnr_b, bpp = _eager_rd_step(model, optimizer, entropy_model, bucket, args, frames, img_idx, norm_idx, takes_image)
@@ -219,7 +235,8 @@ def train(local_rank, args):
             if i % args.print_freq == 0 or i == n_iter - 1:
                 log.line('[{}] Rank:{}, Epoch[{}/{}], Step [{}/{}], lr:{:.2e} pred_PSNR: {}, loss:{}, bpp:{}'.format(
                     log.stamp(), local_rank, epoch + 1, args.epochs, i + 1, n_iter, lr, rt.fmt((psnr_sum / seen).cpu(), 2),
-                    rt.fmt(loss.cpu(), 4), rt.fmt((bpp / args.full_data_length).cpu(), 6)))
+                    rt.fmt(loss.cpu(), 4), rt.fmt((bpp / args.full_data_length).cpu(), 6))
+                    + ('' if yuv_term is None else f', yuv_psnr: {yuvloss.psnr_text(cstep.yuv_stats_out if cstep is not None else args._yuv_stats_out)}'))
         now = time.time()
         if is_main:
             print("Time/epoch: \tCurrent:{:.2f} \tAverage:{:.2f}".format(now - t_epoch, (now - t_start) / (epoch + 1 - args.start_epoch)))

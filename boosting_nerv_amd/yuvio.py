@@ -142,6 +142,68 @@ def to_yuv_reference(rgb, coeffs, return_pre=False):
     return (codes, tuple(pre)) if return_pre else codes
 
 
+def parse_weights(text):
+    """'6_1_1' (the CLI form) or three numbers -> (w_y, w_u, w_v) floats: none negative, a positive sum."""
+    parts = str(text).split("_") if isinstance(text, str) else list(text)
+    try:
+        w = tuple(float(p) for p in parts)
+    except (TypeError, ValueError):
+        w = ()
+    if len(w) != 3 or min(w) < 0 or not 0 < sum(w) < float("inf"):
+        raise ValueError(f"yuvio: plane weights {text!r} are not three numbers Y_U_V, none negative, with a positive sum")
+    return w
+
+
+def plane_loss_reference(rgb, planes, coeffs, window=(0, 0), weights=(6, 1, 1), return_pre=False):
+    """The float64 restatement of the plane loss (DESIGN section 33).  rgb [B, 3, H, W], any float, H and W even, NOT clamped;
+    planes = (y, u, v) integer codes [B, src_h, src_w], [B, src_h/2, src_w/2] twice: sample b is compared against the H x W window at
+    window = (top, left), both even, of frame b.  Returns (L [B], mse [B, 3], grad [B, 3, H, W]): grad is d mean_b(L[b]) / d rgb, written
+    out analytically by the adjoint taps.  return_pre=True: also the triple a_p = offset + denom * value the errors are taken of -- for
+    rgb in [0, 1] the `pre` of to_yuv_reference(rgb, coeffs, return_pre=True)."""
+    P = np.asarray(rgb, dtype=np.float64)
+    if P.ndim != 4 or P.shape[1] != 3 or P.shape[2] % 2 or P.shape[3] % 2:
+        raise ValueError(f"yuvio: {P.shape} is no [B, 3, H, W] batch of even size")
+    B, _, H, W = P.shape
+    top, left = (int(v) for v in window)
+    y, u, v = (np.asarray(a) for a in planes)
+    if top % 2 or left % 2 or top < 0 or left < 0 or y.ndim != 3 or y.shape[0] != B or top + H > y.shape[1] or left + W > y.shape[2]:
+        raise ValueError(f"yuvio: the {H}x{W} window at (top {top}, left {left}) of luma planes {y.shape} for {B} samples")
+    w = np.asarray(parse_weights(weights), dtype=np.float64)
+    w = w / w.sum()
+    M, m = coeffs.to_yuv, float(coeffs.maxcode)
+    src = [y[:, top:top + H, left:left + W].astype(np.float64)]
+    src += [c[:, top // 2:top // 2 + H // 2, left // 2:left // 2 + W // 2].astype(np.float64) for c in (u, v)]
+    xe = np.arange(0, W, 2)
+    pre, err, mse = [], [], np.zeros((B, 3))
+    for p in range(3):
+        val = M[p, 0] * P[:, 0] + M[p, 1] * P[:, 1] + M[p, 2] * P[:, 2]
+        if p:
+            h = (val[..., np.maximum(xe - 1, 0)] + 2.0 * val[..., xe] + val[..., xe + 1]) / 4.0
+            val = 0.5 * (h[:, 0::2, :] + h[:, 1::2, :])
+        a = coeffs.offset[p] + coeffs.denom[p] * val
+        e = (a - src[p]) / m
+        pre.append(a)
+        err.append(e)
+        mse[:, p] = (e * e).mean(axis=(1, 2))
+    L = mse @ w
+    grad = np.zeros_like(P)
+    # luma: every pixel its own error
+    gy = 2.0 * w[0] * coeffs.denom[0] / (B * m * H * W) * err[0]
+    for c in range(3):
+        grad[:, c] += M[0, c] * gy
+    # chroma: sample (j, i) reaches rows 2j, 2j + 1 (1/2 each) and columns 2i - 1 (1/4; clamped: column 0 takes it twice), 2i (1/2), 2i + 1 (1/4)
+    for p in (1, 2):
+        ge = 2.0 * w[p] * coeffs.denom[p] / (B * m * (H * W / 4.0)) * 0.5 * err[p]          # [B, H/2, W/2]
+        t = np.zeros((B, H // 2, W))
+        t[..., xe] += 0.5 * ge
+        t[..., xe + 1] += 0.25 * ge
+        np.add.at(t, (slice(None), slice(None), np.maximum(xe - 1, 0)), 0.25 * ge)
+        t = np.repeat(t, 2, axis=1)
+        for c in range(3):
+            grad[:, c] += M[p, c] * t
+    return (L, mse, grad, tuple(pre)) if return_pre else (L, mse, grad)
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # files
 # ----------------------------------------------------------------------------------------------------------------------
@@ -246,6 +308,33 @@ class YuvFile:
                 ops.yuv420_to_rgb(staged[slot], coeffs, i1 - i0, self.height, self.width, crop=(top, left, ch, cw), out=clip[i0:i1])
             torch.cuda.current_stream().synchronize()
         return clip
+
+    def raw_to_device(self, device, count=None, chunk=32):
+        """The first `count` (default: all) frames as they lie in the file, one uint8 [n * frame_bytes] device tensor: what the plane loss
+        (ops.yuv420_loss) compares against.  1.5 (8 bit) or 3 (10 bit) bytes per pixel and frame beside the 12 of the
+        fp32 clip.  The same two pinned buffers as to_device: the host fills one while the copy engine drains the other."""
+        import torch
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("YuvFile.raw_to_device: the resident raw clip lives on a ROCm GPU (raw() is the host view)")
+        n = self.n_frames if count is None else int(count)
+        if not 0 < n <= self.n_frames:
+            raise ValueError(f"YuvFile.raw_to_device: count={count} of a {self.n_frames}-frame clip")
+        chunk = max(1, min(int(chunk), n))
+        out = torch.empty(n * self.frame_bytes, dtype=torch.uint8, device=device)
+        pinned = [torch.empty(chunk * self.frame_bytes, dtype=torch.uint8, pin_memory=True) for _ in (0, 1)]
+        events = [torch.cuda.Event() for _ in (0, 1)]
+        with torch.cuda.device(device):
+            for k, i0 in enumerate(builtins.range(0, n, chunk)):
+                i1, slot = min(i0 + chunk, n), k % 2
+                nbytes = (i1 - i0) * self.frame_bytes
+                if k >= 2:
+                    events[slot].synchronize()                       # the copy that last read this pinned buffer is done
+                pinned[slot].numpy()[:nbytes] = self.raw(i0, i1)
+                out[i0 * self.frame_bytes:i1 * self.frame_bytes].copy_(pinned[slot][:nbytes], non_blocking=True)
+                events[slot].record()
+            torch.cuda.current_stream().synchronize()
+        return out
 
 
 def write(path, frames, pix_fmt="yuv420p", append=False):

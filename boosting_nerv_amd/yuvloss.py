@@ -1,0 +1,86 @@
+"""The command-line side of the plane loss, shared by train_nerv_all.py and train_nerv_compression.py: the three flags, the
+combinations no run can honour (refused with a ValueError before training starts), the record the steps take (engine.YuvTerm) and the log
+texts.  The loss itself is csrc/yuv.hip behind ops.yuv420_loss / ops.yuv420_loss_value_grad_stats; yuvio.plane_loss_reference restates it.
+
+    --yuv_loss LAMBDA         total loss = loss_fn(--loss) + LAMBDA * L          (default 0: off)
+    --yuv_loss_weights 6_1_1  the plane weights of L
+    --loss YUV420             L alone, times --yuv_loss (which then defaults to 1)
+
+Matrix, range and depth are the loader's (--yuv_matrix, --yuv_range, the file's format)."""
+import numpy as np
+
+PURE = "YUV420"
+
+
+def add_flags(parser):
+    parser.add_argument('--yuv_loss', type=float, default=0., metavar='LAMBDA',
+                        help='add LAMBDA times the 4:2:0 plane loss against the raw .yuv source to the loss (0 = off; 1 under --loss YUV420)')
+    parser.add_argument('--yuv_loss_weights', type=str, default='6_1_1', help='plane weights Y_U_V of the plane loss')
+
+
+def check_flags(args):
+    """The parse-time half: normalises args.yuv_loss / args.yuv_loss_weights and refuses what needs no file to be refused."""
+    from . import yuvio
+    weights = yuvio.parse_weights(args.yuv_loss_weights)
+    if not np.isfinite(args.yuv_loss) or args.yuv_loss < 0:
+        raise ValueError(f"--yuv_loss {args.yuv_loss}: a factor >= 0 (0 switches the term off)")
+    pure = args.loss == PURE
+    if pure and args.yuv_loss == 0:
+        args.yuv_loss = 1.0
+    if not args.yuv_loss > 0:
+        return args
+    what = f"--loss {PURE}" if pure else "--yuv_loss"
+    if getattr(args, "inpanting", "none") != "none":
+        raise ValueError(f"{what} with --inpanting {args.inpanting}: the plane loss has no masked form")
+    if getattr(args, "host_frames", False) or getattr(args, "embed_inter", False):
+        raise ValueError(f"{what} needs the clip resident on the device: drop --host_frames / --embed_inter")
+    if not str(args.data_path).lower().endswith(".yuv"):
+        raise ValueError(f"{what} compares against the planes of a raw source: --data_path {args.data_path} is no .yuv file")
+    h, w = (int(v) for v in args.crop_list.split('_')[:2])
+    if h % 2 or w % 2:
+        raise ValueError(f"{what}: 4:2:0 needs an even crop, --crop_list gives {h}x{w}")
+    args.yuv_loss_weights = "_".join(f"{v:g}" for v in weights)
+    return args
+
+
+def make_term(args, dataset, device, resident):
+    """engine.YuvTerm of this run, or None with the term off: uploads the raw clip beside the fp32 one.  Refuses (ValueError) a clip that is
+    not resident or not raw, and a centre crop that starts at an odd row or column of the source."""
+    from . import yuvio
+    from .engine import YuvTerm
+    if not getattr(args, "yuv_loss", 0) > 0:
+        return None
+    what = f"--loss {PURE}" if args.loss == PURE else "--yuv_loss"
+    if dataset.yuv is None:
+        raise ValueError(f"{what} compares against the planes of a raw source: --data_path {args.data_path} is no .yuv file")
+    if not resident:
+        raise ValueError(f"{what} needs the clip resident on the device: drop --host_frames / --embed_inter")
+    clip = dataset.yuv
+    top, left, ch, cw = clip.crop_window((dataset.crop_h, dataset.crop_w))
+    if top % 2 or left % 2 or ch % 2 or cw % 2:
+        raise ValueError(f"{what}: the {cw}x{ch} centre crop of the {clip.width}x{clip.height} source starts at (top {top}, left {left}); offset and "
+                         "size must be even, a chroma sample covers a 2x2 block of the source (choose --crop_list so that the margins are multiples of 4)")
+    coeffs = yuvio.coefficients(dataset.yuv_matrix, dataset.yuv_range, clip.depth)
+    raw = clip.raw_to_device(device, count=len(dataset.samples))
+    return YuvTerm(raw, coeffs, (clip.height, clip.width), (top, left), weights=args.yuv_loss_weights, lam=args.yuv_loss, pure=args.loss == PURE)
+
+
+def describe(term):
+    c = term.coeffs
+    return (f"YUV loss: lambda {term.lam:g}, weights {'_'.join(f'{v:g}' for v in term.weights)}, matrix {c.matrix}, range {c.range}, {c.depth} bit"
+            + (" (pure: the RGB loss is off)" if term.pure else ""))
+
+
+def psnr_text(stats):
+    """'Y U V': -10 log10 of the batch-mean plane MSEs of a [B, 4] stats tensor (the PSNR of each plane before rounding to codes)."""
+    mse = stats[:, 1:4].double().mean(dim=0).cpu().clamp_min(1e-20)
+    return " ".join(f"{v:.2f}" for v in (-10.0 * mse.log10()).tolist())
+
+
+def eager_term(term, out, img_idx):
+    """(lam * L with its autograd node, stats) for the eager steps: sample b against raw frame img_idx[b]."""
+    import torch
+    from . import ops
+    sel = img_idx.reshape(-1).to(out.device, dtype=torch.float32)
+    loss, stats = ops.yuv420_loss(out, term.raw, term.coeffs, term.src_hw, term.window, sel, **term.kwargs())
+    return term.lam * loss, stats

@@ -389,6 +389,23 @@ int bnerv_yuv420_sse(void* stream, const void* a, size_t a_stride_bytes, const v
 int bnerv_yuv_luma_f32(void* stream, const void* src, int bytes_per_sample, int B, size_t frame_stride_bytes, int src_h, int src_w, int top, int left,
                        float* out, int H, int W, float maxcode);
 
+/* Training against the raw source's planes (additive to ABI 9; csrc/yuv.hip; definition: DESIGN section 33; yuvio.plane_loss_reference is the
+ * float64 restatement).  pred [B, 3, H, W] fp32, H and W even, NOT clamped; src = n_frames raw src_h x src_w frames in file layout; the window
+ * at (top, left), both even.  coeffs is the STORE struct (m = to_yuv, scale = denom).  With a_p the store arithmetic before rounding,
+ *   e_p = (a_p - code_p) / maxcode,  mse_p[b] = mean over plane p of e_p^2,  L[b] = sum_p w_p mse_p[b] (w = weights / sum(weights)),  L = mean_b L[b]
+ *   frame_sel:  null -- sample b is compared against frame b (B <= n_frames); else B device floats, sample b against frame (int)frame_sel[b]
+ *       clamped to [0, n_frames - 1] (the convention of bnerv_fetch_frame's sel_dev: a captured step on a resident clip hands over that word)
+ *   grad (may be null):  accumulate == 0: grad = lambda * dL/dpred, loss[0] = lambda * L;  accumulate != 0: both are ADDED to what is there
+ *   stats [B, 4] = {L[b], mse_y, mse_u, mse_v}, always written, never scaled by lambda
+ * One streaming launch (per-wave partial sums to ws) plus a one-block finalize that adds them in a fixed order: the same operands give the same
+ * bits.  Validates before any launch: null pointers, odd H / W / top / left, a window that leaves the frame, a stride smaller than a frame,
+ * bytes_per_sample, negative weights or a zero weight sum, B > n_frames without frame_sel; BNERV_E_WS for a workspace below _ws_bytes.  fp32
+ * operands need 4-byte, 16-bit samples 2-byte alignment; every wider access is chosen per address. */
+size_t bnerv_yuv420_loss_ws_bytes(int B, int H, int W);
+int bnerv_yuv420_loss(void* stream, const float* pred, int B, int H, int W, const void* src, int bytes_per_sample, size_t frame_stride_bytes,
+                      int n_frames, int src_h, int src_w, int top, int left, const float* frame_sel, const bnerv_yuv_coeffs* coeffs,
+                      const float* weights, float lambda, float* grad, int accumulate, float* loss, float* stats, void* ws, size_t ws_bytes);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * GEMM-shaped dense work on v_mfma_f32_16x16x4_f32 (csrc/gemm.hip).
  *

@@ -1,0 +1,203 @@
+"""Measure the plane loss (csrc/yuv.hip bnerv_yuv420_loss), in ONE process:
+  kernel   the launch pair (stream kernel + finalize) at 720p and 1080p, 8 and 10 bit, writing (accumulate off) and adding into a gradient
+           (accumulate on), replayed from a captured graph of 50 calls, best of 5 replays; the bytes it has to move and the rate that makes; and
+           the same loss and gradient written with stock torch ops (float planes handed to it, autograd backward), eager, HIP events, best of 10;
+  step     C1's (720p) and C3's (1080p) captured step with the term (TrainStep(yuv=YuvTerm), --yuv_loss form) against the step without it
+           (TrainStep(yuv=None): the code path of the parent commit), alternated over `--repeats` rounds of `--steps` steps, host clock
+           around work that ends in a device synchronisation;
+  train    the C1 recipe on a synthetic 720p clip written out as a raw 8-bit .yuv file (`--frames` frames, `--epochs` epochs), trained with
+           --loss Fusion10_freq, the same plus --yuv_loss at `--lambdas`, and --loss YUV420; every run's post-hoc bitstream scored with
+           codec.Decoder.score against the file: PSNR-Y / -U / -V / -YUV, RGB PSNR, MS-SSIM-Y.
+usage: python tools/kyuvloss.py [--only kernel|step|train] [--steps 100] [--repeats 3] [--frames 16] [--epochs 160] [--lambdas 300 3000]
+(needs the GPU)"""
+import argparse
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+N_FRAMES = 4
+
+
+def _raw_clip(n, h, w, depth, dev):
+    """(coeffs, fp32 clip [n, 3, h, w], raw bytes [n * frame]) of the synthetic clip: packed by the store kernel, loaded back by the load kernel."""
+    import torch
+    from boosting_nerv_amd import ops, yuvio
+    from boosting_nerv_amd.synth import SyntheticVideo
+    c = yuvio.coefficients("bt709", "limited", depth)
+    vid = SyntheticVideo(n, h, w)
+    rgb = torch.stack([vid.frame(i, device=dev) for i in range(n)])
+    raw = ops.rgb_to_yuv420(rgb, c).reshape(-1)
+    return c, ops.yuv420_to_rgb(raw, c, n, h, w), raw
+
+
+def _torch_form(c, raw, h, w, dev):
+    """The definition with stock torch ops on float planes prepared once: f(P) -> L (B = 1, weights 6 1 1)."""
+    import torch
+    n = h * w
+    s = raw[:n * 3 // 2 * c.bytes_per_sample].view(torch.uint8 if c.bytes_per_sample == 1 else torch.int16).float()
+    y, u, v = s[:n].view(1, h, w), s[n:n + n // 4].view(1, h // 2, w // 2), s[n + n // 4:].view(1, h // 2, w // 2)
+    M = torch.tensor(c.to_yuv, dtype=torch.float32, device=dev)
+    o, d, m = [float(x) for x in c.offset], [float(x) for x in c.denom], float(c.maxcode)
+
+    def f(P):
+        val = torch.einsum("pc,bchw->bphw", M, P)
+        L = 0.75 * (((o[0] + d[0] * val[:, 0]) - y) / m).square().mean()
+        for p, src in ((1, u), (2, v)):
+            cc = val[:, p]
+            left = torch.cat([cc[..., :1], cc[..., 1:-1:2]], dim=-1)
+            hh = (left + 2.0 * cc[..., 0::2] + cc[..., 1::2]) * 0.25
+            a = o[p] + d[p] * 0.5 * (hh[:, 0::2] + hh[:, 1::2])
+            L = L + 0.125 * ((a - src) / m).square().mean()
+        return L
+    return f
+
+
+def kernel():
+    import torch
+    from kinpaint import time_launch
+    from boosting_nerv_amd import ops
+    dev = torch.device("cuda:0")
+    for h, w in ((720, 1280), (1080, 1920)):
+        for depth in (8, 10):
+            c, clip, raw = _raw_clip(1, h, w, depth, dev)
+            pred = (clip + 0.05 * torch.randn_like(clip)).contiguous()
+            grad, loss = torch.zeros_like(pred), torch.zeros((), device=dev)
+            write = time_launch(lambda: ops.yuv420_loss_value_grad_stats(pred, raw, c, (h, w), (0, 0)))
+            add = time_launch(lambda: ops.yuv420_loss_value_grad_stats(pred, raw, c, (h, w), (0, 0), grad=grad, loss=loss))
+            value = time_launch(lambda: ops.yuv420_loss_value_grad_stats(pred, raw, c, (h, w), (0, 0), need_grad=False))
+            px = h * w
+            b_write, b_add = px * (12 + 12 + 1.5 * c.bytes_per_sample), px * (12 + 24 + 1.5 * c.bytes_per_sample)
+            f = _torch_form(c, raw, h, w, dev)
+            p = pred.clone().requires_grad_(True)
+
+            def stock():
+                p.grad = None
+                f(p).backward()
+            for _ in range(3):
+                stock()
+            best = []
+            for _ in range(10):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); stock(); e1.record()
+                torch.cuda.synchronize()
+                best.append(e0.elapsed_time(e1) * 1e3)
+            mine = ops.yuv420_loss_value_grad_stats(pred, raw, c, (h, w), (0, 0))
+            rel = float((mine[2] - p.grad).abs().max() / p.grad.abs().max())
+            print(f"kernel {h}x{w} {depth} bit: write {write:.1f} us ({b_write / write / 1e6:.2f} TB/s of {b_write / 1e6:.1f} MB), "
+                  f"accumulate {add:.1f} us ({b_add / add / 1e6:.2f} TB/s of {b_add / 1e6:.1f} MB), value only {value:.1f} us;  "
+                  f"stock torch ops fwd+bwd eager {min(best):.1f} us best of 10;  max|grad - torch grad| / max|grad| {rel:.1e}", flush=True)
+
+
+def step(steps, repeats):
+    import torch
+    import bench
+    from boosting_nerv_amd.engine import TrainStep, YuvTerm
+    from boosting_nerv_amd.optimizer import Adan
+    dev = torch.device("cuda:0")
+    for name in ("c1", "c3"):
+        r = bench.RECIPES[name]
+        h, w = r["h"], r["w"]
+        args = bench.build(name)[0]
+        takes_image = "HNeRV_Boost" in args.model or "pe" not in args.embed
+        c, frames, raw = _raw_clip(N_FRAMES, h, w, 8, dev)
+        norm = torch.tensor([(i + 1) / N_FRAMES for i in range(N_FRAMES)], dtype=torch.float64, device=dev)
+        idx = torch.arange(N_FRAMES, device=dev)
+        paths = {}
+        for key, term in (("with the term (yuv=YuvTerm, lam 1000)", YuvTerm(raw, c, (h, w), (0, 0), lam=1000.0)), ("without (yuv=None)", None)):
+            model = bench.build(name)[1].to(dev)
+            opt = Adan(model.parameters(), lr=args.lr)
+            paths[key] = TrainStep(model, opt, args.loss, takes_image, (1, 3, h, w), dev, use_graph=True, warmup_eager=3, yuv=term)
+
+        def run(s_, s):
+            k = s % N_FRAMES
+            if s_.yuv is None:
+                s_(frames[k:k + 1], norm[k:k + 1])
+            else:
+                s_(frames[k:k + 1], norm[k:k + 1], frame_idx=idx[k:k + 1])
+        for s_ in paths.values():
+            for s in range(8):
+                run(s_, s)
+        torch.cuda.synchronize()
+        assert all(s_.graph_a is not None for s_ in paths.values())
+        ms = {k: [] for k in paths}
+        for rnd in range(repeats):
+            for k, s_ in paths.items():
+                torch.cuda.synchronize()
+                t0 = time.time()
+                for s in range(steps):
+                    run(s_, s)
+                torch.cuda.synchronize()
+                ms[k].append((time.time() - t0) / steps * 1e3)
+                print(f"{name} round {rnd} {k}: {ms[k][-1]:.3f} ms/step", flush=True)
+        mean = {k: sum(v) / len(v) for k, v in ms.items()}
+        ka, kb = list(paths)
+        for k in paths:
+            print(f"{name} step {k}: {mean[k]:.3f} ms/step (spread {max(ms[k]) - min(ms[k]):.3f} over {repeats} rounds of {steps} steps)")
+        print(f"{name} step with - without = {(mean[ka] - mean[kb]) * 1e3:.1f} us ({(mean[ka] / mean[kb] - 1) * 100:.2f} %)", flush=True)
+        del paths
+
+
+def train(frames, epochs, lambdas):
+    import torch
+    import bench
+    from boosting_nerv_amd import codec, yuvio
+    from boosting_nerv_amd import train_nerv_all as T
+    from boosting_nerv_amd.synth import SyntheticVideo
+    h, w = 720, 1280
+    flags = bench.RECIPES["c1"]["flags"].split()
+    for drop in ("-e", "--eval_freq", "--loss"):
+        if drop in flags:
+            i = flags.index(drop)
+            del flags[i:i + 2]
+    c = yuvio.coefficients("bt709", "limited", 8)
+    runs = [("Fusion10_freq", ["--loss", "Fusion10_freq"])]
+    runs += [(f"Fusion10_freq + {lam:g} L", ["--loss", "Fusion10_freq", "--yuv_loss", f"{lam:g}"]) for lam in lambdas]
+    runs += [("YUV420", ["--loss", "YUV420"])]
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as tmp:
+        os.chdir(tmp)
+        try:
+            vid = SyntheticVideo(frames, h, w)
+            src = os.path.join(tmp, f"synth_{w}x{h}_8bit.yuv")
+            yuvio.write(src, (yuvio.to_yuv_reference(vid.frame(i).numpy(), c) for i in range(frames)), c.pix_fmt)
+            ref = yuvio.YuvFile(src)
+            print(f"train: {frames} frames of the synthetic clip as {os.path.basename(src)}, {epochs} epochs ({frames * epochs} steps)")
+            print("| loss | PSNR-Y | PSNR-U | PSNR-V | PSNR-YUV | PSNR-RGB | MS-SSIM-Y | train s |")
+            print("|---|---|---|---|---|---|---|---|")
+            for k, (tag, extra) in enumerate(runs):
+                out = f"r{k}"
+                t0 = time.time()
+                T.main(flags + extra + ["--data_path", src, "--vid", "kyuvloss", "--outf", out, "-e", str(epochs), "--eval_freq", str(epochs), "--not_resume",
+                                        "--bitstream", f"{out}.bnrq", "-p", "100000"])
+                torch.cuda.synchronize()
+                secs = time.time() - t0
+                m = codec.Decoder(f"{out}.bnrq", "cuda:0", pack=c.pix_fmt).score(ref, rgb=True)["mean"]
+                print(f"| {tag} | {m['psnr_y']:.3f} | {m['psnr_u']:.3f} | {m['psnr_v']:.3f} | {m['psnr_yuv']:.3f} | {m['psnr_rgb']:.3f} | {m['msssim_y']:.5f} | {secs:.0f} |",
+                      flush=True)
+        finally:
+            os.chdir(cwd)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--only", choices=["kernel", "step", "train"], default=None)
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--frames", type=int, default=16)
+    ap.add_argument("--epochs", type=int, default=160)
+    ap.add_argument("--lambdas", type=float, nargs="+", default=[300.0, 3000.0])
+    a = ap.parse_args()
+    if a.only in (None, "kernel"):
+        kernel()
+    if a.only in (None, "step"):
+        step(a.steps, a.repeats)
+    if a.only in (None, "train"):
+        train(a.frames, a.epochs, a.lambdas)
+
+
+if __name__ == "__main__":
+    main()
