@@ -171,6 +171,13 @@ class RanswItem(C.Structure):      # bnerv_ransw_item
                 ("has_beta", C.c_int), ("shift", C.c_uint32), ("span_m1", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+CHAIN_UNROLL, CHAIN_SEG = 8, 64    # BNERV_CHAIN_UNROLL, BNERV_CHAIN_SEG
+
+
+class DeltaStats(C.Structure):     # bnerv_delta_stats
+    _fields_ = [("max_key", C.c_uint32), ("min_key_inv", C.c_uint32), ("s1", C.c_int64), ("s2", C.c_uint64)]
+
+
 PRUNE_SLICE = 16384     # BNERV_PRUNE_SLICE
 
 
@@ -265,6 +272,9 @@ SYMBOLS = {
     "bnerv_sym_hist_wide": (_I, [_V, _V, _I, _V, _Z, _V, _Z, _V]),
     "bnerv_rans_encode_wide": (_I, [_V, _V, _Z, _V, _I, _V, _Z, _I, _V, _Z, _I, _V, _V]),
     "bnerv_rans_dequant_wide": (_I, [_V, _V, _Z, _V, _Z, _V, _Z, _V, _I, _V, _Z, _I, _V]),
+    "bnerv_embed_delta": (_I, [_V, _V, _Z, _I, _Z, _V, _Z, _V]),
+    "bnerv_rans_decode_wide": (_I, [_V, _V, _Z, _V, _Z, _V, _Z, _V, _I, _V, _Z, _I, _V]),
+    "bnerv_embed_chain_dequant": (_I, [_V, _V, _Z, _V, _V, _V, _I, _Z, _V, _Z, _V]),
     "bnerv_huff_encode": (C.c_long, [_V, _V, _I, _V, _I, _V, _Z, _V, _Z]),
     "bnerv_huff_decode": (_I, [_V, _Z, _V, _Z, _V, _I, _V, _I, _V]),
     "bnerv_huff_dequant": (_I, [_V, _V, _Z, _V, _Z, _V, _I, _V, _I, _V]),

@@ -39,7 +39,14 @@ encode(..., run=N, tables=..., wide=True) on the device, repack(..., wide=True) 
 The post-hoc file has a sparse kind (zstream.py) for pruned models: train_nerv_all.py --bitstream FILE --bitstream_sparse
 quantises every prunable tensor with hnerv_utils.quant_tensor_sparse -- a zero weight stays exactly zero -- and encode_posthoc() writes the
 twin under a Huffman alphabet with leaves for runs of zeros; Decoder lets ONE kernel (ops.huffz_dequant) decode it.  decode, psnr and info
-work on it; there is no repack into it (a .bnrq twin has already lost its zeros)."""
+work on it; there is no repack into it (a .bnrq twin has already lost its zeros).
+
+The wide kind has a temporal form (tstream.py) for HNeRV_Boost: the embedding record of frame t >= 1 holds the frame's
+symbols or their integer differences to the frame before, whichever costs fewer bits -- encode(..., run=N, tables=..., wide=True,
+temporal=True) on the device, repack(..., wide=True, temporal=True) the same bytes on the host; Decoder entropy-decodes the embedding
+records to integers (ops.AnsDecodeWide) and resolves the chains in one launch (ops.EmbedChainDequant):
+
+    python -m boosting_nerv_amd.codec repack in.bnrv out.bnrt [--run N] [--tables empirical] --temporal"""
 import argparse
 import builtins
 import json
@@ -49,7 +56,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import bitstream, estream, qstream, rstream, wstream, zstream
+from . import bitstream, estream, qstream, rstream, tstream, wstream, zstream
 from .bitstream import Record
 
 TABLES = ("gaussian", "empirical")
@@ -182,7 +189,7 @@ def _frames_in_order(frames_or_loader, args, device):
 
 
 @torch.no_grad()
-def encode(model, entropy_model, args, frames_or_loader, path, run=0, tables="gaussian", wide=False):
+def encode(model, entropy_model, args, frames_or_loader, path, run=0, tables="gaussian", wide=False, temporal=False):
     """Write the model (and, for HNeRV_Boost, every frame's embedding) as a bitstream to `path` (a file name or a binary file object);
     returns bitstream.info of what was written.
 
@@ -197,13 +204,21 @@ def encode(model, entropy_model, args, frames_or_loader, path, run=0, tables="ga
     never leave it, no version-1 message is built; returns estream.info then.
 
     wide=True (with run > 0) writes the wide kind (wstream.py): the device path of tables="empirical" with a shift per record, so a record
-    may span any number of symbol values; with tables="gaussian" every record stays under its Gaussian.  Returns wstream.info then."""
+    may span any number of symbol values; with tables="gaussian" every record stays under its Gaussian.  Returns wstream.info then.
+
+    temporal=True (with wide=True; HNeRV_Boost only) writes the temporal kind (tstream.py): the wide file in which the embedding record of a frame
+    t >= 1 holds the differences to the frame before where that costs fewer bits (_embed_pred) -- one more launch for the differences, their
+    candidates in the same histogram, encode and compaction launches.  Returns tstream.info then."""
     if tables not in TABLES:
         raise ValueError(f"codec.encode: tables = {tables!r} ({' | '.join(TABLES)})")
+    if temporal and not wide:
+        raise ValueError("codec.encode: temporal=True needs wide=True (the temporal kind is the wide file with predicted embedding records)")
     if wide:
         if not run:
             raise ValueError("codec.encode: wide=True needs run > 0 (only a chunked kind is decoded by the wide kernel)")
-        return _encode_empirical(model, entropy_model, args, frames_or_loader, path, rstream.check_run(run), wide=tables)
+        if temporal:
+            check_temporal_model(getattr(args, "model", None))
+        return _encode_empirical(model, entropy_model, args, frames_or_loader, path, rstream.check_run(run), wide=tables, temporal=temporal)
     if tables == "empirical":
         if not run:
             raise ValueError("codec.encode: tables='empirical' needs run > 0 (only the chunked kind carries tables)")
@@ -299,14 +314,51 @@ def _wide_record(side, shift, table_cdf, n_words, run_words):
     return wstream.WRecord(count, scale, lo, hi, estream.GAUSSIAN, shift, mean, std, None, run_words[0], beta), 0
 
 
-def _encode_empirical(model, entropy_model, args, frames_or_loader, path, run, wide=None):
+def check_temporal_model(name):
+    """The refusal of the temporal kind that depends on the run's flags alone (train_nerv_compression calls it before it trains)."""
+    if name != "HNeRV_Boost":
+        raise ValueError(f"codec: the temporal kind predicts frame embeddings, which --model {name} does not have (HNeRV_Boost does); write the wide kind")
+
+
+def _record_bytes(rec):
+    out = []
+    wstream._pack_record(out, rec, rec.beta is not None)
+    return sum(len(b) for b in out)
+
+
+def _embed_pred(intra, inter):
+    """The choice rule of the temporal kind, one place for the host and the device path: each candidate -- the frame's
+    symbols, the differences to the frame before; both already through _wide_record -- costs 32 * its words + 8 * its serialised record
+    bytes; the cheaper one wins, a tie goes to intra.  inter: None for a frame that has no eligible difference record.  -> 0 | 1."""
+    if inter is None:
+        return tstream.INTRA
+    cost = [32 * int(r.run_words.sum(dtype=np.uint64)) + 8 * _record_bytes(r) for r in (intra, inter)]
+    return tstream.INTER if cost[1] < cost[0] else tstream.INTRA
+
+
+def _inter_side(side, prev_range, lo, hi, s1, s2):
+    """The side values (_wide_record's) of the difference record of a frame, or None where it is not eligible: differences in [-2^20, 2^20], at
+    most 2^24 of them (tstream.eligible), and both frames within +-2^30 so that no int32 difference wrapped.  side: the frame's own;
+    prev_range: (lo, hi) of the frame before; lo, hi, s1, s2: of the differences."""
+    count, scale, _, _, flo, fhi, beta = side
+    if not tstream.eligible(count, lo, hi) or max(abs(int(v)) for v in (flo, fhi) + tuple(prev_range)) > 1 << 30:
+        return None
+    mean, std = tstream.delta_moments(count, s1, s2)
+    return (count, scale, mean, std, int(lo), int(hi) if hi > lo else int(lo) + 1, beta)
+
+
+def _encode_empirical(model, entropy_model, args, frames_or_loader, path, run, wide=None, temporal=False):
     """encode(..., run, tables="empirical"): the symbols stay on the device.  Every quantiser called once for its symbols, the moments of the
     evaluation pass evaluate() accounts with (fused or tensor by tensor), the embeddings frame by frame as encode() makes them, ONE host copy of every record's (mean, std, scale,
     beta) and symbol range, then: histogram launch -> counts to the host -> both tables per record -> ONE encode launch over both -> the
     choice per record -> compaction -> one copy of the words.
 
     wide: None, or the `tables` of the wide kind (wstream.py) -- the same walk with a shift per record, bucket histograms and bucket tables, the
-    wide kernels; under "gaussian" one message per record and no histogram."""
+    wide kernels; under "gaussian" one message per record and no histogram.
+
+    temporal (with wide): the temporal kind (tstream.py) -- ONE more launch (ops.EmbedDelta) for the differences of all frames
+    and their integer moments; the difference record of every eligible frame joins the same histogram, encode and compaction launches as a
+    further message source, and _embed_pred keeps the cheaper of a frame's two records."""
     from . import ops
     from .lib.entropy_model import ans_counts_cdf, ans_gaussian_cdf
     _check_supported(model, entropy_model, args)
@@ -369,22 +421,47 @@ def _encode_empirical(model, entropy_model, args, frames_or_loader, path, run, w
     raw = [sd[k].detach().float().reshape(-1).cpu().numpy() for k in _raw_keys(model, is_hnerv)]
     if wide is not None:
         from .lib.entropy_model import ans_gaussian_bucket_cdf
-        shifts = [wstream.min_shift(r[4], r[5]) for r in sides]
-        per = 2 if wide == "empirical" else 1                 # messages per record
-        items = [(s, r[4], r[5], ans_gaussian_bucket_cdf(r[4], r[5], k, float(r[2]), float(r[3])), k) for s, r, k in zip(symbols, sides, shifts)]
+        coded, slot = list(zip(symbols, sides)), {}           # every message source: (symbols, side); slot: record -> its difference candidate in `coded`
+        if temporal:
+            # ONE launch: the differences of all frames and their (min, max, sum, sum of squares); the candidates join the launches below
+            delta = ops.EmbedDelta(torch.stack(symbols[n_tensors:])).launch().check()
+            dlo, dhi, s1, s2 = delta.host()
+            for t in range(1, n_frames):
+                k = n_tensors + t
+                side = _inter_side(sides[k], sides[k - 1][4:6], int(dlo[t]), int(dhi[t]), int(s1[t]), int(s2[t]))
+                if side is not None:
+                    slot[k] = len(coded)
+                    coded.append((delta.d[t], side))
+        shifts = [wstream.min_shift(r[4], r[5]) for _, r in coded]
+        per = 2 if wide == "empirical" else 1                 # messages per source
+        items = [(s, r[4], r[5], ans_gaussian_bucket_cdf(r[4], r[5], k, float(r[2]), float(r[3])), k) for (s, r), k in zip(coded, shifts)]
         if per == 2:
-            counts = ops.SymHistWide([(s, r[4], r[5], k) for s, r, k in zip(symbols, sides, shifts)]).launch().check().host()
+            counts = ops.SymHistWide([(s, r[4], r[5], k) for (s, r), k in zip(coded, shifts)]).launch().check().host()
             items = [it for g, c in zip(items, counts) for it in (g, (g[0], g[1], g[2], ans_counts_cdf(c), g[4]))]
         enc = ops.AnsEncodeRunsWide(items, run).launch().check()
         run_words = enc.run_words()
-        records, chosen = [], []
-        for k, r in enumerate(sides):
-            rw = run_words[per * k:per * k + per]
-            rec, take = _wide_record(r, shifts[k], items[2 * k + 1][3] if per == 2 else None, [int(w.sum(dtype=np.uint64)) for w in rw], rw)
+
+        def candidate(j):                                     # source j under the choice rule of the wide kind -> (record, its message)
+            rw = run_words[per * j:per * j + per]
+            rec, take = _wide_record(coded[j][1], shifts[j], items[2 * j + 1][3] if per == 2 else None, [int(w.sum(dtype=np.uint64)) for w in rw], rw)
+            return rec, per * j + take
+
+        records, chosen, preds = [], [], []
+        for k in range(n_rec):
+            rec, msg = candidate(k)
+            if k >= n_tensors and temporal:
+                other = candidate(slot[k]) if k in slot else (None, None)
+                preds.append(_embed_pred(rec, other[0]))
+                if preds[-1] == tstream.INTER:
+                    rec, msg = other
             records.append(rec)
-            chosen.append(per * k + take)
+            chosen.append(msg)
         words = enc.compact(chosen, run_words).launch().check().host()
         settings = dict(_settings(args, n_frames, frame_hw), ans_run=run, ans_tables=wide, ans_wide=True)
+        if temporal:
+            blob = tstream.to_bytes(dict(settings, embed_pred=tstream.EMBED_PRED), records[:n_tensors], records[n_tensors:], preds, embed_shape, raw, words)
+            _write_blob(path, blob)
+            return tstream.info(blob)
         blob = wstream.to_bytes(settings, records[:n_tensors], records[n_tensors:], embed_shape, raw, words)
         _write_blob(path, blob)
         return wstream.info(blob)
@@ -432,35 +509,66 @@ def _repack_empirical(src, dst, run):
     return estream.info(blob)
 
 
-def _repack_wide(src, dst, run, tables):
+def _repack_wide(src, dst, run, tables, temporal=False):
     """repack(..., wide=True): the host oracle of encode(..., wide=True) -- the same shifts, tables, coder arithmetic (csrc/ans.cpp) and choice
-    rule, from the symbols of a version-1 or a chunked (BNRC) file."""
+    rule, from the symbols of a version-1 or a chunked (BNRC) file.  temporal: the oracle of encode(..., temporal=True) -- every frame t >= 1
+    also as the record of its differences to the frame before, the cheaper of the two kept (_embed_pred)."""
     from .lib.entropy_model import ans_counts_cdf, ans_decode_gaussian, ans_encode_wide_runs, ans_gaussian_bucket_cdf
     chunked = qstream.magic_of(src) == rstream.MAGIC
     bs = rstream.read(src) if chunked else bitstream.read(src)
     settings = dict(bs.settings, ans_run=run, ans_tables=tables, ans_wide=True)
     words = []
 
-    def chunk(k, r):
-        shift = wstream.min_shift(r.lo, r.hi)
-        sym = rstream.decode_record(bs, k) if chunked else ans_decode_gaussian(r.words, r.count, r.lo, r.hi, float(r.mean), float(r.std))
-        cdfs = [ans_gaussian_bucket_cdf(r.lo, r.hi, shift, float(r.mean), float(r.std))]
-        if tables == "empirical":
-            cdfs.append(ans_counts_cdf(np.bincount((sym - r.lo) >> shift, minlength=wstream.n_buckets(r.lo, r.hi, shift))))
-        coded = [ans_encode_wide_runs(sym, r.lo, r.hi, cdf, shift, run) for cdf in cdfs]
-        rec, take = _wide_record((r.count, r.scale, r.mean, r.std, r.lo, r.hi, r.beta), shift, cdfs[1] if len(cdfs) == 2 else None,
-                                 [w.size for w, _ in coded], [rw for _, rw in coded])
-        words.append(coded[take][0])
-        return rec
+    def symbols_of(k, r):
+        return rstream.decode_record(bs, k) if chunked else ans_decode_gaussian(r.words, r.count, r.lo, r.hi, float(r.mean), float(r.std))
 
-    tensors = [chunk(k, r) for k, r in enumerate(bs.tensors)]
-    embeds = [chunk(len(tensors) + k, r) for k, r in enumerate(bs.embeds)]
-    blob = wstream.to_bytes(settings, tensors, embeds, bs.embed_shape, bs.raw, np.concatenate(words) if words else np.zeros(0, dtype=np.uint32))
+    def code(sym, side):                                      # -> (record, its words)
+        lo, hi = side[4], side[5]
+        shift = wstream.min_shift(lo, hi)
+        cdfs = [ans_gaussian_bucket_cdf(lo, hi, shift, float(side[2]), float(side[3]))]
+        if tables == "empirical":
+            cdfs.append(ans_counts_cdf(np.bincount((sym - lo) >> shift, minlength=wstream.n_buckets(lo, hi, shift))))
+        coded = [ans_encode_wide_runs(sym, lo, hi, cdf, shift, run) for cdf in cdfs]
+        rec, take = _wide_record(side, shift, cdfs[1] if len(cdfs) == 2 else None, [w.size for w, _ in coded], [rw for _, rw in coded])
+        return rec, coded[take][0]
+
+    def side_of(r):
+        return (r.count, r.scale, r.mean, r.std, r.lo, r.hi, r.beta)
+
+    tensors, embeds, preds, before = [], [], [], None
+    for k, r in enumerate(bs.tensors):
+        rec, w = code(symbols_of(k, r), side_of(r))
+        tensors.append(rec)
+        words.append(w)
+    for t, r in enumerate(bs.embeds):
+        sym = symbols_of(len(tensors) + t, r)
+        rec, w = code(sym, side_of(r))
+        if temporal:
+            side = None
+            if t:
+                d = sym.astype(np.int64) - before.astype(np.int64)
+                _, s1, s2 = tstream.delta_sums(d)
+                side = _inter_side(side_of(r), (bs.embeds[t - 1].lo, bs.embeds[t - 1].hi), int(d.min()), int(d.max()), s1, s2)
+            other = code(d.astype(np.int32), side) if side is not None else (None, None)
+            preds.append(_embed_pred(rec, other[0]))
+            if preds[-1] == tstream.INTER:
+                rec, w = other
+            before = sym
+        embeds.append(rec)
+        words.append(w)
+    words = np.concatenate(words) if words else np.zeros(0, dtype=np.uint32)
+    if temporal:
+        if not embeds:
+            raise ValueError(f"codec.repack: a {settings.get('model')} file has no frame embeddings to predict; write the wide kind")
+        blob = tstream.to_bytes(dict(settings, embed_pred=tstream.EMBED_PRED), tensors, embeds, preds, bs.embed_shape, bs.raw, words)
+        _write_blob(dst, blob)
+        return tstream.info(blob)
+    blob = wstream.to_bytes(settings, tensors, embeds, bs.embed_shape, bs.raw, words)
     _write_blob(dst, blob)
     return wstream.info(blob)
 
 
-def repack(src, dst, run=1024, tables="gaussian", wide=False):
+def repack(src, dst, run=1024, tables="gaussian", wide=False, temporal=False):
     """A version-1 CEM file `src` (a file name, a binary file object or bytes) as the chunked kind `dst` (a file name or a binary file
     object): every record rANS-decoded on the host and re-encoded in independent runs of `run` symbols under the same Gaussian.  Header
     settings (plus "ans_run"), record order, side values and the raw section are copied.  Host only: no GPU, no retraining.  Returns
@@ -470,7 +578,9 @@ def repack(src, dst, run=1024, tables="gaussian", wide=False):
     of its own histogram, whichever is smaller; `src` may then be a chunked file as well.  Returns estream.info.
 
     wide=True: the wide kind (wstream.py) under either `tables`, for records of any span; `src` a version-1 or a chunked (BNRC) file.
-    Returns wstream.info."""
+    Returns wstream.info.
+
+    temporal=True (with wide=True): the temporal kind (tstream.py), the host oracle of encode(..., temporal=True).  Returns tstream.info."""
     from .lib.entropy_model import ans_decode_gaussian, ans_encode_gaussian_runs
     if qstream.magic_of(src) in (qstream.MAGIC, zstream.MAGIC):
         raise NotImplementedError("codec.repack: a post-hoc file is not repacked.  A .bnrq twin was quantised with its zeros on the grid, so the pruned "
@@ -479,8 +589,10 @@ def repack(src, dst, run=1024, tables="gaussian", wide=False):
     run = rstream.check_run(run)
     if tables not in TABLES:
         raise ValueError(f"codec.repack: tables = {tables!r} ({' | '.join(TABLES)})")
+    if temporal and not wide:
+        raise ValueError("codec.repack: temporal=True needs wide=True (the temporal kind is the wide file with predicted embedding records)")
     if wide:
-        return _repack_wide(src, dst, run, tables)
+        return _repack_wide(src, dst, run, tables, temporal)
     if tables == "empirical":
         return _repack_empirical(src, dst, run)
     bs = bitstream.read(src)
@@ -527,10 +639,18 @@ def describe_wide(budget):
             f"tables {budget['ans_tables']}")
 
 
+def describe_temporal(budget):
+    """One line of a tstream.info budget (the log of train_nerv_compression --bitstream_temporal, `codec info`)."""
+    return (f"{describe_wide(budget)}; temporal: {budget['n_inter_frames']} frames coded as differences to the frame before, "
+            f"{budget['n_intra_frames']} on their own")
+
+
 def describe_any(budget):
-    """describe, describe_posthoc, describe_sparse, describe_chunked, describe_empirical or describe_wide, by the budget's items."""
+    """describe, describe_posthoc, describe_sparse, describe_chunked, describe_empirical, describe_wide or describe_temporal, by the budget's items."""
     if "zero_parse" in budget:
         return describe_sparse(budget)
+    if "n_inter_frames" in budget:
+        return describe_temporal(budget)
     if "max_shift" in budget:
         return describe_wide(budget)
     if "tables" in budget:
@@ -539,11 +659,11 @@ def describe_any(budget):
 
 
 def info(path_or_buffer):
-    """The bit budget of a file of any kind (bitstream.info, qstream.info, zstream.info, rstream.info, estream.info or wstream.info, by the
-    magic number)."""
+    """The bit budget of a file of any kind (bitstream.info, qstream.info, zstream.info, rstream.info, estream.info, wstream.info or
+    tstream.info, by the magic number)."""
     magic = qstream.magic_of(path_or_buffer)
     return {qstream.MAGIC: qstream.info, zstream.MAGIC: zstream.info, rstream.MAGIC: rstream.info, estream.MAGIC: estream.info,
-            wstream.MAGIC: wstream.info}.get(magic, bitstream.info)(path_or_buffer)
+            wstream.MAGIC: wstream.info, tstream.MAGIC: tstream.info}.get(magic, bitstream.info)(path_or_buffer)
 
 
 def describe(budget):
@@ -709,12 +829,13 @@ class Decoder:
         from .lib.entropy_model import ans_decode_gaussian
         from .train_nerv_all import build_model
         magic = qstream.magic_of(path)
-        self.kind = {qstream.MAGIC: "posthoc", zstream.MAGIC: "sparse", rstream.MAGIC: "chunked", estream.MAGIC: "empirical", wstream.MAGIC: "wide"}.get(magic, "cem")
+        self.kind = {qstream.MAGIC: "posthoc", zstream.MAGIC: "sparse", rstream.MAGIC: "chunked", estream.MAGIC: "empirical", wstream.MAGIC: "wide",
+                     tstream.MAGIC: "temporal"}.get(magic, "cem")
         if self.kind in ("posthoc", "sparse"):
             (self._load_sparse if self.kind == "sparse" else self._load_posthoc)(path, device)
             return self._frame_loop(use_graph, pack, matrix, range)
-        bs = {"chunked": rstream.read, "empirical": estream.read, "wide": wstream.read}.get(self.kind, bitstream.read)(path)
-        what = {"chunked": "rstream", "empirical": "estream", "wide": "wstream"}.get(self.kind, "bitstream")
+        bs = {"chunked": rstream.read, "empirical": estream.read, "wide": wstream.read, "temporal": tstream.read}.get(self.kind, bitstream.read)(path)
+        what = {"chunked": "rstream", "empirical": "estream", "wide": "wstream", "temporal": "tstream"}.get(self.kind, "bitstream")
         s = dict(bs.settings)
         if s.get("model") not in MODELS:
             raise ValueError(f"{what}: header names the model {s.get('model')!r}; this build decodes {', '.join(MODELS)}")
@@ -723,7 +844,7 @@ class Decoder:
         self.n_frames = int(s["full_data_length"])
         self.frame_hw = tuple(int(v) for v in s["crop_list"].split("_")[:2])
         self.is_hnerv = s["model"] == "HNeRV_Boost"
-        margs = SimpleNamespace(**{k: v for k, v in s.items() if k not in ("ans_run", "ans_tables", "ans_wide")})
+        margs = SimpleNamespace(**{k: v for k, v in s.items() if k not in ("ans_run", "ans_tables", "ans_wide", "embed_pred")})
         margs.__dict__.update(quant=False, outf="")
         model = build_model(margs)
         if self.is_hnerv:
@@ -748,7 +869,24 @@ class Decoder:
                 raise ValueError(f"{what}: embedding records in a {s['model']} stream")
             self.embeds = None
         records = list(bs.tensors) + list(bs.embeds)
-        if self.kind in ("chunked", "empirical", "wide"):
+        chain = None
+        if self.kind == "temporal":
+            # the tensor records through the wide kernel as they are; the embedding records entropy-decoded to the integers they hold, then ONE
+            # launch that resolves the chains of predicted frames and de-quantises into self.embeds.  Both error words are read below
+            if not self.is_hnerv:
+                raise ValueError(f"{what}: embedding records in a {s['model']} stream")
+            if any(not t.is_contiguous() for t in targets):
+                raise ValueError(f"{what}: the model the header describes has a quantised tensor that is not dense")
+            n_t = len(bs.tensors)
+            at = sum(n for _, n in wstream.record_words(bs)[:n_t])
+            job = ops.AnsDequantWide(bs.words[:at], [(t.reshape(-1), float(r.scale), r.lo, r.hi, wstream.record_cdf(r), r.shift, r.run_words, None)
+                                                     for t, r in zip(targets, bs.tensors)], int(s["ans_run"])).launch()
+            held = torch.empty(self.n_frames, int(np.prod(bs.embed_shape)), dtype=torch.int32, device=self.device)
+            syms = ops.AnsDecodeWide(bs.words[at:], [(held[i], r.lo, r.hi, wstream.record_cdf(r), r.shift, r.run_words) for i, r in enumerate(bs.embeds)],
+                                     int(s["ans_run"])).launch()
+            chain = ops.EmbedChainDequant(held, bs.preds, [float(r.scale) for r in bs.embeds], [float(r.beta) for r in bs.embeds],
+                                          self.embeds.view(self.n_frames, -1)).launch()
+        elif self.kind in ("chunked", "empirical", "wide"):
             # the words as they lie in the file, every record's table and the run descriptors: one upload each, ONE launch that
             # entropy-decodes and de-quantises; its error word is read at the synchronisation below
             if any(not t.is_contiguous() for t in targets):
@@ -786,6 +924,9 @@ class Decoder:
         torch.cuda.current_stream().synchronize()          # (the pinned symbols may go now)
         if job is not None:
             job.check()
+        if chain is not None:
+            syms.check()
+            chain.check()
         sd = model.state_dict()
         rest = [sd[k] for k in _raw_keys(model, self.is_hnerv)]
         if len(rest) != len(bs.raw) or any(v.numel() != a.size for v, a in zip(rest, bs.raw)):
@@ -1096,6 +1237,8 @@ def build_parser():
                                                                         "histogram, whichever is smaller (SRC may then be a chunked file too)")
     r.add_argument("--wide", action="store_true", help="write the wide kind (BNRW): a record may span more than 4096 symbol values -- a bucket under the "
                                                        "table plus raw low bits (SRC: a version-1 or a BNRC file)")
+    r.add_argument("--temporal", action="store_true", help="(implies --wide) write the temporal kind (BNRT) -- the embedding record of a frame holds the "
+                                                           "differences to the frame before where that costs fewer bits (HNeRV_Boost files)")
     return p
 
 
@@ -1107,7 +1250,7 @@ def main(argv=None):
         print(json.dumps(budget))
         return budget
     if a.cmd == "repack":
-        budget = repack(a.src, a.dst, a.run, a.tables, wide=a.wide)
+        budget = repack(a.src, a.dst, a.run, a.tables, wide=a.wide or a.temporal, temporal=a.temporal)
         print(describe_any(budget))
         print(json.dumps(budget))
         return budget

@@ -13,6 +13,7 @@
 //                   rule.  Decoded offsets are staged as full dwords, CH = 32 per lane and round with a lane stride of 33 dwords (rans.hip
 //                   stages 64 sixteen-bit symbols in the same 33 dwords), so static LDS stays 58 KB per block and two decode waves fit a CU.
 //                   An offset above hi - lo sets bit 0 of the error word and is clamped; it is a value, never an address.
+// rans_decode_wide  the same kernel with an int32 store, out[i] = lo + offset: the symbols of an inter-coded record (csrc/ranst.hip resolves them).
 // Every index that comes from a descriptor is checked against the array it points into before it is used.
 #include "common.h"
 
@@ -149,6 +150,9 @@ __device__ __forceinline__ float dequant1(int q, float s, float b, bool has_beta
     return has_beta ? v + b : v;
 }
 
+// INT_OUT: the store is out[i] = lo + offset as int32 (bnerv_rans_decode_wide: symbols that a later kernel resolves, csrc/ranst.hip) in place of
+// the de-quantised float; everything before the store is the one body
+template <bool INT_OUT>
 __global__ __launch_bounds__(WAVE) void rans_dequant_wide_kernel(const unsigned* __restrict__ words, const unsigned n_words, const unsigned* __restrict__ run_start,
                                                                  const unsigned n_runs, const bnerv_rans_block* __restrict__ blocks,
                                                                  const bnerv_ransw_item* __restrict__ items, const unsigned n_items,
@@ -255,7 +259,8 @@ __global__ __launch_bounds__(WAVE) void rans_dequant_wide_kernel(const unsigned*
             const unsigned f = (b.first + rr) * run, c = it.n - f < run ? it.n - f : run;
             if (e < c) {
                 const unsigned off = stage[rr * DEC_STRIDE + (lane & (DEC_CH - 1u))];
-                it.out[(size_t)f + e] = dequant1((int)((unsigned)it.lo + off), it.scale, it.beta, has_beta);
+                if constexpr (INT_OUT) reinterpret_cast<int*>(it.out)[(size_t)f + e] = (int)((unsigned)it.lo + off);
+                else it.out[(size_t)f + e] = dequant1((int)((unsigned)it.lo + off), it.scale, it.beta, has_beta);
             }
         }
         __syncthreads();
@@ -298,20 +303,33 @@ extern "C" int bnerv_rans_encode_wide(void* stream, const bnerv_rans_block* bloc
     return BNERV_OK;
 }
 
+template <bool INT_OUT>
+static int launch_decode_wide(const char* who, void* stream, const uint32_t* words, size_t n_words, const uint32_t* run_start, size_t n_runs,
+                              const bnerv_rans_block* blocks, size_t n_blocks, const bnerv_ransw_item* items, int n_items,
+                              const uint32_t* tables, size_t n_table_words, int run, int* err) {
+    BNERV_REQUIRE(words && run_start && blocks && items && tables && err, "%s: null args", who);
+    BNERV_REQUIRE(run >= BNERV_RANS_MIN_RUN && run <= BNERV_RANS_MAX_RUN && run % WAVE == 0, "%s: run = %d (a multiple of %d in %d..%d)", who, run, WAVE,
+                  BNERV_RANS_MIN_RUN, BNERV_RANS_MAX_RUN);
+    BNERV_REQUIRE(n_words >= 2 && n_words <= 0xffffffffu && n_runs > 0 && n_runs < 0x7fffffffu && n_blocks > 0 && n_blocks <= 0x7fffffffu && n_items > 0
+                  && n_table_words >= 3 && n_table_words <= 0xffffffffu, "%s: n_words=%zu (two of them padding) n_runs=%zu n_blocks=%zu n_items=%d n_table_words=%zu",
+                  who, n_words, n_runs, n_blocks, n_items, n_table_words);
+    BNERV_REQUIRE(aligned(words, 4) && aligned(run_start, 4) && aligned(tables, 4) && aligned(err, 4), "%s: words / run_start / tables / err are not 4-byte aligned", who);
+    BNERV_REQUIRE(aligned(blocks, 16) && aligned(items, 8), "%s: the descriptor tables are not aligned (blocks 16, items 8 bytes)", who);
+    hipLaunchKernelGGL(rans_dequant_wide_kernel<INT_OUT>, dim3((unsigned)n_blocks), dim3(WAVE), 0, reinterpret_cast<hipStream_t>(stream),
+                       reinterpret_cast<const unsigned*>(words), (unsigned)n_words, reinterpret_cast<const unsigned*>(run_start), (unsigned)n_runs, blocks, items,
+                       (unsigned)n_items, reinterpret_cast<const unsigned*>(tables), (unsigned)n_table_words, (unsigned)run, err);
+    BNERV_LAUNCH_CHECK(who);
+    return BNERV_OK;
+}
+
 extern "C" int bnerv_rans_dequant_wide(void* stream, const uint32_t* words, size_t n_words, const uint32_t* run_start, size_t n_runs,
                                        const bnerv_rans_block* blocks, size_t n_blocks, const bnerv_ransw_item* items, int n_items,
                                        const uint32_t* tables, size_t n_table_words, int run, int* err) {
-    BNERV_REQUIRE(words && run_start && blocks && items && tables && err, "rans_dequant_wide: null args");
-    BNERV_REQUIRE(run >= BNERV_RANS_MIN_RUN && run <= BNERV_RANS_MAX_RUN && run % WAVE == 0, "rans_dequant_wide: run = %d (a multiple of %d in %d..%d)", run, WAVE,
-                  BNERV_RANS_MIN_RUN, BNERV_RANS_MAX_RUN);
-    BNERV_REQUIRE(n_words >= 2 && n_words <= 0xffffffffu && n_runs > 0 && n_runs < 0x7fffffffu && n_blocks > 0 && n_blocks <= 0x7fffffffu && n_items > 0
-                  && n_table_words >= 3 && n_table_words <= 0xffffffffu, "rans_dequant_wide: n_words=%zu (two of them padding) n_runs=%zu n_blocks=%zu n_items=%d n_table_words=%zu",
-                  n_words, n_runs, n_blocks, n_items, n_table_words);
-    BNERV_REQUIRE(aligned(words, 4) && aligned(run_start, 4) && aligned(tables, 4) && aligned(err, 4), "rans_dequant_wide: words / run_start / tables / err are not 4-byte aligned");
-    BNERV_REQUIRE(aligned(blocks, 16) && aligned(items, 8), "rans_dequant_wide: the descriptor tables are not aligned (blocks 16, items 8 bytes)");
-    hipLaunchKernelGGL(rans_dequant_wide_kernel, dim3((unsigned)n_blocks), dim3(WAVE), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const unsigned*>(words),
-                       (unsigned)n_words, reinterpret_cast<const unsigned*>(run_start), (unsigned)n_runs, blocks, items, (unsigned)n_items,
-                       reinterpret_cast<const unsigned*>(tables), (unsigned)n_table_words, (unsigned)run, err);
-    BNERV_LAUNCH_CHECK("rans_dequant_wide");
-    return BNERV_OK;
+    return launch_decode_wide<false>("rans_dequant_wide", stream, words, n_words, run_start, n_runs, blocks, n_blocks, items, n_items, tables, n_table_words, run, err);
+}
+
+extern "C" int bnerv_rans_decode_wide(void* stream, const uint32_t* words, size_t n_words, const uint32_t* run_start, size_t n_runs,
+                                      const bnerv_rans_block* blocks, size_t n_blocks, const bnerv_ransw_item* items, int n_items,
+                                      const uint32_t* tables, size_t n_table_words, int run, int* err) {
+    return launch_decode_wide<true>("rans_decode_wide", stream, words, n_words, run_start, n_runs, blocks, n_blocks, items, n_items, tables, n_table_words, run, err);
 }

@@ -1527,6 +1527,7 @@ class AnsDequantWide(AnsDequant):
         items      one (out, scale, lo, hi, cdf, shift, run_words, beta) per record: [lo, hi] the symbol range, cdf the cumulative table of its
                    B = ceil((hi - lo + 1) / 2^shift) buckets (uint32 numpy, B + 1 entries rising strictly from 0 to 2^24, 2 <= B <= 4096),
                    shift in 0..16; the rest as in AnsDequant"""
+    _out_dtype, _out_name = torch.float32, "fp32"
 
     def __init__(self, words, items, run):
         import numpy as np
@@ -1545,8 +1546,8 @@ class AnsDequantWide(AnsDequant):
         for k, (out, scale, lo, hi, cdf, shift, run_words, beta) in enumerate(items):
             L.require_device(out, "out")
             n = out.numel()
-            if out.dtype != torch.float32 or not out.is_contiguous() or n == 0 or n >= 2 ** 31 or out.data_ptr() % 4 or out.device != device:
-                raise ValueError(f"ans_dequant_wide: item {k}: out must be a non-empty contiguous 4-byte aligned fp32 tensor on {device} (below 2^31 elements)")
+            if out.dtype != self._out_dtype or not out.is_contiguous() or n == 0 or n >= 2 ** 31 or out.data_ptr() % 4 or out.device != device:
+                raise ValueError(f"ans_dequant_wide: item {k}: out must be a non-empty contiguous 4-byte aligned {self._out_name} tensor on {device} (below 2^31 elements)")
             lo, hi, shift, B, cdf = _wide_shape("ans_dequant_wide", k, lo, hi, shift, cdf)
             rw = np.ascontiguousarray(run_words, dtype=np.uint16).reshape(-1)
             n_runs = (n + run - 1) // run
@@ -1595,6 +1596,115 @@ def ans_dequant_wide(words, items, run):
     """ans_dequant_tables for records of any width.  Arguments: AnsDequantWide."""
     AnsDequantWide(words, items, run).launch().check()
     return [it[0] for it in items]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# inter-coded frame embeddings (tstream.py, codec.encode(..., temporal=True); csrc/ranst.hip; DESIGN section 34)
+# ----------------------------------------------------------------------------------------------------------------------
+class AnsDecodeWide(AnsDequantWide):
+    """AnsDequantWide with an int32 result (bnerv_rans_decode_wide, the same kernel body): out[i] = lo + offset, the symbols a record holds.
+
+        items      one (out, lo, hi, cdf, shift, run_words) per record: out a contiguous int32 device tensor; the rest as in AnsDequantWide"""
+    _out_dtype, _out_name = torch.int32, "int32"
+
+    def __init__(self, words, items, run):
+        super().__init__(words, [(out, 1.0, lo, hi, cdf, shift, rw, None) for out, lo, hi, cdf, shift, rw in items], run)
+
+    def launch(self):
+        L.check(L.load().bnerv_rans_decode_wide(L.stream(), L.ptr(self.words), self.n_words, L.ptr(self.starts), self.n_runs, L.ptr(self.blocks), self.n_blocks,
+                                                L.ptr(self.items), self.n_items, L.ptr(self.tables), self.n_table_words, self.run, L.ptr(self.err)),
+                "bnerv_rans_decode_wide")
+        return self
+
+
+def _rows(t, name, dtype, what):
+    """(N, P, pitch) of a 2-D device tensor whose rows are dense (stride 1 along p, any row pitch >= P), any 4-byte alignment."""
+    L.require_device(t, name)
+    if t.dim() != 2 or t.dtype != dtype or t.numel() == 0 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]) or t.data_ptr() % 4:
+        raise ValueError(f"{what}: {name} must be a non-empty [N, P] {dtype} device tensor with dense rows (row pitch >= P), got {t.dtype} {tuple(t.shape)} "
+                         f"strides {tuple(t.stride())}")
+    return int(t.shape[0]), int(t.shape[1]), int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+
+class EmbedDelta:
+    """The frame-to-frame differences of the embedding symbols and their statistics, ONE launch (bnerv_embed_delta).
+
+        q          int32 [N, P] device tensor, dense rows at any row pitch and any 4-byte alignment
+        d          None, or the int32 [N, P] tensor to write (same rules); row 0 is not written
+    launch() zeroes the statistics and fills d[t] = q[t] - q[t - 1] for t >= 1; check() is there for the shape of the other ops (the kernel
+    takes no index from a descriptor: nothing can be flagged); host() -> (lo, hi, s1, s2), numpy arrays of N entries (entry 0 is zero):
+    min d and max d as int64, s1 = sum d as int64, s2 = sum d^2 mod 2^64 as uint64 -- one copy."""
+
+    def __init__(self, q, d=None):
+        self.N, self.P, self.q_pitch = _rows(q, "q", torch.int32, "embed_delta")
+        if d is None:
+            d = torch.empty(self.N, self.P, dtype=torch.int32, device=q.device)
+        N, P, self.d_pitch = _rows(d, "d", torch.int32, "embed_delta")
+        if (N, P) != (self.N, self.P) or d.device != q.device:
+            raise ValueError(f"embed_delta: d is {tuple(d.shape)} on {d.device}, q {tuple(q.shape)} on {q.device}")
+        if self.N > 1 << 20 or max(self.q_pitch, self.d_pitch) >= 2 ** 31:
+            raise ValueError(f"embed_delta: {self.N} frames at pitches {self.q_pitch}, {self.d_pitch} (at most 2^20 frames, pitches below 2^31)")
+        self.q, self.d = q, d
+        self.stats = torch.zeros(self.N, C.sizeof(L.DeltaStats) // 8, dtype=torch.int64, device=q.device)
+
+    def launch(self):
+        L.check(L.load().bnerv_embed_delta(L.stream(), L.ptr(self.q), self.q_pitch, self.N, self.P, L.ptr(self.d), self.d_pitch, L.ptr(self.stats)),
+                "bnerv_embed_delta")
+        return self
+
+    def check(self):
+        return self
+
+    def host(self):
+        import numpy as np
+        raw = self.stats.cpu().numpy()
+        keys = raw[:, 0].copy().view(np.uint32).reshape(-1, 2)             # (max_key, min_key_inv)
+        hi = (keys[:, 0] ^ np.uint32(0x80000000)).view(np.int32).astype(np.int64)
+        lo = (~keys[:, 1] ^ np.uint32(0x80000000)).view(np.int32).astype(np.int64)
+        lo[0] = hi[0] = 0
+        return lo, hi, raw[:, 1].copy(), raw[:, 2].copy().view(np.uint64)
+
+
+class EmbedChainDequant:
+    """The symbols of the embedding records of a temporal file resolved and de-quantised, ONE launch (bnerv_embed_chain_dequant):
+    q_t = pred[t] ? q_{t-1} + sym_t : sym_t,  out[t] = float(q_t) * scale[t] + beta[t]  (product and sum one fp32 operation each).
+
+        sym        int32 [N, P] device tensor, dense rows at any row pitch and any 4-byte alignment
+        pred       N values 0 | 1; pred[0] must be 0 (refused here, before any launch)
+        scale, beta  N floats each
+        out        fp32 [N, P] device tensor (same rules as sym)
+    check() reads the device error word (a host sync) and raises ValueError when a chain left int32."""
+
+    def __init__(self, sym, pred, scale, beta, out):
+        import numpy as np
+        self.N, self.P, self.sym_pitch = _rows(sym, "sym", torch.int32, "embed_chain_dequant")
+        N, P, self.out_pitch = _rows(out, "out", torch.float32, "embed_chain_dequant")
+        if (N, P) != (self.N, self.P) or out.device != sym.device:
+            raise ValueError(f"embed_chain_dequant: out is {tuple(out.shape)} on {out.device}, sym {tuple(sym.shape)} on {sym.device}")
+        pred = np.ascontiguousarray(pred).reshape(-1)
+        if pred.size != self.N or ((pred != 0) & (pred != 1)).any():
+            raise ValueError(f"embed_chain_dequant: pred must be {self.N} values 0 | 1")
+        if pred[0] != 0:
+            raise ValueError("embed_chain_dequant: frame 0 is predicted (pred[0] = 1): there is no frame before it")
+        coef = np.stack([np.asarray(scale, dtype=np.float32).reshape(-1), np.asarray(beta, dtype=np.float32).reshape(-1)])
+        if coef.shape != (2, self.N):
+            raise ValueError(f"embed_chain_dequant: scale and beta must have {self.N} entries each")
+        if self.N > 65535 * L.CHAIN_SEG or max(self.sym_pitch, self.out_pitch) >= 2 ** 31:
+            raise ValueError(f"embed_chain_dequant: {self.N} frames at pitches {self.sym_pitch}, {self.out_pitch}")
+        self.sym, self.out = sym, out
+        self.pred = _upload(pred.astype(np.uint8), sym.device)
+        self.coef = _upload(coef, sym.device).view(torch.float32).reshape(2, self.N)
+        self.err = torch.zeros(1, dtype=torch.int32, device=sym.device)
+
+    def launch(self):
+        L.check(L.load().bnerv_embed_chain_dequant(L.stream(), L.ptr(self.sym), self.sym_pitch, L.ptr(self.pred), L.ptr(self.coef[0]), L.ptr(self.coef[1]),
+                                                   self.N, self.P, L.ptr(self.out), self.out_pitch, L.ptr(self.err)), "bnerv_embed_chain_dequant")
+        return self
+
+    def check(self):
+        if int(self.err.item()) != 0:
+            raise ValueError("embed_chain_dequant: a chain of predicted frames leaves int32 (the file's differences do not belong to its symbols)")
+        return self
 
 
 def frame_to_u8(x, out=None):

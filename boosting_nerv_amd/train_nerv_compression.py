@@ -54,6 +54,9 @@ def build_parser():
     add('--bitstream_wide', action='store_true',
         help='(needs --bitstream_run N > 0) write the wide kind: a record whose symbols span more than 4096 values is coded as a bucket under its table '
              'plus raw low bits; coded on the GPU under either --bitstream_tables')
+    add('--bitstream_temporal', action='store_true',
+        help='(needs --bitstream_run N > 0; --model HNeRV_Boost; implies the wide record) write the temporal kind: the embedding record of a frame holds '
+             'the integer differences to the frame before where that costs fewer bits; coded on the GPU under either --bitstream_tables')
     return p
 
 
@@ -71,8 +74,13 @@ def main(argv=None):
     args = parse_args(argv, parser)
     if args.bitstream_wide and not args.bitstream_run:
         parser.error('--bitstream_wide needs --bitstream_run N > 0 (only a chunked kind is decoded by the wide kernel)')
+    if args.bitstream_temporal and not args.bitstream_run:
+        parser.error('--bitstream_temporal needs --bitstream_run N > 0 (the temporal kind is a chunked kind)')
     if args.bitstream_tables == 'empirical' and not args.bitstream_run:
         parser.error('--bitstream_tables empirical needs --bitstream_run N > 0 (only the chunked kind carries tables)')
+    if args.bitstream_temporal:
+        from . import codec
+        codec.check_temporal_model(args.model)                # (a run that cannot write its --bitstream stops before it trains)
     torch.set_printoptions(precision=2)
     if args.debug:
         args.eval_freq, args.outf = 1, 'output/debug'
@@ -340,7 +348,8 @@ def evaluate(model, full_dataloader, local_rank, args, dump_vis=False, coding=Fa
             from . import codec
             args.bitstream_budget = codec.encode(model, entropy_model, args, full_dataloader, args.bitstream, run=getattr(args, 'bitstream_run', 0),
                                                  tables=getattr(args, 'bitstream_tables', 'gaussian'),
-                                                 **({'wide': True} if getattr(args, 'bitstream_wide', False) else {}))
+                                                 **({'wide': True, 'temporal': True} if getattr(args, 'bitstream_temporal', False) else
+                                                    {'wide': True} if getattr(args, 'bitstream_wide', False) else {}))
             log.line(f'Bitstream {args.bitstream}: {codec.describe_any(args.bitstream_budget)} \n', every_rank=False)
     return values, hw
 

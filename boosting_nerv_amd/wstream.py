@@ -105,8 +105,9 @@ def _check_settings(who, settings):
     return run
 
 
-def _payload(settings, tensors, embeds, embed_shape, raw, words):
-    run = _check_settings("wstream.write", settings)
+def _payload(settings, tensors, embeds, embed_shape, raw, words, check_settings=_check_settings, lead=None):
+    """lead: None, or one bytes object per embedding record, written in front of it (tstream.py: the pred byte)."""
+    run = check_settings("wstream.write", settings)
     header = json.dumps(settings, sort_keys=True, separators=(",", ":")).encode("utf-8")
     out = [_U32.pack(len(header)), header, _U32.pack(len(tensors))]
     for r in list(tensors) + list(embeds):
@@ -117,7 +118,9 @@ def _payload(settings, tensors, embeds, embed_shape, raw, words):
     if embeds and embed_shape is None:
         raise ValueError("wstream.write: embedding records need embed_shape (C, h, w)")
     out.append(struct.pack("<IIII", len(embeds), *(embed_shape if embeds else (0, 0, 0))))
-    for r in embeds:
+    for k, r in enumerate(embeds):
+        if lead is not None:
+            out.append(lead[k])
         _pack_record(out, r, True)
     out.append(_U32.pack(len(raw)))
     for a in raw:
@@ -168,13 +171,23 @@ def _read_record(cur, run, with_beta, side):
     return WRecord(count, np.float32(scale), lo, hi, model, shift, mean, std, freq, run_words, beta)
 
 
-def _parse(path_or_buffer):
-    blob = _blob(path_or_buffer)
+def _parse(path_or_buffer, magic_want=MAGIC, who="wstream", check_settings=_check_settings, lead=None):
+    """-> (WStream, bits, file size, leads).  The hooks are tstream.py's, whose file is this one with another magic, a settings check of its own and
+    a byte in front of every embedding record: lead(cur, k) reads what precedes embedding record k; leads: what it returned."""
+    try:
+        return _parse_file(_blob(path_or_buffer), magic_want, check_settings, lead)
+    except ValueError as e:
+        if who == "wstream":
+            raise
+        raise ValueError(str(e).replace("wstream:", who + ":", 1)) from None
+
+
+def _parse_file(blob, magic_want, check_settings, lead):
     if len(blob) < _PREFIX.size:
         raise ValueError(f"wstream: truncated ({len(blob)} bytes: shorter than the file prefix)")
     magic, version, length = _PREFIX.unpack_from(blob)
-    if magic != MAGIC:
-        raise ValueError(f"wstream: bad magic number {magic!r} (want {MAGIC!r})")
+    if magic != magic_want:
+        raise ValueError(f"wstream: bad magic number {magic!r} (want {magic_want!r})")
     if version != VERSION:
         raise ValueError(f"wstream: unknown format version {version} (this build reads version {VERSION})")
     if len(blob) != _PREFIX.size + length + 4:
@@ -184,22 +197,26 @@ def _parse(path_or_buffer):
         raise ValueError("wstream: CRC mismatch (the payload is damaged)")
     cur = _Cursor(payload)
     try:
-        return _parse_payload(cur, payload, len(blob))
+        return _parse_payload(cur, payload, len(blob), check_settings, lead)
     except ValueError as e:                                # (the cursor is estream's and says so)
         raise ValueError(str(e).replace("estream:", "wstream:", 1)) from None
 
 
-def _parse_payload(cur, payload, nbytes):
+def _parse_payload(cur, payload, nbytes, check_settings, lead):
     n_header, = cur.unpack(_U32, "header")
     try:
         settings = json.loads(cur.take(n_header, "header").decode("utf-8"))
     except (UnicodeDecodeError, json.JSONDecodeError) as e:
         raise ValueError(f"wstream: the settings header is not JSON ({e})") from None
-    run = _check_settings("wstream", settings)
+    run = check_settings("wstream", settings)
     n_tensors, = cur.unpack(_U32, "header")
     tensors = [_read_record(cur, run, False, "tensor_side") for _ in range(n_tensors)]
     n_embeds, C_, h_, w_ = cur.unpack(struct.Struct("<IIII"), "header")
-    embeds = [_read_record(cur, run, True, "embed_side") for _ in range(n_embeds)]
+    embeds, leads = [], []
+    for k in range(n_embeds):
+        if lead is not None:
+            leads.append(lead(cur, k))
+        embeds.append(_read_record(cur, run, True, "embed_side"))
     n_raw, = cur.unpack(_U32, "header")
     raw = []
     for _ in range(n_raw):
@@ -217,7 +234,7 @@ def _parse_payload(cur, payload, nbytes):
     cur.bits["ans_words"] -= 32 * PAD_WORDS
     cur.bits["padding"] = 32 * PAD_WORDS
     cur.bits["header"] += 8 * (_PREFIX.size + 4)           # magic, version, length and the CRC
-    return WStream(settings, tensors, embeds, (C_, h_, w_) if n_embeds else None, raw, words[:total]), cur.bits, nbytes
+    return WStream(settings, tensors, embeds, (C_, h_, w_) if n_embeds else None, raw, words[:total]), cur.bits, nbytes, leads
 
 
 def read(path_or_buffer):
@@ -229,7 +246,10 @@ def info(path_or_buffer):
     """The bit budget of a file, in bits, under estream.info's eight items (the shift byte of a record counts as its side) -- plus "total" =
     their sum = 8 * file size, "ans_run", "ans_tables" and estream.info's counts, "n_wide_records" (records with a shift above 0) and
     "max_shift"."""
-    ws, bits, nbytes = _parse(path_or_buffer)
+    return _budget(*_parse(path_or_buffer)[:3])
+
+
+def _budget(ws, bits, nbytes):
     out = {k: int(bits[k]) for k in ITEMS}
     total = sum(out.values())
     assert total == 8 * nbytes, (total, nbytes)            # every byte was booked exactly once

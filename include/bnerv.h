@@ -568,6 +568,34 @@ int bnerv_rans_dequant_wide(void* stream, const uint32_t* words, size_t n_words,
                             const uint32_t* tables, size_t n_table_words, int run, int* err);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Temporal CEM file: inter-coded frame embeddings (additive to ABI 9; csrc/ranst.hip and csrc/ransw.hip;
+ * boosting_nerv_amd/tstream.py).  All three are device entry points of ONE launch each.
+ *
+ *   bnerv_embed_delta    q: n_frames rows of P int32 symbols, q_pitch elements apart.  d[t][p] = q[t][p] - q[t-1][p] for t >= 1 (row 0 of d is
+ *                        not written), rows d_pitch apart, and stats[t] over row t of d (stats[0] stays zero).  The entry point zeroes
+ *                        `stats` on the stream; min and max are kept as order-preserving keys for which zero is neutral:
+ *                            max d = (int)(max_key ^ 0x80000000),   min d = (int)(~min_key_inv ^ 0x80000000);
+ *                        s1 = sum d (exact: |s1| < 2^63), s2 = sum d^2 mod 2^64 (exact while P * max d^2 < 2^64).  Integer atomics only: the
+ *                        result does not depend on the order of arrival.  Any 4-byte alignment of q and d, any pitch >= P.
+ *   bnerv_rans_decode_wide   bnerv_rans_dequant_wide with an int32 store:  ((int*)items[k].out)[i] = lo + offset;  scale, beta and has_beta
+ *                        of the item are not read.  The same kernel body, the same error bits.
+ *   bnerv_embed_chain_dequant   sym: n_frames rows of P int32, sym_pitch apart.  q_0 = sym_0;  q_t = pred[t] ? q_{t-1} + sym_t : sym_t  (pred[0] is
+ *                        not read as a prediction: callers refuse a file that sets it);  out[t][p] = float(q_t) * scale[t] + beta[t], product
+ *                        and sum one fp32 operation each, rows out_pitch apart.  pred / scale / beta: n_frames device entries.  The chain is
+ *                        summed in 64 bits: a q_t outside int32 sets bit 0 of *err (device int) and is clamped.  A thread walks t with
+ *                        BNERV_CHAIN_UNROLL loads in flight; a block serves BNERV_CHAIN_SEG frames, starting from the nearest frame at or
+ *                        before them that is not predicted. */
+#define BNERV_CHAIN_UNROLL 8
+#define BNERV_CHAIN_SEG 64
+typedef struct { unsigned max_key; unsigned min_key_inv; long long s1; unsigned long long s2; } bnerv_delta_stats;
+int bnerv_embed_delta(void* stream, const int32_t* q, size_t q_pitch, int n_frames, size_t P, int32_t* d, size_t d_pitch, bnerv_delta_stats* stats);
+int bnerv_rans_decode_wide(void* stream, const uint32_t* words, size_t n_words, const uint32_t* run_start, size_t n_runs,
+                           const bnerv_rans_block* blocks, size_t n_blocks, const bnerv_ransw_item* items, int n_items,
+                           const uint32_t* tables, size_t n_table_words, int run, int* err);
+int bnerv_embed_chain_dequant(void* stream, const int32_t* sym, size_t sym_pitch, const unsigned char* pred, const float* scale, const float* beta,
+                              int n_frames, size_t P, float* out, size_t out_pitch, int* err);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Huffman coder of the post-hoc quantised model (additive to ABI 9; csrc/huff.cpp on the host, csrc/huff.hip on the device;
  * boosting_nerv_amd/qstream.py).
  *

@@ -27,11 +27,17 @@ model's BNRE file under ops.AnsDequantTables and, the same records with shift 0,
 its first (stem) weight quantiser cut so that the record spans about 25 000 values -- which only the wide kind holds -- under
 ops.AnsDequantWide; the size of that record against its version-1 message.  Times are per launch and per symbol of a run (a lane decodes
 its run's symbols one after the other).
+--bitstream --temporal compares the temporal kind (tstream.py) with the wide kind of the same run on the seeded c5 model and
+--frames consecutive frames of the 1080p synthetic clip (the files of tools/kencode.py --temporal, coded on the device): codec.Decoder ready
+times of both kinds alternated in one process; the three launches of the temporal decoder (ops.AnsDequantWide over the tensor records,
+ops.AnsDecodeWide over the embedding records, ops.EmbedChainDequant) and the one launch of the wide decoder, each replayed from a graph; the
+temporal file decodes to the parameters, the embeddings and the first and last frame of the version-1 file.
+
 --bitstream --posthoc --sparse times the sparse post-hoc file (zstream.py) against the dense file of the SAME pruned model in
 ONE process: the seeded C1 model pruned by global magnitude to --sparsity (default 0.4), quantised once with quant_tensor (the .bnrq file)
 and once with quant_tensor_sparse (the .bnrz file); model-ready of both files alternated, eager and graph; then the two decode launches
 alone under HIP events (ops.HuffDequant.launch / ops.HuffzDequant.launch, 20 launches replayed from a graph each, alternated over the rounds).
-usage: python tools/kdecode.py --bitstream [--posthoc [--sparse [--sparsity S]]|--chunked|--wide] [--frames 16] [--rounds 3] [--only c1q|c5|pack]   (needs the GPU)"""
+usage: python tools/kdecode.py --bitstream [--posthoc [--sparse [--sparsity S]]|--chunked|--wide|--temporal] [--frames 16] [--rounds 3] [--only c1q|c5|pack]   (needs the GPU)"""
 import argparse
 import io
 import os
@@ -435,6 +441,70 @@ def run_wide(n_frames, rounds):
         del model
 
 
+def run_temporal(n_frames, rounds):
+    import numpy as np
+    import torch
+    from kencode import consecutive_frames
+    from boosting_nerv_amd import codec, ops, tstream, wstream
+    from boosting_nerv_amd.lib.entropy_model import DiffEntropyModel
+    dev = torch.device("cuda:0")
+    args, model = build("c5")
+    model = model.to(dev)
+    model.init_data()
+    h, w = (int(v) for v in args.crop_list.split("_")[:2])
+    frames = consecutive_frames(n_frames, h, w, dev)
+    with torch.no_grad():
+        model.embed_quantizer.init_data(model.forward_encoder(frames[0:1]))
+    args.full_data_length = n_frames
+    em = DiffEntropyModel("gaussian")
+    buf = io.BytesIO()
+    codec.encode(model, em, args, frames, buf)
+    v1 = buf.getvalue()
+    label = f"c5 seeded, frames 100..{100 + n_frames - 1}"
+    for run in (256, 1024):
+        fw, ft = io.BytesIO(), io.BytesIO()
+        bw = codec.encode(model, em, args, frames, fw, run=run, tables="empirical", wide=True)
+        bt = codec.encode(model, em, args, frames, ft, run=run, tables="empirical", wide=True, temporal=True)
+        fw, ft = fw.getvalue(), ft.getvalue()
+        print(f"{label}, run {run}: BNRV {len(v1)} bytes, BNRW {bw['bytes']} bytes, BNRT {bt['bytes']} bytes, {bt['n_inter_frames']} of {bt['n_embeds']} frames as differences",
+              flush=True)
+        ready = {"wide": [], "temporal": []}
+        for _ in range(max(rounds, 3) + 1):                    # (the first pair apart: code objects)
+            for kind, blob in (("wide", fw), ("temporal", ft)):
+                torch.cuda.synchronize()
+                t0 = time.time()
+                dec = codec.Decoder(blob, dev, use_graph=False)
+                torch.cuda.synchronize()
+                ready[kind].append(time.time() - t0)
+                assert dec.kind == kind
+                del dec
+        print(f"{label}, run {run}: Decoder ready (file bytes in memory -> model and embeddings on the device, eager frame loop): wide {min(ready['wide'][1:]) * 1e3:.1f} ms "
+              f"best, {max(ready['wide'][1:]) * 1e3:.1f} worst of {len(ready['wide']) - 1} | temporal {min(ready['temporal'][1:]) * 1e3:.1f} ms best, "
+              f"{max(ready['temporal'][1:]) * 1e3:.1f} worst (first calls {ready['wide'][0] * 1e3:.0f}, {ready['temporal'][0] * 1e3:.0f} ms)", flush=True)
+        ts, ws = tstream.read(ft), wstream.read(fw)
+        n_t, P = len(ts.tensors), int(np.prod(ts.embed_shape))
+        at = sum(n for _, n in wstream.record_words(ts)[:n_t])
+        item = lambda r, out: (out, float(r.scale), r.lo, r.hi, wstream.record_cdf(r), r.shift, r.run_words, None if r.beta is None else float(r.beta))      # noqa: E731
+        held, out = torch.empty(n_frames, P, dtype=torch.int32, device=dev), torch.empty(n_frames, P, device=dev)
+        plans = [("ops.AnsDequantWide, the whole wide file", ops.AnsDequantWide(ws.words, [item(r, torch.empty(r.count, device=dev)) for r in ws.tensors + ws.embeds], run)),
+                 ("ops.AnsDequantWide, tensor records", ops.AnsDequantWide(ts.words[:at], [item(r, torch.empty(r.count, device=dev)) for r in ts.tensors], run)),
+                 ("ops.AnsDecodeWide, embedding records", ops.AnsDecodeWide(ts.words[at:], [(held[i], r.lo, r.hi, wstream.record_cdf(r), r.shift, r.run_words)
+                                                                                             for i, r in enumerate(ts.embeds)], run)),
+                 ("ops.EmbedChainDequant", ops.EmbedChainDequant(held, ts.preds, [float(r.scale) for r in ts.embeds], [float(r.beta) for r in ts.embeds], out))]
+        for _, p in plans:
+            p.launch().check()
+        q = torch.from_numpy(tstream.decode_embeds(ts)).to(dev)
+        assert torch.equal(out, q.float() * float(ts.embeds[0].scale) + float(ts.embeds[0].beta))      # (one scale and beta for the clip)
+        times = time_graph([p.launch for _, p in plans], reps=50, rounds=max(rounds, 3))
+        for (name, p), (best, worst) in zip(plans, times):
+            p.check()
+            print(f"{label} decode launch, run {run}, {name}: {best:.1f} us best, {worst:.1f} worst per launch", flush=True)
+    a, b = codec.Decoder(ft, dev, use_graph=False), codec.Decoder(v1, dev, use_graph=False)
+    assert a.kind == "temporal" and all(torch.equal(x, y) for x, y in zip(a.model.state_dict().values(), b.model.state_dict().values()))
+    assert torch.equal(a.embeds, b.embeds) and torch.equal(a.decode_f32(0), b.decode_f32(0)) and torch.equal(a.decode_f32(n_frames - 1), b.decode_f32(n_frames - 1))
+    print(f"{label}: the BNRT file decodes to the parameters, the embeddings and the first and last frame of its version-1 file", flush=True)
+
+
 def forward_rates(cfg):
     """Decode (forward-only) rate of a bench.py decoder (c1 | c3 | c4) on the HIP path: frames/s for single-frame decodes under
     torch.no_grad(), eager and as a captured hipGraph (N4 row: the figure the reference logs as "FPS" in evaluate())."""
@@ -487,6 +557,7 @@ def main():
     ap.add_argument("--posthoc", action="store_true", help="with --bitstream: the post-hoc quantised file of the regression path (C1 model)")
     ap.add_argument("--chunked", action="store_true", help="with --bitstream: the version-1 CEM file against the chunked file of the same model (c1q, c5)")
     ap.add_argument("--wide", action="store_true", help="with --bitstream: the decode kernel of the wide kind against the narrow one (c1q)")
+    ap.add_argument("--temporal", action="store_true", help="with --bitstream: the temporal kind against the wide kind of the same run (c5)")
     ap.add_argument("--sparse", action="store_true", help="with --bitstream --posthoc: the sparse file against the dense file of the same pruned C1 model")
     ap.add_argument("--sparsity", type=float, default=0.4, help="with --sparse: the global magnitude sparsity the model is pruned to")
     ap.add_argument("--frames", type=int, default=16)
@@ -506,6 +577,9 @@ def main():
         return 0
     if a.wide:
         run_wide(a.frames, a.rounds)
+        return 0
+    if a.temporal:
+        run_temporal(a.frames, a.rounds)
         return 0
     if a.chunked:
         for case in ([a.only] if a.only else ["c1q", "c5"]):

@@ -3,6 +3,8 @@
     python tools/kencode.py [--only c1q|c5] [--frames 16] [--rounds 3]     seeded weights (the cases of tools/kdecode.py)
     python tools/kencode.py --trained tiny|c1 [--epochs E]                 a trained model: sizes only
     python tools/kencode.py --wide [--rounds 3]                            the wide kind (BNRW) on c1q: kernels against the narrow ones
+    python tools/kencode.py --temporal [--frames 16] [--rounds 3]          the temporal kind (BNRT) against the wide kind on c5: sizes, encode times
+    python tools/kencode.py --temporal --trained tiny|c5 [--frames 16] [--epochs E]     the same sizes of a trained model
 
 Seeded cases, in ONE process:
   sizes   the version-1 file (BNRV), the chunked file (BNRC) and the file with per-record tables (BNRE) at runs 256 and 1024; how many
@@ -19,6 +21,12 @@ Seeded cases, in ONE process:
 under ops.AnsEncodeRuns and, with shift 0, under ops.AnsEncodeRunsWide (both tables per record, as the file is coded); then the model of
 tools/kdecode.py --wide, whose stem weight record spans about 25 000 values, under ops.AnsEncodeRunsWide with ops.SymHistWide; the file of
 codec.encode(..., wide=True) against the host repack, byte for byte.
+--temporal: the temporal kind (tstream.py) against the wide kind of the same run and tables on the seeded c5 model and --frames
+CONSECUTIVE frames (100, 101, ...) of the 600-frame 1080p synthetic clip: codec.encode(..., wide=True) and (..., temporal=True) alternated, host
+clock, every call ending in a device synchronisation; the temporal file against the host repack byte for byte; the bound of the choice rule;
+embedding bits per frame (words, record bytes, pred byte) and how many frames are coded as differences.  With --trained tiny: the README's
+tiny recipe; with --trained c5: the C3 regression recipe for --epochs epochs on --frames frames, then one rate-distortion epoch of the c5 recipe
+from that checkpoint -- sizes from the version-1 file either way.
 Both --trained cases write the version-1 file; the other kinds are made from it on the host (codec.repack: the bytes of the device path, tests/test_gpu_estream.py).
 (needs the GPU)"""
 import argparse
@@ -206,6 +214,109 @@ def run_wide(n_frames, rounds, reps):
         del model
 
 
+def embed_bits(stream):
+    """Bits per frame of the embedding records of a wide or temporal stream: their words, their serialised records, the pred byte."""
+    from boosting_nerv_amd import codec
+    pred = 8 if hasattr(stream, "preds") else 0
+    return sum(32 * int(r.run_words.sum()) + 8 * codec._record_bytes(r) + pred for r in stream.embeds) / max(len(stream.embeds), 1)
+
+
+def temporal_sizes(label, v1, runs=RUNS):
+    """BNRT against BNRW of a version-1 file at every run under both tables, on the host (the bytes of the device path); one line each."""
+    from boosting_nerv_amd import codec, tstream, wstream
+    part = lambda b: b["ans_words"] + b["tables"] + b["tensor_side"] + b["embed_side"]      # noqa: E731
+    for run in runs:
+        for tables in ("gaussian", "empirical"):
+            w, t = io.BytesIO(), io.BytesIO()
+            bw = codec.repack(v1, w, run, tables, wide=True)
+            bt = codec.repack(v1, t, run, tables, wide=True, temporal=True)
+            assert part(bt) <= part(bw) + 8 * bt["n_embeds"], (part(bt), part(bw))
+            ew, et = embed_bits(wstream.read(w.getvalue())), embed_bits(tstream.read(t.getvalue()))
+            print(f"{label} run {run}, {tables}: BNRW {bw['bytes']} bytes | BNRT {bt['bytes']} bytes ({100.0 * (bt['bytes'] - bw['bytes']) / bw['bytes']:+.2f} %); "
+                  f"{bt['n_inter_frames']} of {bt['n_embeds']} frames as differences; embedding bits per frame: BNRW {ew:.0f}, BNRT {et:.0f} "
+                  f"({100.0 * (et - ew) / ew:+.1f} %); words + tables + side: BNRT {part(bt)} bits, BNRW {part(bw)} bits", flush=True)
+
+
+def consecutive_frames(n_frames, h, w, dev, first=100, clip=600):
+    import torch
+    from boosting_nerv_amd.synth import SyntheticVideo
+    vid = SyntheticVideo(clip, h, w)
+    return torch.stack([vid.frame(first + i, device=dev) for i in range(n_frames)])
+
+
+def run_temporal(n_frames, rounds):
+    import torch
+    from kdecode import build
+    from boosting_nerv_amd import codec
+    from boosting_nerv_amd.lib.entropy_model import DiffEntropyModel
+    dev = torch.device("cuda:0")
+    args, model = build("c5")
+    model = model.to(dev)
+    model.init_data()
+    h, w = (int(v) for v in args.crop_list.split("_")[:2])
+    frames = consecutive_frames(n_frames, h, w, dev)
+    with torch.no_grad():
+        model.embed_quantizer.init_data(model.forward_encoder(frames[0:1]))
+    args.full_data_length = n_frames
+    em = DiffEntropyModel("gaussian")
+    buf = io.BytesIO()
+    codec.encode(model, em, args, frames, buf)
+    v1 = buf.getvalue()
+    label = f"c5 seeded, frames 100..{100 + n_frames - 1} of synthetic:uvg"
+    print(f"{label}: {args.model} {h}x{w}, BNRV {len(v1)} bytes", flush=True)
+    temporal_sizes(label, v1)
+
+    def encode(run, tables, temporal):
+        out = io.BytesIO()
+        torch.cuda.synchronize()
+        t0 = time.time()
+        codec.encode(model, em, args, frames, out, run=run, tables=tables, wide=True, temporal=temporal)
+        torch.cuda.synchronize()
+        return time.time() - t0, out.getvalue()
+
+    for run in RUNS:
+        for tables in ("gaussian", "empirical"):
+            host = io.BytesIO()
+            codec.repack(v1, host, run, tables, wide=True, temporal=True)
+            assert encode(run, tables, True)[1] == host.getvalue(), (run, tables)
+        print(f"{label} run {run}: the device path's BNRT file is the host repack's, byte for byte, under both tables", flush=True)
+    times = {}
+    for _ in range(rounds):
+        for run in RUNS:
+            for temporal in (False, True):
+                times.setdefault((run, temporal), []).append(encode(run, "empirical", temporal)[0])
+    for run in RUNS:
+        a, b = times[(run, False)], times[(run, True)]
+        print(f"{label} encode, run {run}, tables='empirical' (the {n_frames} encoder forwards included): wide {min(a) * 1e3:.0f} ms best, {max(a) * 1e3:.0f} worst of "
+              f"{len(a)} | temporal {min(b) * 1e3:.0f} ms best, {max(b) * 1e3:.0f} worst", flush=True)
+
+
+def run_trained_temporal(which, epochs, n_frames):
+    import torch
+    import bench
+    from boosting_nerv_amd import train_nerv_all as T
+    from boosting_nerv_amd import train_nerv_compression as C
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as tmp:
+        os.chdir(tmp)
+        try:
+            path = os.path.join(tmp, "trained.bnrv")
+            if which == "tiny":
+                C.main(TINY.split() + ["--bitstream", path])
+                label = "tiny recipe, trained (2 epochs)"
+            else:
+                data = ["--data_path", f"synthetic:{n_frames}x1080x1920", "--vid", "c5", "--not_resume"]
+                T.main(bench.RECIPES["c3"]["flags"].split() + data + ["--outf", "kenc_reg", "-e", str(epochs), "--eval_freq", str(epochs)])
+                ckpt = glob.glob(os.path.join(tmp, "output", "kenc_reg", "**", "model_latest.pth"), recursive=True)
+                assert len(ckpt) == 1, ckpt
+                C.main(bench.RECIPES["c5"]["flags"].split() + data + ["--outf", "kenc_cem", "-e", "1", "--eval_freq", "1", "--weight", ckpt[0], "--bitstream", path])
+                label = f"c5, {epochs} regression epochs (C3 recipe) + 1 rate-distortion epoch on {n_frames} frames"
+            torch.cuda.synchronize()
+            temporal_sizes(label, open(path, "rb").read())
+        finally:
+            os.chdir(cwd)
+
+
 def run_trained(which, epochs, cem_epochs=None):
     import torch
     import bench
@@ -237,7 +348,8 @@ def run_trained(which, epochs, cem_epochs=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", choices=["c1q", "c5"], default=None)
-    ap.add_argument("--trained", choices=["tiny", "c1"], default=None)
+    ap.add_argument("--trained", choices=["tiny", "c1", "c5"], default=None, help="c5: with --temporal only")
+    ap.add_argument("--temporal", action="store_true", help="the temporal kind against the wide kind (c5; with --trained: tiny or c5)")
     ap.add_argument("--epochs", type=int, default=30)
     ap.add_argument("--cem_epochs", type=int, default=None, help="--trained c1: rate-distortion epochs (default: --epochs // 2)")
     ap.add_argument("--wide", action="store_true", help="the encode kernels of the wide kind against the narrow ones (c1q)")
@@ -247,6 +359,14 @@ def main():
     a = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "kencode needs the GPU"
+    if a.temporal:
+        if a.trained:
+            assert a.trained in ("tiny", "c5"), "--temporal --trained takes tiny or c5 (C1 has no frame embeddings)"
+            run_trained_temporal(a.trained, a.epochs, a.frames)
+        else:
+            run_temporal(a.frames, a.rounds)
+        return 0
+    assert a.trained != "c5", "--trained c5 needs --temporal"
     if a.wide:
         run_wide(a.frames, a.rounds, a.reps)
         return 0
