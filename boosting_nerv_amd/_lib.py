@@ -132,7 +132,11 @@ class HuffItem(C.Structure):       # bnerv_huff_item
     _fields_ = [("out", _fp), ("min", _fp), ("scale", _fp), ("dtype", C.c_int), ("n", C.c_uint32), ("red", C.c_uint32), ("inner", C.c_uint32)]
 
 
-RANS_MAX_ALPHABET, RANS_MIN_RUN, RANS_MAX_RUN = 4096, 64, 4096      # BNERV_RANS_MAX_ALPHABET, BNERV_RANS_MIN_RUN, BNERV_RANS_MAX_RUN
+class HuffItemU8(C.Structure):     # bnerv_huff_item_u8
+    _fields_ = [("out", C.c_void_p), ("n", C.c_uint32)]
+
+
+RANS_MAX_ALPHABET, RANS_MIN_RUN, RANS_MAX_RUN = 4096, 64, 4096     # BNERV_RANS_MAX_ALPHABET, BNERV_RANS_MIN_RUN, BNERV_RANS_MAX_RUN
 
 
 class RansBlock(C.Structure):      # bnerv_rans_block
@@ -275,6 +279,9 @@ SYMBOLS = {
     "bnerv_embed_delta": (_I, [_V, _V, _Z, _I, _Z, _V, _Z, _V]),
     "bnerv_rans_decode_wide": (_I, [_V, _V, _Z, _V, _Z, _V, _Z, _V, _I, _V, _Z, _I, _V]),
     "bnerv_embed_chain_dequant": (_I, [_V, _V, _Z, _V, _V, _V, _I, _Z, _V, _Z, _V]),
+    "bnerv_embed_delta_u8": (_I, [_V, _V, _Z, _I, _Z, _V, _Z, _V]),
+    "bnerv_huff_decode_u8": (_I, [_V, _V, _Z, _V, _Z, _V, _I, _V, _I, _V]),
+    "bnerv_embed_chain_dequant_u8": (_I, [_V, _V, _Z, _V, _V, _V, _I, C.c_uint32, C.c_uint32, _I, _Z, _V, _Z]),
     "bnerv_huff_encode": (C.c_long, [_V, _V, _I, _V, _I, _V, _Z, _V, _Z]),
     "bnerv_huff_decode": (_I, [_V, _Z, _V, _Z, _V, _I, _V, _I, _V]),
     "bnerv_huff_dequant": (_I, [_V, _V, _Z, _V, _Z, _V, _I, _V, _I, _V]),

@@ -46,7 +46,14 @@ symbols or their integer differences to the frame before, whichever costs fewer 
 temporal=True) on the device, repack(..., wide=True, temporal=True) the same bytes on the host; Decoder entropy-decodes the embedding
 records to integers (ops.AnsDecodeWide) and resolves the chains in one launch (ops.EmbedChainDequant):
 
-    python -m boosting_nerv_amd.codec repack in.bnrv out.bnrt [--run N] [--tables empirical] --temporal"""
+    python -m boosting_nerv_amd.codec repack in.bnrv out.bnrt [--run N] [--tables empirical] --temporal
+
+The post-hoc file has a temporal kind too (pstream.py) for HNeRV and HNeRV_Boost: train_nerv_all.py --bitstream FILE
+--bitstream_temporal (with or without --bitstream_sparse) writes the tensors as the .bnrq / .bnrz file holds them and the frame embeddings
+frame by frame, each as its 8-bit codes or as their differences mod 256 to the frame before, the two kinds under Huffman codes of their own.
+encode_posthoc(..., temporal=True) takes differences and histograms in one launch (ops.EmbedDeltaU8) when the codes are on the device;
+Decoder entropy-decodes the two strings to bytes (ops.HuffDecodeU8) and resolves the chains in one launch (ops.EmbedChainDequantU8).
+decode, psnr, score and info work on it; there is no repack into it."""
 import argparse
 import builtins
 import json
@@ -56,7 +63,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import bitstream, estream, qstream, rstream, tstream, wstream, zstream
+from . import bitstream, estream, pstream, qstream, rstream, tstream, wstream, zstream
 from .bitstream import Record
 
 TABLES = ("gaussian", "empirical")
@@ -582,7 +589,7 @@ def repack(src, dst, run=1024, tables="gaussian", wide=False, temporal=False):
 
     temporal=True (with wide=True): the temporal kind (tstream.py), the host oracle of encode(..., temporal=True).  Returns tstream.info."""
     from .lib.entropy_model import ans_decode_gaussian, ans_encode_gaussian_runs
-    if qstream.magic_of(src) in (qstream.MAGIC, zstream.MAGIC):
+    if qstream.magic_of(src) in (qstream.MAGIC, zstream.MAGIC, pstream.MAGIC):
         raise NotImplementedError("codec.repack: a post-hoc file is not repacked.  A .bnrq twin was quantised with its zeros on the grid, so the pruned "
                                   "weights are no longer zero in it and no sparse (.bnrz) file can be made from it; write one from the checkpoint: "
                                   "train_nerv_all.py --eval_only --weight ... --bitstream FILE --bitstream_sparse")
@@ -646,7 +653,10 @@ def describe_temporal(budget):
 
 
 def describe_any(budget):
-    """describe, describe_posthoc, describe_sparse, describe_chunked, describe_empirical, describe_wide or describe_temporal, by the budget's items."""
+    """describe, describe_posthoc, describe_sparse, describe_posthoc_temporal, describe_chunked, describe_empirical, describe_wide or describe_temporal, by
+    the budget's items."""
+    if "embed_symbol_bits" in budget:
+        return describe_posthoc_temporal(budget)
     if "zero_parse" in budget:
         return describe_sparse(budget)
     if "n_inter_frames" in budget:
@@ -659,10 +669,10 @@ def describe_any(budget):
 
 
 def info(path_or_buffer):
-    """The bit budget of a file of any kind (bitstream.info, qstream.info, zstream.info, rstream.info, estream.info, wstream.info or
-    tstream.info, by the magic number)."""
+    """The bit budget of a file of any kind (bitstream.info, qstream.info, zstream.info, pstream.info, rstream.info, estream.info, wstream.info
+    or tstream.info, by the magic number)."""
     magic = qstream.magic_of(path_or_buffer)
-    return {qstream.MAGIC: qstream.info, zstream.MAGIC: zstream.info, rstream.MAGIC: rstream.info, estream.MAGIC: estream.info,
+    return {qstream.MAGIC: qstream.info, zstream.MAGIC: zstream.info, pstream.MAGIC: pstream.info, rstream.MAGIC: rstream.info, estream.MAGIC: estream.info,
             wstream.MAGIC: wstream.info, tstream.MAGIC: tstream.info}.get(magic, bitstream.info)(path_or_buffer)
 
 
@@ -737,6 +747,11 @@ def check_posthoc_flags(args):
     """The refusals of encode_posthoc that depend on the run's flags alone -- train_nerv_all calls this right after argument parsing, so a
     run that cannot write its --bitstream stops before it trains."""
     name = getattr(args, "model", None)
+    if getattr(args, "bitstream_temporal", False):
+        if not getattr(args, "bitstream", None):
+            raise ValueError("--bitstream_temporal: the temporal kind is what --bitstream FILE writes; give the file")
+        if "HNeRV" not in str(name):
+            raise ValueError(f"--bitstream_temporal: --model {name} has no frame embeddings to code in time (HNeRV, HNeRV_Boost)")
     if name not in POSTHOC_MODELS:
         raise NotImplementedError(f"codec.encode_posthoc: --model {name} has no bitstream (built for {', '.join(POSTHOC_MODELS)})")
     if getattr(args, "quant_model_bit", 8) == -1:
@@ -747,12 +762,44 @@ def check_posthoc_flags(args):
 
 
 @torch.no_grad()
-def encode_posthoc(model, args, records, quant_embed, path):
+def code_embeds(q, run=qstream.RUN):
+    """The embedding section's coded part from the uint8 codes q [N, P] (a device tensor, or a CPU tensor / numpy array) -> (lengths0, lengths1,
+    pred, run_bits [N, runs per frame], words0, words1), the last six fields of a pstream.PEmbeds.  Device codes: ONE launch (ops.EmbedDeltaU8) and one copy of the differences and
+    histograms; host codes: pstream.symbols.  Then pstream.choose and the host coder once per string -- the same bytes either way."""
+    from .lib.entropy_model import huff_encode
+    if torch.is_tensor(q) and q.is_cuda:
+        from . import ops
+        d, h0, h1 = ops.EmbedDeltaU8(q).launch().check().host()
+        q = q.cpu().numpy()
+    else:
+        q = np.ascontiguousarray(q.numpy() if torch.is_tensor(q) else q, dtype=np.uint8)
+        d, h0, h1 = pstream.symbols(q)
+    n, count = q.shape
+    pred, lengths0, lengths1 = pstream.choose(h0, h1, count, run)
+    run_bits = np.zeros((n, qstream.n_runs(count, run)), dtype=np.uint16)
+    strings = []
+    for kind, src, lengths in ((pstream.INTRA, q, lengths0), (pstream.INTER, d, lengths1)):
+        rows = np.flatnonzero(pred == kind)
+        if rows.size == 0:
+            strings.append(np.zeros(0, dtype=np.uint32))
+            continue
+        words, rb = huff_encode(np.ascontiguousarray(src[rows]).reshape(-1), [count] * rows.size, lengths, run)
+        run_bits[rows] = rb.reshape(rows.size, -1)
+        strings.append(words)
+    written, bound = pstream.section_bits(n, count, strings[0].size, strings[1].size, run), pstream.all_intra_section_bits(q, run)
+    assert written <= bound, (written, bound)              # the bound of pstream.choose, on every section that is written
+    return lengths0, lengths1, pred, run_bits, strings[0], strings[1]
+
+
+@torch.no_grad()
+def encode_posthoc(model, args, records, quant_embed, path, temporal=False):
     """Write what train_nerv_all.evaluate() scored under `quant_*` -- `records` of its quant_model() call and, for the HNeRV models, the
     `quant_embed` record of its frame embeddings -- as a qstream file to `path` (a file name or a binary file object); returns
     qstream.info of what was written.  Nothing is re-quantised: the symbols, the grids and the Huffman code are those of that evaluation,
     so info["symbol_bits"] is _huffman_total_bits of its histogram, args.bits_per_param * numel.
-    Records that carry `keep` (quant_tensor_sparse, --bitstream_sparse) make a zstream file instead; returns zstream.info."""
+    Records that carry `keep` (quant_tensor_sparse, --bitstream_sparse) make a zstream file instead; returns zstream.info.
+    temporal=True (HNeRV models; --bitstream_temporal) makes a pstream file: the tensor records through the same dense or
+    sparse path without the embedding record, the embeddings frame by frame under code_embeds; returns pstream.info."""
     from .lib.entropy_model import huff_encode, huffz_encode
     check_posthoc_flags(args)
     if records is None:
@@ -761,8 +808,10 @@ def encode_posthoc(model, args, records, quant_embed, path):
     is_hnerv = "HNeRV" in name
     if is_hnerv and quant_embed is None:
         raise ValueError(f"codec.encode_posthoc: --model {name} needs the quantised frame embeddings of the evaluation")
-    recs = ([quant_embed] if is_hnerv else []) + list(records.values())
-    for r in recs:
+    if temporal and not is_hnerv:
+        raise ValueError(f"codec.encode_posthoc: temporal=True needs frame embeddings; --model {name} has none (HNeRV, HNeRV_Boost)")
+    recs = ([quant_embed] if is_hnerv and not temporal else []) + list(records.values())
+    for r in recs + ([quant_embed] if temporal else []):
         if r["quant"].dtype != torch.uint8 or r["quant"].numel() == 0:
             raise NotImplementedError(f"codec.encode_posthoc: symbols of dtype {r['quant'].dtype} are not coded (8 bits at most)")
     sparse = any("keep" in r for r in recs)
@@ -788,6 +837,17 @@ def encode_posthoc(model, args, records, quant_embed, path):
         s["embed_shape"] = [int(v) for v in quant_embed["quant"].shape]
     if sparse:
         s.update(zero_parse=parse, n_zero_leaves=int(hist[zstream.ZERO:].sum()))
+    if temporal:
+        q = quant_embed["quant"]
+        if q.dim() != 4:
+            raise ValueError(f"codec.encode_posthoc: the frame embeddings have the shape {tuple(q.shape)}, not [N, C, h, w]")
+        outer, red, inner, flag = _grid_geometry(quant_embed)
+        grid = (quant_embed["min"].detach().reshape(-1).cpu().numpy(), quant_embed["scale"].detach().reshape(-1).cpu().numpy())
+        embeds = pstream.PEmbeds(tuple(int(v) for v in q.shape), outer, red, inner, flag, *grid, *code_embeds(q.detach().reshape(q.shape[0], -1), qstream.RUN))
+        s.update(embed_pred=pstream.EMBED_PRED, tensor_kind="sparse" if sparse else "dense")
+        blob = pstream.to_bytes(s, lengths, out, words, embeds)
+        _write_blob(path, blob)
+        return pstream.info(blob)
     blob = (zstream if sparse else qstream).to_bytes(s, lengths, out, words)
     _write_blob(path, blob)
     return (zstream if sparse else qstream).info(blob)
@@ -798,6 +858,14 @@ def describe_posthoc(budget):
     return (f"{budget['bytes']} bytes = {budget['total']} bits: Huffman codes {budget['symbol_bits']} ({budget['n_symbols']} symbols in {budget['n_records']} "
             f"tensors) + run index {budget['run_index']} ({budget['n_runs']} runs) + grids {budget['grid_side']} + code table {budget['code_table']} "
             f"+ header {budget['header']} + padding {budget['padding']}")
+
+
+def describe_posthoc_temporal(budget):
+    """One line of a pstream.info budget (the log of train_nerv_all --bitstream --bitstream_temporal, `codec info`)."""
+    return (f"{describe_sparse(budget) if 'zero_parse' in budget else describe_posthoc(budget)}; temporal: embeddings {budget['embed_symbol_bits']} "
+            f"({budget['n_embed_symbols']} symbols; {budget['n_intra_frames']} frames on their own in {budget['intra_frame_bits']} bits, "
+            f"{budget['n_inter_frames']} as differences to the frame before in {budget['inter_frame_bits']}) + run index {budget['embed_run_index']} "
+            f"+ side {budget['embed_side']} + code tables {budget['embed_tables']}")
 
 
 def describe_sparse(budget):
@@ -829,10 +897,10 @@ class Decoder:
         from .lib.entropy_model import ans_decode_gaussian
         from .train_nerv_all import build_model
         magic = qstream.magic_of(path)
-        self.kind = {qstream.MAGIC: "posthoc", zstream.MAGIC: "sparse", rstream.MAGIC: "chunked", estream.MAGIC: "empirical", wstream.MAGIC: "wide",
+        self.kind = {qstream.MAGIC: "posthoc", zstream.MAGIC: "sparse", pstream.MAGIC: "posthoc_temporal", rstream.MAGIC: "chunked", estream.MAGIC: "empirical", wstream.MAGIC: "wide",
                      tstream.MAGIC: "temporal"}.get(magic, "cem")
-        if self.kind in ("posthoc", "sparse"):
-            (self._load_sparse if self.kind == "sparse" else self._load_posthoc)(path, device)
+        if self.kind in ("posthoc", "sparse", "posthoc_temporal"):
+            {"posthoc": self._load_posthoc, "sparse": self._load_sparse, "posthoc_temporal": self._load_posthoc_temporal}[self.kind](path, device)
             return self._frame_loop(use_graph, pack, matrix, range)
         bs = {"chunked": rstream.read, "empirical": estream.read, "wide": wstream.read, "temporal": tstream.read}.get(self.kind, bitstream.read)(path)
         what = {"chunked": "rstream", "empirical": "estream", "wide": "wstream", "temporal": "tstream"}.get(self.kind, "bitstream")
@@ -941,6 +1009,12 @@ class Decoder:
         from . import ops
         self._load_posthoc(path, device, zstream, ops.huffz_dequant)
 
+    def _load_posthoc_temporal(self, path, device):
+        """A pstream file: the tensor section through the launch of its kind, the two bit strings of the embedding section
+        entropy-decoded to bytes (one launch per non-empty string), then ONE launch that resolves the chains of the inter frames and
+        de-quantises into self.embeds; every error word is read at one synchronisation."""
+        self._load_posthoc(path, device, pstream)
+
     def _load_posthoc(self, path, device, fmt=qstream, dequant=None):
         """A qstream file: the model without quantisers (and, for the HNeRV models, without its encoder), the bit
         string uploaded once as it lies in the file, ONE launch that Huffman-decodes and de-quantises it into the state_dict tensors and the
@@ -948,7 +1022,8 @@ class Decoder:
         from . import ops
         from .train_nerv_all import build_model
         qs = fmt.read(path)
-        what = "zstream" if fmt is zstream else "qstream"
+        what = fmt.__name__.rsplit(".", 1)[-1]
+        temporal = fmt is pstream
         s = dict(qs.settings)
         if s.get("model") not in POSTHOC_MODELS:
             raise ValueError(f"{what}: header names the model {s.get('model')!r}; this build decodes {', '.join(POSTHOC_MODELS)}")
@@ -957,7 +1032,9 @@ class Decoder:
         self.n_frames = int(s["full_data_length"])
         self.frame_hw = tuple(int(v) for v in s["crop_list"].split("_")[:2])
         self.is_hnerv = "HNeRV" in s["model"]
-        margs = SimpleNamespace(**s)
+        if temporal and not self.is_hnerv:
+            raise ValueError(f"{what}: an embedding section in a {s['model']} stream")
+        margs = SimpleNamespace(**{k: v for k, v in s.items() if k not in ("embed_pred", "tensor_kind")})
         margs.__dict__.update(quant=False, outf="")
         model = build_model(margs)
         if self.is_hnerv:
@@ -967,10 +1044,11 @@ class Decoder:
         targets = []
         if self.is_hnerv:
             shape = tuple(int(v) for v in s.get("embed_shape", ()))
-            if len(shape) != 4 or shape[0] != self.n_frames:
+            if len(shape) != 4 or shape[0] != self.n_frames or (temporal and shape != tuple(qs.embeds.shape)):
                 raise ValueError(f"{what}: the header's embedding shape {shape} does not match its {self.n_frames} frames")
             self.embeds = torch.empty(shape, dtype=torch.float32, device=self.device)
-            targets.append(self.embeds)
+            if not temporal:
+                targets.append(self.embeds)
         else:
             self.embeds = None
         targets += [v for k, v in model.state_dict().items() if "encoder" not in k]
@@ -987,13 +1065,34 @@ class Decoder:
                 spans.append((at, a.nbytes))
                 blobs.append(raw)
                 at += len(raw)
+        if temporal:                                       # the embedding section's grid rides in the same upload
+            for a in (qs.embeds.min, qs.embeds.scale):
+                raw = a.tobytes()
+                raw += b"\0" * (-len(raw) % 4)
+                spans.append((at, a.nbytes))
+                blobs.append(raw)
+                at += len(raw)
         grids = torch.frombuffer(bytearray(b"".join(blobs)), dtype=torch.uint8).to(self.device)
         items = []
         for k, (t, r) in enumerate(zip(targets, qs.records)):
             tdt = torch.float16 if r.dtype == qstream.F16 else torch.float32
             lo, step = (grids[o:o + n].view(tdt) for o, n in spans[2 * k:2 * k + 2])
             items.append((t, lo, step, r.red, r.inner, r.run_bits))
-        (dequant or ops.huff_dequant)(qs.words, qs.lengths, items, int(s["huff_run"]))
+        if not temporal:
+            (dequant or ops.huff_dequant)(qs.words, qs.lengths, items, int(s["huff_run"]))
+            return
+        e, run = qs.embeds, int(s["huff_run"])
+        jobs = [(ops.HuffzDequant if s["tensor_kind"] == "sparse" else ops.HuffDequant)(qs.words, qs.lengths, items, run).launch()]
+        held = torch.empty(self.n_frames, self.embeds[0].numel(), dtype=torch.uint8, device=self.device)
+        for kind, lengths, words in ((pstream.INTRA, e.lengths0, e.words0), (pstream.INTER, e.lengths1, e.words1)):
+            rows = np.flatnonzero(e.pred == kind)
+            if rows.size:
+                jobs.append(ops.HuffDecodeU8(words, lengths, [(held[int(t)], e.run_bits[int(t)]) for t in rows], run).launch())
+        tdt = torch.float16 if e.dtype == qstream.F16 else torch.float32
+        lo, step = (grids[o:o + n].view(tdt) for o, n in spans[-2:])
+        jobs.append(ops.EmbedChainDequantU8(held, e.pred, lo, step, e.red, e.inner, self.embeds.view(self.n_frames, -1)).launch())
+        for job in jobs:                                   # the first check is the one synchronisation; the others read words that are ready
+            job.check()
 
     def _frame_loop(self, use_graph, pack, matrix, range):
         from .engine import FrameDecodeGraph

@@ -18,6 +18,7 @@
 // The store phase is huff.hip's with one select:  out[i] = keep ? float(min[s]) + float(scale[s]) * float(q[i]) : +0.0f.
 #include "common.h"
 #include "huff_code.h"
+#include "huff_rebuild.h"
 
 namespace {
 
@@ -33,13 +34,6 @@ struct Tables {
     unsigned short offset[33];
     unsigned short sorted[BNERV_HUFFZ_LEAVES];
 };
-
-// the product and the sum as two IEEE fp32 operations: the expression quant_tensor_sparse calls `rebuilt` (see codec.hip on the pragma)
-__device__ __forceinline__ float rebuild1(float mn, float sc, unsigned q) {
-#pragma clang fp contract(off)
-    const float p = sc * (float)q;
-    return mn + p;
-}
 
 __global__ __launch_bounds__(WAVE) void huffz_dequant_kernel(const unsigned* __restrict__ words, const size_t n_words, const bnerv_huff_run* __restrict__ runs,
                                                              const unsigned n_runs, const bnerv_huff_item* __restrict__ items, const unsigned n_items,

@@ -952,6 +952,8 @@ class HuffDequant:
     launch() decodes and de-quantises everything in one kernel; check() reads the device error word (a host sync) and raises ValueError
     when a run did not end on its recorded bit."""
     _name, _entry, _leaves = "huff_dequant", "bnerv_huff_dequant", L.HUFF_LEAVES
+    _item_struct = L.HuffItem
+    _item_dtype = [("out", "<u8"), ("min", "<u8"), ("scale", "<u8"), ("dtype", "<i4"), ("n", "<u4"), ("red", "<u4"), ("inner", "<u4")]
 
     def __init__(self, words, lengths, items, run=L.HUFF_RUN):
         import numpy as np
@@ -964,26 +966,16 @@ class HuffDequant:
         if run != L.HUFF_RUN:
             raise ValueError(f"{self._name}: the kernel is built for runs of {L.HUFF_RUN} symbols, not {run}")
         self.run = int(run)
-        table = np.zeros(len(items), dtype=np.dtype([("out", "<u8"), ("min", "<u8"), ("scale", "<u8"), ("dtype", "<i4"), ("n", "<u4"), ("red", "<u4"), ("inner", "<u4")]))
-        assert table.dtype.itemsize == C.sizeof(L.HuffItem)
+        table = np.zeros(len(items), dtype=self._item_dtype)
+        assert table.dtype.itemsize == C.sizeof(self._item_struct)
         starts, item_of, first_of, bit = [], [], [], 0
         device = items[0][0].device
-        for k, (out, lo, step, red, inner, run_bits) in enumerate(items):
-            L.require_device(out, "out"), L.require_device(lo, "min"), L.require_device(step, "scale")
-            n, red, inner = out.numel(), int(red), int(inner)
-            if out.dtype != torch.float32 or not out.is_contiguous() or n == 0 or n >= 2 ** 31 or out.data_ptr() % 4 or out.device != device:
-                raise ValueError(f"{self._name}: item {k}: out must be a non-empty contiguous 4-byte aligned fp32 tensor on {device} (below 2^31 elements)")
-            if red < 1 or inner < 1 or n % (red * inner):
-                raise ValueError(f"{self._name}: item {k}: {n} elements do not split into slices of red={red}, inner={inner}")
-            slices = n // red
-            if lo.dtype != step.dtype or lo.dtype not in (torch.float32, torch.float16) or lo.numel() != slices or step.numel() != slices \
-                    or not lo.is_contiguous() or not step.is_contiguous() or (lo.data_ptr() | step.data_ptr()) % lo.element_size():
-                raise ValueError(f"{self._name}: item {k}: min and scale must be contiguous fp32 or fp16 tensors of {slices} entries each")
-            rb = np.ascontiguousarray(run_bits, dtype=np.uint16)
+        for k, item in enumerate(items):
+            table[k] = self._item(k, item, device)
+            n, rb = int(table[k]["n"]), np.ascontiguousarray(item[-1], dtype=np.uint16)
             n_runs = (n + run - 1) // run
             if rb.size != n_runs:
                 raise ValueError(f"{self._name}: item {k}: {rb.size} run lengths for {n_runs} runs")
-            table[k] = (out.data_ptr(), lo.data_ptr(), step.data_ptr(), L.HUFF_F16 if lo.dtype == torch.float16 else L.HUFF_F32, n, red, inner)
             ends = bit + np.cumsum(rb, dtype=np.uint64)
             starts.append(np.concatenate([np.array([bit], dtype=np.uint64), ends[:-1]]))
             item_of.append(np.full(n_runs, k, dtype=np.uint32))
@@ -1002,7 +994,22 @@ class HuffDequant:
         self.words, self.runs, self.items = up(padded), up(runs), up(table)
         self.n_words, self.n_items = padded.size, len(items)
         self.err = torch.zeros(1, dtype=torch.int32, device=device)
-        self._keep = [(o, a, b) for o, a, b, *_ in items]
+        self._keep = [it[:-1] for it in items]
+
+    def _item(self, k, item, device):
+        """The row of the item table for items[k], checked."""
+        out, lo, step, red, inner, _ = item
+        L.require_device(out, "out"), L.require_device(lo, "min"), L.require_device(step, "scale")
+        n, red, inner = out.numel(), int(red), int(inner)
+        if out.dtype != torch.float32 or not out.is_contiguous() or n == 0 or n >= 2 ** 31 or out.data_ptr() % 4 or out.device != device:
+            raise ValueError(f"{self._name}: item {k}: out must be a non-empty contiguous 4-byte aligned fp32 tensor on {device} (below 2^31 elements)")
+        if red < 1 or inner < 1 or n % (red * inner):
+            raise ValueError(f"{self._name}: item {k}: {n} elements do not split into slices of red={red}, inner={inner}")
+        slices = n // red
+        if lo.dtype != step.dtype or lo.dtype not in (torch.float32, torch.float16) or lo.numel() != slices or step.numel() != slices \
+                or not lo.is_contiguous() or not step.is_contiguous() or (lo.data_ptr() | step.data_ptr()) % lo.element_size():
+            raise ValueError(f"{self._name}: item {k}: min and scale must be contiguous fp32 or fp16 tensors of {slices} entries each")
+        return (out.data_ptr(), lo.data_ptr(), step.data_ptr(), L.HUFF_F16 if lo.dtype == torch.float16 else L.HUFF_F32, n, red, inner)
 
     def launch(self):
         L.check(getattr(L.load(), self._entry)(L.stream(), L.ptr(self.words), self.n_words, L.ptr(self.runs), self.n_runs, L.ptr(self.items), self.n_items,
@@ -1704,6 +1711,125 @@ class EmbedChainDequant:
     def check(self):
         if int(self.err.item()) != 0:
             raise ValueError("embed_chain_dequant: a chain of predicted frames leaves int32 (the file's differences do not belong to its symbols)")
+        return self
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# inter-coded frame embeddings of the post-hoc file (pstream.py, codec.encode_posthoc(..., temporal=True); csrc/hufft.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+def _byte_rows(t, name, what):
+    """(N, P, pitch) of a 2-D uint8 device tensor whose rows are dense (stride 1 along p, any row pitch >= P), at any byte alignment."""
+    L.require_device(t, name)
+    if t.dim() != 2 or t.dtype != torch.uint8 or t.numel() == 0 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError(f"{what}: {name} must be a non-empty [N, P] uint8 device tensor with dense rows (row pitch >= P), got {t.dtype} {tuple(t.shape)} "
+                         f"strides {tuple(t.stride())}")
+    return int(t.shape[0]), int(t.shape[1]), int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+
+class EmbedDeltaU8:
+    """The frame-to-frame differences of the 8-bit embedding codes and the histograms the choice rule reads, ONE launch (bnerv_embed_delta_u8).
+
+        q          uint8 [N, P] device tensor, dense rows at any row pitch and any byte alignment
+        d          None, or the uint8 [N, P] tensor to write (same rules); row 0 is not written
+    launch() zeroes the histograms and fills d[t] = (q[t] - q[t - 1]) mod 256 for t >= 1; check() is there for the shape of the other ops (the
+    kernel takes no index from a descriptor: nothing can be flagged); host() -> (d, h0, h1): the differences as a uint8 [N, P] numpy array
+    (row 0 zero) and the int64 [N, 256] histograms of q[t] and of d[t] (h1[0] is zero)."""
+
+    def __init__(self, q, d=None):
+        self.N, self.P, self.q_pitch = _byte_rows(q, "q", "embed_delta_u8")
+        self._buf = None
+        if d is None:                                      # the histograms and the differences in ONE buffer: host() is one copy
+            self._buf = torch.zeros(self.N * (2048 + self.P), dtype=torch.uint8, device=q.device)
+            d = self._buf[self.N * 2048:].view(self.N, self.P)
+        N, P, self.d_pitch = _byte_rows(d, "d", "embed_delta_u8")
+        if (N, P) != (self.N, self.P) or d.device != q.device:
+            raise ValueError(f"embed_delta_u8: d is {tuple(d.shape)} on {d.device}, q {tuple(q.shape)} on {q.device}")
+        if self.N > 1 << 20 or max(self.q_pitch, self.d_pitch) >= 2 ** 31:
+            raise ValueError(f"embed_delta_u8: {self.N} frames at pitches {self.q_pitch}, {self.d_pitch} (at most 2^20 frames, pitches below 2^31)")
+        self.q, self.d = q, d
+        self.hist = (torch.zeros(self.N * 2048, dtype=torch.uint8, device=q.device) if self._buf is None else self._buf[:self.N * 2048]).view(torch.int32).view(self.N, 2, 256)
+
+    def launch(self):
+        L.check(L.load().bnerv_embed_delta_u8(L.stream(), L.ptr(self.q), self.q_pitch, self.N, self.P, L.ptr(self.d), self.d_pitch, L.ptr(self.hist)),
+                "bnerv_embed_delta_u8")
+        return self
+
+    def check(self):
+        return self
+
+    def host(self):
+        import numpy as np
+        if self._buf is None:
+            d, hist = self.d.cpu().numpy().copy(), self.hist.cpu().numpy()
+        else:
+            raw = self._buf.cpu().numpy()
+            d, hist = raw[self.N * 2048:].reshape(self.N, self.P).copy(), raw[:self.N * 2048].view(np.int32).reshape(self.N, 2, 256)
+        d[0] = 0
+        hist = hist.view(np.uint32).astype(np.int64)
+        return d, hist[:, 0].copy(), hist[:, 1].copy()
+
+
+class HuffDecodeU8(HuffDequant):
+    """One bit string of a pstream embedding section on the device: HuffDequant with a byte result (bnerv_huff_decode_u8,
+    the same kernel body): out[i] = the symbol, nothing is de-quantised.
+
+        items      one (out, run_bits) per frame: out a contiguous uint8 device tensor (a row of the scratch: any byte alignment)"""
+    _name, _entry = "huff_decode_u8", "bnerv_huff_decode_u8"
+    _item_struct = L.HuffItemU8
+    _item_dtype = [("out", "<u8"), ("n", "<u4"), ("_pad", "<u4")]
+
+    def _item(self, k, item, device):
+        out, _ = item
+        L.require_device(out, "out")
+        n = out.numel()
+        if out.dtype != torch.uint8 or not out.is_contiguous() or n == 0 or n >= 2 ** 31 or out.device != device:
+            raise ValueError(f"{self._name}: item {k}: out must be a non-empty contiguous uint8 tensor on {device} (below 2^31 elements)")
+        return (out.data_ptr(), n, 0)
+
+
+class EmbedChainDequantU8:
+    """The symbols of the embedding section of a pstream file resolved and de-quantised, ONE launch (bnerv_embed_chain_dequant_u8):
+    q_t = pred[t] ? (q_{t-1} + sym_t) mod 256 : sym_t,  out = float(min[s]) + float(scale[s]) * float(q)  on the quant_tensor grid of the whole
+    [N, P] tensor, s = (i // (red * inner)) * inner + i % inner, i = t * P + p (product and sum one fp32 operation each).
+
+        sym        uint8 [N, P] device tensor, dense rows at any row pitch and any byte alignment
+        pred       N values 0 | 1; pred[0] must be 0 (refused here, before any launch)
+        lo, step   contiguous fp32 or fp16 device tensors of N * P / red entries each (the grid's min and scale)
+        red, inner the grid's geometry; one pair for the whole tensor is (N * P, 1)
+        out        fp32 [N, P] device tensor, dense rows at any row pitch, 4-byte aligned
+    check() is there for the shape of the other ops: every byte is a code, nothing can be flagged."""
+
+    def __init__(self, sym, pred, lo, step, red, inner, out):
+        import numpy as np
+        self.N, self.P, self.sym_pitch = _byte_rows(sym, "sym", "embed_chain_dequant_u8")
+        N, P, self.out_pitch = _rows(out, "out", torch.float32, "embed_chain_dequant_u8")
+        if (N, P) != (self.N, self.P) or out.device != sym.device:
+            raise ValueError(f"embed_chain_dequant_u8: out is {tuple(out.shape)} on {out.device}, sym {tuple(sym.shape)} on {sym.device}")
+        pred = np.ascontiguousarray(pred).reshape(-1)
+        if pred.size != self.N or ((pred != 0) & (pred != 1)).any():
+            raise ValueError(f"embed_chain_dequant_u8: pred must be {self.N} values 0 | 1")
+        if pred[0] != 0:
+            raise ValueError("embed_chain_dequant_u8: frame 0 is predicted (pred[0] = 1): there is no frame before it")
+        n, red, inner = self.N * self.P, int(red), int(inner)
+        if red < 1 or inner < 1 or n % (red * inner):
+            raise ValueError(f"embed_chain_dequant_u8: {n} elements do not split into slices of red={red}, inner={inner}")
+        L.require_device(lo, "min"), L.require_device(step, "scale")
+        slices = n // red
+        if lo.dtype != step.dtype or lo.dtype not in (torch.float32, torch.float16) or lo.numel() != slices or step.numel() != slices \
+                or not lo.is_contiguous() or not step.is_contiguous() or (lo.data_ptr() | step.data_ptr()) % lo.element_size():
+            raise ValueError(f"embed_chain_dequant_u8: min and scale must be contiguous fp32 or fp16 tensors of {slices} entries each")
+        if self.N > 65535 * L.CHAIN_SEG or max(self.sym_pitch, self.out_pitch) >= 2 ** 31 or n >= 2 ** 31:
+            raise ValueError(f"embed_chain_dequant_u8: {self.N} frames of {self.P} at pitches {self.sym_pitch}, {self.out_pitch}")
+        self.sym, self.out, self.lo, self.step, self.red, self.inner = sym, out, lo, step, red, inner
+        self.dtype = L.HUFF_F16 if lo.dtype == torch.float16 else L.HUFF_F32
+        self.pred = _upload(pred.astype(np.uint8), sym.device)
+
+    def launch(self):
+        L.check(L.load().bnerv_embed_chain_dequant_u8(L.stream(), L.ptr(self.sym), self.sym_pitch, L.ptr(self.pred), L.ptr(self.lo), L.ptr(self.step), self.dtype,
+                                                      self.red, self.inner, self.N, self.P, L.ptr(self.out), self.out_pitch), "bnerv_embed_chain_dequant_u8")
+        return self
+
+    def check(self):
         return self
 
 

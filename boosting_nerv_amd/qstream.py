@@ -69,10 +69,15 @@ def n_runs(count, run=RUN):
     return (int(count) + run - 1) // run
 
 
-def _payload(settings, lengths, records, words):
+def _header(settings):
     header = json.dumps(settings, sort_keys=True, separators=(",", ":")).encode("utf-8")
+    return [_U32.pack(len(header)), header]
+
+
+def _section(lengths, records, words):
+    """The payload behind the header -- code table, records, bit string -- as a list of byte strings (pstream.py holds the same bytes)."""
     ln = np.ascontiguousarray(lengths, dtype=np.uint8)
-    out = [_U32.pack(len(header)), header, ln.tobytes(), _U32.pack(len(records))]
+    out = [ln.tobytes(), _U32.pack(len(records))]
     for r in records:
         dt = _DTYPES[int(r.dtype)]
         out.append(_RECORD.pack(int(r.count), int(r.outer), int(r.red), int(r.inner), int(r.dtype)))
@@ -84,7 +89,11 @@ def _payload(settings, lengths, records, words):
         out.append(np.ascontiguousarray(r.run_bits, dtype="<u2").tobytes())
     w = np.ascontiguousarray(words, dtype="<u4")
     out += [_U32.pack(w.size), w.tobytes()]
-    return b"".join(out)
+    return out
+
+
+def _payload(settings, lengths, records, words):
+    return b"".join(_header(settings) + _section(lengths, records, words))
 
 
 def write(path_or_buffer, settings, lengths, records, words):
@@ -172,6 +181,16 @@ def _parse(path_or_buffer):
     run = settings.get("huff_run") if isinstance(settings, dict) else None
     if not isinstance(run, int) or not 1 <= run <= 2047:
         raise ValueError(f"qstream: the header's run length is {run!r}")
+    lengths, records, words, total = _parse_section(cur, run)
+    if cur.pos != len(payload):
+        raise ValueError(f"qstream: {len(payload) - cur.pos} payload bytes follow the bit string")
+    _book_section(cur, total, words.size)
+    cur.bits["header"] += 8 * (_PREFIX.size + 4)           # magic, version, length and the CRC
+    return QStream(settings, lengths, records, words), cur.bits, len(blob)
+
+
+def _parse_section(cur, run):
+    """What _section wrote, read at the cursor -> (lengths, records, words, the bits the run lengths add up to)."""
     lengths = np.frombuffer(cur.take(LEAVES, "code_table"), dtype=np.uint8).copy()
     check_lengths(lengths)
     n_records, = cur.unpack(_U32, "header")
@@ -188,14 +207,15 @@ def _parse(path_or_buffer):
         records.append(QRecord(count, outer, red, inner, dtype, lo, step, run_bits))
     n_words, = cur.unpack(_U32, "header")
     words = np.frombuffer(cur.take(4 * n_words, "symbol_bits"), dtype="<u4").astype(np.uint32)
-    if cur.pos != len(payload):
-        raise ValueError(f"qstream: {len(payload) - cur.pos} payload bytes follow the bit string")
+    return lengths, records, words, total
+
+
+def _book_section(cur, total, n_words):
+    """The run lengths against the bit string; the string's bits booked as codes and padding."""
     if (total + 31) // 32 != n_words:
         raise ValueError(f"qstream: the run lengths of the records add up to {total} bits, the bit string has {n_words} words")
     cur.bits["padding"] = 32 * n_words - total
     cur.bits["symbol_bits"] = total
-    cur.bits["header"] += 8 * (_PREFIX.size + 4)           # magic, version, length and the CRC
-    return QStream(settings, lengths, records, words), cur.bits, len(blob)
 
 
 def read(path_or_buffer):

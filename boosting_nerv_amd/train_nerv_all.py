@@ -102,6 +102,10 @@ def build_parser():
     parser.add_argument('--bitstream_sparse', action='store_true', default=False,
                         help='with --bitstream: quantise the prunable tensors so that a zero weight stays exactly zero and write the sparse file '
                              'kind, whose Huffman alphabet has leaves for runs of zeros (DESIGN section 31)')
+    parser.add_argument('--bitstream_temporal', action='store_true', default=False,
+                        help='with --bitstream (HNeRV, HNeRV_Boost): write the temporal file kind, in which a frame embedding is coded on its own or '
+                             'as the differences to the frame before, each under a Huffman code of its own (DESIGN section 35); combines with '
+                             '--bitstream_sparse')
     parser.add_argument('--dump_videos', action='store_true', default=False, help='concat the prediction images into video')
     parser.add_argument('--eval_fps', action='store_true', default=False, help='fwd multiple times to test the fps')
     parser.add_argument('--encoder_file', default='', type=str, help='specify the embedding file')
@@ -189,7 +193,7 @@ def build_model(args):
 def main(argv=None):
     args = parse_args(argv)
     torch.set_printoptions(precision=2)
-    if args.bitstream:                                     # what no file can hold is refused before the run, not after its last epoch
+    if args.bitstream or args.bitstream_temporal:          # what no file can hold is refused before the run, not after its last epoch
         from .codec import check_posthoc_flags
         check_posthoc_flags(args)
     if args.debug:
@@ -592,7 +596,8 @@ def evaluate(model, full_dataloader, local_rank, args, dump_vis=False, huffman_c
             log.line(f'Sparsity: {pruner.pruned()} of {pruner.n} prunable weights are zero ({pruner.sparsity():.4f})')
     if local_rank in (0, None) and huffman_coding and getattr(args, 'bitstream', None):
         from . import codec
-        args.bitstream_budget = codec.encode_posthoc(model, args, records, quant_embed if is_hnerv else None, args.bitstream)
+        args.bitstream_budget = codec.encode_posthoc(model, args, records, quant_embed if is_hnerv else None, args.bitstream,
+                                                     temporal=getattr(args, 'bitstream_temporal', False))
         log.line(f'Bitstream {args.bitstream}: {codec.describe_any(args.bitstream_budget)}')
     return values, hw
 

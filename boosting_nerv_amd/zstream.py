@@ -32,7 +32,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from .qstream import F16, F32, ITEMS, RUN, _Cursor, _blob, magic_of, n_runs      # noqa: F401  (the shared framing; re-exported)
+from .qstream import F16, F32, ITEMS, RUN, _Cursor, _blob, _header, magic_of, n_runs     # noqa: F401  (the shared framing; re-exported)
 
 MAGIC = b"BNRZ"
 VERSION = 1
@@ -94,12 +94,12 @@ def parse_histogram(symbols, keep, counts, parse, run=RUN):
     return hist
 
 
-def _payload(settings, lengths, records, words):
-    header = json.dumps(settings, sort_keys=True, separators=(",", ":")).encode("utf-8")
+def _section(lengths, records, words):
+    """The payload behind the header -- code table, records, bit string -- as a list of byte strings (pstream.py holds the same bytes)."""
     ln = np.ascontiguousarray(lengths, dtype=np.uint8)
     if ln.size != LEAVES:
         raise ValueError(f"zstream.write: the code table needs {LEAVES} lengths, got {ln.size}")
-    out = [_U32.pack(len(header)), header, ln.tobytes(), _U32.pack(len(records))]
+    out = [ln.tobytes(), _U32.pack(len(records))]
     for r in records:
         dt = _DTYPES[int(r.dtype)]
         out.append(_RECORD.pack(int(r.count), int(r.outer), int(r.red), int(r.inner), int(r.dtype), int(r.kept)))
@@ -111,7 +111,11 @@ def _payload(settings, lengths, records, words):
         out.append(np.ascontiguousarray(r.run_bits, dtype="<u2").tobytes())
     w = np.ascontiguousarray(words, dtype="<u4")
     out += [_U32.pack(w.size), w.tobytes()]
-    return b"".join(out)
+    return out
+
+
+def _payload(settings, lengths, records, words):
+    return b"".join(_header(settings) + _section(lengths, records, words))
 
 
 def write(path_or_buffer, settings, lengths, records, words):
@@ -162,6 +166,16 @@ def _parse(path_or_buffer):
     zero_leaves = settings.get("n_zero_leaves")
     if settings.get("zero_parse") not in PARSES or not isinstance(zero_leaves, int) or zero_leaves < 0:
         raise ValueError(f"zstream: the header's zero_parse / n_zero_leaves are {settings.get('zero_parse')!r} / {zero_leaves!r}")
+    lengths, records, words, total, zeros = _parse_section(cur, run)
+    if cur.pos != len(payload):
+        raise ValueError(f"zstream: {len(payload) - cur.pos} payload bytes follow the bit string")
+    _book_section(cur, settings, total, words.size, zeros)
+    cur.bits["header"] += 8 * (_PREFIX.size + 4)           # magic, version, length and the CRC
+    return ZStream(settings, lengths, records, words), cur.bits, len(blob), zeros
+
+
+def _parse_section(cur, run):
+    """What _section wrote, read at the cursor -> (lengths, records, words, the bits the run lengths add up to, the zero elements)."""
     try:
         lengths = np.frombuffer(cur.take(LEAVES, "code_table"), dtype=np.uint8).copy()
         check_lengths(lengths)
@@ -184,16 +198,18 @@ def _parse(path_or_buffer):
         words = np.frombuffer(cur.take(4 * n_words, "symbol_bits"), dtype="<u4").astype(np.uint32)
     except ValueError as e:
         raise ValueError(str(e).replace("qstream", "zstream")) from None
-    if cur.pos != len(payload):
-        raise ValueError(f"zstream: {len(payload) - cur.pos} payload bytes follow the bit string")
+    return lengths, records, words, total, zeros
+
+
+def _book_section(cur, settings, total, n_words, zeros):
+    """The run lengths against the bit string and the header's zero-run leaves against the records; the string's bits booked as codes and padding."""
+    zero_leaves = settings["n_zero_leaves"]
     if (total + 31) // 32 != n_words:
         raise ValueError(f"zstream: the run lengths of the records add up to {total} bits, the bit string has {n_words} words")
     if zero_leaves > zeros or (zero_leaves == 0) != (zeros == 0) or (settings["zero_parse"] == "single" and zero_leaves != zeros):
         raise ValueError(f"zstream: the header announces {zero_leaves} zero-run leaves ({settings['zero_parse']}), the records hold {zeros} zero elements")
     cur.bits["padding"] = 32 * n_words - total
     cur.bits["symbol_bits"] = total
-    cur.bits["header"] += 8 * (_PREFIX.size + 4)           # magic, version, length and the CRC
-    return ZStream(settings, lengths, records, words), cur.bits, len(blob), zeros
 
 
 def read(path_or_buffer):

@@ -632,6 +632,32 @@ int bnerv_huff_dequant(void* stream, const uint32_t* words, size_t n_words, cons
                        const bnerv_huff_item* items, int n_items, const unsigned char* lengths_host, int R, int* err);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Temporal post-hoc file: inter-coded frame embeddings under Huffman codes of their own (additive to ABI 9; csrc/hufft.hip and
+ * csrc/huff.hip; boosting_nerv_amd/pstream.py).  All three are device entry points of ONE launch each; every sum is an
+ * integer, so no result depends on the order in which blocks arrive.
+ *
+ *   bnerv_embed_delta_u8   q: n_frames rows of P uint8 codes, q_pitch bytes apart, at any byte alignment.  d[t][p] = (q[t][p] - q[t-1][p]) mod 256
+ *                        for t >= 1 (row 0 of d is not written), rows d_pitch apart, and hist[t][0][s] = the number of p with q[t][p] == s,
+ *                        hist[t][1][s] = the number with d[t][p] == s (hist[0][1] stays zero).  The entry point zeroes `hist`
+ *                        (n_frames * 2 * 256 uint32) on the stream.  A thread owns 16 consecutive bytes of a row and takes each of its three
+ *                        accesses as wide as that address allows; a block counts in LDS and adds its non-zero bins with one integer atomic each.
+ *   bnerv_huff_decode_u8   bnerv_huff_dequant with a byte store:  items[k].out[i] = q[i], the symbols a run holds; the same kernel body, the
+ *                        same descriptors of runs, the same error bit.  Rows may start at any byte.
+ *   bnerv_embed_chain_dequant_u8   sym: n_frames rows of P uint8, sym_pitch apart.  q_0 = sym_0;  q_t = pred[t] ? (q_{t-1} + sym_t) mod 256 : sym_t
+ *                        (pred[0] is not read as a prediction: callers refuse a file that sets it);
+ *                            out[t][p] = float(min[s]) + float(scale[s]) * float(q_t[p]),   s = (i / (red * inner)) * inner + i % inner,  i = t * P + p,
+ *                        product and sum one fp32 operation each, rows out_pitch floats apart; min / scale: device arrays of
+ *                        n_frames * P / red entries of `dtype` (BNERV_HUFF_F32 | BNERV_HUFF_F16).  A block serves BNERV_CHAIN_SEG frames,
+ *                        starting from the nearest frame at or before them that is not predicted.  Nothing can leave its range: there is
+ *                        no error word. */
+typedef struct { unsigned char* out; unsigned n; } bnerv_huff_item_u8;
+int bnerv_embed_delta_u8(void* stream, const unsigned char* q, size_t q_pitch, int n_frames, size_t P, unsigned char* d, size_t d_pitch, uint32_t* hist);
+int bnerv_huff_decode_u8(void* stream, const uint32_t* words, size_t n_words, const bnerv_huff_run* runs, size_t n_runs,
+                         const bnerv_huff_item_u8* items, int n_items, const unsigned char* lengths_host, int R, int* err);
+int bnerv_embed_chain_dequant_u8(void* stream, const unsigned char* sym, size_t sym_pitch, const unsigned char* pred, const void* min, const void* scale,
+                                 int dtype, unsigned red, unsigned inner, int n_frames, size_t P, float* out, size_t out_pitch);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Huffman coder of the SPARSE post-hoc quantised model (additive to ABI 9; csrc/huffz.cpp on the host, csrc/huffz.hip on the device;
  * boosting_nerv_amd/zstream.py).  Bit order, canonical codes, descriptors and item table are those of the coder above.
  *

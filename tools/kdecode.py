@@ -37,7 +37,13 @@ temporal file decodes to the parameters, the embeddings and the first and last f
 ONE process: the seeded C1 model pruned by global magnitude to --sparsity (default 0.4), quantised once with quant_tensor (the .bnrq file)
 and once with quant_tensor_sparse (the .bnrz file); model-ready of both files alternated, eager and graph; then the two decode launches
 alone under HIP events (ops.HuffDequant.launch / ops.HuffzDequant.launch, 20 launches replayed from a graph each, alternated over the rounds).
-usage: python tools/kdecode.py --bitstream [--posthoc [--sparse [--sparsity S]]|--chunked|--wide|--temporal] [--frames 16] [--rounds 3] [--only c1q|c5|pack]   (needs the GPU)"""
+--bitstream --posthoc --temporal times the temporal post-hoc file (pstream.py) against the .bnrq file of the same evaluation on
+the seeded H1 model of tools/kencode.py --posthoc over --frames consecutive 1080p frames: codec.Decoder ready times of both kinds alternated in one
+process; the launches -- ops.HuffDequant over the whole .bnrq file, then over the tensor section alone, ops.HuffDecodeU8 per bit string,
+ops.EmbedChainDequantU8, and the encoder's ops.EmbedDeltaU8 -- each from a graph; and a check that both files decode to the same parameters,
+embeddings and first and last frame.
+
+usage: python tools/kdecode.py --bitstream [--posthoc [--sparse [--sparsity S]|--temporal]|--chunked|--wide|--temporal] [--frames 16] [--rounds 3] [--only c1q|c5|pack]   (needs the GPU)"""
 import argparse
 import io
 import os
@@ -505,6 +511,61 @@ def run_temporal(n_frames, rounds):
     print(f"{label}: the BNRT file decodes to the parameters, the embeddings and the first and last frame of its version-1 file", flush=True)
 
 
+def run_posthoc_temporal(n_frames, rounds):
+    import numpy as np
+    import torch
+    from kencode import describe_posthoc_pair, h1_posthoc
+    from boosting_nerv_amd import codec, ops, pstream, qstream
+    dev = torch.device("cuda:0")
+    model, args, records, quant_embed = h1_posthoc(n_frames, dev)
+    fq, fp = io.BytesIO(), io.BytesIO()
+    bq = codec.encode_posthoc(model, args, records, quant_embed, fq)
+    bp = codec.encode_posthoc(model, args, records, quant_embed, fp, temporal=True)
+    fq, fp = fq.getvalue(), fp.getvalue()
+    label = f"H1 seeded, frames 100..{100 + n_frames - 1} at 1080p"
+    describe_posthoc_pair(label, bq, bp)
+    ready = {"posthoc": [], "posthoc_temporal": []}
+    for _ in range(max(rounds, 3) + 1):                        # (the first pair apart: code objects)
+        for kind, blob in (("posthoc", fq), ("posthoc_temporal", fp)):
+            torch.cuda.synchronize()
+            t0 = time.time()
+            dec = codec.Decoder(blob, dev, use_graph=False)
+            torch.cuda.synchronize()
+            ready[kind].append(time.time() - t0)
+            assert dec.kind == kind
+            del dec
+    a, b = ready["posthoc"], ready["posthoc_temporal"]
+    print(f"{label}: Decoder ready (file bytes in memory -> model and embeddings on the device, eager frame loop): .bnrq {min(a[1:]) * 1e3:.1f} ms best, "
+          f"{max(a[1:]) * 1e3:.1f} worst of {len(a) - 1} | .bnrp {min(b[1:]) * 1e3:.1f} ms best, {max(b[1:]) * 1e3:.1f} worst (first calls {a[0] * 1e3:.0f}, "
+          f"{b[0] * 1e3:.0f} ms)", flush=True)
+    qs, ps = qstream.read(fq), pstream.read(fp)
+    e = ps.embeds
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)      # noqa: E731
+    item = lambda r: (torch.empty(r.count, device=dev), up(r.min), up(r.scale), r.red, r.inner, r.run_bits)      # noqa: E731
+    P = int(np.prod(e.shape[1:]))
+    held, out = torch.empty(n_frames, P, dtype=torch.uint8, device=dev), torch.empty(n_frames, P, device=dev)
+    plans = [("ops.HuffDequant, the whole .bnrq file", ops.HuffDequant(qs.words, qs.lengths, [item(r) for r in qs.records])),
+             ("ops.HuffDequant, tensor section", ops.HuffDequant(ps.words, ps.lengths, [item(r) for r in ps.records]))]
+    for kind, lengths, words, name in ((pstream.INTRA, e.lengths0, e.words0, "intra"), (pstream.INTER, e.lengths1, e.words1, "inter")):
+        rows = np.flatnonzero(e.pred == kind)
+        if rows.size:
+            plans.append((f"ops.HuffDecodeU8, {rows.size} {name} frames", ops.HuffDecodeU8(words, lengths, [(held[int(t)], e.run_bits[int(t)]) for t in rows])))
+    plans.append(("ops.EmbedChainDequantU8", ops.EmbedChainDequantU8(held, e.pred, up(e.min), up(e.scale), e.red, e.inner, out)))
+    plans.append(("ops.EmbedDeltaU8 (encoder)", ops.EmbedDeltaU8(quant_embed["quant"].reshape(n_frames, -1))))
+    for _, p in plans:
+        p.launch().check()
+    assert np.array_equal(pstream.decode_embeds(ps), quant_embed["quant"].reshape(n_frames, -1).cpu().numpy())
+    times = time_graph([p.launch for _, p in plans], reps=50, rounds=max(rounds, 3))
+    for (name, p), (best, worst) in zip(plans, times):
+        p.check()
+        print(f"{label} launch, {name}: {best:.1f} us best, {worst:.1f} worst per launch", flush=True)
+    a, b = codec.Decoder(fp, dev, use_graph=False), codec.Decoder(fq, dev, use_graph=False)
+    assert a.kind == "posthoc_temporal" and all(torch.equal(x, y) for x, y in zip(a.model.state_dict().values(), b.model.state_dict().values()))
+    assert torch.equal(a.embeds, b.embeds) and torch.equal(a.embeds.view(n_frames, -1), out)
+    assert torch.equal(a.decode_f32(0), b.decode_f32(0)) and torch.equal(a.decode_f32(n_frames - 1), b.decode_f32(n_frames - 1))
+    print(f"{label}: the .bnrp file decodes to the parameters, the embeddings and the first and last frame of its .bnrq file", flush=True)
+
+
 def forward_rates(cfg):
     """Decode (forward-only) rate of a bench.py decoder (c1 | c3 | c4) on the HIP path: frames/s for single-frame decodes under
     torch.no_grad(), eager and as a captured hipGraph (N4 row: the figure the reference logs as "FPS" in evaluate())."""
@@ -557,7 +618,7 @@ def main():
     ap.add_argument("--posthoc", action="store_true", help="with --bitstream: the post-hoc quantised file of the regression path (C1 model)")
     ap.add_argument("--chunked", action="store_true", help="with --bitstream: the version-1 CEM file against the chunked file of the same model (c1q, c5)")
     ap.add_argument("--wide", action="store_true", help="with --bitstream: the decode kernel of the wide kind against the narrow one (c1q)")
-    ap.add_argument("--temporal", action="store_true", help="with --bitstream: the temporal kind against the wide kind of the same run (c5)")
+    ap.add_argument("--temporal", action="store_true", help="with --bitstream: the temporal kind against the wide kind of the same run (c5); with --posthoc: the temporal post-hoc kind against .bnrq (H1)")
     ap.add_argument("--sparse", action="store_true", help="with --bitstream --posthoc: the sparse file against the dense file of the same pruned C1 model")
     ap.add_argument("--sparsity", type=float, default=0.4, help="with --sparse: the global magnitude sparsity the model is pruned to")
     ap.add_argument("--frames", type=int, default=16)
@@ -568,6 +629,9 @@ def main():
     assert torch.cuda.is_available(), "kdecode needs the GPU"
     if not a.bitstream:
         forward_rates(a.cfg)
+        return 0
+    if a.posthoc and a.temporal:
+        run_posthoc_temporal(a.frames, a.rounds)
         return 0
     if a.posthoc and a.sparse:
         run_posthoc_sparse(a.frames, a.rounds, a.sparsity)

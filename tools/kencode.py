@@ -5,6 +5,7 @@
     python tools/kencode.py --wide [--rounds 3]                            the wide kind (BNRW) on c1q: kernels against the narrow ones
     python tools/kencode.py --temporal [--frames 16] [--rounds 3]          the temporal kind (BNRT) against the wide kind on c5: sizes, encode times
     python tools/kencode.py --temporal --trained tiny|c5 [--frames 16] [--epochs E]     the same sizes of a trained model
+    python tools/kencode.py --posthoc [--epochs E]                         the temporal post-hoc kind (BNRP) against .bnrq / .bnrz: sizes
 
 Seeded cases, in ONE process:
   sizes   the version-1 file (BNRV), the chunked file (BNRC) and the file with per-record tables (BNRE) at runs 256 and 1024; how many
@@ -27,6 +28,10 @@ clock, every call ending in a device synchronisation; the temporal file against 
 embedding bits per frame (words, record bytes, pred byte) and how many frames are coded as differences.  With --trained tiny: the README's
 tiny recipe; with --trained c5: the C3 regression recipe for --epochs epochs on --frames frames, then one rate-distortion epoch of the c5 recipe
 from that checkpoint -- sizes from the version-1 file either way.
+--posthoc: the temporal POST-HOC file (pstream.py) against the .bnrq and .bnrz file of the same evaluation, sizes only: the
+README's tiny HNeRV recipe trained for --epochs epochs (train_nerv_all.main --bitstream, then --eval_only for the other kinds), and the seeded
+H1 model (regression/bunny/hnerv.sh's HNeRV with the strides 5 3 2 2 2 of the 1080p recipes: a 16 x 9 x 16 embedding) over 16 and 64 CONSECUTIVE
+frames of the 600-frame 1080p synthetic clip; per file the bytes, the frames coded as differences and the bits of an intra and an inter frame.
 Both --trained cases write the version-1 file; the other kinds are made from it on the host (codec.repack: the bytes of the device path, tests/test_gpu_estream.py).
 (needs the GPU)"""
 import argparse
@@ -345,11 +350,76 @@ def run_trained(which, epochs, cem_epochs=None):
             os.chdir(cwd)
 
 
+def h1_posthoc(n_frames, dev, sparse=False):
+    """The seeded H1 model at 1080p with evaluate()'s records for its post-hoc twin over n_frames consecutive frames -> (model, args, records,
+    quant_embed)."""
+    import copy
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hnerv_ref
+    from boosting_nerv_amd import train_nerv_all as T
+    from boosting_nerv_amd.hnerv_utils import quant_tensor
+    args = copy.copy(hnerv_ref.h1_args())
+    args.__dict__.update(enc_strds=[5, 3, 2, 2, 2], dec_strds=[5, 3, 2, 2, 2], quant_model_bit=8, quant_embed_bit=6, crop_list="1080_1920",
+                         final_size=1080 * 1920, full_data_length=n_frames, batchSize=1, bitstream_sparse=sparse)
+    torch.manual_seed(1)
+    model = T.build_model(args).to(dev)
+    frames = consecutive_frames(n_frames, 1080, 1920, dev)
+    with torch.no_grad():
+        (plain, _), records = T.quant_model(model, args)
+        plain.eval()
+        embeds = [plain(frames[i:i + 1], None, norm_idx=torch.tensor([(i + 1) / n_frames], dtype=torch.float64, device=dev))[1][0] for i in range(n_frames)]
+        quant_embed, _ = quant_tensor(torch.cat(embeds, 0), args.quant_embed_bit)
+    return model, args, records, quant_embed
+
+
+def describe_posthoc_pair(label, plain, temporal):
+    """One line: a temporal budget (pstream.info) against the budget of the plain file of the same records."""
+    per = lambda bits, n: f"{bits / n:.0f}" if n else "-"      # noqa: E731
+    extra = temporal["embed_symbol_bits"] + temporal["embed_run_index"] + temporal["embed_side"] + temporal["embed_tables"]
+    print(f"{label}: plain {plain['bytes']} bytes, temporal {temporal['bytes']} bytes (ratio {temporal['bytes'] / plain['bytes']:.4f}); "
+          f"{temporal['n_inter_frames']} of {temporal['n_inter_frames'] + temporal['n_intra_frames']} frames as differences; code bits per frame: intra "
+          f"{per(temporal['intra_frame_bits'], temporal['n_intra_frames'])}, inter {per(temporal['inter_frame_bits'], temporal['n_inter_frames'])}; "
+          f"embedding section {extra} bits of {temporal['total']}", flush=True)
+
+
+def run_posthoc(epochs):
+    import torch
+    from boosting_nerv_amd import codec
+    from boosting_nerv_amd import train_nerv_all as T
+    dev = torch.device("cuda:0")
+    recipe = ("--model HNeRV --optim_type Adam --conv_type convnext pshuffel --act gelu --norm none --loss L2 --enc_strds 5 2 2 --enc_dim 16_4 --dec_strds 5 2 2 "
+              "--ks 0_1_5 --reduce 1.2 --dec_blks 1 1 1 --lr 0.001 --data_path synthetic:4x180x320 --vid tiny --crop_list 180_320 --resize_list -1 --modelsize 0.05 "
+              f"--lower_width 6 -b 1 --eval_freq {epochs} -p 2 -e {epochs} --outf t")
+    here = os.getcwd()
+    with tempfile.TemporaryDirectory() as tmp:
+        os.chdir(tmp)
+        try:
+            T.main((recipe + " --not_resume --bitstream t.bnrp --bitstream_temporal").split())
+            T.main((recipe + " --eval_only --bitstream t.bnrq").split())
+            T.main((recipe + " --eval_only --bitstream s.bnrp --bitstream_sparse --bitstream_temporal").split())
+            T.main((recipe + " --eval_only --bitstream s.bnrz --bitstream_sparse").split())
+            budgets = {k: codec.info(os.path.join(tmp, k)) for k in ("t.bnrp", "t.bnrq", "s.bnrp", "s.bnrz")}
+        finally:
+            os.chdir(here)
+    describe_posthoc_pair(f"tiny HNeRV recipe, {epochs} epochs, dense (.bnrq)", budgets["t.bnrq"], budgets["t.bnrp"])
+    describe_posthoc_pair(f"tiny HNeRV recipe, {epochs} epochs, sparse (.bnrz)", budgets["s.bnrz"], budgets["s.bnrp"])
+    for n in (16, 64):
+        for sparse in (False, True):
+            model, args, records, quant_embed = h1_posthoc(n, dev, sparse)
+            plain, temporal = io.BytesIO(), io.BytesIO()
+            bp = codec.encode_posthoc(model, args, records, quant_embed, plain)
+            bt = codec.encode_posthoc(model, args, records, quant_embed, temporal, temporal=True)
+            describe_posthoc_pair(f"H1 seeded, frames 100..{100 + n - 1} at 1080p, {'sparse (.bnrz)' if sparse else 'dense (.bnrq)'}", bp, bt)
+            print(f"    {codec.describe_any(bt)}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", choices=["c1q", "c5"], default=None)
     ap.add_argument("--trained", choices=["tiny", "c1", "c5"], default=None, help="c5: with --temporal only")
     ap.add_argument("--temporal", action="store_true", help="the temporal kind against the wide kind (c5; with --trained: tiny or c5)")
+    ap.add_argument("--posthoc", action="store_true", help="the temporal post-hoc kind (BNRP) against .bnrq / .bnrz: tiny recipe trained, H1 seeded")
     ap.add_argument("--epochs", type=int, default=30)
     ap.add_argument("--cem_epochs", type=int, default=None, help="--trained c1: rate-distortion epochs (default: --epochs // 2)")
     ap.add_argument("--wide", action="store_true", help="the encode kernels of the wide kind against the narrow ones (c1q)")
@@ -359,6 +429,9 @@ def main():
     a = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "kencode needs the GPU"
+    if a.posthoc:
+        run_posthoc(a.epochs)
+        return 0
     if a.temporal:
         if a.trained:
             assert a.trained in ("tiny", "c5"), "--temporal --trained takes tiny or c5 (C1 has no frame embeddings)"
