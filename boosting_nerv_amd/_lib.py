@@ -53,6 +53,22 @@ class TimeBranchDesc(C.Structure):
                 ("B", C.c_int), ("L", C.c_int), ("SH", C.c_int), ("TH", C.c_int), ("TO", C.c_int), ("n_mlp", C.c_int)]
 
 
+class TimeBranchBwdMlp(C.Structure):
+    _fields_ = [("w1", _fp), ("w2", _fp), ("hs", _fp), ("d_out", _fp), ("dw1", _fp), ("db1", _fp), ("dw2", _fp), ("db2", _fp),
+                ("C", C.c_int), ("_pad", C.c_int)]
+
+
+class TimeBranchBwdDesc(C.Structure):
+    _fields_ = [("pe", _fp), ("sw1", _fp), ("sy0", _fp), ("saux0", _fp), ("saux1", _fp), ("d_sy1", _fp),
+                ("tw1", _fp), ("ty0", _fp), ("taux0", _fp), ("ty1", _fp), ("taux1", _fp), ("d_ty1", _fp),
+                ("d_sw0", _fp), ("d_sb0", _fp), ("d_sw1", _fp), ("d_sb1", _fp), ("d_tw0", _fp), ("d_tb0", _fp), ("d_tw1", _fp), ("d_tb1", _fp),
+                ("sx_part", _fp), ("zt_part", _fp), ("s_dpre", _fp),
+                ("B", C.c_int), ("L", C.c_int), ("SH", C.c_int), ("SO", C.c_int), ("TH", C.c_int), ("TO", C.c_int), ("n_mlp", C.c_int), ("_pad", C.c_int)]
+
+
+TIME_BRANCH_BWD_MLP_BYTES, TIME_BRANCH_BWD_DESC_BYTES = 72, 216      # include/bnerv.h: BNERV_TIME_BRANCH_BWD_*_BYTES
+
+
 class WgradDesc(C.Structure):
     _fields_ = [("x", _fp), ("g", _fp), ("gaux", _fp), ("scale", _fp), ("shift", _fp), ("dw", _fp), ("db", _fp),
                 ("ws", _fp), ("ws_bytes", C.c_size_t),
@@ -204,6 +220,7 @@ SYMBOLS = {
     "bnerv_pe_fwd_f32_from_f64": (_I, [_V, _V, _V, _V, _I, _I]),
     "bnerv_dense_grouped_fwd": (_I, [_V, C.POINTER(DenseFwdDesc), _I, _I]),
     "bnerv_time_branch_fwd": (_I, [_V, C.POINTER(TimeBranchDesc), C.POINTER(TimeBranchMlp)]),
+    "bnerv_time_branch_bwd": (_I, [_V, C.POINTER(TimeBranchBwdDesc), C.POINTER(TimeBranchBwdMlp)]),
     "bnerv_dense_grouped_bwd": (_I, [_V, C.POINTER(DenseBwdDesc), _I, _I]),
     "bnerv_sft_affine_fwd": (_I, [_V, _V, _V, _V, _V, _I, _I, _I]),
     "bnerv_sft_affine_bwd": (_I, [_V, _V, _V, _V, _V, _V, _I, _I, _I]),

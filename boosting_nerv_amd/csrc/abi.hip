@@ -41,10 +41,7 @@ SideJob make_job(const void* src, int n_slabs, int count, int ncols, float* out,
     j.n_slabs = n_slabs;
     j.count = count;
     j.ncols = ncols;
-    // lanes >= n_slabs / 16 (one batch of 16 loads per thread when possible), power of two in [8, 128]
-    int lanes = 8;
-    while (lanes < 128 && lanes * 16 < n_slabs) lanes *= 2;
-    j.epb = 256 / lanes;
+    j.epb = side_epb(n_slabs);
     j.slices = (count + j.epb - 1) / j.epb;
     return j;
 }

@@ -75,8 +75,9 @@ struct BwdArgs { bnerv_dense_bwd_desc g[BNERV_MAX_DENSE_GROUPS]; int B; };
 // split over blockIdx.z in chunks of DW_CHUNK columns -- a single wave walking the whole row is a serial chain of ~140 dependent
 // load/store rounds (70 us per launch at C4); 4 independent columns per lane and round keep the loads in flight.
 constexpr int DW_CHUNK = 1024;
-__device__ __forceinline__ void dense_bwd_w_body(const BwdArgs& a, const int bx, const int by, const int bz) {
-    const BwdArgs* ap = &a;
+template <class Args>      // BwdArgs, or the one-group table of the time-branch backward
+__device__ __forceinline__ void dense_bwd_w_body(const Args& a, const int bx, const int by, const int bz) {
+    const Args* ap = &a;
     const bnerv_dense_bwd_desc g = a.g[by];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int o = bx * 4 + wave;
@@ -89,7 +90,7 @@ __device__ __forceinline__ void dense_bwd_w_body(const BwdArgs& a, const int bx,
             const size_t k = (size_t)b * g.O + o;
             float dp = g.dy[k];
             if (g.act == BNERV_ACT_RELU) dp = g.y[k] > 0.f ? dp : 0.f;
-            else if (g.act == BNERV_ACT_SIN) dp *= g.aux[k];
+            else if (g.act == BNERV_ACT_SIN) dp = __fmul_rn(dp, g.aux[k]);      // (rounded: never contracted into the sums below, in any instantiation)
             if (lane == 0) g.dpre[k] = dp;
             dbsum += dp;
         }
@@ -102,7 +103,7 @@ __device__ __forceinline__ void dense_bwd_w_body(const BwdArgs& a, const int bx,
             const size_t k = (size_t)b * g.O + o;
             float dp = g.dy[k];
             if (g.act == BNERV_ACT_RELU) dp = g.y[k] > 0.f ? dp : 0.f;
-            else if (g.act == BNERV_ACT_SIN) dp *= g.aux[k];
+            else if (g.act == BNERV_ACT_SIN) dp = __fmul_rn(dp, g.aux[k]);      // (rounded: never contracted into the sums below, in any instantiation)
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int i = ib + 64 * u;
@@ -119,8 +120,9 @@ __device__ __forceinline__ void dense_bwd_w_body(const BwdArgs& a, const int bx,
 
 // phase 2: dx_part[chunk][b][i] = sum_{o in chunk} dpre[b][o] * w[o][i]      (threads over i: coalesced rows of w).  dpre is rebuilt
 // from dy and the saved activation here (one value per row), so the two phases do not depend on each other and share ONE launch.
-__device__ __forceinline__ void dense_bwd_x_body(const BwdArgs& a, const int bx, const int by, const int bz) {
-    const BwdArgs* ap = &a;
+template <class Args>
+__device__ __forceinline__ void dense_bwd_x_body(const Args& a, const int bx, const int by, const int bz) {
+    const Args* ap = &a;
     const bnerv_dense_bwd_desc g = a.g[bz];
     if (!g.dx_part) return;
     const int chunk = bx;
@@ -135,7 +137,7 @@ __device__ __forceinline__ void dense_bwd_x_body(const BwdArgs& a, const int bx,
             const size_t k = (size_t)b * g.O + o0 + threadIdx.x;
             dp = g.dy[k];
             if (g.act == BNERV_ACT_RELU) dp = g.y[k] > 0.f ? dp : 0.f;
-            else if (g.act == BNERV_ACT_SIN) dp *= g.aux[k];
+            else if (g.act == BNERV_ACT_SIN) dp = __fmul_rn(dp, g.aux[k]);      // (rounded: never contracted into the sums below, in any instantiation)
         }
         s_dp[threadIdx.x] = dp;
     }
@@ -269,7 +271,8 @@ extern "C" int bnerv_pe_fwd_f64(void* stream, const double* pos, const float* ba
 //     level and was slower than the launches it replaced); PE meanwhile; then stem_t layer 0 -> layer 1 -> the block's MLPs
 //     from LDS.  Chain block 0 also writes PE and stem_t's outputs.
 // The stem's second layer follows as the ordinary grouped launch: 5 launches -> 2.  Every tensor the five-launch form left behind is written,
-// so the backward (bnerv_dense_grouped_bwd x 4) is unchanged.  A row here is 16 lanes x strided fma chains + 4 shuffle steps, in the grouped
+// so either backward can follow: the two launches of bnerv_time_branch_bwd (below; the default) or the grouped form they were derived from
+// (bnerv_dense_grouped_bwd x 4 + a flush), which reads the same tensors and gives the same bits.  A row here is 16 lanes x strided fma chains + 4 shuffle steps, in the grouped
 // kernel a wave-strided sum: same quantities, last-bit differences.
 struct TBMlp { const float* w1; const float* b1; const float* w2; const float* b2; float* hs; float* out; int C; int _pad; };
 struct TBArgs {
@@ -437,6 +440,270 @@ __global__ __launch_bounds__(TB_NT) void time_branch_kernel(const TBArgs a) {
               [&](int k, int r, int b, float v) { a.m[m0 + k].out[(size_t)b * a.m[m0 + k].C + r] = v; });
 }
 
+// ---------------------------------------------------------------- the backward of that branch as TWO launches
+// The grouped backward ran it as five dependent launches -- [every MLP's layer 1 | the stem's layer 1] -> [every MLP's layer 0] -> a flush of
+// two input-gradient reductions -> [stem_t layer 1 | stem layer 0] -> [stem_t layer 0] -- of which only the stem's layer 1 moves data (4.4 MB
+// read, 4.4 MB written); the rest costs what a dependent launch costs.  Only two dependency levels cross blocks: the sum of the per-MLP d z_t
+// slabs feeds stem_t, the sum of the stem's dx chunk slabs feeds the stem's layer 0.  Those two are the launch boundary between
+//   launch A: the stem's layer 1 (dense_bwd_w_body / dense_bwd_x_body, unchanged)  |  one block per modulation MLP: both layers, dh and the
+//             pre-activation gradients never leave the block;
+//   launch B: 32 rows of the stem's layer 0 per block, each block summing the chunk slabs of its own rows  |  ONE chain block: the slab sum
+//             of d z_t, stem_t layer 1, stem_t layer 0.
+// No block waits on another block of its launch.  Bits: every dw is dense_bwd_w_body's fmaf chain over b, every dx dense_bwd_x_body's fmaf
+// chain over the 64 (zero-padded) rows of a chunk, every db the sequential sum over b of the ROUNDED pre-activation gradient (__fmul_rn: no
+// contraction into the sum -- the grouped kernel multiplies, then adds), and the cross-block sums are tbb_slab_sum = side_slice's order.
+struct Bwd1Args { bnerv_dense_bwd_desc g[1]; int B; };
+struct TBBMlp { const float* w1; const float* w2; const float* hs; const float* dout; float* dw1; float* db1; float* dw2; float* db2; int C; int _pad; };
+constexpr int TBB_MAX_MLP = BNERV_MAX_DENSE_GROUPS - 1;      // the five-launch form's limit: n_mlp + 1 groups in one grouped launch
+struct TBBArgsA {
+    Bwd1Args stem;
+    TBBMlp m[TBB_MAX_MLP];
+    const float* zt;        // [B, TO]
+    float* zt_part;         // [n_mlp, B, TO]
+    int nw, wx, nx, xx;     // stem row blocks (wx per column chunk), stem chunk blocks (xx per b)
+    int n_mlp, TO;
+};
+struct TBBArgsB {
+    const float* pe; const float* saux0; const float* sx_part;
+    const float* zt_part; const float* d_ty1; const float* taux1; const float* ty0; const float* tw1; const float* taux0;
+    float* d_sw0; float* d_sb0; float* d_tw1; float* d_tb1; float* d_tw0; float* d_tb0;
+    int B, I, SH, TH, TO, n_sx, n_mlp, nb_stem, epb_sx, epb_zt;
+};
+static_assert(sizeof(TBBMlp) == BNERV_TIME_BRANCH_BWD_MLP_BYTES && sizeof(bnerv_time_branch_bwd_mlp) == BNERV_TIME_BRANCH_BWD_MLP_BYTES, "time branch backward: MLP entry");
+static_assert(sizeof(bnerv_time_branch_bwd_desc) == BNERV_TIME_BRANCH_BWD_DESC_BYTES, "time branch backward: descriptor");
+static_assert(sizeof(TBBArgsA) <= 4096 && sizeof(TBBArgsB) <= 4096, "time branch backward: kernel-argument segment");
+constexpr int TBB_NT = 256, TBB_ROWS = 32;      // TBB_ROWS: rows of the stem's layer 0 per block of launch B (a multiple of every epb)
+
+// dense_bwd_x_body runs its fmaf chain over all 64 rows of a chunk, the rows past the layer's last as fmaf(+0, +0, s) = s + (+0): s for every s
+// but -0, which becomes +0, and doing it once is doing it 64 - nr times.  The chains here run over the nr real rows and end with this.
+__device__ __forceinline__ float tbb_pad_rows(const float s, const int nr) { return nr < BNERV_DENSE_DX_CHUNK ? s + 0.f : s; }
+
+// one modulation MLP, both layers:  out = w2 relu(w1 z_t + b1) + b2
+__device__ __forceinline__ void tbb_mod_block(const TBBArgsA& a, const int mi) {
+    __shared__ float s_w2[TB_MAXC * TB_MAXO], s_w1[TB_MAXO * TB_MAXO];
+    __shared__ float s_dp2[TB_MAXB][TB_MAXC], s_hs[TB_MAXB][TB_MAXO], s_zt[TB_MAXB][TB_MAXO], s_dp1[TB_MAXB][TB_MAXO];
+    __shared__ float s_xp[TB_MAXC / BNERV_DENSE_DX_CHUNK][TB_MAXB][TB_MAXO];
+    const TBBMlp m = a.m[mi];
+    const int tid = threadIdx.x, B = a.stem.B, TO = a.TO, C = m.C;
+    // every global read of the block at once, into registers, then into LDS: one exposed memory latency for the whole two-layer chain
+    constexpr int NW2 = TB_MAXC * TB_MAXO / TBB_NT, NW1 = TB_MAXO * TB_MAXO / TBB_NT, NDP = TB_MAXB * TB_MAXC / TBB_NT;
+    float r_w2[NW2], r_w1[NW1], r_dp[NDP];
+#pragma unroll
+    for (int u = 0; u < NW2; ++u) r_w2[u] = tid + u * TBB_NT < C * TO ? m.w2[tid + u * TBB_NT] : 0.f;
+#pragma unroll
+    for (int u = 0; u < NW1; ++u) r_w1[u] = tid + u * TBB_NT < TO * TO ? m.w1[tid + u * TBB_NT] : 0.f;
+#pragma unroll
+    for (int u = 0; u < NDP; ++u) r_dp[u] = m.dout && tid + u * TBB_NT < B * C ? m.dout[tid + u * TBB_NT] : 0.f;      // (an absent gradient is zeros)
+    const float r_hs = tid < B * TO ? m.hs[tid] : 0.f, r_zt = tid < B * TO ? a.zt[tid] : 0.f;                           // (B * TO <= 128)
+#pragma unroll
+    for (int u = 0; u < NW2; ++u) s_w2[tid + u * TBB_NT] = r_w2[u];
+#pragma unroll
+    for (int u = 0; u < NW1; ++u) s_w1[tid + u * TBB_NT] = r_w1[u];
+#pragma unroll
+    for (int u = 0; u < NDP; ++u)
+        if (tid + u * TBB_NT < B * C) s_dp2[(tid + u * TBB_NT) / C][(tid + u * TBB_NT) % C] = r_dp[u];
+    if (tid < B * TO) { s_hs[tid / TO][tid % TO] = r_hs; s_zt[tid / TO][tid % TO] = r_zt; }
+    __syncthreads();
+    // ---- layer 1 (no activation: dpre2 = d_out)
+    for (int o = tid; o < C; o += TBB_NT) {
+        float s = 0.f;
+        for (int b = 0; b < B; ++b) s += s_dp2[b][o];
+        m.db2[o] = s;
+    }
+    for (int e = tid; e < C * TO; e += TBB_NT) {
+        const int o = e / TO, i = e - o * TO;
+        float s = 0.f;
+        for (int b = 0; b < B; ++b) s = fmaf(s_dp2[b][o], s_hs[b][i], s);
+        m.dw2[e] = s;
+    }
+    const int nch = (C + BNERV_DENSE_DX_CHUNK - 1) / BNERV_DENSE_DX_CHUNK;       // <= 2
+    for (int e = tid; e < nch * B * TO; e += TBB_NT) {
+        const int ch = e / (B * TO), b = (e - ch * B * TO) / TO, i = e % TO;
+        const int o0 = ch * BNERV_DENSE_DX_CHUNK, nr = min(BNERV_DENSE_DX_CHUNK, C - o0);
+        float s = 0.f;
+#pragma unroll 8
+        for (int r = 0; r < nr; ++r) s = fmaf(s_dp2[b][o0 + r], s_w2[(o0 + r) * TO + i], s);
+        s_xp[ch][b][i] = tbb_pad_rows(s, nr);
+    }
+    __syncthreads();
+    // ---- layer 0 (relu).  Two chunks are a two-slab reduction in the five-launch form: slab 0 in lane 0, slab 1 in lane 1, zeros elsewhere
+    for (int e = tid; e < B * TO; e += TBB_NT) {
+        const int b = e / TO, r = e - b * TO;
+        const float dh = nch == 1 ? s_xp[0][b][r] : (0.f + s_xp[0][b][r]) + s_xp[1][b][r];
+        s_dp1[b][r] = s_hs[b][r] > 0.f ? dh : 0.f;
+    }
+    __syncthreads();
+    for (int r = tid; r < TO; r += TBB_NT) {
+        float s = 0.f;
+        for (int b = 0; b < B; ++b) s += s_dp1[b][r];
+        m.db1[r] = s;
+    }
+    for (int e = tid; e < TO * TO; e += TBB_NT) {
+        const int r = e / TO, i = e - r * TO;
+        float s = 0.f;
+        for (int b = 0; b < B; ++b) s = fmaf(s_dp1[b][r], s_zt[b][i], s);
+        m.dw1[e] = s;
+    }
+    for (int e = tid; e < B * TO; e += TBB_NT) {           // this MLP's slab of the d z_t partials
+        const int b = e / TO, i = e - b * TO;
+        float s = 0.f;
+#pragma unroll 8
+        for (int r = 0; r < TO; ++r) s = fmaf(s_dp1[b][r], s_w1[r * TO + i], s);
+        a.zt_part[((size_t)mi * B + b) * TO + i] = tbb_pad_rows(s, TO);
+    }
+}
+
+__global__ __launch_bounds__(TBB_NT) void time_branch_bwd_a_kernel(const TBBArgsA a) {
+    int t = blockIdx.x;                                    // block ranges of one grid: modulation MLPs (the longest chains: first) | stem chunks | stem rows
+    if (t < a.n_mlp) { tbb_mod_block(a, t); return; }
+    t -= a.n_mlp;
+    if (t < a.nx) { dense_bwd_x_body(a.stem, t % a.xx, t / a.xx, 0); return; }
+    t -= a.nx;
+    if (t < a.nw) dense_bwd_w_body(a.stem, t % a.wx, 0, t / a.wx);
+}
+
+// Element i of a slab reduction out[i] = sum_k src[k * count + i] in the order of side_slice (csrc/sidejob.h): thread (e, lane) of an
+// epb x (256 / epb) block sums slabs lane, lane + lanes, ... in batches of 16 combined by the fixed 16-wide tree; lane 0 then adds the
+// lanes' partial sums in sequence and returns the total (other lanes return 0).  In two halves, so that a caller can place its own LDS staging
+// behind the loads: tbb_slab_lane_sum (the loads and the tree), tbb_slab_combine (every thread of the block calls it: two barriers).
+__device__ __forceinline__ float tbb_slab_lane_sum(const float* __restrict__ src, const int n_slabs, const size_t count, const size_t i, const bool live,
+                                                   const int epb) {
+    const int lanes = TBB_NT / epb, lane = threadIdx.x / epb;
+    float acc = 0.f;
+    if (live) {
+        const float* p = src + i;
+        for (int k0 = lane; k0 < n_slabs; k0 += 16 * lanes) {
+            float v[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) {
+                const int k = k0 + u * lanes;
+                v[u] = k < n_slabs ? p[(size_t)k * count] : 0.f;
+            }
+#pragma unroll
+            for (int w = 8; w >= 1; w >>= 1)
+#pragma unroll
+                for (int u = 0; u < w; ++u) v[u] += v[u + w];
+            acc += v[0];
+        }
+    }
+    return acc;
+}
+__device__ __forceinline__ float tbb_slab_combine(const float acc, const bool live, const int epb, float* red) {
+    const int lanes = TBB_NT / epb, e = threadIdx.x % epb, lane = threadIdx.x / epb;
+    red[lane * epb + e] = acc;
+    __syncthreads();
+    float t = 0.f;
+    if (lane == 0 && live)
+        for (int l = 0; l < lanes; ++l) t += red[l * epb + e];
+    __syncthreads();
+    return t;
+}
+
+__global__ __launch_bounds__(TBB_NT) void time_branch_bwd_b_kernel(const TBBArgsB a) {
+    __shared__ float red[TBB_NT];
+    __shared__ float s_pe[TB_MAXB * TB_MAXI];
+    __shared__ float s_d[TB_MAXB][TB_MAXT];                 // pre-activation gradients: the stem's rows of this block / stem_t layer 1
+    __shared__ float s_d0[TB_MAXB][TB_MAXT];                // stem_t layer 0
+    __shared__ float s_ty0[TB_MAXB * TB_MAXT], s_a0[TB_MAXB * TB_MAXT], s_a1[TB_MAXB * TB_MAXO], s_dt[TB_MAXB * TB_MAXO];
+    __shared__ float s_tw1[TB_MAXO * TB_MAXT];
+    const int tid = threadIdx.x, B = a.B, I = a.I, TO = a.TO, TH = a.TH;
+    // EVERY global read of the block's chain is requested before the first wait -- into registers, then behind the first pass's slab loads into
+    // LDS: one exposed memory latency (time_branch_kernel's lesson; a first version read tw1 row by row inside the dx chain: 19 us)
+    float r_pe[TB_MAXB * TB_MAXI / TBB_NT];
+#pragma unroll
+    for (int u = 0; u < TB_MAXB * TB_MAXI / TBB_NT; ++u) r_pe[u] = tid + u * TBB_NT < B * I ? a.pe[tid + u * TBB_NT] : 0.f;
+    if ((int)blockIdx.x < a.nb_stem) {
+        // ---- the stem's layer 0 (sin; the positional encoding has no gradient): rows o0 .. o0 + 31, d_sy0 = the sum of the chunk slabs
+        const int o0 = (int)blockIdx.x * TBB_ROWS, epb = a.epb_sx;
+        const int e = tid % epb, lane = tid / epb;
+        for (int p0 = 0; p0 < B * TBB_ROWS; p0 += epb) {
+            const int idx = p0 + e, b = idx / TBB_ROWS, r = idx - b * TBB_ROWS, o = o0 + r;
+            const bool live = o < a.SH;
+            const size_t k = (size_t)b * a.SH + (live ? o : 0);
+            const float aux = lane == 0 && live ? a.saux0[k] : 0.f;
+            const float acc = tbb_slab_lane_sum(a.sx_part, a.n_sx, (size_t)B * a.SH, k, live, epb);
+            if (p0 == 0) {
+#pragma unroll
+                for (int u = 0; u < TB_MAXB * TB_MAXI / TBB_NT; ++u) s_pe[tid + u * TBB_NT] = r_pe[u];
+            }
+            const float t = tbb_slab_combine(acc, live, epb, red);
+            if (lane == 0 && live) s_d[b][r] = __fmul_rn(t, aux);
+        }
+        __syncthreads();
+        for (int r = tid; r < TBB_ROWS && o0 + r < a.SH; r += TBB_NT) {
+            float s = 0.f;
+            for (int b = 0; b < B; ++b) s += s_d[b][r];
+            a.d_sb0[o0 + r] = s;
+        }
+        for (int e2 = tid; e2 < TBB_ROWS * I; e2 += TBB_NT) {
+            const int r = e2 / I, i = e2 - r * I;
+            if (o0 + r >= a.SH) break;
+            float s = 0.f;
+            for (int b = 0; b < B; ++b) s = fmaf(s_d[b][r], s_pe[b * I + i], s);
+            a.d_sw0[(size_t)(o0 + r) * I + i] = s;
+        }
+        return;
+    }
+    // ---- the chain block: d z_t = sum of the MLPs' slabs (+ the direct gradient), stem_t layer 1 (sin), stem_t layer 0 (sin)
+    {
+        float r_w[TB_MAXO * TB_MAXT / TBB_NT];
+#pragma unroll
+        for (int u = 0; u < TB_MAXO * TB_MAXT / TBB_NT; ++u) r_w[u] = tid + u * TBB_NT < TO * TH ? a.tw1[tid + u * TBB_NT] : 0.f;
+        const float r_y0 = tid < B * TH ? a.ty0[tid] : 0.f, r_a0 = tid < B * TH ? a.taux0[tid] : 0.f;      // (B * TH <= 256 threads, B * TO <= 128)
+        const float r_a1 = tid < B * TO ? a.taux1[tid] : 0.f, r_dt = a.d_ty1 && tid < B * TO ? a.d_ty1[tid] : 0.f;
+        const int epb = a.epb_zt, e = tid % epb, lane = tid / epb;
+        for (int p0 = 0; p0 < B * TO; p0 += epb) {
+            const int idx = p0 + e;
+            const bool live = idx < B * TO;
+            const float acc = tbb_slab_lane_sum(a.zt_part, a.n_mlp, (size_t)B * TO, live ? idx : 0, live, epb);
+            if (p0 == 0) {
+#pragma unroll
+                for (int u = 0; u < TB_MAXB * TB_MAXI / TBB_NT; ++u) s_pe[tid + u * TBB_NT] = r_pe[u];
+#pragma unroll
+                for (int u = 0; u < TB_MAXO * TB_MAXT / TBB_NT; ++u) s_tw1[tid + u * TBB_NT] = r_w[u];
+                s_ty0[tid] = r_y0; s_a0[tid] = r_a0;
+                if (tid < TB_MAXB * TB_MAXO) { s_a1[tid] = r_a1; s_dt[tid] = r_dt; }
+            }
+            const float t = tbb_slab_combine(acc, live, epb, red);          // (its barriers publish what was staged above)
+            if (lane == 0 && live) {
+                const float dz = a.d_ty1 ? t + s_dt[idx] : t;
+                s_d[idx / TO][idx % TO] = __fmul_rn(dz, s_a1[idx]);
+            }
+        }
+    }
+    __syncthreads();
+    for (int r = tid; r < TO; r += TBB_NT) {
+        float s = 0.f;
+        for (int b = 0; b < B; ++b) s += s_d[b][r];
+        a.d_tb1[r] = s;
+    }
+    for (int e = tid; e < TO * TH; e += TBB_NT) {
+        const int r = e / TH, i = e - r * TH;
+        float s = 0.f;
+        for (int b = 0; b < B; ++b) s = fmaf(s_d[b][r], s_ty0[b * TH + i], s);
+        a.d_tw1[e] = s;
+    }
+    for (int e = tid; e < B * TH; e += TBB_NT) {           // dx of layer 1 (one chunk: TO <= 32 rows), straight into layer 0's dpre
+        const int b = e / TH, i = e - b * TH;
+        float s = 0.f;
+#pragma unroll 8
+        for (int r = 0; r < TO; ++r) s = fmaf(s_d[b][r], s_tw1[r * TH + i], s);
+        s_d0[b][i] = __fmul_rn(tbb_pad_rows(s, TO), s_a0[e]);
+    }
+    __syncthreads();
+    for (int r = tid; r < TH; r += TBB_NT) {
+        float s = 0.f;
+        for (int b = 0; b < B; ++b) s += s_d0[b][r];
+        a.d_tb0[r] = s;
+    }
+    for (int e = tid; e < TH * I; e += TBB_NT) {
+        const int r = e / I, i = e - r * I;
+        float s = 0.f;
+        for (int b = 0; b < B; ++b) s = fmaf(s_d0[b][r], s_pe[b * I + i], s);
+        a.d_tw0[e] = s;
+    }
+}
+
 // Descriptor tables travel BY VALUE in the kernel-argument segment (<= 4 KB: BNERV_MAX_DENSE_GROUPS * 88 B), so a captured
 // hipGraph replays them without touching host memory.
 extern "C" int bnerv_dense_grouped_fwd(void* stream, const bnerv_dense_fwd_desc* groups, int n_groups, int B) {
@@ -540,5 +807,46 @@ extern "C" int bnerv_time_branch_fwd(void* stream, const bnerv_time_branch_desc*
     if (const int rc = dyn_lds<&time_branch_kernel>(lds, "time_branch")) return rc;
     hipLaunchKernelGGL(time_branch_kernel, dim3(a.nb_stem + a.nb_chain), dim3(TB_NT), lds, (hipStream_t)stream, a);
     BNERV_LAUNCH_CHECK("time_branch");
+    return BNERV_OK;
+}
+
+// 1: not these launches' branch (the caller issues the five grouped launches); BNERV_OK; negative BNERV_E_*.  Everything is checked before the
+// first device call.
+extern "C" int bnerv_time_branch_bwd(void* stream, const bnerv_time_branch_bwd_desc* dp, const bnerv_time_branch_bwd_mlp* mlps) {
+    BNERV_REQUIRE(dp && mlps, "time_branch_bwd: null descriptor");
+    const bnerv_time_branch_bwd_desc& d = *dp;
+    BNERV_REQUIRE(d.n_mlp > 0, "time_branch_bwd: needs at least one modulation MLP (n_mlp=%d)", d.n_mlp);
+    BNERV_REQUIRE(d.pe && d.sw1 && d.sy0 && d.saux0 && d.saux1 && d.d_sy1 && d.tw1 && d.ty0 && d.taux0 && d.ty1 && d.taux1, "time_branch_bwd: null tensor");
+    BNERV_REQUIRE(d.d_sw0 && d.d_sb0 && d.d_sw1 && d.d_sb1 && d.d_tw0 && d.d_tb0 && d.d_tw1 && d.d_tb1, "time_branch_bwd: null gradient output");
+    BNERV_REQUIRE(d.sx_part && d.zt_part && d.s_dpre, "time_branch_bwd: null scratch");
+    BNERV_REQUIRE(d.B > 0 && d.L > 0 && d.SH > 0 && d.SO > 0 && d.TH > 0 && d.TO > 0, "time_branch_bwd: bad shape");
+    if (d.B > TB_MAXB || 2 * d.L > TB_MAXI || d.SH > 4096 || d.TH > TB_MAXT || d.TO > TB_MAXO || d.n_mlp > TBB_MAX_MLP) return 1;
+    TBBArgsA a{};
+    for (int i = 0; i < d.n_mlp; ++i) {
+        const bnerv_time_branch_bwd_mlp& m = mlps[i];
+        BNERV_REQUIRE(m.w1 && m.w2 && m.hs && m.dw1 && m.db1 && m.dw2 && m.db2 && m.C > 0, "time_branch_bwd: bad modulation MLP %d", i);
+        if (m.C > TB_MAXC) return 1;
+        a.m[i].w1 = m.w1; a.m[i].w2 = m.w2; a.m[i].hs = m.hs; a.m[i].dout = m.d_out;
+        a.m[i].dw1 = m.dw1; a.m[i].db1 = m.db1; a.m[i].dw2 = m.dw2; a.m[i].db2 = m.db2; a.m[i].C = m.C; a.m[i]._pad = 0;
+    }
+    bnerv_dense_bwd_desc& g = a.stem.g[0];                  // the stem's layer 1 as the grouped kernel's group
+    g.x = d.sy0; g.w = d.sw1; g.y = nullptr; g.aux = d.saux1; g.dy = d.d_sy1; g.dpre = d.s_dpre; g.dw = d.d_sw1; g.db = d.d_sb1; g.dx_part = d.sx_part;
+    g.I = d.SH; g.O = d.SO; g.act = BNERV_ACT_SIN; g._pad = 0;
+    a.stem.B = d.B;
+    a.zt = d.ty1; a.zt_part = d.zt_part;
+    a.wx = cdiv(d.SO, 4); a.nw = a.wx * cdiv(d.SH, DW_CHUNK);
+    a.xx = cdiv(d.SO, BNERV_DENSE_DX_CHUNK); a.nx = a.xx * d.B;
+    a.n_mlp = d.n_mlp; a.TO = d.TO;
+    TBBArgsB b;
+    b.pe = d.pe; b.saux0 = d.saux0; b.sx_part = d.sx_part; b.zt_part = d.zt_part; b.d_ty1 = d.d_ty1; b.taux1 = d.taux1; b.ty0 = d.ty0; b.tw1 = d.tw1;
+    b.taux0 = d.taux0; b.d_sw0 = d.d_sw0; b.d_sb0 = d.d_sb0; b.d_tw1 = d.d_tw1; b.d_tb1 = d.d_tb1; b.d_tw0 = d.d_tw0; b.d_tb0 = d.d_tb0;
+    b.B = d.B; b.I = 2 * d.L; b.SH = d.SH; b.TH = d.TH; b.TO = d.TO; b.n_sx = a.xx; b.n_mlp = d.n_mlp;
+    b.nb_stem = cdiv(d.SH, TBB_ROWS);
+    b.epb_sx = side_epb(b.n_sx); b.epb_zt = side_epb(b.n_mlp);          // what bnerv_side_push chooses for the same two reductions
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(time_branch_bwd_a_kernel, dim3(a.nw + a.nx + a.n_mlp), dim3(TBB_NT), 0, st, a);
+    BNERV_LAUNCH_CHECK("time_branch_bwd_a");
+    hipLaunchKernelGGL(time_branch_bwd_b_kernel, dim3(b.nb_stem + 1), dim3(TBB_NT), 0, st, b);
+    BNERV_LAUNCH_CHECK("time_branch_bwd_b");
     return BNERV_OK;
 }

@@ -33,7 +33,13 @@ struct SidePack {
     SideJob j[SIDE_MAX_JOBS];
     int n_jobs, n_slices;
 };
-constexpr int SIDE_FLUSH_JOBS = 32;    // the stand-alone flush takes many more jobs per launch (it is all the launch does)
+// elements per slice of a job over n_slabs slabs: lanes >= n_slabs / 16 (one batch of 16 loads per thread when possible), power of two in [8, 128]
+static inline int side_epb(int n_slabs) {
+    int lanes = 8;
+    while (lanes < 128 && lanes * 16 < n_slabs) lanes *= 2;
+    return 256 / lanes;
+}
+constexpr int SIDE_FLUSH_JOBS = 32;   // the stand-alone flush takes many more jobs per launch (it is all the launch does)
 struct SideFlushPack {
     SideJob j[SIDE_FLUSH_JOBS];
     int n_jobs, n_slices;

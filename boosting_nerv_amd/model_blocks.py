@@ -146,7 +146,8 @@ def mlp_pair_forward(mlps, xs):
 
 def time_branch_forward(pe_t, pos, stem, stem_t, sft_layers):
     """NeRV_Boost's time-embedding branch -- pe_t(pos), the stem and stem_t MLPs on it, and the (scale, shift) modulations of every SFTLayer
-    in ``sft_layers`` from stem_t's output (model_nerv.py:47-51, model_blocks.py:92-105) -- as TWO launches (ops.time_branch) instead of five.
+    in ``sft_layers`` from stem_t's output (model_nerv.py:47-51, model_blocks.py:92-105) -- as TWO launches (ops.time_branch) instead of five; its backward is two launches as
+    well (ops._TimeBranch.backward, bnerv_time_branch_bwd) instead of five, with the same bits.
     Returns (stem_out [B, C, 1, 1], t_embed [B, ch_t, 1, 1], [(scale_i, shift_i)]) or None when the branch is not the kernel's (other
     activations, more than 4 frames per step, no positional encoding, quantised containers): the caller takes the layer-by-layer path."""
     if "pe" not in pe_t.pe_embed or len(stem) != 4 or len(stem_t) != 4 or not sft_layers:

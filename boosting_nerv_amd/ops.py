@@ -382,10 +382,49 @@ def dense_gemm(x, w, b, act="none"):
     return _DenseGemm.apply(x, w, b, _ACT[act])
 
 
+TIME_BRANCH_BWD_CALLS = {"taken": 0, "declined": 0}      # how _TimeBranch.backward's two-launch entry point answered (tests read it)
+
+
+def _time_branch_bwd_two_launches(B, saved, hs, p2, d_sy1, d_ty1, d_outs):
+    """The backward of the whole time branch as two launches (include/bnerv.h bnerv_time_branch_bwd): the gradients of p2 in p2's order
+    (flat [O, I] / [O] tensors), or None when the shapes are not the kernels' -- the caller then runs the five grouped launches.  Every
+    gradient has the bits of that form.  A d_outs[i] of None (the output took no part in the loss) is zeros, a d_ty1 of None adds nothing."""
+    pe, sy0, saux0, sy1, saux1, ty0, taux0, ty1, taux1 = saved
+    sw0, sb0, sw1, sb1, tw0, tb0, tw1, tb1 = p2[:8]
+    mw = p2[8:]
+    n = len(hs)
+    dev = pe.device
+    SH, SO, TH, TO = sw0.shape[0], sw1.shape[0], tw0.shape[0], tw1.shape[0]
+    f = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
+    g = [f(*t.shape) for t in p2]
+    nch = (SO + L.DENSE_DX_CHUNK - 1) // L.DENSE_DX_CHUNK
+    sx_part, zt_part, s_dpre = f(nch, B, SH), f(n, B, TO), f(B, SO)
+    d_sy1 = L.f32c(d_sy1).reshape(B, SO)
+    d_ty1 = None if d_ty1 is None else L.f32c(d_ty1).reshape(B, TO)
+    douts = [None if t is None else L.f32c(t).reshape(B, -1) for t in d_outs]
+    d = L.TimeBranchBwdDesc(L.ptr(pe), L.ptr(sw1), L.ptr(sy0), L.ptr(saux0), L.ptr(saux1), L.ptr(d_sy1),
+                            L.ptr(tw1), L.ptr(ty0), L.ptr(taux0), L.ptr(ty1), L.ptr(taux1), L.ptr(d_ty1),
+                            L.ptr(g[0]), L.ptr(g[1]), L.ptr(g[2]), L.ptr(g[3]), L.ptr(g[4]), L.ptr(g[5]), L.ptr(g[6]), L.ptr(g[7]),
+                            L.ptr(sx_part), L.ptr(zt_part), L.ptr(s_dpre), B, pe.shape[1] // 2, SH, SO, TH, TO, n, 0)
+    ml = (L.TimeBranchBwdMlp * n)()
+    for i in range(n):
+        w1, _, w2, _ = mw[4 * i:4 * i + 4]
+        dw1, db1, dw2, db2 = g[8 + 4 * i:12 + 4 * i]
+        ml[i].w1, ml[i].w2, ml[i].hs, ml[i].d_out = w1.data_ptr(), w2.data_ptr(), hs[i].data_ptr(), L.ptr(douts[i])
+        ml[i].dw1, ml[i].db1, ml[i].dw2, ml[i].db2, ml[i].C = dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(), db2.data_ptr(), w2.shape[0]
+    rc = L.load().bnerv_time_branch_bwd(L.stream(), C.byref(d), ml)
+    if rc == 1:
+        return None
+    L.check(rc, "bnerv_time_branch_bwd")
+    return g
+
+
 class _TimeBranch(torch.autograd.Function):
     """PositionEncoding -> stem layer 0 | stem_t (both layers) -> every TAT modulation MLP as ONE launch (include/bnerv.h
     bnerv_time_branch_fwd), then the stem's second layer as the ordinary grouped launch: 2 launches for the reference's chain of
-    model_nerv.py:47-51 / model_blocks.py:92-105 instead of 5.  The backward is the unchanged grouped dense backward of the four depths."""
+    model_nerv.py:47-51 / model_blocks.py:92-105 instead of 5.  The backward is two launches as well (bnerv_time_branch_bwd: the stem's
+    layer 1 beside both layers of every modulation MLP, then the stem's layer 0 beside stem_t's chain), with the bits of the grouped dense
+    backward of the four depths -- which still runs where that entry point declines the shapes, or with BNERV_TIME_BRANCH_BWD=0."""
 
     @staticmethod
     def forward(ctx, pos, bases, n_mlp, *params):
@@ -423,7 +462,9 @@ class _TimeBranch(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_sy1, d_ty1, *d_outs):
-        """Five launches instead of the layer-by-layer backward's six (and one reduction launch instead of two): the branches' levels are
+        """After the entry flush, two launches (_time_branch_bwd_two_launches).  Where those decline the shapes, or with
+        BNERV_TIME_BRANCH_BWD=0 (read per call), the grouped form they were derived from, whose bits they keep:
+        five launches instead of the layer-by-layer backward's six (and one reduction launch instead of two): the branches' levels are
         grouped by what is READY, not by which forward launch they came from --
             [every modulation MLP's layer 1 | the stem's layer 1]  ->  [every MLP's layer 0]  ->  ONE flush of both pending input-gradient
             reductions (z_t's over the 32 MLPs, the stem's 68 chunks)  ->  [stem_t layer 1 | stem layer 0]  ->  [stem_t layer 0]."""
@@ -439,6 +480,11 @@ class _TimeBranch(torch.autograd.Function):
         w1s, w2s = [mw[4 * i] for i in range(n)], [mw[4 * i + 2] for i in range(n)]
         if n + 1 > L.MAX_DENSE_GROUPS or n == 0:
             raise L.BnervError("time branch backward: group count outside the grouped kernel's table")
+        if os.environ.get("BNERV_TIME_BRANCH_BWD", "1") != "0":
+            g2 = _time_branch_bwd_two_launches(B, sv[:9], hs, p2, d_sy1, d_ty1, d_outs)
+            TIME_BRANCH_BWD_CALLS["taken" if g2 is not None else "declined"] += 1
+            if g2 is not None:
+                return (None, None, None, *[t.reshape(sh) for t, sh in zip(g2, ctx.pshapes)])
         # level 1: layer 1 of every modulation MLP + the stem's layer 1 (its input gradient: 68 chunks, reduced below)
         dxa, dwa, dba = _dense_grouped_bwd([none] * n + [sin], list(hs) + [sy0], w2s + [sw1], list(outs) + [sy1], [None] * n + [saux1],
                                            list(d_outs) + [d_sy1], [True] * (n + 1), [True] * (n + 1), False, B, defer_reduce=True)
@@ -467,7 +513,8 @@ class _TimeBranch(torch.autograd.Function):
 def time_branch(pos, bases, stem, stem_t, mlps):
     """pos [B] fp64, bases fp32 [L]; stem / stem_t = (w0, b0, w1, b1) of the two 2-layer sin MLPs; mlps = [(w1, b1, w2, b2), ...] of the TAT
     modulation branches (relu inside).  Returns (stem_out [B, SO], z_t [B, TO], [out_i [B, C_i]]), or None when the shapes are not the
-    kernel's (the caller runs the five grouped launches).  BNERV_TIME_BRANCH=0 switches it off (A/B)."""
+    kernel's (the caller runs the five grouped launches).  BNERV_TIME_BRANCH=0 switches it off (A/B).  The backward of the returned
+    tensors is two launches (bnerv_time_branch_bwd); BNERV_TIME_BRANCH_BWD=0 runs it as the five grouped launches, same bits (A/B)."""
     if os.environ.get("BNERV_TIME_BRANCH", "1") == "0" or pos.dtype != torch.float64 or not pos.is_cuda or pos.dim() != 1:
         return None
     B, Lv = pos.shape[0], bases.numel()

@@ -94,7 +94,7 @@ int bnerv_dense_grouped_bwd(void* stream, const bnerv_dense_bwd_desc* groups, in
  *   stem_t       : ty0 = sin(tw0 pe + tb0) [TH];  ty1 = sin(tw1 ty0 + tb1) [TO] = z_t
  *   every TAT modulation MLP i:  hs_i = relu(w1_i z_t + b1_i) [TO];  out_i = w2_i hs_i + b2_i [C_i]          SFTLayer, model_blocks.py:92-105
  * (the stem's second layer follows as an ordinary bnerv_dense_grouped_fwd launch).  Every tensor the five-launch form leaves behind --
- * outputs and the cosines saux0 / taux* of the sin layers -- is written, so the backward is the unchanged bnerv_dense_grouped_bwd sequence.
+ * outputs and the cosines saux0 / taux* of the sin layers -- is written, so the backward can be bnerv_time_branch_bwd (below) or the bnerv_dense_grouped_bwd sequence it was derived from.
  * Requires w1_i [TO, TO] and w2_i [C_i, TO] row-major, sw0 / tw0 [*, 2L].  Returns 1 when the shapes are not this kernel's (B > 4, 2L > 256,
  * TH > 64, TO > 32, C_i > 128, more than BNERV_MAX_DENSE_GROUPS MLPs, unaligned weights): the caller issues the grouped launches. */
 typedef struct { const float* w1; const float* b1; const float* w2; const float* b2; float* hs; float* out; int C; int _pad; } bnerv_time_branch_mlp;
@@ -109,6 +109,40 @@ typedef struct {
     int B, L, SH, TH, TO, n_mlp;
 } bnerv_time_branch_desc;
 int bnerv_time_branch_fwd(void* stream, const bnerv_time_branch_desc* d, const bnerv_time_branch_mlp* mlps /* [n_mlp] */);
+
+/* The backward of that branch (the stem's second layer included) as TWO launches instead of the five dependent grouped ones (csrc/dense.hip):
+ *   launch A: the stem's layer 1 (the grouped kernel's own row and chunk blocks: d_sw1, d_sb1, the chunk partials of d_sy0)  |  one block per
+ *             modulation MLP: BOTH its layers (dw2, db2, dw1, db1) and its slab of the d z_t partials;
+ *   launch B: the stem's layer 0 from the summed chunk partials (d_sw0, d_sb0)  |  one block: d z_t = sum of the slabs (+ d_ty1), then stem_t's
+ *             layer 1 and layer 0 (d_tw1, d_tb1, d_tw0, d_tb0).
+ * Every gradient has the bits of the five-launch form: the same fmaf chains, and the two cross-block sums in the order of the deferred slab
+ * reductions.  d_out of an MLP may be NULL (no gradient arrived: zeros), d_ty1 may be NULL (nothing is added).  Scratch is the caller's: sx_part
+ * [ceil(SO / BNERV_DENSE_DX_CHUNK), B, SH], zt_part [n_mlp, B, TO], s_dpre [B, SO].  Nothing is allocated and nothing synchronises (graph capture).
+ * Returns 1 -- before any device call -- when the shapes are not these kernels' (B > 4, 2L > 256, SH > 4096, TH > 64, TO > 32, C_i > 128,
+ * n_mlp + 1 > BNERV_MAX_DENSE_GROUPS): the caller issues the five grouped launches.  Both tables travel by value in the kernel-argument
+ * segment (<= 4096 bytes): sizeof(bnerv_time_branch_bwd_mlp) is BNERV_TIME_BRANCH_BWD_MLP_BYTES, sizeof(bnerv_time_branch_bwd_desc) is
+ * BNERV_TIME_BRANCH_BWD_DESC_BYTES. */
+#define BNERV_TIME_BRANCH_BWD_MLP_BYTES 72
+#define BNERV_TIME_BRANCH_BWD_DESC_BYTES 216
+typedef struct {
+    const float* w1; const float* w2;      /* [TO, TO], [C, TO] */
+    const float* hs;                       /* [B, TO]  relu output of layer 0 (saved by the forward) */
+    const float* d_out;                    /* [B, C]   incoming gradient, or NULL */
+    float* dw1; float* db1; float* dw2; float* db2;      /* written */
+    int C; int _pad;
+} bnerv_time_branch_bwd_mlp;
+typedef struct {
+    const float* pe;                                                             /* [B, 2L] */
+    const float* sw1; const float* sy0; const float* saux0; const float* saux1;  /* stem: [SO, SH], [B, SH] x 2, [B, SO] */
+    const float* d_sy1;                                                          /* [B, SO] */
+    const float* tw1; const float* ty0; const float* taux0; const float* ty1; const float* taux1;     /* stem_t: [TO, TH], [B, TH] x 2, [B, TO] x 2 */
+    const float* d_ty1;                                                          /* [B, TO] or NULL */
+    float* d_sw0; float* d_sb0; float* d_sw1; float* d_sb1;                      /* written: [SH, 2L], [SH], [SO, SH], [SO] */
+    float* d_tw0; float* d_tb0; float* d_tw1; float* d_tb1;                      /* written: [TH, 2L], [TH], [TO, TH], [TO] */
+    float* sx_part; float* zt_part; float* s_dpre;                               /* scratch (see above) */
+    int B, L, SH, SO, TH, TO, n_mlp, _pad;
+} bnerv_time_branch_bwd_desc;
+int bnerv_time_branch_bwd(void* stream, const bnerv_time_branch_bwd_desc* d, const bnerv_time_branch_bwd_mlp* mlps /* [n_mlp] */);
 
 /* Stand-alone TAT affine  y = x*(scale[b,c]+1) + shift[b,c]  (SFTLayer.forward, model_blocks.py:101-105) and its backward:
  *   dx = g*(scale+1);  part[chunk][0][b,c] = sum_chunk g*x;  part[chunk][1][b,c] = sum_chunk g
