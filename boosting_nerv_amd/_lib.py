@@ -266,6 +266,8 @@ SYMBOLS = {
     "bnerv_yuv420_loss_ws_bytes": (_Z, [_I, _I, _I]),
     "bnerv_yuv420_loss": (_I, [_V, _V, _I, _I, _I, _V, _I, _Z, _I, _I, _I, _I, _I, _V, C.POINTER(YuvCoeffs), C.POINTER(C.c_float), _F, _V, _I, _V,
                                _V, _V, _Z]),
+    "bnerv_yuv_luma_pair": (_I, [_V, _V, _I, _I, _I, _V, _I, _Z, _I, _I, _I, _I, _I, _V, C.POINTER(YuvCoeffs), _V, _V]),
+    "bnerv_luma_grad_rgb": (_I, [_V, _V, _I, _I, _I, C.POINTER(C.c_double), _F, _V, _I, _V, _V]),
     "bnerv_dense_gemm_fwd": (_I, [_V, _V, _V, _V, _V, _V, _I, _I, _I, _I]),
     "bnerv_dense_gemm_bwd_ws_bytes": (_Z, [_I, _I, _I]),
     "bnerv_dense_gemm_bwd": (_I, [_V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _Z, _I, _I, _I, _I]),

@@ -20,6 +20,9 @@
 //
 // bnerv_yuv420_loss is the training side of that score: the store arithmetic before rounding, minus the source codes, squared
 // and averaged per plane, with its exact gradient -- one stream launch of rgb_to_yuv420's shape plus a fixed-order finalize; described below.
+//
+// bnerv_yuv_luma_pair and bnerv_luma_grad_rgb stand in front of and behind the C = 1 MS-SSIM call of the MS-SSIM-Y term: the
+// prediction's luma code before rounding over the peak next to bnerv_yuv_luma_f32's plane, and gY scattered back onto the three RGB planes.
 #include "common.h"
 #include <stdint.h>
 
@@ -463,6 +466,85 @@ __global__ __launch_bounds__(THREADS) void yuv420_loss_final_kernel(const float*
     }
 }
 
+// ---- the MS-SSIM-Y term: the two streams around bnerv_loss_fwd_bwd at C = 1 ----
+//
+// yuv_luma_pair_kernel: grid = (blocks over rows x strips, B), the stream kernel of section 33.2 without its row pairs.  A thread owns 4 pixels of
+// one row: one 16-byte load per prediction channel, one 4- or 8-byte load of the samples, two 16-byte stores.  yp = a0 + a_c P_c with a0 = o_0 / m
+// and a_c = d_0 M[0, c] / m formed by the host in float64 (three fmas: the luma code before rounding over the peak, no clamp); ys = code / m with
+// the correctly rounded division, the bits of yuv_luma_f32_kernel.  No LDS, no barrier, no atomics.
+struct lumapair_consts { float a[3], a0, maxcode; };
+
+__device__ __forceinline__ void load_f32_strip(const float* __restrict__ s, const int n, float* v) {
+    if (n == STRIP && (reinterpret_cast<uintptr_t>(s) & 15) == 0) {
+        const f32x4 w = *reinterpret_cast<const f32x4*>(s);
+#pragma unroll
+        for (int q = 0; q < STRIP; ++q) v[q] = w[q];
+    } else {
+#pragma unroll
+        for (int q = 0; q < STRIP; ++q) v[q] = q < n ? s[q] : 0.0f;
+    }
+}
+__device__ __forceinline__ void store_f32_strip(float* __restrict__ d, const int n, const float* v) {
+    if (n == STRIP && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
+        *reinterpret_cast<f32x4*>(d) = f32x4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+        for (int q = 0; q < STRIP; ++q)
+            if (q < n) d[q] = v[q];
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(THREADS) void yuv_luma_pair_kernel(const float* __restrict__ pred, const int H, const int W, const unsigned char* __restrict__ src,
+                                                                const size_t frame_stride, const int n_frames, const int src_w, const int top,
+                                                                const int left, const float* __restrict__ frame_sel, const int nstrips,
+                                                                float* __restrict__ yp, float* __restrict__ ys, const lumapair_consts k) {
+    const int t = (int)blockIdx.x * THREADS + (int)threadIdx.x;
+    if (t >= H * nstrips) return;
+    const int b = (int)blockIdx.y;
+    int f = b;
+    if (frame_sel) f = min(max((int)frame_sel[b], 0), n_frames - 1);
+    const int y = t / nstrips, x0 = (t - y * nstrips) * STRIP, n = min(STRIP, W - x0);
+    const size_t HW = (size_t)H * W, o = (size_t)y * W + x0;
+    const float* const frame = pred + (size_t)b * 3 * HW + o;
+    float c[3][STRIP], s[STRIP], p[STRIP];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) load_f32_strip(frame + (size_t)a * HW, n, c[a]);
+    const T* Y = reinterpret_cast<const T*>(src + (size_t)f * frame_stride);
+    load_luma(Y + (size_t)(top + y) * src_w, left + x0, n, s);
+#pragma unroll
+    for (int q = 0; q < STRIP; ++q) {
+        p[q] = fmaf(k.a[0], c[0][q], fmaf(k.a[1], c[1][q], fmaf(k.a[2], c[2][q], k.a0)));
+        s[q] = __fdiv_rn(s[q], k.maxcode);
+    }
+    store_f32_strip(yp + (size_t)b * HW + o, n, p);
+    store_f32_strip(ys + (size_t)b * HW + o, n, s);
+}
+
+// luma_grad_rgb_kernel: grid = (blocks over strips of a sample's H W values, B).  One 16-byte load of gY, three 16-byte stores (and loads, accumulating):
+// grad[b, c] = kk[c] gY or fma(kk[c], gY, grad[b, c]) with kk[c] = lambda k_c.  Thread 0 of the launch: loss = lambda * loss_term, or added by one fma.
+__global__ __launch_bounds__(THREADS) void luma_grad_rgb_kernel(const float* __restrict__ gy, const int HW, const int nstrips, const float kk0, const float kk1,
+                                                                const float kk2, const float lambda, float* __restrict__ grad, const int accumulate,
+                                                                const float* __restrict__ loss_term, float* __restrict__ loss) {
+    const int t = (int)blockIdx.x * THREADS + (int)threadIdx.x;
+    if (t == 0 && blockIdx.y == 0) loss[0] = accumulate ? fmaf(lambda, loss_term[0], loss[0]) : lambda * loss_term[0];
+    if (t >= nstrips) return;
+    const int i0 = t * STRIP, n = min(STRIP, HW - i0);
+    const float kk[3] = {kk0, kk1, kk2};
+    float g[STRIP];
+    load_f32_strip(gy + (size_t)blockIdx.y * HW + i0, n, g);
+    float* const frame = grad + (size_t)blockIdx.y * 3 * HW + i0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float* d = frame + (size_t)a * HW;
+        float w[STRIP] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (accumulate) load_f32_strip(d, n, w);
+#pragma unroll
+        for (int q = 0; q < STRIP; ++q) w[q] = accumulate ? fmaf(kk[a], g[q], w[q]) : kk[a] * g[q];
+        store_f32_strip(d, n, w);
+    }
+}
+
 int yuv420_loss_blocks(int H, int W) { return cdiv((H / 2) * cdiv(W, STRIP), THREADS); }
 
 // what every entry point asks of the raw side
@@ -620,5 +702,54 @@ extern "C" int bnerv_yuv420_loss(void* stream, const float* pred, int B, int H, 
     hipLaunchKernelGGL(yuv420_loss_final_kernel, dim3(1), dim3(THREADS), 0, s, (const float*)part, B, nblocks * (THREADS / 64), 1.0 / hw, w[0], w[1], w[2],
                        lambda, accumulate, loss, stats);
     BNERV_LAUNCH_CHECK("yuv420_loss_final");
+    return BNERV_OK;
+}
+
+extern "C" int bnerv_yuv_luma_pair(void* stream, const float* pred, int B, int H, int W, const void* src, int bytes_per_sample, size_t frame_stride_bytes,
+                                   int n_frames, int src_h, int src_w, int top, int left, const float* frame_sel, const bnerv_yuv_coeffs* coeffs,
+                                   float* yp_out, float* ys_out) {
+    BNERV_REQUIRE(pred && src && coeffs && yp_out && ys_out, "yuv_luma_pair: null args");
+    BNERV_REQUIRE(n_frames > 0, "yuv_luma_pair: n_frames=%d", n_frames);
+    if (const int rc = check_raw("yuv_luma_pair", src, bytes_per_sample, 1, frame_stride_bytes, src_h, src_w)) return rc;
+    BNERV_REQUIRE(B > 0 && B <= 65535 && (frame_sel || B <= n_frames), "yuv_luma_pair: B=%d samples against %d frames%s", B, n_frames,
+                  frame_sel ? "" : " without frame_sel");
+    BNERV_REQUIRE(H > 0 && W > 0 && top >= 0 && left >= 0 && top <= src_h - H && left <= src_w - W,
+                  "yuv_luma_pair: the %dx%d window at (top %d, left %d) leaves the %dx%d frame", W, H, top, left, src_w, src_h);
+    BNERV_REQUIRE(coeffs->maxcode >= 1.0f, "yuv_luma_pair: maxcode=%g", (double)coeffs->maxcode);
+    BNERV_REQUIRE(((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(yp_out) | reinterpret_cast<uintptr_t>(ys_out) |
+                    reinterpret_cast<uintptr_t>(frame_sel)) & 3) == 0,
+                  "yuv_luma_pair: pred, yp_out, ys_out and frame_sel must be 4-byte aligned");
+    const double m = (double)coeffs->maxcode;
+    lumapair_consts k;
+    for (int c = 0; c < 3; ++c) k.a[c] = (float)((double)coeffs->scale[0] * (double)coeffs->m[c] / m);
+    k.a0 = (float)((double)coeffs->off[0] / m);
+    k.maxcode = coeffs->maxcode;
+    const int nstrips = cdiv(W, STRIP);
+    const dim3 grid(cdiv(H * nstrips, THREADS), B), block(THREADS);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const unsigned char* raw = static_cast<const unsigned char*>(src);
+    if (bytes_per_sample == 1)
+        hipLaunchKernelGGL(yuv_luma_pair_kernel<unsigned char>, grid, block, 0, s, pred, H, W, raw, frame_stride_bytes, n_frames, src_w, top, left, frame_sel,
+                           nstrips, yp_out, ys_out, k);
+    else
+        hipLaunchKernelGGL(yuv_luma_pair_kernel<unsigned short>, grid, block, 0, s, pred, H, W, raw, frame_stride_bytes, n_frames, src_w, top, left, frame_sel,
+                           nstrips, yp_out, ys_out, k);
+    BNERV_LAUNCH_CHECK("yuv_luma_pair");
+    return BNERV_OK;
+}
+
+extern "C" int bnerv_luma_grad_rgb(void* stream, const float* gy, int B, int H, int W, const double* k, float lambda, float* grad, int accumulate,
+                                   const float* loss_term, float* loss) {
+    BNERV_REQUIRE(k && loss_term && loss && (gy != nullptr) == (grad != nullptr), "luma_grad_rgb: null args");      // (gy and grad both null: the loss word alone)
+    BNERV_REQUIRE(B > 0 && B <= 65535, "luma_grad_rgb: B=%d", B);
+    BNERV_REQUIRE(H > 0 && W > 0 && (size_t)H * W <= 0x7fffffffu / 4, "luma_grad_rgb: H=%d W=%d", H, W);
+    BNERV_REQUIRE(((reinterpret_cast<uintptr_t>(gy) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(loss_term) |
+                    reinterpret_cast<uintptr_t>(loss)) & 3) == 0,
+                  "luma_grad_rgb: gy, grad, loss_term and loss must be 4-byte aligned");
+    const int HW = H * W, nstrips = gy ? cdiv(HW, STRIP) : 0;
+    const dim3 grid(gy ? cdiv(nstrips, THREADS) : 1, gy ? B : 1), block(THREADS);
+    hipLaunchKernelGGL(luma_grad_rgb_kernel, grid, block, 0, reinterpret_cast<hipStream_t>(stream), gy, HW, nstrips, (float)((double)lambda * k[0]),
+                       (float)((double)lambda * k[1]), (float)((double)lambda * k[2]), lambda, grad, accumulate, loss_term, loss);
+    BNERV_LAUNCH_CHECK("luma_grad_rgb");
     return BNERV_OK;
 }

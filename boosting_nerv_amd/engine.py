@@ -19,9 +19,10 @@ class YuvTerm:
     """What a step needs to add the plane loss of DESIGN section 33 (ops.yuv420_loss) to its loss: `raw`, the resident raw 4:2:0 clip in
     file layout (YuvFile.raw_to_device: a uint8 device tensor, frame k at byte k * frame_stride_bytes); coeffs = yuvio.coefficients(...);
     src_hw = (src_h, src_w) of a raw frame; window = (top, left) of the training crop in it, both even; the plane weights; lam, the factor
-    of the term in the total loss; pure: the term is the whole loss (--loss YUV420), the RGB loss is not launched."""
+    of the term in the total loss; pure: the term is the whole loss (--loss YUV420), the RGB loss is not launched.  lam_ms > 0 adds lam_ms
+    times the MS-SSIM-Y term of DESIGN section 37 (ops.yuv420_msssim_loss) against the same window's luma; lam may then be 0 (no plane MSE)."""
 
-    def __init__(self, raw, coeffs, src_hw, window, weights=(6, 1, 1), lam=1.0, pure=False, frame_stride_bytes=None):
+    def __init__(self, raw, coeffs, src_hw, window, weights=(6, 1, 1), lam=1.0, pure=False, frame_stride_bytes=None, lam_ms=0.0):
         from . import yuvio
         self.raw, self.coeffs = raw, coeffs
         self.src_hw = tuple(int(v) for v in src_hw)
@@ -30,17 +31,36 @@ class YuvTerm:
         self.lam, self.pure, self.frame_stride_bytes = float(lam), bool(pure), frame_stride_bytes
         if self.window[0] % 2 or self.window[1] % 2 or min(self.window) < 0:
             raise ValueError(f"YuvTerm: the crop offset (top {self.window[0]}, left {self.window[1]}) must be even: a 4:2:0 chroma sample covers a 2x2 block of the source")
-        if not self.lam > 0:
+        self.lam_ms = float(lam_ms)
+        if not self.lam_ms >= 0 or self.lam_ms == float("inf"):
+            raise ValueError(f"YuvTerm: lam_ms={lam_ms} (a finite factor >= 0; 0 switches the MS-SSIM-Y term off)")
+        if not (self.lam > 0 or (self.lam_ms > 0 and self.lam == 0)):
             raise ValueError(f"YuvTerm: lam={lam} (a positive factor; leave the term out to switch it off)")
+        self.ms_out = None                                   # S [B] of the last autograd_term() call with lam_ms > 0
 
     def check_frame(self, H, W):
         if H % 2 or W % 2:
             raise ValueError(f"YuvTerm: 4:2:0 needs an even crop, the frames are {H}x{W}")
         if self.window[0] + H > self.src_hw[0] or self.window[1] + W > self.src_hw[1]:
             raise ValueError(f"YuvTerm: the {H}x{W} crop at {self.window} leaves the {self.src_hw[0]}x{self.src_hw[1]} source frame")
+        if self.lam_ms > 0 and min(H, W) <= ops.MSSSIM_MIN_SIDE:
+            raise ValueError(f"YuvTerm: the five-scale MS-SSIM-Y term needs min(H, W) > {ops.MSSSIM_MIN_SIDE}, the frames are {H}x{W}")
 
     def kwargs(self):
         return dict(weights=self.weights, frame_stride_bytes=self.frame_stride_bytes)
+
+    def autograd_term(self, out, sel):
+        """(lam * L + lam_ms * L_ms with its autograd nodes, plane stats [B, 4] | None, S [B] | None) for the eager steps: sample b of `out`
+        against raw frame int(sel[b]) (fp32 device tensor).  A factor at 0 launches nothing for its part."""
+        total = stats = ms = None
+        if self.lam > 0:
+            term, stats = ops.yuv420_loss(out, self.raw, self.coeffs, self.src_hw, self.window, sel, **self.kwargs())
+            total = self.lam * term
+        if self.lam_ms > 0:
+            term, ms = ops.yuv420_msssim_loss(out, self.raw, self.coeffs, self.src_hw, self.window, sel, frame_stride_bytes=self.frame_stride_bytes)
+            total = self.lam_ms * term if total is None else total + self.lam_ms * term
+        self.ms_out = ms
+        return total, stats, ms
 
 
 class TrainStep:
@@ -75,7 +95,9 @@ class TrainStep:
         # yuv (YuvTerm): the plane loss against the raw source is added to the loss -- value and gradient -- by one more launch behind the
         # RGB loss (or replaces it: yuv.pure).  The frame number(s) it compares against are device words: the schedule record's on a bound
         # clip, yuv_sel (refreshed by a device copy in __call__) otherwise.  yuv_stats_out: its [B, 4] stats {L[b], mse_y, mse_u, mse_v}
-        self.yuv, self.yuv_sel, self.yuv_stats_out = yuv, None, None
+        # (None with yuv.lam == 0).  yuv.lam_ms > 0: the MS-SSIM-Y term's three launch groups go behind it and add into the same loss and
+        # gradient; yuv_ms_out: its S [B]
+        self.yuv, self.yuv_sel, self.yuv_stats_out, self.yuv_ms_out = yuv, None, None, None
         if yuv is not None:
             if mask is not None:
                 raise ValueError("TrainStep: the plane loss has no masked (inpainting) form: give a mask or yuv, not both")
@@ -166,6 +188,8 @@ class TrainStep:
         """(loss, psnr [B], grad) with the plane loss: added by its own launch into the RGB loss call's loss and gradient (no further pass
         over the frame), or alone (yuv.pure; the PSNR then comes from ops.psnr)."""
         y = self.yuv
+        if y.lam_ms > 0:
+            return self._yuv_ms_loss(img_out)
         if y.pure:
             loss, self.yuv_stats_out, grad = ops.yuv420_loss_value_grad_stats(img_out, y.raw, y.coeffs, y.src_hw, y.window, self._yuv_sel(), lam=y.lam,
                                                                               **y.kwargs())
@@ -174,6 +198,21 @@ class TrainStep:
         _, self.yuv_stats_out, _ = ops.yuv420_loss_value_grad_stats(img_out, y.raw, y.coeffs, y.src_hw, y.window, self._yuv_sel(), lam=y.lam,
                                                                     grad=grad, loss=loss, **y.kwargs())
         return loss, stats[:, 4], grad
+
+    def _yuv_ms_loss(self, img_out):
+        """_yuv_loss with the MS-SSIM-Y term (yuv.lam_ms > 0): the launches in front of it are those of lam_ms == 0 -- the RGB loss unless pure,
+        the plane MSE unless lam == 0 -- and the term adds into their loss and gradient (or, pure with lam == 0, writes them)."""
+        y = self.yuv
+        loss = grad = psnr = None
+        if not y.pure:
+            loss, stats, grad = ops.loss_value_grad_stats(img_out, self.static_img, self.loss_type)
+            psnr = stats[:, 4]
+        if y.lam > 0:
+            loss, self.yuv_stats_out, grad = ops.yuv420_loss_value_grad_stats(img_out, y.raw, y.coeffs, y.src_hw, y.window, self._yuv_sel(), lam=y.lam,
+                                                                              grad=grad, loss=loss, **y.kwargs())
+        loss, self.yuv_ms_out, grad = ops.yuv420_msssim_value_grad_stats(img_out, y.raw, y.coeffs, y.src_hw, y.window, self._yuv_sel(), lam=y.lam_ms,
+                                                                         grad=grad, loss=loss, frame_stride_bytes=y.frame_stride_bytes)
+        return loss, (ops.psnr(img_out.detach(), self.static_img) if psnr is None else psnr), grad
 
     def _lazy_flush_valid(self):
         """Lazy flushing (ops.lazy_flush) lets backward RETURN weight / bias gradients and TAT channel sums whose slab reductions are
@@ -445,8 +484,12 @@ class CompressionStep(TrainStep):
             out_loss = hu.loss_fn(img_out, self.static_img, self.loss_type)
         else:                                   # the plane loss through its autograd form, added to (or, pure, in place of) the RGB loss
             y = self.yuv
-            term, self.yuv_stats_out = ops.yuv420_loss(img_out, y.raw, y.coeffs, y.src_hw, y.window, self._yuv_sel(), **y.kwargs())
-            out_loss = y.lam * term if y.pure else hu.loss_fn(img_out, self.static_img, self.loss_type) + y.lam * term
+            if y.lam_ms > 0:
+                term, self.yuv_stats_out, self.yuv_ms_out = y.autograd_term(img_out, self._yuv_sel())
+                out_loss = term if y.pure else hu.loss_fn(img_out, self.static_img, self.loss_type) + term
+            else:
+                term, self.yuv_stats_out = ops.yuv420_loss(img_out, y.raw, y.coeffs, y.src_hw, y.window, self._yuv_sel(), **y.kwargs())
+                out_loss = y.lam * term if y.pure else hu.loss_fn(img_out, self.static_img, self.loss_type) + y.lam * term
         gate = (bpp.detach() / a.full_data_length > a.target_bpp).to(out_loss.dtype)     # `if bpp / N > target_bpp` (:363) on the device
         final_loss = out_loss + gate * a.lambda_rate * bpp
         final_loss.backward()

@@ -2074,6 +2074,123 @@ def yuv420_loss(pred, src, coeffs, src_hw, window, frame_sel=None, weights=(6, 1
     return _Yuv420Loss.apply(pred, src, coeffs, src_hw, window, frame_sel, tuple(float(v) for v in weights), frame_stride_bytes)
 
 
+# ---- the MS-SSIM-Y term: luma pair -> the loss call at C = 1 -> the gradient back onto the RGB planes ----
+MSSSIM_MIN_SIDE = 160      # the five-scale pyramid needs min(H, W) > 160
+
+
+def luma_grad_consts(coeffs):
+    """k_c = d_0 M[0, c] / m in float64: d Yp / d P[c] of the luma plane of DESIGN section 37."""
+    return tuple(float(coeffs.denom[0]) * float(coeffs.to_yuv[0, c]) / float(coeffs.maxcode) for c in range(3))
+
+
+def _luma_pair_args(pred, src, coeffs, src_hw, window, frame_sel, frame_stride_bytes, what):
+    pred = L.require_device(pred, "pred")
+    if pred.dim() != 4 or pred.shape[1] != 3 or pred.dtype != torch.float32 or not pred.is_contiguous() or pred.numel() == 0:
+        raise ValueError(f"{what}: need a non-empty contiguous fp32 [B, 3, H, W] prediction, got {pred.dtype} {tuple(pred.shape)}")
+    B = pred.shape[0]
+    bps = coeffs.bytes_per_sample
+    src_h, src_w = (int(v) for v in src_hw)
+    top, left = (int(v) for v in window)
+    nbytes = _raw_bytes(src, f"{what}: src")
+    if src.device != pred.device:
+        raise ValueError(f"{what}: pred is on {pred.device}, src on {src.device}")
+    frame = src_h * src_w * 3 // 2 * bps
+    stride = frame if frame_stride_bytes is None else int(frame_stride_bytes)
+    if frame <= 0 or stride < frame or nbytes < frame:
+        raise ValueError(f"{what}: frames of {frame} bytes at stride {stride} do not fit the {nbytes} bytes of src")
+    n_frames = (nbytes - frame) // stride + 1
+    if frame_sel is not None:
+        frame_sel = L.require_device(frame_sel, "frame_sel")
+        if frame_sel.dtype != torch.float32 or frame_sel.numel() < B or not frame_sel.is_contiguous() or frame_sel.device != pred.device:
+            raise ValueError(f"{what}: frame_sel must hold {B} contiguous fp32 frame numbers on {pred.device}")
+    return pred, bps, stride, n_frames, src_h, src_w, top, left, frame_sel
+
+
+def yuv_luma_pair(pred, src, coeffs, src_hw, window, frame_sel=None, frame_stride_bytes=None):
+    """(yp, ys), both [B, 1, H, W] fp32, in one launch: yp = (o_0 + d_0 (M[0] . pred)) / m, the luma code of the prediction [B, 3, H, W] (fp32, NOT
+    clamped) before rounding over the peak; ys = the H x W luma window at window = (top, left), any parity, of raw 4:2:0 frames `src` over the
+    peak -- the bits of yuv_luma_f32.  src, src_hw, frame_sel, frame_stride_bytes, coeffs: as yuv420_loss_value_grad_stats."""
+    pred, bps, stride, n_frames, src_h, src_w, top, left, frame_sel = _luma_pair_args(L.f32c(pred.detach()), src, coeffs, src_hw, window, frame_sel,
+                                                                                         frame_stride_bytes, "yuv_luma_pair")
+    B, _, H, W = pred.shape
+    yp = torch.empty(B, 1, H, W, dtype=torch.float32, device=pred.device)
+    ys = torch.empty_like(yp)
+    c = coeffs.store_struct()
+    L.check(L.load().bnerv_yuv_luma_pair(L.stream(), L.ptr(pred), B, H, W, L.ptr(src), bps, stride, n_frames, src_h, src_w, top, left, L.ptr(frame_sel),
+                                         C.byref(c), L.ptr(yp), L.ptr(ys)), "bnerv_yuv_luma_pair")
+    return yp, ys
+
+
+def luma_grad_rgb(gy, k, lam, loss_term, grad=None, loss=None):
+    """The adjoint of yuv_luma_pair's prediction side in one launch: gy [B, 1, H, W] -> grad [B, 3, H, W] = lam k_c gy and loss = lam * loss_term,
+    written -- or, with grad / loss handed in, ADDED to what they hold (one fma each).  gy None: the loss word alone.  Returns (loss, grad)."""
+    loss_term = L.require_device(loss_term, "loss_term")
+    accumulate = loss is not None
+    if loss is None:
+        loss = torch.empty((), dtype=torch.float32, device=loss_term.device)
+    if gy is not None:
+        gy = L.f32c(L.require_device(gy, "gy"))
+        B, _, H, W = gy.shape
+        if grad is None:
+            if accumulate:
+                raise ValueError("luma_grad_rgb: a loss to accumulate into needs the grad to accumulate into as well")
+            grad = torch.empty(B, 3, H, W, dtype=torch.float32, device=gy.device)
+        elif grad.dtype != torch.float32 or tuple(grad.shape) != (B, 3, H, W) or not grad.is_contiguous() or grad.device != gy.device:
+            raise ValueError(f"luma_grad_rgb: grad must be a contiguous fp32 [{B}, 3, {H}, {W}] tensor on {gy.device}")
+    else:
+        B, H, W, grad = 1, 1, 1, None
+    if loss.dtype != torch.float32 or loss.numel() != 1 or not loss.is_contiguous() or loss.device != loss_term.device:
+        raise ValueError(f"luma_grad_rgb: loss must be a contiguous fp32 scalar tensor on {loss_term.device}")
+    kk = (C.c_double * 3)(*(float(v) for v in k))
+    L.check(L.load().bnerv_luma_grad_rgb(L.stream(), L.ptr(gy), B, H, W, kk, float(lam), L.ptr(grad), int(accumulate), L.ptr(loss_term), L.ptr(loss)),
+            "bnerv_luma_grad_rgb")
+    return loss, grad
+
+
+def _yuv420_msssim_launch(pred, src, coeffs, src_hw, window, frame_sel, lam, grad, loss, frame_stride_bytes, need_grad):
+    if min(pred.shape[-2:]) <= MSSSIM_MIN_SIDE:
+        raise ValueError(f"yuv420_msssim: the five-scale MS-SSIM needs min(H, W) > {MSSSIM_MIN_SIDE}, got {tuple(pred.shape[-2:])}")
+    yp, ys = yuv_luma_pair(pred, src, coeffs, src_hw, window, frame_sel, frame_stride_bytes)
+    term, stats, gy = _loss_launch(yp, ys, (0.0, 0.0, 1.0, 0.0, 0.0), need_grad)
+    loss, grad = luma_grad_rgb(gy, luma_grad_consts(coeffs), lam, term, grad if need_grad else None, loss)
+    return loss, stats[:, 3], grad
+
+
+def yuv420_msssim_value_grad_stats(pred, src, coeffs, src_hw, window, frame_sel=None, lam=1.0, grad=None, loss=None, frame_stride_bytes=None,
+                                   need_grad=True):
+    """The MS-SSIM-Y term of DESIGN section 37 without an autograd node (the captured step's form): L_ms = mean_b (1 - S[b]), S[b] the
+    five-scale MS-SSIM (data range 1) of the prediction's luma code before rounding over the peak against the source luma window over the peak.
+    Operands as yuv420_loss_value_grad_stats.  Returns (lam * L_ms, S [B], lam * dL_ms/dpred); three launch groups: yuv_luma_pair, the loss
+    call at C = 1, luma_grad_rgb.  grad and loss handed in: the term is ADDED to them and they are returned; loss handed in alone, or
+    need_grad=False: value and S only, grad is None."""
+    if grad is not None and loss is None:
+        raise ValueError("yuv420_msssim: a grad to accumulate into needs the loss to accumulate into as well")
+    need_grad = bool(need_grad) and (grad is not None or loss is None)
+    return _yuv420_msssim_launch(L.f32c(pred.detach()), src, coeffs, src_hw, window, frame_sel, lam, grad, loss, frame_stride_bytes, need_grad)
+
+
+class _Yuv420Msssim(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, src, coeffs, src_hw, window, frame_sel, frame_stride_bytes):
+        loss, S, grad = _yuv420_msssim_launch(L.f32c(pred.detach()), src, coeffs, src_hw, window, frame_sel, 1.0, None, None, frame_stride_bytes,
+                                              ctx.needs_input_grad[0])
+        ctx.grad = grad
+        ctx.mark_non_differentiable(S)
+        return loss, S
+
+    @staticmethod
+    def backward(ctx, gl, _gs):
+        _enter_backward()
+        g = ctx.grad
+        ctx.grad = None
+        return (g * gl if g is not None else None), None, None, None, None, None, None
+
+
+def yuv420_msssim_loss(pred, src, coeffs, src_hw, window, frame_sel=None, frame_stride_bytes=None):
+    """The MS-SSIM-Y term as an autograd function (the eager steps): returns (L_ms [scalar], S [B]); see yuv420_msssim_value_grad_stats."""
+    return _Yuv420Msssim.apply(pred, src, coeffs, src_hw, window, frame_sel, frame_stride_bytes)
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # depthwise conv of the ConvNeXt encoder block (first kernels of row N3)
 # ----------------------------------------------------------------------------------------------------------------------

@@ -392,16 +392,16 @@ def train(local_rank, args):
             lr = adjust_lr(optimizer, (epoch + float(i) / n_iter) / args.epochs, i, args)
             if step is not None:
                 _, psnr_b = step(frames, norm_idx) if yuv_term is None else step(frames, norm_idx, frame_idx=img_idx)
-                yuv_stats = step.yuv_stats_out
+                yuv_stats, yuv_ms = step.yuv_stats_out, step.yuv_ms_out
             else:
                 psnr_b = _generic_step(model, optimizer, bucket, args, frames, img_idx, norm_idx, takes_image, yuv_term)
-                yuv_stats = getattr(args, '_yuv_stats_out', None)
+                yuv_stats, yuv_ms = getattr(args, '_yuv_stats_out', None), getattr(yuv_term, 'ms_out', None)
             psnr_sum += psnr_b.sum()
             seen += psnr_b.numel()
             if i % args.print_freq == 0 or i == n_iter - 1:                 # the only host sync of the loop
                 log.line('[{}] Rank:{}, Epoch[{}/{}], Step [{}/{}], lr:{:.2e} pred_PSNR: {}'.format(
                     log.stamp(), local_rank, epoch + 1, args.epochs, i + 1, n_iter, lr, rt.fmt((psnr_sum / seen).cpu(), 4))
-                    + ('' if yuv_term is None else f', yuv_psnr: {yuvloss.psnr_text(yuv_stats)}'))
+                    + ('' if yuv_term is None else yuvloss.train_text(yuv_term, yuv_stats, yuv_ms)))
         train_psnr = psnr_sum / max(seen, 1)
         if world > 1:
             dist.all_reduce(train_psnr)

@@ -244,7 +244,8 @@ def train(local_rank, args):
                 log.line('[{}] Rank:{}, Epoch[{}/{}], Step [{}/{}], lr:{:.2e} pred_PSNR: {}, loss:{}, bpp:{}'.format(
                     log.stamp(), local_rank, epoch + 1, args.epochs, i + 1, n_iter, lr, rt.fmt((psnr_sum / seen).cpu(), 2),
                     rt.fmt(loss.cpu(), 4), rt.fmt((bpp / args.full_data_length).cpu(), 6))
-                    + ('' if yuv_term is None else f', yuv_psnr: {yuvloss.psnr_text(cstep.yuv_stats_out if cstep is not None else args._yuv_stats_out)}'))
+                    + ('' if yuv_term is None else yuvloss.train_text(yuv_term, cstep.yuv_stats_out if cstep is not None else args._yuv_stats_out,
+                                                                        cstep.yuv_ms_out if cstep is not None else yuv_term.ms_out)))
         now = time.time()
         if is_main:
             print("Time/epoch: \tCurrent:{:.2f} \tAverage:{:.2f}".format(now - t_epoch, (now - t_start) / (epoch + 1 - args.start_epoch)))

@@ -204,6 +204,30 @@ def plane_loss_reference(rgb, planes, coeffs, window=(0, 0), weights=(6, 1, 1), 
     return (L, mse, grad, tuple(pre)) if return_pre else (L, mse, grad)
 
 
+def luma_pre_reference(rgb, planes, coeffs, window=(0, 0), return_pre=False):
+    """The float64 restatement of the two planes the MS-SSIM-Y term compares (DESIGN section 37).  rgb [B, 3, H, W], any float, NOT clamped;
+    planes = (y, u, v) integer codes as plane_loss_reference takes them (only y [B, src_h, src_w] is read); window = (top, left), any parity.
+    Returns (Yp [B, 1, H, W], Ys [B, 1, H, W], k [3]): Yp = (offset_0 + denom_0 (to_yuv[0] . rgb)) / maxcode, the luma code before rounding
+    over the peak (for rgb in [0, 1], maxcode * Yp is the luma `pre` of to_yuv_reference); Ys = code / maxcode; k_c = denom_0 to_yuv[0, c] /
+    maxcode = d Yp / d rgb[c].  return_pre=True: also a_0 = offset_0 + denom_0 (to_yuv[0] . rgb), the value Yp is the quotient of (the
+    division rounds once, so maxcode * Yp itself is a_0 only to an ulp)."""
+    P = np.asarray(rgb, dtype=np.float64)
+    if P.ndim != 4 or P.shape[1] != 3:
+        raise ValueError(f"yuvio: {P.shape} is no [B, 3, H, W] batch")
+    B, _, H, W = P.shape
+    top, left = (int(v) for v in window)
+    y = np.asarray(planes[0] if isinstance(planes, (tuple, list)) else planes)
+    if top < 0 or left < 0 or y.ndim != 3 or y.shape[0] != B or top + H > y.shape[1] or left + W > y.shape[2]:
+        raise ValueError(f"yuvio: the {H}x{W} window at (top {top}, left {left}) of luma planes {y.shape} for {B} samples")
+    M, m = coeffs.to_yuv, float(coeffs.maxcode)
+    val = M[0, 0] * P[:, 0] + M[0, 1] * P[:, 1] + M[0, 2] * P[:, 2]
+    pre = coeffs.offset[0] + coeffs.denom[0] * val
+    Yp = pre / m
+    Ys = y[:, top:top + H, left:left + W].astype(np.float64) / m
+    k = coeffs.denom[0] * M[0] / m
+    return (Yp[:, None], Ys[:, None], k, pre[:, None]) if return_pre else (Yp[:, None], Ys[:, None], k)
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # files
 # ----------------------------------------------------------------------------------------------------------------------

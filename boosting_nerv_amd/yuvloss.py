@@ -5,6 +5,8 @@ texts.  The loss itself is csrc/yuv.hip behind ops.yuv420_loss / ops.yuv420_loss
     --yuv_loss LAMBDA         total loss = loss_fn(--loss) + LAMBDA * L          (default 0: off)
     --yuv_loss_weights 6_1_1  the plane weights of L
     --loss YUV420             L alone, times --yuv_loss (which then defaults to 1)
+    --yuv_msssim LAMBDA       + LAMBDA * L_ms, the MS-SSIM-Y term of DESIGN section 37 (default 0: off; with or without --yuv_loss;
+                              under --loss YUV420 the loss is yuv_loss * L + yuv_msssim * L_ms)
 
 Matrix, range and depth are the loader's (--yuv_matrix, --yuv_range, the file's format)."""
 import numpy as np
@@ -16,6 +18,8 @@ def add_flags(parser):
     parser.add_argument('--yuv_loss', type=float, default=0., metavar='LAMBDA',
                         help='add LAMBDA times the 4:2:0 plane loss against the raw .yuv source to the loss (0 = off; 1 under --loss YUV420)')
     parser.add_argument('--yuv_loss_weights', type=str, default='6_1_1', help='plane weights Y_U_V of the plane loss')
+    parser.add_argument('--yuv_msssim', type=float, default=0., metavar='LAMBDA',
+                        help='add LAMBDA times (1 - MS-SSIM of the luma plane against the raw .yuv source) to the loss (0 = off)')
 
 
 def check_flags(args):
@@ -24,12 +28,15 @@ def check_flags(args):
     weights = yuvio.parse_weights(args.yuv_loss_weights)
     if not np.isfinite(args.yuv_loss) or args.yuv_loss < 0:
         raise ValueError(f"--yuv_loss {args.yuv_loss}: a factor >= 0 (0 switches the term off)")
+    ms = float(getattr(args, "yuv_msssim", 0.0))
+    if not np.isfinite(ms) or ms < 0:
+        raise ValueError(f"--yuv_msssim {ms}: a factor >= 0 (0 switches the term off)")
     pure = args.loss == PURE
     if pure and args.yuv_loss == 0:
         args.yuv_loss = 1.0
-    if not args.yuv_loss > 0:
+    if not (args.yuv_loss > 0 or ms > 0):
         return args
-    what = f"--loss {PURE}" if pure else "--yuv_loss"
+    what = f"--loss {PURE}" if pure else ("--yuv_loss" if args.yuv_loss > 0 else "--yuv_msssim")
     if getattr(args, "inpanting", "none") != "none":
         raise ValueError(f"{what} with --inpanting {args.inpanting}: the plane loss has no masked form")
     if getattr(args, "host_frames", False) or getattr(args, "embed_inter", False):
@@ -39,6 +46,8 @@ def check_flags(args):
     h, w = (int(v) for v in args.crop_list.split('_')[:2])
     if h % 2 or w % 2:
         raise ValueError(f"{what}: 4:2:0 needs an even crop, --crop_list gives {h}x{w}")
+    if ms > 0 and min(h, w) <= 160:
+        raise ValueError(f"--yuv_msssim: the five-scale MS-SSIM needs min(H, W) > 160, --crop_list gives {h}x{w}")
     args.yuv_loss_weights = "_".join(f"{v:g}" for v in weights)
     return args
 
@@ -48,9 +57,10 @@ def make_term(args, dataset, device, resident):
     not resident or not raw, and a centre crop that starts at an odd row or column of the source."""
     from . import yuvio
     from .engine import YuvTerm
-    if not getattr(args, "yuv_loss", 0) > 0:
+    ms = float(getattr(args, "yuv_msssim", 0.0))
+    if not (getattr(args, "yuv_loss", 0) > 0 or ms > 0):
         return None
-    what = f"--loss {PURE}" if args.loss == PURE else "--yuv_loss"
+    what = f"--loss {PURE}" if args.loss == PURE else ("--yuv_loss" if getattr(args, "yuv_loss", 0) > 0 else "--yuv_msssim")
     if dataset.yuv is None:
         raise ValueError(f"{what} compares against the planes of a raw source: --data_path {args.data_path} is no .yuv file")
     if not resident:
@@ -62,13 +72,15 @@ def make_term(args, dataset, device, resident):
                          "size must be even, a chroma sample covers a 2x2 block of the source (choose --crop_list so that the margins are multiples of 4)")
     coeffs = yuvio.coefficients(dataset.yuv_matrix, dataset.yuv_range, clip.depth)
     raw = clip.raw_to_device(device, count=len(dataset.samples))
-    return YuvTerm(raw, coeffs, (clip.height, clip.width), (top, left), weights=args.yuv_loss_weights, lam=args.yuv_loss, pure=args.loss == PURE)
+    if ms > 0 and min(ch, cw) <= 160:
+        raise ValueError(f"--yuv_msssim: the five-scale MS-SSIM needs min(H, W) > 160, the crop is {ch}x{cw}")
+    return YuvTerm(raw, coeffs, (clip.height, clip.width), (top, left), weights=args.yuv_loss_weights, lam=args.yuv_loss, pure=args.loss == PURE, lam_ms=ms)
 
 
 def describe(term):
     c = term.coeffs
     return (f"YUV loss: lambda {term.lam:g}, weights {'_'.join(f'{v:g}' for v in term.weights)}, matrix {c.matrix}, range {c.range}, {c.depth} bit"
-            + (" (pure: the RGB loss is off)" if term.pure else ""))
+            + (f", MS-SSIM-Y lambda {term.lam_ms:g}" if term.lam_ms > 0 else "") + (" (pure: the RGB loss is off)" if term.pure else ""))
 
 
 def psnr_text(stats):
@@ -77,10 +89,19 @@ def psnr_text(stats):
     return " ".join(f"{v:.2f}" for v in (-10.0 * mse.log10()).tolist())
 
 
+def train_text(term, stats, ms=None):
+    """What a train line carries behind its PSNR with the term on: ', yuv_psnr: Y U V' (with --yuv_loss) and ', yuv_msssim_y: v' (with
+    --yuv_msssim; the batch mean of S)."""
+    text = "" if stats is None else f", yuv_psnr: {psnr_text(stats)}"
+    if term.lam_ms > 0 and ms is not None:
+        text += f", yuv_msssim_y: {float(ms.double().mean().cpu()):.4f}"
+    return text
+
+
 def eager_term(term, out, img_idx):
-    """(lam * L with its autograd node, stats) for the eager steps: sample b against raw frame img_idx[b]."""
+    """(lam * L [+ lam_ms * L_ms] with its autograd node, stats) for the eager steps: sample b against raw frame img_idx[b].  With
+    --yuv_msssim S [B] is left in term.ms_out, and stats is None where --yuv_loss is 0."""
     import torch
-    from . import ops
     sel = img_idx.reshape(-1).to(out.device, dtype=torch.float32)
-    loss, stats = ops.yuv420_loss(out, term.raw, term.coeffs, term.src_hw, term.window, sel, **term.kwargs())
-    return term.lam * loss, stats
+    total, stats, _ = term.autograd_term(out, sel)
+    return total, stats

@@ -440,6 +440,22 @@ int bnerv_yuv420_loss(void* stream, const float* pred, int B, int H, int W, cons
                       int n_frames, int src_h, int src_w, int top, int left, const float* frame_sel, const bnerv_yuv_coeffs* coeffs,
                       const float* weights, float lambda, float* grad, int accumulate, float* loss, float* stats, void* ws, size_t ws_bytes);
 
+/* The MS-SSIM-Y term of training against the raw source (additive to ABI 9; csrc/yuv.hip; definition: DESIGN section 37; yuvio.luma_pre_reference
+ * is the float64 restatement).  Two streaming launches around bnerv_loss_fwd_bwd at C = 1 with (c_l1, c_l2, c_ms, c_fft) = (0, 0, 1, 0):
+ *   bnerv_yuv_luma_pair:  pred [B, 3, H, W] fp32, NOT clamped, and the H x W luma window at (top, left), any parity, of raw frames (src, n_frames,
+ *       frame_sel: as bnerv_yuv420_loss; coeffs: the STORE struct) -> yp_out [B, 1, H, W] = (off[0] + scale[0] (m[0] R + m[1] G + m[2] B)) / maxcode, the
+ *       luma code before rounding over the peak, and ys_out [B, 1, H, W] = float(code) / maxcode, the bits of bnerv_yuv_luma_f32.
+ *   bnerv_luma_grad_rgb:  gy [B, 1, H, W] = dL/dyp -> grad [B, 3, H, W]: accumulate == 0: grad[b, c] = (lambda k[c]) gy, loss[0] = lambda * loss_term[0];
+ *       accumulate != 0: grad[b, c] = fma(lambda k[c], gy, grad[b, c]), loss[0] = fma(lambda, loss_term[0], loss[0]).  k[c] = scale[0] m[c] / maxcode
+ *       in float64 (the host's); loss_term and loss are device words.  gy and grad both null: the loss word alone.
+ * Both validate before any launch (null pointers, bytes_per_sample, a window that leaves the frame, a stride smaller than a frame, B > n_frames
+ * without frame_sel); fp32 operands need 4-byte alignment, every wider access is chosen per address.  No LDS, barriers or atomics. */
+int bnerv_yuv_luma_pair(void* stream, const float* pred, int B, int H, int W, const void* src, int bytes_per_sample, size_t frame_stride_bytes,
+                        int n_frames, int src_h, int src_w, int top, int left, const float* frame_sel, const bnerv_yuv_coeffs* coeffs,
+                        float* yp_out, float* ys_out);
+int bnerv_luma_grad_rgb(void* stream, const float* gy, int B, int H, int W, const double* k, float lambda, float* grad, int accumulate,
+                        const float* loss_term, float* loss);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * GEMM-shaped dense work on v_mfma_f32_16x16x4_f32 (csrc/gemm.hip).
  *

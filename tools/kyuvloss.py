@@ -8,7 +8,14 @@
   train    the C1 recipe on a synthetic 720p clip written out as a raw 8-bit .yuv file (`--frames` frames, `--epochs` epochs), trained with
            --loss Fusion10_freq, the same plus --yuv_loss at `--lambdas`, and --loss YUV420; every run's post-hoc bitstream scored with
            codec.Decoder.score against the file: PSNR-Y / -U / -V / -YUV, RGB PSNR, MS-SSIM-Y.
-usage: python tools/kyuvloss.py [--only kernel|step|train] [--steps 100] [--repeats 3] [--frames 16] [--epochs 160] [--lambdas 300 3000]
+and the MS-SSIM-Y term (bnerv_yuv_luma_pair, bnerv_loss_fwd_bwd at C = 1, bnerv_luma_grad_rgb):
+  msssim-kernel  the pair kernel, the C = 1 loss call and the scatter, each replayed from a captured graph of 50 calls at 720p and 1080p, the
+                 whole term, and the 3-channel Fusion10 MS-SSIM call beside them for scale;
+  msssim-step    C1's and C3's captured step with YuvTerm(lam 1000, lam_ms 50) against the same YuvTerm with lam_ms = 0 (the parent's path),
+                 alternated as `step` does;
+  msssim-train   the `train` schedule with --yuv_msssim at `--ms_lambdas` added to its rows.
+usage: python tools/kyuvloss.py [--only kernel|step|train|msssim-kernel|msssim-step|msssim-train] [--steps 100] [--repeats 3] [--frames 16]
+                                [--epochs 160] [--lambdas 300 3000] [--ms_lambdas 50]
 (needs the GPU)"""
 import argparse
 import os
@@ -92,7 +99,31 @@ def kernel():
                   f"stock torch ops fwd+bwd eager {min(best):.1f} us best of 10;  max|grad - torch grad| / max|grad| {rel:.1e}", flush=True)
 
 
-def step(steps, repeats):
+def msssim_kernel():
+    import torch
+    from kinpaint import time_launch
+    from boosting_nerv_amd import ops
+    dev = torch.device("cuda:0")
+    for h, w in ((720, 1280), (1080, 1920)):
+        c, clip, raw = _raw_clip(1, h, w, 8, dev)
+        pred = (clip + 0.05 * torch.randn_like(clip)).contiguous()
+        grad, loss = torch.zeros_like(pred), torch.zeros((), device=dev)
+        yp, ys = ops.yuv_luma_pair(pred, raw, c, (h, w), (0, 0))
+        term, _, gy = ops._loss_launch(yp, ys, (0.0, 0.0, 1.0, 0.0, 0.0), True)
+        k = ops.luma_grad_consts(c)
+        t_pair = time_launch(lambda: ops.yuv_luma_pair(pred, raw, c, (h, w), (0, 0)))
+        t_loss = time_launch(lambda: ops._loss_launch(yp, ys, (0.0, 0.0, 1.0, 0.0, 0.0), True))
+        t_write = time_launch(lambda: ops.luma_grad_rgb(gy, k, 50.0, term))
+        t_add = time_launch(lambda: ops.luma_grad_rgb(gy, k, 50.0, term, grad=grad, loss=loss))
+        t_term = time_launch(lambda: ops.yuv420_msssim_value_grad_stats(pred, raw, c, (h, w), (0, 0), lam=50.0, grad=grad, loss=loss))
+        t_rgb = time_launch(lambda: ops.loss_value_grad_stats(pred, clip, "Fusion10"))
+        px = h * w
+        print(f"msssim-kernel {h}x{w}: luma pair {t_pair:.1f} us ({px * 21 / t_pair / 1e6:.2f} TB/s of {px * 21 / 1e6:.1f} MB), C = 1 loss call "
+              f"{t_loss:.1f} us, scatter write {t_write:.1f} us ({px * 16 / t_write / 1e6:.2f} TB/s), scatter accumulate {t_add:.1f} us "
+              f"({px * 28 / t_add / 1e6:.2f} TB/s); the whole term, accumulating {t_term:.1f} us;  Fusion10 at C = 3 {t_rgb:.1f} us", flush=True)
+
+
+def step(steps, repeats, ms=False):
     import torch
     import bench
     from boosting_nerv_amd.engine import TrainStep, YuvTerm
@@ -107,7 +138,11 @@ def step(steps, repeats):
         norm = torch.tensor([(i + 1) / N_FRAMES for i in range(N_FRAMES)], dtype=torch.float64, device=dev)
         idx = torch.arange(N_FRAMES, device=dev)
         paths = {}
-        for key, term in (("with the term (yuv=YuvTerm, lam 1000)", YuvTerm(raw, c, (h, w), (0, 0), lam=1000.0)), ("without (yuv=None)", None)):
+        pair = (("with the term (yuv=YuvTerm, lam 1000)", YuvTerm(raw, c, (h, w), (0, 0), lam=1000.0)), ("without (yuv=None)", None))
+        if ms:
+            pair = (("with MS-SSIM-Y (YuvTerm, lam 1000, lam_ms 50)", YuvTerm(raw, c, (h, w), (0, 0), lam=1000.0, lam_ms=50.0)),
+                    ("without (YuvTerm, lam 1000, lam_ms 0)", YuvTerm(raw, c, (h, w), (0, 0), lam=1000.0)))
+        for key, term in pair:
             model = bench.build(name)[1].to(dev)
             opt = Adan(model.parameters(), lr=args.lr)
             paths[key] = TrainStep(model, opt, args.loss, takes_image, (1, 3, h, w), dev, use_graph=True, warmup_eager=3, yuv=term)
@@ -141,7 +176,7 @@ def step(steps, repeats):
         del paths
 
 
-def train(frames, epochs, lambdas):
+def train(frames, epochs, lambdas, ms_lambdas=()):
     import torch
     import bench
     from boosting_nerv_amd import codec, yuvio
@@ -157,6 +192,12 @@ def train(frames, epochs, lambdas):
     runs = [("Fusion10_freq", ["--loss", "Fusion10_freq"])]
     runs += [(f"Fusion10_freq + {lam:g} L", ["--loss", "Fusion10_freq", "--yuv_loss", f"{lam:g}"]) for lam in lambdas]
     runs += [("YUV420", ["--loss", "YUV420"])]
+    if ms_lambdas:
+        runs = [runs[0]]
+        for ms in ms_lambdas:
+            runs += [(f"Fusion10_freq + {ms:g} L_ms", ["--loss", "Fusion10_freq", "--yuv_msssim", f"{ms:g}"])]
+            runs += [(f"Fusion10_freq + {lam:g} L + {ms:g} L_ms", ["--loss", "Fusion10_freq", "--yuv_loss", f"{lam:g}", "--yuv_msssim", f"{ms:g}"]) for lam in lambdas]
+            runs += [(f"YUV420 + {ms:g} L_ms", ["--loss", "YUV420", "--yuv_msssim", f"{ms:g}"])]
     cwd = os.getcwd()
     with tempfile.TemporaryDirectory() as tmp:
         os.chdir(tmp)
@@ -184,12 +225,13 @@ def train(frames, epochs, lambdas):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=["kernel", "step", "train"], default=None)
+    ap.add_argument("--only", choices=["kernel", "step", "train", "msssim-kernel", "msssim-step", "msssim-train"], default=None)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--epochs", type=int, default=160)
     ap.add_argument("--lambdas", type=float, nargs="+", default=[300.0, 3000.0])
+    ap.add_argument("--ms_lambdas", type=float, nargs="+", default=[50.0])
     a = ap.parse_args()
     if a.only in (None, "kernel"):
         kernel()
@@ -197,6 +239,12 @@ def main():
         step(a.steps, a.repeats)
     if a.only in (None, "train"):
         train(a.frames, a.epochs, a.lambdas)
+    if a.only == "msssim-kernel":
+        msssim_kernel()
+    if a.only == "msssim-step":
+        step(a.steps, a.repeats, ms=True)
+    if a.only == "msssim-train":
+        train(a.frames, a.epochs, a.lambdas, a.ms_lambdas)
 
 
 if __name__ == "__main__":
