@@ -345,6 +345,7 @@ SYMBOLS = {
     "bnerv_prune_masks": (_I, [_V, _V, _I, _V, _Z, _V]),
     "bnerv_mask_mul": (_I, [_V, _V, _I, _V, _Z]),
     "bnerv_grad_mask_table": (_I, [_V, _V, _I, _I, _V]),
+    "bnerv_embed_expand": (_I, [_V, _V, _V, _V, _I, _I, _I]),
 }
 
 _lib = None

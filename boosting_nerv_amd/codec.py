@@ -53,7 +53,13 @@ The post-hoc file has a temporal kind too (pstream.py) for HN
 frame by frame, each as its 8-bit codes or as their differences mod 256 to the frame before, the two kinds under Huffman codes of their own.
 encode_posthoc(..., temporal=True) takes differences and histograms in one launch (ops.EmbedDeltaU8) when the codes are on the device;
 Decoder entropy-decodes the two strings to bytes (ops.HuffDecodeU8) and resolves the chains in one launch (ops.EmbedChainDequantU8).
-decode, psnr, score and info work on it; there is no repack into it."""
+decode, psnr, score and info work on it; there is no repack into it.
+
+All three post-hoc kinds have an interpolation form: train_nerv_all.py --interpolation --embed_inter_stored --bitstream FILE
+stores the embeddings of the training frames only and the header key embed_stored = [N, a, b, c]; Decoder rebuilds the plan
+(hnerv_utils.interp_plan), decodes the compact [S, P] table through the launches above and fills the embeddings of all N frames in one launch
+(ops.embed_expand) -- the launch the evaluation used, so the decoded frames are the evaluated ones.  Decoder.stored_frames lists the stored
+frames, info reports n_stored_frames."""
 import argparse
 import builtins
 import json
@@ -654,7 +660,10 @@ def describe_temporal(budget):
 
 def describe_any(budget):
     """describe, describe_posthoc, describe_sparse, describe_posthoc_temporal, describe_chunked, describe_empirical, describe_wide or describe_temporal, by
-    the budget's items."""
+    the budget's items; an interpolation file adds how many frames' embeddings it stores."""
+    if "n_stored_frames" in budget:
+        rest = {k: v for k, v in budget.items() if k != "n_stored_frames"}
+        return f"{describe_any(rest)}; interpolation: the embeddings of {budget['n_stored_frames']} stored frames, every other frame derived from them"
     if "embed_symbol_bits" in budget:
         return describe_posthoc_temporal(budget)
     if "zero_parse" in budget:
@@ -835,6 +844,13 @@ def encode_posthoc(model, args, records, quant_embed, path, temporal=False):
     s.update(final_size=int(args.final_size), quant_model_bit=int(args.quant_model_bit), quant_embed_bit=int(args.quant_embed_bit), huff_run=qstream.RUN)
     if is_hnerv:
         s["embed_shape"] = [int(v) for v in quant_embed["quant"].shape]
+    if is_hnerv and getattr(args, "embed_inter_stored", False):
+        # an interpolation file: the record holds the stored frames only, the key lets a decoder rebuild the plan
+        from .hnerv_utils import interp_plan, parse_split
+        stored, _ = interp_plan(args.full_data_length, args.data_split, getattr(args, "shuffle_data", False))
+        if s["embed_shape"][0] != len(stored):
+            raise ValueError(f"codec.encode_posthoc: --embed_inter_stored stores {len(stored)} frames, the embedding record holds {s['embed_shape'][0]}")
+        s["embed_stored"] = [int(args.full_data_length)] + parse_split(args.data_split)
     if sparse:
         s.update(zero_parse=parse, n_zero_leaves=int(hist[zstream.ZERO:].sum()))
     if temporal:
@@ -910,6 +926,7 @@ class Decoder:
         self.settings = s
         self.device = torch.device(device)
         self.n_frames = int(s["full_data_length"])
+        self.stored_frames = list(builtins.range(self.n_frames))
         self.frame_hw = tuple(int(v) for v in s["crop_list"].split("_")[:2])
         self.is_hnerv = s["model"] == "HNeRV_Boost"
         margs = SimpleNamespace(**{k: v for k, v in s.items() if k not in ("ans_run", "ans_tables", "ans_wide", "embed_pred")})
@@ -1034,7 +1051,7 @@ class Decoder:
         self.is_hnerv = "HNeRV" in s["model"]
         if temporal and not self.is_hnerv:
             raise ValueError(f"{what}: an embedding section in a {s['model']} stream")
-        margs = SimpleNamespace(**{k: v for k, v in s.items() if k not in ("embed_pred", "tensor_kind")})
+        margs = SimpleNamespace(**{k: v for k, v in s.items() if k not in ("embed_pred", "tensor_kind", "embed_stored")})
         margs.__dict__.update(quant=False, outf="")
         model = build_model(margs)
         if self.is_hnerv:
@@ -1044,13 +1061,19 @@ class Decoder:
         targets = []
         if self.is_hnerv:
             shape = tuple(int(v) for v in s.get("embed_shape", ()))
-            if len(shape) != 4 or shape[0] != self.n_frames or (temporal and shape != tuple(qs.embeds.shape)):
-                raise ValueError(f"{what}: the header's embedding shape {shape} does not match its {self.n_frames} frames")
-            self.embeds = torch.empty(shape, dtype=torch.float32, device=self.device)
+            plan = self._stored_plan(s, what)
+            if len(shape) != 4 or shape[0] not in (self.n_frames, len(self.stored_frames)) or (temporal and shape != tuple(qs.embeds.shape)):
+                raise ValueError(f"{what}: the header's embedding shape {shape} does not match its {self.n_frames} frames"
+                                 + (f" or the {len(self.stored_frames)} it stores" if plan is not None else ""))
+            if shape[0] == self.n_frames:                  # every frame's embedding is in the file
+                plan, self.stored_frames = None, list(builtins.range(self.n_frames))
+            # an interpolation file decodes into the compact [S, C, h, w] table first; ONE launch then fills self.embeds [N, C, h, w] (below)
+            held_embeds = torch.empty(shape, dtype=torch.float32, device=self.device)
+            self.embeds = held_embeds if plan is None else torch.empty((self.n_frames,) + shape[1:], dtype=torch.float32, device=self.device)
             if not temporal:
-                targets.append(self.embeds)
+                targets.append(held_embeds)
         else:
-            self.embeds = None
+            self.embeds, plan, self.stored_frames = None, None, list(builtins.range(self.n_frames))
         targets += [v for k, v in model.state_dict().items() if "encoder" not in k]
         if len(targets) != len(qs.records) or any(t.numel() != r.count for t, r in zip(targets, qs.records)):
             raise ValueError(f"{what}: the records do not match the model the header describes")
@@ -1080,19 +1103,37 @@ class Decoder:
             items.append((t, lo, step, r.red, r.inner, r.run_bits))
         if not temporal:
             (dequant or ops.huff_dequant)(qs.words, qs.lengths, items, int(s["huff_run"]))
+            if plan is not None:
+                ops.embed_expand(held_embeds, plan, self.embeds)
             return
         e, run = qs.embeds, int(s["huff_run"])
+        n_held = int(held_embeds.shape[0])
         jobs = [(ops.HuffzDequant if s["tensor_kind"] == "sparse" else ops.HuffDequant)(qs.words, qs.lengths, items, run).launch()]
-        held = torch.empty(self.n_frames, self.embeds[0].numel(), dtype=torch.uint8, device=self.device)
+        held = torch.empty(n_held, held_embeds[0].numel(), dtype=torch.uint8, device=self.device)
         for kind, lengths, words in ((pstream.INTRA, e.lengths0, e.words0), (pstream.INTER, e.lengths1, e.words1)):
             rows = np.flatnonzero(e.pred == kind)
             if rows.size:
                 jobs.append(ops.HuffDecodeU8(words, lengths, [(held[int(t)], e.run_bits[int(t)]) for t in rows], run).launch())
         tdt = torch.float16 if e.dtype == qstream.F16 else torch.float32
         lo, step = (grids[o:o + n].view(tdt) for o, n in spans[-2:])
-        jobs.append(ops.EmbedChainDequantU8(held, e.pred, lo, step, e.red, e.inner, self.embeds.view(self.n_frames, -1)).launch())
+        jobs.append(ops.EmbedChainDequantU8(held, e.pred, lo, step, e.red, e.inner, held_embeds.view(n_held, -1)).launch())
+        if plan is not None:
+            ops.embed_expand(held_embeds, plan, self.embeds)
         for job in jobs:                                   # the first check is the one synchronisation; the others read words that are ready
             job.check()
+
+    def _stored_plan(self, s, what):
+        """The plan of an interpolation file (header key embed_stored = [N, a, b, c]), None for any other file; sets
+        self.stored_frames, the frames whose embeddings the file holds."""
+        from .hnerv_utils import interp_plan
+        self.stored_frames = list(builtins.range(self.n_frames))
+        key = s.get("embed_stored")
+        if key is None:
+            return None
+        if not isinstance(key, list) or len(key) != 4 or any(not isinstance(v, int) or isinstance(v, bool) for v in key) or key[0] != self.n_frames:
+            raise ValueError(f"{what}: the header's embed_stored {key!r} is not [N, a, b, c] of its {self.n_frames} frames")
+        self.stored_frames, plan = interp_plan(key[0], key[1:])
+        return plan
 
     def _frame_loop(self, use_graph, pack, matrix, range):
         from .engine import FrameDecodeGraph

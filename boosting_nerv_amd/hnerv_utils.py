@@ -144,6 +144,79 @@ def data_split(img_list, split_num_list, shuffle_data, rand_num=0):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# interpolation from stored embeddings: which frames a file stores, and how every other frame's embedding follows
+# from theirs.  Host only; csrc/interp.hip (ops.embed_expand) executes the plan
+# ----------------------------------------------------------------------------------------------------------------------
+INTERP_ENTRY = np.dtype([("ia", "<i4"), ("ib", "<i4"), ("w", "<f4")])      # bnerv_interp_entry: one row of a plan, three dwords
+
+
+def parse_split(split):
+    """--data_split 'a_b_c' (or its three integers) -> [a, b, c]."""
+    nums = [int(x) for x in split.split("_")] if isinstance(split, str) else [int(x) for x in split]
+    if len(nums) != 3 or nums[2] < 1 or min(nums) < 0:
+        raise ValueError(f"interp_plan: --data_split {split!r} is not a_b_c with c >= 1")
+    return nums
+
+
+def interp_plan(n_frames, split, shuffle_data=False):
+    """(stored, plan) of an --interpolation --embed_inter_stored run over n_frames frames.
+    stored: the training frames of data_split(range(N), split, False), ascending -- positions < a of every period of c frames.
+    plan: [N] rows (ia, ib, w) of INTERP_ENTRY, ia and ib indices into `stored`, w fp32.  Stored frame stored[k]: (k, k, 0).  Every other
+    frame t is derived -- held out or not: between its nearest stored frames stored[ia] < t < stored[ib] with
+    w = fp32(t - stored[ia]) / fp32(stored[ib] - stored[ia]); with a stored frame on one side only, (k, k, 0) of that side.  With 1_1_2
+    and an odd frame count this is the reference's rule: neighbours idx - 1 and idx + 1, w = 0.5.
+    ValueError: no stored frame; shuffle_data (a shuffled split has no neighbours in time)."""
+    if shuffle_data:
+        raise ValueError("interp_plan: --shuffle_data permutes the frames before the split: a held-out frame has no neighbours in time to derive it from")
+    n_frames = int(n_frames)
+    stored, _ = data_split(list(range(n_frames)), parse_split(split), False)
+    if not stored:
+        raise ValueError(f"interp_plan: --data_split {split!r} over {n_frames} frames stores no frame")
+    plan = np.zeros(n_frames, dtype=INTERP_ENTRY)
+    k = 0                                                  # stored[k] is the nearest stored frame at or below t, once there is one
+    for t in range(n_frames):
+        while k + 1 < len(stored) and stored[k + 1] <= t:
+            k += 1
+        if stored[k] >= t or k + 1 == len(stored):         # stored itself, in front of the first stored frame, or behind the last
+            plan[t] = (k, k, 0.0)
+        else:
+            plan[t] = (k, k + 1, np.float32(t - stored[k]) / np.float32(stored[k + 1] - stored[k]))
+    return stored, plan
+
+
+def check_interp_plan(plan, n_stored):
+    """The plan as a contiguous INTERP_ENTRY array; ValueError for an index outside 0..n_stored-1 or a weight outside [0, 1) -- what whoever
+    launches ops.embed_expand calls before the plan goes to the device."""
+    plan = np.ascontiguousarray(plan, dtype=INTERP_ENTRY).reshape(-1)
+    if plan.size == 0:
+        raise ValueError("interp plan: no rows")
+    for name in ("ia", "ib"):
+        if int(plan[name].min()) < 0 or int(plan[name].max()) >= int(n_stored):
+            raise ValueError(f"interp plan: {name} outside 0..{int(n_stored) - 1}")
+    if not bool(np.all((plan["w"] >= 0) & (plan["w"] < 1))):
+        raise ValueError("interp plan: a weight outside [0, 1)")
+    return plan
+
+
+def embed_expand_reference(src, plan):
+    """numpy fp32 restatement of ops.embed_expand (csrc/interp.hip), bit for bit: src [S, P] -> [N, P].  ia == ib: copy; w == 0.5:
+    0.5 * (L + R); otherwise (1 - w) * L + w * R with every operation rounded to fp32 on its own."""
+    src = np.ascontiguousarray(src, dtype=np.float32)
+    plan = check_interp_plan(plan, src.shape[0])
+    out = np.empty((plan.size,) + src.shape[1:], dtype=np.float32)
+    half = np.float32(0.5)
+    for t, (ia, ib, w) in enumerate(plan.tolist()):
+        w = np.float32(w)
+        if ia == ib:
+            out[t] = src[ia]
+        elif w == half:
+            out[t] = half * (src[ia] + src[ib])
+        else:
+            out[t] = (np.float32(1.0) - w) * src[ia] + w * src[ib]
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # post-hoc 8-bit quantisation used by evaluate() / quant_model (reference hnerv_utils.py:101-134, :183-186): eval-time
 # reporting on stock torch ops, not part of the train hot path
 # ----------------------------------------------------------------------------------------------------------------------

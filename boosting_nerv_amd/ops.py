@@ -2525,6 +2525,34 @@ def ssim(x, y):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# interpolation from stored embeddings (csrc/interp.hip; hnerv_utils.interp_plan makes the plan)
+# ----------------------------------------------------------------------------------------------------------------------
+def embed_expand(src, plan, out=None):
+    """out [N, ...] from src [S, ...] (fp32, on the device) under `plan` (hnerv_utils.interp_plan: N rows (ia, ib, w), a host array): a
+    stored frame's row is copied, a derived frame's row is blended from two stored rows -- ONE launch (bnerv_embed_expand), the bits of
+    hnerv_utils.embed_expand_reference.  The plan is validated here (indices inside src, 0 <= w < 1: ValueError) and goes up as one small
+    array.  src and out are used in place: contiguous, at any 4-byte boundary (the 16-byte form runs where it can)."""
+    from .hnerv_utils import check_interp_plan
+    L.require_device(src, "embed_expand: src")
+    if src.dtype != torch.float32 or not src.is_contiguous() or src.dim() < 1 or src.numel() == 0:
+        raise ValueError(f"embed_expand: src must be a non-empty contiguous fp32 tensor [S, ...], got {src.dtype} {tuple(src.shape)}")
+    S, P = int(src.shape[0]), int(src[0].numel())
+    plan = check_interp_plan(plan, S)
+    N = int(plan.size)
+    if out is None:
+        out = torch.empty((N,) + tuple(src.shape[1:]), dtype=torch.float32, device=src.device)
+    L.require_device(out, "embed_expand: out")
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.device != src.device or tuple(out.shape) != (N,) + tuple(src.shape[1:]):
+        raise ValueError(f"embed_expand: out must be a contiguous fp32 tensor {(N,) + tuple(src.shape[1:])} on {src.device}, got {out.dtype} {tuple(out.shape)}")
+    lo, hi = out.data_ptr(), out.data_ptr() + 4 * N * P
+    if src.data_ptr() < hi and lo < src.data_ptr() + 4 * S * P:
+        raise ValueError("embed_expand: src and out overlap")
+    plan_dev = _upload(plan, src.device)
+    L.check(L.load().bnerv_embed_expand(L.stream(), L.ptr(src), L.ptr(plan_dev), L.ptr(out), S, N, P), "bnerv_embed_expand")
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # global magnitude pruning (csrc/prune.hip; boosting_nerv_amd/prune.py drives it)
 # ----------------------------------------------------------------------------------------------------------------------
 class PruneTable:

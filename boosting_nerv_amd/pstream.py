@@ -307,6 +307,7 @@ def info(path_or_buffer):
                embed_section_bits=embed_section_bits(e, int(ps.settings["huff_run"])), bytes=nbytes, tensor_kind=ps.settings["tensor_kind"])
     if zeros is not None:
         out.update(n_zero_elements=int(zeros), n_zero_leaves=int(ps.settings["n_zero_leaves"]), zero_parse=ps.settings["zero_parse"])
+    out.update(qstream.stored_frames_item(ps.settings))
     return out
 
 

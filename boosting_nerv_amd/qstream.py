@@ -235,4 +235,16 @@ def info(path_or_buffer):
     assert total == 8 * nbytes, (total, nbytes)            # every byte was booked exactly once
     out.update(total=total, n_records=len(qs.records), n_runs=int(sum(r.run_bits.size for r in qs.records)),
                n_symbols=int(sum(r.count for r in qs.records)), bytes=nbytes)
+    out.update(stored_frames_item(qs.settings))
     return out
+
+
+def stored_frames_item(settings):
+    """{"n_stored_frames": S} for the header of an interpolation file (the key embed_stored = [N, a, b, c]; the embedding
+    record holds S = embed_shape[0] of the N frames), {} for any other header.  A count, not a budget item: the bits are booked as ever."""
+    if "embed_stored" not in settings:
+        return {}
+    shape = settings.get("embed_shape")
+    if not isinstance(shape, list) or not shape or not isinstance(shape[0], int):
+        raise ValueError(f"qstream: a header with embed_stored and the embedding shape {shape!r}")
+    return {"n_stored_frames": int(shape[0])}

@@ -29,7 +29,7 @@ from . import runtime as rt
 from . import yuvloss
 from .dp import GradBucket
 from .engine import TrainStep
-from .hnerv_utils import TransformInput, VideoDataSet, adjust_lr, data_split, loss_fn, psnr_fn_device, quant_tensor, quant_tensor_sparse, worker_init_fn
+from .hnerv_utils import TransformInput, VideoDataSet, adjust_lr, data_split, interp_plan, loss_fn, psnr_fn_device, quant_tensor, quant_tensor_sparse, worker_init_fn
 from .model_enerv import ENeRV_Boost
 from .model_hnerv import HNeRV, HNeRV_Boost
 from .model_nerv import NeRV_Boost
@@ -84,6 +84,10 @@ def build_parser():
     parser.add_argument('--inpanting', default='none', type=str, help='do inpanting')
     parser.add_argument('--interpolation', action='store_true', default=False, help='do interpolation')
     parser.add_argument('--embed_inter', action='store_true', default=False, help='do interpolation')
+    parser.add_argument('--embed_inter_stored', action='store_true', default=False,
+                        help='with --interpolation (HNeRV, HNeRV_Boost), in place of --embed_inter: the embedding of every frame that is not a training '
+                             'frame is derived from the embeddings of its nearest training frames in time, quantised as a file stores them, so '
+                             '--bitstream writes the training frames\' embeddings only (DESIGN section 38)')
     parser.add_argument('--cabac', action='store_true', default=False)
     # global magnitude pruning with masked fine-tuning (prune.py); off by default
     parser.add_argument('--prune_sparsity', type=float, default=0., help='final total sparsity of the decoder weights, in [0, 1); 0 = no pruning')
@@ -145,6 +149,15 @@ def parse_args(argv=None):
     args.prune_steps = sorted(steps)
     if args.bitstream_sparse and not args.bitstream:
         raise ValueError("--bitstream_sparse: the sparse twin is what --bitstream FILE writes; give the file")
+    if args.embed_inter_stored:
+        if args.embed_inter:
+            raise ValueError("--embed_inter_stored stands in place of --embed_inter (held-out embeddings from stored ones, not from the source frames): give one")
+        if not args.interpolation:
+            raise ValueError("--embed_inter_stored: the held-out frames it derives are those of an --interpolation run")
+        if args.model not in ("HNeRV", "HNeRV_Boost"):
+            raise ValueError(f"--embed_inter_stored: --model {args.model} has no frame embeddings to derive (HNeRV, HNeRV_Boost)")
+        if args.shuffle_data:
+            raise ValueError("--embed_inter_stored: --shuffle_data permutes the frames before the split; a held-out frame then has no neighbours in time")
     return yuvloss.check_flags(args)
 
 
@@ -365,6 +378,10 @@ def train(local_rank, args):
              + f', inpainting mask: {args.inpanting if mask is not None else "none"}, clip_max_norm: {args.clip_max_norm}', echo=False)
     if yuv_term is not None:
         log.line(yuvloss.describe(yuv_term), echo=False)
+    if args.embed_inter_stored:
+        stored, _ = interp_plan(args.full_data_length, args.data_split)
+        log.line(f'Interpolation: {len(stored)} of {args.full_data_length} frames stored, {args.full_data_length - len(stored)} derived '
+                 f'(split {args.data_split})', echo=False)
     # the generic path (stock Adam) averages its gradients over the ranks with the same flat bucket the fused step uses
     bucket = GradBucket(model.parameters()) if (step is None and world > 1) else None
 
@@ -534,6 +551,23 @@ def _timed_decodes(net, cur_input, embed, norm_idx, graph):
 
 
 @torch.no_grad()
+def _encode_stored(net, full_dataloader, args, frames_dev):
+    """[S, C, h, w]: the encoder's embedding of every stored frame of an --embed_inter_stored run (interp_plan's `stored`, in that order), one
+    frame per call as the evaluation loop feeds it.  Frames come from the resident clip, or from the loader's dataset under --host_frames."""
+    stored = interp_plan(args.full_data_length, args.data_split, args.shuffle_data)[0]
+    device = next(net.parameters()).device
+    was_training = net.training
+    net.eval()
+    rows = []
+    for k in stored:
+        frame = frames_dev[k:k + 1] if frames_dev is not None else data_to_gpu(full_dataloader.dataset[k]['img'][None], device)
+        img_in, _gt, _mask = args.transform_func(frame, torch.tensor([k], device=device))
+        rows.append(net.forward_encoder(img_in))
+    net.train(was_training)
+    return torch.cat(rows, 0).contiguous()
+
+
+@torch.no_grad()
 def evaluate(model, full_dataloader, local_rank, args, dump_vis=False, huffman_coding=False):
     """PSNR / MS-SSIM of the fp32 model and of its post-hoc quantised twin over the whole clip (seen / unseen frames apart),
     decode FPS, and -- on request -- the Huffman bit accounting of the quantised tensors.  Returns (values per metric slot, (h, w))."""
@@ -545,6 +579,14 @@ def evaluate(model, full_dataloader, local_rank, args, dump_vis=False, huffman_c
     is_hnerv = "HNeRV" in args.model
     embeds, dequant_embeds, quant_embed = [], None, None
     fps, hw = 0.0, (0, 0)
+    # --embed_inter_stored: the encoder runs over the stored frames only; every frame's embedding, in both slots, is a row
+    # of ops.embed_expand over that table (fp32 slot) or over its de-quantised twin (quantised slot: what a decoder of the file holds)
+    from_stored = getattr(args, 'embed_inter_stored', False) and is_hnerv
+    if from_stored:
+        plan = interp_plan(args.full_data_length, args.data_split, args.shuffle_data)[1]
+        stored_table = _encode_stored(nets[0], full_dataloader, args, frames_dev)
+        quant_embed, deq = quant_tensor(stored_table, args.quant_embed_bit)
+        expanded = [ops.embed_expand(stored_table, plan), ops.embed_expand(deq.float().contiguous(), plan)]
     for slot, net in enumerate(nets):
         net.eval()
         net.time_decode = True
@@ -562,12 +604,15 @@ def evaluate(model, full_dataloader, local_rank, args, dump_vis=False, huffman_c
             frames = frames_dev[img_idx] if frames_dev is not None else data_to_gpu(sample['img'], device)
             img_in, img_gt, _mask = args.transform_func(frames, img_idx)
             cur_input = img_in if takes_image else norm_idx
-            embed_in = dequant_embeds[i] if (slot and is_hnerv) else None
+            if from_stored:
+                embed_in = expanded[slot][img_idx]
+            else:
+                embed_in = dequant_embeds[i] if (slot and is_hnerv) else None
             extra = {}
             if args.interpolation and args.embed_inter and 'pre_img' in sample and img_idx.item() in args.val_ind_list:
                 extra = dict(pre_img=data_to_gpu(sample['pre_img'], device), post_img=data_to_gpu(sample['post_img'], device))
             out, embed_list, dec_time = net(cur_input, embed_in, norm_idx=norm_idx, **extra)
-            if slot == 0:
+            if slot == 0 and not from_stored:
                 embeds.append(embed_list[0])
             if args.eval_fps:
                 more, graph = _timed_decodes(net, cur_input, embed_list[0], norm_idx, graph)
@@ -582,7 +627,7 @@ def evaluate(model, full_dataloader, local_rank, args, dump_vis=False, huffman_c
                 fps = args.batchSize / (sum(times) / len(times))
                 log.line(f'[{log.stamp()}] Rank:{local_rank}, Eval at Step [{i + 1}/{n_batches}] , FPS {round(fps, 1)}, ' + book.describe(book.running()),
                          every_rank=False)
-        if slot == 0 and is_hnerv:
+        if slot == 0 and is_hnerv and not from_stored:
             quant_embed, deq = quant_tensor(torch.cat(embeds, 0), args.quant_embed_bit)
             dequant_embeds = deq.split(args.batchSize, dim=0)
         args.fps, hw = fps, tuple(frames.shape[-2:])

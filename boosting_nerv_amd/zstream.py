@@ -32,7 +32,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from .qstream import F16, F32, ITEMS, RUN, _Cursor, _blob, _header, magic_of, n_runs     # noqa: F401  (the shared framing; re-exported)
+from .qstream import F16, F32, ITEMS, RUN, _Cursor, _blob, _header, magic_of, n_runs, stored_frames_item     # noqa: F401  (the shared framing; re-exported)
 
 MAGIC = b"BNRZ"
 VERSION = 1
@@ -229,4 +229,5 @@ def info(path_or_buffer):
     out.update(total=total, n_records=len(zs.records), n_runs=int(sum(r.run_bits.size for r in zs.records)),
                n_symbols=int(sum(r.count for r in zs.records)), bytes=nbytes, n_zero_elements=int(zeros),
                n_zero_leaves=int(zs.settings["n_zero_leaves"]), zero_parse=zs.settings["zero_parse"])
+    out.update(stored_frames_item(zs.settings))
     return out

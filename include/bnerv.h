@@ -981,6 +981,20 @@ int bnerv_prune_masks(void* stream, const bnerv_prune_item* items, int n_items, 
 int bnerv_mask_mul(void* stream, const bnerv_prune_item* items, int n_items, const uint32_t* blocks, size_t n_blocks);
 int bnerv_grad_mask_table(void* stream, const bnerv_adan_entry* table_dev, int n_tensors, int total_blocks, const unsigned char* const* masks_dev);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Interpolation file (additive to ABI 9; csrc/interp.hip): the frame embeddings a file does not store, derived from
+ * those it stores.  out [N, P] from src [S, P] under plan_dev (device memory, N entries, hnerv_utils.interp_plan): row t of out is
+ *   ia == ib   src[ia]                                               (a stored frame, or a derived one with a stored frame on one side only)
+ *   w == 0.5f  0.5f * (src[ia] + src[ib])                            (the reference's expression, model_hnerv.py:82, :237)
+ *   otherwise  (1.0f - w) * src[ia] + w * src[ib], both products and the sum rounded to fp32 on their own (no fused contraction)
+ * -- the same bits as hnerv_utils.embed_expand_reference.  The caller validates the plan (0 <= ia, ib < S, 0 <= w < 1) before it uploads
+ * it; a row whose entry names a row outside src is left unwritten.  One streaming launch, grid (ceil(P / 1024), N): N <= 65535.
+ * Alignment: any 4-byte boundary and any P; the 16-byte form runs when P % 4 == 0 and src and out are 16-byte aligned (every row then is),
+ * the scalar form otherwise (same bits; no refusal).  src and out must not overlap.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct { int ia, ib; float w; } bnerv_interp_entry;
+int bnerv_embed_expand(void* stream, const float* src, const bnerv_interp_entry* plan_dev, float* out, int S, int N, int P);
+
 #ifdef __cplusplus
 }
 #endif
