@@ -346,6 +346,8 @@ SYMBOLS = {
     "bnerv_mask_mul": (_I, [_V, _V, _I, _V, _Z]),
     "bnerv_grad_mask_table": (_I, [_V, _V, _I, _I, _V]),
     "bnerv_embed_expand": (_I, [_V, _V, _V, _V, _I, _I, _I]),
+    "bnerv_resize_rows": (_I, [_V, _V, _V, _V, C.c_longlong, _I, _I, _I, _I]),
+    "bnerv_resize_cols": (_I, [_V, _V, _V, _V, _I, _I, _I, _I, _I, _I]),
 }
 
 _lib = None

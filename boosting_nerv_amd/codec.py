@@ -59,11 +59,17 @@ All three post-hoc kinds have an interpolation form: train_n
 stores the embeddings of the training frames only and the header key embed_stored = [N, a, b, c]; Decoder rebuilds the plan
 (hnerv_utils.interp_plan), decodes the compact [S, P] table through the launches above and fills the embeddings of all N frames in one launch
 (ops.embed_expand) -- the launch the evaluation used, so the decoded frames are the evaluated ones.  Decoder.stored_frames lists the stored
-frames, info reports n_stored_frames."""
+frames, info reports n_stored_frames.
+
+A file of any kind written by a run under --resize_list H_W holds frames of H x W: the header's crop_list, the frame size
+to every decoder, is the resized size, and one more key, source_crop, names the crop of the source the frames were resampled from.  decode
+needs nothing else; info prints the key; score takes the master through the same crop, conversion and resize (ops.resize_bicubic) and reports
+the RGB metrics only; psnr, the host plane metric, refuses such a file."""
 import argparse
 import builtins
 import json
 import os
+import re
 from types import SimpleNamespace
 
 import numpy as np
@@ -100,6 +106,11 @@ def _settings(args, n_frames, frame_hw):
     if missing:
         raise ValueError(f"codec.encode: args lacks the model settings {missing}")
     s.update(full_data_length=int(n_frames), final_size=int(frame_hw[0] * frame_hw[1]), crop_list=f"{int(frame_hw[0])}_{int(frame_hw[1])}")
+    from .resize import parse_resize
+    if parse_resize(getattr(args, "resize_list", "-1")) is not None:
+        # a resized run: crop_list above is the frame size every decoder reads; source_crop is the crop of the source the
+        # frames were resampled from, what `codec score` needs to put a master through the same crop and resize
+        s["source_crop"] = "_".join(str(int(v)) for v in str(args.crop_list).split("_")[:2])
     return s
 
 
@@ -276,7 +287,8 @@ def _frame_hw(args, frames_or_loader, seen):
     if seen is not None:
         return seen
     if hasattr(args, "crop_list"):
-        return tuple(int(v) for v in args.crop_list.split("_")[:2])
+        from .hnerv_utils import frame_hw
+        return frame_hw(args)
     if torch.is_tensor(frames_or_loader):
         return tuple(frames_or_loader.shape[-2:])
     raise ValueError("codec.encode: the frame size is unknown (no args.crop_list and no frame tensor)")
@@ -661,6 +673,9 @@ def describe_temporal(budget):
 def describe_any(budget):
     """describe, describe_posthoc, describe_sparse, describe_posthoc_temporal, describe_chunked, describe_empirical, describe_wide or describe_temporal, by
     the budget's items; an interpolation file adds how many frames' embeddings it stores."""
+    if "source_crop" in budget:
+        rest = {k: v for k, v in budget.items() if k != "source_crop"}
+        return f"{describe_any(rest)}; frames resized from a source crop of {str(budget['source_crop']).replace('_', 'x')} (source_crop {budget['source_crop']})"
     if "n_stored_frames" in budget:
         rest = {k: v for k, v in budget.items() if k != "n_stored_frames"}
         return f"{describe_any(rest)}; interpolation: the embeddings of {budget['n_stored_frames']} stored frames, every other frame derived from them"
@@ -680,9 +695,16 @@ def describe_any(budget):
 def info(path_or_buffer):
     """The bit budget of a file of any kind (bitstream.info, qstream.info, zstream.info, pstream.info, rstream.info, estream.info, wstream.info
     or tstream.info, by the magic number)."""
+    if hasattr(path_or_buffer, "read") and not hasattr(path_or_buffer, "getvalue"):
+        path_or_buffer = path_or_buffer.read()                              # (a file object is read once; it is parsed twice below)
     magic = qstream.magic_of(path_or_buffer)
-    return {qstream.MAGIC: qstream.info, zstream.MAGIC: zstream.info, pstream.MAGIC: pstream.info, rstream.MAGIC: rstream.info, estream.MAGIC: estream.info,
-            wstream.MAGIC: wstream.info, tstream.MAGIC: tstream.info}.get(magic, bitstream.info)(path_or_buffer)
+    fmt = {qstream.MAGIC: qstream, zstream.MAGIC: zstream, pstream.MAGIC: pstream, rstream.MAGIC: rstream, estream.MAGIC: estream,
+           wstream.MAGIC: wstream, tstream.MAGIC: tstream}.get(magic, bitstream)
+    budget = fmt.info(path_or_buffer)
+    source_crop = fmt.read(path_or_buffer).settings.get("source_crop")       # a resized run's file (DESIGN section 39); a key, not a budget item
+    if source_crop is not None:
+        budget["source_crop"] = source_crop
+    return budget
 
 
 def describe(budget):
@@ -839,8 +861,8 @@ def encode_posthoc(model, args, records, quant_embed, path, temporal=False):
         out.append(zstream.ZRecord(n, outer, red, inner, flag, int(keep[el:el + n].sum()), *grid) if sparse else qstream.QRecord(n, outer, red, inner, flag, *grid))
         at += k
         el += n
-    frame_hw = tuple(int(v) for v in args.crop_list.split("_")[:2])
-    s = _settings(args, args.full_data_length, frame_hw)
+    from .hnerv_utils import frame_hw
+    s = _settings(args, args.full_data_length, frame_hw(args))
     s.update(final_size=int(args.final_size), quant_model_bit=int(args.quant_model_bit), quant_embed_bit=int(args.quant_embed_bit), huff_run=qstream.RUN)
     if is_hnerv:
         s["embed_shape"] = [int(v) for v in quant_embed["quant"].shape]
@@ -888,6 +910,17 @@ def describe_sparse(budget):
     """One line of a zstream.info budget (the log of train_nerv_all --bitstream --bitstream_sparse, `codec info`)."""
     return (f"{describe_posthoc(budget)}; sparse: {budget['n_zero_elements']} zero elements in {budget['n_zero_leaves']} zero-run leaves, "
             f"parse {budget['zero_parse']}")
+
+
+def _source_crop(settings):
+    """(H, W) of a header's source_crop key (a resized run's file), None without the key."""
+    key = settings.get("source_crop")
+    if key is None:
+        return None
+    m = re.fullmatch(r"(\d+)_(\d+)", key) if isinstance(key, str) else None
+    if not m or int(m.group(1)) < 1 or int(m.group(2)) < 1:
+        raise ValueError(f"codec: the header's source_crop {key!r} is not H_W")
+    return int(m.group(1)), int(m.group(2))
 
 
 class Decoder:
@@ -1209,7 +1242,61 @@ class Decoder:
         self._events[(self.n_frames - 1) % 2].synchronize()
         yield take((self.n_frames - 1) % 2)
 
-    def score(self, ref, msssim=True, rgb=False, chunk=32):
+    def source_crop(self):
+        """(H, W) of the source crop a resized file's frames were resampled from (header key source_crop); None for a
+        file whose frames are the crop itself."""
+        return _source_crop(self.settings)
+
+    def _score_resized(self, ref, src_crop, msssim, chunk):
+        """score() of a resized file: every staged source frame through crop -> ops.yuv420_to_rgb -> ops.resize_bicubic (what the loader of
+        the run did to it), then ops.psnr / ops.msssim of the fp32 frame against it.  The source has no planes at the frame's size: the plane
+        entries are None."""
+        from . import ops
+        n, (H, W), dev = self.n_frames, self.frame_hw, self.device
+        ch, cw = (int(v) for v in src_crop)
+        window = ref.crop_window((ch, cw))                          # (NotImplementedError for a source smaller than the crop)
+        ms = bool(msssim) and min(H, W) > 160
+        names = ["psnr_rgb"] + (["msssim_rgb"] if ms else [])
+        table = torch.zeros(len(names), n, dtype=torch.float32, device=dev)
+        rows = {k: table[r] for r, k in enumerate(names)}
+        full = torch.empty(1, 3, ch, cw, dtype=torch.float32, device=dev)
+        src_rgb = torch.empty(1, 3, H, W, dtype=torch.float32, device=dev)
+        scratch = torch.empty(3 * ch * W, dtype=torch.float32, device=dev)
+        src_hw = (ref.height, ref.width)
+        chunk = max(1, min(int(chunk), n))
+        pinned = [torch.empty(chunk * ref.frame_bytes, dtype=torch.uint8, pin_memory=True) for _ in (0, 1)]
+        staged = [torch.empty(chunk * ref.frame_bytes, dtype=torch.uint8, device=dev) for _ in (0, 1)]
+        events = [torch.cuda.Event() for _ in (0, 1)]
+        with torch.cuda.device(dev):
+            for k, i0 in enumerate(builtins.range(0, n, chunk)):
+                i1, slot = min(i0 + chunk, n), k % 2
+                nbytes = (i1 - i0) * ref.frame_bytes
+                if k >= 2:
+                    events[slot].synchronize()                       # the copy that last read this pinned buffer is done
+                pinned[slot].numpy()[:nbytes] = ref.raw(i0, i1)
+                staged[slot][:nbytes].copy_(pinned[slot][:nbytes], non_blocking=True)
+                events[slot].record()
+                for i in builtins.range(i0, i1):
+                    src = staged[slot][(i - i0) * ref.frame_bytes:(i - i0 + 1) * ref.frame_bytes]
+                    out, _packed = self._launch(i)
+                    ops.yuv420_to_rgb(src, self.coeffs, 1, *src_hw, crop=window, out=full)
+                    ops.resize_bicubic(full, (H, W), out=src_rgb, scratch=scratch)
+                    rows["psnr_rgb"][i:i + 1].copy_(ops.psnr(out, src_rgb))
+                    if ms:
+                        rows["msssim_rgb"][i:i + 1].copy_(ops.msssim(out, src_rgb))
+            means = table.sum(dim=1) / float(n)
+            table_h, means_h = table.cpu().numpy(), means.cpu().numpy()      # the one read
+        result = {"sse": None, "mean": {}, "resized_from": (ch, cw)}
+        for key in ("psnr_y", "psnr_u", "psnr_v", "psnr_yuv", "msssim_y"):
+            result[key], result["mean"][key] = None, None
+        for key in ("psnr_rgb", "msssim_rgb"):
+            if key in rows:
+                result[key], result["mean"][key] = table_h[names.index(key)], float(means_h[names.index(key)])
+            else:
+                result[key], result["mean"][key] = None, None
+        return result
+
+    def score(self, ref, msssim=True, rgb=False, chunk=32, resize_from=None):
         """Every frame against the raw source `ref` (a yuvio.YuvFile of this decoder's pack format with at least len(self) frames), on the
         device.  The source goes up as it lies on disk, `chunk` frames at a time through two pinned buffers (the staging
         of YuvFile.to_device); behind every frame's launch the packed result is scored against the staged source frame -- ops.yuv420_sse,
@@ -1219,7 +1306,12 @@ class Decoder:
 
         -> {"sse": [N, 3] int64, "psnr_y" | "psnr_u" | "psnr_v" | "psnr_yuv": [N] float64 (yuvio.psnr_from_sse of the exact integers),
             "msssim_y": [N] float32, with rgb "psnr_rgb" and "msssim_rgb": [N] float32, "mean": {name: the mean of the per-frame values}}.
-        MS-SSIM needs min(H, W) > 160: below that (or with msssim=False) the MS-SSIM entries are None."""
+        MS-SSIM needs min(H, W) > 160: below that (or with msssim=False) the MS-SSIM entries are None.
+
+        A resized file (header key source_crop, written under --resize_list) is scored against the master put through
+        the run's own crop and resize: "psnr_rgb" and "msssim_rgb" as above (`rgb` is implied), while "sse", "psnr_y|u|v|yuv" and
+        "msssim_y" are None -- the source has no planes at the frame's size.  resize_from=(H, W) names the source crop of a file that does
+        not carry the key."""
         from . import ops, yuvio
         self._need_pack(True, "score")
         if ref.pix_fmt != self.pack:
@@ -1227,6 +1319,9 @@ class Decoder:
         n, (H, W) = self.n_frames, self.frame_hw
         if len(ref) < n:
             raise ValueError(f"Decoder.score: {ref.path} has {len(ref)} frames, the bitstream {n}")
+        src_crop = tuple(int(v) for v in resize_from) if resize_from is not None else _source_crop(getattr(self, "settings", None) or {})
+        if src_crop is not None:
+            return Decoder._score_resized(self, ref, src_crop, msssim, chunk)
         top, left = (v & ~1 for v in yuvio.crop_offsets(ref.height, ref.width, H, W))
         bps, src_hw, dev = ref.bytes_per_sample, (ref.height, ref.width), self.device
         ms = bool(msssim) and min(H, W) > 160
@@ -1296,6 +1391,9 @@ def _psnr(a):
     ref = yuvio.YuvFile(a.ref, w, h, a.pix_fmt)
     dec = Decoder(a.file, "cuda", use_graph=not a.no_graph, pack=ref.pix_fmt, matrix=a.matrix, range=a.range)
     H, W = dec.frame_hw
+    if dec.source_crop() is not None:
+        raise ValueError(f"codec psnr: {a.file} holds frames resized from a {'x'.join(str(v) for v in dec.source_crop())} crop: the source has no planes at "
+                         f"{H}x{W} for the plane metrics; `codec score` scores such a file in RGB against the resized source")
     if len(ref) < len(dec):
         raise ValueError(f"codec psnr: {a.ref} has {len(ref)} frames, the bitstream {len(dec)}")
     top, left = (v & ~1 for v in yuvio.crop_offsets(ref.height, ref.width, H, W))
@@ -1329,15 +1427,19 @@ def _score(a):
     got = dec.score(ref, msssim=not a.no_msssim, rgb=a.rgb)
     names = [k for k in ("psnr_y", "psnr_u", "psnr_v", "psnr_yuv", "msssim_y", "psnr_rgb", "msssim_rgb") if got.get(k) is not None]
     result = {k: got["mean"][k] for k in names}
-    result.update({f"sse_{p}": int(got["sse"][:, c].sum()) for c, p in enumerate("yuv")})
+    planes = got["sse"] is not None                 # (a resized file has no plane metrics: Decoder.score)
+    result.update({f"sse_{p}": int(got["sse"][:, c].sum()) if planes else None for c, p in enumerate("yuv")})
     result.update(frames=len(dec), pix_fmt=ref.pix_fmt, matrix=a.matrix, range=a.range)
+    if not planes:
+        result.update(source_crop="_".join(str(v) for v in got["resized_from"]))
     if a.per_frame:
         with open(a.per_frame, "w") as f:
-            f.write(",".join(["frame", "sse_y", "sse_u", "sse_v"] + names) + "\n")
+            f.write(",".join(["frame"] + (["sse_y", "sse_u", "sse_v"] if planes else []) + names) + "\n")
             for i in builtins.range(len(dec)):
-                f.write(",".join([str(i)] + [str(int(v)) for v in got["sse"][i]] + [repr(float(got[k][i])) for k in names]) + "\n")
+                f.write(",".join([str(i)] + ([str(int(v)) for v in got["sse"][i]] if planes else []) + [repr(float(got[k][i])) for k in names]) + "\n")
     print(" | ".join(f"{k.upper().replace('_', '-')} {result[k]:.4f}" + (" dB" if k.startswith("psnr") else "") for k in names)
-          + f" | {len(dec)} frames of {H}x{W}, {ref.pix_fmt}")
+          + f" | {len(dec)} frames of {H}x{W}, {ref.pix_fmt}"
+          + ("" if planes else f" | resized from a {'x'.join(str(v) for v in got['resized_from'])} crop: no source planes exist at this size, RGB metrics only"))
     print(json.dumps(result))
     return result
 

@@ -29,8 +29,17 @@ def _center_crop(img, ch, cw):
     return img.crop((left, top, left + cw, top + ch))
 
 
+def frame_hw(args):
+    """(H, W) of the frames a run trains on, decodes and stores: the --resize_list size when one is given, the --crop_list size otherwise."""
+    from .resize import parse_resize
+    size = parse_resize(getattr(args, "resize_list", "-1"))
+    return size if size is not None else tuple(int(x) for x in args.crop_list.split("_")[:2])
+
+
 class VideoDataSet(Dataset):
     """Sorted directory of frames (PNG/JPG), centre-cropped to --crop_list, ToTensor, norm_idx = (idx+1)/N  (:19-47).
+    ``--resize_list H_W`` resamples every cropped frame to H x W with the antialiased bicubic of resize.py: crop, then
+    resize, for every kind of source -- resize.resize_reference here, ops.resize_bicubic (the same bits) when the clip is made resident.
     ``--data_path synthetic:bunny | synthetic:uvg | synthetic:NxHxW`` selects the in-repo deterministic generator instead
     (no dataset ships with the reference).  A ``--data_path`` ending in ``.yuv`` is a raw planar YUV 4:2:0 clip (yuvio.YuvFile; --yuv_size,
     --yuv_fmt, --yuv_matrix, --yuv_range): same samples, same crop, decoded by the float64 restatement here and by the conversion kernel
@@ -38,6 +47,11 @@ class VideoDataSet(Dataset):
 
     def __init__(self, args):
         self.crop_h, self.crop_w = [int(x) for x in args.crop_list.split("_")[:2]]
+        from .resize import axis_table, parse_resize
+        self.frame_h, self.frame_w = frame_hw(args)
+        self.resize = parse_resize(getattr(args, "resize_list", "-1"))          # None: the frames stay at the crop size
+        if self.resize is not None:
+            axis_table(self.crop_h, self.frame_h), axis_table(self.crop_w, self.frame_w)      # (ValueError over the tap limit, before any frame is read)
         self.synthetic = None
         self.yuv = None
         if str(args.data_path).lower().endswith(".yuv"):
@@ -59,7 +73,7 @@ class VideoDataSet(Dataset):
         if getattr(args, "interpolation", False) and len(self.samples) % 2 == 0:
             self.samples.pop()
         self.crop = True
-        self.final_size = self.crop_h * self.crop_w
+        self.final_size = self.frame_h * self.frame_w
         self.embed_inter = getattr(args, "embed_inter", False) and getattr(args, "interpolation", False)
         if self.synthetic is None and self.yuv is None:
             from PIL import Image
@@ -70,22 +84,48 @@ class VideoDataSet(Dataset):
     def __len__(self):
         return len(self.samples)
 
-    def _load(self, idx):
+    def _load_crop(self, idx):
+        """Frame idx at the crop size, before any resize."""
         if self.synthetic is not None:
-            if idx not in self._cache:
-                self._cache[idx] = self.synthetic.frame(idx)
-            return self._cache[idx]
+            return self.synthetic.frame(idx)
         if self.yuv is not None:
             return torch.from_numpy(self.yuv.frame_rgb(self.samples[idx], (self.crop_h, self.crop_w), self.yuv_matrix, self.yuv_range))
         from PIL import Image
         return _to_tensor(_center_crop(Image.open(self.samples[idx]).convert("RGB"), self.crop_h, self.crop_w))
 
-    def to_device(self, device):
+    def _load(self, idx):
+        if self.synthetic is not None and idx in self._cache:
+            return self._cache[idx]
+        img = self._load_crop(idx)
+        if self.resize is not None:
+            from .resize import resize_reference
+            img = resize_reference(img, self.resize)
+        if self.synthetic is not None:
+            self._cache[idx] = img
+        return img
+
+    def to_device(self, device, chunk=32):
         """The clip as a resident [N, 3, H, W] fp32 device tensor: a raw YUV clip goes up as it lies in the file and is converted there
-        (YuvFile.to_device, no host fp32 frames); every other source is stacked on the host and uploaded."""
+        (YuvFile.to_device, no host fp32 frames); every other source is stacked on the host and uploaded.  Under --resize_list the frames go
+        up at the crop size `chunk` at a time and are resampled into their slice of the clip (ops.resize_bicubic): the full-size clip never
+        exists on the device."""
         if self.yuv is not None:
-            return self.yuv.to_device(device, crop=(self.crop_h, self.crop_w), matrix=self.yuv_matrix, range=self.yuv_range, count=len(self.samples))
-        return torch.stack([self[i]['img'] for i in range(len(self))]).to(device)
+            return self.yuv.to_device(device, chunk=chunk, crop=(self.crop_h, self.crop_w), matrix=self.yuv_matrix, range=self.yuv_range,
+                                      count=len(self.samples), resize=self.resize)
+        if self.resize is None:
+            return torch.stack([self[i]['img'] for i in range(len(self))]).to(device)
+        device = torch.device(device)
+        n = len(self)
+        chunk = max(1, min(int(chunk), n))
+        clip = torch.empty(n, 3, self.frame_h, self.frame_w, dtype=torch.float32, device=device)
+        scratch = torch.empty(chunk * 3 * self.crop_h * self.frame_w, dtype=torch.float32, device=device)
+        with torch.cuda.device(device):
+            for i0 in range(0, n, chunk):
+                i1 = min(i0 + chunk, n)
+                full = torch.stack([self._load_crop(i) for i in range(i0, i1)]).to(device)
+                ops.resize_bicubic(full, self.resize, out=clip[i0:i1], scratch=scratch)
+            torch.cuda.current_stream().synchronize()
+        return clip
 
     def __getitem__(self, idx):
         img = self._load(idx)

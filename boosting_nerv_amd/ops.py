@@ -2553,6 +2553,61 @@ def embed_expand(src, plan, out=None):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# frame resize (csrc/resize.hip; boosting_nerv_amd/resize.py holds the definition)
+# ----------------------------------------------------------------------------------------------------------------------
+_resize_tables = {}      # (n_in, n_out, device) -> (packed table on the device, T, LDS span of the row pass)
+
+
+def _resize_table(n_in, n_out, device):
+    """The device table of one axis (resize.pack_table), uploaded once per (n_in, n_out, device).  Raises ValueError over the tap limit."""
+    from . import resize as R
+    key = (int(n_in), int(n_out), str(device))
+    if key not in _resize_tables:
+        first, count, w = R.axis_table(n_in, n_out)
+        _resize_tables[key] = (_upload(R.pack_table(first, count, w), device).view(torch.int32), int(w.shape[1]), R.strip_span(first, count))
+    return _resize_tables[key]
+
+
+def _spans_overlap(a, b):
+    return a.data_ptr() < b.data_ptr() + b.numel() * b.element_size() and b.data_ptr() < a.data_ptr() + a.numel() * a.element_size()
+
+
+def resize_bicubic(x, size, clamp=True, out=None, scratch=None):
+    """x [B, C, H, W] fp32 on the device -> [B, C, h, w], size = (h, w): the antialiased bicubic of resize.resize_reference, bit for bit.
+    Two launches: rows [B*C, H, W] -> [B*C, H, w] into `scratch` (bnerv_resize_rows), columns -> [B*C, h, w] (bnerv_resize_cols), the clamp
+    to [0, 1] in the second.  x, out and scratch (a contiguous fp32 tensor of at least B*C*H*w elements) are used in place at any 4-byte
+    boundary; the 16-byte forms run where they can.  An axis over the tap limit is refused (ValueError) before any launch."""
+    L.require_device(x, "resize_bicubic: x")
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError(f"resize_bicubic: need a non-empty contiguous fp32 [B, C, H, W] tensor, got {x.dtype} {tuple(x.shape)}")
+    B, Cc, H, W = (int(v) for v in x.shape)
+    h, w = (int(v) for v in size)
+    if h < 1 or w < 1:
+        raise ValueError(f"resize_bicubic: size {h}x{w}")
+    tab_w, T_w, span = _resize_table(W, w, x.device)          # (both tables before any launch: the tap limit is refused here)
+    tab_h, T_h, _ = _resize_table(H, h, x.device)
+    planes = B * Cc
+    if planes > 65535:
+        raise ValueError(f"resize_bicubic: {planes} planes (at most 65535 per call)")
+    if out is None:
+        out = torch.empty(B, Cc, h, w, dtype=torch.float32, device=x.device)
+    elif (not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (B, Cc, h, w) or not out.is_contiguous() or out.device != x.device):
+        raise ValueError(f"resize_bicubic: out must be a contiguous fp32 [{B}, {Cc}, {h}, {w}] tensor on {x.device}")
+    if _spans_overlap(x, out):
+        raise ValueError("resize_bicubic: x and out overlap")
+    need = planes * H * w
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.float32, device=x.device)
+    elif (not scratch.is_cuda or scratch.dtype != torch.float32 or not scratch.is_contiguous() or scratch.numel() < need or scratch.device != x.device
+          or _spans_overlap(scratch, x) or _spans_overlap(scratch, out)):
+        raise ValueError(f"resize_bicubic: scratch must be a contiguous fp32 tensor of at least {need} elements on {x.device}, apart from x and out")
+    lib = L.load()
+    L.check(lib.bnerv_resize_rows(L.stream(), L.ptr(x), L.ptr(scratch), L.ptr(tab_w), planes * H, W, w, T_w, span), "bnerv_resize_rows")
+    L.check(lib.bnerv_resize_cols(L.stream(), L.ptr(scratch), L.ptr(out), L.ptr(tab_h), planes, H, h, w, T_h, 1 if clamp else 0), "bnerv_resize_cols")
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # global magnitude pruning (csrc/prune.hip; boosting_nerv_amd/prune.py drives it)
 # ----------------------------------------------------------------------------------------------------------------------
 class PruneTable:

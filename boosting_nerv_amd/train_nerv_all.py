@@ -29,7 +29,7 @@ from . import runtime as rt
 from . import yuvloss
 from .dp import GradBucket
 from .engine import TrainStep
-from .hnerv_utils import TransformInput, VideoDataSet, adjust_lr, data_split, interp_plan, loss_fn, psnr_fn_device, quant_tensor, quant_tensor_sparse, worker_init_fn
+from .hnerv_utils import TransformInput, VideoDataSet, adjust_lr, frame_hw, data_split, interp_plan, loss_fn, psnr_fn_device, quant_tensor, quant_tensor_sparse, worker_init_fn
 from .model_enerv import ENeRV_Boost
 from .model_hnerv import HNeRV, HNeRV_Boost
 from .model_nerv import NeRV_Boost
@@ -364,7 +364,7 @@ def train(local_rank, args):
             rt.write_results_csv(args, top, values, [torch.tensor(0)], 'eval.csv')
         return
 
-    h, w = (int(x) for x in args.crop_list.split('_')[:2])
+    h, w = frame_hw(args)
     takes_image = 'pe' not in args.embed or "HNeRV_Boost" in args.model
     mode = step_mode(optimizer, args)                                                 # "captured": Adan, and Adam for the HNeRV baseline
     # the reference's masks depend on the frame size only: built once, on a dummy frame of the crop size (None without --inpanting)
@@ -378,6 +378,9 @@ def train(local_rank, args):
              + f', inpainting mask: {args.inpanting if mask is not None else "none"}, clip_max_norm: {args.clip_max_norm}', echo=False)
     if yuv_term is not None:
         log.line(yuvloss.describe(yuv_term), echo=False)
+    if full_dataset.resize is not None:
+        from .resize import describe as describe_resize
+        log.line(describe_resize((full_dataset.crop_h, full_dataset.crop_w), full_dataset.resize), echo=False)
     if args.embed_inter_stored:
         stored, _ = interp_plan(args.full_data_length, args.data_split)
         log.line(f'Interpolation: {len(stored)} of {args.full_data_length} frames stored, {args.full_data_length - len(stored)} derived '

@@ -23,7 +23,7 @@ from . import runtime as rt
 from . import train_nerv_all as T
 from . import yuvloss
 from .dp import GradBucket
-from .hnerv_utils import TransformInput, adjust_lr, loss_fn
+from .hnerv_utils import TransformInput, adjust_lr, frame_hw, loss_fn
 from .lib.entropy_model import DiffEntropyModel
 from .lib.quant_ops import CustomConv2d, CustomLinear
 
@@ -209,7 +209,7 @@ def train(local_rank, args):
         return
 
     model.init_data()                                                  # quantiser scales from the current weight ranges (:338)
-    h_, w_ = (int(v) for v in args.crop_list.split('_')[:2])
+    h_, w_ = frame_hw(args)
     fused = hasattr(optimizer, 'prepare_step') and args.transform_func.identity and args.clip_max_norm <= 0 and not getattr(args, 'no_graph', False)
     cstep = None
     if fused:
@@ -217,6 +217,9 @@ def train(local_rank, args):
         cstep = CompressionStep(model, optimizer, entropy_model, args, (args.batchSize, 3, h_, w_), device, world_size=world, yuv=yuv_term)
     if yuv_term is not None:
         log.line(yuvloss.describe(yuv_term), echo=False)
+    if full_dataset.resize is not None:
+        from .resize import describe as describe_resize
+        log.line(describe_resize((full_dataset.crop_h, full_dataset.crop_w), full_dataset.resize), echo=False)
     bucket = GradBucket(model.parameters()) if (cstep is None and world > 1) else None
 
     t_start = time.time()

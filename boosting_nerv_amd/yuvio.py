@@ -302,9 +302,11 @@ class YuvFile:
         """Frame i as fp32 [3, ch, cw] through the float64 restatement (the host path)."""
         return to_rgb_reference(*self.planes(i), coefficients(matrix, range, self.depth), self.crop_window(crop)).astype(np.float32)
 
-    def to_device(self, device, chunk=32, crop=None, matrix="bt709", range="limited", count=None):
+    def to_device(self, device, chunk=32, crop=None, matrix="bt709", range="limited", count=None, resize=None):
         """The first `count` (default: all) frames as a resident [N, 3, ch, cw] fp32 clip.  Chunks of frames go through two pinned buffers --
-        the host fills one while the copy engine drains the other -- and every chunk is converted with ONE kernel launch."""
+        the host fills one while the copy engine drains the other -- and every chunk is converted with ONE kernel launch.
+        resize=(h, w): the clip is [N, 3, h, w]; every chunk is converted into a chunk-sized fp32 scratch and resampled from there into its
+        slice of the clip (ops.resize_bicubic): the full-size fp32 clip never exists on the device."""
         import torch
         from . import ops
         device = torch.device(device)
@@ -316,7 +318,13 @@ class YuvFile:
         top, left, ch, cw = self.crop_window(crop)
         coeffs = coefficients(matrix, range, self.depth)
         chunk = max(1, min(int(chunk), n))
-        clip = torch.empty(n, 3, ch, cw, dtype=torch.float32, device=device)
+        if resize is None:
+            clip = torch.empty(n, 3, ch, cw, dtype=torch.float32, device=device)
+        else:
+            rh, rw = (int(v) for v in resize)
+            clip = torch.empty(n, 3, rh, rw, dtype=torch.float32, device=device)
+            full = torch.empty(chunk, 3, ch, cw, dtype=torch.float32, device=device)
+            scratch = torch.empty(chunk * 3 * ch * rw, dtype=torch.float32, device=device)
         pinned = [torch.empty(chunk * self.frame_bytes, dtype=torch.uint8, pin_memory=True) for _ in (0, 1)]
         staged = [torch.empty(chunk * self.frame_bytes, dtype=torch.uint8, device=device) for _ in (0, 1)]
         events = [torch.cuda.Event() for _ in (0, 1)]
@@ -329,7 +337,11 @@ class YuvFile:
                 pinned[slot].numpy()[:nbytes] = self.raw(i0, i1)
                 staged[slot][:nbytes].copy_(pinned[slot][:nbytes], non_blocking=True)
                 events[slot].record()
-                ops.yuv420_to_rgb(staged[slot], coeffs, i1 - i0, self.height, self.width, crop=(top, left, ch, cw), out=clip[i0:i1])
+                if resize is None:
+                    ops.yuv420_to_rgb(staged[slot], coeffs, i1 - i0, self.height, self.width, crop=(top, left, ch, cw), out=clip[i0:i1])
+                else:
+                    ops.yuv420_to_rgb(staged[slot], coeffs, i1 - i0, self.height, self.width, crop=(top, left, ch, cw), out=full[:i1 - i0])
+                    ops.resize_bicubic(full[:i1 - i0], (rh, rw), out=clip[i0:i1], scratch=scratch)
             torch.cuda.current_stream().synchronize()
         return clip
 

@@ -34,16 +34,24 @@ def check_flags(args):
     pure = args.loss == PURE
     if pure and args.yuv_loss == 0:
         args.yuv_loss = 1.0
+    from .resize import parse_resize
+    resize = parse_resize(getattr(args, "resize_list", "-1"))             # (ValueError for anything but -1 or H_W)
+    if resize is not None and getattr(args, "embed_inter", False):
+        raise ValueError(f"--resize_list {args.resize_list} with --embed_inter: the neighbour frames of a held-out frame come through the host loader "
+                         "only; --embed_inter_stored interpolates from stored embeddings instead")
     if not (args.yuv_loss > 0 or ms > 0):
         return args
     what = f"--loss {PURE}" if pure else ("--yuv_loss" if args.yuv_loss > 0 else "--yuv_msssim")
+    if resize is not None:
+        raise ValueError(f"{what} with --resize_list {args.resize_list}: the raw source has no planes at the resized frame's size to compare against")
     if getattr(args, "inpanting", "none") != "none":
         raise ValueError(f"{what} with --inpanting {args.inpanting}: the plane loss has no masked form")
     if getattr(args, "host_frames", False) or getattr(args, "embed_inter", False):
         raise ValueError(f"{what} needs the clip resident on the device: drop --host_frames / --embed_inter")
     if not str(args.data_path).lower().endswith(".yuv"):
         raise ValueError(f"{what} compares against the planes of a raw source: --data_path {args.data_path} is no .yuv file")
-    h, w = (int(v) for v in args.crop_list.split('_')[:2])
+    from .hnerv_utils import frame_hw
+    h, w = frame_hw(args)
     if h % 2 or w % 2:
         raise ValueError(f"{what}: 4:2:0 needs an even crop, --crop_list gives {h}x{w}")
     if ms > 0 and min(h, w) <= 160:

@@ -995,6 +995,32 @@ int bnerv_grad_mask_table(void* stream, const bnerv_adan_entry* table_dev, int n
 typedef struct { int ia, ib; float w; } bnerv_interp_entry;
 int bnerv_embed_expand(void* stream, const float* src, const bnerv_interp_entry* plan_dev, float* out, int S, int N, int P);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Frame resize (additive to ABI 9; csrc/resize.hip): the separable antialiased bicubic of boosting_nerv_amd/resize.py,
+ * one axis per launch.  Every output sample is  acc = fp32(acc + fp32(w_j * x_j))  over its taps in ascending j from 0.0f, the product
+ * and the sum rounded on their own (no fused contraction) -- the bits of resize.resize_reference.
+ *
+ * table_dev (device memory, 4-byte aligned, (2 + 2 T) n_out words; resize.axis_table makes it, resize.pack_table lays it out):
+ *   int32 first[n_out] | int32 count[n_out] | fp32 weights[n_out][T] | fp32 weights transposed [T][n_out]
+ * Output sample i reads input first[i] .. first[i] + count[i] - 1 of its axis; 1 <= T <= BNERV_RESIZE_MAX_TAPS.  The caller validates the
+ * table before it uploads it; a kernel clamps what it reads of it (first, count) to the axis, so a bad table cannot become a wild read.
+ *
+ *   bnerv_resize_rows  x [rows, n_in] -> out [rows, n_out] along the last axis.  A block stages the input span of BNERV_RESIZE_STRIP
+ *                      output columns for a group of rows in LDS (coalesced reads whatever the scale; 16-byte loads when n_in % 4 == 0 and
+ *                      x is 16-byte aligned), taps are LDS reads.  `span` is the LDS pitch of a row in floats: a multiple of 4, at least
+ *                      max over strips of (first[last] + count[last] - (first[first of strip] & ~3)) (resize.strip_span); the rows per
+ *                      block are sized from it here (16, or 4 when 16 rows of `span` floats exceed 48 KiB; 4 rows of the largest span a
+ *                      table of <= 64 taps can have always fit).
+ *   bnerv_resize_cols  x [planes, n_in, width] -> out [planes, n_out, width] along the middle axis: consecutive lanes take consecutive
+ *                      columns, every tap row is a coalesced read; 16-byte loads and stores when width % 4 == 0 and x and out are 16-byte
+ *                      aligned, the scalar form otherwise (same bits).  clamp != 0: the result is clamped to [0, 1].
+ * x and out: any 4-byte boundary, no overlap.  No atomics, no workspace; rows <= 2^27, planes <= 65535, n_out <= 262140 (cols).
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define BNERV_RESIZE_MAX_TAPS 64
+#define BNERV_RESIZE_STRIP 64
+int bnerv_resize_rows(void* stream, const float* x, float* out, const void* table_dev, long long rows, int n_in, int n_out, int T, int span);
+int bnerv_resize_cols(void* stream, const float* x, float* out, const void* table_dev, int planes, int n_in, int n_out, int width, int T, int clamp);
+
 #ifdef __cplusplus
 }
 #endif
