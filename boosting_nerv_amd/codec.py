@@ -70,15 +70,25 @@ import builtins
 import json
 import os
 import re
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
-from . import bitstream, estream, pstream, qstream, rstream, tstream, wstream, zstream
+from . import bitstream, container, estream, pstream, qstream, rstream, tstream, wstream, zstream
 from .bitstream import Record
 
 TABLES = ("gaussian", "empirical")
+Kind = namedtuple("Kind", "fmt name who posthoc")         # a kind of file: its module, Decoder.kind, the name in the decoder's refusals, post-hoc or CEM
+KINDS = {k.fmt.MAGIC: k for k in (Kind(bitstream, "cem", "bitstream", False), Kind(qstream, "posthoc", "qstream", True), Kind(zstream, "sparse", "zstream", True),
+                                  Kind(pstream, "posthoc_temporal", "pstream", True), Kind(rstream, "chunked", "rstream", False),
+                                  Kind(estream, "empirical", "estream", False), Kind(wstream, "wide", "wstream", False), Kind(tstream, "temporal", "tstream", False))}
+
+
+def _kind_of(src):
+    """The row of KINDS a file's magic number names; any other file is taken for the version-1 kind, whose reader then refuses it."""
+    return KINDS.get(container.magic_of(src), KINDS[bitstream.MAGIC])
 
 # the settings the model constructors read (model_nerv.py, model_hnerv.py, model_enerv.py, model_blocks.py), resolved: fc_dim after the size
 # solver, enc_dim after its rewrite -- the architecture rows of args.yaml
@@ -294,14 +304,6 @@ def _frame_hw(args, frames_or_loader, seen):
     raise ValueError("codec.encode: the frame size is unknown (no args.crop_list and no frame tensor)")
 
 
-def _write_blob(dst, blob):
-    if hasattr(dst, "write"):
-        dst.write(blob)
-    else:
-        with open(dst, "wb") as f:
-            f.write(blob)
-
-
 def _too_wide(who, lo, hi):
     if hi - lo + 1 > rstream.MAX_ALPHABET:
         raise NotImplementedError(f"{who}: a record's symbols span [{lo}, {hi}]: {hi - lo + 1} values; the chunked kind carries "
@@ -346,9 +348,7 @@ def check_temporal_model(name):
 
 
 def _record_bytes(rec):
-    out = []
-    wstream._pack_record(out, rec, rec.beta is not None)
-    return sum(len(b) for b in out)
+    return len(rstream.record_bytes(wstream.KIND, rec, rec.beta is not None))
 
 
 def _embed_pred(intra, inter):
@@ -485,10 +485,10 @@ def _encode_empirical(model, entropy_model, args, frames_or_loader, path, run, w
         settings = dict(_settings(args, n_frames, frame_hw), ans_run=run, ans_tables=wide, ans_wide=True)
         if temporal:
             blob = tstream.to_bytes(dict(settings, embed_pred=tstream.EMBED_PRED), records[:n_tensors], records[n_tensors:], preds, embed_shape, raw, words)
-            _write_blob(path, blob)
+            container.write_blob(path, blob)
             return tstream.info(blob)
         blob = wstream.to_bytes(settings, records[:n_tensors], records[n_tensors:], embed_shape, raw, words)
-        _write_blob(path, blob)
+        container.write_blob(path, blob)
         return wstream.info(blob)
     counts = ops.SymHist([(s, r[4], r[5] - r[4] + 1) for s, r in zip(symbols, sides)]).launch().check().host()
     items = []
@@ -505,7 +505,7 @@ def _encode_empirical(model, entropy_model, args, frames_or_loader, path, run, w
     words = enc.compact(chosen, run_words).launch().check().host()
     settings = dict(_settings(args, n_frames, frame_hw), ans_run=run, ans_tables="empirical")
     blob = estream.to_bytes(settings, records[:n_tensors], records[n_tensors:], embed_shape, raw, words)
-    _write_blob(path, blob)
+    container.write_blob(path, blob)
     return estream.info(blob)
 
 
@@ -513,7 +513,7 @@ def _repack_empirical(src, dst, run):
     """repack(..., tables="empirical"): the host oracle of _encode_empirical -- the same tables, the same coder arithmetic (csrc/ans.cpp), the
     same choice rule, from the symbols of a version-1 or a chunked file."""
     from .lib.entropy_model import ans_counts_cdf, ans_decode_gaussian, ans_encode_table_runs, ans_gaussian_cdf
-    chunked = qstream.magic_of(src) == rstream.MAGIC
+    chunked = container.magic_of(src) == rstream.MAGIC
     bs = rstream.read(src) if chunked else bitstream.read(src)
     settings = dict(bs.settings, ans_run=run, ans_tables="empirical")
     words = []
@@ -530,7 +530,7 @@ def _repack_empirical(src, dst, run):
     tensors = [chunk(k, r) for k, r in enumerate(bs.tensors)]
     embeds = [chunk(len(tensors) + k, r) for k, r in enumerate(bs.embeds)]
     blob = estream.to_bytes(settings, tensors, embeds, bs.embed_shape, bs.raw, np.concatenate(words) if words else np.zeros(0, dtype=np.uint32))
-    _write_blob(dst, blob)
+    container.write_blob(dst, blob)
     return estream.info(blob)
 
 
@@ -539,7 +539,7 @@ def _repack_wide(src, dst, run, tables, temporal=False):
     rule, from the symbols of a version-1 or a chunked (BNRC) file.  temporal: the oracle of encode(..., temporal=True) -- every frame t >= 1
     also as the record of its differences to the frame before, the cheaper of the two kept (_embed_pred)."""
     from .lib.entropy_model import ans_counts_cdf, ans_decode_gaussian, ans_encode_wide_runs, ans_gaussian_bucket_cdf
-    chunked = qstream.magic_of(src) == rstream.MAGIC
+    chunked = container.magic_of(src) == rstream.MAGIC
     bs = rstream.read(src) if chunked else bitstream.read(src)
     settings = dict(bs.settings, ans_run=run, ans_tables=tables, ans_wide=True)
     words = []
@@ -586,10 +586,10 @@ def _repack_wide(src, dst, run, tables, temporal=False):
         if not embeds:
             raise ValueError(f"codec.repack: a {settings.get('model')} file has no frame embeddings to predict; write the wide kind")
         blob = tstream.to_bytes(dict(settings, embed_pred=tstream.EMBED_PRED), tensors, embeds, preds, bs.embed_shape, bs.raw, words)
-        _write_blob(dst, blob)
+        container.write_blob(dst, blob)
         return tstream.info(blob)
     blob = wstream.to_bytes(settings, tensors, embeds, bs.embed_shape, bs.raw, words)
-    _write_blob(dst, blob)
+    container.write_blob(dst, blob)
     return wstream.info(blob)
 
 
@@ -607,7 +607,7 @@ def repack(src, dst, run=1024, tables="gaussian", wide=False, temporal=False):
 
     temporal=True (with wide=True): the temporal kind (tstream.py), the host oracle of encode(..., temporal=True).  Returns tstream.info."""
     from .lib.entropy_model import ans_decode_gaussian, ans_encode_gaussian_runs
-    if qstream.magic_of(src) in (qstream.MAGIC, zstream.MAGIC, pstream.MAGIC):
+    if _kind_of(src).posthoc:
         raise NotImplementedError("codec.repack: a post-hoc file is not repacked.  A .bnrq twin was quantised with its zeros on the grid, so the pruned "
                                   "weights are no longer zero in it and no sparse (.bnrz) file can be made from it; write one from the checkpoint: "
                                   "train_nerv_all.py --eval_only --weight ... --bitstream FILE --bitstream_sparse")
@@ -637,7 +637,7 @@ def repack(src, dst, run=1024, tables="gaussian", wide=False, temporal=False):
     tensors = [chunk(r) for r in bs.tensors]
     embeds = [chunk(r) for r in bs.embeds]
     blob = rstream.to_bytes(settings, tensors, embeds, bs.embed_shape, bs.raw, np.concatenate(words) if words else np.zeros(0, dtype=np.uint32))
-    _write_blob(dst, blob)
+    container.write_blob(dst, blob)
     return rstream.info(blob)
 
 
@@ -697,9 +697,7 @@ def info(path_or_buffer):
     or tstream.info, by the magic number)."""
     if hasattr(path_or_buffer, "read") and not hasattr(path_or_buffer, "getvalue"):
         path_or_buffer = path_or_buffer.read()                              # (a file object is read once; it is parsed twice below)
-    magic = qstream.magic_of(path_or_buffer)
-    fmt = {qstream.MAGIC: qstream, zstream.MAGIC: zstream, pstream.MAGIC: pstream, rstream.MAGIC: rstream, estream.MAGIC: estream,
-           wstream.MAGIC: wstream, tstream.MAGIC: tstream}.get(magic, bitstream)
+    fmt = _kind_of(path_or_buffer).fmt
     budget = fmt.info(path_or_buffer)
     source_crop = fmt.read(path_or_buffer).settings.get("source_crop")       # a resized run's file (DESIGN section 39); a key, not a budget item
     if source_crop is not None:
@@ -884,10 +882,10 @@ def encode_posthoc(model, args, records, quant_embed, path, temporal=False):
         embeds = pstream.PEmbeds(tuple(int(v) for v in q.shape), outer, red, inner, flag, *grid, *code_embeds(q.detach().reshape(q.shape[0], -1), qstream.RUN))
         s.update(embed_pred=pstream.EMBED_PRED, tensor_kind="sparse" if sparse else "dense")
         blob = pstream.to_bytes(s, lengths, out, words, embeds)
-        _write_blob(path, blob)
+        container.write_blob(path, blob)
         return pstream.info(blob)
     blob = (zstream if sparse else qstream).to_bytes(s, lengths, out, words)
-    _write_blob(path, blob)
+    container.write_blob(path, blob)
     return (zstream if sparse else qstream).info(blob)
 
 
@@ -945,14 +943,12 @@ class Decoder:
         from . import ops
         from .lib.entropy_model import ans_decode_gaussian
         from .train_nerv_all import build_model
-        magic = qstream.magic_of(path)
-        self.kind = {qstream.MAGIC: "posthoc", zstream.MAGIC: "sparse", pstream.MAGIC: "posthoc_temporal", rstream.MAGIC: "chunked", estream.MAGIC: "empirical", wstream.MAGIC: "wide",
-                     tstream.MAGIC: "temporal"}.get(magic, "cem")
-        if self.kind in ("posthoc", "sparse", "posthoc_temporal"):
-            {"posthoc": self._load_posthoc, "sparse": self._load_sparse, "posthoc_temporal": self._load_posthoc_temporal}[self.kind](path, device)
+        kind = _kind_of(path)
+        self.kind, what = kind.name, kind.who
+        if kind.posthoc:
+            getattr(self, "_load_" + kind.name)(path, device)
             return self._frame_loop(use_graph, pack, matrix, range)
-        bs = {"chunked": rstream.read, "empirical": estream.read, "wide": wstream.read, "temporal": tstream.read}.get(self.kind, bitstream.read)(path)
-        what = {"chunked": "rstream", "empirical": "estream", "wide": "wstream", "temporal": "tstream"}.get(self.kind, "bitstream")
+        bs = kind.fmt.read(path)
         s = dict(bs.settings)
         if s.get("model") not in MODELS:
             raise ValueError(f"{what}: header names the model {s.get('model')!r}; this build decodes {', '.join(MODELS)}")

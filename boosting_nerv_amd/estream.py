@@ -3,7 +3,8 @@ every record cut into runs that are range-ANS coded independently and decoded by
 either under the Gaussian of its (mean, std), as there, or under a table of its own symbol frequencies that the file carries, whichever
 makes the file smaller.
 
-Host-only code (numpy and struct), little-endian throughout; the framing is rstream.py's:
+Host-only code (numpy and struct), little-endian throughout; the framing is container.py's and the payload around the records rstream.py's
+(DESIGN section 40).  The Gaussian-or-table half of a record -- model_bytes(), read_model() -- is shared with wstream.py:
 
     magic "BNRE" | version u32 (1) | payload length u64 | payload | CRC32(payload) u32
 
@@ -23,19 +24,17 @@ raw section, runs, the two state words of a run -- is rstream.py's.
 read() raises ValueError wherever rstream.read does, and for a header without "ans_tables": "empirical", a model byte other than 0 or 1, a
 LEB128 value that runs past the payload, exceeds 2^24 or is padded with an empty last byte (one content, one file), and frequencies that
 do not sum to 2^24.  info() books every bit of the file under one of eight items."""
-import json
 import struct
-import zlib
 from collections import namedtuple
 
 import numpy as np
 
-from .bitstream import _blob
-from .rstream import MAX_ALPHABET, PAD_WORDS, _F32, _PREFIX, _U32, check_run, n_runs
+from . import container, rstream
+from .rstream import MAX_ALPHABET, PAD_WORDS, check_run, n_runs, record_words      # noqa: F401  (re-exported)
 
 MAGIC = b"BNRE"
 VERSION = 1
-TOTAL = 1 << 24                            # slots of a table (the coder's 24-bit probabilities)
+TOTAL = container.LEB128_MAX               # slots of a table (the coder's 24-bit probabilities)
 GAUSSIAN, TABLE = 0, 1                     # the model byte
 _HEAD = struct.Struct("<IfiiB")            # count, scale, lo, hi, model
 _MOMENTS = struct.Struct("<ff")            # mean, std
@@ -66,167 +65,63 @@ def table_bytes(freq):
     return leb128(np.asarray(freq, dtype=np.int64) - 1)
 
 
-def _pack_record(out, r, with_beta):
-    out.append(_HEAD.pack(int(r.count), np.float32(r.scale), int(r.lo), int(r.hi), int(r.model)))
+def model_bytes(who, r, n, where):
+    """What follows a record's model byte: mean and std, or the table of its n frequencies; where: the record's place, for the refusal."""
     if r.model == GAUSSIAN:
-        out.append(_MOMENTS.pack(np.float32(r.mean), np.float32(r.std)))
-    elif r.model == TABLE:
-        f = np.asarray(r.freq, dtype=np.int64).reshape(-1)
-        if f.size != r.hi - r.lo + 1 or int(f.min()) < 1 or int(f.sum()) != TOTAL:
-            raise ValueError(f"estream.write: a table of {f.size} frequencies (sum {int(f.sum())}, smallest {int(f.min())}) on the range [{r.lo}, {r.hi}]")
-        out.append(table_bytes(f))
-    else:
-        raise ValueError(f"estream.write: model {r.model!r} (0: Gaussian, 1: table)")
-    out.append(np.ascontiguousarray(r.run_words, dtype="<u2").tobytes())
-    if with_beta:
-        out.append(_F32.pack(np.float32(r.beta)))
+        return _MOMENTS.pack(np.float32(r.mean), np.float32(r.std))
+    if r.model != TABLE:
+        raise ValueError(f"{who}.write: model {r.model!r} (0: Gaussian, 1: table)")
+    f = np.asarray(r.freq, dtype=np.int64).reshape(-1)
+    if f.size != n or int(f.min()) < 1 or int(f.sum()) != TOTAL:
+        raise ValueError(f"{who}.write: a table of {f.size} frequencies (sum {int(f.sum())}, smallest {int(f.min())}) on the range {where}")
+    return table_bytes(f)
 
 
-def _payload(settings, tensors, embeds, embed_shape, raw, words):
-    run = check_run(settings.get("ans_run"))
+def read_model(cur, side, model, n):
+    """What model_bytes wrote -> (mean, std, freq): two np.float32 and None, or None twice and the n uint32 frequencies."""
+    if model == GAUSSIAN:
+        return (*(np.float32(v) for v in cur.unpack(_MOMENTS, side)), None)
+    if model != TABLE:
+        raise ValueError(f"{cur.who}: a record's model byte is {model} (0: Gaussian, 1: table)")
+    freq = np.fromiter((cur.leb128("tables") + 1 for _ in range(n)), dtype=np.int64, count=n)
+    if int(freq.sum()) != TOTAL:
+        raise ValueError(f"{cur.who}: the frequencies of a record's table sum to {int(freq.sum())}, not 2^24")
+    return None, None, freq.astype(np.uint32)
+
+
+def _pack_head(r):
+    return (_HEAD.pack(int(r.count), np.float32(r.scale), int(r.lo), int(r.hi), int(r.model))
+            + model_bytes("estream", r, r.hi - r.lo + 1, f"[{r.lo}, {r.hi}]"))
+
+
+def _read_head(cur, side):
+    count, scale, lo, hi, model = cur.unpack(_HEAD, side)
+    rstream.check_range(cur.who, count, lo, hi)
+    return (count, np.float32(scale), lo, hi, model, *read_model(cur, side, model, hi - lo + 1))
+
+
+def _check_settings(who, settings):
+    run = check_run(settings.get("ans_run") if isinstance(settings, dict) else None)
     if settings.get("ans_tables") != "empirical":
-        raise ValueError('estream.write: the settings need "ans_tables": "empirical"')
-    header = json.dumps(settings, sort_keys=True, separators=(",", ":")).encode("utf-8")
-    out = [_U32.pack(len(header)), header, _U32.pack(len(tensors))]
-    for r in list(tensors) + list(embeds):
-        if len(r.run_words) != n_runs(r.count, run):
-            raise ValueError(f"estream.write: a record of {r.count} symbols with {len(r.run_words)} run lengths (runs of {run})")
-    for r in tensors:
-        _pack_record(out, r, False)
-    if embeds and embed_shape is None:
-        raise ValueError("estream.write: embedding records need embed_shape (C, h, w)")
-    out.append(struct.pack("<IIII", len(embeds), *(embed_shape if embeds else (0, 0, 0))))
-    for r in embeds:
-        _pack_record(out, r, True)
-    out.append(_U32.pack(len(raw)))
-    for a in raw:
-        a = np.ascontiguousarray(a, dtype="<f4").reshape(-1)
-        out.append(_U32.pack(a.size))
-        out.append(a.tobytes())
-    w = np.ascontiguousarray(words, dtype="<u4").reshape(-1)
-    out += [_U32.pack(w.size + PAD_WORDS), w.tobytes(), b"\0" * (4 * PAD_WORDS)]
-    return b"".join(out)
+        raise ValueError(f'{who}: the header\'s "ans_tables" is {settings.get("ans_tables")!r} (this kind says "empirical")')
+    return run
+
+
+KIND = rstream.Kind("estream", MAGIC, ITEMS, ERecord, _pack_head, _read_head, _check_settings, False)
 
 
 def to_bytes(settings, tensors, embeds=(), embed_shape=None, raw=(), words=()):
-    payload = _payload(settings, list(tensors), list(embeds), embed_shape, list(raw), words)
-    return _PREFIX.pack(MAGIC, VERSION, len(payload)) + payload + _U32.pack(zlib.crc32(payload) & 0xFFFFFFFF)
+    return container.frame(MAGIC, VERSION, rstream.payload(KIND, settings, list(tensors), list(embeds), embed_shape, list(raw), words))
 
 
 def write(path_or_buffer, settings, tensors, embeds=(), embed_shape=None, raw=(), words=()):
     """Write a file; returns the number of bytes written.  path_or_buffer: a file name or a binary file object."""
-    blob = to_bytes(settings, tensors, embeds, embed_shape, raw, words)
-    if hasattr(path_or_buffer, "write"):
-        path_or_buffer.write(blob)
-    else:
-        with open(path_or_buffer, "wb") as f:
-            f.write(blob)
-    return len(blob)
-
-
-class _Cursor:
-    """Bounds-checked reads of the payload; `bits` books every byte it hands out under the name of a budget item."""
-
-    def __init__(self, data):
-        self.data, self.pos, self.bits = data, 0, dict.fromkeys(ITEMS, 0)
-
-    def take(self, n, item):
-        if n < 0 or self.pos + n > len(self.data):
-            raise ValueError(f"estream: truncated ({item} needs {n} bytes at offset {self.pos} of a {len(self.data)}-byte payload)")
-        piece = self.data[self.pos:self.pos + n]
-        self.pos += n
-        self.bits[item] += 8 * n
-        return piece
-
-    def unpack(self, st, item):
-        return st.unpack(self.take(st.size, item))
-
-    def leb128(self, item):
-        v, shift = 0, 0
-        while True:
-            if self.pos >= len(self.data):
-                raise ValueError(f"estream: truncated (a LEB128 value of {item} runs past the {len(self.data)}-byte payload)")
-            b = self.data[self.pos]
-            self.pos += 1
-            self.bits[item] += 8
-            v |= (b & 0x7F) << shift
-            shift += 7
-            if v > TOTAL or shift > 28:                    # (shift: a value padded with continuation bytes)
-                raise ValueError(f"estream: a LEB128 value of {item} exceeds 2^24")
-            if not b & 0x80:
-                if b == 0 and shift > 7:                   # one value, one spelling: the writer never ends on an empty group
-                    raise ValueError(f"estream: a LEB128 value of {item} is padded with an empty last byte")
-                return v
-
-
-def _read_record(cur, run, with_beta, side):
-    count, scale, lo, hi, model = cur.unpack(_HEAD, side)
-    if count == 0 or hi < lo:
-        raise ValueError(f"estream: a record of {count} symbols on the range [{lo}, {hi}]")
-    if hi - lo + 1 > MAX_ALPHABET:
-        raise ValueError(f"estream: a record's alphabet [{lo}, {hi}] has {hi - lo + 1} symbols; the device decoder holds {MAX_ALPHABET}")
-    mean = std = freq = None
-    if model == GAUSSIAN:
-        mean, std = (np.float32(v) for v in cur.unpack(_MOMENTS, side))
-    elif model == TABLE:
-        freq = np.fromiter((cur.leb128("tables") + 1 for _ in range(hi - lo + 1)), dtype=np.int64, count=hi - lo + 1)
-        if int(freq.sum()) != TOTAL:
-            raise ValueError(f"estream: the frequencies of a record's table sum to {int(freq.sum())}, not 2^24")
-        freq = freq.astype(np.uint32)
-    else:
-        raise ValueError(f"estream: a record's model byte is {model} (0: Gaussian, 1: table)")
-    run_words = np.frombuffer(cur.take(2 * n_runs(count, run), "run_index"), dtype="<u2").astype(np.uint16)
-    if int(run_words.min()) < 2:
-        raise ValueError(f"estream: run {int(run_words.argmin())} of a record has {int(run_words.min())} words: fewer than its two state words")
-    beta = np.frombuffer(cur.take(4, side), dtype="<f4")[0] if with_beta else None
-    return ERecord(count, np.float32(scale), lo, hi, model, mean, std, freq, run_words, beta)
+    return container.write_blob(path_or_buffer, to_bytes(settings, tensors, embeds, embed_shape, raw, words))
 
 
 def _parse(path_or_buffer):
-    blob = _blob(path_or_buffer)
-    if len(blob) < _PREFIX.size:
-        raise ValueError(f"estream: truncated ({len(blob)} bytes: shorter than the file prefix)")
-    magic, version, length = _PREFIX.unpack_from(blob)
-    if magic != MAGIC:
-        raise ValueError(f"estream: bad magic number {magic!r} (want {MAGIC!r})")
-    if version != VERSION:
-        raise ValueError(f"estream: unknown format version {version} (this build reads version {VERSION})")
-    if len(blob) != _PREFIX.size + length + 4:
-        raise ValueError(f"estream: truncated or padded ({len(blob)} bytes, the prefix announces {_PREFIX.size + length + 4})")
-    payload = blob[_PREFIX.size:_PREFIX.size + length]
-    if zlib.crc32(payload) & 0xFFFFFFFF != _U32.unpack_from(blob, _PREFIX.size + length)[0]:
-        raise ValueError("estream: CRC mismatch (the payload is damaged)")
-    cur = _Cursor(payload)
-    n_header, = cur.unpack(_U32, "header")
-    try:
-        settings = json.loads(cur.take(n_header, "header").decode("utf-8"))
-    except (UnicodeDecodeError, json.JSONDecodeError) as e:
-        raise ValueError(f"estream: the settings header is not JSON ({e})") from None
-    run = check_run(settings.get("ans_run") if isinstance(settings, dict) else None)
-    if settings.get("ans_tables") != "empirical":
-        raise ValueError(f'estream: the header\'s "ans_tables" is {settings.get("ans_tables")!r} (this kind says "empirical")')
-    n_tensors, = cur.unpack(_U32, "header")
-    tensors = [_read_record(cur, run, False, "tensor_side") for _ in range(n_tensors)]
-    n_embeds, C_, h_, w_ = cur.unpack(struct.Struct("<IIII"), "header")
-    embeds = [_read_record(cur, run, True, "embed_side") for _ in range(n_embeds)]
-    n_raw, = cur.unpack(_U32, "header")
-    raw = []
-    for _ in range(n_raw):
-        cnt, = cur.unpack(_U32, "raw")
-        raw.append(np.frombuffer(cur.take(4 * cnt, "raw"), dtype="<f4").astype(np.float32))
-    n_words, = cur.unpack(_U32, "header")
-    words = np.frombuffer(cur.take(4 * n_words, "ans_words"), dtype="<u4").astype(np.uint32)
-    if cur.pos != len(payload):
-        raise ValueError(f"estream: {len(payload) - cur.pos} payload bytes follow the words")
-    total = sum(int(r.run_words.sum(dtype=np.uint64)) for r in tensors + embeds)
-    if total + PAD_WORDS != n_words:
-        raise ValueError(f"estream: the run lengths of the records add up to {total} words, the payload has {n_words} (two of them padding)")
-    if words[total:].any():
-        raise ValueError("estream: the two words after the last run are not zero")
-    cur.bits["ans_words"] -= 32 * PAD_WORDS
-    cur.bits["padding"] = 32 * PAD_WORDS
-    cur.bits["header"] += 8 * (_PREFIX.size + 4)           # magic, version, length and the CRC
-    return EStream(settings, tensors, embeds, (C_, h_, w_) if n_embeds else None, raw, words[:total]), cur.bits, len(blob)
+    fields, bits, nbytes, _ = rstream.parse(KIND, path_or_buffer)
+    return EStream(*fields), bits, nbytes
 
 
 def read(path_or_buffer):
@@ -241,26 +136,13 @@ def info(path_or_buffer):
     settings, the section counts and the container's framing) and "padding" (the two zero words) -- plus "total" = their sum = 8 * file
     size, "ans_run", and the counts "n_tensors", "n_embeds", "n_raw", "n_runs", "n_symbols", "n_table_records", "n_gaussian_records",
     "bytes"."""
-    es, bits, nbytes = _parse(path_or_buffer)
-    out = {k: int(bits[k]) for k in ITEMS}
-    total = sum(out.values())
-    assert total == 8 * nbytes, (total, nbytes)            # every byte was booked exactly once
+    es, out, nbytes = _parse(path_or_buffer)
     recs = es.tensors + es.embeds
     n_table = sum(r.model == TABLE for r in recs)
-    out.update(total=total, ans_run=int(es.settings["ans_run"]), n_tensors=len(es.tensors), n_embeds=len(es.embeds), n_raw=len(es.raw),
+    out.update(total=8 * nbytes, ans_run=int(es.settings["ans_run"]), n_tensors=len(es.tensors), n_embeds=len(es.embeds), n_raw=len(es.raw),
                n_runs=int(sum(r.run_words.size for r in recs)), n_symbols=int(sum(r.count for r in recs)), n_table_records=int(n_table),
                n_gaussian_records=len(recs) - int(n_table), bytes=nbytes)
     return out
-
-
-def record_words(es):
-    """The word span of every record of an EStream, tensors then embeds: [(first word, word count)]."""
-    spans, at = [], 0
-    for r in es.tensors + es.embeds:
-        n = int(r.run_words.sum(dtype=np.uint64))
-        spans.append((at, n))
-        at += n
-    return spans
 
 
 def record_cdf(r):

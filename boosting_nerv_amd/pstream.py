@@ -3,7 +3,8 @@
 as its 8-bit codes q_t ("intra") or as the differences d_t = (q_t - q_{t-1}) mod 256 to the frame before ("inter"), the two kinds under
 Huffman codes of their own.  The quantisation is untouched: a decoder rebuilds the very codes hnerv_utils.quant_tensor produced.
 
-Host-only code (numpy and struct), little-endian throughout; the framing is qstream.py's:
+Host-only code (numpy and struct), little-endian throughout; framing, cursor and settings header are container.py's, the tensor section is written and
+parsed by qstream.py's section functions under the name of this module:
 
     magic "BNRP" | version u32 | payload length u64 | payload | CRC32(payload) u32
 
@@ -32,16 +33,13 @@ and run lengths that do not add up to the two strings.  info() books every bit o
 
 choose() is the rule by which an encoder decides every frame's kind; it only reads histograms, so the host and the device path of
 codec.encode_posthoc(..., temporal=True) decide alike."""
-import io
-import json
-import struct
-import zlib
 from collections import namedtuple
 
 import numpy as np
 
-from . import qstream, zstream
-from .qstream import F16, F32, RUN, _blob, _Cursor, magic_of, n_runs      # noqa: F401  (the shared framing; re-exported)
+from . import container, qstream, zstream
+from .container import U32 as _U32
+from .qstream import F16, F32, RUN, magic_of, n_runs      # noqa: F401  (re-exported)
 
 MAGIC = b"BNRP"
 VERSION = 1
@@ -51,11 +49,8 @@ KINDS = ("dense", "sparse")
 INTRA, INTER = 0, 1
 EMBED_ITEMS = ("embed_symbol_bits", "embed_run_index", "embed_side", "embed_tables")
 ITEMS = qstream.ITEMS + EMBED_ITEMS
-_PREFIX = struct.Struct("<4sIQ")          # magic, version, payload length
-_SHAPE = struct.Struct("<IIII")           # N, C, h, w
-_GRID = struct.Struct("<IIII")            # outer, red, inner, dtype
-_U32 = struct.Struct("<I")
-_DTYPES = {F32: np.dtype("<f4"), F16: np.dtype("<f2")}
+_SHAPE = container.EMBED_HEAD             # N, C, h, w
+_GRID = container.EMBED_HEAD              # outer, red, inner, dtype
 
 PEmbeds = namedtuple("PEmbeds", "shape outer red inner dtype min scale lengths0 lengths1 pred run_bits words0 words1")
 PEmbeds.__doc__ = """The embedding section.  shape: (N, C, h, w);  outer / red / inner / dtype / min / scale: the grid, as in a qstream.QRecord;
@@ -136,13 +131,7 @@ def choose(h0, h1, count=None, run=RUN):
 
 def _embed_section(e):
     n, c, h, w = (int(v) for v in e.shape)
-    dt = _DTYPES[int(e.dtype)]
-    out = [_SHAPE.pack(n, c, h, w), _GRID.pack(int(e.outer), int(e.red), int(e.inner), int(e.dtype))]
-    for a in (e.min, e.scale):
-        a = np.asarray(a)
-        if a.dtype != dt or a.size != int(e.outer) * int(e.inner):
-            raise ValueError(f"pstream.write: a grid array of {a.size} {a.dtype} entries in a grid of {int(e.outer) * int(e.inner)} {dt} slices")
-        out.append(np.ascontiguousarray(a.reshape(-1)).astype(dt, copy=False).tobytes())
+    out = [_SHAPE.pack(n, c, h, w), _GRID.pack(int(e.outer), int(e.red), int(e.inner), int(e.dtype))] + qstream.grid_bytes("pstream", e, "grid")
     for ln in (e.lengths0, e.lengths1):
         ln = np.ascontiguousarray(ln, dtype=np.uint8)
         if ln.size != LEAVES:
@@ -159,30 +148,17 @@ def _embed_section(e):
     return out
 
 
-def _payload(settings, lengths, records, words, embeds):
+def to_bytes(settings, lengths, records, words, embeds):
     kind = settings.get("tensor_kind")
     if kind not in KINDS or settings.get("embed_pred") != EMBED_PRED:
         raise ValueError(f"pstream.write: the settings need embed_pred = {EMBED_PRED!r} and tensor_kind in {KINDS}")
     fmt = zstream if kind == "sparse" else qstream
-    return b"".join(qstream._header(settings) + fmt._section(lengths, list(records), words) + _embed_section(embeds))
+    return container.frame(MAGIC, VERSION, b"".join(qstream._header(settings) + fmt._section(lengths, list(records), words) + _embed_section(embeds)))
 
 
 def write(path_or_buffer, settings, lengths, records, words, embeds):
     """Write a file; returns the number of bytes written.  path_or_buffer: a file name or a binary file object."""
-    payload = _payload(settings, lengths, records, words, embeds)
-    blob = _PREFIX.pack(MAGIC, VERSION, len(payload)) + payload + _U32.pack(zlib.crc32(payload) & 0xFFFFFFFF)
-    if hasattr(path_or_buffer, "write"):
-        path_or_buffer.write(blob)
-    else:
-        with open(path_or_buffer, "wb") as f:
-            f.write(blob)
-    return len(blob)
-
-
-def to_bytes(settings, lengths, records, words, embeds):
-    buf = io.BytesIO()
-    write(buf, settings, lengths, records, words, embeds)
-    return buf.getvalue()
+    return container.write_blob(path_or_buffer, to_bytes(settings, lengths, records, words, embeds))
 
 
 def _parse_embeds(cur, run):
@@ -191,17 +167,15 @@ def _parse_embeds(cur, run):
     if n == 0 or count == 0:
         raise ValueError(f"pstream: an embedding tensor of shape ({n}, {c}, {h}, {w})")
     outer, red, inner, dtype = cur.unpack(_GRID, "embed_side")
-    if dtype not in _DTYPES or outer * red * inner != n * count:
+    if dtype not in (F32, F16) or outer * red * inner != n * count:
         raise ValueError(f"pstream: {n} frames of {count} elements with the grid ({outer}, {red}, {inner}) of dtype flag {dtype}")
-    dt = _DTYPES[dtype]
-    lo = np.frombuffer(cur.take(dt.itemsize * outer * inner, "embed_side"), dtype=dt).astype(dt.newbyteorder("="))
-    step = np.frombuffer(cur.take(dt.itemsize * outer * inner, "embed_side"), dtype=dt).astype(dt.newbyteorder("="))
-    lengths0 = np.frombuffer(cur.take(LEAVES, "embed_tables"), dtype=np.uint8).copy()
-    lengths1 = np.frombuffer(cur.take(LEAVES, "embed_tables"), dtype=np.uint8).copy()
-    qstream.check_lengths(lengths0)
+    lo, step = qstream.read_grid(cur, outer, inner, dtype, "embed_side")
+    lengths0 = cur.array(np.uint8, LEAVES, "embed_tables")
+    lengths1 = cur.array(np.uint8, LEAVES, "embed_tables")
+    qstream.check_lengths(lengths0, who="pstream")
     if lengths1.any():
-        qstream.check_lengths(lengths1)
-    pred = np.frombuffer(cur.take(n, "embed_side"), dtype=np.uint8).copy()
+        qstream.check_lengths(lengths1, who="pstream")
+    pred = cur.array(np.uint8, n, "embed_side")
     if int(pred.max()) > 1:
         raise ValueError(f"pstream: a pred byte of {int(pred.max())} (0 intra, 1 inter)")
     if pred[0] != INTRA:
@@ -209,71 +183,46 @@ def _parse_embeds(cur, run):
     if pred.any() and not lengths1.any():
         raise ValueError(f"pstream: {int(pred.sum())} frames are coded as differences, the inter code table is absent")
     per = n_runs(count, run)
-    run_bits = np.frombuffer(cur.take(2 * n * per, "embed_run_index"), dtype="<u2").astype(np.uint16).reshape(n, per)
+    run_bits = cur.array("<u2", n * per, "embed_run_index").reshape(n, per)
     strings, bits = [], []
     for kind in (INTRA, INTER):
         n_words, = cur.unpack(_U32, "embed_side")
-        strings.append(np.frombuffer(cur.take(4 * n_words, "embed_symbol_bits"), dtype="<u4").astype(np.uint32))
+        strings.append(cur.array("<u4", n_words, "embed_symbol_bits"))
         bits.append(int(run_bits[pred == kind].sum(dtype=np.uint64)))
     return PEmbeds((n, c, h, w), outer, red, inner, dtype, lo, step, lengths0, lengths1, pred, run_bits, strings[0], strings[1]), bits
 
 
 def _parse(path_or_buffer):
-    blob = _blob(path_or_buffer)
-    if len(blob) < _PREFIX.size:
-        raise ValueError(f"pstream: truncated ({len(blob)} bytes: shorter than the file prefix)")
-    magic, version, length = _PREFIX.unpack_from(blob)
-    if magic != MAGIC:
-        raise ValueError(f"pstream: bad magic number {magic!r} (want {MAGIC!r})")
-    if version != VERSION:
-        raise ValueError(f"pstream: unknown format version {version} (this build reads version {VERSION})")
-    if len(blob) != _PREFIX.size + length + 4:
-        raise ValueError(f"pstream: truncated or padded ({len(blob)} bytes, the prefix announces {_PREFIX.size + length + 4})")
-    payload = blob[_PREFIX.size:_PREFIX.size + length]
-    if zlib.crc32(payload) & 0xFFFFFFFF != _U32.unpack_from(blob, _PREFIX.size + length)[0]:
-        raise ValueError("pstream: CRC mismatch (the payload is damaged)")
-    cur = _Cursor(payload)
-    cur.bits.update(dict.fromkeys(EMBED_ITEMS, 0))
-    zeros = None
-    try:
-        n_header, = cur.unpack(_U32, "header")
-        try:
-            settings = json.loads(cur.take(n_header, "header").decode("utf-8"))
-        except (UnicodeDecodeError, json.JSONDecodeError) as e:
-            raise ValueError(f"pstream: the settings header is not JSON ({e})") from None
-        if not isinstance(settings, dict):
-            raise ValueError("pstream: the settings header is not a JSON object")
-        if settings.get("embed_pred") != EMBED_PRED:
-            raise ValueError(f"pstream: the header's embed_pred is {settings.get('embed_pred')!r} (this build reads {EMBED_PRED!r})")
-        kind = settings.get("tensor_kind")
-        if kind not in KINDS:
-            raise ValueError(f"pstream: the header's tensor_kind is {kind!r} ({' | '.join(KINDS)})")
+    blob = container.blob_of(path_or_buffer)
+    cur = container.Cursor(container.unframe(blob, MAGIC, VERSION, "pstream"), "pstream", ITEMS)
+    settings = container.read_settings(cur)
+    if not isinstance(settings, dict):
+        raise ValueError("pstream: the settings header is not a JSON object")
+    if settings.get("embed_pred") != EMBED_PRED:
+        raise ValueError(f"pstream: the header's embed_pred is {settings.get('embed_pred')!r} (this build reads {EMBED_PRED!r})")
+    kind = settings.get("tensor_kind")
+    if kind not in KINDS:
+        raise ValueError(f"pstream: the header's tensor_kind is {kind!r} ({' | '.join(KINDS)})")
+    if kind == "sparse":
+        run = zstream.check_settings("pstream", settings)
+    else:
         run = settings.get("huff_run")
-        if not isinstance(run, int) or not 1 <= run <= (RUN if kind == "sparse" else 2047):
+        if not isinstance(run, int) or not 1 <= run <= 2047:
             raise ValueError(f"pstream: the header's run length is {run!r}")
-        if kind == "sparse":
-            zero_leaves = settings.get("n_zero_leaves")
-            if settings.get("zero_parse") not in zstream.PARSES or not isinstance(zero_leaves, int) or zero_leaves < 0:
-                raise ValueError(f"pstream: the header's zero_parse / n_zero_leaves are {settings.get('zero_parse')!r} / {zero_leaves!r}")
-            lengths, records, words, total, zeros = zstream._parse_section(cur, run)
-        else:
-            lengths, records, words, total = qstream._parse_section(cur, run)
-        embeds, bits = _parse_embeds(cur, run)
-        if cur.pos != len(payload):
-            raise ValueError(f"pstream: {len(payload) - cur.pos} payload bytes follow the bit strings")
-        if kind == "sparse":
-            zstream._book_section(cur, settings, total, words.size, zeros)
-        else:
-            qstream._book_section(cur, total, words.size)
-        for b, wd, name in zip(bits, (embeds.words0, embeds.words1), ("intra", "inter")):
-            if (b + 31) // 32 != wd.size:
-                raise ValueError(f"pstream: the run lengths of the {name} frames add up to {b} bits, their bit string has {wd.size} words")
-    except ValueError as e:
-        raise ValueError(str(e).replace("qstream", "pstream").replace("zstream", "pstream")) from None
+    lengths, records, words, total = qstream.parse_section(cur, zstream.SECTION if kind == "sparse" else qstream.SECTION, run)
+    embeds, bits = _parse_embeds(cur, run)
+    cur.end("the bit strings")
+    zeros = None
+    if kind == "sparse":
+        zeros = zstream.book_section(cur, settings, records, total, words.size)
+    else:
+        qstream.book_section(cur, total, words.size)
+    for b, wd, name in zip(bits, (embeds.words0, embeds.words1), ("intra", "inter")):
+        if (b + 31) // 32 != wd.size:
+            raise ValueError(f"pstream: the run lengths of the {name} frames add up to {b} bits, their bit string has {wd.size} words")
     cur.bits["embed_symbol_bits"] = sum(bits)
     cur.bits["padding"] += 32 * (embeds.words0.size + embeds.words1.size) - sum(bits)
-    cur.bits["header"] += 8 * (_PREFIX.size + 4)           # magic, version, length and the CRC
-    return PStream(settings, lengths, records, words, embeds), cur.bits, len(blob), zeros, bits
+    return PStream(settings, lengths, records, words, embeds), container.budget(cur, len(blob)), len(blob), zeros, bits
 
 
 def read(path_or_buffer):
@@ -295,13 +244,10 @@ def info(path_or_buffer):
     "n_embed_symbols", "n_embed_runs", "n_inter_frames", "n_intra_frames", "intra_frame_bits", "inter_frame_bits" (the codes of all frames
     of a kind), "embed_section_bits" (section_bits: what choose() compares), "bytes", "tensor_kind", and for a sparse tensor section
     zstream.info's "n_zero_elements", "n_zero_leaves", "zero_parse"."""
-    ps, bits, nbytes, zeros, strings = _parse(path_or_buffer)
-    out = {k: int(bits[k]) for k in ITEMS}
-    total = sum(out.values())
-    assert total == 8 * nbytes, (total, nbytes)            # every byte was booked exactly once
+    ps, out, nbytes, zeros, strings = _parse(path_or_buffer)
     e = ps.embeds
     n_inter = int(e.pred.sum())
-    out.update(total=total, n_records=len(ps.records), n_runs=int(sum(r.run_bits.size for r in ps.records)),
+    out.update(total=8 * nbytes, n_records=len(ps.records), n_runs=int(sum(r.run_bits.size for r in ps.records)),
                n_symbols=int(sum(r.count for r in ps.records)), n_embed_symbols=int(np.prod(e.shape)), n_embed_runs=int(e.run_bits.size),
                n_inter_frames=n_inter, n_intra_frames=int(e.pred.size) - n_inter, intra_frame_bits=strings[0], inter_frame_bits=strings[1],
                embed_section_bits=embed_section_bits(e, int(ps.settings["huff_run"])), bytes=nbytes, tensor_kind=ps.settings["tensor_kind"])

@@ -3,7 +3,8 @@ CEM file of wstream.py in which the embedding record of frame t >= 1 holds eithe
 record) or the integer differences d_t = q_t - q_{t-1} (inter), whichever the encoder found cheaper.  ScaleBeta_T has one learnt (scale,
 beta) for the clip, so the symbols of all frames lie on one integer grid and the difference is exact: nothing is lost.
 
-Host-only code (numpy and struct), little-endian throughout; framing, tensor records, raw section and words section are wstream.py's:
+Host-only code (numpy and struct), little-endian throughout; the framing is container.py's, the payload rstream.py's and the records
+wstream.py's: this kind is wstream.KIND with a magic and a settings check of its own and a lead byte:
 
     magic "BNRT" | version u32 (1) | payload length u64 | payload | CRC32(payload) u32
 
@@ -21,15 +22,12 @@ read() raises ValueError wherever wstream.read does, and for a pred byte above 1
 C * h * w, a header without "embed_pred": "prev", and a file without embedding records (nothing to predict: write the wide kind).  info()
 books every bit under estream's eight items; the pred byte counts as embedding side."""
 import math
-import struct
-import zlib
 from collections import namedtuple
 
 import numpy as np
 
-from . import wstream
-from .estream import ITEMS
-from .rstream import _PREFIX, _U32
+from . import container, rstream, wstream
+from .estream import ITEMS      # noqa: F401  (re-exported)
 
 MAGIC = b"BNRT"
 VERSION = 1
@@ -65,34 +63,26 @@ def _check_embeds(who, embeds, preds, embed_shape):
             raise ValueError(f"{who}: the embedding record of frame {k} has {r.count} symbols, the embedding shape {tuple(embed_shape)} has {count}")
 
 
+KIND = wstream.KIND._replace(who="tstream", magic=MAGIC, check_settings=_check_settings, lead=True)
+
+
 def to_bytes(settings, tensors, embeds, preds, embed_shape, raw=(), words=()):
     embeds, preds = list(embeds), [int(p) for p in preds]
     if embeds and embed_shape is None:
         raise ValueError("tstream.write: embedding records need embed_shape (C, h, w)")
     _check_embeds("tstream.write", embeds, preds, embed_shape if embeds else (0,))
-    payload = wstream._payload(settings, list(tensors), embeds, embed_shape, list(raw), words, check_settings=_check_settings,
-                               lead=[bytes([p]) for p in preds])
-    return _PREFIX.pack(MAGIC, VERSION, len(payload)) + payload + _U32.pack(zlib.crc32(payload) & 0xFFFFFFFF)
+    return container.frame(MAGIC, VERSION, rstream.payload(KIND, settings, list(tensors), embeds, embed_shape, list(raw), words, preds))
 
 
 def write(path_or_buffer, settings, tensors, embeds, preds, embed_shape, raw=(), words=()):
     """Write a file; returns the number of bytes written.  path_or_buffer: a file name or a binary file object."""
-    blob = to_bytes(settings, tensors, embeds, preds, embed_shape, raw, words)
-    if hasattr(path_or_buffer, "write"):
-        path_or_buffer.write(blob)
-    else:
-        with open(path_or_buffer, "wb") as f:
-            f.write(blob)
-    return len(blob)
-
-
-_U8 = struct.Struct("<B")
+    return container.write_blob(path_or_buffer, to_bytes(settings, tensors, embeds, preds, embed_shape, raw, words))
 
 
 def _parse(path_or_buffer):
-    ws, bits, nbytes, preds = wstream._parse(path_or_buffer, MAGIC, "tstream", _check_settings, lambda cur, k: cur.unpack(_U8, "embed_side")[0])
-    _check_embeds("tstream", ws.embeds, preds, ws.embed_shape if ws.embeds else (0,))
-    return TStream(ws.settings, ws.tensors, ws.embeds, preds, ws.embed_shape, ws.raw, ws.words), bits, nbytes
+    (settings, tensors, embeds, embed_shape, raw, words), bits, nbytes, preds = rstream.parse(KIND, path_or_buffer)
+    _check_embeds("tstream", embeds, preds, embed_shape if embeds else (0,))
+    return TStream(settings, tensors, embeds, preds, embed_shape, raw, words), bits, nbytes
 
 
 def read(path_or_buffer):
@@ -105,7 +95,6 @@ def info(path_or_buffer):
     their sum = 8 * file size, wstream.info's counts, "n_inter_frames" and "n_intra_frames"."""
     ts, bits, nbytes = _parse(path_or_buffer)
     out = wstream._budget(ts, bits, nbytes)
-    assert sum(out[k] for k in ITEMS) == 8 * nbytes
     out.update(embed_pred=ts.settings["embed_pred"], n_inter_frames=int(sum(p == INTER for p in ts.preds)), n_intra_frames=int(sum(p == INTRA for p in ts.preds)))
     return out
 

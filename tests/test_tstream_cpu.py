@@ -114,7 +114,7 @@ def test_read_refusals():
     n_words = sum(int(r.run_words.sum()) for r in ts.tensors)
     with pytest.raises(ValueError, match="nothing to predict"):
         tstream.to_bytes(ts.settings, ts.tensors, [], [], None, ts.raw, ts.words[:n_words])
-    wide = wstream._payload({k: v for k, v in ts.settings.items()}, ts.tensors, [], None, ts.raw, ts.words[:n_words], check_settings=tstream._check_settings)
+    wide = rstream.payload(tstream.KIND, {k: v for k, v in ts.settings.items()}, ts.tensors, [], None, ts.raw, ts.words[:n_words])
     with pytest.raises(ValueError, match="nothing to predict"):
         tstream.read(_reframe(wide))
     # ---- the writer refuses what the reader would
