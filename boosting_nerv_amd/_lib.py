@@ -348,6 +348,7 @@ SYMBOLS = {
     "bnerv_embed_expand": (_I, [_V, _V, _V, _V, _I, _I, _I]),
     "bnerv_resize_rows": (_I, [_V, _V, _V, _V, C.c_longlong, _I, _I, _I, _I]),
     "bnerv_resize_cols": (_I, [_V, _V, _V, _V, _I, _I, _I, _I, _I, _I]),
+    "bnerv_resize_cols_yuv420": (_I, [_V, _V, _V, _I, _I, _I, _I, _I, _V, _I, _Z, C.POINTER(YuvCoeffs)]),
 }
 
 _lib = None

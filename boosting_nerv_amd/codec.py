@@ -64,7 +64,14 @@ frames, info reports n_stored_frames.
 A file of any kind written by a run under --resize_list H_W holds frames of H x W: the header's crop_list, the frame size
 to every decoder, is the resized size, and one more key, source_crop, names the crop of the source the frames were resampled from.  decode
 needs nothing else; info prints the key; score takes the master through the same crop, conversion and resize (ops.resize_bicubic) and reports
-the RGB metrics only; psnr, the host plane metric, refuses such a file."""
+the RGB metrics only; psnr, the host plane metric, refuses such a file.
+
+decode, psnr and score take --upscale [WxH] (Decoder(upscale=)): every frame is up-sampled with the loader's bicubic behind
+the forward -- for raw video by ops.resize_to_yuv420, which never writes the full-size fp32 frame -- and written, or scored against the source's
+planes, at that size; without a value the size is the header's source_crop, the master's size of a resized run's file:
+
+    python -m boosting_nerv_amd.codec decode FILE --upscale --format yuv --out clip_1920x1080_8bit.yuv
+    python -m boosting_nerv_amd.codec score FILE --upscale --ref master_1920x1080_8bit.yuv"""
 import argparse
 import builtins
 import json
@@ -921,6 +928,44 @@ def _source_crop(settings):
     return int(m.group(1)), int(m.group(2))
 
 
+def resolve_upscale(upscale, settings, frame_hw, pack="rgb8"):
+    """The size a decoder packs its frames at: None | True | (H, W) -> None (frame_hw itself) or (H, W).  True is the header's source_crop,
+    the crop of the master a resized run's frames were resampled from; ValueError for a file without the key, for a size that is not two
+    positive integers, and for an odd size under a 4:2:0 pack.  Needs no device."""
+    if upscale is None or upscale is False:
+        return None
+    if upscale is True:
+        size = _source_crop(settings)
+        if size is None:
+            raise ValueError("Decoder: upscale=True takes the size from the header's source_crop, and this file has none (it was not written under "
+                             "--resize_list): pass upscale=(H, W)")
+    else:
+        try:
+            size = tuple(int(v) for v in upscale)
+        except (TypeError, ValueError):
+            size = ()
+        if len(size) != 2 or size[0] < 1 or size[1] < 1 or tuple(upscale) != size:
+            raise ValueError(f"Decoder: upscale={upscale!r} (None, True for the header's source_crop, or (H, W))")
+    if pack != "rgb8" and (size[0] % 2 or size[1] % 2):
+        raise ValueError(f"Decoder: 4:2:0 needs even dimensions, upscale gives {size[0]}x{size[1]}")
+    from .resize import axis_table
+    for n_in, n_out in zip(frame_hw, size):
+        axis_table(n_in, n_out)                            # (ValueError over the tap limit)
+    return size
+
+
+def score_window(ref_hw, out_hw):
+    """(top, left) of the window of a ref_hw source that an up-scaling decoder's out_hw frames are scored against: the loader's centre crop.
+    The plane metrics need it on the chroma grid: an odd offset is refused (ValueError), not rounded down -- the up-sampled frame is the
+    crop the run trained on, one luma sample beside it is another picture (the rule of yuvloss.make_term)."""
+    from . import yuvio
+    top, left = yuvio.crop_offsets(ref_hw[0], ref_hw[1], out_hw[0], out_hw[1])
+    if top % 2 or left % 2:
+        raise ValueError(f"Decoder.score: the centre crop of {out_hw[0]}x{out_hw[1]} starts at row {top}, column {left} of the {ref_hw[0]}x{ref_hw[1]} "
+                         "source: 4:2:0 planes can only be compared from an even row and column")
+    return top, left
+
+
 class Decoder:
     """A bitstream, ready to decode frames on `device`.
 
@@ -937,14 +982,19 @@ class Decoder:
     kernel behind the forward instead of the uint8 one -- colour settings are decode-time choices, the file knows nothing of them:
         dec.decode_yuv(i)        frame i in file layout: a 1-D array of 1.5 H W samples (uint8, or little-endian uint16), planes Y, U, V
         dec.frames_yuv()         every frame in order, pipelined like frames_u8
-    decode_u8 / frames_u8 need the default pack="rgb8"."""
+    decode_u8 / frames_u8 need the default pack="rgb8".
 
-    def __init__(self, path, device="cuda", use_graph=True, pack="rgb8", matrix="bt709", range="limited"):
+    upscale=(H, W), or True for the header's source_crop (a file written under --resize_list), packs every frame up-sampled to H x W with
+    the loader's own bicubic: `out_hw` is that size and decode_u8, decode_yuv, frames_*, split_planes, iteration and
+    score work at it, while `frame_hw` and decode_f32 stay the model's.  decode_up_f32(i) is the up-sampled fp32 frame."""
+
+    def __init__(self, path, device="cuda", use_graph=True, pack="rgb8", matrix="bt709", range="limited", upscale=None):
         from . import ops
         from .lib.entropy_model import ans_decode_gaussian
         from .train_nerv_all import build_model
         kind = _kind_of(path)
         self.kind, what = kind.name, kind.who
+        self._asked = (upscale, pack)
         if kind.posthoc:
             getattr(self, "_load_" + kind.name)(path, device)
             return self._frame_loop(use_graph, pack, matrix, range)
@@ -957,6 +1007,7 @@ class Decoder:
         self.n_frames = int(s["full_data_length"])
         self.stored_frames = list(builtins.range(self.n_frames))
         self.frame_hw = tuple(int(v) for v in s["crop_list"].split("_")[:2])
+        self.upscale = resolve_upscale(self._asked[0], s, self.frame_hw, self._asked[1])      # (refused here, before the model is built)
         self.is_hnerv = s["model"] == "HNeRV_Boost"
         margs = SimpleNamespace(**{k: v for k, v in s.items() if k not in ("ans_run", "ans_tables", "ans_wide", "embed_pred")})
         margs.__dict__.update(quant=False, outf="")
@@ -1077,6 +1128,7 @@ class Decoder:
         self.device = torch.device(device)
         self.n_frames = int(s["full_data_length"])
         self.frame_hw = tuple(int(v) for v in s["crop_list"].split("_")[:2])
+        self.upscale = resolve_upscale(self._asked[0], s, self.frame_hw, self._asked[1])      # (refused here, before the model is built)
         self.is_hnerv = "HNeRV" in s["model"]
         if temporal and not self.is_hnerv:
             raise ValueError(f"{what}: an embedding section in a {s['model']} stream")
@@ -1170,8 +1222,8 @@ class Decoder:
         self.norms = torch.tensor([float(i + 1) / self.n_frames for i in builtins.range(self.n_frames)], dtype=torch.float64, device=self.device)
         first_embed = self.embeds[0:1] if self.is_hnerv else None
         self._loop = FrameDecodeGraph(model, self.norms[0:1], first_embed, self.norms[0:1], self.frame_hw, use_graph=use_graph,
-                                      pack=pack, matrix=matrix, range=range)
-        self.pack, self.coeffs = pack, self._loop.coeffs
+                                      pack=pack, matrix=matrix, range=range, upscale=self.upscale)
+        self.pack, self.coeffs, self.out_hw = pack, self._loop.coeffs, self._loop.out_hw
         self._pinned = [torch.empty(self._loop.u8.shape[1:], dtype=torch.uint8, pin_memory=pin) for _ in (0, 1)]
         self._events = [torch.cuda.Event() for _ in builtins.range(2)] if pin else None
 
@@ -1186,6 +1238,13 @@ class Decoder:
 
     def decode_f32(self, i):
         return self._launch(i)[0].clone()
+
+    def decode_up_f32(self, i):
+        """[1, 3, *out_hw] fp32: ops.resize_bicubic of decode_f32(i), the frame an up-scaling decoder packs."""
+        from . import ops
+        if self.upscale is None:
+            raise RuntimeError("Decoder.decode_up_f32: this decoder does not up-scale (pass upscale= to Decoder)")
+        return ops.resize_bicubic(self._launch(i)[0], self.out_hw)
 
     def _to_host(self, u8, slot):
         self._pinned[slot].copy_(u8[0], non_blocking=True)
@@ -1213,7 +1272,7 @@ class Decoder:
 
     def split_planes(self, frame):
         """A frame of decode_yuv / frames_yuv as its (y, u, v) planes (views)."""
-        H, W = self.frame_hw
+        H, W = self.out_hw
         hw, q = H * W, (H // 2) * (W // 2)
         return frame[:hw].reshape(H, W), frame[hw:hw + q].reshape(H // 2, W // 2), frame[hw + q:].reshape(H // 2, W // 2)
 
@@ -1307,18 +1366,26 @@ class Decoder:
         A resized file (header key source_crop, written under --resize_list) is scored against the master put through
         the run's own crop and resize: "psnr_rgb" and "msssim_rgb" as above (`rgb` is implied), while "sse", "psnr_y|u|v|yuv" and
         "msssim_y" are None -- the source has no planes at the frame's size.  resize_from=(H, W) names the source crop of a file that does
-        not carry the key."""
+        not carry the key.
+
+        An up-scaling decoder (Decoder(upscale=...)) is scored at the size it packs, out_hw, through the plane loop above:
+        the packed up-sampled frame against the loader's centre crop of the source (score_window: an odd offset is refused before any
+        launch), with `rgb` decode_up_f32 against the source crop.  The result has every key above plus "upscaled_from": frame_hw."""
         from . import ops, yuvio
         self._need_pack(True, "score")
         if ref.pix_fmt != self.pack:
             raise RuntimeError(f"Decoder.score: this decoder packs {self.pack}, the source is {ref.pix_fmt} (pass pack={ref.pix_fmt!r} to Decoder)")
-        n, (H, W) = self.n_frames, self.frame_hw
+        up = getattr(self, "upscale", None)
+        n, (H, W) = self.n_frames, self.frame_hw if up is None else self.out_hw
         if len(ref) < n:
             raise ValueError(f"Decoder.score: {ref.path} has {len(ref)} frames, the bitstream {n}")
         src_crop = tuple(int(v) for v in resize_from) if resize_from is not None else _source_crop(getattr(self, "settings", None) or {})
-        if src_crop is not None:
+        if up is not None:
+            top, left = score_window((ref.height, ref.width), (H, W))
+        elif src_crop is not None:
             return Decoder._score_resized(self, ref, src_crop, msssim, chunk)
-        top, left = (v & ~1 for v in yuvio.crop_offsets(ref.height, ref.width, H, W))
+        else:
+            top, left = (v & ~1 for v in yuvio.crop_offsets(ref.height, ref.width, H, W))
         bps, src_hw, dev = ref.bytes_per_sample, (ref.height, ref.width), self.device
         ms = bool(msssim) and min(H, W) > 160
         names = (["msssim_y"] if ms else []) + (["psnr_rgb"] if rgb else []) + (["msssim_rgb"] if rgb and ms else [])
@@ -1327,6 +1394,8 @@ class Decoder:
         rows = {k: table[r] for r, k in enumerate(names)}
         luma = [torch.empty(1, 1, H, W, dtype=torch.float32, device=dev) for _ in (0, 1)] if ms else None
         src_rgb = torch.empty(1, 3, H, W, dtype=torch.float32, device=dev) if rgb else None
+        up_rgb = torch.empty(1, 3, H, W, dtype=torch.float32, device=dev) if rgb and up is not None else None
+        up_scratch = torch.empty(3 * self.frame_hw[0] * W, dtype=torch.float32, device=dev) if up_rgb is not None else None
         rgb_window = ref.crop_window((H, W))
         chunk = max(1, min(int(chunk), n))
         pinned = [torch.empty(chunk * ref.frame_bytes, dtype=torch.uint8, pin_memory=True) for _ in (0, 1)]
@@ -1351,6 +1420,8 @@ class Decoder:
                         rows["msssim_y"][i:i + 1].copy_(ops.msssim(luma[0], luma[1]))
                     if rgb:
                         ops.yuv420_to_rgb(src, self.coeffs, 1, *src_hw, crop=rgb_window, out=src_rgb)
+                        if up_rgb is not None:                       # (decode_up_f32(i), into a buffer of this loop)
+                            out = ops.resize_bicubic(out, (H, W), out=up_rgb, scratch=up_scratch)
                         rows["psnr_rgb"][i:i + 1].copy_(ops.psnr(out, src_rgb))
                         if ms:
                             rows["msssim_rgb"][i:i + 1].copy_(ops.msssim(out, src_rgb))
@@ -1366,6 +1437,8 @@ class Decoder:
                 result[key], result["mean"][key] = table_h[names.index(key)], float(means_h[names.index(key)])
             elif key == "msssim_y" or rgb:
                 result[key], result["mean"][key] = None, None
+        if up is not None:
+            result["upscaled_from"] = tuple(self.frame_hw)
         return result
 
     def __iter__(self):
@@ -1379,20 +1452,45 @@ def _colour_flags(p, default_fmt):
     p.add_argument("--range", choices=("limited", "full"), default="limited")
 
 
+def _upscale_flag(p):
+    p.add_argument("--upscale", nargs="?", const=True, default=None, metavar="WxH", type=_parse_upscale,
+                   help="up-sample every decoded frame to WxH with the loader's bicubic before it is packed (without a value: the header's "
+                        "source_crop, the master's size of a file written under --resize_list)")
+
+
+def _parse_upscale(text):
+    """--upscale WxH -> (H, W), the order of Decoder(upscale=)."""
+    from . import yuvio
+    try:
+        w, h = yuvio.parse_size(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return h, w
+
+
+def _upscaled(dec, sep="_"):
+    """The model's frame size of an up-scaling decoder: H_W for the JSON line (the header's form), HxW for the human one."""
+    return sep.join(str(v) for v in dec.frame_hw)
+
+
 def _psnr(a):
     """`codec psnr`: every decoded frame, packed to the source's pixel format on the device, against the source's planes (cropped at even
     offsets where the clip is smaller than the source).  The averages are means of per-frame dB, like evaluate()."""
     from . import yuvio
     w, h = yuvio.parse_size(a.size) if a.size else (None, None)
     ref = yuvio.YuvFile(a.ref, w, h, a.pix_fmt)
-    dec = Decoder(a.file, "cuda", use_graph=not a.no_graph, pack=ref.pix_fmt, matrix=a.matrix, range=a.range)
-    H, W = dec.frame_hw
-    if dec.source_crop() is not None:
+    dec = Decoder(a.file, "cuda", use_graph=not a.no_graph, pack=ref.pix_fmt, matrix=a.matrix, range=a.range, upscale=a.upscale)
+    H, W = dec.out_hw
+    if dec.source_crop() is not None and dec.upscale is None:
         raise ValueError(f"codec psnr: {a.file} holds frames resized from a {'x'.join(str(v) for v in dec.source_crop())} crop: the source has no planes at "
-                         f"{H}x{W} for the plane metrics; `codec score` scores such a file in RGB against the resized source")
+                         f"{H}x{W} for the plane metrics; `codec score` scores such a file in RGB against the resized source, and --upscale "
+                         "scores it against the source's planes at the crop's size")
     if len(ref) < len(dec):
         raise ValueError(f"codec psnr: {a.ref} has {len(ref)} frames, the bitstream {len(dec)}")
-    top, left = (v & ~1 for v in yuvio.crop_offsets(ref.height, ref.width, H, W))
+    if dec.upscale is not None:
+        top, left = score_window((ref.height, ref.width), (H, W))
+    else:
+        top, left = (v & ~1 for v in yuvio.crop_offsets(ref.height, ref.width, H, W))
     names = ("psnr_y", "psnr_u", "psnr_v", "psnr_yuv")
     sums, sse = dict.fromkeys(names, 0.0), dict.fromkeys(("sse_y", "sse_u", "sse_v"), 0)
     for i, frame in enumerate(dec.frames_yuv(copy=False)):
@@ -1405,7 +1503,10 @@ def _psnr(a):
             sse[k] += one[k]
     result = {k: sums[k] / len(dec) for k in names}
     result.update(sse, frames=len(dec), pix_fmt=ref.pix_fmt, matrix=a.matrix, range=a.range)
-    print(" | ".join(f"{k.upper().replace('_', '-')} {result[k]:.4f} dB" for k in names) + f" | {len(dec)} frames of {H}x{W}, {ref.pix_fmt}")
+    if dec.upscale is not None:
+        result.update(upscaled_from=_upscaled(dec))
+    print(" | ".join(f"{k.upper().replace('_', '-')} {result[k]:.4f} dB" for k in names) + f" | {len(dec)} frames of {H}x{W}, {ref.pix_fmt}"
+          + (f" | upscaled from {_upscaled(dec, 'x')}" if dec.upscale is not None else ""))
     print(json.dumps(result))
     return result
 
@@ -1416,8 +1517,8 @@ def _score(a):
     from . import yuvio
     w, h = yuvio.parse_size(a.size) if a.size else (None, None)
     ref = yuvio.YuvFile(a.ref, w, h, a.pix_fmt)
-    dec = Decoder(a.file, "cuda", use_graph=not a.no_graph, pack=ref.pix_fmt, matrix=a.matrix, range=a.range)
-    H, W = dec.frame_hw
+    dec = Decoder(a.file, "cuda", use_graph=not a.no_graph, pack=ref.pix_fmt, matrix=a.matrix, range=a.range, upscale=a.upscale)
+    H, W = dec.out_hw
     if len(ref) < len(dec):
         raise ValueError(f"codec score: {a.ref} has {len(ref)} frames, the bitstream {len(dec)}")
     got = dec.score(ref, msssim=not a.no_msssim, rgb=a.rgb)
@@ -1428,13 +1529,15 @@ def _score(a):
     result.update(frames=len(dec), pix_fmt=ref.pix_fmt, matrix=a.matrix, range=a.range)
     if not planes:
         result.update(source_crop="_".join(str(v) for v in got["resized_from"]))
+    if dec.upscale is not None:
+        result.update(upscaled_from=_upscaled(dec))
     if a.per_frame:
         with open(a.per_frame, "w") as f:
             f.write(",".join(["frame"] + (["sse_y", "sse_u", "sse_v"] if planes else []) + names) + "\n")
             for i in builtins.range(len(dec)):
                 f.write(",".join([str(i)] + ([str(int(v)) for v in got["sse"][i]] if planes else []) + [repr(float(got[k][i])) for k in names]) + "\n")
     print(" | ".join(f"{k.upper().replace('_', '-')} {result[k]:.4f}" + (" dB" if k.startswith("psnr") else "") for k in names)
-          + f" | {len(dec)} frames of {H}x{W}, {ref.pix_fmt}"
+          + f" | {len(dec)} frames of {H}x{W}, {ref.pix_fmt}" + (f" | upscaled from {_upscaled(dec, 'x')}" if dec.upscale is not None else "")
           + ("" if planes else f" | resized from a {'x'.join(str(v) for v in got['resized_from'])} crop: no source planes exist at this size, RGB metrics only"))
     print(json.dumps(result))
     return result
@@ -1449,12 +1552,14 @@ def build_parser():
     d.add_argument("--format", choices=("png", "npy", "yuv"), default="png")
     d.add_argument("--no_graph", action="store_true", help="eager launches instead of the captured graph")
     _colour_flags(d, "yuv420p")
+    _upscale_flag(d)
     q = sub.add_parser("psnr", help="decode FILE and score it against the raw 4:2:0 source --ref: PSNR-Y, -U, -V and the 6:1:1 PSNR-YUV")
     q.add_argument("file")
     q.add_argument("--ref", required=True, help="the source clip, raw planar YUV 4:2:0")
     q.add_argument("--size", default=None, help="WxH of --ref (default: from a UVG-style file name)")
     q.add_argument("--no_graph", action="store_true", help="eager launches instead of the captured graph")
     _colour_flags(q, None)
+    _upscale_flag(q)
     c = sub.add_parser("score", help="decode FILE and score it against the raw 4:2:0 source --ref on the device: the numbers of psnr plus MS-SSIM-Y "
                                      "(--rgb: the RGB PSNR / MS-SSIM of the training log)")
     c.add_argument("file")
@@ -1465,6 +1570,7 @@ def build_parser():
     c.add_argument("--per_frame", default=None, metavar="OUT.csv", help="write one CSV row per frame")
     c.add_argument("--no_graph", action="store_true", help="eager launches instead of the captured graph")
     _colour_flags(c, None)
+    _upscale_flag(c)
     i = sub.add_parser("info", help="print the bit budget of FILE")
     i.add_argument("file")
     r = sub.add_parser("repack", help="rewrite the version-1 CEM file SRC as the chunked kind DST, whose symbols decode on the device (host only)")
@@ -1500,20 +1606,20 @@ def main(argv=None):
         return _score(a)
     if a.format == "yuv":
         from . import yuvio
-        dec = Decoder(a.file, "cuda", use_graph=not a.no_graph, pack=a.pix_fmt, matrix=a.matrix, range=a.range)
+        dec = Decoder(a.file, "cuda", use_graph=not a.no_graph, pack=a.pix_fmt, matrix=a.matrix, range=a.range, upscale=a.upscale)
         yuvio.write(a.out, dec.frames_yuv(copy=False), a.pix_fmt)
-        print(f"decoded {len(dec)} frames of {dec.frame_hw[0]}x{dec.frame_hw[1]} into {a.out} ({a.pix_fmt}, {a.matrix}, {a.range} range, "
+        print(f"decoded {len(dec)} frames of {dec.out_hw[0]}x{dec.out_hw[1]} into {a.out} ({a.pix_fmt}, {a.matrix}, {a.range} range, "
               f"{os.path.getsize(a.out)} bytes)")
         return len(dec)
     os.makedirs(a.out, exist_ok=True)
-    dec = Decoder(a.file, "cuda", use_graph=not a.no_graph)
+    dec = Decoder(a.file, "cuda", use_graph=not a.no_graph, upscale=a.upscale)
     for k, frame in enumerate(dec.frames_u8(copy=False)):
         if a.format == "png":
             from PIL import Image
             Image.fromarray(frame).save(os.path.join(a.out, f"frame_{k:04d}.png"))
         else:
             np.save(os.path.join(a.out, f"frame_{k:04d}.npy"), frame)
-    print(f"decoded {len(dec)} frames of {dec.frame_hw[0]}x{dec.frame_hw[1]} into {a.out}")
+    print(f"decoded {len(dec)} frames of {dec.out_hw[0]}x{dec.out_hw[1]} into {a.out}")
     return len(dec)
 
 

@@ -581,16 +581,24 @@ class DecodeGraph:
 
 class _ForwardAndPack:
     """What FrameDecodeGraph captures: the model's forward followed by the packing kernel into a static frame buffer -- uint8 RGB
-    (coeffs None) or raw YUV 4:2:0 in file layout (coeffs: yuvio.coefficients of the pixel format)."""
+    (coeffs None) or raw YUV 4:2:0 in file layout (coeffs: yuvio.coefficients of the pixel format).  up = (size, scratch, full): the frame is
+    up-sampled to `size` on the way -- ops.resize_to_yuv420 in place of the store kernel, or ops.resize_bicubic into the
+    static fp32 frame `full` in front of ops.frame_to_u8."""
     time_decode = False
 
-    def __init__(self, model, packed, coeffs=None):
-        self.model, self.packed, self.coeffs = model, packed, coeffs
+    def __init__(self, model, packed, coeffs=None, up=None):
+        self.model, self.packed, self.coeffs, self.up = model, packed, coeffs, up
 
     def __call__(self, cur_input, embed, norm_idx=None):
         from . import ops
         out = self.model(cur_input, embed, norm_idx=norm_idx)[0]
-        if self.coeffs is None:
+        if self.up is not None:
+            size, scratch, full = self.up
+            if self.coeffs is None:
+                ops.frame_to_u8(ops.resize_bicubic(out, size, out=full, scratch=scratch), out=self.packed)
+            else:
+                ops.resize_to_yuv420(out, size, self.coeffs, out=self.packed, scratch=scratch)
+        elif self.coeffs is None:
             ops.frame_to_u8(out, out=self.packed)
         else:
             ops.rgb_to_yuv420(out, self.coeffs, out=self.packed)
@@ -603,14 +611,23 @@ class FrameDecodeGraph:
     with device-side copies and replays on the current stream; `out` ([B, 3, H, W] fp32) and `u8` ([B, H, W, 3] uint8) are the static results,
     valid in stream order until the next launch.  use_graph=False runs the same two steps eagerly into the same buffers.
     pack selects the packing node behind the forward: "rgb8" (ops.frame_to_u8), or "yuv420p" / "yuv420p10le" (ops.rgb_to_yuv420 with the
-    given matrix and range; `u8` is then [B, frame bytes] uint8, every frame in file layout: planes Y, U, V)."""
+    given matrix and range; `u8` is then [B, frame bytes] uint8, every frame in file layout: planes Y, U, V).
+    upscale=(H, W) packs the frame up-sampled to H x W: `out` stays the model's frame of frame_hw, `u8` and `out_hw` are
+    of the up-sampled size; the pack node is ops.resize_to_yuv420, or ops.resize_bicubic + ops.frame_to_u8 for "rgb8".  Its buffers (the row
+    pass's scratch, for "rgb8" the full-size fp32 frame) are allocated here, once, and its tables uploaded before the capture."""
 
-    def __init__(self, model, cur_input, embed, norm_idx, frame_hw, use_graph=True, pack="rgb8", matrix="bt709", range="limited"):
+    def __init__(self, model, cur_input, embed, norm_idx, frame_hw, use_graph=True, pack="rgb8", matrix="bt709", range="limited", upscale=None):
         self.use_graph, self.pack = use_graph, pack
+        dev = norm_idx.device
         B, (H, W) = norm_idx.shape[0], frame_hw
+        if upscale is not None:
+            H, W = (int(v) for v in upscale)
+            if H < 1 or W < 1:
+                raise ValueError(f"FrameDecodeGraph: upscale={tuple(upscale)}")
+        self.out_hw = (H, W)
         if pack == "rgb8":
             self.coeffs = None
-            self.u8 = torch.empty(B, H, W, 3, dtype=torch.uint8, device=norm_idx.device)
+            self.u8 = torch.empty(B, H, W, 3, dtype=torch.uint8, device=dev)
         else:
             from . import yuvio
             if pack not in yuvio.PIX_FMTS:
@@ -618,8 +635,15 @@ class FrameDecodeGraph:
             if H % 2 or W % 2:
                 raise ValueError(f"FrameDecodeGraph: 4:2:0 needs even dimensions, the frames are {H}x{W}")
             self.coeffs = yuvio.coefficients(matrix, range, yuvio.PIX_FMTS[pack])
-            self.u8 = torch.empty(B, yuvio.frame_samples(H, W) * self.coeffs.bytes_per_sample, dtype=torch.uint8, device=norm_idx.device)
-        self._body = _ForwardAndPack(model, self.u8, self.coeffs)
+            self.u8 = torch.empty(B, yuvio.frame_samples(H, W) * self.coeffs.bytes_per_sample, dtype=torch.uint8, device=dev)
+        up = None
+        if upscale is not None:
+            from . import ops
+            ops._resize_table(frame_hw[1], W, dev)          # (the tap limit is refused here; the uploads precede the capture)
+            ops._resize_table(frame_hw[0], H, dev)
+            up = ((H, W), torch.empty(B * 3 * frame_hw[0] * W, dtype=torch.float32, device=dev),
+                  torch.empty(B, 3, H, W, dtype=torch.float32, device=dev) if self.coeffs is None else None)
+        self._body = _ForwardAndPack(model, self.u8, self.coeffs, up)
         td = getattr(model, "time_decode", False)
         model.time_decode = False
         try:

@@ -2607,6 +2607,47 @@ def resize_bicubic(x, size, clamp=True, out=None, scratch=None):
     return out
 
 
+def resize_to_yuv420(x, size, coeffs, out=None, frame_stride_bytes=None, scratch=None):
+    """x [B, 3, h, w] fp32 on the device -> B raw 4:2:0 frames of size = (H, W), both even, in file layout: a uint8 [B, frame_stride_bytes]
+    tensor (default stride: one frame) holding the codes of yuvio.to_yuv_reference(resize.resize_reference(x, (H, W)), coeffs) -- what
+    rgb_to_yuv420(resize_bicubic(x, (H, W))) writes, without the full-size fp32 frame.  Two launches: rows [B*3, h, w] ->
+    [B*3, h, W] into `scratch` (bnerv_resize_rows; a contiguous fp32 tensor of at least B*3*h*W elements), then the column pass fused with the
+    store (bnerv_resize_cols_yuv420).  x and scratch are used in place at any 4-byte boundary.  An axis over the tap limit is refused
+    (ValueError) before any launch."""
+    L.require_device(x, "resize_to_yuv420: x")
+    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError(f"resize_to_yuv420: need a non-empty contiguous fp32 [B, 3, h, w] tensor, got {x.dtype} {tuple(x.shape)}")
+    B, _, h, w = (int(v) for v in x.shape)
+    H, W = (int(v) for v in size)
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError(f"resize_to_yuv420: 4:2:0 needs even dimensions, size is {H}x{W}")
+    tab_w, T_w, span = _resize_table(w, W, x.device)          # (both tables before any launch: the tap limit is refused here)
+    tab_h, T_h, _ = _resize_table(h, H, x.device)
+    if B * 3 > 65535:
+        raise ValueError(f"resize_to_yuv420: {B} frames (at most 21845 per call)")
+    bps = coeffs.bytes_per_sample
+    frame = H * W * 3 // 2 * bps
+    stride = frame if frame_stride_bytes is None else int(frame_stride_bytes)
+    if stride < frame or (bps == 2 and stride % 2):
+        raise ValueError(f"resize_to_yuv420: frame_stride_bytes={stride} for frames of {frame} bytes of {bps}-byte samples")
+    if out is None:
+        out = torch.empty(B, stride, dtype=torch.uint8, device=x.device)
+    elif (not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != x.device or out.numel() < (B - 1) * stride + frame
+          or _spans_overlap(out, x)):
+        raise ValueError(f"resize_to_yuv420: out must be a contiguous uint8 tensor of at least {(B - 1) * stride + frame} bytes on {x.device}, apart from x")
+    need = B * 3 * h * W
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.float32, device=x.device)
+    elif (not scratch.is_cuda or scratch.dtype != torch.float32 or not scratch.is_contiguous() or scratch.numel() < need or scratch.device != x.device
+          or _spans_overlap(scratch, x) or _spans_overlap(scratch, out)):
+        raise ValueError(f"resize_to_yuv420: scratch must be a contiguous fp32 tensor of at least {need} elements on {x.device}, apart from x and out")
+    lib, c = L.load(), coeffs.store_struct()
+    L.check(lib.bnerv_resize_rows(L.stream(), L.ptr(x), L.ptr(scratch), L.ptr(tab_w), B * 3 * h, w, W, T_w, span), "bnerv_resize_rows")
+    L.check(lib.bnerv_resize_cols_yuv420(L.stream(), L.ptr(scratch), L.ptr(tab_h), B, h, H, W, T_h, L.ptr(out), bps, stride, C.byref(c)),
+            "bnerv_resize_cols_yuv420")
+    return out
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # global magnitude pruning (csrc/prune.hip; boosting_nerv_amd/prune.py drives it)
 # ----------------------------------------------------------------------------------------------------------------------

@@ -1021,6 +1021,22 @@ int bnerv_embed_expand(void* stream, const float* src, const bnerv_interp_entry*
 int bnerv_resize_rows(void* stream, const float* x, float* out, const void* table_dev, long long rows, int n_in, int n_out, int T, int span);
 int bnerv_resize_cols(void* stream, const float* x, float* out, const void* table_dev, int planes, int n_in, int n_out, int width, int T, int clamp);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Vertical resize fused with the raw 4:2:0 store (additive to ABI 9; csrc/upyuv.hip): the second launch of a decoder
+ * that up-samples to the master's size and writes raw video.
+ *
+ *   bnerv_resize_cols_yuv420  x [B * 3, n_in, W] fp32 (what bnerv_resize_rows wrote for B RGB frames) and the table of n_in -> H (layout
+ *                             above) -> out: B raw frames in file layout (planes Y [H, W], U, V [H/2, W/2]), frame b at byte
+ *                             b * frame_stride_bytes -- the bytes of bnerv_rgb_to_yuv420 on the frame bnerv_resize_cols (clamp = 1) gives:
+ *                             every value is that kernel's tap sum, clamped to [0, 1], then the store's matrix, [1 2 1] / 4 chroma filter,
+ *                             mean of the row pair and floor(offset + scale * v + 0.5).  The full-size fp32 frame is never written.
+ * Any table within BNERV_RESIZE_MAX_TAPS: up, down or identity; first and count are clamped to the axis.  H and W even; B <= 65535.
+ * x and the table: any 4-byte boundary (16-byte loads where a strip's address allows, element by element otherwise); out: any address at
+ * 1 byte per sample, an even address and frame stride at 2.  No LDS, no atomics, no workspace; nothing is allocated or synchronised.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int bnerv_resize_cols_yuv420(void* stream, const float* x, const void* table_dev, int B, int n_in, int H, int W, int T, void* out,
+                             int bytes_per_sample, size_t frame_stride_bytes, const bnerv_yuv_coeffs* coeffs);
+
 #ifdef __cplusplus
 }
 #endif
