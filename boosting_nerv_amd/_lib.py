@@ -349,6 +349,10 @@ SYMBOLS = {
     "bnerv_resize_rows": (_I, [_V, _V, _V, _V, C.c_longlong, _I, _I, _I, _I]),
     "bnerv_resize_cols": (_I, [_V, _V, _V, _V, _I, _I, _I, _I, _I, _I]),
     "bnerv_resize_cols_yuv420": (_I, [_V, _V, _V, _I, _I, _I, _I, _I, _V, _I, _Z, C.POINTER(YuvCoeffs)]),
+    "bnerv_yuv420_up_loss_ws_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "bnerv_yuv420_up_loss_fwd": (_I, [_V, _V, _I, _I, _I, _I, _I, _V, _I, _I, _V, _I, _V, _I, _Z, _I, _I, _I, _I, _I, _V, C.POINTER(YuvCoeffs),
+                                      C.POINTER(C.c_float), _F, _I, _I, _V, _V, _V, _Z]),
+    "bnerv_yuv420_up_loss_bwd": (_I, [_V, _I, _I, _I, _I, _I, _V, _I, _V, _I, _I, C.POINTER(YuvCoeffs), _F, _V, _I, _V, _Z]),
 }
 
 _lib = None

@@ -7,7 +7,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result"
 mkdir -p _obj
 pids=()
-UNITS="abi conv conv4 conv5 convs convbf wgrad wgrad1 eltwise head3 stem gemm dense optim loss dwconv cem lnorm codec yuv huff rans ransenc ransw ranst prune huffz hufft interp resize upyuv"
+UNITS="abi conv conv4 conv5 convs convbf wgrad wgrad1 eltwise head3 stem gemm dense optim loss dwconv cem lnorm codec yuv huff rans ransenc ransw ranst prune huffz hufft interp resize upyuv upyuvloss"
 for f in $UNITS; do
   stale=0
   for h in *.h ../../include/bnerv.h; do [ $h -nt _obj/$f.o ] && stale=1; done

@@ -20,9 +20,11 @@ class YuvTerm:
     file layout (YuvFile.raw_to_device: a uint8 device tensor, frame k at byte k * frame_stride_bytes); coeffs = yuvio.coefficients(...);
     src_hw = (src_h, src_w) of a raw frame; window = (top, left) of the training crop in it, both even; the plane weights; lam, the factor
     of the term in the total loss; pure: the term is the whole loss (--loss YUV420), the RGB loss is not launched.  lam_ms > 0 adds lam_ms
-    times the MS-SSIM-Y term of DESIGN section 37 (ops.yuv420_msssim_loss) against the same window's luma; lam may then be 0 (no plane MSE)."""
+    times the MS-SSIM-Y term of DESIGN section 37 (ops.yuv420_msssim_loss) against the same window's luma; lam may then be 0 (no plane MSE).
+    up = (H, W): the prediction is smaller (or larger) than the window; the loss is taken at the window's H x W through the up-sampler
+    (ops.yuv420_up_loss), which has no MS-SSIM-Y form."""
 
-    def __init__(self, raw, coeffs, src_hw, window, weights=(6, 1, 1), lam=1.0, pure=False, frame_stride_bytes=None, lam_ms=0.0):
+    def __init__(self, raw, coeffs, src_hw, window, weights=(6, 1, 1), lam=1.0, pure=False, frame_stride_bytes=None, lam_ms=0.0, up=None):
         from . import yuvio
         self.raw, self.coeffs = raw, coeffs
         self.src_hw = tuple(int(v) for v in src_hw)
@@ -37,8 +39,18 @@ class YuvTerm:
         if not (self.lam > 0 or (self.lam_ms > 0 and self.lam == 0)):
             raise ValueError(f"YuvTerm: lam={lam} (a positive factor; leave the term out to switch it off)")
         self.ms_out = None                                   # S [B] of the last autograd_term() call with lam_ms > 0
+        self.up = None if up is None else tuple(int(v) for v in up)
+        if self.up is not None:
+            if len(self.up) != 2 or min(self.up) < 2 or self.up[0] % 2 or self.up[1] % 2:
+                raise ValueError(f"YuvTerm: up={up} (the window's size (H, W), both even)")
+            if self.lam_ms > 0:
+                raise ValueError("YuvTerm: the MS-SSIM-Y term has no form through the up-sampler: up with lam_ms > 0")
 
     def check_frame(self, H, W):
+        if self.up is not None:                              # the window is the master's, whatever size the prediction has
+            if H < 1 or W < 1:
+                raise ValueError(f"YuvTerm: the frames are {H}x{W}")
+            H, W = self.up
         if H % 2 or W % 2:
             raise ValueError(f"YuvTerm: 4:2:0 needs an even crop, the frames are {H}x{W}")
         if self.window[0] + H > self.src_hw[0] or self.window[1] + W > self.src_hw[1]:
@@ -49,12 +61,24 @@ class YuvTerm:
     def kwargs(self):
         return dict(weights=self.weights, frame_stride_bytes=self.frame_stride_bytes)
 
+    def value_grad_stats(self, out, sel, **kw):
+        """ops.yuv420_loss_value_grad_stats of this term, or its form through the up-sampler with `up` set."""
+        if self.up is None:
+            return ops.yuv420_loss_value_grad_stats(out, self.raw, self.coeffs, self.src_hw, self.window, sel, **kw, **self.kwargs())
+        return ops.yuv420_up_loss_value_grad_stats(out, self.up, self.raw, self.coeffs, self.src_hw, self.window, sel, **kw, **self.kwargs())
+
+    def loss(self, out, sel):
+        """(L with its autograd node, stats [B, 4]): ops.yuv420_loss, or ops.yuv420_up_loss with `up` set."""
+        if self.up is None:
+            return ops.yuv420_loss(out, self.raw, self.coeffs, self.src_hw, self.window, sel, **self.kwargs())
+        return ops.yuv420_up_loss(out, self.up, self.raw, self.coeffs, self.src_hw, self.window, sel, **self.kwargs())
+
     def autograd_term(self, out, sel):
         """(lam * L + lam_ms * L_ms with its autograd nodes, plane stats [B, 4] | None, S [B] | None) for the eager steps: sample b of `out`
         against raw frame int(sel[b]) (fp32 device tensor).  A factor at 0 launches nothing for its part."""
         total = stats = ms = None
         if self.lam > 0:
-            term, stats = ops.yuv420_loss(out, self.raw, self.coeffs, self.src_hw, self.window, sel, **self.kwargs())
+            term, stats = self.loss(out, sel)
             total = self.lam * term
         if self.lam_ms > 0:
             term, ms = ops.yuv420_msssim_loss(out, self.raw, self.coeffs, self.src_hw, self.window, sel, frame_stride_bytes=self.frame_stride_bytes)
@@ -191,12 +215,10 @@ class TrainStep:
         if y.lam_ms > 0:
             return self._yuv_ms_loss(img_out)
         if y.pure:
-            loss, self.yuv_stats_out, grad = ops.yuv420_loss_value_grad_stats(img_out, y.raw, y.coeffs, y.src_hw, y.window, self._yuv_sel(), lam=y.lam,
-                                                                              **y.kwargs())
+            loss, self.yuv_stats_out, grad = y.value_grad_stats(img_out, self._yuv_sel(), lam=y.lam)
             return loss, ops.psnr(img_out.detach(), self.static_img), grad
         loss, stats, grad = ops.loss_value_grad_stats(img_out, self.static_img, self.loss_type)
-        _, self.yuv_stats_out, _ = ops.yuv420_loss_value_grad_stats(img_out, y.raw, y.coeffs, y.src_hw, y.window, self._yuv_sel(), lam=y.lam,
-                                                                    grad=grad, loss=loss, **y.kwargs())
+        _, self.yuv_stats_out, _ = y.value_grad_stats(img_out, self._yuv_sel(), lam=y.lam, grad=grad, loss=loss)
         return loss, stats[:, 4], grad
 
     def _yuv_ms_loss(self, img_out):
@@ -208,8 +230,7 @@ class TrainStep:
             loss, stats, grad = ops.loss_value_grad_stats(img_out, self.static_img, self.loss_type)
             psnr = stats[:, 4]
         if y.lam > 0:
-            loss, self.yuv_stats_out, grad = ops.yuv420_loss_value_grad_stats(img_out, y.raw, y.coeffs, y.src_hw, y.window, self._yuv_sel(), lam=y.lam,
-                                                                              grad=grad, loss=loss, **y.kwargs())
+            loss, self.yuv_stats_out, grad = y.value_grad_stats(img_out, self._yuv_sel(), lam=y.lam, grad=grad, loss=loss)
         loss, self.yuv_ms_out, grad = ops.yuv420_msssim_value_grad_stats(img_out, y.raw, y.coeffs, y.src_hw, y.window, self._yuv_sel(), lam=y.lam_ms,
                                                                          grad=grad, loss=loss, frame_stride_bytes=y.frame_stride_bytes)
         return loss, (ops.psnr(img_out.detach(), self.static_img) if psnr is None else psnr), grad
@@ -488,7 +509,7 @@ class CompressionStep(TrainStep):
                 term, self.yuv_stats_out, self.yuv_ms_out = y.autograd_term(img_out, self._yuv_sel())
                 out_loss = term if y.pure else hu.loss_fn(img_out, self.static_img, self.loss_type) + term
             else:
-                term, self.yuv_stats_out = ops.yuv420_loss(img_out, y.raw, y.coeffs, y.src_hw, y.window, self._yuv_sel(), **y.kwargs())
+                term, self.yuv_stats_out = y.loss(img_out, self._yuv_sel())
                 out_loss = y.lam * term if y.pure else hu.loss_fn(img_out, self.static_img, self.loss_type) + y.lam * term
         gate = (bpp.detach() / a.full_data_length > a.target_bpp).to(out_loss.dtype)     # `if bpp / N > target_bpp` (:363) on the device
         final_loss = out_loss + gate * a.lambda_rate * bpp

@@ -2648,6 +2648,128 @@ def resize_to_yuv420(x, size, coeffs, out=None, frame_stride_bytes=None, scratch
     return out
 
 
+# ---- the plane loss through the up-sampler (csrc/upyuvloss.hip) ----
+_resize_adjoints = {}    # (n_in, n_out, device) -> (packed adjoint table on the device, Ta, LDS span of the row adjoint)
+
+
+def _resize_adjoint_table(n_in, n_out, device):
+    """The device form of resize.adjoint_table, uploaded once per (n_in, n_out, device).  Raises ValueError over the tap limit."""
+    from . import resize as R
+    key = (int(n_in), int(n_out), str(device))
+    if key not in _resize_adjoints:
+        first, count, w = R.adjoint_table(n_in, n_out)
+        _resize_adjoints[key] = (_upload(R.pack_table(first, count, w), device).view(torch.int32), int(w.shape[1]), R.strip_span(first, count))
+    return _resize_adjoints[key]
+
+
+def _yuv420_up_loss_launch(pred, size, src, coeffs, src_hw, window, frame_sel, weights, lam, grad, loss, frame_stride_bytes, accumulate, need_grad):
+    pred = L.require_device(pred, "pred")
+    if pred.dim() != 4 or pred.shape[1] != 3 or pred.dtype != torch.float32 or not pred.is_contiguous() or pred.numel() == 0:
+        raise ValueError(f"yuv420_up_loss: need a non-empty contiguous fp32 [B, 3, h, w] prediction, got {pred.dtype} {tuple(pred.shape)}")
+    B, _, h, w = (int(v) for v in pred.shape)
+    H, W = (int(v) for v in size)
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError(f"yuv420_up_loss: 4:2:0 needs even dimensions, size is {H}x{W}")
+    if B * 3 > 65535:
+        raise ValueError(f"yuv420_up_loss: {B} samples (at most 21845 per call)")
+    bps = coeffs.bytes_per_sample
+    src_h, src_w = (int(v) for v in src_hw)
+    top, left = (int(v) for v in window)
+    if top < 0 or left < 0 or top % 2 or left % 2 or src_h % 2 or src_w % 2:
+        raise ValueError(f"yuv420_up_loss: the window offset (top {top}, left {left}) and the {src_w}x{src_h} source must be even and not negative")
+    if top + H > src_h or left + W > src_w:
+        raise ValueError(f"yuv420_up_loss: the {W}x{H} window at (top {top}, left {left}) leaves the {src_w}x{src_h} frame")
+    nbytes = _raw_bytes(src, "yuv420_up_loss: src")
+    if src.device != pred.device:
+        raise ValueError(f"yuv420_up_loss: pred is on {pred.device}, src on {src.device}")
+    frame = src_h * src_w * 3 // 2 * bps
+    stride = frame if frame_stride_bytes is None else int(frame_stride_bytes)
+    if frame <= 0 or stride < frame or nbytes < frame:
+        raise ValueError(f"yuv420_up_loss: frames of {frame} bytes at stride {stride} do not fit the {nbytes} bytes of src")
+    n_frames = (nbytes - frame) // stride + 1
+    if frame_sel is not None:
+        frame_sel = L.require_device(frame_sel, "frame_sel")
+        if frame_sel.dtype != torch.float32 or frame_sel.numel() < B or not frame_sel.is_contiguous() or frame_sel.device != pred.device:
+            raise ValueError(f"yuv420_up_loss: frame_sel must hold {B} contiguous fp32 frame numbers on {pred.device}")
+    elif B > n_frames:
+        raise ValueError(f"yuv420_up_loss: {B} samples against {n_frames} frames without frame_sel")
+    for name, t, shape in (("grad", grad, tuple(pred.shape)), ("loss", loss, None)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != pred.device or
+                              (t.numel() != 1 if shape is None else tuple(t.shape) != shape)):
+            raise ValueError(f"yuv420_up_loss: {name} must be a contiguous fp32 {'scalar' if shape is None else list(shape)} tensor on {pred.device}")
+    from .yuvio import parse_weights
+    weights = parse_weights(weights)
+    # the four tables before any launch: either tap limit is refused here
+    tab_w, T_w, span_w = _resize_table(w, W, pred.device)
+    tab_h, T_h, _ = _resize_table(h, H, pred.device)
+    if need_grad:
+        adj_h, Ta_h, _ = _resize_adjoint_table(h, H, pred.device)
+        adj_w, Ta_w, span_a = _resize_adjoint_table(w, W, pred.device)
+    if loss is None:
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+    stats = torch.empty(B, YUV_LOSS_STATS, dtype=torch.float32, device=pred.device)
+    lib = L.load()
+    ws_bytes = lib.bnerv_yuv420_up_loss_ws_bytes(B, h, w, H, W)
+    if ws_bytes == 0:
+        raise ValueError(f"yuv420_up_loss: no workspace for B={B}, {w}x{h} -> {W}x{H}")
+    ws = _ws(ws_bytes, pred.device)
+    c = coeffs.store_struct()
+    wv = (C.c_float * 3)(*weights)
+    L.check(lib.bnerv_yuv420_up_loss_fwd(L.stream(), L.ptr(pred), B, h, w, H, W, L.ptr(tab_w), T_w, span_w, L.ptr(tab_h), T_h, L.ptr(src), bps, stride,
+                                         n_frames, src_h, src_w, top, left, L.ptr(frame_sel), C.byref(c), wv, float(lam), 1 if need_grad else 0,
+                                         int(accumulate), L.ptr(loss), L.ptr(stats), L.ptr(ws), ws_bytes), "bnerv_yuv420_up_loss_fwd")
+    if need_grad:
+        L.check(lib.bnerv_yuv420_up_loss_bwd(L.stream(), B, h, w, H, W, L.ptr(adj_h), Ta_h, L.ptr(adj_w), Ta_w, span_a, C.byref(c), float(lam), L.ptr(grad),
+                                             int(accumulate), L.ptr(ws), ws_bytes), "bnerv_yuv420_up_loss_bwd")
+    return loss, stats, grad
+
+
+def yuv420_up_loss_value_grad_stats(pred, size, src, coeffs, src_hw, window, frame_sel=None, weights=(6, 1, 1), lam=1.0, grad=None, loss=None,
+                                    frame_stride_bytes=None, need_grad=True):
+    """The plane loss at the master's size for a prediction below (or above, or at) it, without an autograd node: pred
+    [B, 3, h, w] fp32, not clamped, is up-sampled to size = (H, W), both even, by the table filter of resize.py without its clamp, and that
+    frame -- never stored -- is compared against the H x W window at window = (top, left), both even, of raw 4:2:0 frames `src`; everything
+    else (src, coeffs, src_hw, frame_sel, weights, lam, frame_stride_bytes, stats) as yuv420_loss_value_grad_stats.  Returns (lam * L, stats
+    [B, 4] = {L[b], mse_y, mse_u, mse_v} at the master's size, lam * dL/dpred [B, 3, h, w], the exact adjoint).  grad and loss handed in: the
+    term is ADDED to them and they are returned; loss handed in alone, or need_grad=False: value and stats only, grad is None.  Five launches
+    (three value-only); an odd size, a window that leaves the source, a table over its tap limit and a wrong grad / loss are refused
+    (ValueError) before any launch."""
+    accumulate = loss is not None
+    if grad is not None and loss is None:
+        raise ValueError("yuv420_up_loss: a grad to accumulate into needs the loss to accumulate into as well")
+    pred = L.f32c(pred.detach())
+    if grad is None and need_grad and not accumulate:
+        grad = torch.empty_like(pred)
+    return _yuv420_up_loss_launch(pred, size, src, coeffs, src_hw, window, frame_sel, weights, lam, grad, loss, frame_stride_bytes, accumulate,
+                                  grad is not None)
+
+
+class _Yuv420UpLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, size, src, coeffs, src_hw, window, frame_sel, weights, frame_stride_bytes):
+        p = L.f32c(pred.detach())
+        grad = torch.empty_like(p) if ctx.needs_input_grad[0] else None
+        loss, stats, grad = _yuv420_up_loss_launch(p, size, src, coeffs, src_hw, window, frame_sel, weights, 1.0, grad, None, frame_stride_bytes, False,
+                                                   grad is not None)
+        ctx.grad = grad
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, gl, _gs):
+        _enter_backward()
+        g = ctx.grad
+        ctx.grad = None
+        return (g * gl if g is not None else None), None, None, None, None, None, None, None, None
+
+
+def yuv420_up_loss(pred, size, src, coeffs, src_hw, window, frame_sel=None, weights=(6, 1, 1), frame_stride_bytes=None):
+    """The plane loss through the up-sampler as an autograd function (the eager steps): returns (L [scalar], stats [B, 4]); see
+    yuv420_up_loss_value_grad_stats."""
+    return _Yuv420UpLoss.apply(pred, tuple(int(v) for v in size), src, coeffs, src_hw, window, frame_sel, tuple(float(v) for v in weights),
+                               frame_stride_bytes)
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # global magnitude pruning (csrc/prune.hip; boosting_nerv_amd/prune.py drives it)
 # ----------------------------------------------------------------------------------------------------------------------

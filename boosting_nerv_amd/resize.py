@@ -15,6 +15,8 @@ its own input: the resize returns its input exactly.
     resize_reference(x, (h, w))        the fp32 definition: horizontal pass, then vertical, acc = fp32(acc + fp32(w_j * x_j)) over the taps
                                        in ascending j from 0.0f, an fp32 intermediate, a final clamp to [0, 1]; ops.resize_bicubic gives its bits
     resize_reference64(x, (h, w))      the same with float64 tables and sums (for error bounds)
+    adjoint_table(n_in, n_out)         the transpose of axis_table in the same shape, per INPUT sample (the gradient
+                                       of a loss taken through the resize)
     parse_resize('-1' | 'H_W')         None | (H, W)
 
 An axis whose outputs need more than MAX_TAPS = 64 taps (a reduction of more than about 15x) is refused with a ValueError."""
@@ -68,6 +70,50 @@ def axis_table(n_in, n_out):
             a.setflags(write=False)
         _tables[key] = got
     return _tables[key]
+
+
+_adjoints = {}
+
+
+def adjoint_table(n_in, n_out):
+    """The transpose of axis_table(n_in, n_out) in the same table shape, so pack_table packs it and strip_span sizes its
+    LDS pitch: (first int32 [n_in], count int32 [n_in], weights fp32 [n_in, Ta]).  Input i lists the contiguous range of outputs whose tap
+    range holds i -- contiguous because first and first + count do not decrease along the axis -- and entry k is the forward table's fp32
+    word w[first_out + k][i - first[first_out + k]].  An input no output reads gets count 0 (a zero gradient).  Ta > MAX_TAPS (an
+    enlargement of more than about 16x): ValueError.  Cached by (n_in, n_out), read-only arrays."""
+    key = (int(n_in), int(n_out))
+    if key not in _adjoints:
+        first, count, w = axis_table(*key)
+        f64, e64 = first.astype(np.int64), first.astype(np.int64) + count.astype(np.int64)
+        if np.any(np.diff(f64) < 0) or np.any(np.diff(e64) < 0):
+            raise ValueError(f"resize: the tap ranges of {key[0]} -> {key[1]} samples are not monotone")
+        i = np.arange(key[0], dtype=np.int64)
+        lo = np.searchsorted(e64, i, side="right")                     # outputs with end <= i: those in front of the range
+        hi = np.searchsorted(f64, i, side="right")                     # outputs with first <= i
+        cnt = np.maximum(hi - lo, 0)
+        Ta = max(int(cnt.max()), 1)
+        if Ta > MAX_TAPS:
+            raise ValueError(f"resize: the adjoint of {key[0]} -> {key[1]} samples needs {Ta} taps per input, the limit is {MAX_TAPS} "
+                             "(an enlargement of about 16x)")
+        wa = np.zeros((key[0], Ta), dtype=np.float32)
+        k = np.arange(Ta, dtype=np.int64)[None, :]
+        o = np.minimum(lo[:, None] + k, key[1] - 1)
+        live = k < cnt[:, None]
+        j = np.clip(i[:, None] - f64[o], 0, w.shape[1] - 1)
+        wa[live] = w[o, j][live]
+        got = (lo.astype(np.int32), cnt.astype(np.int32), wa)
+        for a in got:
+            a.setflags(write=False)
+        _adjoints[key] = got
+    return _adjoints[key]
+
+
+def dense_matrix(first, count, weights, n_cols):
+    """The dense float64 matrix [len(first), n_cols] of a table: row r holds weights[r, :count[r]] at columns first[r] ..; the fp32 words, widened."""
+    m = np.zeros((len(first), int(n_cols)), dtype=np.float64)
+    for r in range(len(first)):
+        m[r, first[r]:first[r] + count[r]] = weights[r, :count[r]]
+    return m
 
 
 def strip_span(first, count, strip=STRIP):

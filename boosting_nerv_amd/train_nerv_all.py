@@ -377,7 +377,7 @@ def train(local_rank, args):
     log.line(f'Train step: {mode}' + (' (eager: --no_graph)' if mode == "captured" and args.no_graph else '')
              + f', inpainting mask: {args.inpanting if mask is not None else "none"}, clip_max_norm: {args.clip_max_norm}', echo=False)
     if yuv_term is not None:
-        log.line(yuvloss.describe(yuv_term), echo=False)
+        log.line(yuvloss.describe(yuv_term, full_dataset.resize), echo=False)
     if full_dataset.resize is not None:
         from .resize import describe as describe_resize
         log.line(describe_resize((full_dataset.crop_h, full_dataset.crop_w), full_dataset.resize), echo=False)

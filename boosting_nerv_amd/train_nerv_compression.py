@@ -216,7 +216,7 @@ def train(local_rank, args):
         from .engine import CompressionStep
         cstep = CompressionStep(model, optimizer, entropy_model, args, (args.batchSize, 3, h_, w_), device, world_size=world, yuv=yuv_term)
     if yuv_term is not None:
-        log.line(yuvloss.describe(yuv_term), echo=False)
+        log.line(yuvloss.describe(yuv_term, full_dataset.resize), echo=False)
     if full_dataset.resize is not None:
         from .resize import describe as describe_resize
         log.line(describe_resize((full_dataset.crop_h, full_dataset.crop_w), full_dataset.resize), echo=False)

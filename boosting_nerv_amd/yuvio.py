@@ -204,6 +204,27 @@ def plane_loss_reference(rgb, planes, coeffs, window=(0, 0), weights=(6, 1, 1), 
     return (L, mse, grad, tuple(pre)) if return_pre else (L, mse, grad)
 
 
+def plane_loss_up_reference(rgb, planes, coeffs, size, window=(0, 0), weights=(6, 1, 1)):
+    """The float64 restatement of the plane loss through the up-sampler.  rgb [B, 3, h, w], any float, any h and w, NOT
+    clamped; size = (H, W), both even: the window at window = (top, left) of the planes that Q = U rgb is compared against, U the two-pass
+    table filter of resize.py without its clamp.  The dense Wr [W, w], Wc [H, h] are built from the fp32 words of resize.axis_table -- the
+    words the kernels read -- and widened: Q[c] = Wc P[c] Wr^T, (L, mse, gQ) = plane_loss_reference(Q, ...), grad = Wc^T gQ Wr.
+    Returns (L [B], mse [B, 3], grad [B, 3, h, w])."""
+    from . import resize as R
+    P = np.asarray(rgb, dtype=np.float64)
+    if P.ndim != 4 or P.shape[1] != 3 or P.size == 0:
+        raise ValueError(f"yuvio: {P.shape} is no non-empty [B, 3, h, w] batch")
+    H, W = (int(v) for v in size)
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError(f"yuvio: 4:2:0 needs even dimensions, size is {H}x{W}")
+    h, w = P.shape[2:]
+    Wr = R.dense_matrix(*R.axis_table(w, W), w)
+    Wc = R.dense_matrix(*R.axis_table(h, H), h)
+    Q = Wc @ P @ Wr.T
+    L, mse, gQ = plane_loss_reference(Q, planes, coeffs, window, weights)
+    return L, mse, Wc.T @ gQ @ Wr
+
+
 def luma_pre_reference(rgb, planes, coeffs, window=(0, 0), return_pre=False):
     """The float64 restatement of the two planes the MS-SSIM-Y term compares (DESIGN section 37).  rgb [B, 3, H, W], any float, NOT clamped;
     planes = (y, u, v) integer codes as plane_loss_reference takes them (only y [B, src_h, src_w] is read); window = (top, left), any parity.

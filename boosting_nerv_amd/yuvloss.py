@@ -7,6 +7,8 @@ texts.  The loss itself is csrc/yuv.hip behind ops.yuv420_loss / ops.yuv420_loss
     --loss YUV420             L alone, times --yuv_loss (which then defaults to 1)
     --yuv_msssim LAMBDA       + LAMBDA * L_ms, the MS-SSIM-Y term of DESIGN section 37 (default 0: off; with or without --yuv_loss;
                               under --loss YUV420 the loss is yuv_loss * L + yuv_msssim * L_ms)
+    --yuv_upscale             with --resize_list H_W: L is taken at the --crop_list size, the prediction up-sampled by the loader's own bicubic
+                              inside the loss (ops.yuv420_up_loss); not with --yuv_msssim
 
 Matrix, range and depth are the loader's (--yuv_matrix, --yuv_range, the file's format)."""
 import numpy as np
@@ -20,6 +22,8 @@ def add_flags(parser):
     parser.add_argument('--yuv_loss_weights', type=str, default='6_1_1', help='plane weights Y_U_V of the plane loss')
     parser.add_argument('--yuv_msssim', type=float, default=0., metavar='LAMBDA',
                         help='add LAMBDA times (1 - MS-SSIM of the luma plane against the raw .yuv source) to the loss (0 = off)')
+    parser.add_argument('--yuv_upscale', action='store_true',
+                        help='with --resize_list: take the plane loss at the --crop_list size, through the up-sampler (not with --yuv_msssim)')
 
 
 def check_flags(args):
@@ -39,11 +43,19 @@ def check_flags(args):
     if resize is not None and getattr(args, "embed_inter", False):
         raise ValueError(f"--resize_list {args.resize_list} with --embed_inter: the neighbour frames of a held-out frame come through the host loader "
                          "only; --embed_inter_stored interpolates from stored embeddings instead")
+    up = bool(getattr(args, "yuv_upscale", False))
+    if up and resize is None:
+        raise ValueError("--yuv_upscale without --resize_list: the prediction already has the size of the source's window")
+    if up and ms > 0:
+        raise ValueError("--yuv_upscale with --yuv_msssim: the MS-SSIM-Y term has no form through the up-sampler")
+    if up and not args.yuv_loss > 0:
+        raise ValueError(f"--yuv_upscale without a plane loss: give --yuv_loss LAMBDA or --loss {PURE}")
     if not (args.yuv_loss > 0 or ms > 0):
         return args
     what = f"--loss {PURE}" if pure else ("--yuv_loss" if args.yuv_loss > 0 else "--yuv_msssim")
-    if resize is not None:
-        raise ValueError(f"{what} with --resize_list {args.resize_list}: the raw source has no planes at the resized frame's size to compare against")
+    if resize is not None and not up:
+        raise ValueError(f"{what} with --resize_list {args.resize_list}: the raw source has no planes at the resized frame's size to compare against "
+                         "(--yuv_upscale takes the plane loss at the --crop_list size, through the up-sampler)")
     if getattr(args, "inpanting", "none") != "none":
         raise ValueError(f"{what} with --inpanting {args.inpanting}: the plane loss has no masked form")
     if getattr(args, "host_frames", False) or getattr(args, "embed_inter", False):
@@ -51,7 +63,7 @@ def check_flags(args):
     if not str(args.data_path).lower().endswith(".yuv"):
         raise ValueError(f"{what} compares against the planes of a raw source: --data_path {args.data_path} is no .yuv file")
     from .hnerv_utils import frame_hw
-    h, w = frame_hw(args)
+    h, w = tuple(int(x) for x in args.crop_list.split("_")[:2]) if up else frame_hw(args)      # (the window the planes are compared in)
     if h % 2 or w % 2:
         raise ValueError(f"{what}: 4:2:0 needs an even crop, --crop_list gives {h}x{w}")
     if ms > 0 and min(h, w) <= 160:
@@ -82,12 +94,18 @@ def make_term(args, dataset, device, resident):
     raw = clip.raw_to_device(device, count=len(dataset.samples))
     if ms > 0 and min(ch, cw) <= 160:
         raise ValueError(f"--yuv_msssim: the five-scale MS-SSIM needs min(H, W) > 160, the crop is {ch}x{cw}")
-    return YuvTerm(raw, coeffs, (clip.height, clip.width), (top, left), weights=args.yuv_loss_weights, lam=args.yuv_loss, pure=args.loss == PURE, lam_ms=ms)
+    up = (ch, cw) if getattr(args, "yuv_upscale", False) else None
+    return YuvTerm(raw, coeffs, (clip.height, clip.width), (top, left), weights=args.yuv_loss_weights, lam=args.yuv_loss, pure=args.loss == PURE, lam_ms=ms,
+                   up=up)
 
 
-def describe(term):
+def describe(term, frame_hw=None):
+    """The run log's line; frame_hw: the size of the frames the run trains on (named with the term taken through the up-sampler)."""
     c = term.coeffs
-    return (f"YUV loss: lambda {term.lam:g}, weights {'_'.join(f'{v:g}' for v in term.weights)}, matrix {c.matrix}, range {c.range}, {c.depth} bit"
+    up = ""
+    if getattr(term, "up", None) is not None:
+        up = f", at {term.up[0]}x{term.up[1]} through the up-sampler" + ("" if frame_hw is None else f" (from {frame_hw[0]}x{frame_hw[1]})")
+    return (f"YUV loss: lambda {term.lam:g}, weights {'_'.join(f'{v:g}' for v in term.weights)}, matrix {c.matrix}, range {c.range}, {c.depth} bit" + up
             + (f", MS-SSIM-Y lambda {term.lam_ms:g}" if term.lam_ms > 0 else "") + (" (pure: the RGB loss is off)" if term.pure else ""))
 
 

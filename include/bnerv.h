@@ -1037,6 +1037,38 @@ int bnerv_resize_cols(void* stream, const float* x, float* out, const void* tabl
 int bnerv_resize_cols_yuv420(void* stream, const float* x, const void* table_dev, int B, int n_in, int H, int W, int T, void* out,
                              int bytes_per_sample, size_t frame_stride_bytes, const bnerv_yuv_coeffs* coeffs);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * The plane loss at the master's size for a prediction below it (additive to ABI 9; csrc/upyuvloss.hip, DESIGN section 42;
+ * yuvio.plane_loss_up_reference is the float64 restatement):  L_up(P) = L(U P)  with L, mse_p, weights, lambda and stats those of
+ * bnerv_yuv420_loss and U the two-pass table filter above WITHOUT its clamp (Q[c] = Wc P[c] Wr^T), and the exact adjoint
+ * dL_up/dP = Wc^T (dL/dQ) Wr.  pred [B, 3, h, w] fp32, not clamped, any h and w; the H x W window (both even) at (top, left), both even,
+ * of the raw src_h x src_w frames.
+ *
+ *   _fwd  bnerv_resize_rows (pred -> S [B*3, h, W] in ws; table_w_dev of w -> W, T_w, span_w as that call takes them), then one launch that
+ *         forms bnerv_resize_cols_yuv420's tap sums (table_h_dev of h -> H, T_h), does not clamp them, takes the errors against the source
+ *         (src, bytes_per_sample, frame_stride_bytes, n_frames, frame_sel, coeffs = the STORE struct, weights: as bnerv_yuv420_loss) and
+ *         writes per-wave partial sums and, with need_grad != 0, the error planes 2 w_p d_p e_p / (B m n_p) into ws; then the one-block
+ *         finalize: stats [B, 4] = {L[b], mse_y, mse_u, mse_v} (never scaled), loss[0] = lambda * L, or += with accumulate != 0.
+ *   _bwd  (after a _fwd with need_grad != 0 on the same ws) two launches: the adjoint of the column pass over adj_h_dev, the ADJOINT table of
+ *         h -> H (resize.adjoint_table: for every input row the contiguous range of output rows that read it and their weights, in the
+ *         table layout above with n_in entries; Ta_h its width), chroma carried at half width; then the adjoint of the row pass with the
+ *         colour mix over adj_w_dev / Ta_w, span_a the LDS pitch in floats (resize.strip_span of the adjoint table; a multiple of 4, three
+ *         rows of it within 48 KiB).  grad [B, 3, h, w] = lambda * dL_up/dP, or += with accumulate != 0.
+ * ws: _ws_bytes(B, h, w, H, W) bytes = S (12 B h W) + error planes (6 B H W) + the column adjoint's output (8 B h W) + partials, every part
+ * rounded up to 16 bytes; no [B, 3, H, W] buffer exists.  Validates before any launch and without a device: null pointers, odd H / W / top /
+ * left or source size, a window that leaves the frame, a stride smaller than a frame, bytes_per_sample, tap counts outside 1 ..
+ * BNERV_RESIZE_MAX_TAPS, weights, B > n_frames without frame_sel, B > 21845; BNERV_E_WS for a short workspace.  fp32 operands and tables need
+ * 4-byte alignment; every wider access is chosen per address.  Table entries are clamped to the axis and the LDS pitch where they are read.
+ * No float atomics: the same operands give the same bits.  Nothing is allocated or synchronised.
+ * ------------------------------------------------------------------------------------------------------------------ */
+size_t bnerv_yuv420_up_loss_ws_bytes(int B, int h, int w, int H, int W);
+int bnerv_yuv420_up_loss_fwd(void* stream, const float* pred, int B, int h, int w, int H, int W, const void* table_w_dev, int T_w, int span_w,
+                             const void* table_h_dev, int T_h, const void* src, int bytes_per_sample, size_t frame_stride_bytes, int n_frames,
+                             int src_h, int src_w, int top, int left, const float* frame_sel, const bnerv_yuv_coeffs* coeffs, const float* weights,
+                             float lambda, int need_grad, int accumulate, float* loss, float* stats, void* ws, size_t ws_bytes);
+int bnerv_yuv420_up_loss_bwd(void* stream, int B, int h, int w, int H, int W, const void* adj_h_dev, int Ta_h, const void* adj_w_dev, int Ta_w,
+                             int span_a, const bnerv_yuv_coeffs* coeffs, float lambda, float* grad, int accumulate, void* ws, size_t ws_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,8 +14,17 @@ and the MS-SSIM-Y term (bnerv_yuv_luma_pair, bnerv_loss_fwd_b
   msssim-step    C1's and C3's captured step with YuvTerm(lam 1000, lam_ms 50) against the same YuvTerm with lam_ms = 0 (the parent's path),
                  alternated as `step` does;
   msssim-train   the `train` schedule with --yuv_msssim at `--ms_lambdas` added to its rows.
-usage: python tools/kyuvloss.py [--only kernel|step|train|msssim-kernel|msssim-step|msssim-train] [--steps 100] [--repeats 3] [--frames 16]
-                                [--epochs 160] [--lambdas 300 3000] [--ms_lambdas 50]
+and the plane loss through the up-sampler (csrc/upyuvloss.hip, bnerv_yuv420_up_loss_fwd / _bwd):
+  up-kernel  the five-launch call at 360x640 -> 720x1280 and 540x960 -> 1080x1920, 8 and 10 bit, writing, adding and value only, as `kernel`
+             times its pair; beside it the same loss and gradient through stock torch ops with F.interpolate(mode='bicubic',
+             align_corners=False, antialias=True) as the up-sampler (antialias=True selects the Keys cubic with a = -0.5, the filter of
+             resize.py; without it torch's bicubic uses a = -0.75, another function); the bytes each form has to move;
+  up-step    the captured step of the C1 recipe with one stage less (360x640) with YuvTerm(lam 1000, up=(720, 1280)) against the same step
+             without the term, alternated as `step` does;
+  up-train   the `train` schedule at 360x640 from the 720p master (--resize_list 360_640): --loss Fusion10_freq alone against
+             + --yuv_loss LAMBDA --yuv_upscale at `--lambdas`, both scored by Decoder(upscale=True).score against the master.  One seed per row.
+usage: python tools/kyuvloss.py [--only kernel|step|train|msssim-kernel|msssim-step|msssim-train|up-kernel|up-step|up-train] [--steps 100]
+                                [--repeats 3] [--frames 16] [--epochs 160] [--lambdas 300 3000] [--ms_lambdas 50]
 (needs the GPU)"""
 import argparse
 import os
@@ -97,6 +106,144 @@ def kernel():
             print(f"kernel {h}x{w} {depth} bit: write {write:.1f} us ({b_write / write / 1e6:.2f} TB/s of {b_write / 1e6:.1f} MB), "
                   f"accumulate {add:.1f} us ({b_add / add / 1e6:.2f} TB/s of {b_add / 1e6:.1f} MB), value only {value:.1f} us;  "
                   f"stock torch ops fwd+bwd eager {min(best):.1f} us best of 10;  max|grad - torch grad| / max|grad| {rel:.1e}", flush=True)
+
+
+UP_SHAPES = (((360, 640), (720, 1280)), ((540, 960), (1080, 1920)))
+UP_FLAGS = ("--model NeRV_Boost --sft_block res_sft --ch_t 32 --optim_type Adan --conv_type convnext pshuffel_3x3 --act sin --norm none "
+            "--crop_list 720_1280 --resize_list 360_640 --loss Fusion10_freq --embed pe_1.25_80 --fc_hw 9_16 --dec_strds 5 2 2 2 --ks 0_3_3 "
+            "--reduce 2 --dec_blks 1 1 2 2 --modelsize 0.8 --lower_width 12 -b 1 --lr 0.003")
+
+
+def up_traffic(h, w, H, W, bps, need_grad=True, accumulate=False):
+    """Bytes one call has to move for one frame, from the shapes: (this form, a chain through existing ops with [3, H, W] fp32 buffers)."""
+    samples = H * W * 3 // 2 * bps
+    rows = 12 * h * w + 12 * h * W                                     # the row pass: P in, S out
+    fwd = 12 * h * W + samples + (6 * H * W if need_grad else 0)       # S in, the samples in, the error planes out
+    bwd = (6 * H * W + 8 * h * W) + (8 * h * W + 12 * h * w * (2 if accumulate else 1)) if need_grad else 0
+    chain = rows + 12 * h * W + 12 * H * W + (12 * H * W + samples + 12 * H * W) + (12 * H * W + 12 * h * W) + (12 * h * W + 12 * h * w)
+    return rows + fwd + bwd, chain
+
+
+def up_kernel():
+    import torch
+    import torch.nn.functional as F
+    from kinpaint import time_launch
+    from boosting_nerv_amd import ops
+    dev = torch.device("cuda:0")
+    for (h, w), (H, W) in UP_SHAPES:
+        for depth in (8, 10):
+            c, clip, raw = _raw_clip(1, H, W, depth, dev)
+            small = ops.resize_bicubic(clip, (h, w))
+            pred = (small + 0.05 * torch.randn_like(small)).contiguous()
+            grad, loss = torch.zeros_like(pred), torch.zeros((), device=dev)
+            call = lambda **kw: ops.yuv420_up_loss_value_grad_stats(pred, (H, W), raw, c, (H, W), (0, 0), **kw)
+            write = time_launch(lambda: call())
+            add = time_launch(lambda: call(grad=grad, loss=loss))
+            value = time_launch(lambda: call(need_grad=False))
+            f = _torch_form(c, raw, H, W, dev)
+            p = pred.clone().requires_grad_(True)
+
+            def stock():
+                p.grad = None
+                f(F.interpolate(p, size=(H, W), mode="bicubic", align_corners=False, antialias=True)).backward()
+            for _ in range(3):
+                stock()
+            best = []
+            for _ in range(10):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); stock(); e1.record()
+                torch.cuda.synchronize()
+                best.append(e0.elapsed_time(e1) * 1e3)
+            mine = call()
+            rel = float((mine[2] - p.grad).abs().max() / p.grad.abs().max())
+            b_w, chain = up_traffic(h, w, H, W, c.bytes_per_sample)
+            b_a, b_v = up_traffic(h, w, H, W, c.bytes_per_sample, accumulate=True)[0], up_traffic(h, w, H, W, c.bytes_per_sample, need_grad=False)[0]
+            print(f"up-kernel {h}x{w} -> {H}x{W} {depth} bit: write {write:.1f} us ({b_w / write / 1e6:.2f} TB/s of {b_w / 1e6:.1f} MB), "
+                  f"accumulate {add:.1f} us ({b_a / 1e6:.1f} MB), value only {value:.1f} us ({b_v / 1e6:.1f} MB); a chain through [3, H, W] fp32 "
+                  f"buffers would move {chain / 1e6:.1f} MB;  stock torch ops (F.interpolate bicubic, a = -0.5) fwd+bwd eager {min(best):.1f} us best of 10;  "
+                  f"max|grad - torch grad| / max|grad| {rel:.1e}", flush=True)
+
+
+def up_step(steps, repeats):
+    import torch
+    from boosting_nerv_amd import ops
+    from boosting_nerv_amd import train_nerv_all as T
+    from boosting_nerv_amd.engine import TrainStep, YuvTerm
+    from boosting_nerv_amd.optimizer import Adan
+    dev = torch.device("cuda:0")
+    (h, w), (H, W) = UP_SHAPES[0]
+    args = T.build_parser().parse_args(UP_FLAGS.split() + ["--data_path", f"synthetic:{N_FRAMES}x{H}x{W}", "--vid", "bench"])
+    args.final_size, args.full_data_length, args.outf = h * w, 132, "bench"
+    args.fc_dim, _ = T.solve_fc_dim(args, args.final_size, args.full_data_length)
+    c, master, raw = _raw_clip(N_FRAMES, H, W, 8, dev)
+    frames = ops.resize_bicubic(master, (h, w))
+    norm = torch.tensor([(i + 1) / N_FRAMES for i in range(N_FRAMES)], dtype=torch.float64, device=dev)
+    idx = torch.arange(N_FRAMES, device=dev)
+    paths = {}
+    for key, term in (("with the term (YuvTerm, lam 1000, up)", YuvTerm(raw, c, (H, W), (0, 0), lam=1000.0, up=(H, W))), ("without (yuv=None)", None)):
+        torch.manual_seed(args.manualSeed)
+        model = T.build_model(args).to(dev)
+        paths[key] = TrainStep(model, Adan(model.parameters(), lr=args.lr), args.loss, False, (1, 3, h, w), dev, use_graph=True, warmup_eager=3, yuv=term)
+
+    def run(s_, s):
+        k = s % N_FRAMES
+        if s_.yuv is None:
+            s_(frames[k:k + 1], norm[k:k + 1])
+        else:
+            s_(frames[k:k + 1], norm[k:k + 1], frame_idx=idx[k:k + 1])
+    for s_ in paths.values():
+        for s in range(8):
+            run(s_, s)
+    torch.cuda.synchronize()
+    assert all(s_.graph_a is not None for s_ in paths.values())
+    ms = {k: [] for k in paths}
+    for rnd in range(repeats):
+        for k, s_ in paths.items():
+            torch.cuda.synchronize()
+            t0 = time.time()
+            for s in range(steps):
+                run(s_, s)
+            torch.cuda.synchronize()
+            ms[k].append((time.time() - t0) / steps * 1e3)
+            print(f"up-step {h}x{w} round {rnd} {k}: {ms[k][-1]:.3f} ms/step", flush=True)
+    mean = {k: sum(v) / len(v) for k, v in ms.items()}
+    ka, kb = list(paths)
+    for k in paths:
+        print(f"up-step {k}: {mean[k]:.3f} ms/step (spread {max(ms[k]) - min(ms[k]):.3f} over {repeats} rounds of {steps} steps)")
+    print(f"up-step with - without = {(mean[ka] - mean[kb]) * 1e3:.1f} us ({(mean[ka] / mean[kb] - 1) * 100:.2f} %)", flush=True)
+
+
+def up_train(frames, epochs, lambdas):
+    import torch
+    from boosting_nerv_amd import codec, yuvio
+    from boosting_nerv_amd import train_nerv_all as T
+    from boosting_nerv_amd.synth import SyntheticVideo
+    (h, w), (H, W) = UP_SHAPES[0]
+    c = yuvio.coefficients("bt709", "limited", 8)
+    runs = [("Fusion10_freq", [])] + [(f"Fusion10_freq + {lam:g} L_up", ["--yuv_loss", f"{lam:g}", "--yuv_upscale"]) for lam in lambdas]
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as tmp:
+        os.chdir(tmp)
+        try:
+            vid = SyntheticVideo(frames, H, W)
+            src = os.path.join(tmp, f"synth_{W}x{H}_8bit.yuv")
+            yuvio.write(src, (yuvio.to_yuv_reference(vid.frame(i).numpy(), c) for i in range(frames)), c.pix_fmt)
+            ref = yuvio.YuvFile(src)
+            print(f"up-train: {frames} frames of the synthetic clip as {os.path.basename(src)}, trained at {h}x{w}, {epochs} epochs ({frames * epochs} steps), "
+                  "one seed per row; scored at the master's size (Decoder(upscale=True).score)")
+            print("| loss | PSNR-Y | PSNR-U | PSNR-V | PSNR-YUV | train s |")
+            print("|---|---|---|---|---|---|")
+            for k, (tag, extra) in enumerate(runs):
+                out = f"u{k}"
+                t0 = time.time()
+                T.main(UP_FLAGS.split() + extra + ["--data_path", src, "--vid", "kyuvloss", "--outf", out, "-e", str(epochs), "--eval_freq", str(epochs),
+                                                   "--not_resume", "--bitstream", f"{out}.bnrq", "-p", "100000"])
+                torch.cuda.synchronize()
+                secs = time.time() - t0
+                m = codec.Decoder(f"{out}.bnrq", "cuda:0", pack=c.pix_fmt, upscale=True).score(ref)["mean"]
+                print(f"| {tag} | {m['psnr_y']:.3f} | {m['psnr_u']:.3f} | {m['psnr_v']:.3f} | {m['psnr_yuv']:.3f} | {secs:.0f} |", flush=True)
+        finally:
+            os.chdir(cwd)
 
 
 def msssim_kernel():
@@ -225,7 +372,8 @@ def train(frames, epochs, lambdas, ms_lambdas=()):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=["kernel", "step", "train", "msssim-kernel", "msssim-step", "msssim-train"], default=None)
+    ap.add_argument("--only", choices=["kernel", "step", "train", "msssim-kernel", "msssim-step", "msssim-train", "up-kernel", "up-step", "up-train"],
+                    default=None)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--frames", type=int, default=16)
@@ -245,6 +393,12 @@ def main():
         step(a.steps, a.repeats, ms=True)
     if a.only == "msssim-train":
         train(a.frames, a.epochs, a.lambdas, a.ms_lambdas)
+    if a.only == "up-kernel":
+        up_kernel()
+    if a.only == "up-step":
+        up_step(a.steps, a.repeats)
+    if a.only == "up-train":
+        up_train(a.frames, a.epochs, a.lambdas)
 
 
 if __name__ == "__main__":
